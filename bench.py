@@ -8,6 +8,10 @@ already resident in HBM when the timed region starts.  For N > 1 there is one pr
 data-path collective inside the frame) and the frame ends with ONE all_gather of the tile slabs over xGMI.
 `value` = rays traced by all ranks / max-over-ranks wall time.  Rank 0 prints one JSON line.
 
+A plain run sets up, warms up, times the steps, writes the last step's outputs if --dump-outputs DIR is given, and prints the line.
+Everything else the line can carry — the roofline of the dominant kernel, the GPU's clocks / power, the BVH and ReSTIR workloads under
+`extra`, the CPU baseline — comes with --full (--no-extra / --no-cpu-baseline drop parts of it again).
+
 Launching: either under a launcher (`python -m torch.distributed.run --nproc-per-node N bench.py --gpus N`, which sets
 RANK / LOCAL_RANK / WORLD_SIZE / MASTER_*), or plainly as `python bench.py --gpus N`: then this process — before it imports
 torch or touches the GPU — starts N children of itself with those variables set, relays rank 0's JSON line and exits with the
@@ -380,6 +384,21 @@ def time_extra(rt, dev_index, workload, steps=5):
 
 RESTIR_EXTRAS = {"restir_garage_1080p": "garage", "restir_atrium_1080p": "sponza"}     # the reference's shipping frame (3 DispatchRays: pass 1 + temporal + spatial reuse)
 
+DUMP_IMAGE_BYTES = 60 << 20     # --dump-outputs: an image above this is written as a fixed, seeded sample of its pixels (64 MB in all at most)
+
+
+def dump_outputs(d, image, rays):
+    """--dump-outputs DIR: what a caller of the timed path receives from its last step — the accumulation image (H, W, 4) float32, or a seeded
+    pixel sample of it (n, 4) when it is larger than DUMP_IMAGE_BYTES — and the rays traced by type (primary, extension, shadow) as float64"""
+    os.makedirs(d, exist_ok=True)
+    if image.nbytes > DUMP_IMAGE_BYTES:
+        px = image.reshape(-1, image.shape[-1])
+        idx = np.sort(np.random.default_rng(0).choice(px.shape[0], DUMP_IMAGE_BYTES // px[0].nbytes, replace=False))
+        np.save(os.path.join(d, "accum_sample.npy"), px[idx])
+    else:
+        np.save(os.path.join(d, "accum.npy"), image)
+    np.save(os.path.join(d, "rays.npy"), np.asarray(rays, dtype=np.float64))
+
 
 def time_restir(rt, dev_index, kind, frames=6):
     """The reference's own frame — rtx_render_restir: pass 1 + temporal + spatial reuse with its defines nee 4 / bounces 3 (Common_v6.hlsl:8-12) — at 1920x1080 on the
@@ -440,17 +459,23 @@ def main():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default="cornell_1080p_64spp_8b", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-kernel-timing", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the BVH workloads timed beside the headline (N = 1, default workload only)")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the BVH workloads timed beside the headline (N = 1, default workload only)")
     ap.add_argument("--paths-per-batch", type=int, default=0)
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"], help="gloo: host-staged gather, for testing the N>1 flow on one GPU")
     ap.add_argument("--device", type=int, default=-1, help="force this CUDA device on every rank (testing only)")
     ap.add_argument("--checksum", action="store_true", help="add a checksum of the final accumulation buffer to the JSON line")
     ap.add_argument("--opt", action="append", default=[], help="tuning: rtx option id=value (repeatable)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline, the GPU's clocks / power, the BVH and ReSTIR workloads (extra) and the CPU baseline; a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy (accum: the image, float32; rays: rays by type, float64)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:          # no launcher: be the launcher (before torch / the GPU are touched)
         sys.exit(spawn_ranks(args.gpus, sys.argv[1:]))
@@ -521,7 +546,7 @@ def main():
         frame(i)
     kms = np.zeros(rt.K_COUNT); kitems = np.zeros(rt.K_COUNT); klaunch = np.zeros(rt.K_COUNT)
     rays = np.zeros(3)
-    env = gpu_env(dev_index) if rank == 0 else None            # clocks / power / temperature / versions: once, BEFORE the timed region
+    env = gpu_env(dev_index) if rank == 0 and args.full else None      # clocks / power / temperature / versions: once, BEFORE the timed region
     # per-step times from events on the stream the frames run on (recording an event costs no synchronise; they are read after the closing barrier)
     ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
     barrier()
@@ -544,6 +569,12 @@ def main():
     ms_per_step = dt_max * 1e3 / max(args.steps, 1)
     value = float(rays_all.sum()) / dt_max / 1e6 if dt_max > 0 else 0.0
     step_ms = [a.elapsed_time(b) for a, b in ev]               # this rank's frames, GPU time on the frames' stream
+    if args.dump_outputs:                                      # the last step's frame (every rank holds the assembled one) and its rays, all ranks summed
+        last_rays = np.array([st.rays_primary, st.rays_extension, st.rays_shadow], dtype=np.float64)
+        if world > 1:
+            last_rays = sharding.sum_over_ranks(dist, last_rays, cdev)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, accum.cpu().numpy(), last_rays)
 
     if rank == 0:
         sha = None
@@ -552,7 +583,7 @@ def main():
             sha = hashlib.sha1(accum.cpu().numpy().tobytes()).hexdigest()
         # ---- roofline of the dominant kernel (HIP-event time per class, measured in the timed region, on the context's stream) ----
         roof = None
-        if not args.no_kernel_timing:
+        if args.full and not args.no_kernel_timing:
             local_px = float(W) * H * spp * args.steps / world
             roof = roofline_record(rt, args.workload if world == 1 else "", kms, kitems, klaunch, rays, local_px, args.steps)
             comp = (roof or {}).get("compute")
@@ -565,7 +596,7 @@ def main():
                                           "(bounce_fused: extension + shadow rays; the tiny-scene path has no tree: node steps / triangle tests per ray are reported for C3 / C5 under extra.*.work_per_ray)")
         # ---- the general BVH path beside the headline: driver-timed numbers for C3 / C5 (GPU only, ~2 s each + scene build) ----
         extra = None
-        if world == 1 and not args.no_extra and args.workload == "cornell_1080p_64spp_8b":
+        if args.full and world == 1 and not args.no_extra and args.workload == "cornell_1080p_64spp_8b":
             ctx.close(); ctx = None
             del accum
             torch.cuda.empty_cache()
@@ -582,7 +613,7 @@ def main():
                     extra[name] = {"error": str(e)[:200]}
         # ---- CPU baseline: the oracle (a port of the reference's shader math) on this host's cores ----
         cpu = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             orc = graft.load_oracle()
             o = orc.Oracle().load(scene, W / H)
             cores = os.cpu_count() or 1

@@ -28,7 +28,8 @@ int main() {
     }
     // a whole scene build (flatten, lights, build, collapse, any-hit probe) of a scene large enough for the parallel phase
     rtxh_scene* s = rtxh_scene_sponza_class(66000, 260);
-    if (!s || rtxh_scene_save(s, "/tmp/tsan_scene.rtxscn") != 0) { printf("scene build failed: %s\n", rtxh_last_error()); return 5; }
+    // saved into the working directory: the test runs this in a temporary directory of its own
+    if (!s || rtxh_scene_save(s, "tsan_scene.rtxscn") != 0) { printf("scene build failed: %s\n", rtxh_last_error()); return 5; }
     rtxh_scene_free(s);
     printf("done\n");
     return 0;

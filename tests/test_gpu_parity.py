@@ -1920,7 +1920,7 @@ def test_bench_runs_a_real_asset_and_reports_bounded_rooflines(golden_dir, tmp_p
                 yield from fractions(v, path + "/" + k)
         elif isinstance(o, (int, float)) and ("frac" in path.rsplit("/", 1)[-1]):
             yield path, o
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-extra"], capture_output=True, text=True, timeout=600, cwd=root)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-extra"], capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     b = json.loads(r.stdout.strip().splitlines()[-1])
     fr = list(fractions(b))
@@ -1956,7 +1956,7 @@ def test_bench_two_ranks_assemble_the_single_rank_frame():
     import json, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
-    common = ["--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-extra", "--checksum"]
+    common = ["--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline", "--no-extra", "--checksum"]
     one = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + common, capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert one.returncode == 0, one.stderr[-2000:]
     a = json.loads(one.stdout.strip().splitlines()[-1])
@@ -1982,6 +1982,30 @@ def test_bench_two_ranks_assemble_the_single_rank_frame():
     bad = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1"] + common, capture_output=True, text=True, timeout=120,
                          env=dict(env2, WORLD_SIZE="2", RANK="0", LOCAL_RANK="0"), cwd=root)
     assert bad.returncode != 0 and "does not match WORLD_SIZE" in bad.stderr
+
+
+def test_bench_plain_run_dumps_its_last_frame(tmp_path):
+    """A plain `bench.py` run carries the headline only (no roofline, extra or CPU baseline: those come with --full), and --dump-outputs DIR writes what its last
+    timed step computed: the image as float32 (the bytes --checksum hashes) and the rays by type as float64.  Two runs with the same arguments write the same arrays."""
+    import hashlib, json, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lines, dumps = [], []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "cornell_1080p_1spp_4b", "--steps", "1", "--warmup", "1", "--checksum",
+                            "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, cwd=root)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines.append(json.loads(r.stdout.strip().splitlines()[-1]))
+        dumps.append((np.load(d / "accum.npy"), np.load(d / "rays.npy")))
+    a, (img, rays) = lines[0], dumps[0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert a[k] is not None, k
+    assert a["steps"] == 1 and a["ms_per_step"] > 0 and a["value"] > 0
+    assert a["roofline"] is None and a["cpu_baseline"] is None and "extra" not in a
+    assert img.dtype == np.float32 and img.shape == (1080, 1920, 4) and rays.dtype == np.float64
+    assert hashlib.sha1(img.tobytes()).hexdigest() == a["accum_sha1"]
+    assert list(rays) == [a["config"]["rays_per_frame"][k] for k in ("primary", "extension", "shadow")]
+    assert np.array_equal(bits(img), bits(dumps[1][0])) and np.array_equal(rays, dumps[1][1]) and lines[1]["accum_sha1"] == a["accum_sha1"]
 
 
 def test_native_multi_gpu_frame_of_the_cli(tmp_path):

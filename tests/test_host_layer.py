@@ -728,3 +728,34 @@ def test_bench_asset_policy_loads_real_models_when_present(rt, golden_dir, tmp_p
     assert np.isfinite(v).all() and np.isfinite(p).all()
     if not os.path.isfile(os.path.join(root, "assets", "bistro.obj")):
         assert bench.asset_path("bistro") is None                                # nothing there: bench falls back to the generator (not built here: 3.8 M triangles)
+
+
+def test_bench_dump_outputs_samples_an_image_above_its_limit(tmp_path):
+    """bench.py --dump-outputs: an image up to DUMP_IMAGE_BYTES is written whole as accum.npy; a larger one (a 3840 x 2160 frame) as a fixed, seeded pixel sample,
+    accum_sample.npy, the same pixels on every run, taken from the image unchanged; with rays.npy the whole dump stays within 64 MB"""
+    import importlib, sys
+    sys.path.insert(0, ROOT)
+    bench = importlib.import_module("bench")
+    rays = [8294400, 1.5e9, 1.2e9]
+    small = np.random.default_rng(1).random((54, 96, 4), dtype=np.float32)
+    bench.dump_outputs(str(tmp_path / "small"), small, rays)
+    assert sorted(os.listdir(tmp_path / "small")) == ["accum.npy", "rays.npy"]
+    assert np.array_equal(bits(np.load(tmp_path / "small" / "accum.npy")), bits(small))
+    pix = np.arange(2160 * 3840)
+    big = np.stack([pix // 4096, pix % 4096, pix % 7, pix % 11], axis=-1).astype(np.float32).reshape(2160, 3840, 4)   # channels 0 / 1 name the pixel exactly
+    assert big.nbytes > bench.DUMP_IMAGE_BYTES
+    dumps = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        bench.dump_outputs(str(d), big, rays)
+        assert sorted(os.listdir(d)) == ["accum_sample.npy", "rays.npy"]
+        assert sum(os.path.getsize(d / f) for f in os.listdir(d)) <= 64 << 20
+        dumps.append(np.load(d / "accum_sample.npy"))
+    s = dumps[0]
+    assert s.dtype == np.float32 and s.ndim == 2 and s.shape[1] == 4 and s.nbytes == bench.DUMP_IMAGE_BYTES
+    assert np.array_equal(bits(s), bits(dumps[1]))                                         # seeded: the same sample every run
+    idx = s[:, 0].astype(np.int64) * 4096 + s[:, 1].astype(np.int64)                      # pixel index of each row
+    assert np.array_equal(s, big.reshape(-1, 4)[idx]) and (np.diff(idx) > 0).all()         # pixels of the image, unchanged, distinct, in image order
+    assert idx[-1] - idx[0] > 0.9 * 2160 * 3840                                           # spread over the whole frame
+    r = np.load(tmp_path / "a" / "rays.npy")
+    assert r.dtype == np.float64 and list(r) == rays

@@ -37,7 +37,7 @@ for wl, name in (("cornell", "c2"), ("sponza", "c3"), ("bistro", "c5")):
         tab, tot = kernel_table(kt, per=3, what="frame")            # bench.py --steps 2 --warmup 1: three frames are in the trace
         line = [l for l in open(os.path.join(kt, "bench.log")) if l.startswith("{")]
         with open(os.path.join(P, f"{tag}_{name}.md"), "w") as f:
-            f.write(f"# rocprofv3 --kernel-trace --stats of `python3 bench.py --workload <{wl}> --steps 2 --warmup 1 --no-cpu-baseline --no-extra` ({tag})\n\n"
+            f.write(f"# rocprofv3 --kernel-trace --stats of `python3 bench.py --workload <{wl}> --steps 2 --warmup 1 --full --no-cpu-baseline --no-extra` ({tag})\n\n"
                     f"Three frames are in the trace (one warm-up + two timed), all three with per-kernel events, i.e. the launches one after the other (bench.py warms up in the timed frames' mode since round 4); "
                     f"per frame = totals / 3.  Sum of kernel time per frame: {tot:.2f} ms.  Registers / occupancy: profiles/{tag}_kernel_resources.md.\n\n" + tab + "\n")
             if line:

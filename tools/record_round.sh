@@ -10,7 +10,7 @@ bash tools/roofline_run.sh gpurun_out/${tag}_roof_bistro bistro_1080p_16spp_8b "
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 for wl in cornell_1080p_64spp_8b sponza_1080p_16spp_8b bistro_1080p_16spp_8b; do
   d=gpurun_out/${tag}_kt_${wl%%_*}; mkdir -p $d
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $d -o p --output-format csv -- python3 bench.py --workload $wl --steps 2 --warmup 1 --no-cpu-baseline --no-extra > $d/bench.log 2>&1; echo "kernel trace $wl rc=$?"
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $d -o p --output-format csv -- python3 bench.py --workload $wl --steps 2 --warmup 1 --full --no-cpu-baseline --no-extra > $d/bench.log 2>&1; echo "kernel trace $wl rc=$?"
 done
 for sc in garage sponza bistro; do
   d=gpurun_out/${tag}_kt_restir_$sc; mkdir -p $d
