@@ -22,6 +22,7 @@
 #include <rocprim/rocprim.hpp>
 #include <chrono>
 #include "rtx_build.hpp"
+#include "rtx_devmem.hpp"
 #include "rtx_staging.hpp"
 #include "rtx_kernels.hpp"
 #include "rtx_wide.hpp"
@@ -30,12 +31,6 @@ namespace rtx {
 
 namespace {
 constexpr uint32_t kB = 256;
-struct GBuf {
-    void* p = nullptr; size_t bytes = 0;
-    hipError_t ensure(size_t n) { if (n <= bytes && p) return hipSuccess; if (p) { (void)hipFree(p); p = nullptr; bytes = 0; } if (!n) n = 16; hipError_t e = hipMalloc(&p, n); if (e == hipSuccess) bytes = n; return e; }
-    void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
-    template <class T> T* as() const { return (T*)p; }
-};
 struct Pool { F4* mn; F4* mx; int32_t* left; int32_t* right; WideDp* dp; uint32_t nleaf; };      // ids [0, nleaf): leaves in Morton order (left = -1, right = global triangle id)
 
 __device__ __forceinline__ uint32_t enc_f(float f) { const uint32_t b = f2u(f); return (b & 0x80000000u) ? ~b : (b | 0x80000000u); }      // unsigned order == float order
@@ -214,15 +209,13 @@ __global__ __launch_bounds__(kB) void k_lay_need(const Node8GPU* __restrict__ no
 }  // namespace
 
 struct GpuBvhBuilder::Impl {
-    GBuf bmn, bmx, bounds, keys[2], vals[2], sort_tmp, pmn, pmx, pleft, pright, pdp, cl[2], nn, flags, offs, scan_tmp, counts, cids, cboxes, crecs, src[2], codes, meta, packed, nodes, need;
-    uint32_t* h_counts = nullptr;         // pinned: the two counters a PLOC round / a layout level reports
+    DevBuf bmn, bmx, bounds, keys[2], vals[2], sort_tmp, pmn, pmx, pleft, pright, pdp, cl[2], nn, flags, offs, scan_tmp, counts, cids, cboxes, crecs, src[2], codes, meta, packed, nodes, need;
+    PinnedBuf h_counts;                   // pinned: the two counters a PLOC round / a layout level reports
     Staging staging;                      // host arrays (cluster records down, the top of the tree up) pass through pinned chunks (rtx_staging.hpp)
-    std::vector<GBuf*> all() { return {&bmn, &bmx, &bounds, &keys[0], &keys[1], &vals[0], &vals[1], &sort_tmp, &pmn, &pmx, &pleft, &pright, &pdp, &cl[0], &cl[1], &nn, &flags, &offs, &scan_tmp,
-                                       &counts, &cids, &cboxes, &crecs, &src[0], &src[1], &codes, &meta, &packed, &nodes, &need}; }
 };
 GpuBvhBuilder::GpuBvhBuilder() : m(new Impl) {}
-GpuBvhBuilder::~GpuBvhBuilder() { release(); delete m; }
-void GpuBvhBuilder::release() { for (GBuf* b : m->all()) b->release(); if (m->h_counts) { (void)hipHostFree(m->h_counts); m->h_counts = nullptr; } m->staging.release(); }
+GpuBvhBuilder::~GpuBvhBuilder() = default;
+void GpuBvhBuilder::release() { m.reset(new Impl); }
 const Node8GPU* GpuBvhBuilder::nodes() const { return m->nodes.as<Node8GPU>(); }
 
 #define GBCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return std::string("gpu build: ") + #call + ": " + hipGetErrorString(e_); } while (0)
@@ -243,7 +236,8 @@ std::string GpuBvhBuilder::build(hipStream_t st, const F4* d_objtris, const TriS
     for (int k = 0; k < 2; k++) { GBCHK(B.keys[k].ensure((size_t)n * 8)); GBCHK(B.vals[k].ensure((size_t)n * 4)); GBCHK(B.cl[k].ensure((size_t)n * 4)); GBCHK(B.src[k].ensure((size_t)n * 4)); }
     GBCHK(B.pmn.ensure((size_t)cap * 16)); GBCHK(B.pmx.ensure((size_t)cap * 16)); GBCHK(B.pleft.ensure((size_t)cap * 4)); GBCHK(B.pright.ensure((size_t)cap * 4)); GBCHK(B.pdp.ensure((size_t)cap * sizeof(WideDp)));
     GBCHK(B.nn.ensure((size_t)n * 4)); GBCHK(B.flags.ensure((size_t)n * 8)); GBCHK(B.offs.ensure((size_t)n * 8)); GBCHK(B.counts.ensure(16));
-    if (!B.h_counts) GBCHK(hipHostMalloc((void**)&B.h_counts, 16, hipHostMallocDefault));
+    GBCHK(B.h_counts.ensure(16));
+    uint32_t* h_counts = B.h_counts.as<uint32_t>();
     // ---- boxes, keys, sort ----
     const uint32_t init[8] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u, 0x3f800000u /* scale starts at 1.0 */, 0u};
     GBCHK(B.staging.to_device(st, B.bounds.p, init, 32));
@@ -283,8 +277,8 @@ std::string GpuBvhBuilder::build(hipStream_t st, const F4* d_objtris, const TriS
         hipLaunchKernelGGL(k_ploc_merge, dim3(gb), dim3(kB), 0, st, cin, B.nn.as<int32_t>(), B.flags.as<unsigned long long>(), B.offs.as<unsigned long long>(), (int)mcl, next_id, P, pad, opt.tri_cost,
                            cout, B.counts.as<uint32_t>());
         GBCHK(hipGetLastError());
-        GBCHK(B.staging.to_host(st, B.h_counts, B.counts.p, 8)); GBCHK(hipStreamSynchronize(st));
-        const uint32_t left = B.h_counts[0], merges = B.h_counts[1];
+        GBCHK(B.staging.to_host(st, h_counts, B.counts.p, 8)); GBCHK(hipStreamSynchronize(st));
+        const uint32_t left = h_counts[0], merges = h_counts[1];
         if (merges == 0 || left + merges != mcl) return "gpu build: a PLOC round made no progress";
         mcl = left; next_id += merges; cur ^= 1; R.ploc_iterations++;
         if (R.ploc_iterations > 4096) return "gpu build: PLOC does not converge";
@@ -293,7 +287,7 @@ std::string GpuBvhBuilder::build(hipStream_t st, const F4* d_objtris, const TriS
     R.clusters_top = mcl;
     // ---- the top of the tree on the host ----
     int32_t root;
-    if (mcl == 1) { GBCHK(B.staging.to_host(st, B.h_counts, B.cl[cur].p, 4)); GBCHK(hipStreamSynchronize(st)); root = (int32_t)B.h_counts[0]; }
+    if (mcl == 1) { GBCHK(B.staging.to_host(st, h_counts, B.cl[cur].p, 4)); GBCHK(hipStreamSynchronize(st)); root = (int32_t)h_counts[0]; }
     else {
         GBCHK(B.cids.ensure((size_t)mcl * 4)); GBCHK(B.cboxes.ensure((size_t)mcl * 24)); GBCHK(B.crecs.ensure((size_t)mcl * sizeof(WideDp)));
         hipLaunchKernelGGL(k_gb_clusters, dim3((mcl + kB - 1) / kB), dim3(kB), 0, st, B.cl[cur].as<int32_t>(), mcl, P, B.cids.as<int32_t>(), B.cboxes.as<float>(), B.crecs.as<WideDp>());
@@ -340,9 +334,9 @@ std::string GpuBvhBuilder::build(hipStream_t st, const F4* d_objtris, const TriS
         hipLaunchKernelGGL(k_lay_emit, dim3(gb), dim3(kB), 0, st, B.codes.as<int32_t>(), B.meta.as<uint2>(), B.packed.as<unsigned long long>(), B.offs.as<unsigned long long>(), level_cnt, node_base, tri_total, P,
                            B.nodes.as<Node8GPU>(), B.src[sc ^ 1].as<int32_t>(), d_tris_out, B.counts.as<uint32_t>());
         GBCHK(hipGetLastError());
-        GBCHK(B.staging.to_host(st, B.h_counts, B.counts.p, 8)); GBCHK(hipStreamSynchronize(st));
+        GBCHK(B.staging.to_host(st, h_counts, B.counts.p, 8)); GBCHK(hipStreamSynchronize(st));
         node_base += level_cnt; R.level_start8.push_back(node_base);
-        tri_total += B.h_counts[1]; level_cnt = B.h_counts[0]; sc ^= 1;
+        tri_total += h_counts[1]; level_cnt = h_counts[0]; sc ^= 1;
         if (tri_total > n || R.level_start8.size() > 256) return "gpu build: layout out of bounds";
     }
     if (tri_total != n) return "gpu build: the layout lost triangles (" + std::to_string(tri_total) + " of " + std::to_string(n) + ")";
@@ -352,8 +346,8 @@ std::string GpuBvhBuilder::build(hipStream_t st, const F4* d_objtris, const TriS
         if (count) hipLaunchKernelGGL(k_lay_need, dim3((count + kB - 1) / kB), dim3(kB), 0, st, B.nodes.as<Node8GPU>(), first, count, B.need.as<uint32_t>());
     }
     GBCHK(hipGetLastError());
-    GBCHK(B.staging.to_host(st, B.h_counts, B.need.p, 4)); GBCHK(hipStreamSynchronize(st));
-    R.stack8 = B.h_counts[0];
+    GBCHK(B.staging.to_host(st, h_counts, B.need.p, 4)); GBCHK(hipStreamSynchronize(st));
+    R.stack8 = h_counts[0];
     R.ms_layout = ms_since(t0);
     return "";
 }

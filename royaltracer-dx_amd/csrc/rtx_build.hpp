@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <memory>
 #include <string>
 #include <vector>
 #include "rtx_types.hpp"
@@ -31,7 +32,7 @@ public:
     const Node8GPU* nodes() const;                 // device: R.nnodes8 records of the last build (topology only), valid until the next build
     void release();                                // frees the scratch memory (~130 B per triangle)
 private:
-    struct Impl; Impl* m;
+    struct Impl; std::unique_ptr<Impl> m;
 };
 
 // ---- the flatten of a geometry-changing commit ON THE DEVICE (RTX_OPT_GPU_BUILD): object-space triangles and shade records (Hit_v6.hlsl:12-61) of every instanced triangle from

@@ -1,0 +1,187 @@
+// rtx_ctx.hpp — PRIVATE header of the C-ABI's translation units: the context (struct rtx_ctx), the macros every entry point uses and the helpers they share.
+//   rtx_api.hip          create / destroy, options, stream, scene inputs, camera, accumulation, reads, statistics, tile pack / unpack, the shard tiling
+//   rtx_commit.hip       rtx_commit_scene (host or GPU build, GPU refit), the scene cache, finalise_scene
+//   rtx_render.hip       rtx_render (the wavefront path tracer) and finish_render
+//   rtx_restir_api.hip   the ReSTIR frames, their work lists and lanes, the history / halo exchange between shards
+//   rtx_debug.hip        the rtx_debug_* entry points
+// Ownership: every resource of a context is a member of an owning type (rtx_devmem.hpp, rtx_staging.hpp), so `delete c` releases it all.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <memory>
+#include <string>
+#include <vector>
+#include "../../include/rtx.h"
+#include "rtx_kernels.hpp"
+#include "rtx_scene_host.hpp"
+#include "rtx_build.hpp"
+#include "rtx_devmem.hpp"
+#include "rtx_staging.hpp"
+
+using namespace rtx;
+
+// (hidden: the helpers shared by the runtime's translation units are not part of librtx_hip.so's exports)
+#pragma GCC visibility push(hidden)
+
+struct TimedLaunch { int cls; hipEvent_t a, b; };
+
+struct rtx_ctx {
+    StreamLease streams;            // declared FIRST, so destroyed last: memory and events are freed before the streams go back to the pool.  [0] the context's own stream, [1] aux, [2 .. 4] the lanes
+    // ---- the context itself (rtx_api.hip) ----
+    int device = 0;
+    hipStream_t stream = nullptr; bool own_stream = false;
+    int num_cus = 256;
+    std::string err;
+    Staging staging;                // the two pinned chunks every copy from / to caller memory passes through (rtx_staging.hpp)
+    Events ev;                      // frame begin / end and the pool of kernel timing and stream joins
+    std::vector<TimedLaunch> timed; // the timed launches of the last frame (RTX_OPT_KERNEL_TIMING)
+    rtx_stats stats{};
+
+    // ---- options: every value rtx_set_option writes (rtx_api.hip) ----
+    struct Options {
+        bool timing = false;                        // RTX_OPT_KERNEL_TIMING
+        bool async = false;                         // RTX_OPT_ASYNC
+        int octant_sort = 0;                        // RTX_OPT_OCTANT_SORT (2 = tooling: all keys zero, i.e. the machinery's overhead without a re-ordering)
+        int node_stride = 0;                        // RTX_OPT_NODE_STRIDE
+        int restir_keys = 1;                        // RTX_OPT_RESTIR_KEYS
+        int sample_interleave = 1;                  // RTX_OPT_SAMPLE_INTERLEAVE
+        bool trace_counters = false;                // RTX_OPT_TRACE_COUNTERS
+        int any_order_opt = -1;                     // RTX_OPT_ANYHIT_ORDER: -1 = what the commit-time probe chose (BuiltScene::any_order)
+        uint64_t paths_per_batch = 128u << 20;      // RTX_OPT_PATHS_PER_BATCH
+        uint32_t sort_materials = 0;                // RTX_OPT_SORT_MATERIALS
+        int lds_nodes_opt = -1;                     // RTX_OPT_LDS_NODES
+        int partial_refit = 1;                      // RTX_OPT_PARTIAL_REFIT: partial GPU refit (node_aabb / d_scale hold the last full refit's state)
+        int lds_closest_opt = -1;                   // RTX_OPT_LDS_NODES_CLOSEST
+        bool small_scene = true;                    // RTX_OPT_SMALL_SCENE
+        bool fused = true;                          // RTX_OPT_FUSED_BOUNCE
+        bool bounce_ring = true;                    // RTX_OPT_BOUNCE_VARIANT
+        int stack_private = -1;                     // RTX_OPT_STACK_PRIVATE
+        bool lpt_order = true;                      // RTX_OPT_LPT_ORDER: fused kernels take their sub-queues longest first
+        bool fused_bvh = false;                     // RTX_OPT_FUSED_BVH: general path = one k_bounce_bvh launch per batch (trace -> shade -> shadow per sub-queue and bounce); measured SLOWER, default off
+        bool work_stealing = false;                 // RTX_OPT_WORK_STEALING: trace kernels of general scenes continue with other sub-queues instead of draining (refill_steal); measured SLOWER, default off
+        bool compact_state = true;                  // RTX_OPT_COMPACT_STATE: separate-kernel path keeps ray / throughput / hit records by queue position, ping-pong (DevPaths::out_*)
+        bool overlap_shadow = true;                 // RTX_OPT_OVERLAP_SHADOW: k_trace_shadow of bounce b on a second stream, beside k_trace_closest of bounce b + 1 (not while kernels are timed)
+        uint32_t blocks_per_cu = 0;                 // RTX_OPT_BLOCKS_PER_CU (0 = auto)
+        bool taper = true; uint32_t taper_levels = 4;   // RTX_OPT_TAPER
+        uint32_t merge_rays = 1024;                 // RTX_OPT_MERGE_RAYS
+        bool gpu_refit = true;                      // RTX_OPT_GPU_REFIT
+        int gpu_build = 0;                          // RTX_OPT_GPU_BUILD
+        uint32_t stack_cap = 11;                    // RTX_OPT_STACK_CAP: traversal-stack entries kept in LDS (0 = all of them)
+        int shade_dense = 0;                        // RTX_OPT_SHADE_DENSE
+        uint32_t occluder_cache = 0;                // RTX_OPT_OCCLUDER_CACHE
+        bool restir_wave = true;                    // RTX_OPT_RESTIR_WAVEFRONT
+        uint32_t restir_lane_min = 1u << 16;        // RTX_OPT_RESTIR_LANE_MIN: pixel lists shorter than this run as one chain
+        uint32_t restir_lanes = 2;                  // RTX_OPT_RESTIR_LANES: the work list of a ReSTIR frame as 1 .. 4 independent parts on as many streams (the tails of one part's many short launches fill with the others' work)
+        uint32_t restir_chunks = 4;                 // RTX_OPT_RESTIR_CHUNKS: 256-item chunks per sub-queue (= workgroup) of the ReSTIR stages
+        uint32_t trace_sched = 6;                   // RTX_OPT_TRACE_SCHED
+        uint32_t refill_min = 12;                   // RTX_OPT_REFILL_MIN
+    } opt;                                          // (RTX_OPT_BVH_REINSERT / RTX_OPT_BVH_SPLIT write host.bvh)
+    DevBuf d_trace_cnt;                             // RTX_OPT_TRACE_COUNTERS: the counters (allocated when the option is switched on)
+
+    // ---- scene inputs, camera, accumulation (rtx_api.hip) ----
+    SceneHost host;
+    bool committed = false;                         // cleared by every input or layout option that changes the scene; set by finalise_scene
+    float view[16], proj[16], prev_view[16], prev_proj[16]; bool camera_set = false; DevBuf d_cam;
+    DevBuf d_accum; void* ext_accum = nullptr; size_t ext_accum_bytes = 0; uint32_t acc_w = 0, acc_h = 0;
+    DevBuf d_srgb;                                  // rtx_read_srgb8 / rtx_read_layer
+    F4* accum_ptr() { return (F4*)(ext_accum ? ext_accum : d_accum.p); }
+
+    // ---- the resident scene (rtx_commit.hip) ----
+    DevScene dsc{};                                 // what the kernels read of it: finalise_scene, plus the option values of options_to_scene (rtx_api.hip)
+    struct Scene {
+        BuiltScene built;
+        bool committed_once = false;
+        DevBuf d_nodes, d_tris, d_small, d_small_tris, d_small_poly, d_shade, d_mats, d_insts, d_lights, d_cdf;
+        std::vector<float> h_cdf; std::vector<uint32_t> h_one;     // host sources of small asynchronous uploads
+        // the wide tree as the DEVICE holds it (the host mirror B.nodes8 / B.tris8 is empty after a GPU build): counts, the root record (octant-sort grid), who built it
+        uint32_t n_nodes8 = 0, n_tris8 = 0; Node8GPU root8{}; bool dev_built = false; std::unique_ptr<GpuBvhBuilder> builder; GpuBuildResult build_info;
+        // RTX_OPT_GPU_BUILD: the meshes as they were handed over, resident on the device (append-only like the host's list: a commit uploads only what was added since the last one),
+        // and the per-instance ranges k_flatten reads (csrc/rtx_build.hip)
+        DevBuf d_pool_verts, d_pool_idx, d_pool_matids, d_flat_insts; size_t pool_verts = 0, pool_idx = 0, pool_matids = 0, pool_meshes = 0; std::vector<uint32_t> pool_vert_base, pool_idx_base; std::vector<FlatInst> h_flat;
+        DevBuf d_inst_moved, d_tri_dirty, d_node_dirty; bool node_aabb_valid = false;      // partial GPU refit: node_aabb / d_scale hold the last full refit's state
+        DevBuf d_objtris, d_node_aabb, d_scale;          // GPU refit: object-space vertices (uploaded on first use), per-node float boxes, max |coordinate|
+        bool device_scene_valid = false, objtris_uploaded = false;
+        DevBuf d_nodes_wide; bool wide_nodes = false;    // the copy with one node per 128-B line (RTX_OPT_NODE_STRIDE)
+        uint32_t lds_nodes_closest = 0;                  // staged nodes of the closest-hit launches (pick_lds_closest)
+        DevBuf d_stack_ovf;                              // the traversal stack's overflow columns of deeper trees (RTX_OPT_STACK_CAP)
+    } scene;
+
+    // ---- the path tracer's frame (rtx_render.hip) ----
+    struct PathFrame {
+        DevBuf d_ray_o, d_ray_d, d_thr, d_rad, d_hit, d_sh_o, d_sh_d, d_sh_c, d_queue[2], d_counters;
+        DevBuf d_alt_o, d_alt_d, d_alt_thr;              // the second path-state set of the compact state
+        DevBuf d_hitmask, d_order, d_pmask;
+        DevBuf d_oct[2], d_perm;                         // RTX_OPT_OCTANT_SORT
+        DevBuf d_hitq;                                   // RTX_OPT_FUSED_BVH
+        DevBuf d_heads;                                  // RTX_OPT_WORK_STEALING: per trace launch of a batch, G fetch cursors + the retired count
+        PinnedBuf h_counters;                            // the per-batch counters of a frame, read back in one copy each
+        // RTX_OPT_MERGE_RAYS: thin launches of the traversal kernels take several sub-queues per workgroup (MergedQ).  The host cannot see a launch's ray count (it is on the
+        // device), so it predicts it from the counters of the previous rtx_render of this context: per path entering the batch, how many were still alive at bounce b and how many
+        // shadow rays slot j of bounce b cast.  A wrong prediction costs time only.
+        uint64_t pred_paths = 0; std::vector<uint64_t> pred_q, pred_s; uint32_t pred_nee1 = 0;
+        hipStream_t aux = nullptr;                       // RTX_OPT_OVERLAP_SHADOW: the shadow stream (streams.set.s[1], taken on first use)
+        // RTX_OPT_ASYNC: what finish_render needs of the frame that rtx_render enqueued
+        struct Pending { bool active = false; size_t ncnt = 0; uint32_t nbatches = 0, G = 0, mb = 0, nee = 0, nee1 = 1; bool fused = false, fused_bvh = false; } pending;
+    } pt;
+
+    // ---- ReSTIR (rtx_restir_api.hip) ----
+    struct Restir {
+        DevBuf d_res_di, d_res_gi, d_sdata, d_last_di, d_last_gi, d_last_sd, d_p1cnt, d_p1scratch; size_t p1_slots = 0, last_slots = 0;
+        DevBuf d_rs_key_a, d_rs_key_b;                   // RTX_OPT_RESTIR_KEYS
+        // work lists (x | y << 16 per pixel, 8 x 8 pixel blocks in MORTON order so that consecutive chunks are compact screen regions): the shard's own pixels
+        // (pass 3) and — on shards — its tiles dilated by the 20-px radius of the spatial pass (passes 1 and 2); key = (width, height, tile, rank, count, deal)
+        DevBuf d_halo, d_own; uint32_t halo_count = 0, own_count = 0; uint32_t halo_key[6] = {0, 0, 0, 0, 0, 0};
+        // where this context holds last frame's history (pixel rectangle, exclusive upper bounds): the whole image after a reset / an unsharded frame / rtx_restir_unpack_state,
+        // the own rectangle after a sharded frame, + halo_px after rtx_restir_unpack_halo; hist_all = the whole image whatever its size
+        uint32_t hist[4] = {0, 0, 0, 0}; bool hist_all = true;
+        // wavefront ReSTIR (rtx_restir_wave.hpp): path state by queue position (two sets), hit records, per-item records, the any-hit ray queue, queue lengths
+        struct RsArea { DevBuf state, hit, cls, fin, cold, occ, cand, sho, shd, pay, cnt; } rs_area[4];      // one per pipeline lane (RTX_OPT_RESTIR_LANES)
+        hipStream_t lane_stream[3] = {nullptr, nullptr, nullptr};      // lanes 1 .. 3 (lane 0 runs on the context's stream): streams.set.s[2 ..], taken on first use
+    } rs;
+};
+
+// message of the calls that have no context to hold one (rtx_create failing, rtx_shard_slab_bytes, rtx_restir_state_slab_bytes, rtx_restir_halo_plan): PER THREAD, so the N threads
+// of the native multi-GPU frame (host/MultiGpu.cpp) that ask for their slab sizes at once never write the same string; rtx_last_error(NULL) reads the caller's own
+extern thread_local std::string g_create_err;
+
+#define HIPCHK(c, call)                                                                          \
+    do { hipError_t e_ = (call);                                                                 \
+         if (e_ != hipSuccess) { (c)->err = std::string(#call) + ": " + hipGetErrorString(e_);  \
+                                 return e_ == hipErrorOutOfMemory ? RTX_ERR_OOM : RTX_ERR_HIP; } } while (0)
+// RTX_OPT_ASYNC: an rtx_render that only ENQUEUED its frame leaves statistics to be collected (finish_render: stream sync + counter read-back).  Every entry point joins
+// first (BIND) — except the calls a frame's epilogue is made of, which must stay stream-ordered behind the render without a host join (BIND_NOWAIT: pack / unpack)
+int finish_render(rtx_ctx* c);
+#define BIND_NOWAIT(c) do { if (!(c)) return RTX_ERR_INVALID; HIPCHK(c, hipSetDevice((c)->device)); } while (0)
+#define BIND(c) do { BIND_NOWAIT(c); if ((c)->pt.pending.active) { const int r_ = finish_render(c); if (r_ != RTX_OK) return r_; } } while (0)
+
+// EVERY copy between host arrays and the device goes through these two (rtx_staging.hpp: pinned chunks of the context).  to_device: the source is consumed when it returns
+// and the copy is ordered on the context's stream — no lifetime rule, no synchronise.  to_host: complete when it returns (it waits for the stream up to the copy).
+#define TO_DEVICE(c, dst, src, bytes) HIPCHK(c, (c)->staging.to_device((c)->stream, (dst), (src), (bytes)))
+#define TO_HOST(c, dst, src, bytes) HIPCHK(c, (c)->staging.to_host((c)->stream, (dst), (src), (bytes)))
+template <class T> static int upload(rtx_ctx* c, DevBuf& b, const std::vector<T>& v) {
+    HIPCHK(c, b.ensure(v.size() * sizeof(T)));
+    TO_DEVICE(c, b.p, v.data(), v.size() * sizeof(T));
+    return RTX_OK;
+}
+
+// one launch of kernel class `cls`: counted, and timed between two events of the pool while RTX_OPT_KERNEL_TIMING is on
+struct Timed {
+    rtx_ctx* c; int cls; hipEvent_t a = nullptr, b = nullptr;
+    hipStream_t s;
+    Timed(rtx_ctx* c_, int cls_, hipStream_t s_ = nullptr) : c(c_), cls(cls_), s(s_ ? s_ : c_->stream) { c->stats.kernel_launches[cls]++; if (c->opt.timing) { a = c->ev.take(); b = c->ev.take(); if (a) (void)hipEventRecord(a, s); } }
+    ~Timed() { if (c->opt.timing && a && b) { (void)hipEventRecord(b, s); c->timed.push_back({cls, a, b}); } }
+};
+
+// rtx_api.hip
+void options_to_scene(rtx_ctx* c, bool committed);
+int ensure_accum(rtx_ctx* c, uint32_t w, uint32_t h, bool clear);
+const char* validate_tiling(const rtx_params* p, uint32_t& ts, uint32_t& cnt, uint64_t& npl, uint32_t* gx_out = nullptr, uint32_t* gy_out = nullptr);
+int make_frame(rtx_ctx* c, const rtx_params* p, DevFrame& f);
+void block_rect(uint32_t W, uint32_t H, uint32_t ts, uint32_t TX, uint32_t TY, uint32_t gx, uint32_t gy, uint32_t r, uint32_t out[4]);
+// rtx_commit.hip
+void pick_lds_closest(rtx_ctx* c);
+
+#pragma GCC visibility pop

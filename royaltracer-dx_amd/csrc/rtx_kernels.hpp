@@ -49,7 +49,7 @@ struct DevFrame {
     uint32_t nblocks, qcap, chunks_per_sample;   // chunks_per_sample = npl / 256
     uint32_t interleave;     // RTX_OPT_SAMPLE_INTERLEAVE (k_raygen): 0 = a chunk of 256 queue entries is 256 pixel slots of ONE sample; s > 0 = 256 >> s pixel slots x 2^s consecutive samples, a pixel's samples in neighbouring lanes
     uint32_t taper_levels;   // k_raygen: 0 = chunks dealt evenly (chunk c -> sub-queue c mod nblocks); L > 0 = tapered deal with L weight classes (taper_row_width below)
-    // ReSTIR on shards: the pixel rectangle [hist_x0, hist_x1) x [hist_y0, hist_y1) in which this context holds last frame's history (rtx_api.hip: rtx_ctx::hist); the temporal
+    // ReSTIR on shards: the pixel rectangle [hist_x0, hist_x1) x [hist_y0, hist_y1) in which this context holds last frame's history (rtx_ctx.hpp: rtx_ctx::rs.hist); the temporal
     // pass counts its reads outside it in *hist_stale (nullptr: not counted — unsharded frames hold the whole image)
     uint32_t hist_x0, hist_y0, hist_x1, hist_y1; unsigned long long* hist_stale;
 };

@@ -291,7 +291,7 @@ __device__ __forceinline__ void traverse(const DevScene& sc, const TraceLds& L, 
     }
 }
 
-// traversal that also counts node steps and triangle tests (rtx_debug_trace_stats: tree-quality measurements; ANY: the any-hit order probe of a GPU-built tree, rtx_api.hip)
+// traversal that also counts node steps and triangle tests (rtx_debug_trace_stats: tree-quality measurements; ANY: the any-hit order probe of a GPU-built tree, rtx_commit.hip)
 template <bool ANY = false>
 __device__ __forceinline__ void traverse_stats(const DevScene& sc, const TraceLds& L, f3 o, f3 d, float tmin, float tmax,
                                          float& bt, float& bu, float& bv, uint32_t& bprim) {

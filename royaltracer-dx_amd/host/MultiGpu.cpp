@@ -11,7 +11,7 @@
 #include <mutex>
 #include <utility>
 
-// The ranks' streams are borrowed from a process-wide list and handed back idle, never destroyed — as the library does with its own (csrc/rtx_api.hip: StreamPool;
+// The ranks' streams are borrowed from a process-wide list and handed back idle, never destroyed — as the library does with its own (csrc/rtx_devmem.hpp: StreamPool;
 // profiles/r05_determinism.md: a process that creates and destroys HIP streams by the thousand gets, rarely, a stray write into its heap).
 static std::mutex g_rank_stream_mu; static std::vector<std::pair<int, hipStream_t>> g_rank_streams;
 static hipStream_t rank_stream_acquire(int device) {

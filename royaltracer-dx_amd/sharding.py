@@ -112,7 +112,7 @@ HALO_RECORD_BYTES = 140          # Reservoir_DI 40 | Reservoir_GI 40 | SampleDat
 
 
 def halo_plan(width, height, tile_size, rank, world, halo):
-    """numpy-side mirror of rtx_restir_halo_plan (csrc/rtx_api.hip: halo_plan): [dict(rank, send=(x0, y0, x1, y1), recv=(...), send_offset, send_bytes, recv_offset,
+    """numpy-side mirror of rtx_restir_halo_plan (csrc/rtx_restir_api.hip: halo_plan): [dict(rank, send=(x0, y0, x1, y1), recv=(...), send_offset, send_bytes, recv_offset,
     recv_bytes)] in ascending rank order, total send bytes, total receive bytes.  send = my rectangle ∩ the peer's dilated by `halo`; recv = the peer's ∩ mine dilated."""
     L = layout(width, height, tile_size, world, True)
     if world < 2 or not L["gx"]:

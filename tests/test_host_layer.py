@@ -1,6 +1,7 @@
 """CPU suite, part 2: the host layer (scene loader / material / camera API mirroring the reference) and
 the C-ABI library itself (loads, exports every declared symbol, refuses to run without a GPU)."""
 import ctypes
+import glob
 import json
 import os
 import re
@@ -356,19 +357,34 @@ def test_library_exports_every_declared_symbol(rt):
             assert hasattr(rt.lib, n), f"{n} declared in include/{h} but not exported by librtx_hip.so"
 
 
-def test_product_library_keeps_the_process_allocator_and_never_destroys_streams():
+def test_product_library_keeps_the_process_allocator_never_destroys_streams_and_stages_host_copies():
     """Round 5 (profiles/r05_determinism.md): (1) the heap fence that hunted the stray write (csrc/rtx_heap_fence.cpp) is an EMPTY translation unit in the product — librtx_hip.so
     must not define operator new / delete; (2) the cure: the library borrows its HIP streams from a process-wide pool and never destroys one — no call to hipStreamDestroy is
-    left in the C-ABI sources, nor in host/MultiGpu.cpp (the native N-GPU frame keeps its ranks' streams in a list of its own)."""
+    left in any file of csrc/, nor in host/MultiGpu.cpp (the native N-GPU frame keeps its ranks' streams in a list of its own); (3) every copy between host arrays and the
+    device goes through rtx_staging.hpp — in all of csrc/ one direct device-to-host copy remains, the pinned counter block of a path-tracer frame (rtx_render.hip)."""
     pkg = os.path.join(ROOT, "royaltracer-dx_amd")
     nm = subprocess.run(["nm", "-DC", "--defined-only", os.path.join(pkg, "librtx_hip.so")], capture_output=True, text=True).stdout
     assert "operator new" not in nm and "operator delete" not in nm
-    for f in ("rtx_api.hip", "rtx_build.hip", "rtx_kernels.hip", "rtx_staging.hpp"):
-        src = re.sub(r"//[^\n]*", "", open(os.path.join(pkg, "csrc", f)).read())
-        assert "hipStreamDestroy(" not in src, f
-    assert "hipStreamDestroy(" not in re.sub(r"//[^\n]*", "", open(os.path.join(pkg, "host", "MultiGpu.cpp")).read())
-    api = open(os.path.join(pkg, "csrc", "rtx_api.hip")).read()
-    assert "hipMemcpyHostToDevice" not in api and api.count("hipMemcpyDeviceToHost") == 1        # host copies go through rtx_staging.hpp; the one left fills the PINNED counter block of a frame
+    csrc = sorted(glob.glob(os.path.join(pkg, "csrc", "*")))
+    assert len(csrc) >= 20
+    for f in csrc + [os.path.join(pkg, "host", "MultiGpu.cpp")]:
+        assert "hipStreamDestroy(" not in re.sub(r"//[^\n]*", "", open(f).read()), f
+    # host copies go through rtx_staging.hpp; the one left fills the PINNED counter block of a frame
+    rest = "".join(open(f).read() for f in csrc if os.path.basename(f) != "rtx_staging.hpp")
+    assert "hipMemcpyHostToDevice" not in rest and rest.count("hipMemcpyDeviceToHost") == 1
+    assert open(os.path.join(pkg, "csrc", "rtx_render.hip")).read().count("hipMemcpyDeviceToHost") == 1
+
+
+def test_device_memory_events_and_pinned_memory_are_owned_by_the_owning_types():
+    """csrc/rtx_devmem.hpp (and the staging chunks of rtx_staging.hpp) allocate, free and destroy every buffer and event of the library: a resource is a member of an
+    owning type and is released by its destructor, with no hand-kept list of buffers to forget one in."""
+    pkg = os.path.join(ROOT, "royaltracer-dx_amd")
+    others = [f for f in sorted(glob.glob(os.path.join(pkg, "csrc", "*"))) if os.path.basename(f) not in ("rtx_devmem.hpp", "rtx_staging.hpp")]
+    assert len(others) >= 20
+    for f in others:
+        src = re.sub(r"//[^\n]*", "", open(f).read())
+        for call in ("hipMalloc(", "hipFree(", "hipHostMalloc(", "hipHostFree(", "hipEventDestroy("):
+            assert call not in src, (f, call)
 
 
 def test_no_cpu_fallback_without_a_gpu(rt):
