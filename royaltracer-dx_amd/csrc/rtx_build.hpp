@@ -36,7 +36,7 @@ private:
 };
 
 // ---- the flatten of a geometry-changing commit ON THE DEVICE (RTX_OPT_GPU_BUILD): object-space triangles and shade records (Hit_v6.hlsl:12-61) of every instanced triangle from
-//      the meshes as they were handed over.  The host twin is SceneHost::build's flatten loop (csrc/rtx_scene_host.cpp) — same functions of rtx_math.hpp, same order. ----
+//      the meshes as they were handed over.  The host twin is the flatten step of SceneHost::build (csrc/rtx_scene_host.cpp: flatten_range) — same functions of rtx_math.hpp, same order. ----
 struct FlatInst { uint32_t tri_base, ntri, vert_base, idx_base, matid_base, pad_[3]; };       // one per instance, in instance order (tri_base ascending)
 void launch_flatten(hipStream_t st, const float* verts7, const uint32_t* idx, const uint32_t* matids, uint32_t nmatids, const FlatInst* insts, uint32_t ninst, uint32_t ntri,
                     F4* objtris_out, TriShade* shade_out);

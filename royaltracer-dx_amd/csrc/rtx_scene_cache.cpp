@@ -199,7 +199,7 @@ static bool load_scene_cache_impl(const char* path, SceneHost& H, BuiltScene& B,
     if (r.at != h.payload) { err = "scene cache: trailing bytes"; return false; }
     // consistency of what was read (indices stay inside their arrays: the kernels and the refit trust these)
     const size_t nt = Bn.shade.size(), nmat = Hn.mats128.size() / 32;
-    const size_t nrec_pad = ((size_t)sc.small_nrec + 1) & ~(size_t)1;      // records are stored in pairs (rtx_scene_host.cpp)
+    const size_t nrec_pad = ((size_t)sc.small_nrec + 1) & ~(size_t)1;      // records are stored in pairs (rtx_small_scene.cpp)
     const size_t nrefs = Bn.tris8.size();                                      // leaf entries: the triangle count, plus the references spatial splits added
     bool ok = nrefs >= nt && Bn.tri_slots8.size() == nrefs && Bn.mats.size() == nmat && Bn.insts.size() == Hn.insts.size() && Bn.lights80.size() == Bn.lights.size() * 20 &&
               Hn.mats128.size() % 32 == 0 && (Bn.nodes8.empty() || Bn.level_start8.size() >= 2) && sc.small_nocc <= sc.small_nrec && sc.small_nrec <= kSmallSceneMaxTris &&
@@ -269,17 +269,6 @@ bool load_scene_cache(const char* path, SceneHost& H, BuiltScene& B, std::string
     catch (const std::bad_alloc&) { err = "scene cache: out of memory while reading"; }
     catch (const std::exception& e) { err = std::string("scene cache: ") + e.what(); }
     return false;
-}
-
-// object-space triangles of the GPU refit, re-derived from the meshes (what build() fills; a loaded cache does not carry them)
-void SceneHost::fill_objtris(BuiltScene& B) const {
-    size_t nt = 0; for (const InstHost& in : insts) nt += meshes[in.mesh].idx.size() / 3;
-    B.objtris.resize(nt * 3);
-    for (const InstHost& in : insts) {
-        const MeshHost& m = meshes[in.mesh];
-        for (uint32_t t = 0; t < m.idx.size() / 3; t++)
-            for (int k = 0; k < 3; k++) { const float* p = &m.verts[(size_t)m.idx[t * 3 + k] * 7]; B.objtris[((size_t)in.tri_base + t) * 3 + k] = {p[0], p[1], p[2], 0.0f}; }
-    }
 }
 
 }  // namespace rtx

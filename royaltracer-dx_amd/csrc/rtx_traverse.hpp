@@ -337,13 +337,13 @@ __device__ __forceinline__ void traverse_stats(const DevScene& sc, const TraceLd
 // and collects a per-lane candidate bit mask.  Phase 2 runs the exact Moeller-Trumbore test on the few
 // candidates of each lane.  The result is the same minimum-over-all-triangles as the BVH path and the oracle's
 // brute force: phase 1 only removes triangles that the exact test would reject (tolerances: the edge-plane distance
-// delta and the t margin, built in rtx_scene_host.cpp).
+// delta and the t margin, built in rtx_small_scene.cpp).
 
 template <bool ANY>
 __device__ __forceinline__ void traverse_small(const DevScene& sc, const SmallRecPair* __restrict__ sp, const TraceLds& L, f3 o, f3 d, float tmin, float tmax,
                                                float& bt, float& bu, float& bv, uint32_t& bprim, uint32_t nrec, unsigned long long keep = ~0ull, Prof* pf = nullptr, int pf_sec = 0) {
     // keep (wave-uniform): bit r clear = no ray of this wave can touch record r (primary-ray packet culling); nrec = sc.nsmall, or sc.nsmall_occ for NEE shadow segments (both end points inside the scene's convex hull: the records
-    // after the first nsmall_occ are faces OF that hull and cannot lie between them, rtx_scene_host.cpp)
+    // after the first nsmall_occ are faces OF that hull and cannot lie between them, rtx_small_scene.cpp)
     bt = tmax; bu = 0.0f; bv = 0.0f; bprim = kMissPrim;
     uint32_t cand_lo = 0u, cand_hi = 0u;
     const uint32_t npairs = (nrec + 1u) >> 1;

@@ -7,7 +7,7 @@ namespace rtx {
 
 struct alignas(16) F4 { float x, y, z, w; };
 
-// BVH2 node with BOTH children's boxes stored in the parent: the HOST-side build / refit form (rtx_scene_host.cpp); the kernels
+// BVH2 node with BOTH children's boxes stored in the parent: the HOST-side build / refit form (rtx_bvh_build.cpp); the kernels
 // traverse the compressed 8-wide collapse below.
 //   a = (c0.min.xyz, c0.max.x)   b = (c0.max.yz, c1.min.xy)   c = (c1.min.z, c1.max.xyz)
 //   d = (child0 bits, child1 bits, -, -)
@@ -32,7 +32,7 @@ constexpr uint32_t kStackEntryBytes = 6;      // LDS traversal stack: bytes per 
 struct alignas(16) Node8GPU { float px, py, pz; uint32_t e_imask; uint32_t child_base, tri_base, trivalid, pad; uint32_t q[12]; };
 static_assert(sizeof(Node8GPU) == 80, "Node8GPU must be 80 bytes");
 
-// World-space triangle (device copy: in the wide tree's order, rtx_scene_host.cpp): v0 (w = global triangle id bits), e1 = v1 - v0, e2 = v2 - v0.
+// World-space triangle (device copy: in the wide tree's order, rtx_bvh_wide.cpp): v0 (w = global triangle id bits), e1 = v1 - v0, e2 = v2 - v0.
 struct alignas(16) TriGPU { F4 v0, e1, e2; };
 
 // Tiny scenes (<= 64 triangles, e.g. the Cornell Box): no BVH.  Triangles are merged, where possible, into planar
@@ -54,7 +54,7 @@ struct alignas(16) TriShade {
     float flat[3];
     float n0[3], n1[3], n2[3];
     float area;
-    float guard_tau;   // tiny scenes: a hit whose smallest barycentric is below this may lie within the guard margin of a hull plane (rtx_scene_host.cpp); 0 = never
+    float guard_tau;   // tiny scenes: a hit whose smallest barycentric is below this may lie within the guard margin of a hull plane (rtx_small_scene.cpp); 0 = never
 };
 static_assert(sizeof(TriShade) == 64, "TriShade must be 64 bytes");
 

@@ -1,7 +1,7 @@
 // rtx_wide.hpp — from a binary BVH to the slots of an 8-wide node: which binary subtrees become wide nodes or leaf slots (surface-area-heuristic dynamic program after Ylitie,
 // Karras, Laine, HPG 2017, section 3.1), the children of one wide node, and their assignment to octant slots.
 //
-// ONE source for two builders: the host collapse (csrc/rtx_scene_host.cpp: collapse_bvh8) and the GPU build (csrc/rtx_build.hip) include this file, so that both take the same
+// ONE source for two builders: the host collapse (csrc/rtx_bvh_wide.cpp: collapse_bvh8) and the GPU build (csrc/rtx_build.hip) include this file, so that both take the same
 // decisions from the same inputs — same operations in the same order, double arithmetic where the host always had it, no contraction (-ffp-contract=off on both sides).
 // A tree built on the GPU can therefore be compared with its host twin node for node (tests: test_gpu_build_equals_its_host_twin).
 #pragma once
@@ -106,7 +106,7 @@ RTX_HD void wide_assign_slots(const WBox* ch, int m, float bmn[3], float bmx[3],
     }
 }
 
-// ---- PLOC (Meister & Bittner 2018), the pieces host twin and device share (rtx_scene_host.cpp: ploc_clusters; rtx_build.hip: k_ploc_*) ----
+// ---- PLOC (Meister & Bittner 2018), the pieces host twin and device share (rtx_bvh_build.cpp: ploc_clusters; rtx_build.hip: k_ploc_*) ----
 RTX_HD uint64_t ploc_spread21(uint32_t v) {            // 21 bits -> every third bit of 63
     uint64_t x = v & 0x1fffffu;
     x = (x | x << 32) & 0x1f00000000ffffull; x = (x | x << 16) & 0x1f0000ff0000ffull; x = (x | x << 8) & 0x100f00f00f00f00full;

@@ -26,6 +26,25 @@ template <class F> static int guarded_rc(F&& f) {
     try { f(); return RTX_OK; } catch (const std::exception& e) { g_err = e.what(); return RTX_ERR_INVALID; }
 }
 
+// host-layer Scene -> the scene state behind the C-ABI (what UploadScene hands to a context call by call); false: H.err says why
+static bool to_scene_host(const Scene& s, rtx::SceneHost& H) {
+    if (!H.set_materials(s.materials.data(), (uint32_t)s.materials.size())) return false;
+    for (const SceneModel& m : s.models) { uint32_t id; if (!H.add_mesh(m.vertices.data(), (uint32_t)m.vertices.size(), m.indices.data(), (uint32_t)m.indices.size(), m.materialIDs.data(), &id)) return false; }
+    for (const SceneInstance& in : s.instances) { uint32_t id; if (!H.add_instance(in.model, in.transform.data(), &id)) return false; }
+    return true;
+}
+// the scene as rtx_commit_scene builds it on the host (tiny-scene records, any-hit order: for host-side inspection)
+static bool build_for_inspection(const rtxh_scene* sc, rtx::BuiltScene& B) {
+    rtx::SceneHost H;
+    return to_scene_host(sc->s, H) && H.build(B);
+}
+// the binary tree the CURRENT builder options give for these triangles (9 floats each, leaf boxes padded by pad_abs) and its wide form, as a commit derives them
+static bool build_trees(const std::vector<float>& w, float pad_abs, rtx::BuiltScene& B) {
+    rtx::build_bvh(w, pad_abs, B.nodes, B.leaf_order, B.max_depth);
+    rtx::leaf_triangles(w, B.leaf_order, B.tris);
+    return rtx::wide_from_binary(B);
+}
+
 extern "C" {
 
 rtxh_scene* rtxh_scene_cornell(void) { return guarded([] { return MakeCornellBox(); }); }
@@ -95,10 +114,7 @@ int rtxh_scene_upload(const rtxh_scene* s, rtx_ctx* c, float aspect) {
 int rtxh_scene_save(const rtxh_scene* s, const char* path) {
     rtx::SceneHost H; rtx::BuiltScene B;
     const Scene& sc = s->s;
-    bool ok = H.set_materials(sc.materials.data(), (uint32_t)sc.materials.size());
-    for (const SceneModel& m : sc.models) { uint32_t id; ok = ok && H.add_mesh(m.vertices.data(), (uint32_t)m.vertices.size(), m.indices.data(), (uint32_t)m.indices.size(), m.materialIDs.data(), &id); }
-    for (const SceneInstance& in : sc.instances) { uint32_t id; ok = ok && H.add_instance(in.model, in.transform.data(), &id); }
-    if (!ok || !H.build(B)) { g_err = H.err; return RTX_ERR_INVALID; }
+    if (!to_scene_host(sc, H) || !H.build(B)) { g_err = H.err; return RTX_ERR_INVALID; }
     const float cam[12] = {sc.eye.x, sc.eye.y, sc.eye.z, sc.center.x, sc.center.y, sc.center.z, sc.up.x, sc.up.y, sc.up.z, sc.fovY_deg, sc.zn, sc.zf};
     std::string err;
     rtx::CacheAux aux;                                                // MaterialExt + texture names ride along (an OBJ / MTL scene answers the accessors after a load, too)
@@ -199,15 +215,14 @@ static int bvh_validate(const std::vector<float>& w, const std::vector<rtx::Node
 // stack bound is what the deepest root-to-leaf path can push
 int rtxh_bvh8_check(const float* wt, uint32_t ntris, uint32_t* nodes8_out, uint32_t* stack_out) {
     std::vector<float> w(wt, wt + (size_t)ntris * 9);
-    std::vector<rtx::NodeGPU> nodes; std::vector<uint32_t> order; uint32_t depth = 0;
-    rtx::build_bvh(w, 0.0f, nodes, order, depth);
-    std::vector<rtx::Node8GPU> n8; std::vector<uint32_t> slots, levels; uint32_t stack = 0;
-    if (!rtx::collapse_bvh8(nodes, n8, slots, stack, &levels)) return 30;
+    rtx::BuiltScene B;
+    if (!build_trees(w, 0.0f, B)) return 30;
+    const std::vector<rtx::Node8GPU>& n8 = B.nodes8; const std::vector<uint32_t>& levels = B.level_start8;
     if (nodes8_out) *nodes8_out = (uint32_t)n8.size();
-    if (stack_out) *stack_out = stack;
+    if (stack_out) *stack_out = B.stack8;
     uint32_t seen = 0;
-    if (int r = rtx::validate_bvh8(w, n8, order, slots, &seen)) return r;
-    if (seen != stack) return 19;
+    if (int r = rtx::validate_bvh8(w, n8, B.leaf_order, B.tri_slots8, &seen)) return r;
+    if (seen != B.stack8) return 19;
     // the level table the GPU refit sweeps bottom-up: contiguous ranges, and every internal child lives exactly one level below
     if (levels.size() < 2 || levels.front() != 0 || levels.back() != n8.size()) return 31;
     for (size_t l = 0; l + 1 < levels.size(); l++) {
@@ -223,20 +238,13 @@ int rtxh_bvh8_check(const float* wt, uint32_t ntris, uint32_t* nodes8_out, uint3
     return 0;
 }
 
-// the device traversal replayed on the host (csrc/rtx_scene_host.cpp: replay_trace) over the wide tree the CURRENT builder options give for these triangles, leaf
+// the device traversal replayed on the host (csrc/rtx_bvh_replay.cpp: replay_trace) over the wide tree the CURRENT builder options give for these triangles, leaf
 // boxes padded as rtx_commit_scene pads them: out4 = (t, node steps, triangle tests, global id bits or 0xffffffff) per ray (o.xyz, tmin, d.xyz, tmax)
 int rtxh_bvh_replay(const float* wt, uint32_t ntris, const float* rays8, uint32_t nrays, int any, uint32_t any_order, float* out4, uint32_t* refs_out) {
     std::vector<float> w(wt, wt + (size_t)ntris * 9);
     float scale = 1.0f; for (float x : w) scale = std::max(scale, std::fabs(x));
-    rtx::BuiltScene B; uint32_t depth = 0;
-    rtx::build_bvh(w, 2e-6f * scale, B.nodes, B.leaf_order, depth);
-    if (!rtx::collapse_bvh8(B.nodes, B.nodes8, B.tri_slots8, B.stack8)) return 30;
-    B.tris8.resize(B.tri_slots8.size());
-    for (size_t i = 0; i < B.tri_slots8.size(); i++) {
-        const uint32_t g = B.leaf_order[B.tri_slots8[i]]; const float* t = &w[(size_t)g * 9];
-        const rtx::f3 e1 = rtx::mk3(t[3] - t[0], t[4] - t[1], t[5] - t[2]), e2 = rtx::mk3(t[6] - t[0], t[7] - t[1], t[8] - t[2]);
-        B.tris8[i].v0 = {t[0], t[1], t[2], rtx::u2f(g)}; B.tris8[i].e1 = {e1.x, e1.y, e1.z, rtx::tri_det_floor(e1, e2)}; B.tris8[i].e2 = {e2.x, e2.y, e2.z, 0.0f};
-    }
+    rtx::BuiltScene B;
+    if (!build_trees(w, 2e-6f * scale, B)) return 30;
     if (refs_out) *refs_out = (uint32_t)B.tris8.size();
     for (uint32_t i = 0; i < nrays; i++) {
         const float* r = rays8 + (size_t)i * 8;
@@ -251,19 +259,17 @@ int rtxh_bvh_option(const char* key, double value) { return rtx::bvh_build_optio
 // shape of the wide tree: hist[0..4] = leaf slots holding 0 (unused slot) / 1 / 2 / 3 / 4 triangles, hist[5] = internal child slots
 int rtxh_bvh8_stats(const float* wt, uint32_t ntris, uint32_t hist[6], uint32_t* nodes8_out) {
     std::vector<float> w(wt, wt + (size_t)ntris * 9);
-    std::vector<rtx::NodeGPU> nodes; std::vector<uint32_t> order; uint32_t depth = 0;
-    rtx::build_bvh(w, 0.0f, nodes, order, depth);
-    std::vector<rtx::Node8GPU> n8; std::vector<uint32_t> slots; uint32_t stack = 0;
-    if (!rtx::collapse_bvh8(nodes, n8, slots, stack)) return 30;
+    rtx::BuiltScene B;
+    if (!build_trees(w, 0.0f, B)) return 30;
     for (int i = 0; i < 6; i++) hist[i] = 0;
-    for (const rtx::Node8GPU& N : n8) {
+    for (const rtx::Node8GPU& N : B.nodes8) {
         const uint32_t imask = N.e_imask >> 24;
         for (int sl = 0; sl < 8; sl++) {
             if ((imask >> sl) & 1u) { hist[5]++; continue; }
             hist[__builtin_popcount((N.trivalid >> (4 * sl)) & 0xfu)]++;
         }
     }
-    if (nodes8_out) *nodes8_out = (uint32_t)n8.size();
+    if (nodes8_out) *nodes8_out = (uint32_t)B.nodes8.size();
     return 0;
 }
 
@@ -279,17 +285,15 @@ int rtxh_bvh_check(const float* wt, uint32_t ntris, uint32_t* nodes_out, uint32_
 // build on `before`, refit (topology kept) to `after`: the refitted boxes must contain the moved triangles
 int rtxh_bvh_refit_check(const float* before, const float* after, uint32_t ntris) {
     std::vector<float> a(before, before + (size_t)ntris * 9), b(after, after + (size_t)ntris * 9);
-    std::vector<rtx::NodeGPU> nodes; std::vector<uint32_t> order; uint32_t depth = 0;
-    rtx::build_bvh(a, 0.0f, nodes, order, depth);
-    rtx::refit_bvh(b, 0.0f, nodes, order);
-    if (int r = bvh_validate(b, nodes, order, nullptr)) return r;
-    std::vector<rtx::Node8GPU> n8; std::vector<uint32_t> slots; uint32_t stack = 0;
-    if (!rtx::collapse_bvh8(nodes, n8, slots, stack)) return 30;
-    return rtx::validate_bvh8(b, n8, order, slots, nullptr);
+    rtx::BuiltScene B;
+    rtx::build_bvh(a, 0.0f, B.nodes, B.leaf_order, B.max_depth);
+    rtx::refit_bvh(b, 0.0f, B.nodes, B.leaf_order);
+    if (int r = bvh_validate(b, B.nodes, B.leaf_order, nullptr)) return r;
+    rtx::leaf_triangles(b, B.leaf_order, B.tris);
+    if (!rtx::wide_from_binary(B)) return 30;
+    return rtx::validate_bvh8(b, B.nodes8, B.leaf_order, B.tri_slots8, nullptr);
 }
 
-// the tiny-scene pre-test records as rtx_commit_scene builds them (for host-side conservativeness tests)
-static bool build_for_inspection(const rtxh_scene* sc, rtx::BuiltScene& B);
 // records [0, *nocc_out) can lie between two scene points; the rest are faces of the scene's convex hull (skipped by NEE segments)
 int rtxh_scene_small_occluders(const rtxh_scene* sc, uint32_t* nocc_out) {
     rtx::BuiltScene B;
@@ -297,28 +301,17 @@ int rtxh_scene_small_occluders(const rtxh_scene* sc, uint32_t* nocc_out) {
     *nocc_out = B.small_nocc;
     return RTX_OK;
 }
-// what rtx_commit_scene's probe would choose for this scene (csrc/rtx_scene_host.cpp: probe_anyhit_order), and the replayed cost of the probe's segments per order
+// what rtx_commit_scene's probe would choose for this scene (csrc/rtx_bvh_replay.cpp: probe_anyhit_order), and the replayed cost of the probe's segments per order
 int rtxh_scene_anyhit_order(const rtxh_scene* sc, uint32_t* order_out) {
     rtx::BuiltScene B;
     if (!sc || !order_out || !build_for_inspection(sc, B)) return RTX_ERR_INVALID;
     *order_out = B.any_order;
     return RTX_OK;
 }
-static bool build_for_inspection(const rtxh_scene* sc, rtx::BuiltScene& B) {
-    rtx::SceneHost H;
-    const Scene& s = sc->s;
-    if (!H.set_materials(s.materials.data(), (uint32_t)s.materials.size())) return false;
-    for (const SceneModel& m : s.models) { uint32_t id; if (!H.add_mesh(m.vertices.data(), (uint32_t)m.vertices.size(), m.indices.data(), (uint32_t)m.indices.size(), m.materialIDs.data(), &id)) return false; }
-    for (const SceneInstance& in : s.instances) { uint32_t id; if (!H.add_instance(in.model, in.transform.data(), &id)) return false; }
-    return H.build(B);
-}
+// the tiny-scene pre-test records as rtx_commit_scene builds them (for host-side conservativeness tests)
 int rtxh_scene_small_records(const rtxh_scene* sc, float* recs20, int32_t* tri_ids2, uint32_t max_recs, uint32_t* nrec_out, float* delta_out, float* cm_out) {
-    rtx::SceneHost H; rtx::BuiltScene B;
-    const Scene& s = sc->s;
-    if (!H.set_materials(s.materials.data(), (uint32_t)s.materials.size())) return RTX_ERR_INVALID;
-    for (const SceneModel& m : s.models) { uint32_t id; if (!H.add_mesh(m.vertices.data(), (uint32_t)m.vertices.size(), m.indices.data(), (uint32_t)m.indices.size(), m.materialIDs.data(), &id)) return RTX_ERR_INVALID; }
-    for (const SceneInstance& in : s.instances) { uint32_t id; if (!H.add_instance(in.model, in.transform.data(), &id)) return RTX_ERR_INVALID; }
-    if (!H.build(B)) return RTX_ERR_INVALID;
+    rtx::BuiltScene B;
+    if (!build_for_inspection(sc, B)) return RTX_ERR_INVALID;
     if (nrec_out) *nrec_out = B.small_nrec;
     if (delta_out) *delta_out = 0.0f;                     // the tolerance is already folded into the records' edge constants (B.small_delta)
     if (cm_out) *cm_out = B.small_cm;

@@ -417,7 +417,7 @@ def test_params_struct_layout(rt, orc):
 
 
 def test_tiny_scene_pretest_records_are_conservative(rt, orc, cornell):
-    """The plane/edge pre-test of the tiny-scene path (rtx_scene_host.cpp) may only discard triangles the exact test
+    """The plane/edge pre-test of the tiny-scene path (rtx_small_scene.cpp) may only discard triangles the exact test
     rejects: emulate it in float64 for every brute-force hit of 100 k rays (camera, random, from-surface, grazing)."""
     recs, ids, delta, cm = cornell.small_records()
     assert len(recs) == 17 and (ids[:, 1] >= 0).sum() == 15                    # 15 planar quads + 2 single triangles (the twisted red wall)
@@ -531,6 +531,13 @@ def test_tiny_scene_hull_faces_come_last(rt, cornell):
     assert (ids[nocc:] >= 0).sum() == 10
 
 
+def _host_layer_sources(pk):
+    """the C++ host layer without the device API: the host scene and its BVH, the scene cache, the host facade (what the sanitizer runs compile beside their driver)"""
+    csrc = ("rtx_scene_host.cpp", "rtx_small_scene.cpp", "rtx_bvh_build.cpp", "rtx_bvh_wide.cpp", "rtx_bvh_replay.cpp", "rtx_scene_cache.cpp")
+    host = ("DirectXMathLite.cpp", "manipulator.cpp", "ObjLoader.cpp", "Scenes.cpp", "Renderer.cpp", "ImageIO.cpp", "rtx_host_c.cpp")
+    return [os.path.join(pk, "csrc", f) for f in csrc] + [os.path.join(pk, "host", f) for f in host]
+
+
 def test_host_layer_under_asan_ubsan(tmp_path, golden_dir):
     """the C++ host layer (scene generators, OBJ loader, BVH build / DP collapse / refit / validators, tiny-scene records, image
     writers) compiled with g++ -fsanitize=address,undefined and run on the CPU with the device API stubbed"""
@@ -539,9 +546,7 @@ def test_host_layer_under_asan_ubsan(tmp_path, golden_dir):
         pytest.skip("g++ not available")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     pk = os.path.join(root, "royaltracer-dx_amd")
-    srcs = [os.path.join(root, "tests", "sanitize", f) for f in ("host_main.cpp", "device_stubs.cpp")]
-    srcs += [os.path.join(pk, "csrc", "rtx_scene_host.cpp"), os.path.join(pk, "csrc", "rtx_scene_cache.cpp")] + [os.path.join(pk, "host", f) for f in
-             ("DirectXMathLite.cpp", "manipulator.cpp", "ObjLoader.cpp", "Scenes.cpp", "Renderer.cpp", "ImageIO.cpp", "rtx_host_c.cpp")]
+    srcs = [os.path.join(root, "tests", "sanitize", f) for f in ("host_main.cpp", "device_stubs.cpp")] + _host_layer_sources(pk)
     exe = str(tmp_path / "san_host")
     cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-ffp-contract=off",
            "-I" + os.path.join(root, "include"), "-I" + os.path.join(pk, "csrc"), "-I" + os.path.join(pk, "host"), "-pthread", "-o", exe] + srcs
@@ -562,9 +567,7 @@ def test_parallel_builder_under_tsan(tmp_path):
         pytest.skip("g++ not available")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     pk = os.path.join(root, "royaltracer-dx_amd")
-    srcs = [os.path.join(root, "tests", "sanitize", f) for f in ("tsan_main.cpp", "device_stubs.cpp")]
-    srcs += [os.path.join(pk, "csrc", "rtx_scene_host.cpp"), os.path.join(pk, "csrc", "rtx_scene_cache.cpp")] + [os.path.join(pk, "host", f) for f in
-             ("DirectXMathLite.cpp", "manipulator.cpp", "ObjLoader.cpp", "Scenes.cpp", "Renderer.cpp", "ImageIO.cpp", "rtx_host_c.cpp")]
+    srcs = [os.path.join(root, "tests", "sanitize", f) for f in ("tsan_main.cpp", "device_stubs.cpp")] + _host_layer_sources(pk)
     exe = str(tmp_path / "tsan_host")
     cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=thread", "-fno-omit-frame-pointer", "-ffp-contract=off",
            "-I" + os.path.join(root, "include"), "-I" + os.path.join(pk, "csrc"), "-I" + os.path.join(pk, "host"), "-pthread", "-o", exe] + srcs

@@ -1,10 +1,10 @@
 // bvh_lab.cpp — CPU laboratory for the BVH builder (tooling; no GPU, no HIP).  Builds a scene's wide BVH with the product's own
-// builder code (csrc/rtx_scene_host.cpp compiled into this executable) and replays the device traversal of csrc/rtx_traverse.hpp
+// builder code (csrc/rtx_scene_host.cpp and csrc/rtx_bvh_*.cpp compiled into this executable) and replays the device traversal of csrc/rtx_traverse.hpp
 // (node8_hits / descend8 / traverse, non-speculative order) in scalar C++ on path-like rays (camera rays + cosine-sampled bounces),
 // counting node steps and triangle tests per ray.  The point: judge a builder change by WORK PER RAY here, in seconds, before
 // spending GPU minutes on frame times.
 //   make -C tools bvh_lab && tools/bvh_lab sponza|bistro|garage [key=value ...]
-// Keys are handed to rtx::bvh_build_options() (see csrc/rtx_scene_host.hpp) — e.g. sweep=4096 reinsert=2 split=1e-5
+// Keys are handed to rtx::bvh_build_options() (see csrc/rtx_bvh_host.hpp) — e.g. sweep=4096 reinsert=2 split=1e-5
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -64,7 +64,7 @@ inline bool tri_test(V3 o, V3 d, const TriGPU& Tg, float tmin, float tmax, float
 struct Hit { float t; uint32_t slot, prim; uint32_t steps, tris; };
 
 int g_any_order = 0;      // any-hit visiting order: 0 = slot order, 1 = near first (octant order), 2 = far first
-// the product's own host-side replay of the device traversal (csrc/rtx_scene_host.cpp: replay_trace)
+// the product's own host-side replay of the device traversal (csrc/rtx_bvh_replay.cpp: replay_trace)
 template <bool ANY>
 Hit traverse(const BuiltScene& B, V3 o, V3 d, float tmin, float tmax, float tknown = -1.0f) {
     const float oo[3] = {o.x, o.y, o.z}, dd[3] = {d.x, d.y, d.z};

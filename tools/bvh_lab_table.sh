@@ -3,7 +3,7 @@
 # (round 5: + the HARD stand-ins — the real assets' triangle-size distribution, host/Scenes.h —, + the sizing of a flat test of the level-2 boxes, what-if rows in the product's arithmetic)
 cd "$(dirname "$0")/.."
 make -s -C tools bvh_lab || exit 1
-echo "# Work per ray on the host replay of the device traversal (tools/bvh_lab: the product's builder + csrc/rtx_scene_host.cpp replay_trace), round 5"
+echo "# Work per ray on the host replay of the device traversal (tools/bvh_lab: the product's builder + csrc/rtx_bvh_replay.cpp replay_trace), round 5"
 echo
 echo "480 x 270 camera rays + four cosine-sampled bounces each, one NEE-like shadow ray per vertex; closest-hit rays in the device's octant order, WITHOUT the speculative schedule"
 echo "(the GPU's own counters, bench.py extra.*.work_per_ray, read ~2 % more node steps).  cost = steps x 205 x 64 / 47 + tests x 70 x 64 / 24 VALU lane-slots (profiles/r02_traversal.md)."

@@ -9,7 +9,7 @@
 using namespace rtx;
 static inline uint32_t f2u_(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
 // soup_lab — is the closest / any hit the same for the product's tree as for brute force over all triangles?  No GPU: the product's builder (SceneHost::build) and the
-// host replay of the device traversal (csrc/rtx_scene_host.cpp: replay_trace) against a loop over every triangle with the replay's own triangle test, on triangle soups and
+// host replay of the device traversal (csrc/rtx_bvh_replay.cpp: replay_trace) against a loop over every triangle with the replay's own triangle test, on triangle soups and
 // rays chosen to break it: aimed at vertices / edges / interiors, LYING IN a triangle's plane, axis-parallel, random.  usage: soup_lab <needles|slivers|coplanar|mixed|random> [tris] [rays] [seed]
 // Exit code 1 when the product's definition (second row) shows a mismatch.
 int main(int argc, char** argv) {
