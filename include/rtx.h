@@ -168,6 +168,10 @@ enum { RTX_OPT_KERNEL_TIMING = 1,    /* 0/1: bracket every launch with hipEvents
                                         of the tree by the host's SAH builder + re-insertion over those clusters, SAH collapse to 8-wide nodes and layout on the device, then the refit
                                         kernels) instead of on the host: what the reference's driver does for it in BottomLevelASGenerator.cpp:178-247 / TopLevelASGenerator.cpp:149-250.
                                         0 (default): host build.  Results never depend on the tree; the host-side mirror of the tree (scene cache save, host refit) is not kept */
+       RTX_OPT_DEFORM_REBUILD = 40,  /* what a commit after rtx_update_mesh_vertices does to the tree.  0 (default): refit (the boxes follow the vertices, the topology stays); 1: rebuild, through
+                                        whichever builder RTX_OPT_GPU_BUILD selects; N >= 2: refit, then rebuild in the same commit if the tree's visit cost (rtx_debug_tree_cost) exceeds
+                                        N per cent of its value right after the last build (GPU-refit path only: a tiny scene or RTX_OPT_GPU_REFIT 0 refits on the host, where no cost
+                                        is kept).  Never changes a result */
        RTX_OPT_STACK_CAP = 39,       /* 11 (default): traversal-stack entries per lane that live in LDS; a tree whose exact stack bound is deeper keeps the rest in per-lane columns in
                                         global memory, so that LDS (the staged top of the tree, workgroups per CU) is sized for what almost every ray needs.  0 = the whole stack in LDS (until round 5).
                                         Never changes a result.  Takes effect with the next rtx_commit_scene */
@@ -195,6 +199,12 @@ int  rtx_add_instance(rtx_ctx*, uint32_t mesh, const float o2w[16], uint32_t* in
 /* t3 `instanceProps` update (UpdateInstancePropertiesBuffer, Renderer.cpp:2091-2121; prevObjectToWorld := the old matrix);
    needs rtx_commit_scene again, which then only REFITS the BVH boxes (TLAS refit, Renderer.cpp:594) instead of rebuilding */
 int  rtx_set_instance_transform(rtx_ctx*, uint32_t inst, const float o2w[16]);
+/* New vertex data for a mesh whose topology stays: nverts must equal the mesh's, indices and material ids are kept, Vertex.normal.w must be
+   what it was (the mesh's materialIDs base).  Positions AND normals are taken.  Needs rtx_commit_scene again, which then re-derives only the
+   triangles of this mesh's instances and refits (BottomLevelASGenerator.cpp:185-209, updateOnly) instead of rebuilding (RTX_OPT_DEFORM_REBUILD).
+   RTX_ERR_INVALID (unknown mesh, other vertex count, changed normal.w, null pointer) leaves the scene untouched and committed.  The ReSTIR history is
+   left alone (the temporal pass reprojects through prevObjectToWorld only): call rtx_restir_reset for a frame without ghosting. */
+int  rtx_update_mesh_vertices(rtx_ctx*, uint32_t mesh, const void* verts28, uint32_t nverts);
 /* CreateAccelerationStructures (Renderer.cpp:893-946) + CollectEmissiveTriangles (:2123-2213) +
    CreateEmissiveTrianglesBuffer (:2237-2280): BVH build, emissive CDF, upload */
 int  rtx_commit_scene(rtx_ctx*);
@@ -297,6 +307,10 @@ int  rtx_debug_validate_bvh(rtx_ctx*);
 /* FNV-1a hashes of the wide tree as the device holds it: out[0] the node records, out[1] the leaf-ordered triangle records — two contexts hold the same tree iff both agree
    (the GPU build against its host twin, a loaded scene cache against the build it was saved from) */
 int  rtx_debug_tree_hash(rtx_ctx*, uint64_t out2[2]);
+/* tree quality after refits (tooling, and what RTX_OPT_DEFORM_REBUILD >= 2 decides by): the sum over the wide nodes of half-area(node box) / half-area(root box) — the expected
+   number of node visits of a random line — out2[0] as the tree is now, out2[1] right after its last build.  Reproducible to the bit.  RTX_ERR_STATE for a tree the GPU refit
+   does not handle (tiny scenes).  A host-built tree that was never refitted is refitted here once (unchanged geometry) to get its boxes */
+int  rtx_debug_tree_cost(rtx_ctx*, double out2[2]);
 /* the wide tree itself (tooling: diffing two trees that should be equal): which = 0 the device's records, 1 the host builder's mirror of them (RTX_ERR_STATE when the tree was
    built on the device).  nodes: rtx_stats.bvh_nodes x 80 bytes, tris: rtx_stats.bvh_refs x 48 bytes; either may be NULL */
 int  rtx_debug_read_tree(rtx_ctx*, int which, void* nodes, uint64_t nodes_bytes, void* tris, uint64_t tris_bytes);

@@ -51,6 +51,9 @@ int         rtxh_scene_mesh(const rtxh_scene*, uint32_t i, const void** verts28,
 uint32_t    rtxh_scene_num_instances(const rtxh_scene*);
 int         rtxh_scene_instance(const rtxh_scene*, uint32_t i, uint32_t* mesh, float o2w[16]);
 uint64_t    rtxh_scene_num_triangles(const rtxh_scene*);
+/* new vertices for mesh i of the scene, topology kept (the host-layer twin of rtx_update_mesh_vertices, same checks: mesh exists, same vertex count, Vertex.normal.w
+   unchanged, non-null); RTX_ERR_INVALID + rtxh_last_error leaves the scene as it was.  No GPU needed */
+int         rtxh_scene_set_mesh_vertices(rtxh_scene*, uint32_t mesh, const void* verts28, uint32_t nverts);
 /* eye[3], center[3], up[3], fovY in degrees, znear, zfar (Renderer.cpp:46-48, 1730-1731) */
 int         rtxh_scene_camera(const rtxh_scene*, float eye[3], float center[3], float up[3], float* fovy_deg, float* zn, float* zf);
 int         rtxh_scene_set_camera(rtxh_scene*, const float eye[3], const float center[3], const float up[3]);   /* CameraManip.setLookat of the scene (Renderer.cpp:46-48); an OBJ file carries no camera */
@@ -109,6 +112,9 @@ int  rtxh_renderer_on_update(rtxh_renderer*);
 /* Renderer::SetInstanceTransform: m_instances[i].second of the reference's OnUpdate (Renderer.cpp:444-449); the next on_update hands the matrix to the context and refits the
    resident tree on the GPU (transform-only rtx_commit_scene; the reference refits its TLAS every frame, Renderer.cpp:594) */
 int  rtxh_renderer_set_instance_transform(rtxh_renderer*, uint32_t instance, const float o2w[16]);
+/* Renderer::SetMeshVertices: the next on_update hands the vertices to the context (rtx_update_mesh_vertices) and commits — a refit of the resident tree, or what
+   RTX_OPT_DEFORM_REBUILD says */
+int  rtxh_renderer_set_mesh_vertices(rtxh_renderer*, uint32_t mesh, const void* verts28, uint32_t nverts);
 int  rtxh_renderer_on_render(rtxh_renderer*);
 int  rtxh_renderer_read_accum(rtxh_renderer*, float* rgba32f, size_t bytes);
 int  rtxh_renderer_read_output(rtxh_renderer*, uint8_t* rgba8, size_t bytes);

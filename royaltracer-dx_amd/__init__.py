@@ -43,6 +43,7 @@ OPT_RESTIR_WAVEFRONT, OPT_RESTIR_CHUNKS, OPT_OCCLUDER_CACHE, OPT_RESTIR_LANES, O
 OPT_BVH_REINSERT, OPT_BVH_SPLIT, OPT_ANYHIT_ORDER, OPT_RESTIR_LANE_MIN, OPT_TRACE_COUNTERS, OPT_ASYNC, OPT_OCTANT_SORT, OPT_SAMPLE_INTERLEAVE, OPT_NODE_STRIDE, OPT_RESTIR_KEYS, OPT_LDS_NODES_CLOSEST, OPT_PARTIAL_REFIT = 26, 27, 28, 29, 30, 31, 32, 33, 34, 35, 36, 37
 OPT_GPU_BUILD = 38
 OPT_STACK_CAP = 39
+OPT_DEFORM_REBUILD = 40
 
 
 class RtxError(RuntimeError):
@@ -99,6 +100,7 @@ _sig("rtx_set_materials", C.c_int, _vp, _vp, _u32)
 _sig("rtx_add_mesh", C.c_int, _vp, _vp, _u32, _vp, _u32, _vp, _u32p)
 _sig("rtx_add_instance", C.c_int, _vp, _u32, _fp, _u32p)
 _sig("rtx_set_instance_transform", C.c_int, _vp, _u32, _fp)
+_sig("rtx_update_mesh_vertices", C.c_int, _vp, _u32, _vp, _u32)
 _sig("rtx_commit_scene", C.c_int, _vp)
 _sig("rtx_set_camera", C.c_int, _vp, _fp, _fp)
 _sig("rtx_save_scene_cache", C.c_int, _vp, C.c_char_p)
@@ -123,6 +125,7 @@ _sig("rtx_restir_halo_plan", C.c_int, C.POINTER(Params), _u32, C.POINTER(HaloPee
 _sig("rtx_restir_pack_halo", C.c_int, _vp, C.POINTER(Params), _u32, _vp)
 _sig("rtx_restir_unpack_halo", C.c_int, _vp, C.POINTER(Params), _u32, _vp)
 _sig("rtx_debug_tree_hash", C.c_int, _vp, C.POINTER(C.c_uint64))
+_sig("rtx_debug_tree_cost", C.c_int, _vp, C.POINTER(C.c_double))
 _sig("rtx_debug_read_host_build", C.c_int, _vp, C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p, C.POINTER(C.c_uint64))
 _sig("rtx_debug_host_checksums", C.c_int, _vp, C.POINTER(C.c_uint64))
 _sig("rtx_debug_read_tree", C.c_int, _vp, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64)
@@ -196,6 +199,8 @@ _sig("rtxh_write_ppm", C.c_int, C.c_char_p, _vp, _u32, _u32)
 _sig("rtxh_write_exr", C.c_int, C.c_char_p, _vp, _u32, _u32)
 _sig("rtxh_scene_small_records", C.c_int, _vp, _vp, _vp, _u32, _u32p, _fp, _fp)
 _sig("rtxh_scene_set_camera", C.c_int, _vp, _fp, _fp, _fp)
+_sig("rtxh_scene_set_mesh_vertices", C.c_int, _vp, _u32, _vp, _u32)
+_sig("rtxh_renderer_set_mesh_vertices", C.c_int, _vp, _u32, _vp, _u32)
 _sig("rtxh_renderer_create", _vp, _u32, _u32, C.c_char_p, C.c_int)
 _sig("rtxh_renderer_set_scene", C.c_int, _vp, _vp)
 _sig("rtxh_renderer_params", C.POINTER(Params), _vp)
@@ -295,6 +300,15 @@ class Scene:
         e, c, u = (np.asarray(v, np.float32) for v in (eye, center, up))
         lib.rtxh_scene_set_camera(self._h, _fptr(e), _fptr(c), _fptr(u))
         self.eye, self.center, self.up = e, c, u
+
+    def set_mesh_vertices(self, mesh, verts):
+        """new vertices (n, 7) for mesh `mesh`, topology kept: same count, column 6 (Vertex.normal.w) unchanged; updates the handle and the numpy copy"""
+        v = _f32(verts).reshape(-1, 7)
+        if lib.rtxh_scene_set_mesh_vertices(self._h, int(mesh), _ptr(v), len(v)) != RTX_OK:
+            raise RtxError("rtxh_scene_set_mesh_vertices failed: " + lib.rtxh_last_error().decode())
+        old = self.meshes[mesh]
+        self.meshes[mesh] = (v.copy(), old[1], old[2])
+        self.cache_path = None                         # (a loaded scene no longer matches its file: Context.upload goes through the arrays)
 
     def bounds(self):
         """world-space bounding box of all instances -> (lo, hi)"""
@@ -504,6 +518,11 @@ class Context:
         m = _f32(o2w).reshape(16)
         self._ck(lib.rtx_set_instance_transform(self._h, inst, _fptr(m)), "rtx_set_instance_transform")
 
+    def update_mesh_vertices(self, mesh, verts):
+        """new vertices (n, 7) for a mesh whose topology stays; the next commit() re-derives this mesh's instances and refits (OPT_DEFORM_REBUILD)"""
+        v = _f32(verts).reshape(-1, 7)
+        self._ck(lib.rtx_update_mesh_vertices(self._h, int(mesh), _ptr(v), len(v)), "rtx_update_mesh_vertices")
+
     def commit(self):
         self._ck(lib.rtx_commit_scene(self._h), "rtx_commit_scene")
 
@@ -651,6 +670,12 @@ class Context:
         self._ck(lib.rtx_debug_tree_hash(self._h, h), "rtx_debug_tree_hash")
         return int(h[0]), int(h[1])
 
+    def tree_cost(self):
+        """(visit cost of the resident tree now, right after its last build): sum over the wide nodes of half-area(node) / half-area(root); reproducible to the bit"""
+        out = (C.c_double * 2)()
+        self._ck(lib.rtx_debug_tree_cost(self._h, out), "rtx_debug_tree_cost")
+        return float(out[0]), float(out[1])
+
     def read_tree(self, which=0):
         """(node records (n, 80) uint8, leaf-ordered triangle records (m, 12) float32) of the device (which=0) or of the host builder's mirror (which=1)"""
         st = self.stats()
@@ -761,6 +786,11 @@ class Renderer:
         """Renderer::SetInstanceTransform: takes effect in the next on_update (transform-only commit = GPU refit)"""
         m = _f32(o2w16).reshape(16)
         self._ck(lib.rtxh_renderer_set_instance_transform(self._h, int(instance), _ptr(m)), "SetInstanceTransform")
+
+    def set_mesh_vertices(self, mesh, verts):
+        """Renderer::SetMeshVertices: new vertices (n, 7) for a model whose topology stays; takes effect in the next on_update (vertex-changing commit = re-flatten + refit)"""
+        v = _f32(verts).reshape(-1, 7)
+        self._ck(lib.rtxh_renderer_set_mesh_vertices(self._h, int(mesh), _ptr(v), len(v)), "SetMeshVertices")
 
     def on_render(self):
         self._ck(lib.rtxh_renderer_on_render(self._h), "OnRender")

@@ -159,6 +159,7 @@ int rtx_set_option(rtx_ctx* c, int option, int64_t value) {
     case RTX_OPT_MERGE_RAYS: if (value < 0 || value > (1 << 20)) { c->err = "merge_rays must be in [0, 2^20]"; return RTX_ERR_INVALID; } c->opt.merge_rays = (uint32_t)value; return RTX_OK;
     case RTX_OPT_GPU_REFIT: c->opt.gpu_refit = value != 0; return RTX_OK;
     case RTX_OPT_GPU_BUILD: c->opt.gpu_build = value != 0; return RTX_OK;
+    case RTX_OPT_DEFORM_REBUILD: if (value < 0 || value > 1000000) { c->err = "deform_rebuild must be 0 (refit), 1 (rebuild) or a percentage >= 2"; return RTX_ERR_INVALID; } c->opt.deform_rebuild = (int)value; return RTX_OK;
     case RTX_OPT_STACK_CAP: if (value < 0 || value > 30 || (value > 0 && value < 4)) { c->err = "stack_cap must be 0 (the whole stack in LDS) or in [4, 30]"; return RTX_ERR_INVALID; } c->opt.stack_cap = (uint32_t)value; c->committed = false; return RTX_OK;
     case RTX_OPT_SHADE_DENSE: c->opt.shade_dense = (int)value; options_to_scene(c, c->committed); return RTX_OK;
     case RTX_OPT_OCCLUDER_CACHE: c->opt.occluder_cache = value != 0; options_to_scene(c, c->committed); return RTX_OK;
@@ -200,6 +201,12 @@ int rtx_add_instance(rtx_ctx* c, uint32_t mesh, const float o2w[16], uint32_t* i
 int rtx_set_instance_transform(rtx_ctx* c, uint32_t inst, const float o2w[16]) {
     if (!c || !o2w) return RTX_ERR_INVALID;
     if (!c->host.set_instance_transform(inst, o2w)) { c->err = c->host.err; return RTX_ERR_INVALID; }
+    c->committed = false; return RTX_OK;
+}
+
+int rtx_update_mesh_vertices(rtx_ctx* c, uint32_t mesh, const void* verts28, uint32_t nverts) {
+    if (!c) return RTX_ERR_INVALID;
+    if (!c->host.update_mesh_vertices(mesh, verts28, nverts)) { c->err = c->host.err; return RTX_ERR_INVALID; }     // (nothing changed: the scene stays committed)
     c->committed = false; return RTX_OK;
 }
 

@@ -353,14 +353,11 @@ std::string GpuBvhBuilder::build(hipStream_t st, const F4* d_objtris, const TriS
 }
 
 // ---- flatten (rtx_build.hpp) ----
-__global__ void __launch_bounds__(256) k_flatten(const float* __restrict__ verts7, const uint32_t* __restrict__ idx, const uint32_t* __restrict__ matids, uint32_t nmatids,
-                                                 const FlatInst* __restrict__ insts, uint32_t ninst, uint32_t ntri, F4* __restrict__ objtris, TriShade* __restrict__ shade) {
-    const uint32_t g = blockIdx.x * 256u + threadIdx.x;
-    if (g >= ntri) return;
-    uint32_t lo = 0, hi = ninst - 1u;                       // the LAST instance whose first triangle is <= g (instances without triangles share a base with their successor)
-    while (lo < hi) { const uint32_t mid = (lo + hi + 1u) >> 1; if (insts[mid].tri_base <= g) lo = mid; else hi = mid - 1u; }
-    const FlatInst F = insts[lo];
-    const uint32_t t = g - F.tri_base;
+// triangle t of the instance F describes (instance index `inst`): its object-space corners and its shade record, written at the global id F.tri_base + t.  The ONE body of
+// k_flatten and k_reflatten (and the twin of flatten_range, csrc/rtx_scene_host.cpp)
+__device__ __forceinline__ void flatten_triangle(const float* __restrict__ verts7, const uint32_t* __restrict__ idx, const uint32_t* __restrict__ matids, uint32_t nmatids,
+                                                 const FlatInst& F, uint32_t inst, uint32_t t, F4* __restrict__ objtris, TriShade* __restrict__ shade) {
+    const uint32_t g = F.tri_base + t;
     const uint32_t vi[3] = {idx[(size_t)F.idx_base + 3u * t], idx[(size_t)F.idx_base + 3u * t + 1u], idx[(size_t)F.idx_base + 3u * t + 2u]};
     f3 p[3], n[3];
     for (int k = 0; k < 3; k++) {
@@ -371,7 +368,7 @@ __global__ void __launch_bounds__(256) k_flatten(const float* __restrict__ verts
     TriShade s;
     const uint32_t mi = F.matid_base + 3u * t;              // == 3*PrimitiveIndex() + uint(v0.normal.w), Hit_v6.hlsl:16-17
     s.mat = mi < nmatids ? matids[mi] : kMissMat;
-    s.inst = lo;
+    s.inst = inst;
     const f3 cr = cross(p[1] - p[0], p[2] - p[0]);          // :28-30
     s.area = fabsf(length(cr) * 0.5f);                      // :31
     const f3 flat = normalize(cr);                          // :32
@@ -384,10 +381,38 @@ __global__ void __launch_bounds__(256) k_flatten(const float* __restrict__ verts
     s.guard_tau = 0.0f;
     shade[g] = s;
 }
+__global__ void __launch_bounds__(256) k_flatten(const float* __restrict__ verts7, const uint32_t* __restrict__ idx, const uint32_t* __restrict__ matids, uint32_t nmatids,
+                                                 const FlatInst* __restrict__ insts, uint32_t ninst, uint32_t ntri, F4* __restrict__ objtris, TriShade* __restrict__ shade) {
+    const uint32_t g = blockIdx.x * 256u + threadIdx.x;
+    if (g >= ntri) return;
+    uint32_t lo = 0, hi = ninst - 1u;                       // the LAST instance whose first triangle is <= g (instances without triangles share a base with their successor)
+    while (lo < hi) { const uint32_t mid = (lo + hi + 1u) >> 1; if (insts[mid].tri_base <= g) lo = mid; else hi = mid - 1u; }
+    const FlatInst F = insts[lo];
+    flatten_triangle(verts7, idx, matids, nmatids, F, lo, g - F.tri_base, objtris, shade);
+}
+// the flatten of a vertex-changing commit (rtx_update_mesh_vertices): one thread per triangle of the instances of the CHANGED meshes only.  `work` is the compacted list of
+// those instances; work_base (ascending) is an entry's first position in the work list — the binary search runs on it, the records go to tri_base + t as ever — and inst
+// its index in the scene.  Every thread writes its own triangle's records and reads nothing another thread of the launch writes.
+__global__ void __launch_bounds__(256) k_reflatten(const float* __restrict__ verts7, const uint32_t* __restrict__ idx, const uint32_t* __restrict__ matids, uint32_t nmatids,
+                                                   const FlatInst* __restrict__ work, uint32_t nwork, uint32_t nitems, F4* __restrict__ objtris, TriShade* __restrict__ shade) {
+    const uint32_t w = blockIdx.x * 256u + threadIdx.x;
+    if (w >= nitems) return;
+    uint32_t lo = 0, hi = nwork - 1u;
+    while (lo < hi) { const uint32_t mid = (lo + hi + 1u) >> 1; if (work[mid].work_base <= w) lo = mid; else hi = mid - 1u; }
+    const FlatInst F = work[lo];
+    const uint32_t t = w - F.work_base;
+    if (t >= F.ntri) return;                                // (cannot happen for a list the host compacted: work_base[k + 1] = work_base[k] + ntri[k])
+    flatten_triangle(verts7, idx, matids, nmatids, F, F.inst, t, objtris, shade);
+}
 void launch_flatten(hipStream_t st, const float* verts7, const uint32_t* idx, const uint32_t* matids, uint32_t nmatids, const FlatInst* insts, uint32_t ninst, uint32_t ntri,
                     F4* objtris_out, TriShade* shade_out) {
     if (!ntri || !ninst) return;
     hipLaunchKernelGGL(k_flatten, dim3((ntri + 255u) / 256u), dim3(256), 0, st, verts7, idx, matids, nmatids, insts, ninst, ntri, objtris_out, shade_out);
+}
+void launch_reflatten(hipStream_t st, const float* verts7, const uint32_t* idx, const uint32_t* matids, uint32_t nmatids, const FlatInst* work, uint32_t nwork, uint32_t nitems,
+                      F4* objtris_out, TriShade* shade_out) {
+    if (!nitems || !nwork) return;
+    hipLaunchKernelGGL(k_reflatten, dim3((nitems + 255u) / 256u), dim3(256), 0, st, verts7, idx, matids, nmatids, work, nwork, nitems, objtris_out, shade_out);
 }
 
 }  // namespace rtx

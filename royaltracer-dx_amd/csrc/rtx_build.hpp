@@ -37,8 +37,13 @@ private:
 
 // ---- the flatten of a geometry-changing commit ON THE DEVICE (RTX_OPT_GPU_BUILD): object-space triangles and shade records (Hit_v6.hlsl:12-61) of every instanced triangle from
 //      the meshes as they were handed over.  The host twin is the flatten step of SceneHost::build (csrc/rtx_scene_host.cpp: flatten_range) — same functions of rtx_math.hpp, same order. ----
-struct FlatInst { uint32_t tri_base, ntri, vert_base, idx_base, matid_base, pad_[3]; };       // one per instance, in instance order (tri_base ascending)
+// one per instance, in instance order (tri_base ascending).  work_base / inst are read by k_reflatten only: the entry's first position in a compacted work list, its instance index
+struct FlatInst { uint32_t tri_base, ntri, vert_base, idx_base, matid_base, work_base, inst, pad_; };
 void launch_flatten(hipStream_t st, const float* verts7, const uint32_t* idx, const uint32_t* matids, uint32_t nmatids, const FlatInst* insts, uint32_t ninst, uint32_t ntri,
                     F4* objtris_out, TriShade* shade_out);
+// the same records for the triangles of a compacted list of instances (a vertex-changing commit re-derives the instances of the changed meshes only): `work` ascending in
+// work_base, nitems = the sum of its ntri
+void launch_reflatten(hipStream_t st, const float* verts7, const uint32_t* idx, const uint32_t* matids, uint32_t nmatids, const FlatInst* work, uint32_t nwork, uint32_t nitems,
+                      F4* objtris_out, TriShade* shade_out);
 
 }  // namespace rtx

@@ -61,10 +61,12 @@ static int grow_keep(rtx_ctx* c, DevBuf& b, size_t used, size_t need) {
     b = std::move(nb);
     return RTX_OK;
 }
-// the meshes added since the last commit -> the device pool; the per-instance ranges; then the flatten itself
-static int flatten_on_device(rtx_ctx* c, uint32_t ntri) {
+// the device mesh pool follows the host's mesh list: the meshes added since the last commit are appended, the vertex ranges of the meshes named in pool_dirty (vertices
+// replaced since the pool last saw them) are overwritten in place
+static int sync_mesh_pool(rtx_ctx* c) {
     const SceneHost& H = c->host;
-    if (H.meshes.size() < c->scene.pool_meshes) { c->scene.pool_meshes = 0; c->scene.pool_verts = c->scene.pool_idx = c->scene.pool_matids = 0; c->scene.pool_vert_base.clear(); c->scene.pool_idx_base.clear(); }     // (another scene: start over)
+    if (H.meshes.size() < c->scene.pool_meshes) { c->scene.pool_meshes = 0; c->scene.pool_verts = c->scene.pool_idx = c->scene.pool_matids = 0; c->scene.pool_vert_base.clear(); c->scene.pool_idx_base.clear(); c->scene.pool_dirty.clear(); }     // (another scene: start over)
+    const size_t had = c->scene.pool_meshes;
     size_t nv = c->scene.pool_verts, ni = c->scene.pool_idx;
     for (size_t m = c->scene.pool_meshes; m < H.meshes.size(); m++) { nv += H.meshes[m].verts.size() / 7; ni += H.meshes[m].idx.size(); }
     if (nv > 0xFFFFFFFFull || ni > 0xFFFFFFFFull) { c->err = "commit: more than 2^32 vertices or indices"; return RTX_ERR_INVALID; }
@@ -81,11 +83,25 @@ static int flatten_on_device(rtx_ctx* c, uint32_t ntri) {
     }
     c->scene.pool_meshes = H.meshes.size();
     if (H.matids.size() > c->scene.pool_matids) { TO_DEVICE(c, (char*)c->scene.d_pool_matids.p + c->scene.pool_matids * 4, H.matids.data() + c->scene.pool_matids, (H.matids.size() - c->scene.pool_matids) * 4); c->scene.pool_matids = H.matids.size(); }
-    c->scene.h_flat.resize(H.insts.size());
-    for (size_t ii = 0; ii < H.insts.size(); ii++) {
-        const InstHost& in = H.insts[ii]; const MeshHost& M = H.meshes[in.mesh];
-        c->scene.h_flat[ii] = FlatInst{in.tri_base, (uint32_t)(M.idx.size() / 3), c->scene.pool_vert_base[in.mesh], c->scene.pool_idx_base[in.mesh], M.matid_base, {0u, 0u, 0u}};
+    for (uint32_t m : c->scene.pool_dirty) {                 // (the vertex count of a mesh never changes: the range is the one it was appended to)
+        if (m >= had) continue;                              // appended just now, with its current vertices
+        const MeshHost& M = H.meshes[m];
+        TO_DEVICE(c, (char*)c->scene.d_pool_verts.p + (size_t)c->scene.pool_vert_base[m] * 28, M.verts.data(), M.verts.size() * 4);
     }
+    c->scene.pool_dirty.clear();
+    return RTX_OK;
+}
+static FlatInst flat_inst(const rtx_ctx* c, size_t ii, uint32_t work_base) {
+    const InstHost& in = c->host.insts[ii]; const MeshHost& M = c->host.meshes[in.mesh];
+    return FlatInst{in.tri_base, (uint32_t)(M.idx.size() / 3), c->scene.pool_vert_base[in.mesh], c->scene.pool_idx_base[in.mesh], M.matid_base, work_base, (uint32_t)ii, 0u};
+}
+// the pool brought up to date; the per-instance ranges; then the flatten itself
+static int flatten_on_device(rtx_ctx* c, uint32_t ntri) {
+    const SceneHost& H = c->host;
+    int r;
+    if ((r = sync_mesh_pool(c))) return r;
+    c->scene.h_flat.resize(H.insts.size());
+    for (size_t ii = 0; ii < H.insts.size(); ii++) c->scene.h_flat[ii] = flat_inst(c, ii, H.insts[ii].tri_base);
     if ((r = upload(c, c->scene.d_flat_insts, c->scene.h_flat))) return r;
     HIPCHK(c, c->scene.d_objtris.ensure((size_t)ntri * 3 * sizeof(F4))); HIPCHK(c, c->scene.d_shade.ensure((size_t)ntri * sizeof(TriShade)));
     launch_flatten(c->stream, (const float*)c->scene.d_pool_verts.p, (const uint32_t*)c->scene.d_pool_idx.p, (const uint32_t*)c->scene.d_pool_matids.p, (uint32_t)H.matids.size(), (const FlatInst*)c->scene.d_flat_insts.p,
@@ -93,7 +109,79 @@ static int flatten_on_device(rtx_ctx* c, uint32_t ntri) {
     HIPCHK(c, hipGetLastError());
     return RTX_OK;
 }
+// vertex-changing commit of a resident scene: object-space triangles and shade records of the instances of the changed meshes, re-derived in place (k_reflatten) from the
+// pool — which a host-built scene gets here, on its first such commit
+static int reflatten_dirty_meshes(rtx_ctx* c) {
+    const SceneHost& H = c->host;
+    int r;
+    if ((r = sync_mesh_pool(c))) return r;
+    c->scene.h_work.clear();
+    uint64_t nitems = 0;
+    for (size_t ii = 0; ii < H.insts.size(); ii++)
+        if (H.mesh_is_dirty(H.insts[ii].mesh)) { c->scene.h_work.push_back(flat_inst(c, ii, (uint32_t)nitems)); nitems += c->scene.h_work.back().ntri; }
+    if (!nitems) return RTX_OK;                              // (a changed mesh nobody instances)
+    if ((r = upload(c, c->scene.d_work_insts, c->scene.h_work))) return r;
+    launch_reflatten(c->stream, (const float*)c->scene.d_pool_verts.p, (const uint32_t*)c->scene.d_pool_idx.p, (const uint32_t*)c->scene.d_pool_matids.p, (uint32_t)H.matids.size(), (const FlatInst*)c->scene.d_work_insts.p,
+                     (uint32_t)c->scene.h_work.size(), (uint32_t)nitems, (F4*)c->scene.d_objtris.p, (TriShade*)c->scene.d_shade.p);
+    HIPCHK(c, hipGetLastError());
+    return RTX_OK;
+}
 
+// ---- tree quality (k_tree_cost, csrc/rtx_kernels.hip) ----
+static int full_refit(rtx_ctx* c) {              // world triangles from the object-space ones, every node quantised bottom-up, node_aabb filled: what the first transform-only commit after a build runs
+    BuiltScene& B = c->scene.built;
+    HIPCHK(c, c->scene.d_node_aabb.ensure((size_t)c->scene.n_nodes8 * 32));
+    c->scene.h_one.assign(1, 0x3f800000u);                       // scale starts at 1.0 like the host's max(1, |coordinates|)
+    int r;
+    if ((r = upload(c, c->scene.d_scale, c->scene.h_one))) return r;
+    launch_refit(c->stream, (Node8GPU*)c->scene.d_nodes.p, B.level_start8.data(), (uint32_t)B.level_start8.size() - 1, (TriGPU*)c->scene.d_tris.p, c->scene.n_tris8,
+                 (const TriShade*)c->scene.d_shade.p, (const InstGPU*)c->scene.d_insts.p, (const F4*)c->scene.d_objtris.p, (F4*)c->scene.d_node_aabb.p, (uint32_t*)c->scene.d_scale.p, nullptr, nullptr, nullptr);
+    HIPCHK(c, hipGetLastError());
+    c->scene.node_aabb_valid = true;
+    return RTX_OK;
+}
+static int upload_objtris_once(rtx_ctx* c) {
+    BuiltScene& B = c->scene.built;
+    if (c->scene.objtris_uploaded) return RTX_OK;
+    if (B.objtris.empty()) c->host.fill_objtris(B);             // scene came from a cache file: derive them from the meshes now
+    int r = upload(c, c->scene.d_objtris, B.objtris);
+    if (r == RTX_OK) c->scene.objtris_uploaded = true;
+    return r;
+}
+static int enqueue_tree_cost(rtx_ctx* c, DevBuf& partial) {
+    HIPCHK(c, partial.ensure((size_t)tree_cost_partials(c->scene.n_nodes8) * 4));
+    launch_tree_cost(c->stream, (const F4*)c->scene.d_node_aabb.p, c->scene.n_nodes8, (float*)partial.p);
+    HIPCHK(c, hipGetLastError());
+    return RTX_OK;
+}
+static int read_tree_cost(rtx_ctx* c, const DevBuf& partial, double& out) {     // the partial sums added in index order, in double: the same bits whenever the boxes are the same
+    std::vector<float> h(tree_cost_partials(c->scene.n_nodes8));
+    TO_HOST(c, h.data(), partial.p, h.size() * 4);
+    double sum = 0.0;
+    for (size_t i = 0; i + 1 < h.size(); i++) sum += (double)h[i];
+    out = (double)h.back() > 0.0 ? sum / (double)h.back() : 0.0;
+    return RTX_OK;
+}
+// The baseline: the cost of the tree as its last build left it.  A GPU build records it behind its own full refit; a host-built tree has no float boxes on the device until its
+// first refit, so it is taken when first needed — BEFORE the first vertex-changing commit touches the device, or at the first rtx_debug_tree_cost — from a full refit of the
+// unchanged geometry (no commit without new vertices pays for it; transform-only refits that came earlier are part of that baseline).  *refitted: the nodes were re-quantised
+static int ensure_cost_baseline(rtx_ctx* c, bool* refitted) {
+    if (c->scene.cost_base_state) return RTX_OK;
+    int r;
+    if (!c->scene.node_aabb_valid) {
+        if ((r = upload_objtris_once(c))) return r;
+        if ((r = full_refit(c))) return r;
+        if (refitted) *refitted = true;
+    }
+    if ((r = enqueue_tree_cost(c, c->scene.d_cost_base))) return r;
+    c->scene.cost_base_state = 1;
+    return RTX_OK;
+}
+static bool gpu_refittable(const rtx_ctx* c) {
+    const BuiltScene& B = c->scene.built;
+    return c->scene.device_scene_valid && B.small_nrec == 0 && c->scene.n_nodes8 != 0 && B.level_start8.size() >= 2;
+}
+static int refresh_wide_nodes(rtx_ctx* c);
 // probe_anyhit_order (csrc/rtx_scene_host.cpp) for a tree the host holds no mirror of (RTX_OPT_GPU_BUILD): the same 2 048 NEE-like segments — a point on a random triangle to a
 // CDF-sampled point on a light —, traced ON THE DEVICE in the three visiting orders by the counting form of the any-hit traversal, judged by the same cost model
 static int probe_anyhit_order_on_device(rtx_ctx* c, uint32_t& best_out) {
@@ -144,82 +232,104 @@ static int probe_anyhit_order_on_device(rtx_ctx* c, uint32_t& best_out) {
     return RTX_OK;
 }
 
+// Transform- or vertex-only commit of a resident scene: refit ON THE GPU — the kernels re-derive the world triangles and re-quantise the wide nodes bottom-up; the host only
+// re-derives the instance matrices and the light list.  New vertices (rtx_update_mesh_vertices): the changed meshes go to the pool and k_reflatten re-derives the object-space
+// triangles and shade records of their instances first; refresh_transforms has flagged those instances like moved ones, so the same partial refit follows.
+static int refit_resident(rtx_ctx* c, bool deform) {
+    BuiltScene& B = c->scene.built;
+    int r;
+    if (deform && (r = ensure_cost_baseline(c, nullptr))) return r;      // (while the device still holds the geometry of the last commit)
+    const bool mats_changed = c->host.mats_dirty;
+    if (!c->host.refresh_transforms(B)) { c->err = c->host.err; return RTX_ERR_INVALID; }
+    if (mats_changed && (r = upload(c, c->scene.d_mats, B.mats))) return r;      // rtx_set_materials on a resident scene: new table beside the new light list
+    if ((r = upload(c, c->scene.d_insts, B.insts))) return r;
+    if ((r = upload_lights(c))) return r;
+    if ((r = upload_objtris_once(c))) return r;
+    if (deform) {
+        if ((r = reflatten_dirty_meshes(c))) return r;
+        // the host's copies of the per-triangle records now describe the old vertices.  The stale-mirror rule: nothing reads them again — the object-space triangles are dropped
+        // (fill_objtris re-derives them from the meshes if they are ever uploaded again), the shade records stay for their count only and rtx_save_scene_cache refuses
+        if (!c->scene.dev_built) { B.objtris.clear(); B.objtris.shrink_to_fit(); c->scene.host_mirror_stale = true; }
+    }
+    HIPCHK(c, c->scene.d_node_aabb.ensure((size_t)c->scene.n_nodes8 * 32));
+    // the first refit after a build is a full one (it fills node_aabb); later ones touch the moved instances only, unless every instance moved anyway
+    size_t nmoved = 0; for (uint32_t m : B.inst_moved) nmoved += m;
+    const bool partial = c->opt.partial_refit && c->scene.node_aabb_valid && B.inst_moved.size() == B.insts.size() && nmoved < B.insts.size();
+    if (!partial) return full_refit(c);
+    if ((r = upload(c, c->scene.d_inst_moved, B.inst_moved))) return r;
+    HIPCHK(c, c->scene.d_tri_dirty.ensure(c->scene.n_tris8)); HIPCHK(c, c->scene.d_node_dirty.ensure(c->scene.n_nodes8));
+    launch_refit(c->stream, (Node8GPU*)c->scene.d_nodes.p, B.level_start8.data(), (uint32_t)B.level_start8.size() - 1, (TriGPU*)c->scene.d_tris.p, c->scene.n_tris8,
+                 (const TriShade*)c->scene.d_shade.p, (const InstGPU*)c->scene.d_insts.p, (const F4*)c->scene.d_objtris.p, (F4*)c->scene.d_node_aabb.p, (uint32_t*)c->scene.d_scale.p,
+                 (const uint32_t*)c->scene.d_inst_moved.p, (uint8_t*)c->scene.d_tri_dirty.p, (uint8_t*)c->scene.d_node_dirty.p);
+    HIPCHK(c, hipGetLastError());
+    return RTX_OK;
+}
+
+// Anything else: host build (or host refit — topo_dirty == false: from the meshes as they are now, new vertices included) + upload, or the build on the device
+static int build_and_upload(rtx_ctx* c) {
+    BuiltScene& B = c->scene.built;
+    int r;
+    c->scene.device_scene_valid = false; c->scene.objtris_uploaded = false; c->scene.node_aabb_valid = false; c->scene.host_mirror_stale = false;
+    size_t ntri_all = 0; for (const InstHost& in : c->host.insts) ntri_all += c->host.meshes[in.mesh].idx.size() / 3;
+    // RTX_OPT_GPU_BUILD: the tree on the device (csrc/rtx_build.hip).  Not for tiny scenes (their pre-test records are built from the host tree's leaf order) nor with
+    // spatial splits (a host-builder feature); there the host builds as before.
+    const bool on_gpu = c->opt.gpu_build && ntri_all > 4096u && c->host.bvh.split_alpha <= 0.0;
+    if (!(on_gpu ? c->host.prepare_device_build(B) : c->host.build(B))) { c->err = c->host.err; return RTX_ERR_INVALID; }
+    if (!on_gpu) return upload_built(c);
+    const uint32_t nt = B.built_tris;
+    if ((r = upload(c, c->scene.d_mats, B.mats))) return r;
+    if ((r = upload(c, c->scene.d_insts, B.insts))) return r;
+    if ((r = upload_lights(c))) return r;
+    if ((r = flatten_on_device(c, nt))) return r; c->scene.objtris_uploaded = true;          // object-space triangles + shade records, from the resident meshes
+    for (DevBuf* b : {&c->scene.d_small, &c->scene.d_small_tris, &c->scene.d_small_poly}) HIPCHK(c, b->ensure(16));
+    HIPCHK(c, c->scene.d_tris.ensure((size_t)nt * sizeof(TriGPU)));
+    if (!c->scene.builder) c->scene.builder.reset(new GpuBvhBuilder());
+    BvhBuildOptions bo = c->host.bvh; if (bo.ploc_radius <= 0) bo.ploc_radius = 16;
+    const std::string e = c->scene.builder->build(c->stream, (const F4*)c->scene.d_objtris.p, (const TriShade*)c->scene.d_shade.p, (const InstGPU*)c->scene.d_insts.p, nt, bo, (TriGPU*)c->scene.d_tris.p, c->scene.build_info);
+    if (!e.empty()) { c->err = e; return RTX_ERR_HIP; }
+    const GpuBuildResult& G = c->scene.build_info;
+    HIPCHK(c, c->scene.d_nodes.ensure((size_t)G.nnodes8 * sizeof(Node8GPU)));
+    HIPCHK(c, hipMemcpyAsync(c->scene.d_nodes.p, c->scene.builder->nodes(), (size_t)G.nnodes8 * sizeof(Node8GPU), hipMemcpyDeviceToDevice, c->stream));
+    c->scene.n_nodes8 = G.nnodes8; c->scene.n_tris8 = G.ntris8; c->scene.dev_built = true; B.bvh_pad = 2e-6f * G.scale;
+    B.level_start8 = G.level_start8; B.stack8 = G.stack8;
+    // the boxes: a FULL refit — world triangles from the object-space ones, every node quantised bottom-up (what a transform-only commit runs)
+    if ((r = full_refit(c))) return r;
+    if (c->scene.n_nodes8) { if ((r = enqueue_tree_cost(c, c->scene.d_cost_base))) return r; c->scene.cost_base_state = 1; }     // the baseline of RTX_OPT_DEFORM_REBUILD: one small launch, read when asked for
+    TO_HOST(c, &c->scene.root8, c->scene.d_nodes.p, sizeof(Node8GPU));
+    if (getenv("RTX_BUILD_TIMES")) fprintf(stderr, "[build] GPU: prims %.2f ms, sort %.2f ms, PLOC %.2f ms (%u rounds -> %u clusters), top on the host %.2f ms, layout %.2f ms: %u wide nodes, stack %u\n",
+                                           G.ms_prims, G.ms_sort, G.ms_ploc, G.ploc_iterations, G.clusters_top, G.ms_top_host, G.ms_layout, G.nnodes8, G.stack8);
+    return RTX_OK;
+}
+
 int rtx_commit_scene(rtx_ctx* c) {
     BIND(c);
+    // rtx_update_mesh_vertices since the last commit: topology stays, so this commit REFITS (BottomLevelASGenerator.cpp:185-209, updateOnly) — unless RTX_OPT_DEFORM_REBUILD
+    // says rebuild (1), or (N >= 2) the refitted tree has degraded past N % of its cost after the last build, which the same commit then answers with a rebuild
+    const bool deform = !c->host.dirty_meshes.empty();
+    for (uint32_t m : c->host.dirty_meshes)
+        if (m < c->scene.pool_meshes && std::find(c->scene.pool_dirty.begin(), c->scene.pool_dirty.end(), m) == c->scene.pool_dirty.end()) c->scene.pool_dirty.push_back(m);
+    if (deform && c->opt.deform_rebuild == 1) c->host.topo_dirty = true;
     if (c->host.topo_dirty || c->host.mats_dirty || !c->scene.committed_once)      // (a transform-only commit changes neither the ids nor the table: not 11 M comparisons per frame)
         for (size_t i = 0; i < c->host.matids.size(); i++)
             if (c->host.matids[i] >= c->host.mats128.size() / 32) { c->err = "commit: material id out of range"; return RTX_ERR_INVALID; }
     c->scene.committed_once = true;
-    BuiltScene& B = c->scene.built;
     int r;
-    // Transform-only commit of a scene that is already resident (and not a tiny one, whose pre-test records depend on world
-    // positions): refit ON THE GPU — the kernels re-derive the world triangles and re-quantise the wide nodes bottom-up; the host
-    // only re-derives the instance matrices and the light list.  Anything else: host build (or host refit) + upload.
-    const bool gpu_path = c->opt.gpu_refit && c->scene.device_scene_valid && !c->host.topo_dirty && B.small_nrec == 0 && c->scene.n_nodes8 != 0 && B.level_start8.size() >= 2;
-    if (gpu_path) {
-        const bool mats_changed = c->host.mats_dirty;
-        if (!c->host.refresh_transforms(B)) { c->err = c->host.err; return RTX_ERR_INVALID; }
-        if (mats_changed && (r = upload(c, c->scene.d_mats, B.mats))) return r;      // rtx_set_materials on a resident scene: new table beside the new light list
-        if ((r = upload(c, c->scene.d_insts, B.insts))) return r;
-        if ((r = upload_lights(c))) return r;
-        if (!c->scene.objtris_uploaded) {
-            if (B.objtris.empty()) c->host.fill_objtris(B);             // scene came from a cache file: derive them from the meshes now
-            if ((r = upload(c, c->scene.d_objtris, B.objtris))) return r; c->scene.objtris_uploaded = true;
-        }
-        HIPCHK(c, c->scene.d_node_aabb.ensure((size_t)c->scene.n_nodes8 * 32));
-        // the first refit after a build is a full one (it fills node_aabb); later ones touch the moved instances only, unless every instance moved anyway
-        size_t nmoved = 0; for (uint32_t m : B.inst_moved) nmoved += m;
-        const bool partial = c->opt.partial_refit && c->scene.node_aabb_valid && B.inst_moved.size() == B.insts.size() && nmoved < B.insts.size();
-        if (partial) {
-            if ((r = upload(c, c->scene.d_inst_moved, B.inst_moved))) return r;
-            HIPCHK(c, c->scene.d_tri_dirty.ensure(c->scene.n_tris8)); HIPCHK(c, c->scene.d_node_dirty.ensure(c->scene.n_nodes8));
-        } else {
-            c->scene.h_one.assign(1, 0x3f800000u);                       // scale starts at 1.0 like the host's max(1, |coordinates|)
-            if ((r = upload(c, c->scene.d_scale, c->scene.h_one))) return r;
-        }
-        launch_refit(c->stream, (Node8GPU*)c->scene.d_nodes.p, B.level_start8.data(), (uint32_t)B.level_start8.size() - 1, (TriGPU*)c->scene.d_tris.p, c->scene.n_tris8,
-                     (const TriShade*)c->scene.d_shade.p, (const InstGPU*)c->scene.d_insts.p, (const F4*)c->scene.d_objtris.p, (F4*)c->scene.d_node_aabb.p, (uint32_t*)c->scene.d_scale.p,
-                     partial ? (const uint32_t*)c->scene.d_inst_moved.p : nullptr, (uint8_t*)c->scene.d_tri_dirty.p, (uint8_t*)c->scene.d_node_dirty.p);
-        HIPCHK(c, hipGetLastError());
-        c->scene.node_aabb_valid = true;
-    } else {
-        c->scene.device_scene_valid = false; c->scene.objtris_uploaded = false; c->scene.node_aabb_valid = false;
-        size_t ntri_all = 0; for (const InstHost& in : c->host.insts) ntri_all += c->host.meshes[in.mesh].idx.size() / 3;
-        // RTX_OPT_GPU_BUILD: the tree on the device (csrc/rtx_build.hip).  Not for tiny scenes (their pre-test records are built from the host tree's leaf order) nor with
-        // spatial splits (a host-builder feature); there the host builds as before.
-        const bool on_gpu = c->opt.gpu_build && ntri_all > 4096u && c->host.bvh.split_alpha <= 0.0;
-        if (!(on_gpu ? c->host.prepare_device_build(B) : c->host.build(B))) { c->err = c->host.err; return RTX_ERR_INVALID; }
-        if (!on_gpu) { if ((r = upload_built(c))) return r; }
-        else {
-            const uint32_t nt = B.built_tris;
-            if ((r = upload(c, c->scene.d_mats, B.mats))) return r;
-            if ((r = upload(c, c->scene.d_insts, B.insts))) return r;
-            if ((r = upload_lights(c))) return r;
-            if ((r = flatten_on_device(c, nt))) return r; c->scene.objtris_uploaded = true;          // object-space triangles + shade records, from the resident meshes
-            for (DevBuf* b : {&c->scene.d_small, &c->scene.d_small_tris, &c->scene.d_small_poly}) HIPCHK(c, b->ensure(16));
-            HIPCHK(c, c->scene.d_tris.ensure((size_t)nt * sizeof(TriGPU)));
-            if (!c->scene.builder) c->scene.builder.reset(new GpuBvhBuilder());
-            BvhBuildOptions bo = c->host.bvh; if (bo.ploc_radius <= 0) bo.ploc_radius = 16;
-            const std::string e = c->scene.builder->build(c->stream, (const F4*)c->scene.d_objtris.p, (const TriShade*)c->scene.d_shade.p, (const InstGPU*)c->scene.d_insts.p, nt, bo, (TriGPU*)c->scene.d_tris.p, c->scene.build_info);
-            if (!e.empty()) { c->err = e; return RTX_ERR_HIP; }
-            const GpuBuildResult& G = c->scene.build_info;
-            HIPCHK(c, c->scene.d_nodes.ensure((size_t)G.nnodes8 * sizeof(Node8GPU)));
-            HIPCHK(c, hipMemcpyAsync(c->scene.d_nodes.p, c->scene.builder->nodes(), (size_t)G.nnodes8 * sizeof(Node8GPU), hipMemcpyDeviceToDevice, c->stream));
-            c->scene.n_nodes8 = G.nnodes8; c->scene.n_tris8 = G.ntris8; c->scene.dev_built = true; B.bvh_pad = 2e-6f * G.scale;
-            B.level_start8 = G.level_start8; B.stack8 = G.stack8;
-            // the boxes: a FULL refit — world triangles from the object-space ones, every node quantised bottom-up (what a transform-only commit runs)
-            HIPCHK(c, c->scene.d_node_aabb.ensure((size_t)c->scene.n_nodes8 * 32));
-            c->scene.h_one.assign(1, 0x3f800000u);
-            if ((r = upload(c, c->scene.d_scale, c->scene.h_one))) return r;
-            launch_refit(c->stream, (Node8GPU*)c->scene.d_nodes.p, B.level_start8.data(), (uint32_t)B.level_start8.size() - 1, (TriGPU*)c->scene.d_tris.p, c->scene.n_tris8,
-                         (const TriShade*)c->scene.d_shade.p, (const InstGPU*)c->scene.d_insts.p, (const F4*)c->scene.d_objtris.p, (F4*)c->scene.d_node_aabb.p, (uint32_t*)c->scene.d_scale.p, nullptr, nullptr, nullptr);
-            HIPCHK(c, hipGetLastError());
-            TO_HOST(c, &c->scene.root8, c->scene.d_nodes.p, sizeof(Node8GPU));
-            c->scene.node_aabb_valid = true;
-            if (getenv("RTX_BUILD_TIMES")) fprintf(stderr, "[build] GPU: prims %.2f ms, sort %.2f ms, PLOC %.2f ms (%u rounds -> %u clusters), top on the host %.2f ms, layout %.2f ms: %u wide nodes, stack %u\n",
-                                                   G.ms_prims, G.ms_sort, G.ms_ploc, G.ploc_iterations, G.clusters_top, G.ms_top_host, G.ms_layout, G.nnodes8, G.stack8);
+    // On the GPU: a scene that is already resident and not a tiny one (whose pre-test records depend on world positions).
+    bool build = !(c->opt.gpu_refit && gpu_refittable(c) && !c->host.topo_dirty);
+    if (!build) {
+        if ((r = refit_resident(c, deform))) return r;
+        c->scene.cost_now_state = 0;
+        if (deform && c->opt.deform_rebuild >= 2) {
+            double cost[2];
+            if ((r = tree_costs(c, cost))) return r;
+            if (cost[0] * 100.0 > cost[1] * (double)c->opt.deform_rebuild) { c->host.topo_dirty = true; build = true; }
         }
     }
+    if (build) {
+        c->scene.cost_base_state = c->scene.cost_now_state = 0;
+        if ((r = build_and_upload(c))) return r;
+    }
+    c->host.dirty_meshes.clear();
     r = finalise_scene(c);
     if (r == RTX_OK && c->scene.dev_built && c->scene.n_nodes8) {          // the visiting order of any-hit rays, probed on the device (the host probe replays its mirror of the tree)
         uint32_t best = 0;
@@ -235,6 +345,7 @@ int rtx_commit_scene(rtx_ctx* c) {
 int rtx_save_scene_cache(rtx_ctx* c, const char* path) {
     if (!c) return RTX_ERR_INVALID;
     if (!c->committed) { c->err = "save_scene_cache: scene not committed"; return RTX_ERR_STATE; }
+    if (c->scene.host_mirror_stale) { c->err = "save_scene_cache: the per-triangle records were re-derived on the GPU after rtx_update_mesh_vertices and the host holds no current copy; commit with RTX_OPT_DEFORM_REBUILD 1 (host builder) to save a cache"; return RTX_ERR_STATE; }
     if (c->scene.dev_built) { c->err = "save_scene_cache: the tree was built on the GPU (RTX_OPT_GPU_BUILD) and has no host mirror; commit with the host builder to save a cache"; return RTX_ERR_STATE; }
     if (!save_scene_cache(c->host, c->scene.built, path, c->err)) return RTX_ERR_INVALID;
     return RTX_OK;
@@ -243,11 +354,19 @@ int rtx_load_scene_cache(rtx_ctx* c, const char* path) {
     BIND(c);
     if (!load_scene_cache(path, c->host, c->scene.built, c->err)) return RTX_ERR_INVALID;     // on failure the previous scene is untouched
     c->committed = false; c->scene.device_scene_valid = false; c->scene.objtris_uploaded = false; c->scene.node_aabb_valid = false;
+    c->scene.host_mirror_stale = false; c->scene.cost_base_state = c->scene.cost_now_state = 0;
+    c->scene.pool_meshes = 0; c->scene.pool_verts = c->scene.pool_idx = c->scene.pool_matids = 0; c->scene.pool_vert_base.clear(); c->scene.pool_idx_base.clear(); c->scene.pool_dirty.clear();     // (another scene)
     int r = upload_built(c);
     if (r) return r;
     return finalise_scene(c);
 }
 
+static int refresh_wide_nodes(rtx_ctx* c) {        // the one-node-per-line copy follows the nodes (after every build / refit)
+    if (!c->scene.wide_nodes || !c->scene.n_nodes8) return RTX_OK;
+    HIPCHK(c, c->scene.d_nodes_wide.ensure((size_t)c->scene.n_nodes8 * 128));
+    HIPCHK(c, hipMemcpy2DAsync(c->scene.d_nodes_wide.p, 128, c->scene.d_nodes.p, sizeof(Node8GPU), sizeof(Node8GPU), c->scene.n_nodes8, hipMemcpyDeviceToDevice, c->stream));
+    return RTX_OK;
+}
 static int finalise_scene(rtx_ctx* c) {
     BuiltScene& B = c->scene.built;
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -260,11 +379,8 @@ static int finalise_scene(rtx_ctx* c) {
     // bounces >= 1 only — incoherent rays on a tree far larger than L2 gain (street scene, 3.8 M triangles: k_trace_closest -2.4 %), coherent ones (camera rays, ReSTIR's
     // stages) and the any-hit kernel like neighbours sharing lines (+1 %), small trees do not care (profiles/r04_node_stride_ab.md).  128: every traversal fetches the wide copy.
     c->scene.wide_nodes = s.nnodes && (c->opt.node_stride == 128 || (c->opt.node_stride == 0 && (size_t)s.nnodes * sizeof(Node8GPU) > ((size_t)16 << 20)));
-    if (c->scene.wide_nodes) {
-        HIPCHK(c, c->scene.d_nodes_wide.ensure((size_t)s.nnodes * 128));
-        HIPCHK(c, hipMemcpy2DAsync(c->scene.d_nodes_wide.p, 128, c->scene.d_nodes.p, sizeof(Node8GPU), sizeof(Node8GPU), s.nnodes, hipMemcpyDeviceToDevice, c->stream));
-        if (c->opt.node_stride == 128) { s.nodes_f = (const F4*)c->scene.d_nodes_wide.p; s.node_v4 = 8u; }
-    }
+    { const int rw = refresh_wide_nodes(c); if (rw) return rw; }
+    if (c->scene.wide_nodes && c->opt.node_stride == 128) { s.nodes_f = (const F4*)c->scene.d_nodes_wide.p; s.node_v4 = 8u; }
     s.tris = (const TriGPU*)c->scene.d_tris.p; s.ntris = c->scene.n_tris8;
     s.shade = (const TriShade*)c->scene.d_shade.p;
     s.small = (const SmallRecPair*)c->scene.d_small.p; s.small_tris = (const TriGPU*)c->scene.d_small_tris.p; s.small_poly = (const F4*)c->scene.d_small_poly.p; s.small_cm = B.small_cm; s.small_delta = B.small_delta;
@@ -343,3 +459,15 @@ static int finalise_scene(rtx_ctx* c) {
 }
 
 }  // extern "C"
+
+int tree_costs(rtx_ctx* c, double out2[2]) {
+    if (!gpu_refittable(c) || c->host.topo_dirty) { c->err = "tree_cost: this tree is not refitted on the GPU (a tiny scene with pre-test records, or no tree)"; return RTX_ERR_STATE; }
+    int r; bool refitted = false;
+    if ((r = ensure_cost_baseline(c, &refitted))) return r;
+    if (refitted && (r = refresh_wide_nodes(c))) return r;          // (a re-quantised tree: the one-node-per-line copy follows, as after every refit)
+    if (c->scene.cost_base_state == 1) { if ((r = read_tree_cost(c, c->scene.d_cost_base, c->scene.cost_base))) return r; c->scene.cost_base_state = 2; }
+    if (c->scene.cost_now_state == 0) { if ((r = enqueue_tree_cost(c, c->scene.d_cost_now))) return r; c->scene.cost_now_state = 1; }
+    if (c->scene.cost_now_state == 1) { if ((r = read_tree_cost(c, c->scene.d_cost_now, c->scene.cost_now))) return r; c->scene.cost_now_state = 2; }
+    out2[0] = c->scene.cost_now; out2[1] = c->scene.cost_base;
+    return RTX_OK;
+}

@@ -69,6 +69,7 @@ struct rtx_ctx {
         uint32_t merge_rays = 1024;                 // RTX_OPT_MERGE_RAYS
         bool gpu_refit = true;                      // RTX_OPT_GPU_REFIT
         int gpu_build = 0;                          // RTX_OPT_GPU_BUILD
+        int deform_rebuild = 0;                     // RTX_OPT_DEFORM_REBUILD: 0 a vertex-changing commit refits, 1 it rebuilds, N >= 2 it rebuilds once the tree's visit cost exceeds N % of its value after the last build
         uint32_t stack_cap = 11;                    // RTX_OPT_STACK_CAP: traversal-stack entries kept in LDS (0 = all of them)
         int shade_dense = 0;                        // RTX_OPT_SHADE_DENSE
         uint32_t occluder_cache = 0;                // RTX_OPT_OCCLUDER_CACHE
@@ -98,8 +99,13 @@ struct rtx_ctx {
         std::vector<float> h_cdf; std::vector<uint32_t> h_one;     // host sources of small asynchronous uploads
         // the wide tree as the DEVICE holds it (the host mirror B.nodes8 / B.tris8 is empty after a GPU build): counts, the root record (octant-sort grid), who built it
         uint32_t n_nodes8 = 0, n_tris8 = 0; Node8GPU root8{}; bool dev_built = false; std::unique_ptr<GpuBvhBuilder> builder; GpuBuildResult build_info;
-        // RTX_OPT_GPU_BUILD: the meshes as they were handed over, resident on the device (append-only like the host's list: a commit uploads only what was added since the last one),
-        // and the per-instance ranges k_flatten reads (csrc/rtx_build.hip)
+        // the meshes as they were handed over, resident on the device (RTX_OPT_GPU_BUILD: from the first commit; a host-built scene: from its first vertex-changing commit).  A
+        // commit uploads what was added since the last one and overwrites the vertex ranges named in pool_dirty (rtx_update_mesh_vertices); the per-instance ranges k_flatten
+        // reads, and the compacted list of the instances of changed meshes k_reflatten reads (csrc/rtx_build.hip)
+        DevBuf d_work_insts; std::vector<FlatInst> h_work; std::vector<uint32_t> pool_dirty;
+        bool host_mirror_stale = false;                  // B.shade / B.objtris describe the vertices of an earlier commit (the device re-derived its records from the pool): nothing may read them
+        // tree quality (k_tree_cost): per-workgroup partial sums on the device, and their sums once read.  state 0 = not computed for the tree as it is, 1 = enqueued, 2 = read
+        DevBuf d_cost_base, d_cost_now; int cost_base_state = 0, cost_now_state = 0; double cost_base = 0.0, cost_now = 0.0;
         DevBuf d_pool_verts, d_pool_idx, d_pool_matids, d_flat_insts; size_t pool_verts = 0, pool_idx = 0, pool_matids = 0, pool_meshes = 0; std::vector<uint32_t> pool_vert_base, pool_idx_base; std::vector<FlatInst> h_flat;
         DevBuf d_inst_moved, d_tri_dirty, d_node_dirty; bool node_aabb_valid = false;      // partial GPU refit: node_aabb / d_scale hold the last full refit's state
         DevBuf d_objtris, d_node_aabb, d_scale;          // GPU refit: object-space vertices (uploaded on first use), per-node float boxes, max |coordinate|
@@ -183,5 +189,6 @@ int make_frame(rtx_ctx* c, const rtx_params* p, DevFrame& f);
 void block_rect(uint32_t W, uint32_t H, uint32_t ts, uint32_t TX, uint32_t TY, uint32_t gx, uint32_t gy, uint32_t r, uint32_t out[4]);
 // rtx_commit.hip
 void pick_lds_closest(rtx_ctx* c);
+int tree_costs(rtx_ctx* c, double out2[2]);     // {visit cost of the resident tree now, after its last build}; RTX_ERR_STATE for a tree the GPU refit does not handle
 
 #pragma GCC visibility pop

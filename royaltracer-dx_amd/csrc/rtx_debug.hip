@@ -61,6 +61,12 @@ int rtx_debug_tree_hash(rtx_ctx* c, uint64_t out2[2]) {
     out2[0] = fnv(nodes); out2[1] = fnv(tris);
     return RTX_OK;
 }
+int rtx_debug_tree_cost(rtx_ctx* c, double out2[2]) {
+    BIND(c);
+    if (!out2) { c->err = "tree_cost: null array"; return RTX_ERR_INVALID; }
+    if (!c->committed) { c->err = "scene not committed"; return RTX_ERR_STATE; }
+    return tree_costs(c, out2);
+}
 int rtx_debug_read_tree(rtx_ctx* c, int which, void* nodes, uint64_t nodes_bytes, void* tris, uint64_t tris_bytes) {
     BIND(c);
     if (!c->committed) { c->err = "scene not committed"; return RTX_ERR_STATE; }

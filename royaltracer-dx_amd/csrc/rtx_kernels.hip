@@ -1191,6 +1191,26 @@ __global__ __launch_bounds__(kBlock) void k_refit_nodes(Node8GPU* __restrict__ n
     nodes[n] = N;
 }
 
+// Tree quality after refits: the sum over the wide nodes of the half-area of their float box (node_aabb, as the last refit left it).  Divided by the root's half-area that is
+// the expected number of node visits of a random line through the scene — what work_per_ray.node_steps tracks —, so a refitted tree whose boxes have grown to cover their
+// object shows it here.  The value steers a rebuild decision (RTX_OPT_DEFORM_REBUILD), so two runs must give the same bits: a wave reduction in a fixed order, the four wave
+// sums of a workgroup added in wave order, ONE partial per workgroup (a plain store; the host adds them in index order, in double) — no float atomics.  partial[gridDim.x] =
+// the root's half-area.  A workgroup reads node_aabb only: it does not depend on another workgroup of the launch.
+__device__ __forceinline__ float box_half_area(const F4 mn, const F4 mx) {
+    const float ex = mx.x - mn.x, ey = mx.y - mn.y, ez = mx.z - mn.z;
+    return ex * ey + ey * ez + ez * ex;
+}
+__global__ __launch_bounds__(kBlock) void k_tree_cost(const F4* __restrict__ node_aabb, uint32_t nnodes, float* __restrict__ partial) {
+    __shared__ float s_wave[kBlock / 64];
+    const uint32_t n = blockIdx.x * kBlock + threadIdx.x;
+    float a = n < nnodes ? box_half_area(node_aabb[2 * (size_t)n], node_aabb[2 * (size_t)n + 1]) : 0.0f;
+    if (n == 0) partial[gridDim.x] = a;
+    for (int off = 32; off > 0; off >>= 1) a += __shfl_down(a, off, 64);
+    if ((threadIdx.x & 63u) == 0) s_wave[threadIdx.x >> 6] = a;
+    __syncthreads();
+    if (threadIdx.x == 0) { float t = s_wave[0]; for (int w = 1; w < kBlock / 64; w++) t += s_wave[w]; partial[blockIdx.x] = t; }
+}
+
 // ---------------------------------------------------------------------------------------------
 static inline uint32_t grid_for(uint32_t items, uint32_t max_blocks) {
     uint32_t b = (items + kBlock - 1) / kBlock;
@@ -1401,6 +1421,10 @@ void launch_refit(hipStream_t st, Node8GPU* nodes, const uint32_t* level_start, 
         const uint32_t first = level_start[l], count = level_start[l + 1] - first;
         if (count) hipLaunchKernelGGL(k_refit_nodes, dim3((count + kBlock - 1) / kBlock), dim3(kBlock), 0, st, nodes, first, count, tris, node_aabb, scale_bits, (const uint8_t*)tri_dirty, node_dirty);
     }
+}
+uint32_t tree_cost_partials(uint32_t nnodes) { return (nnodes + kBlock - 1) / kBlock + 1u; }
+void launch_tree_cost(hipStream_t st, const F4* node_aabb, uint32_t nnodes, float* partial) {
+    if (nnodes) hipLaunchKernelGGL(k_tree_cost, dim3((nnodes + kBlock - 1) / kBlock), dim3(kBlock), 0, st, node_aabb, nnodes, partial);
 }
 void launch_dbg_trace(hipStream_t st, const DevScene& sc, const F4* rays, uint32_t n, int any, F4* hits) {
     hipLaunchKernelGGL(k_dbg_trace, dim3(grid_for(n, 2048)), dim3(kBlock), trace_lds_bytes(sc), st, sc, sc.small, rays, n, any, hits);

@@ -187,6 +187,9 @@ void launch_unpack_tiles(hipStream_t, uint32_t max_blocks, const DevFrame&, uint
 void launch_refit(hipStream_t, Node8GPU* nodes, const uint32_t* level_start, uint32_t nlevels, TriGPU* tris, uint32_t ntris, const TriShade* shade,
                   const InstGPU* insts, const F4* objtris, F4* node_aabb, uint32_t* scale_bits,
                   const uint32_t* moved = nullptr, uint8_t* tri_dirty = nullptr, uint8_t* node_dirty = nullptr);   // moved != nullptr: PARTIAL refit of the instances flagged in it (node_aabb must hold the previous refit's boxes)
+// tree quality (k_tree_cost): partial[0 .. tree_cost_partials(nnodes) - 2] = per-workgroup sums of the nodes' box half-areas, the last entry = the root's; node_aabb as a refit left it
+uint32_t tree_cost_partials(uint32_t nnodes);
+void launch_tree_cost(hipStream_t, const F4* node_aabb, uint32_t nnodes, float* partial);
 void launch_dbg_trace(hipStream_t, const DevScene&, const F4* rays, uint32_t n, int any, F4* hits);
 void launch_dbg_surface(hipStream_t, const DevScene&, const F4* rays, const F4* hits, uint32_t n, F4* out);
 void launch_dbg_bsdf_eval(hipStream_t, const DevScene&, uint32_t mat, uint32_t flags, const float* in9, uint32_t n, float* out8);

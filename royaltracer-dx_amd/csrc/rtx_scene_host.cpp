@@ -109,6 +109,31 @@ bool SceneHost::set_instance_transform(uint32_t inst, const float* o2w) {
     return true;
 }
 
+bool SceneHost::update_mesh_vertices(uint32_t mesh, const void* verts28, uint32_t nverts) {
+    if (mesh >= meshes.size()) { err = "update_mesh_vertices: unknown mesh"; return false; }
+    if (!verts28) { err = "update_mesh_vertices: null array"; return false; }
+    MeshHost& m = meshes[mesh];
+    if ((size_t)nverts * 7 != m.verts.size()) { err = "update_mesh_vertices: vertex count differs from the mesh's (topology changes need a new mesh)"; return false; }
+    const float* v = (const float*)verts28;
+    for (uint32_t i = 0; i < nverts; i++)
+        if ((uint32_t)v[(size_t)i * 7 + 6] != m.matid_base) { err = "update_mesh_vertices: Vertex.normal.w != materialIDs base offset of this mesh"; return false; }
+    m.verts.assign(v, v + (size_t)nverts * 7);
+    if (!mesh_is_dirty(mesh)) dirty_meshes.push_back(mesh);
+    return true;
+}
+
+bool SceneHost::dirty_mesh_emits() const {
+    const uint32_t nmat = (uint32_t)(mats128.size() / 32);
+    for (uint32_t mesh : dirty_meshes) {
+        const MeshHost& m = meshes[mesh];
+        for (size_t i = 0; i < m.idx.size(); i++) {
+            const uint32_t id = matids[m.matid_base + i];
+            if (id < nmat && mats128[(size_t)id * 32 + 8] + mats128[(size_t)id * 32 + 9] + mats128[(size_t)id * 32 + 10] > 0.0f) return true;
+        }
+    }
+    return false;
+}
+
 void SceneHost::build_lights(BuiltScene& B) const {
     const uint32_t nmat = (uint32_t)(mats128.size() / 32);
     // ---- emissive triangle list + CDF: Renderer.cpp:2123-2233, 2237-2243 ----
@@ -184,10 +209,11 @@ bool SceneHost::refresh_transforms(BuiltScene& B) {
     B.inst_moved.assign(insts.size(), 0u);
     for (size_t ii = 0; ii < insts.size(); ii++) {
         const InstHost& in = insts[ii];
-        B.inst_moved[ii] = memcmp(B.insts[ii].o2w, in.o2w, 64) != 0 ? 1u : 0u;
+        B.inst_moved[ii] = (memcmp(B.insts[ii].o2w, in.o2w, 64) != 0 || mesh_is_dirty(in.mesh)) ? 1u : 0u;      // (new vertices dirty the same triangles and nodes a new matrix does)
         copy_instance(B.insts[ii], in);
     }
-    if (mats_changed) build_lights(B); else refresh_lights(B);       // (new materials can change WHICH triangles emit: full scan)
+    // new materials can change WHICH triangles emit, new vertices of an emitting mesh their areas, hence weights and order: full scan
+    if (mats_changed || dirty_mesh_emits()) build_lights(B); else refresh_lights(B);
     B.refit_count++;
     return true;
 }

@@ -44,7 +44,7 @@ struct BuiltScene {
     float total_weight = 0.0f;
     uint32_t max_depth = 0;
     uint32_t refit_count = 0;           // commits since the last full build that only refitted the boxes
-    std::vector<uint32_t> inst_moved;   // refresh_transforms: 1 = the instance's objectToWorld differs from the last commit's (the GPU refit touches the triangles and nodes of these only)
+    std::vector<uint32_t> inst_moved;   // refresh_transforms: 1 = the instance's objectToWorld differs from the last commit's, or its mesh's vertices do (the GPU refit touches the triangles and nodes of these only)
 };
 
 struct SceneHost {
@@ -55,15 +55,20 @@ struct SceneHost {
     std::string err;
     bool topo_dirty = true;                     // meshes / instances added since the last build (a transform change alone refits)
     bool mats_dirty = true;                     // rtx_set_materials since the material table was last derived
+    std::vector<uint32_t> dirty_meshes;         // rtx_update_mesh_vertices since the last commit: meshes whose vertices changed (topology kept; the commit clears the list)
     BvhBuildOptions bvh = bvh_build_options();  // builder knobs of this scene (rtx_set_option RTX_OPT_BVH_*)
 
     bool set_materials(const void* mats, uint32_t count);
     bool add_mesh(const void* verts28, uint32_t nverts, const uint32_t* idx, uint32_t nidx, const uint32_t* matids, uint32_t* out);
     bool add_instance(uint32_t mesh, const float* o2w, uint32_t* out);
     bool set_instance_transform(uint32_t inst, const float* o2w);
+    // new positions and normals for a mesh whose topology stays (BottomLevelASGenerator.cpp:185-209, updateOnly): same vertex count, same Vertex.normal.w; on failure nothing changes
+    bool update_mesh_vertices(uint32_t mesh, const void* verts28, uint32_t nverts);
+    bool mesh_is_dirty(uint32_t mesh) const { for (uint32_t m : dirty_meshes) if (m == mesh) return true; return false; }
+    bool dirty_mesh_emits() const;              // a dirty mesh carries a triangle that emits under the current material table (the light list then needs the full scan: weights and order depend on areas)
     bool build(BuiltScene& out);                // the host's whole commit: materials, flattening + shade records, lights, the tree (built, or refitted after a transform-only change), its wide form, tiny-scene records, any-hit probe
     void build_materials(BuiltScene& out);      // mats128 -> MatGPU table (clears mats_dirty)
-    // transform-only update of the records the GPU refit does not derive itself: instance matrices and the light list
+    // transform- or vertex-only update of the records the GPU refit does not derive itself: instance matrices and the light list; inst_moved also names the instances of dirty meshes
     bool refresh_transforms(BuiltScene& out);
     void build_lights(BuiltScene& out) const;
     void refresh_lights(BuiltScene& out) const; // the world-space half of the light records from lights80 (transform-only commits)

@@ -190,6 +190,16 @@ void MultiGpuFrame::SetInstanceTransform(uint32_t instance, const float o2w[16])
     m_refitMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
+void MultiGpuFrame::SetMeshVertices(uint32_t mesh, const void* verts28, uint32_t nverts) {
+    const auto t0 = std::chrono::steady_clock::now();
+    RunOnRanks([&](int r) {
+        if (rtx_update_mesh_vertices(m->ctx[r], mesh, verts28, nverts) != RTX_OK || rtx_commit_scene(m->ctx[r]) != RTX_OK)
+            throw std::runtime_error(std::string("MultiGpuFrame::SetMeshVertices: ") + rtx_last_error(m->ctx[r]));
+    });
+    for (size_t r = 0; r < m->ctx.size(); r++) { if (!m->ctx[r]) continue; hipck(hipSetDevice(m_devices[r]), "hipSetDevice"); hipck(hipStreamSynchronize(m->stream[r]), "sync refit"); }
+    m_refitMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
 void MultiGpuFrame::RenderRestir(const rtx_params& p0) {
     const int n = (int)m->ctx.size();
     rtx_params probe = p0; probe.shard_rank = 0; probe.shard_count = (uint32_t)n;

@@ -39,7 +39,9 @@ public:
     // a moving instance (the reference re-sets instance 1 and refits its TLAS every frame: Renderer.cpp:444-452, 594): rtx_set_instance_transform + a transform-only
     // rtx_commit_scene on EVERY rank — the scene is replicated, so every rank refits its own copy of the tree on its GPU (k_refit_tris / k_refit_nodes)
     void SetInstanceTransform(uint32_t instance, const float o2w[16]);
-    double LastRefitMs() const { return m_refitMs; }        // wall time of the last SetInstanceTransform: max over ranks
+    // a deforming mesh: rtx_update_mesh_vertices + the commit on EVERY rank (each refits its own replica of the tree); verts28 = the mesh's vertex count x 28 bytes
+    void SetMeshVertices(uint32_t mesh, const void* verts28, uint32_t nverts);
+    double LastRefitMs() const { return m_refitMs; }        // wall time of the last SetInstanceTransform / SetMeshVertices: max over ranks
     void SetCamera(const float view[16], const float proj[16]);   // every rank (rtx_set_camera keeps the previous matrices for the reprojection)
     void ResetRestir();                                   // forget the ReSTIR history on every rank
     void SetOption(int option, int64_t value);            // rtx_set_option on every rank

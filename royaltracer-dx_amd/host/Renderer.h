@@ -26,6 +26,10 @@ public:
     // m_instances[i].second = ... of the reference's OnUpdate (Renderer.cpp:444-449): the matrix takes effect in the next OnUpdate, which hands it to the context and
     // re-commits — a transform-only commit, i.e. a REFIT of the resident tree on the GPU (the reference refits its TLAS every frame, Renderer.cpp:594, 2091-2121)
     void SetInstanceTransform(UINT instance, const XMMATRIX& objectToWorld);
+    // new vertices for a model whose topology stays (a skinned character, a cloth): taken now, handed to the context in the next OnUpdate (rtx_update_mesh_vertices), whose
+    // commit refits the resident tree — the reference's helper has the door (BottomLevelASGenerator.cpp:185-209, updateOnly), its Renderer never opens it.  Throws
+    // std::invalid_argument for an unknown model, another vertex count or a changed Vertex.normal.w
+    void SetMeshVertices(UINT mesh, const std::vector<Vertex>& vertices);
     double LastRefitMs() const { return m_refitMs; }
 
     void OnInit();      // Renderer.cpp:44-103: camera lookat, load models, build acceleration structures, upload
@@ -57,5 +61,5 @@ private:
     UINT m_currentDisplayLevel = 0;                  // Renderer.h:298
     std::vector<UINT> m_displayLevels = {0, 10, 11, 12, 13, 14, 15, 16, 17, 20, 21, 22, 23, 24, 25, 26, 27, 28};   // Renderer.h:299
     float m_prevView[16]; bool m_havePrev = false;   // m_prevViewMatrix
-    std::vector<UINT> m_movedInstances; double m_refitMs = 0.0;
+    std::vector<UINT> m_movedInstances, m_changedMeshes; double m_refitMs = 0.0;
 };

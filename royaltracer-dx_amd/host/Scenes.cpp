@@ -564,6 +564,18 @@ void SceneViewProj(const Scene& s, float aspect, float view[16], float proj[16])
     memcpy(proj, P.data(), 64);
 }
 
+bool SetSceneMeshVertices(Scene& s, UINT model, const void* verts28, uint32_t nverts, std::string& err) {
+    if (model >= s.models.size()) { err = "set_mesh_vertices: unknown mesh"; return false; }
+    if (!verts28) { err = "set_mesh_vertices: null array"; return false; }
+    SceneModel& m = s.models[model];
+    if (nverts != m.vertices.size()) { err = "set_mesh_vertices: vertex count differs from the mesh's"; return false; }
+    const Vertex* v = (const Vertex*)verts28;
+    for (uint32_t i = 0; i < nverts; i++)
+        if ((uint32_t)v[i].normal_material.w != (uint32_t)m.vertices[i].normal_material.w) { err = "set_mesh_vertices: Vertex.normal.w changed (it is the mesh's base in materialIDs[])"; return false; }
+    m.vertices.assign(v, v + nverts);
+    return true;
+}
+
 int UploadScene(const Scene& s, rtx_ctx* ctx, float aspect) {
     int r;
     if ((r = rtx_set_materials(ctx, s.materials.data(), (uint32_t)s.materials.size()))) return r;

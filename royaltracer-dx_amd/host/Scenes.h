@@ -32,6 +32,9 @@ Scene MakeBistroClass(uint32_t target_tris = 3800000, uint32_t seed = 3800, bool
 // the reference's own startup scene: each file through ObjLoader::loadObjFile, one instance per model,
 // instance 1 rotated 1.57 rad about Y (Renderer.cpp:363-407, 444-449)
 Scene LoadObjScene(const std::vector<std::string>& files, const std::string& mtl_dir);
+// new vertices for a model whose topology stays (the scene-level twin of rtx_update_mesh_vertices, same checks: the model exists, same vertex count, Vertex.normal.w — the
+// model's base in materialIDs[] — unchanged, non-null); false + err leaves the scene as it was
+bool SetSceneMeshVertices(Scene&, UINT model, const void* verts28, uint32_t nverts, std::string& err);
 // rtx_set_materials / rtx_add_mesh / rtx_add_instance / rtx_commit_scene / rtx_set_camera for `aspect`
 int UploadScene(const Scene&, rtx_ctx*, float aspect);
 void SceneViewProj(const Scene&, float aspect, float view[16], float proj[16]);

@@ -98,6 +98,13 @@ int rtxh_scene_set_camera(rtxh_scene* s, const float eye[3], const float center[
     s->s.eye = XMFLOAT3(eye[0], eye[1], eye[2]); s->s.center = XMFLOAT3(center[0], center[1], center[2]); s->s.up = XMFLOAT3(up[0], up[1], up[2]);
     return RTX_OK;
 }
+int rtxh_scene_set_mesh_vertices(rtxh_scene* s, uint32_t mesh, const void* verts28, uint32_t nverts) {
+    if (!s) { g_err = "set_mesh_vertices: null scene"; return RTX_ERR_INVALID; }
+    std::string err;
+    if (!SetSceneMeshVertices(s->s, mesh, verts28, nverts, err)) { g_err = err; return RTX_ERR_INVALID; }
+    s->cache_path.clear();                // (a scene that came from a cache file no longer matches it: it uploads through the arrays from now on)
+    return RTX_OK;
+}
 int rtxh_scene_view_proj(const rtxh_scene* s, float aspect, float view[16], float proj[16]) { SceneViewProj(s->s, aspect, view, proj); return RTX_OK; }
 int rtxh_scene_upload(const rtxh_scene* s, rtx_ctx* c, float aspect) {
     if (s->cache_path.empty()) return UploadScene(s->s, c, aspect);
@@ -336,6 +343,9 @@ rtx_ctx* rtxh_renderer_context(rtxh_renderer* r) { return r->r->Context(); }
 int rtxh_renderer_on_init(rtxh_renderer* r) { return guarded_rc([&] { r->r->OnInit(); }); }
 int rtxh_renderer_on_update(rtxh_renderer* r) { return guarded_rc([&] { r->r->OnUpdate(); }); }
 int rtxh_renderer_set_instance_transform(rtxh_renderer* r, uint32_t instance, const float o2w[16]) { return guarded_rc([&] { XMMATRIX m; memcpy(m.data(), o2w, 64); r->r->SetInstanceTransform(instance, m); }); }
+int rtxh_renderer_set_mesh_vertices(rtxh_renderer* r, uint32_t mesh, const void* verts28, uint32_t nverts) {
+    return guarded_rc([&] { if (!verts28) throw std::invalid_argument("set_mesh_vertices: null array"); const Vertex* v = (const Vertex*)verts28; r->r->SetMeshVertices(mesh, std::vector<Vertex>(v, v + nverts)); });
+}
 int rtxh_renderer_on_render(rtxh_renderer* r) { return guarded_rc([&] { r->r->OnRender(); }); }
 int rtxh_renderer_read_accum(rtxh_renderer* r, float* out, size_t bytes) {
     return guarded_rc([&] { auto v = r->r->ReadAccumulation(); if (bytes < v.size() * 4) throw std::runtime_error("buffer too small"); memcpy(out, v.data(), v.size() * 4); });
