@@ -175,6 +175,10 @@ enum { RTX_OPT_KERNEL_TIMING = 1,    /* 0/1: bracket every launch with hipEvents
        RTX_OPT_STACK_CAP = 39,       /* 11 (default): traversal-stack entries per lane that live in LDS; a tree whose exact stack bound is deeper keeps the rest in per-lane columns in
                                         global memory, so that LDS (the staged top of the tree, workgroups per CU) is sized for what almost every ray needs.  0 = the whole stack in LDS (until round 5).
                                         Never changes a result.  Takes effect with the next rtx_commit_scene */
+       RTX_OPT_SHARED_PRIMARY = 41,  /* 1 (default): fused tiny-scene path without RTX_FLAG_JITTER: all samples of a pixel shoot the same camera ray, so the primary hit and the surface
+                                        there are computed once per pixel and rtx_render call (k_primary_surface) instead of once per sample; raygen only enqueues the hitting paths and
+                                        bounce 0 starts from the pixel's record.  0: every sample traces and reconstructs its own.  Never changes a result.  rays_primary still counts
+                                        one camera ray per sample */
        RTX_OPT_BLOCKS_PER_CU = 12    /* tuning: workgroups (= private sub-queues) per compute unit; default 0 = auto: 40 (tiny scenes) / 32 at full frame size (8 measured 4-7 % slower there: tail imbalance), fewer — down to 8 — when a batch is so
                                         small (a shard) that a sub-queue would start with fewer than ~16 / ~8 chunks of 256 paths */ };
 

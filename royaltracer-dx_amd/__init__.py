@@ -44,6 +44,7 @@ OPT_BVH_REINSERT, OPT_BVH_SPLIT, OPT_ANYHIT_ORDER, OPT_RESTIR_LANE_MIN, OPT_TRAC
 OPT_GPU_BUILD = 38
 OPT_STACK_CAP = 39
 OPT_DEFORM_REBUILD = 40
+OPT_SHARED_PRIMARY = 41
 
 
 class RtxError(RuntimeError):

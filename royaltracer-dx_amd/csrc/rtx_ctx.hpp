@@ -58,6 +58,7 @@ struct rtx_ctx {
         bool small_scene = true;                    // RTX_OPT_SMALL_SCENE
         bool fused = true;                          // RTX_OPT_FUSED_BOUNCE
         bool bounce_ring = true;                    // RTX_OPT_BOUNCE_VARIANT
+        bool shared_primary = true;                 // RTX_OPT_SHARED_PRIMARY
         int stack_private = -1;                     // RTX_OPT_STACK_PRIVATE
         bool lpt_order = true;                      // RTX_OPT_LPT_ORDER: fused kernels take their sub-queues longest first
         bool fused_bvh = false;                     // RTX_OPT_FUSED_BVH: general path = one k_bounce_bvh launch per batch (trace -> shade -> shadow per sub-queue and bounce); measured SLOWER, default off
@@ -120,6 +121,7 @@ struct rtx_ctx {
         DevBuf d_ray_o, d_ray_d, d_thr, d_rad, d_hit, d_sh_o, d_sh_d, d_sh_c, d_queue[2], d_counters;
         DevBuf d_alt_o, d_alt_d, d_alt_thr;              // the second path-state set of the compact state
         DevBuf d_hitmask, d_order, d_pmask;
+        DevBuf d_prim_rec, d_prim_hits;                  // RTX_OPT_SHARED_PRIMARY: the per-pixel primary surface records and per-block hit masks of the current call (k_primary_surface)
         DevBuf d_oct[2], d_perm;                         // RTX_OPT_OCTANT_SORT
         DevBuf d_hitq;                                   // RTX_OPT_FUSED_BVH
         DevBuf d_heads;                                  // RTX_OPT_WORK_STEALING: per trace launch of a batch, G fetch cursors + the retired count

@@ -160,6 +160,79 @@ __global__ __launch_bounds__(kBlock) void k_raygen_trace_small(DevScene sc, cons
     if (threadIdx.x == 0) { qcount[blockIdx.x] = s_n[0]; gencount[blockIdx.x] = s_n[1]; }
 }
 
+// RTX_OPT_SHARED_PRIMARY.  Without RTX_FLAG_JITTER every sample of a pixel shoots the same camera ray, so its hit and the surface reconstructed there depend on the camera,
+// the scene and the pixel only: they are computed ONCE per render call (one wave per 8x8 block, lane = pixel slot, the calls and arguments of k_raygen_trace_small and of the
+// bounce-0 kernel, hence the same bits) and shared by all samples and batches of the call.  Record of slot pl, three streams of f.npl entries:
+//   rec[pl] = (direction.xyz, material id)   rec[npl + pl] = (position.xyz, near_hull)   rec[2 npl + pl] = (normal.xyz, -)     rec[3 npl] = (camera origin, -)
+// hits[blk] = the lanes of block blk whose ray hit something; masks[blk] = the packet-culling mask (k_packet_masks: this kernel takes its place).
+__global__ __launch_bounds__(kBlock) void k_primary_surface(DevScene sc, const SmallRecPair* __restrict__ small, DevFrame f, const CameraGPU* __restrict__ cam_p,
+                                                            unsigned long long* __restrict__ masks, unsigned long long* __restrict__ hits, F4* __restrict__ rec) {
+    extern __shared__ F4 lds[];
+    __shared__ CameraGPU cam;
+    if (threadIdx.x < 64) ((float*)&cam)[threadIdx.x] = ((const float*)cam_p)[threadIdx.x];
+    const TraceLds L = stage_lds(sc, lds);
+    __syncthreads();
+    const uint32_t pl = blockIdx.x * kBlock + threadIdx.x;                       // f.npl is a multiple of 256: every lane owns a slot
+    if (pl >= f.npl) return;
+    uint32_t x0 = 0, y0 = 0, x = 0, y = 0;
+    (void)slot_to_pixel(f, pl & ~63u, x0, y0);                                   // slot 0 of the block = its top-left pixel
+    const unsigned long long keep = packet_keep_mask(sc, cam, f, x0 & ~7u, y0 & ~7u);
+    const bool valid = slot_to_pixel(f, pl, x, y);
+    f3 o = mk3(0, 0, 0), d = mk3(0, 0, 1);
+    if (valid) primary_ray(cam, f.width, f.height, x, y, 0.0f, 0.0f, o, d);
+    float t, u, v; uint32_t prim;
+    traverse_small<false>(sc, small, L, o, d, kTMinCam, valid ? kTMax : 0.0f, t, u, v, prim, sc.nsmall, keep);
+    const bool hit = valid && prim != kMissPrim;
+    const unsigned long long hm = __ballot(hit);
+    if (lane_id() == 0) { masks[pl >> 6] = keep; hits[pl >> 6] = hm; }
+    if (pl == 0) rec[(size_t)3 * f.npl] = {cam.viewI[12], cam.viewI[13], cam.viewI[14], 0.0f};
+    if (hit) {
+        const Surf sf = surface(sc, o, d, t, u, v, prim);
+        rec[pl] = {d.x, d.y, d.z, u2f(sf.mat)};
+        rec[(size_t)f.npl + pl] = {sf.pos.x, sf.pos.y, sf.pos.z, u2f(sf.near_hull ? 1u : 0u)};
+        rec[(size_t)2 * f.npl + pl] = {sf.normal.x, sf.normal.y, sf.normal.z, 0.0f};
+    }
+}
+
+// the raygen of the shared-primary path: the chunk deal of k_raygen_trace_small (so every sub-queue holds the same entries in the same order), no trace and no path state.
+// A hitting path gets its queue entry and one 16-byte record in the place of the hit record: (pixel slot, seed.x, seed.y, -) — all the bounce-0 kernel needs beside the pixel's
+// shared record
+__global__ __launch_bounds__(kBlock) void k_raygen_shared(DevFrame f, DevPaths p, uint32_t* __restrict__ queue, uint32_t* __restrict__ qcount, uint32_t* __restrict__ gencount,
+                                                          const unsigned long long* __restrict__ hits /* k_primary_surface */) {
+    __shared__ uint32_t s_n[2];
+    if (threadIdx.x < 2) s_n[threadIdx.x] = 0;
+    __syncthreads();
+    uint32_t* myq = queue + (size_t)blockIdx.x * f.qcap;
+    const uint32_t nchunks = f.chunks_per_sample * f.batch_spp;
+    uint32_t generated = 0;
+    for (uint32_t k = 0, row0 = 0; row0 < nchunks; k++) {                                  // the deal of k_raygen: even, or tapered rows (taper_row_width)
+        const uint32_t nk = f.taper_levels ? taper_row_width(k, gridDim.x, f.taper_levels) : gridDim.x;
+        uint32_t pos = blockIdx.x;
+        if (f.taper_levels && blockIdx.x < nk) { pos += (k * 2654435761u) % nk; if (pos >= nk) pos -= nk; }
+        const uint32_t c = row0 + pos;
+        row0 += nk;
+        if (blockIdx.x >= nk || c >= nchunks) continue;                                   // wave-uniform
+        const uint32_t sl = c / f.chunks_per_sample, cl = c - sl * f.chunks_per_sample;
+        const uint32_t pl = cl * kBlock + threadIdx.x;
+        const uint32_t pid = sl * f.npl + pl;
+        uint32_t x = 0, y = 0;
+        if (slot_to_pixel(f, pl, x, y)) generated++;
+        const unsigned long long hm = hits[pl >> 6];                                      // wave-uniform; a set bit implies a valid slot
+        const bool hit = ((hm >> (pl & 63u)) & 1ull) != 0ull;
+        if (lane_id() == 0) p.hitmask[pid >> 6] = hm;
+        if (hit) {
+            if (f.max_bounces == 0u) p.rad[pid] = {0.0f, 0.0f, 0.0f, 0.0f};   // otherwise the bounce-0 kernel writes every hit path's radiance slot
+            uint32_t s0, s1; seed_init(x, y, f.sample_first + sl, f.frame_seed, s0, s1);
+            p.hit[pid] = {u2f(pl), u2f(s0), u2f(s1), 0.0f};
+        }
+        const uint32_t slot = block_push(hit, &s_n[0]);
+        if (hit) myq[slot] = pid;
+    }
+    atomicAdd(&s_n[1], generated);
+    __syncthreads();
+    if (threadIdx.x == 0) { qcount[blockIdx.x] = s_n[0]; gencount[blockIdx.x] = s_n[1]; }
+}
+
 // RTX_OPT_TRACE_COUNTERS: a wave adds its lanes' tallies of node steps and triangle tests to two 64-bit counters (one atomic pair per wave, at its exit)
 __device__ __forceinline__ void trace_count_flush(unsigned long long* cnt, uint32_t nodes, uint32_t tris) {
     unsigned long long a = nodes, b = tris;
@@ -530,13 +603,16 @@ __global__ __launch_bounds__(kBlock, RTX_SHADE_WAVES) void k_shade_dense(DevScen
 // stay in registers.  Radiance additions happen in the oracle's order (emissive, then NEE slot 0, 1, ...).
 // LAMBERT: RTX_FLAG_LAMBERT_ONLY is a launch constant, so it is a template parameter too: the Lambert-only instantiation carries no GGX code
 // (fewer live registers, fewer SGPR spills through v_writelane / v_readlane in the loop).
-template <int WAVES, bool HAVE_HIT, bool LAMBERT, bool RING>
+// HAVE_HIT: 0 = bounces >= 1 (the kernel traces its extension rays); bounce 0: 1 = path state and hit record come from k_raygen_trace_small, 2 = RTX_OPT_SHARED_PRIMARY: the
+// path starts from its pixel's shared record (k_primary_surface) and the (pixel slot, seeds) entry of k_raygen_shared — no surface() here, and 32 B read per path instead of 64
+template <int WAVES, int HAVE_HIT, bool LAMBERT, bool RING>
 __global__ __launch_bounds__(kBlock, WAVES) void k_bounce_small(DevScene sc, const SmallRecPair* __restrict__ small, DevFrame f_in, DevPaths p,
                                                          uint32_t bounce_first, uint32_t bounce_end,
                                                          uint32_t* __restrict__ queue_a, uint32_t* __restrict__ queue_b /* bounce b reads (b & 1 ? b : a), writes the other */,
                                                          uint32_t* __restrict__ qrows /* [bounce][gridDim.x] sub-queue lengths entering each bounce */,
                                                          uint32_t* __restrict__ srows /* [bounce][nee][gridDim.x]: shadow rays traced (statistics) */,
-                                                         const uint32_t* __restrict__ order /* workgroup -> sub-queue, longest first (k_order_queues); may be null */) {
+                                                         const uint32_t* __restrict__ order /* workgroup -> sub-queue, longest first (k_order_queues); may be null */,
+                                                         const F4* __restrict__ prim_rec /* HAVE_HIT 2: the per-pixel records of k_primary_surface (read by that instantiation only) */) {
     // BOUNCE RANGE: sub-queues are workgroup-private, so bounce b + 1 of sub-queue q depends on bounce b of the SAME sub-queue only.  One
     // launch therefore runs the bounces [bounce_first, bounce_end) of its sub-queue back to back, with a workgroup barrier in between
     // (workgroup-scope release / acquire: the path state and queue entries a bounce writes are read by the same workgroup).  A frame has
@@ -600,6 +676,7 @@ __global__ __launch_bounds__(kBlock, WAVES) void k_bounce_small(DevScene sc, con
     for (uint32_t bounce = bounce_first; bounce < bounce_end; bounce++) {
     const bool last = (bounce + 1u == f.max_bounces);
     const float tmin = bounce_tmin(bounce);
+    const uint32_t sbounce = HAVE_HIT == 2 ? 0u : bounce;     // what the shading sees: that instantiation is launched for bounce 0 only, so its MIS and Russian-roulette branches fold away
     const uint32_t* myq = ((bounce & 1u) ? queue_b : queue_a) + qb;
     uint32_t* mynext = ((bounce & 1u) ? queue_a : queue_b) + qb;
     if (!HAVE_HIT && RING) { if (threadIdx.x < 3) s_rc[threadIdx.x] = 0; if (threadIdx.x == 3) s_ring[0] = 0; __syncthreads(); }
@@ -610,7 +687,21 @@ __global__ __launch_bounds__(kBlock, WAVES) void k_bounce_small(DevScene sc, con
         float t = 0.0f, u = 0.0f, v = 0.0f; uint32_t prim = kMissPrim;
         bool active;
         PF_MARK(0);
-        if (HAVE_HIT) {                                   // bounce 0: the primary hit comes from k_raygen_trace_small; every queue entry is a hit
+        Surf sf; sf.mat = 0; sf.normal = mk3(0, 0, 1); sf.pos = mk3(0, 0, 0);
+        if (HAVE_HIT == 2) {                              // bounce 0 from the shared record: every queue entry is a hit, its surface is the pixel's
+            const uint32_t i = base + threadIdx.x;
+            active = i < n;
+            if (active) {
+                S.pid = myq[i];
+                const F4 e = p.hit[S.pid];                                     // k_raygen_shared: (pixel slot, seed.x, seed.y, -)
+                const uint32_t pl = f2u(e.x);
+                const F4 r0 = prim_rec[pl], r1 = prim_rec[(size_t)f.npl + pl], r2 = prim_rec[(size_t)2 * f.npl + pl], ro = prim_rec[(size_t)3 * f.npl];
+                S.s0 = f2u(e.y); S.s1 = f2u(e.z);
+                S.o = mk3(ro.x, ro.y, ro.z); S.d = mk3(r0.x, r0.y, r0.z); S.thr = mk3(1.0f, 1.0f, 1.0f); S.prev_pdf = 1.0f;
+                sf.pos = mk3(r1.x, r1.y, r1.z); sf.normal = mk3(r2.x, r2.y, r2.z); sf.mat = f2u(r0.w); sf.near_hull = f2u(r1.w) != 0u;
+                prim = 0u;                                                     // (any id but kMissPrim)
+            }
+        } else if (HAVE_HIT) {                            // bounce 0: the primary hit comes from k_raygen_trace_small; every queue entry is a hit
             const uint32_t i = base + threadIdx.x;
             active = i < n;
             if (active) { S = load_path(p, myq[i]); const F4 h = p.hit[S.pid]; t = h.x; u = h.y; v = h.z; prim = f2u(h.w); }
@@ -650,14 +741,13 @@ __global__ __launch_bounds__(kBlock, WAVES) void k_bounce_small(DevScene sc, con
             if (threadIdx.x == 0) s_ring[0] = head + take;
         }
         PF_MARK(2);
-        Surf sf; sf.mat = 0; sf.normal = mk3(0, 0, 1); sf.pos = mk3(0, 0, 0);
         bool shading = false;
         if (active && prim != kMissPrim) {
             PF_COUNT(3);
-            sf = surface(sc, S.o, S.d, t, u, v, prim);
+            if (HAVE_HIT != 2) sf = surface(sc, S.o, S.d, t, u, v, prim);
             if (sf.mat < sc.nmat) {
                 const MatGPU& m = mats[sf.mat];
-                if (m.Ke_len > 0.0f) add_emissive(sc, p, S, sf, m, bounce, nee, HAVE_HIT);
+                if (m.Ke_len > 0.0f) add_emissive(sc, p, S, sf, m, sbounce, nee, HAVE_HIT != 0);
                 else shading = true;
             } else if (HAVE_HIT) p.rad[S.pid] = {0.0f, 0.0f, 0.0f, 0.0f};
         }
@@ -700,7 +790,7 @@ __global__ __launch_bounds__(kBlock, WAVES) void k_bounce_small(DevScene sc, con
         if (loaded) p.rad[S.pid] = radv;
         bool alive = false;
         f3 smp = mk3(0, 0, 1); float P = 0.0f;
-        if (shading && !last) { PF_COUNT(9); alive = bsdf_continue(*mp, f, bounce, S, normal, outgoing, smp, P, eta_p); }
+        if (shading && !last) { PF_COUNT(9); alive = bsdf_continue(*mp, f, sbounce, S, normal, outgoing, smp, P, eta_p); }
         if (alive) { PF_COUNT(10); store_path(p, S, pos, smp, P); }
         const uint32_t slot = block_push(alive, &s_cnt[0]);
         if (alive) mynext[slot] = S.pid;
@@ -1243,6 +1333,12 @@ void launch_packet_masks(hipStream_t st, const DevScene& sc, const DevFrame& f, 
 void launch_raygen_trace_small(hipStream_t st, const DevScene& sc, const DevFrame& f, const DevPaths& p, const CameraGPU* cam, uint32_t* queue, uint32_t* qcount, uint32_t* gencount, const unsigned long long* masks) {
     hipLaunchKernelGGL(k_raygen_trace_small, dim3(f.nblocks), dim3(kBlock), trace_lds_bytes(sc), st, sc, sc.small, f, p, cam, queue, qcount, gencount, masks);
 }
+void launch_primary_surface(hipStream_t st, const DevScene& sc, const DevFrame& f, const CameraGPU* cam, unsigned long long* masks, unsigned long long* hits, F4* rec) {
+    hipLaunchKernelGGL(k_primary_surface, dim3(f.npl / kBlock), dim3(kBlock), trace_lds_bytes(sc), st, sc, sc.small, f, cam, masks, hits, rec);
+}
+void launch_raygen_shared(hipStream_t st, const DevFrame& f, const DevPaths& p, uint32_t* queue, uint32_t* qcount, uint32_t* gencount, const unsigned long long* hits) {
+    hipLaunchKernelGGL(k_raygen_shared, dim3(f.nblocks), dim3(kBlock), 0, st, f, p, queue, qcount, gencount, hits);
+}
 void launch_trace_closest(hipStream_t st, const DevFrame& f, const DevScene& sc, const DevPaths& p, uint32_t bounce, const uint32_t* queue, const uint32_t* qcount, uint32_t* heads, uint32_t merge) {
     const float tmin = bounce == 0 ? kTMinCam : kSBias;
     if (sc.nsmall) heads = nullptr;                     // (the un-fused tiny-scene test path has no persistent waves)
@@ -1264,14 +1360,15 @@ void launch_trace_closest(hipStream_t st, const DevFrame& f, const DevScene& sc,
 #undef RTX_LAUNCH_TC
 }
 void launch_bounce_small(hipStream_t st, const DevScene& sc, const DevFrame& f, const DevPaths& p, uint32_t bounce_first, uint32_t bounce_end,
-                         uint32_t* queue_a, uint32_t* queue_b, uint32_t* qrows, uint32_t* srows, const uint32_t* order, bool ring) {
+                         uint32_t* queue_a, uint32_t* queue_b, uint32_t* qrows, uint32_t* srows, const uint32_t* order, bool ring, const F4* prim_rec) {
     // general instantiation: 118 VGPRs, 4 waves/SIMD (5 or 6 spill and measured slower); Lambert-only: 85 VGPRs, 5 waves/SIMD (a build for 6 waves, 80 VGPRs
     // with 2 spilled, measured the same: 19.13 vs 19.03 ms).  Bounce 0 (reads the primary hits) is its own instantiation and launch.
     const bool lam = (f.flags & 1u) != 0u, have_hit = bounce_first == 0u;
-#define RTX_LAUNCH_BOUNCE(HH, LL, RR) hipLaunchKernelGGL((k_bounce_small<4, HH, LL, RR>), dim3(f.nblocks), dim3(kBlock), trace_lds_bytes(sc), st, sc, sc.small, f, p, bounce_first, bounce_end, queue_a, queue_b, qrows, srows, order)
-    if (have_hit) { if (lam) RTX_LAUNCH_BOUNCE(true, true, false); else RTX_LAUNCH_BOUNCE(true, false, false); }
-    else if (ring) { if (lam) RTX_LAUNCH_BOUNCE(false, true, true); else RTX_LAUNCH_BOUNCE(false, false, true); }
-    else { if (lam) RTX_LAUNCH_BOUNCE(false, true, false); else RTX_LAUNCH_BOUNCE(false, false, false); }
+#define RTX_LAUNCH_BOUNCE(HH, LL, RR) hipLaunchKernelGGL((k_bounce_small<4, HH, LL, RR>), dim3(f.nblocks), dim3(kBlock), trace_lds_bytes(sc), st, sc, sc.small, f, p, bounce_first, bounce_end, queue_a, queue_b, qrows, srows, order, prim_rec)
+    if (have_hit && prim_rec) { if (lam) RTX_LAUNCH_BOUNCE(2, true, false); else RTX_LAUNCH_BOUNCE(2, false, false); }
+    else if (have_hit) { if (lam) RTX_LAUNCH_BOUNCE(1, true, false); else RTX_LAUNCH_BOUNCE(1, false, false); }
+    else if (ring) { if (lam) RTX_LAUNCH_BOUNCE(0, true, true); else RTX_LAUNCH_BOUNCE(0, false, true); }
+    else { if (lam) RTX_LAUNCH_BOUNCE(0, true, false); else RTX_LAUNCH_BOUNCE(0, false, false); }
 #undef RTX_LAUNCH_BOUNCE
 }
 void launch_bounce_bvh(hipStream_t st, const DevScene& sc, const DevFrame& f, const DevPaths& p, uint32_t bounce_first, uint32_t bounce_end,

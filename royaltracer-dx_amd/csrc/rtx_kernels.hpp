@@ -100,7 +100,7 @@ struct DevPaths {
     F4* ray_d;   // dir.xyz, pdf of the BSDF sample that produced this ray
     F4* thr;     // throughput.xyz, seed.x bits
     F4* rad;     // radiance.xyz, -           (touched only when something is added)
-    F4* hit;     // t, u, v, global triangle id bits
+    F4* hit;     // t, u, v, global triangle id bits   (RTX_OPT_SHARED_PRIMARY, raygen -> bounce 0: pixel slot, seed.x, seed.y bits, -)
     unsigned long long* hitmask;   // fused tiny-scene path: bit (pid & 63) of word pid >> 6 = the primary ray hit something (rad is
                                    // initialised only for those; k_accumulate treats the others as zero).  nullptr: rad is zeroed for all
     // shadow queues: [nee slot j][workgroup b][qcap] entries
@@ -144,8 +144,13 @@ void launch_raygen(hipStream_t, const DevFrame&, const DevPaths&, const CameraGP
 void launch_trace_closest(hipStream_t, const DevFrame&, const DevScene&, const DevPaths&, uint32_t bounce, const uint32_t* queue, const uint32_t* qcount, uint32_t* heads, uint32_t merge = 1);   // merge: consecutive sub-queues per workgroup (MergedQ)
 void launch_packet_masks(hipStream_t, const DevScene&, const DevFrame&, const CameraGPU* cam, unsigned long long* masks);   // one 64-bit record mask per 8x8 pixel block of the shard
 void launch_raygen_trace_small(hipStream_t, const DevScene&, const DevFrame&, const DevPaths&, const CameraGPU* cam, uint32_t* queue, uint32_t* qcount, uint32_t* gencount, const unsigned long long* masks);
+// RTX_OPT_SHARED_PRIMARY: per pixel slot of the shard the primary hit and its surface (rec: 3 npl + 1 entries; hits: one lane mask per 8x8 block; masks as launch_packet_masks, which
+// this launch replaces), then a raygen that only enqueues the hitting paths with their pixel slot and seeds
+void launch_primary_surface(hipStream_t, const DevScene&, const DevFrame&, const CameraGPU* cam, unsigned long long* masks, unsigned long long* hits, F4* rec);
+void launch_raygen_shared(hipStream_t, const DevFrame&, const DevPaths&, uint32_t* queue, uint32_t* qcount, uint32_t* gencount, const unsigned long long* hits);
 void launch_bounce_small(hipStream_t, const DevScene&, const DevFrame&, const DevPaths&, uint32_t bounce_first, uint32_t bounce_end,
-                         uint32_t* queue_a, uint32_t* queue_b, uint32_t* qrows, uint32_t* srows, const uint32_t* order, bool ring = true);   // bounce 0 alone (reads the primary hits), or a range of later bounces; ring: hits go through the LDS ring
+                         uint32_t* queue_a, uint32_t* queue_b, uint32_t* qrows, uint32_t* srows, const uint32_t* order, bool ring = true,
+                         const F4* prim_rec = nullptr);   // bounce 0 alone (reads the primary hits; prim_rec: starts from the records of launch_primary_surface instead), or a range of later bounces; ring: hits go through the LDS ring
 // general (BVH) path: trace -> shade -> shadow of a bounce range for every workgroup-private sub-queue in one launch (hitq: G * qcap indices of scratch)
 void launch_bounce_bvh(hipStream_t, const DevScene&, const DevFrame&, const DevPaths&, uint32_t bounce_first, uint32_t bounce_end,
                        uint32_t* queue_a, uint32_t* queue_b, uint32_t* hitq, uint32_t* qrows, uint32_t* srows, const uint32_t* order);

@@ -56,6 +56,7 @@ BatchPlan plan_batches(const rtx_ctx* c, const rtx_params* p, const DevFrame& f,
 // S(b, j): shadow queue lengths, then one row of paths generated (fused raygen + trace); every workgroup stores its own entry, so nothing needs zeroing per batch
 struct FrameRun {
     DevPaths P; uint32_t* queue[2]; uint32_t* cnt; const CameraGPU* cam; hipStream_t st;
+    const F4* prim_rec;           // RTX_OPT_SHARED_PRIMARY in effect: the per-pixel primary surface records of this call (nullptr: every sample traces its own camera ray)
     uint32_t G, mb, nee, nee1; bool compact, osort, stealing; size_t hstride, nheads;
     uint32_t* Q(uint32_t b) const { return cnt + (size_t)b * G; }
     uint32_t* S(uint32_t b, uint32_t j) const { return cnt + ((size_t)(mb + 1) + (size_t)b * nee1 + j) * G; }
@@ -65,12 +66,13 @@ struct FrameRun {
 int enqueue_tiny_fused(rtx_ctx* c, const FrameRun& R, const DevFrame& fb) {
     const hipStream_t st = R.st;
     uint32_t* gen_row = R.cnt + ((size_t)(R.mb + 1) + (size_t)R.mb * R.nee1) * R.G;
-    { Timed t(c, RTX_K_RAYGEN); launch_raygen_trace_small(st, c->dsc, fb, R.P, R.cam, R.queue[0], R.Q(0), gen_row, (const unsigned long long*)c->pt.d_pmask.p); }
+    if (R.prim_rec) { Timed t(c, RTX_K_RAYGEN); launch_raygen_shared(st, fb, R.P, R.queue[0], R.Q(0), gen_row, (const unsigned long long*)c->pt.d_prim_hits.p); }
+    else { Timed t(c, RTX_K_RAYGEN); launch_raygen_trace_small(st, c->dsc, fb, R.P, R.cam, R.queue[0], R.Q(0), gen_row, (const unsigned long long*)c->pt.d_pmask.p); }
     // dispatch order of the fused bounce kernels: longest sub-queue first, from the lengths after the primary rays (the later
     // bounces keep the ranking: survivors are a near-constant fraction)
     const uint32_t* order = nullptr;
     if (c->opt.lpt_order && R.G > 1) { launch_order_queues(st, R.Q(0), R.G, (uint32_t*)c->pt.d_order.p); order = (const uint32_t*)c->pt.d_order.p; }
-    { Timed t(c, RTX_K_BOUNCE); launch_bounce_small(st, c->dsc, fb, R.P, 0, 1, R.queue[0], R.queue[1], R.Q(0), R.S(0, 0), order); }
+    { Timed t(c, RTX_K_BOUNCE); launch_bounce_small(st, c->dsc, fb, R.P, 0, 1, R.queue[0], R.queue[1], R.Q(0), R.S(0, 0), order, false, R.prim_rec); }
     if (R.mb > 1) { Timed t(c, RTX_K_BOUNCE); launch_bounce_small(st, c->dsc, fb, R.P, 1, R.mb, R.queue[0], R.queue[1], R.Q(0), R.S(0, 0), order, c->opt.bounce_ring); }
     return RTX_OK;
 }
@@ -193,6 +195,10 @@ int rtx_render(rtx_ctx* c, const rtx_params* p) {
     R.nheads = R.stealing ? (size_t)p->max_bounces * (1 + std::max<uint32_t>(nee, 1)) * R.hstride : 0;
     if (R.stealing) HIPCHK(c, c->pt.d_heads.ensure(R.nheads * 4));
     HIPCHK(c, c->pt.d_pmask.ensure(((size_t)f.npl / 64 + 1) * 8));
+    // RTX_OPT_SHARED_PRIMARY: without jitter the camera ray of a pixel is the same for every sample, so the fused tiny-scene path traces and reconstructs it once per call
+    const bool shared_primary = tiny_fused && c->opt.shared_primary && !(p->flags & RTX_FLAG_JITTER);
+    if (shared_primary) { HIPCHK(c, c->pt.d_prim_rec.ensure(((size_t)f.npl * 3 + 1) * 16)); HIPCHK(c, c->pt.d_prim_hits.ensure(((size_t)f.npl / 64 + 1) * 8)); }
+    R.prim_rec = shared_primary ? (const F4*)c->pt.d_prim_rec.p : nullptr;
     const size_t shn = qtot * R.nee1;
     HIPCHK(c, c->pt.d_sh_o.ensure(shn * 16)); HIPCHK(c, c->pt.d_sh_d.ensure(shn * 16)); HIPCHK(c, c->pt.d_sh_c.ensure(shn * 16));
     DevPaths& P = R.P;
@@ -221,7 +227,9 @@ int rtx_render(rtx_ctx* c, const rtx_params* p) {
     struct AuxJoin { rtx_ctx* c; bool armed = true; ~AuxJoin() { if (armed && c->pt.aux) (void)hipStreamSynchronize(c->pt.aux); } } aux_join{c};
     HIPCHK(c, hipEventRecord(c->ev.begin, st));
     HIPCHK(c, hipMemsetAsync(R.cnt, 0, ncnt * 4, st));
-    if (tiny_fused) launch_packet_masks(st, c->dsc, f, R.cam, (unsigned long long*)c->pt.d_pmask.p);   // per 8x8 block, shared by all samples
+    // per 8x8 block resp. per pixel, shared by all samples and batches of this call; recomputed every call (camera, scene, size and shard may all have changed)
+    if (shared_primary) { Timed t(c, RTX_K_RAYGEN); launch_primary_surface(st, c->dsc, f, R.cam, (unsigned long long*)c->pt.d_pmask.p, (unsigned long long*)c->pt.d_prim_hits.p, (F4*)c->pt.d_prim_rec.p); }
+    else if (tiny_fused) launch_packet_masks(st, c->dsc, f, R.cam, (unsigned long long*)c->pt.d_pmask.p);
     for (uint32_t bi = 0; bi < nbatches; bi++) {
         DevFrame fb = f;
         fb.sample_first = p->sample_base + bi * bspp;
