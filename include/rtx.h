@@ -203,6 +203,23 @@ int  rtx_add_instance(rtx_ctx*, uint32_t mesh, const float o2w[16], uint32_t* in
 /* t3 `instanceProps` update (UpdateInstancePropertiesBuffer, Renderer.cpp:2091-2121; prevObjectToWorld := the old matrix);
    needs rtx_commit_scene again, which then only REFITS the BVH boxes (TLAS refit, Renderer.cpp:594) instead of rebuilding */
 int  rtx_set_instance_transform(rtx_ctx*, uint32_t inst, const float o2w[16]);
+/* instanceDescs[i].InstanceMask (TopLevelASGenerator.cpp:198; every TraceRay of the reference passes 0xFF): visible = 0 is mask 0 — the instance exists for no ray, closest
+   hit or any hit, its emissive triangles are no lights (rtx_get_lights, rtx_stats.lights), and every result is bit-identical to the scene without it — while instance ids and
+   global triangle ids stay what they were (hits4, debug layer 14, SampleData.objID, the instance word of a light record; rtx_stats.triangles stays the total).  All or
+   nothing: no per-ray-type masks.  Every instance starts visible; valid before the first commit and on a resident scene.  Like rtx_set_instance_transform it needs
+   rtx_commit_scene again (rendering in between is RTX_ERR_STATE), and on a resident scene that commit is never a rebuild: a REFIT (rtx_stats.bvh_refits + 1) that re-derives
+   the instance's triangles as never-hit records and takes them out of (or puts them back into) the boxes above them, so rays neither hit hidden triangles nor pay for them; it
+   may share the commit with transform changes and vertex updates, of the same instance too.  The tree's topology is always the one built over ALL instances, and hide -> commit
+   -> show -> commit restores the device tree to the bit (rtx_debug_tree_hash).  An unknown instance is RTX_ERR_INVALID and leaves the scene committed and untouched; the
+   value the instance already has is accepted and dirties nothing.  A geometry-changing commit (rtx_add_instance, builder options, RTX_OPT_DEFORM_REBUILD 1) keeps every
+   instance's visibility.  SPAWN POOL: add the objects a scene will ever need up front, hidden, and commit once; showing one later costs a partial refit plus, if it carries
+   emitters, the light scan, where rtx_add_instance costs a rebuild.
+   Paths: the host builder's tree (also RTX_OPT_GPU_REFIT 0, the host refit) gets one full pass of the GPU refit kernels behind its upload while anything is hidden, so hidden
+   triangles are culled from the boxes there too; a tiny scene (<= 64 triangles) with a hidden instance runs on the general BVH path until everything is visible again (its
+   pre-test records are derived from geometry; results are identical by the parity contract).  The ReSTIR history is left alone, as after a vertex update: call
+   rtx_restir_reset for a frame without ghosting.  rtx_save_scene_cache with any hidden instance is RTX_ERR_STATE (the file holds no visibility); a loaded cache has everything
+   visible. */
+int  rtx_set_instance_visible(rtx_ctx*, uint32_t inst, int visible);
 /* New vertex data for a mesh whose topology stays: nverts must equal the mesh's, indices and material ids are kept, Vertex.normal.w must be
    what it was (the mesh's materialIDs base).  Positions AND normals are taken.  Needs rtx_commit_scene again, which then re-derives only the
    triangles of this mesh's instances and refits (BottomLevelASGenerator.cpp:185-209, updateOnly) instead of rebuilding (RTX_OPT_DEFORM_REBUILD).
@@ -306,7 +323,8 @@ int  rtx_debug_trace_stats(rtx_ctx*, const float* rays8, uint32_t n, float* stat
 /* RTX_OPT_TRACE_COUNTERS: node steps / triangle tests of the closest-hit rays and of the any-hit rays traced by the persistent kernels since the last call (which resets them) */
 int  rtx_debug_trace_counters(rtx_ctx*, uint64_t out4[4]);
 /* downloads the resident wide BVH and checks it on the host: 0 = every triangle is in exactly one leaf slot and inside all the
-   decoded boxes above it (what the GPU refit must preserve); > 0 = validator code; < 0 = RTX_ERR_* */
+   decoded boxes above it (what the GPU refit must preserve); > 0 = validator code; < 0 = RTX_ERR_*.  Triangles of hidden instances (rtx_set_instance_visible; e1.w = +inf)
+   must be exactly those of the instances committed as hidden, still sit in their leaf slot, are exempt from containment and must not widen any box */
 int  rtx_debug_validate_bvh(rtx_ctx*);
 /* FNV-1a hashes of the wide tree as the device holds it: out[0] the node records, out[1] the leaf-ordered triangle records — two contexts hold the same tree iff both agree
    (the GPU build against its host twin, a loaded scene cache against the build it was saved from) */

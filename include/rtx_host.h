@@ -112,6 +112,9 @@ int  rtxh_renderer_on_update(rtxh_renderer*);
 /* Renderer::SetInstanceTransform: m_instances[i].second of the reference's OnUpdate (Renderer.cpp:444-449); the next on_update hands the matrix to the context and refits the
    resident tree on the GPU (transform-only rtx_commit_scene; the reference refits its TLAS every frame, Renderer.cpp:594) */
 int  rtxh_renderer_set_instance_transform(rtxh_renderer*, uint32_t instance, const float o2w[16]);
+/* Renderer::SetInstanceVisible: instanceDescs[i].InstanceMask 0 / 0xFF (TopLevelASGenerator.cpp:198); the next on_update hands it to the context (rtx_set_instance_visible)
+   and commits, a refit of the resident tree.  RTX_ERR_INVALID for an unknown instance */
+int  rtxh_renderer_set_instance_visible(rtxh_renderer*, uint32_t instance, int visible);
 /* Renderer::SetMeshVertices: the next on_update hands the vertices to the context (rtx_update_mesh_vertices) and commits — a refit of the resident tree, or what
    RTX_OPT_DEFORM_REBUILD says */
 int  rtxh_renderer_set_mesh_vertices(rtxh_renderer*, uint32_t mesh, const void* verts28, uint32_t nverts);

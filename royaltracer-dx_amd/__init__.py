@@ -101,6 +101,7 @@ _sig("rtx_set_materials", C.c_int, _vp, _vp, _u32)
 _sig("rtx_add_mesh", C.c_int, _vp, _vp, _u32, _vp, _u32, _vp, _u32p)
 _sig("rtx_add_instance", C.c_int, _vp, _u32, _fp, _u32p)
 _sig("rtx_set_instance_transform", C.c_int, _vp, _u32, _fp)
+_sig("rtx_set_instance_visible", C.c_int, _vp, _u32, C.c_int)
 _sig("rtx_update_mesh_vertices", C.c_int, _vp, _u32, _vp, _u32)
 _sig("rtx_commit_scene", C.c_int, _vp)
 _sig("rtx_set_camera", C.c_int, _vp, _fp, _fp)
@@ -211,6 +212,7 @@ _sig("rtxh_renderer_context", _vp, _vp)
 _sig("rtxh_renderer_on_init", C.c_int, _vp)
 _sig("rtxh_renderer_on_update", C.c_int, _vp)
 _sig("rtxh_renderer_set_instance_transform", C.c_int, _vp, _u32, _vp)
+_sig("rtxh_renderer_set_instance_visible", C.c_int, _vp, _u32, C.c_int)
 _sig("rtxh_renderer_on_render", C.c_int, _vp)
 _sig("rtxh_renderer_read_accum", C.c_int, _vp, _vp, C.c_size_t)
 _sig("rtxh_renderer_read_output", C.c_int, _vp, _vp, C.c_size_t)
@@ -519,6 +521,10 @@ class Context:
         m = _f32(o2w).reshape(16)
         self._ck(lib.rtx_set_instance_transform(self._h, inst, _fptr(m)), "rtx_set_instance_transform")
 
+    def set_instance_visible(self, inst, visible):
+        """InstanceMask 0 / 0xFF: a hidden instance exists for no ray and lights nothing, ids stay; the next commit() is a refit, never a rebuild"""
+        self._ck(lib.rtx_set_instance_visible(self._h, int(inst), 1 if visible else 0), "rtx_set_instance_visible")
+
     def update_mesh_vertices(self, mesh, verts):
         """new vertices (n, 7) for a mesh whose topology stays; the next commit() re-derives this mesh's instances and refits (OPT_DEFORM_REBUILD)"""
         v = _f32(verts).reshape(-1, 7)
@@ -787,6 +793,10 @@ class Renderer:
         """Renderer::SetInstanceTransform: takes effect in the next on_update (transform-only commit = GPU refit)"""
         m = _f32(o2w16).reshape(16)
         self._ck(lib.rtxh_renderer_set_instance_transform(self._h, int(instance), _ptr(m)), "SetInstanceTransform")
+
+    def set_instance_visible(self, instance, visible):
+        """Renderer::SetInstanceVisible: takes effect in the next on_update (a refit of the resident tree)"""
+        self._ck(lib.rtxh_renderer_set_instance_visible(self._h, int(instance), 1 if visible else 0), "SetInstanceVisible")
 
     def set_mesh_vertices(self, mesh, verts):
         """Renderer::SetMeshVertices: new vertices (n, 7) for a model whose topology stays; takes effect in the next on_update (vertex-changing commit = re-flatten + refit)"""

@@ -204,6 +204,13 @@ int rtx_set_instance_transform(rtx_ctx* c, uint32_t inst, const float o2w[16]) {
     if (!c->host.set_instance_transform(inst, o2w)) { c->err = c->host.err; return RTX_ERR_INVALID; }
     c->committed = false; return RTX_OK;
 }
+int rtx_set_instance_visible(rtx_ctx* c, uint32_t inst, int visible) {
+    if (!c) return RTX_ERR_INVALID;
+    bool changed = false;
+    if (!c->host.set_instance_visible(inst, visible != 0, &changed)) { c->err = c->host.err; return RTX_ERR_INVALID; }     // (nothing changed: the scene stays committed)
+    if (changed) c->committed = false;                     // the value it already had: nothing to commit
+    return RTX_OK;
+}
 
 int rtx_update_mesh_vertices(rtx_ctx* c, uint32_t mesh, const void* verts28, uint32_t nverts) {
     if (!c) return RTX_ERR_INVALID;

@@ -73,7 +73,10 @@ void leaf_triangles(const std::vector<float>& wtri, const std::vector<uint32_t>&
 bool wide_from_binary(BuiltScene& B, const BvhBuildOptions& opt = bvh_build_options());
 // coverage check of a wide tree on its DECODED boxes (tests, rtx_debug_validate_bvh): 0 = children follow parents, every leaf slot entry order[tri_slots[i]] is a
 // triangle, and every triangle is COVERED: referenced once and inside all boxes above that reference, or — a triangle a spatial split handed to several leaves —
-// each of a fixed set of 28 points on it (corners, edge thirds, interior lattice) lies inside all boxes above one of its references; otherwise a small positive code
+// each of a fixed set of 28 points on it (corners, edge thirds, interior lattice) lies inside all boxes above one of its references; otherwise a small positive code.
+// hidden (optional, one flag per leaf entry; rtx_set_instance_visible): a hidden entry must still sit in exactly one leaf slot but is exempt from containment, and it must
+// not widen any box: a child without visible content is quantised empty (near byte 255, far byte 0 on every axis: code 25 otherwise), every other child's decoded box
+// exceeds the bounds of the visible triangles below it by no more than the leaf padding pad_abs, two steps of the node's byte grid and float rounding (code 26)
 struct CoverCheck {                                         // coverage bookkeeping of the tree validators
     struct Part { uint32_t tri; double b[6]; };
     const std::vector<float>& w; std::vector<uint32_t> refs; std::vector<Part> boxes;
@@ -83,7 +86,7 @@ struct CoverCheck {                                         // coverage bookkeep
     int finish();
 };
 int validate_bvh8(const std::vector<float>& world_tris9, const std::vector<Node8GPU>& nodes, const std::vector<uint32_t>& order,
-                  const std::vector<uint32_t>& tri_slots, uint32_t* max_stack_seen);
+                  const std::vector<uint32_t>& tri_slots, uint32_t* max_stack_seen, const std::vector<uint8_t>* hidden = nullptr, double pad_abs = 0.0);
 
 // ---- rtx_bvh_replay.cpp ----
 // host-side replay of the device traversal on B.nodes8 / B.tris8 (counts for tools/bvh_lab.cpp and the any-hit probe)

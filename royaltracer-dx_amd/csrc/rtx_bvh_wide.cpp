@@ -227,7 +227,7 @@ int CoverCheck::finish() {
 
 // the compressed 8-wide collapse: same coverage properties, checked on the DECODED byte-grid boxes of the wide nodes
 int validate_bvh8(const std::vector<float>& w, const std::vector<Node8GPU>& nodes, const std::vector<uint32_t>& order,
-                  const std::vector<uint32_t>& tri_slots, uint32_t* max_stack_seen) {
+                  const std::vector<uint32_t>& tri_slots, uint32_t* max_stack_seen, const std::vector<uint8_t>* hidden, double pad_abs) {
     const uint32_t ntris = (uint32_t)(w.size() / 9), nrefs = (uint32_t)tri_slots.size();
     if (order.size() != nrefs || nrefs < ntris) return 20;
     struct It { uint32_t node; double mn[3], mx[3]; uint32_t pushes; };
@@ -235,8 +235,37 @@ int validate_bvh8(const std::vector<float>& w, const std::vector<Node8GPU>& node
     if (nodes.empty()) return ntris ? 10 : 0;
     CoverCheck cover(w);
     for (uint32_t s = 0; s < nrefs; s++) { if (tri_slots[s] >= nrefs || order[tri_slots[s]] >= ntris) return 14; cover.count(order[tri_slots[s]]); }
-    std::vector<It> st;
     const double inf = INFINITY;
+    // hidden entries: the bounds of the VISIBLE triangles below every node, bottom-up (children have larger indices than their parent), and the slack a decoded box may have
+    struct VBox { double mn[3], mx[3]; };
+    std::vector<VBox> vis;
+    double slack = 0.0;
+    if (hidden) {
+        if (hidden->size() != nrefs) return 20;
+        double scale = 1.0; for (float c : w) scale = std::max(scale, std::fabs((double)c));
+        slack = pad_abs + 1e-6 * scale;
+        vis.assign(nodes.size(), VBox{{inf, inf, inf}, {-inf, -inf, -inf}});
+        for (size_t n = nodes.size(); n-- > 0;) {
+            const Node8GPU& N = nodes[n];
+            const uint32_t imask = N.e_imask >> 24;
+            uint32_t rank = 0, tri_at = N.tri_base;
+            for (int sl = 0; sl < 8; sl++) {
+                const uint32_t nib = (N.trivalid >> (4 * sl)) & 0xfu;
+                if ((imask >> sl) & 1u) {
+                    const uint32_t c = N.child_base + rank++;
+                    if (c <= n) return 12;
+                    if (c >= nodes.size()) return 13;
+                    for (int a = 0; a < 3; a++) { vis[n].mn[a] = std::min(vis[n].mn[a], vis[c].mn[a]); vis[n].mx[a] = std::max(vis[n].mx[a], vis[c].mx[a]); }
+                } else for (uint32_t k = 0; k < (uint32_t)__builtin_popcount(nib); k++, tri_at++) {
+                    if (tri_at >= nrefs) return 14;
+                    if ((*hidden)[tri_at]) continue;
+                    const float* t = &w[(size_t)order[tri_slots[tri_at]] * 9];
+                    for (int v = 0; v < 3; v++) for (int a = 0; a < 3; a++) { vis[n].mn[a] = std::min(vis[n].mn[a], (double)t[v * 3 + a]); vis[n].mx[a] = std::max(vis[n].mx[a], (double)t[v * 3 + a]); }
+                }
+            }
+        }
+    }
+    std::vector<It> st;
     st.push_back({0u, {-inf, -inf, -inf}, {inf, inf, inf}, 0u});
     uint32_t deepest = 0;
     while (!st.empty()) {
@@ -259,9 +288,25 @@ int validate_bvh8(const std::vector<float>& w, const std::vector<Node8GPU>& node
             if (internal && nib) return 22;
             if (!internal && !nib) continue;
             double mn[3], mx[3];
+            bool quantised_empty = true;
             for (int a = 0; a < 3; a++) {
                 const uint32_t qlo = (N.q[2 * a + (sl >> 2)] >> (8 * (sl & 3))) & 0xffu, qhi = (N.q[2 * (3 + a) + (sl >> 2)] >> (8 * (sl & 3))) & 0xffu;
                 mn[a] = std::max(p[a] + qlo * step[a], it.mn[a]); mx[a] = std::min(p[a] + qhi * step[a], it.mx[a]);
+                quantised_empty = quantised_empty && qlo == 255u && qhi == 0u;
+            }
+            if (hidden) {                                                        // what the child's box may cover: the visible triangles below it
+                VBox need{{inf, inf, inf}, {-inf, -inf, -inf}};
+                if (internal) { const uint32_t c = N.child_base + rank; if (c >= nodes.size()) return 13; need = vis[c]; }
+                else for (uint32_t k = 0, s = tri_at; k < (uint32_t)__builtin_popcount(nib) && s < nrefs; k++, s++) {
+                    if ((*hidden)[s]) continue;
+                    const float* t = &w[(size_t)order[tri_slots[s]] * 9];
+                    for (int v = 0; v < 3; v++) for (int a = 0; a < 3; a++) { need.mn[a] = std::min(need.mn[a], (double)t[v * 3 + a]); need.mx[a] = std::max(need.mx[a], (double)t[v * 3 + a]); }
+                }
+                if (need.mn[0] > need.mx[0]) { if (!quantised_empty) return 25; }
+                else for (int a = 0; a < 3; a++) {
+                    const uint32_t qlo = (N.q[2 * a + (sl >> 2)] >> (8 * (sl & 3))) & 0xffu, qhi = (N.q[2 * (3 + a) + (sl >> 2)] >> (8 * (sl & 3))) & 0xffu;
+                    if (p[a] + qlo * step[a] < need.mn[a] - slack - 2.0 * step[a] || p[a] + qhi * step[a] > need.mx[a] + slack + 2.0 * step[a]) return 26;
+                }
             }
             if (internal) {
                 const uint32_t c = N.child_base + rank++;
@@ -276,6 +321,7 @@ int validate_bvh8(const std::vector<float>& w, const std::vector<Node8GPU>& node
                     if (tri_at >= nrefs) return 14;
                     if (used[tri_at]) return 15;                                 // every leaf entry belongs to one leaf slot
                     used[tri_at] = 1;
+                    if (hidden && (*hidden)[tri_at]) continue;                   // in its slot, exempt from containment: no ray may find it
                     if (int r = cover.add(order[tri_slots[tri_at]], mn, mx)) return r;
                 }
             }

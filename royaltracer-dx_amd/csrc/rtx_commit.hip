@@ -127,6 +127,14 @@ static int reflatten_dirty_meshes(rtx_ctx* c) {
     return RTX_OK;
 }
 
+// instance visibility as committed (BuiltScene::inst_hidden), one word per instance, uploaded like inst_moved.  While nothing is hidden the refit kernels get no array at
+// all: such scenes run exactly the launches, and upload exactly the bytes, they did before visibility existed
+static int upload_hidden(rtx_ctx* c) {
+    const BuiltScene& B = c->scene.built;
+    return B.any_hidden ? upload(c, c->scene.d_inst_hidden, B.inst_hidden) : RTX_OK;
+}
+static const uint32_t* hidden_words(const rtx_ctx* c) { return c->scene.built.any_hidden ? (const uint32_t*)c->scene.d_inst_hidden.p : nullptr; }
+
 // ---- tree quality (k_tree_cost, csrc/rtx_kernels.hip) ----
 static int full_refit(rtx_ctx* c) {              // world triangles from the object-space ones, every node quantised bottom-up, node_aabb filled: what the first transform-only commit after a build runs
     BuiltScene& B = c->scene.built;
@@ -134,8 +142,10 @@ static int full_refit(rtx_ctx* c) {              // world triangles from the obj
     c->scene.h_one.assign(1, 0x3f800000u);                       // scale starts at 1.0 like the host's max(1, |coordinates|)
     int r;
     if ((r = upload(c, c->scene.d_scale, c->scene.h_one))) return r;
+    if ((r = upload_hidden(c))) return r;
     launch_refit(c->stream, (Node8GPU*)c->scene.d_nodes.p, B.level_start8.data(), (uint32_t)B.level_start8.size() - 1, (TriGPU*)c->scene.d_tris.p, c->scene.n_tris8,
-                 (const TriShade*)c->scene.d_shade.p, (const InstGPU*)c->scene.d_insts.p, (const F4*)c->scene.d_objtris.p, (F4*)c->scene.d_node_aabb.p, (uint32_t*)c->scene.d_scale.p, nullptr, nullptr, nullptr);
+                 (const TriShade*)c->scene.d_shade.p, (const InstGPU*)c->scene.d_insts.p, (const F4*)c->scene.d_objtris.p, (F4*)c->scene.d_node_aabb.p, (uint32_t*)c->scene.d_scale.p, nullptr, nullptr, nullptr,
+                 hidden_words(c));
     HIPCHK(c, hipGetLastError());
     c->scene.node_aabb_valid = true;
     return RTX_OK;
@@ -257,10 +267,11 @@ static int refit_resident(rtx_ctx* c, bool deform) {
     const bool partial = c->opt.partial_refit && c->scene.node_aabb_valid && B.inst_moved.size() == B.insts.size() && nmoved < B.insts.size();
     if (!partial) return full_refit(c);
     if ((r = upload(c, c->scene.d_inst_moved, B.inst_moved))) return r;
+    if ((r = upload_hidden(c))) return r;
     HIPCHK(c, c->scene.d_tri_dirty.ensure(c->scene.n_tris8)); HIPCHK(c, c->scene.d_node_dirty.ensure(c->scene.n_nodes8));
     launch_refit(c->stream, (Node8GPU*)c->scene.d_nodes.p, B.level_start8.data(), (uint32_t)B.level_start8.size() - 1, (TriGPU*)c->scene.d_tris.p, c->scene.n_tris8,
                  (const TriShade*)c->scene.d_shade.p, (const InstGPU*)c->scene.d_insts.p, (const F4*)c->scene.d_objtris.p, (F4*)c->scene.d_node_aabb.p, (uint32_t*)c->scene.d_scale.p,
-                 (const uint32_t*)c->scene.d_inst_moved.p, (uint8_t*)c->scene.d_tri_dirty.p, (uint8_t*)c->scene.d_node_dirty.p);
+                 (const uint32_t*)c->scene.d_inst_moved.p, (uint8_t*)c->scene.d_tri_dirty.p, (uint8_t*)c->scene.d_node_dirty.p, hidden_words(c));
     HIPCHK(c, hipGetLastError());
     return RTX_OK;
 }
@@ -275,7 +286,18 @@ static int build_and_upload(rtx_ctx* c) {
     // spatial splits (a host-builder feature); there the host builds as before.
     const bool on_gpu = c->opt.gpu_build && ntri_all > 4096u && c->host.bvh.split_alpha <= 0.0;
     if (!(on_gpu ? c->host.prepare_device_build(B) : c->host.build(B))) { c->err = c->host.err; return RTX_ERR_INVALID; }
-    if (!on_gpu) return upload_built(c);
+    if (!on_gpu) {
+        if ((r = upload_built(c))) return r;
+        // The host builder knows nothing of visibility: its tree, boxes and triangle records are those of all instances.  With a hidden instance — and only then — the
+        // hand-over ends like the GPU build's: ONE full pass of the refit kernels, which writes the never-hit records and takes the hidden triangles out of the boxes.
+        // (This holds for the host refit of RTX_OPT_GPU_REFIT 0 as well, and for a tiny scene, which SceneHost::build sends through the general path while anything is hidden.)
+        if (B.any_hidden && c->scene.n_nodes8 && B.level_start8.size() >= 2) {
+            if ((r = upload_objtris_once(c))) return r;
+            if ((r = full_refit(c))) return r;
+            TO_HOST(c, &c->scene.root8, c->scene.d_nodes.p, sizeof(Node8GPU));
+        }
+        return RTX_OK;
+    }
     const uint32_t nt = B.built_tris;
     if ((r = upload(c, c->scene.d_mats, B.mats))) return r;
     if ((r = upload(c, c->scene.d_insts, B.insts))) return r;
@@ -316,6 +338,12 @@ int rtx_commit_scene(rtx_ctx* c) {
     int r;
     // On the GPU: a scene that is already resident and not a tiny one (whose pre-test records depend on world positions).
     bool build = !(c->opt.gpu_refit && gpu_refittable(c) && !c->host.topo_dirty);
+    // a tiny scene whose last instance was just shown again returns to its pre-test records: a host refit (SceneHost::build derives them from world positions)
+    const BuiltScene& B0 = c->scene.built;
+    if (!build && !c->scene.dev_built && !B0.leaf_order.empty() && B0.leaf_order.size() <= kSmallSceneMaxTris && B0.any_hidden && !c->host.any_hidden()) build = true;
+    bool flipped = false;                                  // a resident scene's visibility differs from the caller's
+    for (size_t ii = 0; ii < c->host.insts.size() && !flipped; ii++) flipped = (ii < B0.inst_hidden.size() && B0.inst_hidden[ii] != 0u) != c->host.is_hidden(ii);
+    const bool probe = build || !flipped;                  // the any-hit order is a property of the tree and the lights' whereabouts: not re-probed because something was hidden or shown
     if (!build) {
         if ((r = refit_resident(c, deform))) return r;
         c->scene.cost_now_state = 0;
@@ -331,7 +359,7 @@ int rtx_commit_scene(rtx_ctx* c) {
     }
     c->host.dirty_meshes.clear();
     r = finalise_scene(c);
-    if (r == RTX_OK && c->scene.dev_built && c->scene.n_nodes8) {          // the visiting order of any-hit rays, probed on the device (the host probe replays its mirror of the tree)
+    if (r == RTX_OK && c->scene.dev_built && c->scene.n_nodes8 && probe) {          // the visiting order of any-hit rays, probed on the device (the host probe replays its mirror of the tree)
         uint32_t best = 0;
         if ((r = probe_anyhit_order_on_device(c, best))) return r;
         c->scene.built.any_order = best;
@@ -346,6 +374,7 @@ int rtx_save_scene_cache(rtx_ctx* c, const char* path) {
     if (!c) return RTX_ERR_INVALID;
     if (!c->committed) { c->err = "save_scene_cache: scene not committed"; return RTX_ERR_STATE; }
     if (c->scene.host_mirror_stale) { c->err = "save_scene_cache: the per-triangle records were re-derived on the GPU after rtx_update_mesh_vertices and the host holds no current copy; commit with RTX_OPT_DEFORM_REBUILD 1 (host builder) to save a cache"; return RTX_ERR_STATE; }
+    if (c->scene.built.any_hidden) { c->err = "save_scene_cache: an instance is hidden (rtx_set_instance_visible): the device's boxes and triangle records leave it out and the file format holds no visibility; show every instance and commit to save a cache"; return RTX_ERR_STATE; }
     if (c->scene.dev_built) { c->err = "save_scene_cache: the tree was built on the GPU (RTX_OPT_GPU_BUILD) and has no host mirror; commit with the host builder to save a cache"; return RTX_ERR_STATE; }
     if (!save_scene_cache(c->host, c->scene.built, path, c->err)) return RTX_ERR_INVALID;
     return RTX_OK;

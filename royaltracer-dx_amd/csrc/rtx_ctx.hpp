@@ -108,6 +108,7 @@ struct rtx_ctx {
         // tree quality (k_tree_cost): per-workgroup partial sums on the device, and their sums once read.  state 0 = not computed for the tree as it is, 1 = enqueued, 2 = read
         DevBuf d_cost_base, d_cost_now; int cost_base_state = 0, cost_now_state = 0; double cost_base = 0.0, cost_now = 0.0;
         DevBuf d_pool_verts, d_pool_idx, d_pool_matids, d_flat_insts; size_t pool_verts = 0, pool_idx = 0, pool_matids = 0, pool_meshes = 0; std::vector<uint32_t> pool_vert_base, pool_idx_base; std::vector<FlatInst> h_flat;
+        DevBuf d_inst_hidden;                            // rtx_set_instance_visible: BuiltScene::inst_hidden for the refit kernels (uploaded only while something is hidden)
         DevBuf d_inst_moved, d_tri_dirty, d_node_dirty; bool node_aabb_valid = false;      // partial GPU refit: node_aabb / d_scale hold the last full refit's state
         DevBuf d_objtris, d_node_aabb, d_scale;          // GPU refit: object-space vertices (uploaded on first use), per-node float boxes, max |coordinate|
         bool device_scene_valid = false, objtris_uploaded = false;

@@ -48,7 +48,20 @@ int rtx_debug_validate_bvh(rtx_ctx* c) {
         const TriGPU& T = tris[i]; ident[i] = (uint32_t)i; gid[i] = f2u(T.v0.w); float* o = &w[(size_t)gid[i] * 9];
         o[0] = T.v0.x; o[1] = T.v0.y; o[2] = T.v0.z; o[3] = T.v0.x + T.e1.x; o[4] = T.v0.y + T.e1.y; o[5] = T.v0.z + T.e1.z; o[6] = T.v0.x + T.e2.x; o[7] = T.v0.y + T.e2.y; o[8] = T.v0.z + T.e2.z;
     }
-    return validate_bvh8(w, nodes, gid, ident, nullptr);
+    // hidden instances (rtx_set_instance_visible): the never-hit marker e1.w = +inf must sit on exactly the triangles of the instances committed as hidden (code 27), and the
+    // hidden triangles may widen no box (validate_bvh8).  The leaf padding is the refit kernels': 2e-6 x the coordinate scale the device holds
+    const BuiltScene& B = c->scene.built;
+    std::vector<uint8_t> hidden(tris.size(), 0); bool any = false;
+    for (size_t i = 0; i < tris.size(); i++) {
+        hidden[i] = tris[i].e1.w == INFINITY ? 1 : 0; any = any || hidden[i];
+        size_t ii = (size_t)(std::upper_bound(c->host.insts.begin(), c->host.insts.end(), gid[i], [](uint32_t v, const InstHost& in) { return v < in.tri_base; }) - c->host.insts.begin());      // one past the last instance starting at or before the triangle
+        const bool want = ii > 0 && ii - 1 < B.inst_hidden.size() && B.inst_hidden[ii - 1] != 0u;
+        if (want != (hidden[i] != 0)) return 27;
+    }
+    if (!any) return validate_bvh8(w, nodes, gid, ident, nullptr);
+    float scale = 1.0f;
+    if (c->scene.node_aabb_valid && c->scene.d_scale.p) { TO_HOST(c, &scale, c->scene.d_scale.p, 4); }
+    return validate_bvh8(w, nodes, gid, ident, nullptr, &hidden, 2e-6 * (double)scale);
 }
 int rtx_debug_tree_hash(rtx_ctx* c, uint64_t out2[2]) {
     BIND(c);

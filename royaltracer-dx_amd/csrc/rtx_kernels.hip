@@ -1182,8 +1182,15 @@ __device__ __forceinline__ float sub_up(float a, float b) { return next_above(a 
 // which leaf entries those were), and k_refit_nodes re-quantises only nodes with a dirty triangle or a dirty child (node_dirty), taking the float box of a clean child
 // from node_aabb, which the previous refit left there.  A frame that moves one small instance of a large scene (the reference's own loop: Renderer.cpp:444-452) then costs
 // the launches, not the scene.  The padding scale only grows in a partial refit (the untouched boxes keep the padding they were built with: still conservative).
+// INSTANCE VISIBILITY (rtx_set_instance_visible): `hidden` != nullptr names the instances that no ray may see.  A triangle of such an instance keeps its true world-space
+// record — same operations, same bits — except e1.w, the determinant floor, which becomes +inf: the first comparison of tri_test / tri_test_flat, |det| > e1.w, then fails for
+// every ray (finite or NaN det), with no instruction added to any traversal kernel.  That record is all correctness rests on; k_refit_nodes below reads the same marker to
+// leave the triangle out of every box, so that rays do not pay for it either.  A hidden triangle does not feed the padding scale.
+// VIS = false is the instantiation of scenes with nothing hidden: the kernels as they were before visibility existed, instruction for instruction.
+template <bool VIS>
 __global__ __launch_bounds__(kBlock) void k_refit_tris(TriGPU* __restrict__ tris, uint32_t ntris, const TriShade* __restrict__ shade, const InstGPU* __restrict__ insts,
-                                                       const F4* __restrict__ objtris, uint32_t* __restrict__ scale_bits, const uint32_t* __restrict__ moved, uint8_t* __restrict__ tri_dirty) {
+                                                       const F4* __restrict__ objtris, uint32_t* __restrict__ scale_bits, const uint32_t* __restrict__ moved, uint8_t* __restrict__ tri_dirty,
+                                                       const uint32_t* __restrict__ hidden) {
     __shared__ uint32_t s_max;
     if (threadIdx.x == 0) s_max = 0;
     __syncthreads();
@@ -1198,16 +1205,22 @@ __global__ __launch_bounds__(kBlock) void k_refit_tris(TriGPU* __restrict__ tris
         const F4 a = objtris[(size_t)g * 3], b = objtris[(size_t)g * 3 + 1], c = objtris[(size_t)g * 3 + 2];
         const f3 w0 = xform_point(M, mk3(a.x, a.y, a.z)), w1 = xform_point(M, mk3(b.x, b.y, b.z)), w2 = xform_point(M, mk3(c.x, c.y, c.z));
         const f3 e1 = w1 - w0, e2 = w2 - w0;
+        const bool hide = VIS && hidden[inst] != 0u;
         tris[s].v0 = {w0.x, w0.y, w0.z, u2f(g)};
-        tris[s].e1 = {e1.x, e1.y, e1.z, tri_det_floor(e1, e2)};        // (as the host build: same operations, same bits)
+        tris[s].e1 = {e1.x, e1.y, e1.z, hide ? __builtin_inff() : tri_det_floor(e1, e2)};        // (as the host build: same operations, same bits; +inf: the never-hit record)
         tris[s].e2 = {e2.x, e2.y, e2.z, 0.0f};
-        amax = fmaxf(fmaxf(fmaxf(fabsf(w0.x), fabsf(w0.y)), fmaxf(fabsf(w0.z), fabsf(w1.x))), fmaxf(fmaxf(fabsf(w1.y), fabsf(w1.z)), fmaxf(fmaxf(fabsf(w2.x), fabsf(w2.y)), fabsf(w2.z))));
+        if (!hide) amax = fmaxf(fmaxf(fmaxf(fabsf(w0.x), fabsf(w0.y)), fmaxf(fabsf(w0.z), fabsf(w1.x))), fmaxf(fmaxf(fabsf(w1.y), fabsf(w1.z)), fmaxf(fmaxf(fabsf(w2.x), fabsf(w2.y)), fabsf(w2.z))));
     }
     atomicMax(&s_max, f2u(amax));                      // non-negative floats order like their bit patterns
     __syncthreads();
     if (threadIdx.x == 0 && s_max) atomicMax(scale_bits, s_max);
 }
 
+// Empty children: a leaf slot none of whose triangles is visible (e1.w == +inf), and an internal child whose subtree holds none (its float box in node_aabb is INVERTED,
+// min = +inf > max = -inf, which is also what a clean child of the partial refit hands up), is left out of the node's box and quantised to near byte 255 / far byte 0 on every
+// axis, an interval the slab test cannot enter.  imask and trivalid keep the topology, so showing the instance again is the same refit.  A node without visible content stores
+// the inverted box and a fixed record (origin 0, unit grid, every child empty); the root may be such a node.
+template <bool VIS>
 __global__ __launch_bounds__(kBlock) void k_refit_nodes(Node8GPU* __restrict__ nodes, uint32_t first, uint32_t count, const TriGPU* __restrict__ tris,
                                                         F4* __restrict__ node_aabb /* 2 per node: min, max */, const uint32_t* __restrict__ scale_bits,
                                                         const uint8_t* __restrict__ tri_dirty, uint8_t* __restrict__ node_dirty) {
@@ -1228,7 +1241,7 @@ __global__ __launch_bounds__(kBlock) void k_refit_nodes(Node8GPU* __restrict__ n
     }
     float cmn[8][3], cmx[8][3];
     float bmn[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()}, bmx[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
-    uint32_t rank = 0, tri_at = N.tri_base, used = 0;
+    uint32_t rank = 0, tri_at = N.tri_base, used = 0, empty = 0;
 #pragma unroll
     for (int sl = 0; sl < 8; sl++) {
         const uint32_t nib = (N.trivalid >> (4 * sl)) & 0xfu;
@@ -1236,22 +1249,28 @@ __global__ __launch_bounds__(kBlock) void k_refit_nodes(Node8GPU* __restrict__ n
         if ((imask >> sl) & 1u) {
             const F4 mn = node_aabb[2 * (size_t)(N.child_base + rank)], mx = node_aabb[2 * (size_t)(N.child_base + rank) + 1];
             rank++;
+            if (VIS && mn.x > mx.x) { empty |= 1u << sl; continue; }   // nothing visible below this child
             cmn[sl][0] = mn.x; cmn[sl][1] = mn.y; cmn[sl][2] = mn.z; cmx[sl][0] = mx.x; cmx[sl][1] = mx.y; cmx[sl][2] = mx.z;
         } else if (nib) {
             float mn[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()}, mx[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
             const uint32_t cnt = (uint32_t)__builtin_popcount(nib);
+            bool visible = false;
             for (uint32_t k = 0; k < cnt; k++, tri_at++) {
                 const TriGPU T = tris[tri_at];
+                if (VIS && T.e1.w == __builtin_inff()) continue;        // a hidden instance's triangle: in its slot, in no box
+                visible = true;
                 const float v[3][3] = {{T.v0.x, T.v0.y, T.v0.z}, {T.v0.x + T.e1.x, T.v0.y + T.e1.y, T.v0.z + T.e1.z}, {T.v0.x + T.e2.x, T.v0.y + T.e2.y, T.v0.z + T.e2.z}};
                 for (int a = 0; a < 3; a++) { mn[a] = fminf(mn[a], fminf(v[0][a], fminf(v[1][a], v[2][a]))); mx[a] = fmaxf(mx[a], fmaxf(v[0][a], fmaxf(v[1][a], v[2][a]))); }
             }
+            if (VIS && !visible) { empty |= 1u << sl; continue; }
             for (int a = 0; a < 3; a++) { cmn[sl][a] = mn[a] - pad; cmx[sl][a] = mx[a] + pad; }
         } else continue;
         used |= 1u << sl;
         for (int a = 0; a < 3; a++) { bmn[a] = fminf(bmn[a], cmn[sl][a]); bmx[a] = fmaxf(bmx[a], cmx[sl][a]); }
     }
+    if (VIS) { node_aabb[2 * (size_t)n] = {bmn[0], bmn[1], bmn[2], 0.0f}; node_aabb[2 * (size_t)n + 1] = {bmx[0], bmx[1], bmx[2], 0.0f}; }      // (!used: inverted, a parent reads it as empty)
     if (!used) { for (int a = 0; a < 3; a++) { bmn[a] = 0.0f; bmx[a] = 0.0f; } }
-    node_aabb[2 * (size_t)n] = {bmn[0], bmn[1], bmn[2], 0.0f}; node_aabb[2 * (size_t)n + 1] = {bmx[0], bmx[1], bmx[2], 0.0f};
+    if (!VIS) { node_aabb[2 * (size_t)n] = {bmn[0], bmn[1], bmn[2], 0.0f}; node_aabb[2 * (size_t)n + 1] = {bmx[0], bmx[1], bmx[2], 0.0f}; }     // (a node without any child: a point, as ever)
     // byte grid: p = box minimum, smallest power of two with 255 steps covering the (upward-rounded) extent
     uint32_t eb[3]; float inv_step[3];
     for (int a = 0; a < 3; a++) {
@@ -1263,6 +1282,7 @@ __global__ __launch_bounds__(kBlock) void k_refit_nodes(Node8GPU* __restrict__ n
             if (e < -120) e = -120;
             if (e > 120) e = 120;                               // (cannot cover; such coordinates are rejected at commit)
         }
+        if (VIS && !used) e = 0;
         eb[a] = (uint32_t)(e + 127); inv_step[a] = u2f((uint32_t)(127 - e) << 23);
     }
     N.px = bmn[0]; N.py = bmn[1]; N.pz = bmn[2];
@@ -1270,6 +1290,7 @@ __global__ __launch_bounds__(kBlock) void k_refit_nodes(Node8GPU* __restrict__ n
     for (int r = 0; r < 12; r++) N.q[r] = 0;
 #pragma unroll
     for (int sl = 0; sl < 8; sl++) {
+        if (VIS && ((empty >> sl) & 1u)) for (int a = 0; a < 3; a++) N.q[2 * a + (sl >> 2)] |= 255u << (8 * (sl & 3));      // near byte 255, far byte 0
         if (!((used >> sl) & 1u)) continue;
         for (int a = 0; a < 3; a++) {
             float qlo = floorf(sub_down(cmn[sl][a], bmn[a]) * inv_step[a]), qhi = ceilf(sub_up(cmx[sl][a], bmn[a]) * inv_step[a]);
@@ -1287,6 +1308,7 @@ __global__ __launch_bounds__(kBlock) void k_refit_nodes(Node8GPU* __restrict__ n
 // sums of a workgroup added in wave order, ONE partial per workgroup (a plain store; the host adds them in index order, in double) — no float atomics.  partial[gridDim.x] =
 // the root's half-area.  A workgroup reads node_aabb only: it does not depend on another workgroup of the launch.
 __device__ __forceinline__ float box_half_area(const F4 mn, const F4 mx) {
+    if (mn.x > mx.x) return 0.0f;                          // a node without visible content (k_refit_nodes): nothing to visit
     const float ex = mx.x - mn.x, ey = mx.y - mn.y, ez = mx.z - mn.z;
     return ex * ey + ey * ez + ez * ex;
 }
@@ -1511,12 +1533,14 @@ void launch_unpack_tiles(hipStream_t st, uint32_t max_blocks, const DevFrame& f,
     hipLaunchKernelGGL(k_unpack_tiles, dim3(grid_for(f.npl * nshards, max_blocks)), dim3(kBlock), 0, st, f, nshards, slabs, accum);
 }
 void launch_refit(hipStream_t st, Node8GPU* nodes, const uint32_t* level_start, uint32_t nlevels, TriGPU* tris, uint32_t ntris, const TriShade* shade,
-                  const InstGPU* insts, const F4* objtris, F4* node_aabb, uint32_t* scale_bits, const uint32_t* moved, uint8_t* tri_dirty, uint8_t* node_dirty) {
+                  const InstGPU* insts, const F4* objtris, F4* node_aabb, uint32_t* scale_bits, const uint32_t* moved, uint8_t* tri_dirty, uint8_t* node_dirty, const uint32_t* hidden) {
     if (!moved) tri_dirty = nullptr;                              // full refit
-    if (ntris) hipLaunchKernelGGL(k_refit_tris, dim3((ntris + kBlock - 1) / kBlock), dim3(kBlock), 0, st, tris, ntris, shade, insts, objtris, scale_bits, moved, tri_dirty);
+    auto refit_tris = hidden ? k_refit_tris<true> : k_refit_tris<false>;
+    auto refit_nodes = hidden ? k_refit_nodes<true> : k_refit_nodes<false>;
+    if (ntris) hipLaunchKernelGGL(refit_tris, dim3((ntris + kBlock - 1) / kBlock), dim3(kBlock), 0, st, tris, ntris, shade, insts, objtris, scale_bits, moved, tri_dirty, hidden);
     for (uint32_t l = nlevels; l-- > 0;) {                       // deepest level first: children are refitted before their parents
         const uint32_t first = level_start[l], count = level_start[l + 1] - first;
-        if (count) hipLaunchKernelGGL(k_refit_nodes, dim3((count + kBlock - 1) / kBlock), dim3(kBlock), 0, st, nodes, first, count, tris, node_aabb, scale_bits, (const uint8_t*)tri_dirty, node_dirty);
+        if (count) hipLaunchKernelGGL(refit_nodes, dim3((count + kBlock - 1) / kBlock), dim3(kBlock), 0, st, nodes, first, count, tris, node_aabb, scale_bits, (const uint8_t*)tri_dirty, node_dirty);
     }
 }
 uint32_t tree_cost_partials(uint32_t nnodes) { return (nnodes + kBlock - 1) / kBlock + 1u; }

@@ -191,7 +191,8 @@ void launch_unpack_tiles(hipStream_t, uint32_t max_blocks, const DevFrame&, uint
 // transform-only commit: re-derive world triangles and re-quantise the wide nodes on the GPU (level_start: host array, nlevels + 1 entries)
 void launch_refit(hipStream_t, Node8GPU* nodes, const uint32_t* level_start, uint32_t nlevels, TriGPU* tris, uint32_t ntris, const TriShade* shade,
                   const InstGPU* insts, const F4* objtris, F4* node_aabb, uint32_t* scale_bits,
-                  const uint32_t* moved = nullptr, uint8_t* tri_dirty = nullptr, uint8_t* node_dirty = nullptr);   // moved != nullptr: PARTIAL refit of the instances flagged in it (node_aabb must hold the previous refit's boxes)
+                  const uint32_t* moved = nullptr, uint8_t* tri_dirty = nullptr, uint8_t* node_dirty = nullptr,    // moved != nullptr: PARTIAL refit of the instances flagged in it (node_aabb must hold the previous refit's boxes)
+                  const uint32_t* hidden = nullptr);   // hidden != nullptr: one word per instance, non-zero = no ray sees it (never-hit triangle records, left out of every box)
 // tree quality (k_tree_cost): partial[0 .. tree_cost_partials(nnodes) - 2] = per-workgroup sums of the nodes' box half-areas, the last entry = the root's; node_aabb as a refit left it
 uint32_t tree_cost_partials(uint32_t nnodes);
 void launch_tree_cost(hipStream_t, const F4* node_aabb, uint32_t nnodes, float* partial);

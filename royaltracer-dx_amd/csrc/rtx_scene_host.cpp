@@ -109,6 +109,17 @@ bool SceneHost::set_instance_transform(uint32_t inst, const float* o2w) {
     return true;
 }
 
+bool SceneHost::set_instance_visible(uint32_t inst, bool visible, bool* changed) {
+    if (inst >= insts.size()) { err = "set_instance_visible: unknown instance"; return false; }
+    *changed = is_hidden(inst) == visible;
+    if (*changed) { if (inst_hidden.size() < insts.size()) inst_hidden.resize(insts.size(), 0); inst_hidden[inst] = visible ? 0 : 1; }
+    return true;
+}
+void SceneHost::commit_visibility(BuiltScene& B) const {
+    B.inst_hidden.assign(insts.size(), 0u); B.any_hidden = false;
+    for (size_t ii = 0; ii < insts.size(); ii++) if (is_hidden(ii)) { B.inst_hidden[ii] = 1u; B.any_hidden = true; }
+}
+
 bool SceneHost::update_mesh_vertices(uint32_t mesh, const void* verts28, uint32_t nverts) {
     if (mesh >= meshes.size()) { err = "update_mesh_vertices: unknown mesh"; return false; }
     if (!verts28) { err = "update_mesh_vertices: null array"; return false; }
@@ -122,17 +133,19 @@ bool SceneHost::update_mesh_vertices(uint32_t mesh, const void* verts28, uint32_
     return true;
 }
 
-bool SceneHost::dirty_mesh_emits() const {
-    const uint32_t nmat = (uint32_t)(mats128.size() / 32);
-    for (uint32_t mesh : dirty_meshes) {
-        const MeshHost& m = meshes[mesh];
-        for (size_t i = 0; i < m.idx.size(); i++) {
-            const uint32_t id = matids[m.matid_base + i];
-            if (id < nmat && mats128[(size_t)id * 32 + 8] + mats128[(size_t)id * 32 + 9] + mats128[(size_t)id * 32 + 10] > 0.0f) return true;
-        }
+static bool mesh_emits(const SceneHost& H, const MeshHost& m) {
+    const uint32_t nmat = (uint32_t)(H.mats128.size() / 32);
+    for (size_t i = 0; i < m.idx.size(); i++) {
+        const uint32_t id = H.matids[m.matid_base + i];
+        if (id < nmat && H.mats128[(size_t)id * 32 + 8] + H.mats128[(size_t)id * 32 + 9] + H.mats128[(size_t)id * 32 + 10] > 0.0f) return true;
     }
     return false;
 }
+bool SceneHost::dirty_mesh_emits() const {
+    for (uint32_t mesh : dirty_meshes) if (mesh_emits(*this, meshes[mesh])) return true;
+    return false;
+}
+bool SceneHost::instance_emits(size_t inst) const { return mesh_emits(*this, meshes[insts[inst].mesh]); }
 
 void SceneHost::build_lights(BuiltScene& B) const {
     const uint32_t nmat = (uint32_t)(mats128.size() / 32);
@@ -140,6 +153,7 @@ void SceneHost::build_lights(BuiltScene& B) const {
     struct Tmp { float w; uint32_t order; uint32_t inst; f3 p0, p1, p2; float em[3]; };
     std::vector<Tmp> tmp;
     for (size_t ii = 0; ii < insts.size(); ii++) {
+        if (is_hidden(ii)) continue;                                 // InstanceMask 0: its emitters are no lights (the list of the scene without the instance, instance ids kept)
         const MeshHost& m = meshes[insts[ii].mesh];
         for (uint32_t t = 0; t < m.idx.size() / 3; t++) {
             uint32_t m0 = matids[m.matid_base + t * 3], m1 = matids[m.matid_base + t * 3 + 1], m2 = matids[m.matid_base + t * 3 + 2];
@@ -207,13 +221,18 @@ bool SceneHost::refresh_transforms(BuiltScene& B) {
     const bool mats_changed = mats_dirty;
     if (mats_dirty) build_materials(B);          // rtx_set_materials since the last commit: new table (the light list below reads the new Ke)
     B.inst_moved.assign(insts.size(), 0u);
+    B.inst_hidden.resize(insts.size(), 0u);
+    bool emitter_flipped = false;
     for (size_t ii = 0; ii < insts.size(); ii++) {
         const InstHost& in = insts[ii];
-        B.inst_moved[ii] = (memcmp(B.insts[ii].o2w, in.o2w, 64) != 0 || mesh_is_dirty(in.mesh)) ? 1u : 0u;      // (new vertices dirty the same triangles and nodes a new matrix does)
+        const bool flipped = (B.inst_hidden[ii] != 0u) != is_hidden(ii);      // a visibility flip re-derives the same triangles and nodes: the never-hit record on or off, the boxes without or with them
+        B.inst_moved[ii] = (memcmp(B.insts[ii].o2w, in.o2w, 64) != 0 || mesh_is_dirty(in.mesh) || flipped) ? 1u : 0u;      // (new vertices dirty the same triangles and nodes a new matrix does)
+        if (flipped && !emitter_flipped && instance_emits(ii)) emitter_flipped = true;
         copy_instance(B.insts[ii], in);
     }
-    // new materials can change WHICH triangles emit, new vertices of an emitting mesh their areas, hence weights and order: full scan
-    if (mats_changed || dirty_mesh_emits()) build_lights(B); else refresh_lights(B);
+    commit_visibility(B);
+    // new materials can change WHICH triangles emit, new vertices of an emitting mesh their areas, hence weights and order, a hidden or shown emitter the list itself: full scan
+    if (mats_changed || dirty_mesh_emits() || emitter_flipped) build_lights(B); else refresh_lights(B);
     B.refit_count++;
     return true;
 }
@@ -244,6 +263,7 @@ static uint32_t number_triangle_ranges(SceneHost& H, BuiltScene& B) {
     for (auto& in : H.insts) { in.tri_base = nt; nt += (uint32_t)(H.meshes[in.mesh].idx.size() / 3); }
     B.insts.resize(H.insts.size());
     for (size_t ii = 0; ii < H.insts.size(); ii++) copy_instance(B.insts[ii], H.insts[ii]);
+    H.commit_visibility(B);                     // a geometry-changing commit keeps every instance's visibility
     return nt;
 }
 
@@ -361,7 +381,10 @@ bool SceneHost::build(BuiltScene& B) {
     leaf_triangles(wtri, B.leaf_order, B.tris);
     if (!wide_from_binary(B, bvh)) { err = "build: BVH collapse failed"; return false; }
     sw.lap("collapse_bvh8");
-    build_small_scene(B, wtri, scale);
+    // a tiny scene with a hidden instance takes the general BVH path until everything is visible again: its pre-test records, merged quads, hull faces and the NEE hull
+    // shortcut are derived from geometry, and a hidden triangle may take part in none of them (identical results by the parity contract)
+    if (B.any_hidden) { B.small_recs.clear(); B.small_tris.clear(); B.small_poly.clear(); B.small_nrec = 0; B.small_nocc = 0; }
+    else build_small_scene(B, wtri, scale);
     sw.lap("tris8 / small scene");
     B.any_order = probe_anyhit_order(B);
     sw.lap("probe");

@@ -44,7 +44,9 @@ struct BuiltScene {
     float total_weight = 0.0f;
     uint32_t max_depth = 0;
     uint32_t refit_count = 0;           // commits since the last full build that only refitted the boxes
-    std::vector<uint32_t> inst_moved;   // refresh_transforms: 1 = the instance's objectToWorld differs from the last commit's, or its mesh's vertices do (the GPU refit touches the triangles and nodes of these only)
+    std::vector<uint32_t> inst_hidden;  // one word per instance, non-zero = hidden, AS COMMITTED: what the resident tree's boxes, the never-hit triangle records and the light list reflect (the refit kernels read it)
+    bool any_hidden = false;            // ... and whether any word of it is set
+    std::vector<uint32_t> inst_moved;   // refresh_transforms: 1 = the instance's objectToWorld differs from the last commit's, or its mesh's vertices do, or its visibility does (the GPU refit touches the triangles and nodes of these only)
 };
 
 struct SceneHost {
@@ -56,12 +58,19 @@ struct SceneHost {
     bool topo_dirty = true;                     // meshes / instances added since the last build (a transform change alone refits)
     bool mats_dirty = true;                     // rtx_set_materials since the material table was last derived
     std::vector<uint32_t> dirty_meshes;         // rtx_update_mesh_vertices since the last commit: meshes whose vertices changed (topology kept; the commit clears the list)
+    std::vector<uint8_t> inst_hidden;           // rtx_set_instance_visible: 1 = hidden, as the caller wants it from the next commit on; shorter than insts = the rest is visible (every instance starts visible)
     BvhBuildOptions bvh = bvh_build_options();  // builder knobs of this scene (rtx_set_option RTX_OPT_BVH_*)
 
     bool set_materials(const void* mats, uint32_t count);
     bool add_mesh(const void* verts28, uint32_t nverts, const uint32_t* idx, uint32_t nidx, const uint32_t* matids, uint32_t* out);
     bool add_instance(uint32_t mesh, const float* o2w, uint32_t* out);
     bool set_instance_transform(uint32_t inst, const float* o2w);
+    // instanceDescs[i].InstanceMask (TopLevelASGenerator.cpp:198): all or nothing.  *changed = the value differs from the one held (false: nothing to commit)
+    bool set_instance_visible(uint32_t inst, bool visible, bool* changed);
+    bool is_hidden(size_t inst) const { return inst < inst_hidden.size() && inst_hidden[inst] != 0; }
+    bool any_hidden() const { for (uint8_t h : inst_hidden) if (h) return true; return false; }
+    void commit_visibility(BuiltScene& out) const;     // out.inst_hidden / any_hidden := the caller's values
+    bool instance_emits(size_t inst) const;     // the instance's mesh carries a triangle that emits under the current material table
     // new positions and normals for a mesh whose topology stays (BottomLevelASGenerator.cpp:185-209, updateOnly): same vertex count, same Vertex.normal.w; on failure nothing changes
     bool update_mesh_vertices(uint32_t mesh, const void* verts28, uint32_t nverts);
     bool mesh_is_dirty(uint32_t mesh) const { for (uint32_t m : dirty_meshes) if (m == mesh) return true; return false; }

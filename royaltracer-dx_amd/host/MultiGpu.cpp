@@ -190,6 +190,16 @@ void MultiGpuFrame::SetInstanceTransform(uint32_t instance, const float o2w[16])
     m_refitMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
+void MultiGpuFrame::SetInstanceVisible(uint32_t instance, bool visible) {
+    const auto t0 = std::chrono::steady_clock::now();
+    RunOnRanks([&](int r) {
+        if (rtx_set_instance_visible(m->ctx[r], instance, visible ? 1 : 0) != RTX_OK || rtx_commit_scene(m->ctx[r]) != RTX_OK)
+            throw std::runtime_error(std::string("MultiGpuFrame::SetInstanceVisible: ") + rtx_last_error(m->ctx[r]));
+    });
+    for (size_t r = 0; r < m->ctx.size(); r++) { if (!m->ctx[r]) continue; hipck(hipSetDevice(m_devices[r]), "hipSetDevice"); hipck(hipStreamSynchronize(m->stream[r]), "sync refit"); }
+    m_refitMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
 void MultiGpuFrame::SetMeshVertices(uint32_t mesh, const void* verts28, uint32_t nverts) {
     const auto t0 = std::chrono::steady_clock::now();
     RunOnRanks([&](int r) {

@@ -41,7 +41,9 @@ public:
     void SetInstanceTransform(uint32_t instance, const float o2w[16]);
     // a deforming mesh: rtx_update_mesh_vertices + the commit on EVERY rank (each refits its own replica of the tree); verts28 = the mesh's vertex count x 28 bytes
     void SetMeshVertices(uint32_t mesh, const void* verts28, uint32_t nverts);
-    double LastRefitMs() const { return m_refitMs; }        // wall time of the last SetInstanceTransform / SetMeshVertices: max over ranks
+    // a hidden or shown instance (InstanceMask 0 / 0xFF, TopLevelASGenerator.cpp:198): rtx_set_instance_visible + the commit, a refit, on EVERY rank
+    void SetInstanceVisible(uint32_t instance, bool visible);
+    double LastRefitMs() const { return m_refitMs; }        // wall time of the last SetInstanceTransform / SetMeshVertices / SetInstanceVisible: max over ranks
     void SetCamera(const float view[16], const float proj[16]);   // every rank (rtx_set_camera keeps the previous matrices for the reprojection)
     void ResetRestir();                                   // forget the ReSTIR history on every rank
     void SetOption(int option, int64_t value);            // rtx_set_option on every rank

@@ -9,6 +9,7 @@ using nv_helpers_dx12::Manipulator;
 // A WEAK reference: the host layer is also linked without the device library, against a fixed list of stand-ins for the C-ABI (the sanitizer runs of the test suite), where
 // this entry point resolves to null; inside librtx_hip.so it is the definition of csrc/rtx_api.hip
 extern "C" int rtx_update_mesh_vertices(rtx_ctx*, uint32_t mesh, const void* verts28, uint32_t nverts) __attribute__((weak));
+extern "C" int rtx_set_instance_visible(rtx_ctx*, uint32_t inst, int visible) __attribute__((weak));
 
 Renderer::Renderer(UINT width, UINT height, std::string name) : m_width(width), m_height(height), m_aspectRatio((float)width / (float)height), m_title(std::move(name)) {
     m_params.width = width; m_params.height = height;
@@ -63,6 +64,15 @@ void Renderer::SetInstanceTransform(UINT instance, const XMMATRIX& objectToWorld
     m_movedInstances.push_back(instance);
 }
 
+void Renderer::SetInstanceVisible(UINT instance, bool visible) {
+    if (instance >= m_scene.instances.size()) throw std::out_of_range("Renderer::SetInstanceVisible: no such instance");
+    m_hidden.resize(m_scene.instances.size(), 0);
+    if ((m_hidden[instance] != 0) == !visible) return;
+    m_hidden[instance] = visible ? 0 : 1;
+    for (UINT i : m_flippedInstances) if (i == instance) return;
+    m_flippedInstances.push_back(instance);
+}
+
 void Renderer::SetMeshVertices(UINT mesh, const std::vector<Vertex>& vertices) {
     std::string err;
     if (!SetSceneMeshVertices(m_scene, mesh, vertices.data(), (uint32_t)vertices.size(), err)) throw std::invalid_argument("Renderer::SetMeshVertices: " + err);
@@ -76,14 +86,16 @@ void Renderer::OnUpdate() {
     // The reference re-sets instance 1 every frame (Renderer.cpp:444-449), rebuilds InstanceProperties (:451, 2091-2121) and refits the TLAS (:594).  Here an instance
     // moves when SetInstanceTransform was called since the last update: its matrix goes to the context (which keeps the old one as prevObjectToWorld for the temporal
     // pass) and ONE transform-only commit refits the resident tree (k_refit_tris / k_refit_nodes).  Nothing moved: nothing to do.  The models SetMeshVertices changed go the
-    // same way, in the same commit.
-    if (!m_movedInstances.empty() || !m_changedMeshes.empty()) {
+    // same way, in the same commit, and so do the instances SetInstanceVisible hid or showed.
+    if (!m_movedInstances.empty() || !m_changedMeshes.empty() || !m_flippedInstances.empty()) {
         const auto t0 = std::chrono::steady_clock::now();
         for (UINT i : m_movedInstances) Check(rtx_set_instance_transform(m_ctx, i, m_scene.instances[i].transform.data()), "rtx_set_instance_transform");
         if (!m_changedMeshes.empty() && !rtx_update_mesh_vertices) throw std::runtime_error("Renderer::OnUpdate: this build has no device library (rtx_update_mesh_vertices)");
         for (UINT i : m_changedMeshes) Check(rtx_update_mesh_vertices(m_ctx, i, m_scene.models[i].vertices.data(), (uint32_t)m_scene.models[i].vertices.size()), "rtx_update_mesh_vertices");
+        if (!m_flippedInstances.empty() && !rtx_set_instance_visible) throw std::runtime_error("Renderer::OnUpdate: this build has no device library (rtx_set_instance_visible)");
+        for (UINT i : m_flippedInstances) Check(rtx_set_instance_visible(m_ctx, i, m_hidden[i] ? 0 : 1), "rtx_set_instance_visible");
         Check(rtx_commit_scene(m_ctx), "rtx_commit_scene");
-        m_movedInstances.clear(); m_changedMeshes.clear();
+        m_movedInstances.clear(); m_changedMeshes.clear(); m_flippedInstances.clear();
         m_refitMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     }
 }

@@ -30,6 +30,9 @@ public:
     // commit refits the resident tree — the reference's helper has the door (BottomLevelASGenerator.cpp:185-209, updateOnly), its Renderer never opens it.  Throws
     // std::invalid_argument for an unknown model, another vertex count or a changed Vertex.normal.w
     void SetMeshVertices(UINT mesh, const std::vector<Vertex>& vertices);
+    // instanceDescs[i].InstanceMask (TopLevelASGenerator.cpp:198) as all or nothing: the instance exists for no ray from the next OnUpdate on (rtx_set_instance_visible), whose
+    // commit refits the resident tree; ids stay.  The value the instance already has changes nothing.  Throws std::out_of_range for an unknown instance
+    void SetInstanceVisible(UINT instance, bool visible);
     double LastRefitMs() const { return m_refitMs; }
 
     void OnInit();      // Renderer.cpp:44-103: camera lookat, load models, build acceleration structures, upload
@@ -62,4 +65,5 @@ private:
     std::vector<UINT> m_displayLevels = {0, 10, 11, 12, 13, 14, 15, 16, 17, 20, 21, 22, 23, 24, 25, 26, 27, 28};   // Renderer.h:299
     float m_prevView[16]; bool m_havePrev = false;   // m_prevViewMatrix
     std::vector<UINT> m_movedInstances, m_changedMeshes; double m_refitMs = 0.0;
+    std::vector<uint8_t> m_hidden; std::vector<UINT> m_flippedInstances;      // visibility per instance as last asked for; the instances whose value changed since the last OnUpdate
 };

@@ -342,6 +342,7 @@ rtx_params* rtxh_renderer_restir_params(rtxh_renderer* r) { return &r->r->Restir
 rtx_ctx* rtxh_renderer_context(rtxh_renderer* r) { return r->r->Context(); }
 int rtxh_renderer_on_init(rtxh_renderer* r) { return guarded_rc([&] { r->r->OnInit(); }); }
 int rtxh_renderer_on_update(rtxh_renderer* r) { return guarded_rc([&] { r->r->OnUpdate(); }); }
+int rtxh_renderer_set_instance_visible(rtxh_renderer* r, uint32_t instance, int visible) { return guarded_rc([&] { r->r->SetInstanceVisible(instance, visible != 0); }); }
 int rtxh_renderer_set_instance_transform(rtxh_renderer* r, uint32_t instance, const float o2w[16]) { return guarded_rc([&] { XMMATRIX m; memcpy(m.data(), o2w, 64); r->r->SetInstanceTransform(instance, m); }); }
 int rtxh_renderer_set_mesh_vertices(rtxh_renderer* r, uint32_t mesh, const void* verts28, uint32_t nverts) {
     return guarded_rc([&] { if (!verts28) throw std::invalid_argument("set_mesh_vertices: null array"); const Vertex* v = (const Vertex*)verts28; r->r->SetMeshVertices(mesh, std::vector<Vertex>(v, v + nverts)); });

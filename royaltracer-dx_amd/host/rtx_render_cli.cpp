@@ -10,9 +10,12 @@
 //                   [--orbit deg] moves the camera about the look-at point between frames (exercises the reprojection)
 //                   [--spin deg] turns instance 1 (the reference's moving instance, Renderer.cpp:444-449) by `deg` about the vertical axis before every frame after the first: a
 //                   transform-only commit = a refit of the resident tree on the GPU, on every rank with --gpus N (the reference refits its TLAS every frame, Renderer.cpp:594)
+//                   [--hide i[,j...]] hides the listed instances before the first frame (rtx_set_instance_visible: InstanceMask 0, TopLevelASGenerator.cpp:198)
+//                   [--blink i] toggles the visibility of instance i before every frame after the first and prints the commit's time: a refit, never a rebuild
 //                   [--only-rank r] with --gpus N --gather copy: rank r of N alone, through the same host path (measurement on one GPU: tools/shard_time.py native=1)
 //                   [--gpus N [--devices 0,1,..] [--gather rccl|copy]]   the native N-GPU frame (MultiGpu.h): one process, N contexts, pixel tiles
 //                   round-robin, ONE RCCL all-gather per frame; `--gather copy` replaces the collective by device copies (several ranks on one GPU: tests)
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cmath>
@@ -29,12 +32,14 @@ int main(int argc, char** argv) {
     std::string scene = "cornell", out, objs, mtl = "./";
     UINT w = 1920, h = 1080, spp = 1, frames = 1, bounces = 8, nee = 1; int device = 0; bool lambert = false;
     int gpus = 1; std::string devlist, gather = "rccl", mode = "pt"; bool literal = false, nee_set = false, bounces_set = false, force_gather = false; float orbit = 0.0f, spin = 0.0f; int only_rank = -1; UINT halo = 0;
+    std::vector<UINT> hide; int blink = -1;
     for (int i = 1; i < argc; i++) {
         auto arg = [&](const char* k) { return !strcmp(argv[i], k) && i + 1 < argc; };
         if (arg("--scene")) scene = argv[++i]; else if (arg("--obj")) { objs = argv[++i]; scene = "obj"; } else if (arg("--mtl")) mtl = argv[++i];
         else if (arg("--w")) w = atoi(argv[++i]); else if (arg("--h")) h = atoi(argv[++i]); else if (arg("--spp")) spp = atoi(argv[++i]);
         else if (arg("--frames")) frames = atoi(argv[++i]); else if (arg("--bounces")) { bounces = atoi(argv[++i]); bounces_set = true; } else if (arg("--nee")) { nee = atoi(argv[++i]); nee_set = true; }
         else if (arg("--mode")) mode = argv[++i]; else if (arg("--orbit")) orbit = (float)atof(argv[++i]); else if (arg("--spin")) spin = (float)atof(argv[++i]); else if (arg("--only-rank")) only_rank = atoi(argv[++i]); else if (!strcmp(argv[i], "--literal")) literal = true; else if (!strcmp(argv[i], "--force-gather")) force_gather = true;
+        else if (arg("--hide")) { std::stringstream ss(argv[++i]); std::string t; while (std::getline(ss, t, ',')) hide.push_back((UINT)atoi(t.c_str())); } else if (arg("--blink")) blink = atoi(argv[++i]);
         else if (arg("--halo")) halo = (UINT)atoi(argv[++i]); else if (arg("--gpus")) gpus = atoi(argv[++i]); else if (arg("--devices")) devlist = argv[++i]; else if (arg("--gather")) gather = argv[++i];
         else if (arg("--out")) out = argv[++i]; else if (arg("--device")) device = atoi(argv[++i]); else if (!strcmp(argv[i], "--lambert")) lambert = true;
         else { fprintf(stderr, "unknown argument %s\n", argv[i]); return 2; }
@@ -66,6 +71,8 @@ int main(int argc, char** argv) {
             MultiGpuFrame mg(devs, gather == "copy" ? MultiGpuFrame::Gather::COPY : MultiGpuFrame::Gather::RCCL, force_gather, only_rank);      // --force-gather: the collective also with one rank
             mg.SetScene(sc, (float)w / (float)h);
             mg.Clear(w, h);
+            for (UINT i : hide) mg.SetInstanceVisible(i, false);
+            bool blink_hidden = blink >= 0 && std::find(hide.begin(), hide.end(), (UINT)blink) != hide.end();
             rtx_params p{}; p.width = w; p.height = h; p.spp = spp; p.max_bounces = bounces; p.nee_samples = nee; p.rr_start = 3;
             p.tile_size = gpus > 1 ? 32 : 64;      // round-robin deal: 32-px tiles even out the background across 8 ranks (max / mean 1.04 instead of 1.15, tools/shard_time.py)
             p.flags = lambert ? RTX_FLAG_LAMBERT_ONLY : (scene == "bistro" ? RTX_FLAG_TRANSMISSION : 0);
@@ -75,6 +82,7 @@ int main(int argc, char** argv) {
             for (UINT f = 0; f < frames; f++) {
                 p.sample_base = 1 + f * spp; p.frame_seed = f + 1;
                 if (spin != 0.0f && f > 0) { mg.SetInstanceTransform(1, spun(sc, f).data()); if (!restir) mg.Clear(w, h); printf("refit on %d ranks: %.3f ms\n", gpus, mg.LastRefitMs()); }
+                if (blink >= 0 && f > 0) { blink_hidden = !blink_hidden; mg.SetInstanceVisible((uint32_t)blink, !blink_hidden); if (!restir) mg.Clear(w, h); printf("visibility commit on %d ranks: %.3f ms\n", gpus, mg.LastRefitMs()); }
                 if (restir) {
                     nv_helpers_dx12::Manipulator cam; cam.setLookat(orbit_eye(sc, f), sc.center, sc.up);
                     XMMATRIX proj = XMMatrixPerspectiveFovRH(sc.fovY_deg * XM_PI / 180.0f, (float)w / (float)h, sc.zn, sc.zf);
@@ -109,6 +117,8 @@ int main(int argc, char** argv) {
         }
         r.OnInit();
         if (restir && rtx_set_option(r.Context(), RTX_OPT_RESTIR_WAVEFRONT, literal ? 0 : 1) != RTX_OK) throw std::runtime_error(rtx_last_error(r.Context()));
+        for (UINT i : hide) r.SetInstanceVisible(i, false);
+        bool blink_hidden = blink >= 0 && std::find(hide.begin(), hide.end(), (UINT)blink) != hide.end();
         XMFLOAT3 eye0, ctr0, up0; nv_helpers_dx12::CameraManip.getLookat(eye0, ctr0, up0);
         Scene inst0; bool have_inst0 = false;
         for (UINT f = 0; f < frames; f++) {
@@ -119,7 +129,10 @@ int main(int argc, char** argv) {
                 if (!restir) rtx_clear_accum(r.Context(), w, h);               // a moved scene restarts the progressive accumulation (the ReSTIR frame reprojects instead)
             }
             if (orbit != 0.0f) { Scene tmp; tmp.eye = eye0; tmp.center = ctr0; tmp.up = up0; nv_helpers_dx12::CameraManip.setLookat(orbit_eye(tmp, f), ctr0, up0); }
+            const bool blinked = blink >= 0 && f > 0;
+            if (blinked) { blink_hidden = !blink_hidden; r.SetInstanceVisible((UINT)blink, !blink_hidden); if (!restir) rtx_clear_accum(r.Context(), w, h); }
             r.OnUpdate(); r.Params().sample_base = 1 + f * spp; r.OnRender();
+            if (blinked) printf("visibility commit: %.3f ms\n", r.LastRefitMs());
             rtx_stats s = r.Stats();
             double rays = (double)(s.rays_primary + s.rays_extension + s.rays_shadow);
             printf("frame %u: %.3f ms, %.1f Mrays/s (primary %llu, extension %llu, shadow %llu)\n", f, s.render_ms, rays / (s.render_ms * 1e3),
