@@ -1,5 +1,5 @@
 // rtx_api.hip — the C-ABI of include/rtx.h: the context, its options and stream, scene inputs, camera, accumulation, image reads, statistics, the shard tiling.
-// Host code only (kernels are in rtx_kernels.hip).  No CPU rendering path exists here by design.  The context and the other parts of the C-ABI: rtx_ctx.hpp.
+// Host code only (kernels: the headers rtx_kernels.hip includes, and rtx_refit.hip).  No CPU rendering path exists here by design.  The context and the other parts of the C-ABI: rtx_ctx.hpp.
 #include "rtx_ctx.hpp"
 
 thread_local std::string g_create_err;

@@ -135,7 +135,7 @@ static int upload_hidden(rtx_ctx* c) {
 }
 static const uint32_t* hidden_words(const rtx_ctx* c) { return c->scene.built.any_hidden ? (const uint32_t*)c->scene.d_inst_hidden.p : nullptr; }
 
-// ---- tree quality (k_tree_cost, csrc/rtx_kernels.hip) ----
+// ---- tree quality (k_tree_cost, csrc/rtx_refit.hip) ----
 static int full_refit(rtx_ctx* c) {              // world triangles from the object-space ones, every node quantised bottom-up, node_aabb filled: what the first transform-only commit after a build runs
     BuiltScene& B = c->scene.built;
     HIPCHK(c, c->scene.d_node_aabb.ensure((size_t)c->scene.n_nodes8 * 32));

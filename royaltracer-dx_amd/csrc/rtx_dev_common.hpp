@@ -1,5 +1,5 @@
 // rtx_dev_common.hpp — device-side helpers shared by all kernels: block size, wave helpers, sub-queue compaction, path slot -> pixel, primary ray
-// (included by rtx_kernels.hip only; see its header comment for the overall design)
+// (included by the kernel headers of rtx_kernels.hip — see its header comment for the overall design — and, for kBlock, by rtx_refit.hip)
 #pragma once
 #include "rtx_kernels.hpp"
 
@@ -54,6 +54,25 @@ __device__ __forceinline__ void primary_ray(const CameraGPU& cam, uint32_t W, ui
     f3 tg = mk3(P[0] * dx + P[4] * ndy + P[8] + P[12], P[1] * dx + P[5] * ndy + P[9] + P[13], P[2] * dx + P[6] * ndy + P[10] + P[14]);
     d = normalize(xform_dir(Vi, tg));
     o = mk3(Vi[12], Vi[13], Vi[14]);
+}
+
+// the camera in LDS: every kernel that shoots primary rays copies the 64 floats once per workgroup (the caller owns the __shared__ object and the barrier)
+static_assert(sizeof(CameraGPU) == 64 * sizeof(float), "stage_camera copies one float per lane of the first wave");
+__device__ __forceinline__ void stage_camera(CameraGPU& cam, const CameraGPU* __restrict__ cam_p) {
+    if (threadIdx.x < 64) ((float*)&cam)[threadIdx.x] = ((const float*)cam_p)[threadIdx.x];
+}
+
+// THE CHUNK DEAL of the raygen kernels, one row of it: a kernel walks the rows k = 0, 1, ... with `for (uint32_t k = 0, row0 = 0, c; row0 < nchunks; k++)`, nchunks =
+// f.chunks_per_sample * f.batch_spp; this returns whether row k holds a chunk for this workgroup's sub-queue, and which (c), and advances row0.  Chunk c = 256 consecutive path
+// slots of ONE sample; chunks are dealt round-robin to workgroups so that every workgroup's sub-queue holds a representative sample of the image (load balance across bounces).
+// Even deal: chunks b, b + G, b + 2 G, ...; tapered deal (f.taper_levels > 0): row k hands chunks row0 .. row0 + n_k - 1 to the sub-queues 0 .. n_k - 1 (taper_row_width).
+__device__ __forceinline__ bool dealt_chunk(const DevFrame& f, uint32_t k, uint32_t& row0, uint32_t nchunks, uint32_t& c) {
+    const uint32_t nk = f.taper_levels ? taper_row_width(k, gridDim.x, f.taper_levels) : gridDim.x;
+    uint32_t pos = blockIdx.x;
+    if (f.taper_levels && blockIdx.x < nk) { pos += (k * 2654435761u) % nk; if (pos >= nk) pos -= nk; }      // rotate the row: every sub-queue sees every part of the image over its rows
+    c = row0 + pos;
+    row0 += nk;
+    return !(blockIdx.x >= nk || c >= nchunks);                                           // wave-uniform
 }
 
 }  // namespace rtx

@@ -1,0 +1,82 @@
+// rtx_k_dbg.hpp — kernel-level debug probes of the parity tests
+// One of the kernel headers of rtx_kernels.hip, the path tracer's single translation unit (see its header comment for the design and for why).
+#pragma once
+#include "rtx_shade.hpp"
+
+namespace rtx {
+
+// ---------------------------------------------------------------------------------------------
+// kernel-level debug entry points (parity tests): same device functions as the render loop
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void k_dbg_trace(DevScene sc, const SmallRecPair* __restrict__ small, const F4* __restrict__ rays, uint32_t n, int any, F4* __restrict__ hits) {
+    extern __shared__ F4 lds[];
+    const TraceLds L = stage_lds(sc, lds);
+    __syncthreads();
+    const uint32_t stride = gridDim.x * kBlock;
+    for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
+        const F4 ro = rays[2 * i], rd = rays[2 * i + 1];
+        float t, u, v; uint32_t prim;
+        if (any == 2) traverse_stats<false>(sc, L, mk3(ro.x, ro.y, ro.z), mk3(rd.x, rd.y, rd.z), ro.w, rd.w, t, u, v, prim);
+        else if (any == 3) traverse_stats<true>(sc, L, mk3(ro.x, ro.y, ro.z), mk3(rd.x, rd.y, rd.z), ro.w, rd.w, t, u, v, prim);      // any-hit in the order sc.any_order, counted (u = node steps, v = triangle tests)
+        else if (any) trace_ray<true>(sc, small, L, mk3(ro.x, ro.y, ro.z), mk3(rd.x, rd.y, rd.z), ro.w, rd.w, t, u, v, prim);
+        else trace_ray<false>(sc, small, L, mk3(ro.x, ro.y, ro.z), mk3(rd.x, rd.y, rd.z), ro.w, rd.w, t, u, v, prim);
+        hits[i] = {t, u, v, u2f(prim)};
+    }
+}
+__global__ __launch_bounds__(kBlock) void k_dbg_surface(DevScene sc, const F4* __restrict__ rays, const F4* __restrict__ hits, uint32_t n, F4* __restrict__ out) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const F4 h = hits[i];
+    F4 z = {0, 0, 0, 0};
+    out[4 * i] = z; out[4 * i + 1] = z; out[4 * i + 2] = z; out[4 * i + 3] = z;
+    if (f2u(h.w) == kMissPrim) { out[4 * i].w = u2f(kMissMat); return; }
+    const F4 ro = rays[2 * i], rd = rays[2 * i + 1];
+    const Surf s = surface(sc, mk3(ro.x, ro.y, ro.z), mk3(rd.x, rd.y, rd.z), h.x, h.y, h.z, f2u(h.w));
+    out[4 * i] = {s.pos.x, s.pos.y, s.pos.z, u2f(s.mat)};
+    out[4 * i + 1] = {s.normal.x, s.normal.y, s.normal.z, s.area};
+    out[4 * i + 2] = {u2f(s.inst), s.flat.x, s.flat.y, s.flat.z};
+}
+__global__ __launch_bounds__(kBlock) void k_dbg_bsdf_eval(DevScene sc, uint32_t mat, uint32_t flags, const float* __restrict__ in9, uint32_t n, float* __restrict__ out8) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const float* q = in9 + (size_t)i * 9; float* o = out8 + (size_t)i * 8;
+    f3 F; float P, pd, ps;
+    f3 nrm = mk3(q[0], q[1], q[2]); const f3 wo = mk3(q[3], q[4], q[5]);
+    const float eta_p = transmission_eta(sc.mats[mat], flags, wo, nrm);
+    if (flags & 0x80000000u) {                       // the form k_shade runs: view terms computed once (MixView), mixture evaluated against them — must give the same bits
+        const uint32_t fl = flags & 0x7FFFFFFFu;
+        const MixView mv = mix_view(sc.mats[mat], fl, nrm, wo, eta_p);
+        bsdf_mixture_v(sc.mats[mat], fl, mv, nrm, mk3(q[6], q[7], q[8]), wo, F, P, eta_p); pd = mv.pd; ps = mv.ps;
+    } else bsdf_mixture(sc.mats[mat], flags, nrm, mk3(q[6], q[7], q[8]), wo, F, P, pd, ps, eta_p);
+    o[0] = F.x; o[1] = F.y; o[2] = F.z; o[3] = P; o[4] = pd; o[5] = ps; o[6] = eta_p; o[7] = 0.0f;
+}
+__global__ __launch_bounds__(kBlock) void k_dbg_bsdf_sample(DevScene sc, uint32_t mat, uint32_t flags, const float* __restrict__ in8, uint32_t n, float* __restrict__ out8) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const float* q = in8 + (size_t)i * 8; float* o = out8 + (size_t)i * 8;
+    uint32_t s0 = f2u(q[6]), s1 = f2u(q[7]);
+    f3 nrm = mk3(q[0], q[1], q[2]); const f3 wo = mk3(q[3], q[4], q[5]);
+    const float eta_p = transmission_eta(sc.mats[mat], flags, wo, nrm);
+    const uint32_t fl = flags & 0x7FFFFFFFu;
+    const uint32_t st = (flags & 0x80000000u) ? select_strategy_v(sc.mats[mat], mix_view(sc.mats[mat], fl, nrm, wo, eta_p), fl, s0, s1, eta_p) : select_strategy(sc.mats[mat], wo, nrm, flags, s0, s1, eta_p);
+    const f3 wi = sample_bsdf(sc.mats[mat], st, wo, nrm, s0, s1, eta_p);
+    o[0] = wi.x; o[1] = wi.y; o[2] = wi.z; o[3] = u2f(st); o[4] = u2f(s0); o[5] = u2f(s1); o[6] = 0.0f; o[7] = 0.0f;
+}
+__global__ void k_dbg_tea(uint32_t s0, uint32_t s1, uint32_t n, float* __restrict__ out, uint32_t* __restrict__ seed_out) {
+    if (threadIdx.x || blockIdx.x) return;
+    for (uint32_t i = 0; i < n; i++) out[i] = tea_next(s0, s1);
+    seed_out[0] = s0; seed_out[1] = s1;
+}
+__global__ __launch_bounds__(kBlock) void k_dbg_primary(DevFrame f, const CameraGPU* __restrict__ cam, uint32_t sample_id, F4* __restrict__ rays) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= f.width * f.height) return;
+    const uint32_t x = i % f.width, y = i / f.width;
+    uint32_t s0, s1; seed_init(x, y, sample_id, f.frame_seed, s0, s1);
+    float jx = 0.0f, jy = 0.0f;
+    if (f.flags & 2u) { jx = tea_next(s0, s1); jy = tea_next(s0, s1); }
+    f3 o, d; primary_ray(*cam, f.width, f.height, x, y, jx, jy, o, d);
+    rays[2 * i] = {o.x, o.y, o.z, kTMinCam};
+    rays[2 * i + 1] = {d.x, d.y, d.z, kTMax};
+}
+
+}  // namespace rtx

@@ -1,0 +1,244 @@
+// rtx_k_shade.hpp — the shading kernels of the general path (the device functions they call: rtx_shade.hpp)
+// One of the kernel headers of rtx_kernels.hip, the path tracer's single translation unit (see its header comment for the design and for why).
+// Uses the PF_* section-profile macros that rtx_kernels.hip defines before it includes this file.
+#pragma once
+#include "rtx_shade.hpp"
+
+namespace rtx {
+
+// shade: one thread per queued path (general path: hits come from k_trace_closest, shadow rays go to queues).
+// SORT = material-sorted shading: the workgroup's sub-queue is consumed in chunks of kSortChunk entries; each chunk is
+// counting-sorted in LDS by the material id of the hit (misses last), so that a wave shades ONE material and its
+// branches (emissive / Lambert / GGX strategy, miss) are wave-uniform.  The sort never leaves LDS: the queue index and
+// the hit record it reads are needed by the shading anyway.  Results do not depend on the order (per-path state only).
+// MEASURED (MI355X, 1080p 16 spp 8 bounces, ms per 2 frames in k_shade): Bistro-class (30 % GGX) 18.1 unsorted vs 23.3
+// sorted, Sponza-class 16.1 vs 32.1 — k_shade is HBM-bound, not divergence-bound, and the permutation turns its
+// coalesced per-path state streams into gathers; k_trace_shadow gains 4-8 % from the more coherent shadow rays, the
+// frame loses 1-10 %.  Round 2, with the path state kept by queue position (the permutation then stays inside a 2048-entry window of
+// each stream): still slower, k_shade per frame 7.4 -> 10.6 ms (Sponza-class), 8.6 -> 9.8 ms (Bistro-class, where k_shade is VALU-bound at
+// 33 of 64 lanes).  Hence RTX_OPT_SORT_MATERIALS defaults to 0.
+// One item of k_shade / k_shade_dense: entry `qi` of the workgroup's sub-queue (valid = the lane has one).  Every lane of the wave goes through the compactions.
+template <bool LAMBERT>
+__device__ __forceinline__ void shade_item(const DevScene& sc, const DevFrame& f, const DevPaths& p, uint32_t bounce, uint32_t nee, bool last, size_t qb,
+                                           const uint32_t* __restrict__ myq, uint32_t* __restrict__ mynext, uint32_t* s_cnt, bool valid, uint32_t qi, Prof* pf, const float* lds_cdf = nullptr, const LightGPU* lds_lights = nullptr, const MatGPU* lds_mats = nullptr) {
+    PathState S; S.pid = 0; S.o = mk3(0, 0, 0); S.d = mk3(0, 0, 1); S.thr = mk3(0, 0, 0); S.prev_pdf = 1.0f; S.s0 = S.s1 = 0;
+    Surf sf; sf.mat = 0; sf.normal = mk3(0, 0, 1); sf.pos = mk3(0, 0, 0);
+    bool shading = false;
+#ifndef RTX_NO_LDS_MATS
+    const MatGPU* mats = lds_mats ? lds_mats : sc.mats;      // (uniform; k_shade stages a short material table beside the light list)
+#else
+    const MatGPU* mats = sc.mats;
+#endif
+    if (valid) {
+        const uint32_t pid = myq[qi];
+        const uint32_t src = p.out_o ? (uint32_t)qb + qi : pid;               // compact state: hit and path state live at the queue position
+        const F4 h = ld_stream(p.hit + src);
+        const uint32_t prim = f2u(h.w);
+        if (prim != kMissPrim) {                                          // miss: Miss.hlsl:3-11 -> black, terminate
+            S = load_path_stream(p, src); S.pid = pid;
+            PF_MARK(0); PF_COUNT(1);
+            sf = surface(sc, S.o, S.d, h.x, h.y, h.z, prim);
+            PF_MARK(1);
+            if (sf.mat < sc.nmat) {
+                const MatGPU& m = mats[sf.mat];
+                if (m.Ke_len > 0.0f) add_emissive(sc, p, S, sf, m, bounce, nee);   // Hit.hlsl:126, Sampler_v6.hlsl:457
+                else shading = true;
+            }
+        }
+    }
+    const f3 outgoing = -S.d, pos = sf.pos;
+    const MatGPU* mp = mats + (shading ? sf.mat : 0u);
+    f3 normal = sf.normal;
+    const float eta_p = LAMBERT ? 0.0f : transmission_eta(*mp, f.flags, outgoing, normal);          // (extension) hits from behind a dielectric flip the shading normal
+    // the view-dependent terms of the mixture BSDF, once per shading point: the NEE samples and the continuation share them (rtx_bsdf.hpp: MixView)
+    MixView mvs; const MixView* mv = nullptr;
+#ifndef RTX_NO_MIXVIEW          // (A/B build: make VARIANT=nomv VARFLAGS=-DRTX_NO_MIXVIEW)
+    if (!LAMBERT) { mvs = mix_view(*mp, f.flags, normal, outgoing, eta_p); mv = &mvs; }
+#endif
+    PF_MARK(2);
+    for (uint32_t j = 0; j < nee; j++) {                                  // NEE: visibility deferred to k_trace_shadow
+        bool push = false;
+        F4 so = {0, 0, 0, 0}, sd = {0, 0, 0, 0}; f3 con = mk3(0, 0, 0);
+        if (shading) { PF_COUNT(3); }
+        if (shading) push = nee_sample(sc, *mp, f.flags, nee, S, pos, normal, outgoing, so, sd, con, sc.nsmall != 0u && sf.near_hull, eta_p, mv, lds_cdf, lds_lights);
+        PF_MARK(3);
+        if (push) { PF_COUNT(4); }
+        const size_t seg = (size_t)j * f.qcap * gridDim.x + qb;           // NEE slot j, this workgroup's sub-queue
+        const uint32_t slot = block_push(push, &s_cnt[1 + j]);
+        if (push) { st_stream(p.sh_o + seg + slot, so); st_stream(p.sh_d + seg + slot, sd); st_stream(p.sh_c + seg + slot, F4{con.x, con.y, con.z, u2f(S.pid)}); }
+    }
+    PF_MARK(4);
+    bool alive = false;
+    f3 smp = mk3(0, 0, 1); float P = 0.0f;
+    if (shading && !last) { PF_COUNT(5); }
+    if (shading && !last) alive = bsdf_continue(*mp, f, bounce, S, normal, outgoing, smp, P, eta_p, mv);
+    PF_MARK(5);
+    if (alive) { PF_COUNT(6); }
+    const uint32_t slot = block_push(alive, &s_cnt[0]);
+    if (alive) {
+        if (p.out_o) store_path_at_stream(p.out_o, p.out_d, p.out_thr, (uint32_t)qb + slot, S, pos, smp, P);     // densely, at its place in the next queue
+        else store_path(p, S, pos, smp, P);
+        if (p.oct_out) {                                              // RTX_OPT_OCTANT_SORT: the key the next bounce's closest-hit kernel groups its fetches by
+            uint32_t key = (f2u(smp.x) >> 31) | ((f2u(smp.y) >> 31) << 1) | ((f2u(smp.z) >> 31) << 2);            // 1: the direction octant (what ray_octant() will see: sign bits)
+            if (p.key_mode == 3u) {                                   // 3: the cell of the ray's ORIGIN on a grid over the scene's box (sc.cell_*: 8 bits in all, split by the box's extents)
+                const uint32_t bx = sc.cell_bits & 15u, by = (sc.cell_bits >> 4) & 15u, bz = (sc.cell_bits >> 8) & 15u;
+                const uint32_t cx = (uint32_t)fminf(fmaxf((pos.x - sc.cell_o[0]) * sc.cell_s[0], 0.0f), (float)((1u << bx) - 1u));
+                const uint32_t cy = (uint32_t)fminf(fmaxf((pos.y - sc.cell_o[1]) * sc.cell_s[1], 0.0f), (float)((1u << by) - 1u));
+                const uint32_t cz = (uint32_t)fminf(fmaxf((pos.z - sc.cell_o[2]) * sc.cell_s[2], 0.0f), (float)((1u << bz) - 1u));
+                key = cx | (cy << bx) | (cz << (bx + by));
+            }
+            if (p.key_mode == 5u) key = ((uint32_t)slot * 2654435761u) >> 24;      // 5 (tooling): a hashed key — the scattered fetch without any grouping, to price the fetch alone
+            p.oct_out[qb + slot] = (uint8_t)key;
+        }
+        mynext[slot] = S.pid;
+    }
+}
+
+// RTX_FLAG_LAMBERT_ONLY is a launch constant, so k_shade / k_shade_dense take it as a template parameter: bit 0 of the flags their code sees is known at compile time
+template <bool LAMBERT>
+__device__ __forceinline__ DevFrame frame_with_lambert(const DevFrame& f_in) {
+    DevFrame f = f_in;
+    f.flags = LAMBERT ? (f_in.flags | 1u) : (f_in.flags & ~1u);
+    return f;
+}
+
+constexpr uint32_t kSortChunk = 2048, kSortKeys = 64, kLdsCdf = 256;
+// k_shade's dynamic LDS (launch and kernel agree through this one function): the light list (records + CDF) when it has <= 256 entries, the material table behind it while
+// both stay within kShadeLds bytes.  RTX_SHADE_LDS (A/B builds) moves the budget; 0 = lights only.
+#ifndef RTX_SHADE_LDS
+#define RTX_SHADE_LDS 24576
+#endif
+constexpr uint32_t kShadeLds = RTX_SHADE_LDS;
+__host__ __device__ inline void shade_lds_plan(uint32_t nlights, uint32_t nmat, bool sort, uint32_t& lights_bytes, uint32_t& mats_bytes) {
+    lights_bytes = (!sort && nlights <= kLdsCdf) ? ((nlights * 84u + 15u) & ~15u) : 0u;
+    mats_bytes = (!sort && nmat && lights_bytes + nmat * 160u <= kShadeLds) ? nmat * 160u : 0u;
+}
+#ifndef RTX_SHADE_WAVES
+#define RTX_SHADE_WAVES 7          // waves per SIMD k_shade is compiled for: 7 = 72 VGPRs + 1 spilled (GGX) / 66 (Lambert); uncapped: 94 VGPRs, 5 waves; 6: 80, no spills; 8: 64, 9 spilled.
+                                   // k_shade per frame, C3 / C5: 7.42 / 8.77 ms uncapped, 6.93 / 8.54 at 6, 7.50 / 8.83 at 8 (round 2); round 4: 6.27 / 6.85 at 6, 6.28 / 6.72 at 7
+#endif
+template <bool SORT, bool LAMBERT>     // LAMBERT: RTX_FLAG_LAMBERT_ONLY as a compile-time constant (no GGX / transmission code in that instantiation)
+__global__ __launch_bounds__(kBlock, RTX_SHADE_WAVES) void k_shade(DevScene sc, DevFrame f_in, DevPaths p, uint32_t bounce,
+                                                  const uint32_t* __restrict__ queue, const uint32_t* __restrict__ qcount,
+                                                  uint32_t* __restrict__ next_queue, uint32_t* __restrict__ next_count,
+                                                  uint32_t* __restrict__ shcounts /* [nee][gridDim.x] */) {
+    const DevFrame f = frame_with_lambert<LAMBERT>(f_in);
+    __shared__ uint32_t s_cnt[1 + kMaxNee];                 // [0] next-queue length, [1 + j] shadow queue j length
+    __shared__ uint32_t s_pid[SORT ? kSortChunk : 1], s_sorted[SORT ? kSortChunk : 1], s_hist[SORT ? kSortKeys : 1];
+    __shared__ uint8_t s_key[SORT ? kSortChunk : 1];
+    // (round 5) a light list of <= 256 entries in LDS — the records (80 B each) and behind them the CDF: NEE's binary search is 1-8 DEPENDENT reads per sample (street scene:
+    // 204 lights), the record one more.  Dynamic LDS, sized by the list at launch (shade_lds_bytes): a scene with two lights pays 168 bytes, not a workgroup per CU
+    extern __shared__ F4 s_lights[];
+    float* s_cdf = (float*)(s_lights + (size_t)sc.nlights * 5u);
+    uint32_t lights_bytes, mats_bytes; shade_lds_plan(sc.nlights, sc.nmat, SORT, lights_bytes, mats_bytes);
+    const bool cdf_in_lds = lights_bytes != 0u;
+    if (cdf_in_lds) {
+        for (uint32_t i = threadIdx.x; i < sc.nlights * 5u; i += kBlock) s_lights[i] = ((const F4*)sc.lights)[i];
+        for (uint32_t i = threadIdx.x; i < sc.nlights; i += kBlock) s_cdf[i] = sc.cdf[i];
+    }
+    if (threadIdx.x <= kMaxNee) s_cnt[threadIdx.x] = 0;
+    __syncthreads();
+    const float* lds_cdf = cdf_in_lds ? s_cdf : nullptr;
+    const LightGPU* lds_lights = cdf_in_lds ? (const LightGPU*)s_lights : nullptr;
+    // ... and the material table (160 B each) behind the CDF when launch_shade found room for it (mats_in_lds: what it sized the dynamic LDS for)
+    const MatGPU* lds_mats = nullptr;
+    if (mats_bytes) {
+        F4* dst = (F4*)((char*)s_lights + lights_bytes);
+        for (uint32_t i = threadIdx.x; i < sc.nmat * 10u; i += kBlock) dst[i] = ((const F4*)sc.mats)[i];
+        lds_mats = (const MatGPU*)dst;
+    }
+    const uint32_t n = qcount[blockIdx.x];
+    const uint32_t nee = sc.nlights ? f.nee_samples : 0u;
+    const bool last = (bounce + 1u == f.max_bounces);
+    const size_t qb = (size_t)blockIdx.x * f.qcap;
+    const uint32_t* myq = queue + qb;
+    uint32_t* mynext = next_queue + qb;
+    const uint32_t chunk = SORT ? kSortChunk : n;
+    PF_BEGIN;                                               // (PROFILE build: sections 0 load, 1 surface, 2 emissive / setup, 3 NEE sample, 4 shadow push, 5 BSDF sample, 6 store)
+    for (uint32_t cb = 0; cb < n; cb += chunk) {
+        const uint32_t cn = (n - cb < chunk) ? n - cb : chunk;
+        if (SORT) {
+            if (threadIdx.x < kSortKeys) s_hist[threadIdx.x] = 0;
+            __syncthreads();
+            for (uint32_t i = threadIdx.x; i < cn; i += kBlock) {
+                const uint32_t prim = f2u(p.hit[p.out_o ? (uint32_t)qb + cb + i : myq[cb + i]].w);
+                const uint32_t key = prim == kMissPrim ? kSortKeys - 1u : (sc.shade[prim].mat % (kSortKeys - 1u));
+                s_pid[i] = i; s_key[i] = (uint8_t)key;                 // (the entry's place in the chunk: the queue position is needed too)
+                atomicAdd(&s_hist[key], 1u);
+            }
+            __syncthreads();
+            if (threadIdx.x < 64) {                             // exclusive scan of the 64 bucket counts by one wave
+                const uint32_t c = s_hist[threadIdx.x];
+                uint32_t incl = c;
+#pragma unroll
+                for (int d = 1; d < 64; d <<= 1) { const uint32_t t = __shfl_up(incl, d); if ((int)threadIdx.x >= d) incl += t; }
+                s_hist[threadIdx.x] = incl - c;
+            }
+            __syncthreads();
+            for (uint32_t i = threadIdx.x; i < cn; i += kBlock) s_sorted[atomicAdd(&s_hist[s_key[i]], 1u)] = s_pid[i];
+            __syncthreads();
+        }
+        for (uint32_t base = threadIdx.x & ~63u; base < cn; base += kBlock) {
+            const uint32_t i = base + (threadIdx.x & 63u);
+            shade_item<LAMBERT>(sc, f, p, bounce, nee, last, qb, myq, mynext, s_cnt, i < cn, cb + (SORT ? s_sorted[i] : i), pf, lds_cdf, lds_lights, lds_mats);
+        }
+        if (SORT) __syncthreads();                              // the next chunk overwrites the LDS buffers
+    }
+    PF_MARK(6);
+    PF_FLUSH;
+    __syncthreads();
+    if (threadIdx.x == 0) next_count[blockIdx.x] = s_cnt[0];
+    if (threadIdx.x >= 1 && threadIdx.x <= nee) shcounts[(size_t)(threadIdx.x - 1) * gridDim.x + blockIdx.x] = s_cnt[threadIdx.x];
+}
+
+// k_shade with the HITS of the sub-queue compacted before they are shaded (RTX_OPT_SHADE_DENSE).  In an open scene a large part of a bounce's rays leaves the scene
+// (the Bistro-class street keeps 86 / 66 / 53 / 44 % of its paths through bounces 1-4) and in k_shade their lanes idle through surface reconstruction, NEE and BSDF
+// sampling, which on that scene is VALU-bound work at 33 of 64 lanes (profiles/r02_pmc_bvh.md).  Here the workgroup reads the hit records of 256 entries at a time, pushes
+// the entries that hit something into an LDS ring (ballot + one LDS atomic per wave), and shades ring entries 256 at a time — full waves of hits, as the hit ring of the
+// fused tiny-scene kernel does.  The permutation stays inside the workgroup's sub-queue, so the state streams stay coalesced (monotone gathers within a 2-KB window; this is
+// not the global material sort that was rightly rejected).  Same arithmetic per item; only the order of the entries in the next queue changes, which no result depends on.
+// Ring bookkeeping as in k_bounce_small: hits of pass k are counted in s_blk[k % 3] and summed in a register after the pass's barrier, a word is cleared one pass later.
+template <bool LAMBERT>
+__global__ __launch_bounds__(kBlock, RTX_SHADE_WAVES) void k_shade_dense(DevScene sc, DevFrame f_in, DevPaths p, uint32_t bounce,
+                                                        const uint32_t* __restrict__ queue, const uint32_t* __restrict__ qcount,
+                                                        uint32_t* __restrict__ next_queue, uint32_t* __restrict__ next_count, uint32_t* __restrict__ shcounts) {
+    const DevFrame f = frame_with_lambert<LAMBERT>(f_in);
+    constexpr uint32_t kRing = 512u;
+    __shared__ uint32_t s_cnt[1 + kMaxNee], s_list[kRing], s_blk[3];
+    if (threadIdx.x <= kMaxNee) s_cnt[threadIdx.x] = 0;
+    if (threadIdx.x < 3) s_blk[threadIdx.x] = 0;
+    __syncthreads();
+    const uint32_t n = qcount[blockIdx.x];
+    const uint32_t nee = sc.nlights ? f.nee_samples : 0u;
+    const bool last = (bounce + 1u == f.max_bounces);
+    const size_t qb = (size_t)blockIdx.x * f.qcap;
+    const uint32_t* myq = queue + qb;
+    uint32_t* mynext = next_queue + qb;
+    Prof* pf = nullptr;
+    uint32_t prod = 0, head = 0, rk = 0;                    // hits pushed / shaded so far, pass number mod 3 (all uniform, in registers)
+    for (uint32_t base = 0; base < n; base += kBlock) {
+        const uint32_t i = base + threadIdx.x;
+        bool is_hit = false;
+        if (i < n) is_hit = f2u(p.hit[p.out_o ? (uint32_t)qb + i : myq[i]].w) != kMissPrim;        // miss: Miss.hlsl:3-11 -> black, the path ends: nothing to do
+        const uint32_t slot = prod + block_push(is_hit, &s_blk[rk]);
+        if (is_hit) s_list[slot & (kRing - 1u)] = i;
+        __syncthreads();
+        prod += s_blk[rk];
+        if (threadIdx.x == 0) s_blk[rk == 0u ? 2u : rk - 1u] = 0;
+        rk = rk == 2u ? 0u : rk + 1u;
+        const bool flush = base + kBlock >= n;
+        while (prod - head >= (uint32_t)kBlock || (flush && prod != head)) {                      // uniform
+            const uint32_t take = prod - head < (uint32_t)kBlock ? prod - head : (uint32_t)kBlock;
+            const bool valid = threadIdx.x < take;
+            const uint32_t qi = valid ? s_list[(head + threadIdx.x) & (kRing - 1u)] : 0u;
+            shade_item<LAMBERT>(sc, f, p, bounce, nee, last, qb, myq, mynext, s_cnt, valid, qi, pf);
+            head += take;
+            __syncthreads();                                // every lane has read its ring slot before the next pass overwrites it
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) next_count[blockIdx.x] = s_cnt[0];
+    if (threadIdx.x >= 1 && threadIdx.x <= nee) shcounts[(size_t)(threadIdx.x - 1) * gridDim.x + blockIdx.x] = s_cnt[threadIdx.x];
+}
+
+}  // namespace rtx

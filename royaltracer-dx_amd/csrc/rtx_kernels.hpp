@@ -1,4 +1,4 @@
-// rtx_kernels.hpp — kernel argument blocks and host-side launchers (implemented in rtx_kernels.hip).
+// rtx_kernels.hpp — kernel argument blocks and host-side launchers (implemented in rtx_kernels.hip; launch_refit and the tree cost in rtx_refit.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "rtx_types.hpp"
@@ -26,7 +26,7 @@ struct DevScene {
     unsigned long long* stack_ovf; uint32_t stack_ovf_stride;   // RTX_OPT_STACK_CAP: entries beyond stack_depth live here, entry k of lane l at [k * stride + (l & (stride - 1))] (nullptr: the tree needs no more than stack_depth)
     uint32_t stack_private;         // queue kernels: 0 = stack in the LDS column, 1 = private (scratch) array
     uint32_t sort_materials;        // 1 = material-sorted shading in k_shade (general path; tuning knob, default 0)
-    uint32_t refill_min, trace_sched;   // persistent traversal: idle lanes that trigger a refill; wave schedule (rtx_kernels.hip)
+    uint32_t refill_min, trace_sched;   // persistent traversal: idle lanes that trigger a refill; wave schedule (rtx_k_trace.hpp)
     uint32_t shade_dense;               // general path: k_shade compacts the hits of its sub-queue through an LDS ring before shading them (k_shade_dense)
     uint32_t any_order;                 // any-hit rays: visiting order of a node's hit children, 0 slot order / 1 nearest octant first / 2 farthest first (rtx_traverse.hpp: node8_hits)
     float cell_o[3], cell_s[3]; uint32_t cell_bits;     // RTX_OPT_OCTANT_SORT 3: grid over the scene's box, cell = (pos - cell_o) * cell_s per axis, bits per axis x | y << 4 | z << 8 (8 in all)

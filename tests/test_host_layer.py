@@ -387,6 +387,28 @@ def test_device_memory_events_and_pinned_memory_are_owned_by_the_owning_types():
             assert call not in src, (f, call)
 
 
+def test_kernels_live_in_headers_by_concern_and_the_chunk_deal_is_written_once():
+    """csrc/rtx_kernels.hip is the map of the design, the kernel headers' one translation unit and their launchers: it defines no kernel itself.  Every launcher declared in
+    rtx_kernels.hpp is defined exactly once across the .hip files (the refit and tree-cost launchers in rtx_refit.hip).  The chunk deal of the raygen kernels (rows rotated by
+    k * 2654435761u % nk) is written in ONE place, dealt_chunk in rtx_dev_common.hpp — and once more inside k_raygen_trace_small, which keeps it written out because the compiler
+    allocates that kernel's registers differently through the helper (profiles/kernels_split_isa.md); no third copy."""
+    csrc = os.path.join(ROOT, "royaltracer-dx_amd", "csrc")
+    assert "__global__" not in open(os.path.join(csrc, "rtx_kernels.hip")).read()
+    declared = re.findall(r"^void (launch_\w+)\(", open(os.path.join(csrc, "rtx_kernels.hpp")).read(), re.M)
+    assert len(declared) >= 40 and len(set(declared)) == len(declared)
+    hips = {f: open(f).read() for f in sorted(glob.glob(os.path.join(csrc, "*.hip")))}
+    assert len(hips) >= 8
+    for name in declared:
+        where = [os.path.basename(f) for f, src in hips.items() for _ in re.findall(r"^void %s\(" % name, src, re.M)]
+        assert len(where) == 1, (name, where)
+    deal = re.compile(r"2654435761u\)\s*%\s*nk\b")
+    copies = {os.path.basename(f): len(deal.findall(open(f).read())) for f in sorted(glob.glob(os.path.join(csrc, "*")))}
+    assert {f: n for f, n in copies.items() if n} == {"rtx_dev_common.hpp": 1, "rtx_k_raygen.hpp": 1}
+    raygen = open(os.path.join(csrc, "rtx_k_raygen.hpp")).read()
+    kept = raygen[raygen.index("void k_raygen_trace_small("):raygen.index("void k_primary_surface(")]
+    assert len(deal.findall(kept)) == 1 and "dealt_chunk" in kept           # the written-out copy names the helper it must equal
+
+
 def test_no_cpu_fallback_without_a_gpu(rt):
     import torch
     if torch.cuda.is_available():

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Registers, spills, LDS and occupancy of every kernel in csrc/rtx_kernels.hip as hipcc reports them (-Rpass-analysis=kernel-resource-usage); no GPU needed.
+"""Registers, spills, LDS and occupancy of every kernel in csrc/rtx_kernels.hip and csrc/rtx_refit.hip as hipcc reports them (-Rpass-analysis=kernel-resource-usage); no GPU needed.
 usage: python3 tools/kernel_resources.py [filter-substring ...] [-- extra hipcc flags]"""
 import os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -7,8 +7,8 @@ args = sys.argv[1:]
 extra = args[args.index("--") + 1:] if "--" in args else []
 flt = args[:args.index("--")] if "--" in args else args
 cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-fno-slp-vectorize",
-       "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(ROOT, "royaltracer-dx_amd", "csrc", "rtx_kernels.hip"), "-o", "/dev/null"] + extra
-out = subprocess.run(cmd, capture_output=True, text=True).stderr
+       "-Rpass-analysis=kernel-resource-usage", "-o", "/dev/null"] + extra
+out = "".join(subprocess.run(cmd + ["-c", os.path.join(ROOT, "royaltracer-dx_amd", "csrc", f)], capture_output=True, text=True).stderr for f in ("rtx_kernels.hip", "rtx_refit.hip"))
 rows, cur = [], None
 for line in out.splitlines():
     m = re.search(r"Function Name: (\S+)", line)
