@@ -67,7 +67,8 @@ typedef struct rtx_params {
 
 /* kernel classes for rtx_stats */
 enum { RTX_K_RAYGEN = 0, RTX_K_TRACE = 1, RTX_K_SHADE = 2, RTX_K_SHADOW = 3, RTX_K_ACCUM = 4, RTX_K_SORT = 5,
-       RTX_K_BOUNCE = 6 /* fused trace+shade+shadow kernels: k_bounce_small (tiny scenes), k_bounce_bvh (general path) */, RTX_K_COUNT = 8 };
+       RTX_K_BOUNCE = 6 /* fused trace+shade+shadow kernels: k_bounce_small (tiny scenes), k_bounce_bvh (general path) */,
+       RTX_K_ADAPT = 7 /* rtx_render_adaptive: the convergence criterion and the compaction of the active list, once per pass */, RTX_K_COUNT = 8 };
 
 typedef struct rtx_stats {
     uint64_t rays_primary, rays_extension, rays_shadow;  /* BVH queries issued by the last rtx_render */
@@ -246,6 +247,36 @@ int  rtx_bind_accum(rtx_ctx*, void* device_rgba32f, size_t bytes);
 int  rtx_clear_accum(rtx_ctx*, uint32_t width, uint32_t height);   /* view-change reset (RayGen_v6_pass3.hlsl:407-423) */
 /* 3x DispatchRays (PopulateCommandList, Renderer.cpp:646-673) -> here: the wavefront loop; returns with the frame finished (RTX_OPT_ASYNC on a caller-bound stream: enqueued) */
 int  rtx_render(rtx_ctx*, const rtx_params*);
+/* ADAPTIVE SAMPLING (new; the reference gives every pixel the same count): rtx_render with a noise threshold and a sample cap instead of a sample count.  rtx_params.spp is
+   ignored.  The unit of decision is the 256-slot CHUNK every raygen kernel deals: four 8x8 blocks of one tile, a 32 x 8 pixel strip (with tile_size 16 the whole tile).  A chunk
+   is sampled as a whole or not at all.
+   State beside u1, cleared by rtx_clear_accum: `half`, a second RGBA32F W x H image holding the running sum of the samples whose id (sample_base + n) is ODD, added in the same
+   place and order as u1; per chunk the samples taken and a sticky "converged" flag.  Criterion per valid pixel, float32 in exactly this order, a = u1, h = half, N = a.w:
+       d = (|a.x - (h.x + h.x)| + |a.y - (h.y + h.y)|) + |a.z - (h.z + h.z)|          (|sum of the even ids - sum of the odd ids|)
+       s = (a.x + a.y) + a.z
+       converged = d * d < ((threshold * threshold) * max(s, dark_floor * N)) * N
+   A chunk converges when every valid pixel of it has, and is then never sampled again before the next clear.  The comparison is strict: threshold 0 converges nothing and
+   gives rtx_render's image of max_spp samples to the bit.  dark_floor 0 means 0.01.  The halves balance at even counts only: min_spp and step_spp must be even and >= 2,
+   min_spp <= max_spp (else RTX_ERR_INVALID; a failed call leaves the image untouched).
+   One call: chunks without samples get min_spp; then — criterion, list of the chunks neither converged nor at max_spp, its length read back — every listed chunk gets step_spp
+   more samples (fewer to land on max_spp), until the list is empty.  A chunk's next sample id is sample_base + its count, seeds depend on pixel and sample id only, and sums
+   are added in sample order: the image is a function of the arguments, not of batching, sharding or how the calls were split — a later call with a larger max_spp continues
+   where the last one stopped (max 8, then max 16 == max 16 at once, to the bit; keep sample_base).  Shards work as for rtx_render: decisions never look across chunks, and the
+   per-chunk state is kept per IMAGE chunk, so one context may also render several shards in turn.  Always synchronous (the host sizes every pass), RTX_OPT_ASYNC or not.
+   rtx_stats covers the whole call (rays, paths, kernel_ms summed over the passes; the criterion and list kernels under RTX_K_ADAPT); the per-pixel count is u1's w as ever.
+   u1 must hold adaptive samples only: after rtx_render / rtx_render_v6_pass1 / rtx_render_restir, or with another image size or tile_size than the state was begun with,
+   the call is RTX_ERR_STATE until rtx_clear_accum.  Path tracer only (no ReSTIR / pass-1 form). */
+typedef struct rtx_adaptive {
+    uint32_t min_spp, step_spp, max_spp;   /* first pass | later passes | cap, per chunk */
+    float    threshold, dark_floor;        /* relative noise of the mean a pixel may keep; floor under sum / N for dark pixels (0 => 0.01) */
+    uint32_t reserved[3];                  /* 0 */
+} rtx_adaptive;
+typedef struct rtx_adaptive_result {
+    uint32_t passes;                       /* render passes of this call */
+    uint32_t chunks, chunks_converged, chunks_at_max;   /* of this shard, after the call: chunks holding a valid pixel | flagged converged | unconverged at max_spp */
+    uint64_t pixel_samples;                /* valid pixel-samples this call added (== rtx_stats.paths) */
+} rtx_adaptive_result;
+int  rtx_render_adaptive(rtx_ctx*, const rtx_params*, const rtx_adaptive*, rtx_adaptive_result* out /* may be NULL */);
 /* The reference's OWN first pass, literally: RayGen of RayGen_v6_pass1.hlsl:48-190 (first DispatchRays,
    Renderer.cpp:651-654): primary hit, SampleRIS (Sampler_v6.hlsl:653-736), visibility, SamplePathSimple
    (Path_Sampler_v6.hlsl:3-286).  params: nee_samples = nee_samples_DI = nee_samples (Common_v6.hlsl:8-9, reference 4),

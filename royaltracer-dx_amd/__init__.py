@@ -35,8 +35,8 @@ FLAG_LAMBERT_ONLY = 1
 FLAG_JITTER = 2
 FLAG_TRANSMISSION = 4
 FLAG_BLOCK_TILES = 8
-K_RAYGEN, K_TRACE, K_SHADE, K_SHADOW, K_ACCUM, K_SORT, K_BOUNCE, K_COUNT = 0, 1, 2, 3, 4, 5, 6, 8
-KERNEL_NAMES = {K_RAYGEN: "raygen", K_TRACE: "trace_closest", K_SHADE: "shade", K_SHADOW: "trace_shadow", K_ACCUM: "accumulate", K_SORT: "sort", K_BOUNCE: "bounce_fused"}
+K_RAYGEN, K_TRACE, K_SHADE, K_SHADOW, K_ACCUM, K_SORT, K_BOUNCE, K_ADAPT, K_COUNT = 0, 1, 2, 3, 4, 5, 6, 7, 8
+KERNEL_NAMES = {K_RAYGEN: "raygen", K_TRACE: "trace_closest", K_SHADE: "shade", K_SHADOW: "trace_shadow", K_ACCUM: "accumulate", K_SORT: "sort", K_BOUNCE: "bounce_fused", K_ADAPT: "adaptive"}
 OPT_KERNEL_TIMING, OPT_PATHS_PER_BATCH, OPT_SORT_MATERIALS, OPT_LDS_NODES, OPT_SMALL_SCENE, OPT_FUSED_BOUNCE, OPT_BOUNCE_VARIANT = 1, 2, 3, 4, 5, 6, 7
 OPT_REFILL_MIN, OPT_STACK_PRIVATE, OPT_TRACE_SCHED, OPT_GPU_REFIT, OPT_BLOCKS_PER_CU, OPT_LPT_ORDER, OPT_FUSED_BVH, OPT_WORK_STEALING, OPT_COMPACT_STATE, OPT_OVERLAP_SHADOW = 8, 9, 10, 11, 12, 13, 14, 15, 16, 18
 OPT_RESTIR_WAVEFRONT, OPT_RESTIR_CHUNKS, OPT_OCCLUDER_CACHE, OPT_RESTIR_LANES, OPT_SHADE_DENSE, OPT_MERGE_RAYS, OPT_TAPER = 19, 20, 21, 22, 23, 24, 25
@@ -111,6 +111,17 @@ _sig("rtx_bind_accum", C.c_int, _vp, _vp, C.c_size_t)
 _sig("rtx_clear_accum", C.c_int, _vp, _u32, _u32)
 _sig("rtx_render", C.c_int, _vp, C.POINTER(Params))
 _sig("rtx_read_accum", C.c_int, _vp, _vp, C.c_size_t)
+class Adaptive(C.Structure):
+    """rtx_adaptive (include/rtx.h)"""
+    _fields_ = [("min_spp", C.c_uint32), ("step_spp", C.c_uint32), ("max_spp", C.c_uint32), ("threshold", C.c_float), ("dark_floor", C.c_float), ("reserved", C.c_uint32 * 3)]
+
+
+class AdaptiveResult(C.Structure):
+    """rtx_adaptive_result (include/rtx.h)"""
+    _fields_ = [("passes", C.c_uint32), ("chunks", C.c_uint32), ("chunks_converged", C.c_uint32), ("chunks_at_max", C.c_uint32), ("pixel_samples", C.c_uint64)]
+
+
+_sig("rtx_render_adaptive", C.c_int, _vp, C.POINTER(Params), C.POINTER(Adaptive), C.POINTER(AdaptiveResult))
 _sig("rtx_render_v6_pass1", C.c_int, _vp, C.POINTER(Params))
 _sig("rtx_render_restir", C.c_int, _vp, C.POINTER(Params))
 _sig("rtx_restir_reset", C.c_int, _vp)
@@ -568,6 +579,13 @@ class Context:
     def render(self, params):
         self.width, self.height = params.width, params.height
         self._ck(lib.rtx_render(self._h, C.byref(params)), "rtx_render")
+
+    def render_adaptive(self, params, min_spp, step_spp, max_spp, threshold, dark_floor=0.0):
+        """rtx_render_adaptive: sample every 256-slot chunk until its pixels pass the noise threshold or it holds max_spp samples (params.spp is ignored) -> AdaptiveResult"""
+        self.width, self.height = params.width, params.height
+        a, res = Adaptive(int(min_spp), int(step_spp), int(max_spp), float(threshold), float(dark_floor)), AdaptiveResult()
+        self._ck(lib.rtx_render_adaptive(self._h, C.byref(params), C.byref(a), C.byref(res)), "rtx_render_adaptive")
+        return res
 
     def read_accum(self):
         out = np.zeros((self.height, self.width, 4), np.float32)

@@ -26,7 +26,7 @@ int ensure_accum(rtx_ctx* c, uint32_t w, uint32_t h, bool clear) {
         clear = clear || fresh;
     }
     c->acc_w = w; c->acc_h = h;
-    if (clear) HIPCHK(c, hipMemsetAsync(c->accum_ptr(), 0, need, c->stream));
+    if (clear) { HIPCHK(c, hipMemsetAsync(c->accum_ptr(), 0, need, c->stream)); c->ad.pure = true; c->ad.cleared = true; }      // (the adaptive state is zeroed by the call that next uses it)
     return RTX_OK;
 }
 
@@ -75,6 +75,7 @@ int make_frame(rtx_ctx* c, const rtx_params* p, DevFrame& f) {
     f.max_bounces = p->max_bounces; f.nee_samples = p->nee_samples; f.rr_start = p->rr_start;
     f.frame_seed = p->frame_seed; f.flags = p->flags;
     f.hist_x0 = f.hist_y0 = 0; f.hist_x1 = p->width; f.hist_y1 = p->height; f.hist_stale = nullptr;
+    f.list = nullptr;
     return RTX_OK;
 }
 // pixel rectangle [x0, x1) x [y0, y1) of rank r in the RTX_FLAG_BLOCK_TILES deal (shard_tile's rule, clipped to the image)

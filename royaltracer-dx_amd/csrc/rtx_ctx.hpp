@@ -1,7 +1,8 @@
 // rtx_ctx.hpp — PRIVATE header of the C-ABI's translation units: the context (struct rtx_ctx), the macros every entry point uses and the helpers they share.
 //   rtx_api.hip          create / destroy, options, stream, scene inputs, camera, accumulation, reads, statistics, tile pack / unpack, the shard tiling
 //   rtx_commit.hip       rtx_commit_scene (host or GPU build, GPU refit), the scene cache, finalise_scene
-//   rtx_render.hip       rtx_render (the wavefront path tracer) and finish_render
+//   rtx_render.hip       rtx_render (the wavefront path tracer), render_frame and finish_render
+//   rtx_adaptive.hip     rtx_render_adaptive: passes of render_frame over the chunks that have not converged
 //   rtx_restir_api.hip   the ReSTIR frames, their work lists and lanes, the history / halo exchange between shards
 //   rtx_debug.hip        the rtx_debug_* entry points
 // Ownership: every resource of a context is a member of an owning type (rtx_devmem.hpp, rtx_staging.hpp), so `delete c` releases it all.
@@ -136,6 +137,16 @@ struct rtx_ctx {
         struct Pending { bool active = false; size_t ncnt = 0; uint32_t nbatches = 0, G = 0, mb = 0, nee = 0, nee1 = 1; bool fused = false, fused_bvh = false; } pending;
     } pt;
 
+    // ---- adaptive sampling (rtx_adaptive.hip) ----
+    struct Adaptive {
+        // `half` (W x H, the running sum of the odd-id samples) and per IMAGE chunk — tile t, 256-slot strip k of it: word (t << cs) | k, whichever shard renders it — the samples
+        // taken and the sticky flag (AdaptState, rtx_kernels.hpp); the active list of the current pass (local chunk ids of the shard) and the five words read back per pass
+        DevBuf d_half, d_count, d_flag, d_list, d_out;
+        bool pure = true;               // every sample in u1 since its last clear came from rtx_render_adaptive (rtx_render, rtx_render_v6_pass1 and rtx_render_restir clear this)
+        bool cleared = true;            // u1 was cleared since the state above was last used: the next rtx_render_adaptive zeroes it
+        uint32_t key[3] = {0, 0, 0};    // width, height, tile size the state is laid out for
+    } ad;
+
     // ---- ReSTIR (rtx_restir_api.hip) ----
     struct Restir {
         DevBuf d_res_di, d_res_gi, d_sdata, d_last_di, d_last_gi, d_last_sd, d_p1cnt, d_p1scratch; size_t p1_slots = 0, last_slots = 0;
@@ -163,6 +174,11 @@ extern thread_local std::string g_create_err;
 // RTX_OPT_ASYNC: an rtx_render that only ENQUEUED its frame leaves statistics to be collected (finish_render: stream sync + counter read-back).  Every entry point joins
 // first (BIND) — except the calls a frame's epilogue is made of, which must stay stream-ordered behind the render without a host join (BIND_NOWAIT: pack / unpack)
 int finish_render(rtx_ctx* c);
+void collect_timed(rtx_ctx* c);
+// a pass of rtx_render_adaptive for render_frame (rtx_render.hip): the active list (local chunk ids, ascending), the first sample id, the state the accumulation updates;
+// first: the per-call tables of the tiny-scene path (packet masks / shared primary records) are still to be computed
+struct ListPass { const uint32_t* list; uint32_t n_active, sample_first; AdaptState state; bool first; };
+int render_frame(rtx_ctx* c, const rtx_params* p, const DevFrame& f_real, uint32_t spp, const ListPass* lp);
 #define BIND_NOWAIT(c) do { if (!(c)) return RTX_ERR_INVALID; HIPCHK(c, hipSetDevice((c)->device)); } while (0)
 #define BIND(c) do { BIND_NOWAIT(c); if ((c)->pt.pending.active) { const int r_ = finish_render(c); if (r_ != RTX_OK) return r_; } } while (0)
 

@@ -45,6 +45,22 @@ __device__ __forceinline__ bool slot_to_pixel(const DevFrame& f, uint32_t pl, ui
     return x < f.width && y < f.height;
 }
 
+// rtx_render_adaptive renders a frame whose slot space is the list of active chunks (DevFrame::list): virtual slot v -> the shard's real slot.  The raygen kernels and
+// k_accumulate exist in a list-aware instantiation (LIST) that passes every slot through this before slot_to_pixel and before indexing a per-real-slot table; path ids stay
+// virtual (pid = sl * npl + v).  LIST = false is the identity: the default instantiations are the code they were before the parameter existed.
+template <bool LIST> __device__ __forceinline__ uint32_t real_slot(const DevFrame& f, uint32_t v) {
+    if constexpr (LIST) return f.list[v >> 8] * (uint32_t)kBlock + (v & 255u);
+    else return v;
+}
+// the image chunk (tile, 256-slot strip of it) behind local chunk lc of the shard: index of its words in AdaptState; false: the shard's slot range is padded there (no tile)
+__device__ __forceinline__ bool chunk_image_index(const DevFrame& f, uint32_t lc, uint32_t& gi) {
+    const uint32_t cs = 2u * f.tile_shift - 8u;              // chunks per tile = 2^cs (tile_size >= 16)
+    uint32_t tx, ty;
+    if (!shard_tile(f, lc >> cs, tx, ty)) return false;
+    gi = ((ty * f.tiles_x + tx) << cs) | (lc & ((1u << cs) - 1u));
+    return true;
+}
+
 // primary ray, RayGen_v6_pass1.hlsl:51-95
 __device__ __forceinline__ void primary_ray(const CameraGPU& cam, uint32_t W, uint32_t H, uint32_t x, uint32_t y, float jx, float jy, f3& o, f3& d) {
     const float dx = (((float)x + jx) / (float)W) * 2.0f - 1.0f;

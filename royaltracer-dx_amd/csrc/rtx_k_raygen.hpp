@@ -8,6 +8,8 @@ namespace rtx {
 // ---------------------------------------------------------------------------------------------
 // raygen: one thread per path slot of the batch
 // ---------------------------------------------------------------------------------------------
+// LIST (all three raygen kernels): the frame's slot space is the active list of rtx_render_adaptive (real_slot, rtx_dev_common.hpp)
+template <bool LIST>
 __global__ __launch_bounds__(kBlock) void k_raygen(DevFrame f, DevPaths p, const CameraGPU* __restrict__ cam_p, uint32_t* __restrict__ queue, uint32_t* __restrict__ qcount, uint32_t compact) {
     __shared__ CameraGPU cam;
     __shared__ uint32_t s_n;
@@ -28,7 +30,7 @@ __global__ __launch_bounds__(kBlock) void k_raygen(DevFrame f, DevPaths p, const
         }
         const uint32_t pid = sl * f.npl + pl;
         uint32_t x = 0, y = 0;
-        const bool valid = slot_to_pixel(f, pl, x, y);
+        const bool valid = slot_to_pixel(f, real_slot<LIST>(f, pl), x, y);
         const uint32_t slot = block_push(valid, &s_n);
         if (valid) {
             uint32_t s0, s1; seed_init(x, y, f.sample_first + sl, f.frame_seed, s0, s1);
@@ -62,6 +64,7 @@ __global__ __launch_bounds__(kBlock) void k_packet_masks(DevScene sc, DevFrame f
     if (lane_id() == 0) masks[blk] = keep;
 }
 
+template <bool LIST>
 __global__ __launch_bounds__(kBlock) void k_raygen_trace_small(DevScene sc, const SmallRecPair* __restrict__ small, DevFrame f, DevPaths p, const CameraGPU* __restrict__ cam_p,
                                                                uint32_t* __restrict__ queue, uint32_t* __restrict__ qcount, uint32_t* __restrict__ gencount,
                                                                const unsigned long long* __restrict__ masks /* k_packet_masks */) {
@@ -85,8 +88,8 @@ __global__ __launch_bounds__(kBlock) void k_raygen_trace_small(DevScene sc, cons
         row0 += nk;
         if (blockIdx.x >= nk || c >= nchunks) continue;                                   // wave-uniform
         const uint32_t sl = c / f.chunks_per_sample, cl = c - sl * f.chunks_per_sample;
-        const uint32_t pl = cl * kBlock + threadIdx.x;
-        const uint32_t pid = sl * f.npl + pl;
+        const uint32_t pl = real_slot<LIST>(f, cl * kBlock + threadIdx.x);       // the real slot: pixel, packet mask
+        const uint32_t pid = sl * f.npl + cl * kBlock + threadIdx.x;
         uint32_t x = 0, y = 0, s0 = 0, s1 = 0;
         const bool valid = slot_to_pixel(f, pl, x, y);
         f3 o = mk3(0, 0, 0), d = mk3(0, 0, 1);
@@ -158,6 +161,7 @@ __global__ __launch_bounds__(kBlock) void k_primary_surface(DevScene sc, const S
 // the raygen of the shared-primary path: the chunk deal of k_raygen_trace_small (dealt_chunk, so every sub-queue holds the same entries in the same order), no trace and no path state.
 // A hitting path gets its queue entry and one 16-byte record in the place of the hit record: (pixel slot, seed.x, seed.y, -) — all the bounce-0 kernel needs beside the pixel's
 // shared record
+template <bool LIST>
 __global__ __launch_bounds__(kBlock) void k_raygen_shared(DevFrame f, DevPaths p, uint32_t* __restrict__ queue, uint32_t* __restrict__ qcount, uint32_t* __restrict__ gencount,
                                                           const unsigned long long* __restrict__ hits /* k_primary_surface */) {
     __shared__ uint32_t s_n[2];
@@ -169,8 +173,8 @@ __global__ __launch_bounds__(kBlock) void k_raygen_shared(DevFrame f, DevPaths p
     for (uint32_t k = 0, row0 = 0, c; row0 < nchunks; k++) {
         if (!dealt_chunk(f, k, row0, nchunks, c)) continue;
         const uint32_t sl = c / f.chunks_per_sample, cl = c - sl * f.chunks_per_sample;
-        const uint32_t pl = cl * kBlock + threadIdx.x;
-        const uint32_t pid = sl * f.npl + pl;
+        const uint32_t pl = real_slot<LIST>(f, cl * kBlock + threadIdx.x);       // the real slot: pixel, hit mask, and what bounce 0 looks the shared record up by
+        const uint32_t pid = sl * f.npl + cl * kBlock + threadIdx.x;
         uint32_t x = 0, y = 0;
         if (slot_to_pixel(f, pl, x, y)) generated++;
         const unsigned long long hm = hits[pl >> 6];                                      // wave-uniform; a set bit implies a valid slot

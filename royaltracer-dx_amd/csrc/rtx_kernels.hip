@@ -50,6 +50,7 @@ __device__ unsigned long long g_sec[36];          // [0,12) cycles, [12,24) acti
 #include "rtx_k_bounce_small.hpp"   // k_bounce_small
 #include "rtx_k_bounce_bvh.hpp"     // k_bounce_bvh, k_order_queues
 #include "rtx_k_film.hpp"           // k_accumulate, k_srgb8, k_debug_layer, k_pack_tiles, k_unpack_tiles
+#include "rtx_k_adaptive.hpp"       // k_adaptive_error, k_adaptive_compact
 #include "rtx_k_dbg.hpp"            // k_dbg_*
 
 namespace rtx {
@@ -79,20 +80,23 @@ int trace_workgroups_per_cu(const DevScene& sc) {
     return a < b ? a : b;
 }
 void launch_raygen(hipStream_t st, const DevFrame& f, const DevPaths& p, const CameraGPU* cam, uint32_t* queue, uint32_t* qcount, bool compact) {
-    hipLaunchKernelGGL(k_raygen, dim3(f.nblocks), dim3(kBlock), 0, st, f, p, cam, queue, qcount, compact ? 1u : 0u);
+    if (f.list) hipLaunchKernelGGL(k_raygen<true>, dim3(f.nblocks), dim3(kBlock), 0, st, f, p, cam, queue, qcount, compact ? 1u : 0u);
+    else hipLaunchKernelGGL(k_raygen<false>, dim3(f.nblocks), dim3(kBlock), 0, st, f, p, cam, queue, qcount, compact ? 1u : 0u);
 }
 void launch_packet_masks(hipStream_t st, const DevScene& sc, const DevFrame& f, const CameraGPU* cam, unsigned long long* masks) {
     const uint32_t nblk = f.npl / 64u;
     hipLaunchKernelGGL(k_packet_masks, dim3((nblk + 3u) / 4u), dim3(kBlock), 0, st, sc, f, cam, masks);
 }
 void launch_raygen_trace_small(hipStream_t st, const DevScene& sc, const DevFrame& f, const DevPaths& p, const CameraGPU* cam, uint32_t* queue, uint32_t* qcount, uint32_t* gencount, const unsigned long long* masks) {
-    hipLaunchKernelGGL(k_raygen_trace_small, dim3(f.nblocks), dim3(kBlock), trace_lds_bytes(sc), st, sc, sc.small, f, p, cam, queue, qcount, gencount, masks);
+    if (f.list) hipLaunchKernelGGL(k_raygen_trace_small<true>, dim3(f.nblocks), dim3(kBlock), trace_lds_bytes(sc), st, sc, sc.small, f, p, cam, queue, qcount, gencount, masks);
+    else hipLaunchKernelGGL(k_raygen_trace_small<false>, dim3(f.nblocks), dim3(kBlock), trace_lds_bytes(sc), st, sc, sc.small, f, p, cam, queue, qcount, gencount, masks);
 }
 void launch_primary_surface(hipStream_t st, const DevScene& sc, const DevFrame& f, const CameraGPU* cam, unsigned long long* masks, unsigned long long* hits, F4* rec) {
     hipLaunchKernelGGL(k_primary_surface, dim3(f.npl / kBlock), dim3(kBlock), trace_lds_bytes(sc), st, sc, sc.small, f, cam, masks, hits, rec);
 }
 void launch_raygen_shared(hipStream_t st, const DevFrame& f, const DevPaths& p, uint32_t* queue, uint32_t* qcount, uint32_t* gencount, const unsigned long long* hits) {
-    hipLaunchKernelGGL(k_raygen_shared, dim3(f.nblocks), dim3(kBlock), 0, st, f, p, queue, qcount, gencount, hits);
+    if (f.list) hipLaunchKernelGGL(k_raygen_shared<true>, dim3(f.nblocks), dim3(kBlock), 0, st, f, p, queue, qcount, gencount, hits);
+    else hipLaunchKernelGGL(k_raygen_shared<false>, dim3(f.nblocks), dim3(kBlock), 0, st, f, p, queue, qcount, gencount, hits);
 }
 // The launch of a persistent traversal kernel (k_trace_closest, k_trace_shadow): clamps `merge`, sizes the grid and maps (sc, heads) to the instantiation — stack kind, stealing,
 // compiled-in schedule, as std::integral_constants — and its dynamic LDS.  launch(stk, steal, sched, grid, lds_bytes, heads, merge) does the launch.
@@ -246,7 +250,16 @@ void launch_rs_p3_shade(hipStream_t st, const DevScene& sc, const DevFrame& f, c
     hipLaunchKernelGGL(k_rs_p3_shade, dim3(q.G), dim3(kBlock), 0, st, sc, f, q, rs_bufs(bufs), accum);
 }
 void launch_accumulate(hipStream_t st, uint32_t max_blocks, const DevFrame& f, const DevPaths& p, F4* accum) {
-    hipLaunchKernelGGL(k_accumulate, dim3(grid_for(f.npl, max_blocks)), dim3(kBlock), 0, st, f, p, accum);
+    hipLaunchKernelGGL(k_accumulate<false>, dim3(grid_for(f.npl, max_blocks)), dim3(kBlock), 0, st, f, p, accum, AdaptState{});
+}
+void launch_accumulate_list(hipStream_t st, uint32_t max_blocks, const DevFrame& f, const DevPaths& p, F4* accum, const AdaptState& ad) {
+    hipLaunchKernelGGL(k_accumulate<true>, dim3(grid_for(f.npl, max_blocks)), dim3(kBlock), 0, st, f, p, accum, ad);
+}
+void launch_adaptive_error(hipStream_t st, const DevFrame& f, const F4* accum, const AdaptState& ad, float threshold, float dark_floor) {
+    hipLaunchKernelGGL(k_adaptive_error, dim3(f.chunks_per_sample), dim3(kBlock), 0, st, f, accum, ad, threshold, dark_floor);
+}
+void launch_adaptive_compact(hipStream_t st, const DevFrame& f, const AdaptState& ad, uint32_t max_spp, uint32_t* list, uint32_t* out5) {
+    hipLaunchKernelGGL(k_adaptive_compact, dim3(1), dim3(kCompactBlock), 0, st, f, ad, max_spp, list, out5);
 }
 void launch_srgb8(hipStream_t st, const F4* accum, uint32_t npix, uint32_t* out) {
     hipLaunchKernelGGL(k_srgb8, dim3((npix + kBlock - 1) / kBlock), dim3(kBlock), 0, st, accum, npix, out);

@@ -52,6 +52,9 @@ struct DevFrame {
     // ReSTIR on shards: the pixel rectangle [hist_x0, hist_x1) x [hist_y0, hist_y1) in which this context holds last frame's history (rtx_ctx.hpp: rtx_ctx::rs.hist); the temporal
     // pass counts its reads outside it in *hist_stale (nullptr: not counted — unsharded frames hold the whole image)
     uint32_t hist_x0, hist_y0, hist_x1, hist_y1; unsigned long long* hist_stale;
+    // rtx_render_adaptive: a pass renders a frame whose slot space is the ACTIVE LIST — virtual slot v in [0, 256 n_active) is the real slot list[v >> 8] * 256 + (v & 255);
+    // npl and chunks_per_sample are the virtual frame's (256 n_active, n_active), pid = sl * npl + v.  Read by the list-aware instantiations only (nullptr everywhere else)
+    const uint32_t* list;
 };
 
 // TAPERED sub-queue sizes (RTX_OPT_TAPER).  Workgroups are dispatched in index order and every launch of a bounce ends when its LAST workgroup does; with equal sub-queues
@@ -140,6 +143,7 @@ struct RsQ {
 
 size_t trace_lds_bytes(const DevScene& sc);
 int trace_workgroups_per_cu(const DevScene& sc);   // occupancy of the persistent traversal kernels for this LDS layout (hipOccupancyMaxActiveBlocksPerMultiprocessor)
+// (every raygen launch and launch_accumulate: f.list != nullptr selects the list-aware instantiation, rtx_render_adaptive)
 void launch_raygen(hipStream_t, const DevFrame&, const DevPaths&, const CameraGPU* cam, uint32_t* queue, uint32_t* qcount, bool compact);
 void launch_trace_closest(hipStream_t, const DevFrame&, const DevScene&, const DevPaths&, uint32_t bounce, const uint32_t* queue, const uint32_t* qcount, uint32_t* heads, uint32_t merge = 1);   // merge: consecutive sub-queues per workgroup (MergedQ)
 void launch_packet_masks(hipStream_t, const DevScene&, const DevFrame&, const CameraGPU* cam, unsigned long long* masks);   // one 64-bit record mask per 8x8 pixel block of the shard
@@ -184,6 +188,12 @@ void launch_rs_p3_select(hipStream_t, const DevScene&, const DevFrame&, const Rs
 void launch_rs_p3_merge(hipStream_t, const DevScene&, const DevFrame&, const RsQ&, uint32_t* const bufs[6], uint32_t* shcnt);
 void launch_rs_p3_shade(hipStream_t, const DevScene&, const DevFrame&, const RsQ&, uint32_t* const bufs[6], F4* accum);
 void launch_accumulate(hipStream_t, uint32_t max_blocks, const DevFrame&, const DevPaths&, F4* accum);
+// ---- rtx_render_adaptive (rtx_k_adaptive.hpp); f is the REAL frame of the shard, state = the per-chunk words of the image (AdaptState) ----
+struct AdaptState { F4* half; uint32_t* count; uint32_t* flag; };   // half: W x H sums of the odd-id samples; per image chunk: samples taken, 0 sampling / 1 converged / 2 no valid pixel
+void launch_accumulate_list(hipStream_t, uint32_t max_blocks, const DevFrame&, const DevPaths&, F4* accum, const AdaptState&);   // the adaptive form: walks f.list, adds the odd ids into half too, bumps the chunks' counts
+void launch_adaptive_error(hipStream_t, const DevFrame&, const F4* accum, const AdaptState&, float threshold, float dark_floor);     // one workgroup per local chunk: the criterion -> flag
+// the unconverged chunks below max_spp that share the LOWEST count, in ascending order -> list; out[0] their number, [1] that count, [2] chunks converged, [3] unconverged at max_spp, [4] chunks with a valid pixel
+void launch_adaptive_compact(hipStream_t, const DevFrame&, const AdaptState&, uint32_t max_spp, uint32_t* list, uint32_t* out5);
 void launch_srgb8(hipStream_t, const F4* accum, uint32_t npix, uint32_t* out);
 void launch_debug_layer(hipStream_t, uint32_t max_blocks, const DevScene&, uint32_t width, uint32_t height, const CameraGPU* cam, uint32_t layer, uint32_t* out);
 void launch_pack_tiles(hipStream_t, uint32_t max_blocks, const DevFrame&, const F4* accum, F4* slab);

@@ -1,6 +1,6 @@
-// rtx_render.hip — rtx_render, the wavefront path tracer's frame: validate, plan the batches, size the buffers, enqueue every batch by one of three schedules (the fused
-// tiny-scene kernels, one k_bounce_bvh launch, or the separate trace / shade / shadow kernels per bounce), and collect the counters (finish_render).  Part of the C-ABI of
-// include/rtx.h (rtx_ctx.hpp).
+// rtx_render.hip — rtx_render, the wavefront path tracer's frame: validate, then (render_frame, shared with the passes of rtx_render_adaptive) plan the batches, size the
+// buffers, enqueue every batch by one of three schedules (the fused tiny-scene kernels, one k_bounce_bvh launch, or the separate trace / shade / shadow kernels per bounce),
+// and collect the counters (finish_render).  Part of the C-ABI of include/rtx.h (rtx_ctx.hpp).
 #include "rtx_ctx.hpp"
 
 namespace {
@@ -9,9 +9,9 @@ namespace {
 // taper levels, the workgroup count of the grid-wide launches, and whether the path state lives by queue position (compact)
 struct BatchPlan { uint32_t bspp, G, qchunks, taper_levels, max_blocks; bool compact; };
 
-BatchPlan plan_batches(const rtx_ctx* c, const rtx_params* p, const DevFrame& f, bool fused_bvh) {
+BatchPlan plan_batches(const rtx_ctx* c, uint32_t spp, const DevFrame& f, bool fused_bvh) {
     BatchPlan B{};
-    B.bspp = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(p->spp, c->opt.paths_per_batch / f.npl));
+    B.bspp = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(spp, c->opt.paths_per_batch / f.npl));
     // sub-queues per CU: shorter tails with more, but more per-workgroup overhead; the fused tiny-scene kernels (5 workgroups resident per
     // CU, longest-first dispatch, all bounces >= 1 in one launch) measured 18.39 / 18.15 / 18.13 / 18.30 / 18.36 ms at 24 / 32 / 40 / 48 / 64
     // (a 1/4 shard: 5.22 / 4.96 / 4.99 / 4.92 / 4.96 ms; 30 is an outlier, its sub-queues alias with the 8100 image regions); the
@@ -57,6 +57,7 @@ BatchPlan plan_batches(const rtx_ctx* c, const rtx_params* p, const DevFrame& f,
 struct FrameRun {
     DevPaths P; uint32_t* queue[2]; uint32_t* cnt; const CameraGPU* cam; hipStream_t st;
     const F4* prim_rec;           // RTX_OPT_SHARED_PRIMARY in effect: the per-pixel primary surface records of this call (nullptr: every sample traces its own camera ray)
+    uint32_t rec_npl;             // ... and their stream length: the shard's slots (a pass of rtx_render_adaptive renders a shorter, virtual frame: DevFrame::list)
     uint32_t G, mb, nee, nee1; bool compact, osort, stealing; size_t hstride, nheads;
     uint32_t* Q(uint32_t b) const { return cnt + (size_t)b * G; }
     uint32_t* S(uint32_t b, uint32_t j) const { return cnt + ((size_t)(mb + 1) + (size_t)b * nee1 + j) * G; }
@@ -72,7 +73,8 @@ int enqueue_tiny_fused(rtx_ctx* c, const FrameRun& R, const DevFrame& fb) {
     // bounces keep the ranking: survivors are a near-constant fraction)
     const uint32_t* order = nullptr;
     if (c->opt.lpt_order && R.G > 1) { launch_order_queues(st, R.Q(0), R.G, (uint32_t*)c->pt.d_order.p); order = (const uint32_t*)c->pt.d_order.p; }
-    { Timed t(c, RTX_K_BOUNCE); launch_bounce_small(st, c->dsc, fb, R.P, 0, 1, R.queue[0], R.queue[1], R.Q(0), R.S(0, 0), order, false, R.prim_rec); }
+    DevFrame f0 = fb; f0.npl = R.rec_npl;                 // bounce 0 reads npl only to find the record streams, by the REAL slot that k_raygen_shared noted
+    { Timed t(c, RTX_K_BOUNCE); launch_bounce_small(st, c->dsc, f0, R.P, 0, 1, R.queue[0], R.queue[1], R.Q(0), R.S(0, 0), order, false, R.prim_rec); }
     if (R.mb > 1) { Timed t(c, RTX_K_BOUNCE); launch_bounce_small(st, c->dsc, fb, R.P, 1, R.mb, R.queue[0], R.queue[1], R.Q(0), R.S(0, 0), order, c->opt.bounce_ring); }
     return RTX_OK;
 }
@@ -164,12 +166,29 @@ int rtx_render(rtx_ctx* c, const rtx_params* p) {
     memset(c->stats.kernel_items, 0, sizeof(c->stats.kernel_items));
     c->stats.rays_primary = c->stats.rays_extension = c->stats.rays_shadow = c->stats.paths = c->stats.primary_hits = 0; c->stats.render_ms = 0;
     if (p->spp == 0) return RTX_OK;
+    c->ad.pure = false;                        // u1 now holds samples that `half` does not know: rtx_render_adaptive refuses until the next clear
+    if ((r = render_frame(c, p, f, p->spp, nullptr))) return r;
+    // RTX_OPT_ASYNC on a caller-bound stream: the frame is enqueued, the caller goes on enqueueing its epilogue (rtx_pack_tiles -> collective -> rtx_unpack_tiles) behind it
+    // with no host join in between; statistics and the launch-size predictions of the next frame are collected at the next call that needs them (BIND)
+    if (c->opt.async && !c->own_stream) return RTX_OK;
+    return finish_render(c);
+}
+
+}  // extern "C"
+
+// steps 2 - 5 of a frame: `spp` samples for every slot of the frame, enqueued; finish_render collects.  lp: a pass of rtx_render_adaptive — the slots are those of the active
+// list (a virtual frame of 256 n_active slots that is planned, sized and dealt like a small shard), sample ids start at lp->sample_first, the accumulation is the adaptive form
+int render_frame(rtx_ctx* c, const rtx_params* p, const DevFrame& f_real, uint32_t spp, const ListPass* lp) {
+    int r = RTX_OK;
+    DevFrame f = f_real;
+    if (lp) { f.list = lp->list; f.npl = lp->n_active * 256u; f.chunks_per_sample = lp->n_active; }
+    const uint32_t sample_first = lp ? lp->sample_first : p->sample_base;
 
     // ---- 2. plan the batches ----
     const uint32_t nee = c->dsc.nlights ? p->nee_samples : 0;
     const bool tiny_fused = c->dsc.nsmall && c->opt.fused;
     const bool fused_bvh = !c->dsc.nsmall && c->opt.fused_bvh && c->opt.trace_sched >= 5u;      // (the other wave schedules are experiment knobs of the separate kernels)
-    const BatchPlan B = plan_batches(c, p, f, fused_bvh);
+    const BatchPlan B = plan_batches(c, spp, f, fused_bvh);
     const uint32_t bspp = B.bspp, G = B.G;
     const uint64_t cap64 = (uint64_t)f.npl * bspp;
     if (cap64 > 0x7FFFFFFFull) { c->err = "render: batch too large"; return RTX_ERR_INVALID; }
@@ -194,11 +213,11 @@ int rtx_render(rtx_ctx* c, const rtx_params* p) {
     R.hstride = (size_t)G + (G + 31) / 32;                                   // per trace launch: G fetch cursors + the exhausted bitmap
     R.nheads = R.stealing ? (size_t)p->max_bounces * (1 + std::max<uint32_t>(nee, 1)) * R.hstride : 0;
     if (R.stealing) HIPCHK(c, c->pt.d_heads.ensure(R.nheads * 4));
-    HIPCHK(c, c->pt.d_pmask.ensure(((size_t)f.npl / 64 + 1) * 8));
+    HIPCHK(c, c->pt.d_pmask.ensure(((size_t)f_real.npl / 64 + 1) * 8));        // (per real slot, like the shared-primary records: computed once per call)
     // RTX_OPT_SHARED_PRIMARY: without jitter the camera ray of a pixel is the same for every sample, so the fused tiny-scene path traces and reconstructs it once per call
     const bool shared_primary = tiny_fused && c->opt.shared_primary && !(p->flags & RTX_FLAG_JITTER);
-    if (shared_primary) { HIPCHK(c, c->pt.d_prim_rec.ensure(((size_t)f.npl * 3 + 1) * 16)); HIPCHK(c, c->pt.d_prim_hits.ensure(((size_t)f.npl / 64 + 1) * 8)); }
-    R.prim_rec = shared_primary ? (const F4*)c->pt.d_prim_rec.p : nullptr;
+    if (shared_primary) { HIPCHK(c, c->pt.d_prim_rec.ensure(((size_t)f_real.npl * 3 + 1) * 16)); HIPCHK(c, c->pt.d_prim_hits.ensure(((size_t)f_real.npl / 64 + 1) * 8)); }
+    R.prim_rec = shared_primary ? (const F4*)c->pt.d_prim_rec.p : nullptr; R.rec_npl = f_real.npl;
     const size_t shn = qtot * R.nee1;
     HIPCHK(c, c->pt.d_sh_o.ensure(shn * 16)); HIPCHK(c, c->pt.d_sh_d.ensure(shn * 16)); HIPCHK(c, c->pt.d_sh_c.ensure(shn * 16));
     DevPaths& P = R.P;
@@ -213,7 +232,7 @@ int rtx_render(rtx_ctx* c, const rtx_params* p) {
     R.queue[0] = (uint32_t*)c->pt.d_queue[0].p; R.queue[1] = (uint32_t*)c->pt.d_queue[1].p;
     const uint32_t mb = R.mb, nee1 = R.nee1;
     const size_t ncnt = ((size_t)(mb + 1) + (size_t)mb * nee1 + 1) * G;    // (FrameRun: Q rows, S rows, + one row: paths generated)
-    const uint32_t nbatches = (p->spp + bspp - 1) / bspp;
+    const uint32_t nbatches = (spp + bspp - 1) / bspp;
     HIPCHK(c, c->pt.d_counters.ensure(ncnt * 4));
     HIPCHK(c, c->pt.h_counters.ensure(ncnt * nbatches * 4));
     R.cnt = (uint32_t*)c->pt.d_counters.p;
@@ -228,18 +247,19 @@ int rtx_render(rtx_ctx* c, const rtx_params* p) {
     HIPCHK(c, hipEventRecord(c->ev.begin, st));
     HIPCHK(c, hipMemsetAsync(R.cnt, 0, ncnt * 4, st));
     // per 8x8 block resp. per pixel, shared by all samples and batches of this call; recomputed every call (camera, scene, size and shard may all have changed)
-    if (shared_primary) { Timed t(c, RTX_K_RAYGEN); launch_primary_surface(st, c->dsc, f, R.cam, (unsigned long long*)c->pt.d_pmask.p, (unsigned long long*)c->pt.d_prim_hits.p, (F4*)c->pt.d_prim_rec.p); }
-    else if (tiny_fused) launch_packet_masks(st, c->dsc, f, R.cam, (unsigned long long*)c->pt.d_pmask.p);
+    const bool tables_in_place = lp && !lp->first;             // a later pass of the same rtx_render_adaptive call
+    if (shared_primary && !tables_in_place) { Timed t(c, RTX_K_RAYGEN); launch_primary_surface(st, c->dsc, f_real, R.cam, (unsigned long long*)c->pt.d_pmask.p, (unsigned long long*)c->pt.d_prim_hits.p, (F4*)c->pt.d_prim_rec.p); }
+    else if (tiny_fused && !shared_primary && !tables_in_place) launch_packet_masks(st, c->dsc, f_real, R.cam, (unsigned long long*)c->pt.d_pmask.p);
     for (uint32_t bi = 0; bi < nbatches; bi++) {
         DevFrame fb = f;
-        fb.sample_first = p->sample_base + bi * bspp;
-        fb.batch_spp = std::min(bspp, p->spp - bi * bspp);
+        fb.sample_first = sample_first + bi * bspp;
+        fb.batch_spp = std::min(bspp, spp - bi * bspp);
         fb.interleave = 0;                                     // (k_raygen only: the tiny-scene raygen keeps its packet order)
         if (c->opt.sample_interleave) while (fb.interleave < 4u && !((fb.batch_spp >> fb.interleave) & 1u)) fb.interleave++;       // S = the largest power of two <= 16 dividing the batch's sample count
         r = tiny_fused ? enqueue_tiny_fused(c, R, fb) : fused_bvh ? enqueue_fused_bvh(c, R, fb) : enqueue_bounces(c, R, fb);
         if (r) return r;
         // ---- 5. accumulate, copy the counters ----
-        { Timed t(c, RTX_K_ACCUM); launch_accumulate(st, B.max_blocks, fb, P, c->accum_ptr()); }
+        { Timed t(c, RTX_K_ACCUM); if (lp) launch_accumulate_list(st, B.max_blocks, fb, P, c->accum_ptr(), lp->state); else launch_accumulate(st, B.max_blocks, fb, P, c->accum_ptr()); }
         HIPCHK(c, hipMemcpyAsync(c->pt.h_counters.as<uint32_t>() + (size_t)bi * ncnt, R.cnt, ncnt * 4, hipMemcpyDeviceToHost, st));
     }
     HIPCHK(c, hipEventRecord(c->ev.end, st));
@@ -247,13 +267,14 @@ int rtx_render(rtx_ctx* c, const rtx_params* p) {
     aux_join.armed = false;                    // the main stream waited for the last shadow launch (ev_shadow_done) before the accumulation: stream order covers the aux stream
     c->pt.pending.active = true; c->pt.pending.ncnt = ncnt; c->pt.pending.nbatches = nbatches; c->pt.pending.G = G; c->pt.pending.mb = mb; c->pt.pending.nee = nee; c->pt.pending.nee1 = nee1;
     c->pt.pending.fused = tiny_fused; c->pt.pending.fused_bvh = fused_bvh;
-    // RTX_OPT_ASYNC on a caller-bound stream: the frame is enqueued, the caller goes on enqueueing its epilogue (rtx_pack_tiles -> collective -> rtx_unpack_tiles) behind it
-    // with no host join in between; statistics and the launch-size predictions of the next frame are collected at the next call that needs them (BIND)
-    if (c->opt.async && !c->own_stream) return RTX_OK;
-    return finish_render(c);
+    return RTX_OK;
 }
 
-}  // extern "C"
+// the kernel times of the launches bracketed since the last collection (RTX_OPT_KERNEL_TIMING); the stream must have passed them
+void collect_timed(rtx_ctx* c) {
+    for (const TimedLaunch& t : c->timed) { float m = 0.0f; if (hipEventElapsedTime(&m, t.a, t.b) == hipSuccess) c->stats.kernel_ms[t.cls] += m; }
+    c->timed.clear();
+}
 
 int finish_render(rtx_ctx* c) {
     if (!c->pt.pending.active) return RTX_OK;
@@ -262,8 +283,8 @@ int finish_render(rtx_ctx* c) {
     const bool fused = c->pt.pending.fused, fused_bvh = c->pt.pending.fused_bvh;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     float ms = 0.0f;
-    if (hipEventElapsedTime(&ms, c->ev.begin, c->ev.end) == hipSuccess) c->stats.render_ms = ms;
-    for (const TimedLaunch& t : c->timed) { float m = 0.0f; if (hipEventElapsedTime(&m, t.a, t.b) == hipSuccess) c->stats.kernel_ms[t.cls] += m; }
+    if (hipEventElapsedTime(&ms, c->ev.begin, c->ev.end) == hipSuccess) c->stats.render_ms += ms;      // (summed over the passes of rtx_render_adaptive; rtx_render starts from zero)
+    collect_timed(c);
     if (!fused && !fused_bvh) { c->pt.pred_paths = 0; c->pt.pred_q.assign(mb, 0); c->pt.pred_s.assign((size_t)mb * nee1, 0); c->pt.pred_nee1 = nee1; }
     for (uint32_t bi = 0; bi < nbatches; bi++) {
         const uint32_t* h = c->pt.h_counters.as<uint32_t>() + (size_t)bi * ncnt;

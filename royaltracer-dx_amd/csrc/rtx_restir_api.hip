@@ -134,6 +134,7 @@ int rtx_render_v6_pass1(rtx_ctx* c, const rtx_params* p) {
     if (r) return r;
     if (p->max_bounces > 64 || p->nee_samples > 16) { c->err = "params: max_bounces <= 64, nee_samples <= 16"; return RTX_ERR_INVALID; }
     if ((r = ensure_accum(c, p->width, p->height, false))) return r;
+    c->ad.pure = false;                        // (rtx_render_adaptive: u1 gets samples its second sum does not hold)
     const size_t slots = rtx_pass1_slots(p->width, p->height);
     if ((r = p1_alloc(c, slots))) return r;
     stats_begin(c);
@@ -191,6 +192,7 @@ int rtx_render_restir(rtx_ctx* c, const rtx_params* p) {
     const bool sharded = p->shard_count > 1;
     if (sharded && p->spp != 1) { c->err = "render_restir: on shards the history has to be exchanged after every frame (rtx_restir_pack_state / unpack_state): spp must be 1"; return RTX_ERR_INVALID; }
     if ((r = ensure_accum(c, p->width, p->height, false))) return r;
+    c->ad.pure = false;                        // (rtx_render_adaptive: u1 gets samples its second sum does not hold)
     const uint32_t* halo = nullptr; const uint32_t* own = nullptr; uint32_t nhalo = 0, nown = 0;
     // (tiny scenes keep the slot order when unsharded: the Cornell frame measured 3.19 ms that way and 3.69 ms through the Morton list; the BVH scenes gain ~1 %)
     if (sharded || (c->opt.restir_wave && !c->dsc.nsmall)) {

@@ -13,6 +13,8 @@
 //                   [--hide i[,j...]] hides the listed instances before the first frame (rtx_set_instance_visible: InstanceMask 0, TopLevelASGenerator.cpp:198)
 //                   [--blink i] toggles the visibility of instance i before every frame after the first and prints the commit's time: a refit, never a rebuild
 //                   [--only-rank r] with --gpus N --gather copy: rank r of N alone, through the same host path (measurement on one GPU: tools/shard_time.py native=1)
+//                   [--adaptive THRESHOLD [--min-spp N] [--step-spp N]]   rtx_render_adaptive instead of rtx_render (path tracer, one GPU): every 256-slot chunk is sampled until its
+//                   pixels pass the noise threshold, --spp is the cap (defaults: min 8, step 8; both even); prints the result struct per frame
 //                   [--gpus N [--devices 0,1,..] [--gather rccl|copy]]   the native N-GPU frame (MultiGpu.h): one process, N contexts, pixel tiles
 //                   round-robin, ONE RCCL all-gather per frame; `--gather copy` replaces the collective by device copies (several ranks on one GPU: tests)
 #include <algorithm>
@@ -33,6 +35,7 @@ int main(int argc, char** argv) {
     UINT w = 1920, h = 1080, spp = 1, frames = 1, bounces = 8, nee = 1; int device = 0; bool lambert = false;
     int gpus = 1; std::string devlist, gather = "rccl", mode = "pt"; bool literal = false, nee_set = false, bounces_set = false, force_gather = false; float orbit = 0.0f, spin = 0.0f; int only_rank = -1; UINT halo = 0;
     std::vector<UINT> hide; int blink = -1;
+    bool adaptive = false; rtx_adaptive ad{}; ad.min_spp = 8; ad.step_spp = 8;
     for (int i = 1; i < argc; i++) {
         auto arg = [&](const char* k) { return !strcmp(argv[i], k) && i + 1 < argc; };
         if (arg("--scene")) scene = argv[++i]; else if (arg("--obj")) { objs = argv[++i]; scene = "obj"; } else if (arg("--mtl")) mtl = argv[++i];
@@ -40,6 +43,7 @@ int main(int argc, char** argv) {
         else if (arg("--frames")) frames = atoi(argv[++i]); else if (arg("--bounces")) { bounces = atoi(argv[++i]); bounces_set = true; } else if (arg("--nee")) { nee = atoi(argv[++i]); nee_set = true; }
         else if (arg("--mode")) mode = argv[++i]; else if (arg("--orbit")) orbit = (float)atof(argv[++i]); else if (arg("--spin")) spin = (float)atof(argv[++i]); else if (arg("--only-rank")) only_rank = atoi(argv[++i]); else if (!strcmp(argv[i], "--literal")) literal = true; else if (!strcmp(argv[i], "--force-gather")) force_gather = true;
         else if (arg("--hide")) { std::stringstream ss(argv[++i]); std::string t; while (std::getline(ss, t, ',')) hide.push_back((UINT)atoi(t.c_str())); } else if (arg("--blink")) blink = atoi(argv[++i]);
+        else if (arg("--adaptive")) { adaptive = true; ad.threshold = (float)atof(argv[++i]); } else if (arg("--min-spp")) ad.min_spp = (uint32_t)atoi(argv[++i]); else if (arg("--step-spp")) ad.step_spp = (uint32_t)atoi(argv[++i]);
         else if (arg("--halo")) halo = (UINT)atoi(argv[++i]); else if (arg("--gpus")) gpus = atoi(argv[++i]); else if (arg("--devices")) devlist = argv[++i]; else if (arg("--gather")) gather = argv[++i];
         else if (arg("--out")) out = argv[++i]; else if (arg("--device")) device = atoi(argv[++i]); else if (!strcmp(argv[i], "--lambert")) lambert = true;
         else { fprintf(stderr, "unknown argument %s\n", argv[i]); return 2; }
@@ -47,6 +51,7 @@ int main(int argc, char** argv) {
     if (mode != "pt" && mode != "restir") { fprintf(stderr, "--mode must be pt or restir\n"); return 2; }
     const bool restir = mode == "restir";
     if (restir) { if (!nee_set) nee = 4; if (!bounces_set) bounces = 3; }
+    if (adaptive && (restir || gpus > 1 || !devlist.empty())) { fprintf(stderr, "--adaptive is the path tracer on one GPU (no --mode restir, --gpus, --devices)\n"); return 2; }
     // camera of frame f: the scene's eye rotated by f * orbit degrees about the vertical axis through the look-at point
     auto orbit_eye = [&](const Scene& sc, UINT f) {
         const float a = orbit * 3.14159265f / 180.0f * (float)f, cs = cosf(a), sn = sinf(a);
@@ -131,7 +136,15 @@ int main(int argc, char** argv) {
             if (orbit != 0.0f) { Scene tmp; tmp.eye = eye0; tmp.center = ctr0; tmp.up = up0; nv_helpers_dx12::CameraManip.setLookat(orbit_eye(tmp, f), ctr0, up0); }
             const bool blinked = blink >= 0 && f > 0;
             if (blinked) { blink_hidden = !blink_hidden; r.SetInstanceVisible((UINT)blink, !blink_hidden); if (!restir) rtx_clear_accum(r.Context(), w, h); }
-            r.OnUpdate(); r.Params().sample_base = 1 + f * spp; r.OnRender();
+            r.OnUpdate(); r.Params().sample_base = 1 + f * spp;
+            if (adaptive) {                                     // --spp is the cap; a frame after the first continues the image only if the cap grows, so each frame starts afresh
+                rtx_params ap = r.Params(); ap.frame_seed = f + 1; ad.max_spp = spp;
+                rtx_adaptive_result res{};
+                if (f > 0) rtx_clear_accum(r.Context(), w, h);
+                if (rtx_render_adaptive(r.Context(), &ap, &ad, &res) != RTX_OK) throw std::runtime_error(std::string("rtx_render_adaptive: ") + rtx_last_error(r.Context()));
+                printf("adaptive: threshold %g, min %u / step %u / max %u spp: %u passes, %u chunks (%u converged, %u at max), %llu pixel-samples = %.2f spp on average\n", ad.threshold, ad.min_spp, ad.step_spp, ad.max_spp,
+                       res.passes, res.chunks, res.chunks_converged, res.chunks_at_max, (unsigned long long)res.pixel_samples, (double)res.pixel_samples / ((double)w * h));
+            } else r.OnRender();
             if (blinked) printf("visibility commit: %.3f ms\n", r.LastRefitMs());
             rtx_stats s = r.Stats();
             double rays = (double)(s.rays_primary + s.rays_extension + s.rays_shadow);
