@@ -180,6 +180,8 @@ enum { RTX_OPT_KERNEL_TIMING = 1,    /* 0/1: bracket every launch with hipEvents
                                         there are computed once per pixel and rtx_render call (k_primary_surface) instead of once per sample; raygen only enqueues the hitting paths and
                                         bounce 0 starts from the pixel's record.  0: every sample traces and reconstructs its own.  Never changes a result.  rays_primary still counts
                                         one camera ray per sample */
+       RTX_OPT_DENOISE_LDS_STEP = 42,/* tuning, rtx_denoise: the levels with step <= this value (0, 1, 2 or 4) stage their tile and its halo in LDS, the coarser ones read every tap from global memory.
+                                        Default 4: every step that fits (measured faster than the direct form at steps 1, 2 and 4: profiles/denoise_time.md).  Never changes a result */
        RTX_OPT_BLOCKS_PER_CU = 12    /* tuning: workgroups (= private sub-queues) per compute unit; default 0 = auto: 40 (tiny scenes) / 32 at full frame size (8 measured 4-7 % slower there: tail imbalance), fewer — down to 8 — when a batch is so
                                         small (a shard) that a sub-queue would start with fewer than ~16 / ~8 chunks of 256 paths */ };
 
@@ -277,6 +279,53 @@ typedef struct rtx_adaptive_result {
     uint64_t pixel_samples;                /* valid pixel-samples this call added (== rtx_stats.paths) */
 } rtx_adaptive_result;
 int  rtx_render_adaptive(rtx_ctx*, const rtx_params*, const rtx_adaptive*, rtx_adaptive_result* out /* may be NULL */);
+/* DENOISING (new; the reference shows the accumulated mean as it is): an edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) over the mean of u1, guided by the first
+   hit of the pixel-corner primary ray.  u1 is only read: progressive accumulation goes on after a denoise.  The result is a second RGBA32F W x H image (xyz, w = 1.0).
+   All arithmetic is float32 in exactly the written order (no contraction); tests/test_denoise_ref.py replays it in numpy and tests/test_denoise.py holds the device to it bit for bit.
+   GUIDES per pixel: the ray, tmin and trace of rtx_read_layer's layers 10-17 (pixel corner, jitter-free whatever RTX_FLAG_JITTER says; hidden instances are invisible):
+   P = world position, n = shading normal, mat = material id of the surface there.  A pixel is FILTERABLE when the ray hits, mat < material count, no component of that
+   material's Ke is > 0 and u1.w > 0; every other pixel (miss, emitter seen directly, no samples) passes through: its output is its input at every level and it contributes to no neighbour.
+   INPUT colour c = u1.xyz / max(u1.w, 1).  LEVELS i = 0 .. levels-1, step s = 1 << i, each reading the previous one's output.  For a filterable centre p the taps are
+   q = p + s (dx, dy), dy = -2 .. 2 outer, dx = -2 .. 2 inner (row-major, the centre included; the centre is a tap like any other), h = (1/16, 1/4, 3/8, 1/4, 1/16).
+   A tap counts if q is inside the image, filterable, and mat_q == mat_p; for a tap that counts
+       dn = (n_p.x*n_q.x + n_p.y*n_q.y) + n_p.z*n_q.z
+       wn = max(dn, 0), then wn = wn * wn, normal_power_log2 times
+       d  = P_q - P_p
+       dp = |(n_p.x*d.x + n_p.y*d.y) + n_p.z*d.z|
+       wp = max(1 - dp * inv_sigma_plane, 0)
+       dc = (|c_q.x - c_p.x| + |c_q.y - c_p.y|) + |c_q.z - c_p.z|                (this level's input colours)
+       wc = max(1 - dc * (inv_sigma_color * s), 0)                               (sigma_color halves per level; * s is exact)
+       w  = ((h[dy+2] * h[dx+2]) * wn) * (wp * wc)
+       sum.xyz = sum.xyz + w * c_q.xyz ;  sumw = sumw + w                        (sequential, in tap order, from 0)
+   and the output is sum.xyz / sumw (the centre tap has wp = wc = 1 and wn = |n|^(2 << normal_power_log2), so sumw > 0).  inv_sigma_* = 1.0f / sigma_*, once, on the host.
+   rtx_denoise works on whichever u1 is bound and on the whole image (no shard fields: denoise after rtx_unpack_tiles).  Like rtx_pack_tiles it is synchronous on the context's own
+   stream and only ENQUEUES on a caller-bound one, behind a frame that RTX_OPT_ASYNC left in flight, by stream order — unless `out` is given: the counts are read back, which joins
+   the stream up to the denoise.  The guides are recomputed by every call (one primary ray per pixel).
+   Errors: RTX_ERR_STATE before commit (also: a scene edit not yet committed), camera or any accumulation; RTX_ERR_INVALID for a size other than the accumulation buffer's, for
+   levels > 8, normal_power_log2 > 7, a sigma that is negative, not finite or whose reciprocal is not finite, or a nonzero reserved word.  A failed call leaves u1 and the
+   previous denoised image untouched.  rtx_read_denoised* is RTX_ERR_STATE before a successful rtx_denoise and once the accumulation buffer has another size than the denoised image.
+   DEFAULT sigma_plane = 2^-6 * the largest extent of the committed scene's bounding box, defined by these float32 operations: for every instance (hidden ones included) and every vertex v
+   of its mesh, world_k = ((v.x * m[k] + v.y * m[4+k]) + v.z * m[8+k]) + m[12+k], k = 0, 1, 2, m = the instance's objectToWorld; lo / hi = min / max over all of them;
+   extent_k = hi_k - lo_k; sigma_plane = 0.015625f * max(extent). */
+typedef struct rtx_denoise_params {
+    uint32_t levels;              /* 1..8; 0 => 5 */
+    uint32_t normal_power_log2;   /* 1..7; 0 => 5 (cos^32) */
+    float    sigma_color;         /* > 0; 0 => 0.5 */
+    float    sigma_plane;         /* world units, > 0; 0 => 2^-6 * largest extent of the committed scene's bounding box */
+    uint32_t reserved[4];         /* 0 */
+} rtx_denoise_params;
+typedef struct rtx_denoise_result {
+    uint32_t levels;
+    uint32_t pixels_filtered;
+    uint32_t pixels_passed;
+    double   guides_ms;           /* hipEvent, 0 unless RTX_OPT_KERNEL_TIMING */
+    double   filter_ms;           /* hipEvent, 0 unless RTX_OPT_KERNEL_TIMING */
+} rtx_denoise_result;
+int  rtx_denoise(rtx_ctx*, uint32_t width, uint32_t height, const rtx_denoise_params* /* NULL = all defaults */, rtx_denoise_result* /* may be NULL */);
+int  rtx_read_denoised(rtx_ctx*, float* rgba32f, size_t bytes);
+int  rtx_read_denoised_srgb8(rtx_ctx*, uint8_t* rgba8, size_t bytes);   /* k_srgb8 over the denoised image */
+/* the guides as the filter reads them: per pixel P3, material word as uint bits (0xFFFFFFFF = not filterable by geometry; P and n are then 0), n3, 0 */
+int  rtx_debug_denoise_guides(rtx_ctx*, uint32_t width, uint32_t height, float* out8 /* W*H*8 */);
 /* The reference's OWN first pass, literally: RayGen of RayGen_v6_pass1.hlsl:48-190 (first DispatchRays,
    Renderer.cpp:651-654): primary hit, SampleRIS (Sampler_v6.hlsl:653-736), visibility, SamplePathSimple
    (Path_Sampler_v6.hlsl:3-286).  params: nee_samples = nee_samples_DI = nee_samples (Common_v6.hlsl:8-9, reference 4),

@@ -45,6 +45,7 @@ OPT_GPU_BUILD = 38
 OPT_STACK_CAP = 39
 OPT_DEFORM_REBUILD = 40
 OPT_SHARED_PRIMARY = 41
+OPT_DENOISE_LDS_STEP = 42
 
 
 class RtxError(RuntimeError):
@@ -122,6 +123,20 @@ class AdaptiveResult(C.Structure):
 
 
 _sig("rtx_render_adaptive", C.c_int, _vp, C.POINTER(Params), C.POINTER(Adaptive), C.POINTER(AdaptiveResult))
+class DenoiseParams(C.Structure):
+    """rtx_denoise_params (include/rtx.h); 0 = the default of a field"""
+    _fields_ = [("levels", C.c_uint32), ("normal_power_log2", C.c_uint32), ("sigma_color", C.c_float), ("sigma_plane", C.c_float), ("reserved", C.c_uint32 * 4)]
+
+
+class DenoiseResult(C.Structure):
+    """rtx_denoise_result (include/rtx.h)"""
+    _fields_ = [("levels", C.c_uint32), ("pixels_filtered", C.c_uint32), ("pixels_passed", C.c_uint32), ("guides_ms", C.c_double), ("filter_ms", C.c_double)]
+
+
+_sig("rtx_denoise", C.c_int, _vp, _u32, _u32, C.POINTER(DenoiseParams), C.POINTER(DenoiseResult))
+_sig("rtx_read_denoised", C.c_int, _vp, _vp, C.c_size_t)
+_sig("rtx_read_denoised_srgb8", C.c_int, _vp, _vp, C.c_size_t)
+_sig("rtx_debug_denoise_guides", C.c_int, _vp, _u32, _u32, _vp)
 _sig("rtx_render_v6_pass1", C.c_int, _vp, C.POINTER(Params))
 _sig("rtx_render_restir", C.c_int, _vp, C.POINTER(Params))
 _sig("rtx_restir_reset", C.c_int, _vp)
@@ -592,6 +607,31 @@ class Context:
         self._ck(lib.rtx_read_accum(self._h, _ptr(out), out.nbytes), "rtx_read_accum")
         return out
 
+    def denoise(self, width, height, levels=0, sigma_color=0.0, sigma_plane=0.0, normal_power_log2=0, result=True):
+        """rtx_denoise: the edge-avoiding a-trous filter over the mean of u1, guided by first-hit position, normal and material (0 = a field's default) -> DenoiseResult.
+        result=False passes no result struct: on a caller-bound stream the call then only enqueues (no host join) and returns None"""
+        dp = DenoiseParams(int(levels), int(normal_power_log2), float(sigma_color), float(sigma_plane))
+        res = DenoiseResult() if result else None
+        self._ck(lib.rtx_denoise(self._h, int(width), int(height), C.byref(dp), C.byref(res) if result else None), "rtx_denoise")
+        return res
+
+    def read_denoised(self):
+        """the denoised image (H, W, 4) float32: xyz, w = 1"""
+        out = np.zeros((self.height, self.width, 4), np.float32)
+        self._ck(lib.rtx_read_denoised(self._h, _ptr(out), out.nbytes), "rtx_read_denoised")
+        return out
+
+    def read_denoised_srgb8(self):
+        out = np.zeros((self.height, self.width, 4), np.uint8)
+        self._ck(lib.rtx_read_denoised_srgb8(self._h, _ptr(out), out.nbytes), "rtx_read_denoised_srgb8")
+        return out
+
+    def denoise_guides(self, width, height):
+        """the filter's guides (H, W, 8) float32: P3, material word as uint bits (0xFFFFFFFF = not filterable by geometry, P and n then 0), n3, 0"""
+        out = np.zeros((height, width, 8), np.float32)
+        self._ck(lib.rtx_debug_denoise_guides(self._h, int(width), int(height), _ptr(out)), "rtx_debug_denoise_guides")
+        return out
+
     def render_v6_pass1(self, params):
         """the reference's own pass 1 (RIS direct light + SamplePathSimple); see rtx_render_v6_pass1"""
         self.width, self.height = params.width, params.height
@@ -828,6 +868,20 @@ class Renderer:
         out = np.zeros((self.height, self.width, 4), np.float32)
         self._ck(lib.rtxh_renderer_read_accum(self._h, _ptr(out), out.nbytes), "read_accum")
         return out
+
+    def read_denoised(self, **kw):
+        """rtx_denoise over the accumulated image (every default unless Context.denoise's keywords say otherwise) and its read: (H, W, 4) float32, w = 1; the accumulation is left alone"""
+        h = lib.rtxh_renderer_context(self._h)
+        if not h:
+            raise RtxError("read_denoised: renderer not initialised")
+        c = Context.__new__(Context)                    # a borrowed view of the renderer's context: never closed from here
+        c._h, c.width, c.height = None, self.width, self.height
+        try:
+            c._h = h
+            c.denoise(self.width, self.height, **kw)
+            return c.read_denoised()
+        finally:
+            c._h = None
 
     def read_output(self):
         out = np.zeros((self.height, self.width, 4), np.uint8)

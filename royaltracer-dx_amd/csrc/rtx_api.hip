@@ -171,6 +171,7 @@ int rtx_set_option(rtx_ctx* c, int option, int64_t value) {
     case RTX_OPT_RESTIR_CHUNKS: if (value < 1 || value > 64) { c->err = "restir_chunks must be in [1, 64]"; return RTX_ERR_INVALID; } c->opt.restir_chunks = (uint32_t)value; return RTX_OK;
     case RTX_OPT_TRACE_SCHED: if (value > 7) { c->err = "trace_sched must be in [0, 7]"; return RTX_ERR_INVALID; } c->opt.trace_sched = (uint32_t)value; options_to_scene(c, c->committed); return RTX_OK;
     case RTX_OPT_REFILL_MIN: if (value < 1 || value > 64) { c->err = "refill_min must be in [1, 64]"; return RTX_ERR_INVALID; } c->opt.refill_min = (uint32_t)value; options_to_scene(c, c->committed); return RTX_OK;
+    case RTX_OPT_DENOISE_LDS_STEP: if (value != 0 && value != 1 && value != 2 && value != 4) { c->err = "denoise_lds_step must be 0, 1, 2 or 4"; return RTX_ERR_INVALID; } c->dn.lds_step = (uint32_t)value; return RTX_OK;
     default: c->err = "unknown option"; return RTX_ERR_INVALID;
     }
 }

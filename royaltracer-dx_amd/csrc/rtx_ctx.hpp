@@ -3,6 +3,7 @@
 //   rtx_commit.hip       rtx_commit_scene (host or GPU build, GPU refit), the scene cache, finalise_scene
 //   rtx_render.hip       rtx_render (the wavefront path tracer), render_frame and finish_render
 //   rtx_adaptive.hip     rtx_render_adaptive: passes of render_frame over the chunks that have not converged
+//   rtx_denoise.hip      rtx_denoise and the reads of the denoised image
 //   rtx_restir_api.hip   the ReSTIR frames, their work lists and lanes, the history / halo exchange between shards
 //   rtx_debug.hip        the rtx_debug_* entry points
 // Ownership: every resource of a context is a member of an owning type (rtx_devmem.hpp, rtx_staging.hpp), so `delete c` releases it all.
@@ -146,6 +147,14 @@ struct rtx_ctx {
         bool cleared = true;            // u1 was cleared since the state above was last used: the next rtx_render_adaptive zeroes it
         uint32_t key[3] = {0, 0, 0};    // width, height, tile size the state is laid out for
     } ad;
+
+    // ---- the denoiser (rtx_denoise.hip) ----
+    struct Denoise {
+        DevBuf d_guides, d_pp[2], d_out, d_partial, d_count;     // 32 B of guides per pixel, the two ping-pong images, the denoised image; per-workgroup counts of the first level and their sum
+        uint32_t w = 0, h = 0; bool valid = false;                // size of the denoised image; a successful rtx_denoise wrote it
+        Events ev;                                                // guides / filter begin and end (RTX_OPT_KERNEL_TIMING), rewound per call
+        uint32_t lds_step = 4;                                    // RTX_OPT_DENOISE_LDS_STEP
+    } dn;
 
     // ---- ReSTIR (rtx_restir_api.hip) ----
     struct Restir {

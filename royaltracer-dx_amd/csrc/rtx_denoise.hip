@@ -1,0 +1,132 @@
+// rtx_denoise.hip — rtx_denoise: the edge-avoiding a-trous filter over the mean of u1, and the reads of the denoised image.  Validate, guides (k_denoise_guides, one primary
+// ray per pixel, every call), then one k_denoise_level per level between u1, two ping-pong images and the denoised image.  Part of the C-ABI of include/rtx.h (rtx_ctx.hpp);
+// the kernels and the tap arithmetic: rtx_k_denoise.hpp.
+#include <cmath>
+#include "rtx_ctx.hpp"
+
+// the default sigma_plane's box, by the float32 operations include/rtx.h names (this file is compiled without contraction): every vertex of every instance's mesh
+static float scene_largest_extent(const SceneHost& H) {
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (const InstHost& in : H.insts) {
+        const std::vector<float>& v = H.meshes[in.mesh].verts; const float* m = in.o2w;
+        for (size_t i = 0; i + 7 <= v.size(); i += 7)
+            for (int k = 0; k < 3; k++) {
+                const float w = ((v[i] * m[k] + v[i + 1] * m[4 + k]) + v[i + 2] * m[8 + k]) + m[12 + k];
+                lo[k] = w < lo[k] ? w : lo[k]; hi[k] = w > hi[k] ? w : hi[k];
+            }
+    }
+    const float e[3] = {hi[0] - lo[0], hi[1] - lo[1], hi[2] - lo[2]};
+    return std::max(e[0], std::max(e[1], e[2]));
+}
+
+// a denoised image of the accumulation buffer's size exists
+static bool have_denoised(rtx_ctx* c) { return c->dn.valid && c->dn.d_out.p && c->dn.w == c->acc_w && c->dn.h == c->acc_h; }
+
+extern "C" {
+
+int rtx_denoise(rtx_ctx* c, uint32_t width, uint32_t height, const rtx_denoise_params* dp, rtx_denoise_result* out) {
+    // ---- 1. validate: a call that fails leaves u1 and the previous denoised image untouched ----
+    BIND_NOWAIT(c);                       // stream-ordered behind an enqueued rtx_render (RTX_OPT_ASYNC): no host join
+    if (!c->committed) { c->err = "denoise: scene not committed"; return RTX_ERR_STATE; }
+    if (!c->camera_set) { c->err = "denoise: camera not set"; return RTX_ERR_STATE; }
+    if (!c->accum_ptr() || !c->acc_w || !c->acc_h) { c->err = "denoise: no accumulation buffer yet"; return RTX_ERR_STATE; }
+    if (width != c->acc_w || height != c->acc_h) { c->err = "denoise: the size differs from the accumulation buffer's"; return RTX_ERR_INVALID; }
+    const size_t npix = (size_t)width * height;
+    if (npix > 0x7FFFFFFFull) { c->err = "denoise: image too large"; return RTX_ERR_INVALID; }
+    if (c->ext_accum && c->ext_accum_bytes < npix * 16) { c->err = "bound accumulation buffer is smaller than width*height*16 bytes"; return RTX_ERR_INVALID; }
+    rtx_denoise_params q{};
+    if (dp) q = *dp;
+    for (uint32_t r : q.reserved) if (r) { c->err = "denoise: reserved words must be 0"; return RTX_ERR_INVALID; }
+    if (q.levels > 8 || q.normal_power_log2 > 7) { c->err = "denoise: levels must be in [1, 8] and normal_power_log2 in [1, 7] (0 = default)"; return RTX_ERR_INVALID; }
+    if (!q.levels) q.levels = 5;
+    if (!q.normal_power_log2) q.normal_power_log2 = 5;
+    if (!(q.sigma_color >= 0.0f) || !(q.sigma_plane >= 0.0f) || std::isinf(q.sigma_color) || std::isinf(q.sigma_plane)) { c->err = "denoise: sigma_color and sigma_plane must be finite and > 0 (0 = default)"; return RTX_ERR_INVALID; }
+    if (q.sigma_color == 0.0f) q.sigma_color = 0.5f;
+    if (q.sigma_plane == 0.0f) q.sigma_plane = 0.015625f * scene_largest_extent(c->host);
+    const float inv_color = 1.0f / q.sigma_color, inv_plane = 1.0f / q.sigma_plane;
+    if (!std::isfinite(inv_color) || !std::isfinite(inv_plane) || !std::isfinite(inv_color * (float)(1u << (q.levels - 1u)))) { c->err = "denoise: a sigma is too small (or the scene has no extent for the default sigma_plane)"; return RTX_ERR_INVALID; }
+
+    // ---- 2. memory: allocated on first use, resized with the image ----
+    rtx_ctx::Denoise& D = c->dn;
+    const uint32_t nwg = denoise_workgroups(width, height);
+    HIPCHK(c, D.d_guides.ensure(npix * 32)); HIPCHK(c, D.d_partial.ensure((size_t)nwg * 4)); HIPCHK(c, D.d_count.ensure(16));
+    if (q.levels > 1) HIPCHK(c, D.d_pp[0].ensure(npix * 16));
+    if (q.levels > 2) HIPCHK(c, D.d_pp[1].ensure(npix * 16));
+    HIPCHK(c, D.d_out.ensure(npix * 16));
+    D.valid = false; D.w = width; D.h = height;
+
+    // ---- 3. guides, then the levels: u1 -> pp[0] -> pp[1] -> ... -> the denoised image ----
+    const hipStream_t st = c->stream;
+    const bool timing = c->opt.timing;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    D.ev.used = 0;
+    if (timing) for (hipEvent_t& e : ev) e = D.ev.take();
+    const bool timed = timing && ev[0] && ev[1] && ev[2] && ev[3];
+    if (timed) (void)hipEventRecord(ev[0], st);
+    launch_denoise_guides(st, (uint32_t)c->num_cus * 8u, c->dsc, width, height, (const CameraGPU*)c->d_cam.p, (F4*)D.d_guides.p);
+    if (timed) { (void)hipEventRecord(ev[1], st); (void)hipEventRecord(ev[2], st); }
+    const F4* in = c->accum_ptr();
+    for (uint32_t i = 0; i < q.levels; i++) {
+        DenoiseLevel a{};
+        a.width = width; a.height = height; a.step = 1u << i; a.normal_power_log2 = q.normal_power_log2; a.first = i == 0; a.last = i + 1 == q.levels;
+        a.inv_sigma_plane = inv_plane; a.inv_sigma_color_s = inv_color * (float)a.step;
+        F4* dst = (F4*)(a.last ? D.d_out.p : D.d_pp[i & 1u].p);
+        launch_denoise_level(st, a, in, (const F4*)D.d_guides.p, dst, (uint32_t*)D.d_partial.p, a.step <= D.lds_step);
+        in = dst;
+    }
+    if (timed) (void)hipEventRecord(ev[3], st);
+    if (out) launch_denoise_count(st, (const uint32_t*)D.d_partial.p, nwg, (uint32_t*)D.d_count.p);
+    HIPCHK(c, hipGetLastError());
+    D.valid = true;
+    if (out) {
+        uint32_t filtered = 0;
+        TO_HOST(c, &filtered, D.d_count.p, 4);                               // (complete when it returns: the stream is joined up to here)
+        *out = rtx_denoise_result{};
+        out->levels = q.levels; out->pixels_filtered = filtered; out->pixels_passed = (uint32_t)npix - filtered;
+        if (timed) {
+            float ms = 0.0f;
+            if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) out->guides_ms = ms;
+            if (hipEventElapsedTime(&ms, ev[2], ev[3]) == hipSuccess) out->filter_ms = ms;
+        }
+    }
+    if (c->own_stream) HIPCHK(c, hipStreamSynchronize(c->stream));            // on a caller-bound stream what follows is stream-ordered: no host bubble
+    return RTX_OK;
+}
+
+int rtx_read_denoised(rtx_ctx* c, float* out, size_t bytes) {
+    BIND(c);
+    if (!have_denoised(c)) { c->err = "read_denoised: no denoised image of the accumulation buffer's size (rtx_denoise first)"; return RTX_ERR_STATE; }
+    const size_t need = (size_t)c->dn.w * c->dn.h * 16;
+    if (!out || bytes < need) { c->err = "read_denoised: buffer too small"; return RTX_ERR_INVALID; }
+    TO_HOST(c, out, c->dn.d_out.p, need);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RTX_OK;
+}
+
+int rtx_read_denoised_srgb8(rtx_ctx* c, uint8_t* out, size_t bytes) {
+    BIND(c);
+    if (!have_denoised(c)) { c->err = "read_denoised_srgb8: no denoised image of the accumulation buffer's size (rtx_denoise first)"; return RTX_ERR_STATE; }
+    const uint32_t npix = c->dn.w * c->dn.h;
+    if (!out || bytes < (size_t)npix * 4) { c->err = "read_denoised_srgb8: buffer too small"; return RTX_ERR_INVALID; }
+    HIPCHK(c, c->d_srgb.ensure((size_t)npix * 4));
+    launch_srgb8(c->stream, (const F4*)c->dn.d_out.p, npix, (uint32_t*)c->d_srgb.p);
+    TO_HOST(c, out, c->d_srgb.p, (size_t)npix * 4);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RTX_OK;
+}
+
+int rtx_debug_denoise_guides(rtx_ctx* c, uint32_t width, uint32_t height, float* out8) {
+    BIND(c);
+    if (!c->committed || !c->camera_set) { c->err = "denoise_guides: scene not committed or camera not set"; return RTX_ERR_STATE; }
+    const size_t npix = (size_t)width * height;
+    if (!out8 || !npix || npix > 0x7FFFFFFFull) { c->err = "denoise_guides: bad size"; return RTX_ERR_INVALID; }
+    DevBuf d_g;                                                              // (not the filter's own record: a debug call must not disturb a denoised image of another size)
+    HIPCHK(c, d_g.ensure(npix * 32));
+    launch_denoise_guides(c->stream, (uint32_t)c->num_cus * 8u, c->dsc, width, height, (const CameraGPU*)c->d_cam.p, (F4*)d_g.p);
+    HIPCHK(c, hipGetLastError());
+    TO_HOST(c, out8, d_g.p, npix * 32);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RTX_OK;
+}
+
+}  // extern "C"

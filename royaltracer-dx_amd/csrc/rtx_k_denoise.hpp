@@ -1,0 +1,151 @@
+// rtx_k_denoise.hpp — rtx_denoise: the edge-avoiding a-trous filter guided by first-hit geometry (definition: include/rtx.h; host side: rtx_denoise.hip)
+// One of the kernel headers of rtx_kernels.hip, the path tracer's single translation unit (see its header comment for the design and for why).
+//
+// PARITY-CRITICAL: tests/test_denoise_ref.py replays dn_tap operation for operation in numpy float32.  Only + - * / abs max, in the written order; no dot() / madd3() here
+// (those are fused), and the tap sum is sequential in tap order.  Do not reassociate, do not split the 5 x 5 window into passes.
+#pragma once
+#include "rtx_shade.hpp"
+
+namespace rtx {
+
+constexpr uint32_t kDnNoGeo = 0xFFFFFFFFu;          // material word of a guide record: the pixel is not filterable by geometry (miss, material out of range, emitter seen directly)
+constexpr uint32_t kDnTileW = 32, kDnTileH = 8;     // one workgroup = 32 x 8 pixels: a wave is two rows of 32 neighbouring pixels, 512 contiguous bytes of a colour row each
+
+// Guides: k_debug_layer's ray (pixel corner, jitter-free, kTMinCam) and surface(); two F4 per pixel: (P, material word) (n, 0).  A pixel that is not filterable by geometry
+// gets (0, 0, 0, kDnNoGeo) (0, 0, 0, 0), so that a tap's class test and its material test are ONE compare of the material word with the centre's.
+__global__ __launch_bounds__(kBlock) void k_denoise_guides(DevScene sc, const SmallRecPair* __restrict__ small, uint32_t width, uint32_t height, const CameraGPU* __restrict__ cam, F4* __restrict__ guides) {
+    extern __shared__ F4 lds[];
+    const TraceLds L = stage_lds(sc, lds);
+    __syncthreads();
+    const uint32_t stride = gridDim.x * kBlock;
+    for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < width * height; i += stride) {
+        const uint32_t x = i % width, y = i / width;
+        f3 o, d; primary_ray(*cam, width, height, x, y, 0.0f, 0.0f, o, d);
+        float t, u, v; uint32_t prim;
+        trace_ray<false>(sc, small, L, o, d, kTMinCam, kTMax, t, u, v, prim);
+        F4 g0 = {0.0f, 0.0f, 0.0f, u2f(kDnNoGeo)}, g1 = {0.0f, 0.0f, 0.0f, 0.0f};
+        if (prim != kMissPrim) {
+            const Surf sf = surface(sc, o, d, t, u, v, prim);
+            if (sf.mat < sc.nmat) {
+                const MatGPU& m = sc.mats[sf.mat];
+                if (!(m.KeFull[0] > 0.0f || m.KeFull[1] > 0.0f || m.KeFull[2] > 0.0f)) {
+                    g0 = {sf.pos.x, sf.pos.y, sf.pos.z, u2f(sf.mat)};
+                    g1 = {sf.normal.x, sf.normal.y, sf.normal.z, 0.0f};
+                }
+            }
+        }
+        guides[2 * (size_t)i] = g0; guides[2 * (size_t)i + 1] = g1;
+    }
+}
+
+// the colour a level reads.  Level 0 (FIRST) reads u1 and forms the mean as k_srgb8 does, c = u1.xyz / max(u1.w, 1), with w := 1 where the pixel holds samples, else 0;
+// every later level reads the previous one's output, which carries that mark in w unchanged
+template <bool FIRST> __device__ __forceinline__ F4 dn_colour(F4 a) {
+    if constexpr (FIRST) { const float cnt = maxf_(a.w, 1.0f); return {a.x / cnt, a.y / cnt, a.z / cnt, a.w > 0.0f ? 1.0f : 0.0f}; }
+    else return a;
+}
+
+// one tap that counts (inside the image, filterable, the centre's material): rtx.h's eight lines
+struct DnSum { float x, y, z, w; };
+__device__ __forceinline__ void dn_tap(DnSum& S, const DenoiseLevel& a, F4 g0p, F4 g1p, F4 cp, F4 g0q, F4 g1q, F4 cq, float hh) {
+    const float dn = (g1p.x * g1q.x + g1p.y * g1q.y) + g1p.z * g1q.z;
+    float wn = maxf_(dn, 0.0f);
+    for (uint32_t k = 0; k < a.normal_power_log2; k++) wn = wn * wn;
+    const float dx = g0q.x - g0p.x, dy = g0q.y - g0p.y, dz = g0q.z - g0p.z;
+    const float dp = fabsf((g1p.x * dx + g1p.y * dy) + g1p.z * dz);
+    const float wp = maxf_(1.0f - dp * a.inv_sigma_plane, 0.0f);
+    const float dc = (fabsf(cq.x - cp.x) + fabsf(cq.y - cp.y)) + fabsf(cq.z - cp.z);
+    const float wc = maxf_(1.0f - dc * a.inv_sigma_color_s, 0.0f);
+    const float w = (hh * wn) * (wp * wc);
+    S.x = S.x + w * cq.x; S.y = S.y + w * cq.y; S.z = S.z + w * cq.z; S.w = S.w + w;
+}
+__device__ __forceinline__ float dn_h(int k) { return k == 0 ? 0.375f : ((k == 1 || k == -1) ? 0.25f : 0.0625f); }      // (1/16, 1/4, 3/8, 1/4, 1/16): every product of two is exact
+
+// One level, one thread per pixel.  S = 0: DIRECT — every tap is a global load; the lanes of a wave read neighbouring addresses at every tap (the offset is the same for
+// all), so the loads coalesce and the 25-fold reuse is the cache's.  S = 1, 2, 4: STAGED — the tile plus its 2 S halo (colour and both guide records, 48 B per pixel) goes
+// through LDS once, pixels outside the image as kDnNoGeo; S is the level's step and must equal a.step.  No atomics, no dependency between workgroups.
+// FIRST also counts the filterable pixels of the tile into partial[workgroup] (k_denoise_count sums them).
+template <uint32_t S, bool FIRST>
+__global__ __launch_bounds__(kBlock) void k_denoise_level(DenoiseLevel a, const F4* __restrict__ in, const F4* __restrict__ guides, F4* __restrict__ out, uint32_t* __restrict__ partial) {
+    constexpr uint32_t RW = kDnTileW + 4u * S, RH = kDnTileH + 4u * S;
+    __shared__ F4 s_c[S ? RW * RH : 1], s_g0[S ? RW * RH : 1], s_g1[S ? RW * RH : 1];
+    __shared__ uint32_t s_cnt[kBlock / 64];
+    const uint32_t tx = blockIdx.x % a.tiles_x, ty = blockIdx.x / a.tiles_x;
+    const uint32_t lx = threadIdx.x & (kDnTileW - 1u), ly = threadIdx.x / kDnTileW;
+    const int x0 = (int)(tx * kDnTileW), y0 = (int)(ty * kDnTileH), W = (int)a.width, H = (int)a.height;
+    const int x = x0 + (int)lx, y = y0 + (int)ly, s = (int)a.step;
+    if constexpr (S != 0) {
+        for (uint32_t i = threadIdx.x; i < RW * RH; i += kBlock) {
+            const int qx = x0 - 2 * (int)S + (int)(i % RW), qy = y0 - 2 * (int)S + (int)(i / RW);
+            // a position outside the image reads its nearest pixel (always in bounds, no divergent load) and is marked kDnNoGeo: it counts for no tap
+            const bool ins = qx >= 0 && qx < W && qy >= 0 && qy < H;
+            const size_t q = (size_t)(qy < 0 ? 0 : (qy >= H ? H - 1 : qy)) * a.width + (size_t)(qx < 0 ? 0 : (qx >= W ? W - 1 : qx));
+            const F4 c = dn_colour<FIRST>(in[q]), g1 = guides[2 * q + 1];
+            F4 g0 = guides[2 * q];
+            if (!ins) g0.w = u2f(kDnNoGeo);
+            s_c[i] = c; s_g0[i] = g0; s_g1[i] = g1;
+        }
+        __syncthreads();
+    }
+    bool filt = false;
+    if (x < W && y < H) {
+        const size_t p = (size_t)y * a.width + (size_t)x;
+        const uint32_t lp = (ly + 2u * S) * RW + lx + 2u * S;
+        F4 cp, g0p, g1p = {0.0f, 0.0f, 0.0f, 0.0f};
+        if constexpr (S != 0) { cp = s_c[lp]; g0p = s_g0[lp]; }
+        else { cp = dn_colour<FIRST>(in[p]); g0p = guides[2 * p]; }
+        const uint32_t matp = f2u(g0p.w);
+        filt = matp != kDnNoGeo && cp.w != 0.0f;
+        F4 o = cp;
+        if (filt) {
+            if constexpr (S != 0) g1p = s_g1[lp]; else g1p = guides[2 * p + 1];
+            DnSum sum = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+            for (int dy = -2; dy <= 2; dy++) {
+#pragma unroll
+                for (int dx = -2; dx <= 2; dx++) {
+                    const float hh = dn_h(dy) * dn_h(dx);
+                    if constexpr (S != 0) {
+                        const uint32_t lq = (uint32_t)((int)lp + (dy * (int)RW + dx) * (int)S);
+                        const F4 g0q = s_g0[lq];
+                        if (f2u(g0q.w) != matp) continue;
+                        const F4 cq = s_c[lq];
+                        if (cq.w == 0.0f) continue;
+                        dn_tap(sum, a, g0p, g1p, cp, g0q, s_g1[lq], cq, hh);
+                    } else {
+                        const int qx = x + s * dx, qy = y + s * dy;
+                        if (qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
+                        const size_t q = (size_t)qy * a.width + (size_t)qx;
+                        const F4 g0q = guides[2 * q];
+                        if (f2u(g0q.w) != matp) continue;
+                        const F4 cq = dn_colour<FIRST>(in[q]);
+                        if (cq.w == 0.0f) continue;
+                        dn_tap(sum, a, g0p, g1p, cp, g0q, guides[2 * q + 1], cq, hh);
+                    }
+                }
+            }
+            o.x = sum.x / sum.w; o.y = sum.y / sum.w; o.z = sum.z / sum.w;
+        }
+        if (a.last) o.w = 1.0f;
+        out[p] = o;
+    }
+    if constexpr (FIRST) {
+        const unsigned long long m = __ballot(filt);
+        if (lane_id() == 0) s_cnt[threadIdx.x >> 6] = (uint32_t)__popcll(m);
+        __syncthreads();
+        if (threadIdx.x == 0) partial[blockIdx.x] = (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);
+    }
+}
+
+// the filterable pixels of the image: the sum of the level-0 workgroups' counts (one workgroup, a plain store)
+__global__ __launch_bounds__(kBlock) void k_denoise_count(const uint32_t* __restrict__ partial, uint32_t n, uint32_t* __restrict__ out) {
+    __shared__ uint32_t s_sum[kBlock];
+    uint32_t v = 0;
+    for (uint32_t i = threadIdx.x; i < n; i += kBlock) v += partial[i];
+    s_sum[threadIdx.x] = v;
+    __syncthreads();
+    for (uint32_t h = kBlock / 2; h > 0; h >>= 1) { if (threadIdx.x < h) s_sum[threadIdx.x] += s_sum[threadIdx.x + h]; __syncthreads(); }
+    if (threadIdx.x == 0) out[0] = s_sum[0];
+}
+
+}  // namespace rtx

@@ -51,6 +51,7 @@ __device__ unsigned long long g_sec[36];          // [0,12) cycles, [12,24) acti
 #include "rtx_k_bounce_bvh.hpp"     // k_bounce_bvh, k_order_queues
 #include "rtx_k_film.hpp"           // k_accumulate, k_srgb8, k_debug_layer, k_pack_tiles, k_unpack_tiles
 #include "rtx_k_adaptive.hpp"       // k_adaptive_error, k_adaptive_compact
+#include "rtx_k_denoise.hpp"        // k_denoise_guides, k_denoise_level, k_denoise_count
 #include "rtx_k_dbg.hpp"            // k_dbg_*
 
 namespace rtx {
@@ -260,6 +261,23 @@ void launch_adaptive_error(hipStream_t st, const DevFrame& f, const F4* accum, c
 }
 void launch_adaptive_compact(hipStream_t st, const DevFrame& f, const AdaptState& ad, uint32_t max_spp, uint32_t* list, uint32_t* out5) {
     hipLaunchKernelGGL(k_adaptive_compact, dim3(1), dim3(kCompactBlock), 0, st, f, ad, max_spp, list, out5);
+}
+void launch_denoise_guides(hipStream_t st, uint32_t max_blocks, const DevScene& sc, uint32_t width, uint32_t height, const CameraGPU* cam, F4* guides) {
+    hipLaunchKernelGGL(k_denoise_guides, dim3(grid_for(width * height, max_blocks)), dim3(kBlock), trace_lds_bytes(sc), st, sc, sc.small, width, height, cam, guides);
+}
+uint32_t denoise_workgroups(uint32_t width, uint32_t height) { return ((width + kDnTileW - 1u) / kDnTileW) * ((height + kDnTileH - 1u) / kDnTileH); }
+void launch_denoise_level(hipStream_t st, DenoiseLevel a, const F4* in, const F4* guides, F4* out, uint32_t* partial, bool staged) {
+    a.tiles_x = (a.width + kDnTileW - 1u) / kDnTileW;
+    const dim3 grid(denoise_workgroups(a.width, a.height));
+#define RTX_LAUNCH_DN(SS, FF) hipLaunchKernelGGL((k_denoise_level<SS, FF>), grid, dim3(kBlock), 0, st, a, in, guides, out, partial)
+    if (a.first) { if (staged && a.step == 1u) RTX_LAUNCH_DN(1, true); else RTX_LAUNCH_DN(0, true); }      // (the first level is the only one with step 1)
+    else if (staged && a.step == 2u) RTX_LAUNCH_DN(2, false);
+    else if (staged && a.step == 4u) RTX_LAUNCH_DN(4, false);
+    else RTX_LAUNCH_DN(0, false);
+#undef RTX_LAUNCH_DN
+}
+void launch_denoise_count(hipStream_t st, const uint32_t* partial, uint32_t n, uint32_t* out) {
+    hipLaunchKernelGGL(k_denoise_count, dim3(1), dim3(kBlock), 0, st, partial, n, out);
 }
 void launch_srgb8(hipStream_t st, const F4* accum, uint32_t npix, uint32_t* out) {
     hipLaunchKernelGGL(k_srgb8, dim3((npix + kBlock - 1) / kBlock), dim3(kBlock), 0, st, accum, npix, out);

@@ -194,6 +194,15 @@ void launch_accumulate_list(hipStream_t, uint32_t max_blocks, const DevFrame&, c
 void launch_adaptive_error(hipStream_t, const DevFrame&, const F4* accum, const AdaptState&, float threshold, float dark_floor);     // one workgroup per local chunk: the criterion -> flag
 // the unconverged chunks below max_spp that share the LOWEST count, in ascending order -> list; out[0] their number, [1] that count, [2] chunks converged, [3] unconverged at max_spp, [4] chunks with a valid pixel
 void launch_adaptive_compact(hipStream_t, const DevFrame&, const AdaptState&, uint32_t max_spp, uint32_t* list, uint32_t* out5);
+// ---- rtx_denoise (rtx_k_denoise.hpp) ----
+// one level of the a-trous filter: step = 1 << level; first: `in` is u1 (the mean is formed on the fly), else the previous level's output; last: w of the output is 1.0;
+// inv_sigma_color_s = (1 / sigma_color) * step
+struct DenoiseLevel { uint32_t width, height, tiles_x, step, normal_power_log2, first, last; float inv_sigma_plane, inv_sigma_color_s; };
+void launch_denoise_guides(hipStream_t, uint32_t max_blocks, const DevScene&, uint32_t width, uint32_t height, const CameraGPU* cam, F4* guides);   // two F4 per pixel
+uint32_t denoise_workgroups(uint32_t width, uint32_t height);                                         // tiles of a level launch = entries of `partial`
+// staged: the tile and its halo go through LDS (steps 1, 2 and 4 only); partial: per-workgroup counts of filterable pixels, written by the first level
+void launch_denoise_level(hipStream_t, DenoiseLevel, const F4* in, const F4* guides, F4* out, uint32_t* partial, bool staged);
+void launch_denoise_count(hipStream_t, const uint32_t* partial, uint32_t n, uint32_t* out);
 void launch_srgb8(hipStream_t, const F4* accum, uint32_t npix, uint32_t* out);
 void launch_debug_layer(hipStream_t, uint32_t max_blocks, const DevScene&, uint32_t width, uint32_t height, const CameraGPU* cam, uint32_t layer, uint32_t* out);
 void launch_pack_tiles(hipStream_t, uint32_t max_blocks, const DevFrame&, const F4* accum, F4* slab);

@@ -309,6 +309,22 @@ std::vector<float> MultiGpuFrame::ReadAccumulation(int rank) {
     if (rtx_read_accum(m->ctx[rank], out.data(), out.size() * 4) != RTX_OK) throw std::runtime_error(rtx_last_error(m->ctx[rank]));
     return out;
 }
+void MultiGpuFrame::Denoise(const rtx_denoise_params* params, int rank) {
+    hipck(hipSetDevice(m_devices[rank]), "hipSetDevice");
+    if (rtx_denoise(m->ctx[rank], m_w, m_h, params, nullptr) != RTX_OK) throw std::runtime_error(std::string("rtx_denoise: ") + rtx_last_error(m->ctx[rank]));
+}
+std::vector<float> MultiGpuFrame::ReadDenoised(int rank) {
+    std::vector<float> out((size_t)m_w * m_h * 4);
+    hipck(hipSetDevice(m_devices[rank]), "hipSetDevice");
+    if (rtx_read_denoised(m->ctx[rank], out.data(), out.size() * 4) != RTX_OK) throw std::runtime_error(rtx_last_error(m->ctx[rank]));
+    return out;
+}
+std::vector<uint8_t> MultiGpuFrame::ReadDenoisedOutput(int rank) {
+    std::vector<uint8_t> out((size_t)m_w * m_h * 4);
+    hipck(hipSetDevice(m_devices[rank]), "hipSetDevice");
+    if (rtx_read_denoised_srgb8(m->ctx[rank], out.data(), out.size()) != RTX_OK) throw std::runtime_error(rtx_last_error(m->ctx[rank]));
+    return out;
+}
 std::vector<uint8_t> MultiGpuFrame::ReadOutput(int rank) {
     std::vector<uint8_t> out((size_t)m_w * m_h * 4);
     hipck(hipSetDevice(m_devices[rank]), "hipSetDevice");

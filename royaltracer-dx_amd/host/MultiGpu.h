@@ -50,6 +50,10 @@ public:
     void Clear(uint32_t width, uint32_t height);          // zero every rank's accumulation buffer (view-change reset)
     std::vector<float> ReadAccumulation(int rank = 0);
     std::vector<uint8_t> ReadOutput(int rank = 0);
+    // rtx_denoise on ONE rank's assembled image (after Render's gather every rank holds the whole accumulation buffer; the filter needs no shard fields), and its reads
+    void Denoise(const rtx_denoise_params* params = nullptr, int rank = 0);
+    std::vector<float> ReadDenoised(int rank = 0);
+    std::vector<uint8_t> ReadDenoisedOutput(int rank = 0);
     rtx_stats Stats(int rank) const { return m_stats[rank]; }
     double LastFrameMs() const { return m_lastMs; }       // wall time of Render: max over ranks, gather included
     int Ranks() const { return (int)m_devices.size(); }

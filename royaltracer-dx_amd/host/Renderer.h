@@ -45,6 +45,12 @@ public:
     const std::string& GetTitle() const { return m_title; }
     uint32_t FrameIndex() const { return m_time; }
     std::vector<float> ReadAccumulation();          // gPermanentData (RGBA32F)
+    // rtx_denoise over the accumulated image as it stands (nullptr = every default): the edge-avoiding a-trous filter guided by first-hit position, normal and material.
+    // Path tracer frames only (std::logic_error in ReSTIR mode: that frame has its own reuse passes).  gPermanentData is left alone, so OnRender keeps accumulating; the
+    // denoised image is read with ReadDenoised (RGBA32F, w = 1) / ReadDenoisedOutput (RGBA8 after the sRGB OETF).  Defined in RendererDenoise.cpp
+    rtx_denoise_result Denoise(const rtx_denoise_params* params = nullptr);
+    std::vector<float> ReadDenoised();
+    std::vector<uint8_t> ReadDenoisedOutput();
     std::vector<uint8_t> ReadOutput();              // the DISPLAYED layer of gOutput (RGBA8): what the reference copies to the back buffer (Renderer.cpp:690-698)
     void OnKeyUp(uint8_t key);                      // 'C' cycles m_displayLevels (Renderer.cpp:748-754); other keys do nothing here (VK_SPACE toggles a raster path that does not exist)
     UINT CurrentDisplayLayer() const { return m_displayLevels[m_currentDisplayLevel]; }

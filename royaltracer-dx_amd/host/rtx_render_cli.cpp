@@ -15,6 +15,9 @@
 //                   [--only-rank r] with --gpus N --gather copy: rank r of N alone, through the same host path (measurement on one GPU: tools/shard_time.py native=1)
 //                   [--adaptive THRESHOLD [--min-spp N] [--step-spp N]]   rtx_render_adaptive instead of rtx_render (path tracer, one GPU): every 256-slot chunk is sampled until its
 //                   pixels pass the noise threshold, --spp is the cap (defaults: min 8, step 8; both even); prints the result struct per frame
+//                   [--denoise [--denoise-levels N] [--sigma-color X] [--sigma-plane X]]   after the last frame rtx_denoise filters the accumulated image (edge-avoiding a-trous,
+//                   guided by first-hit position, normal and material; defaults: 5 levels, 0.5, 2^-6 of the scene's extent) and --out gets the DENOISED image; works with
+//                   --adaptive and with --gpus N (on rank 0, after the gather); refused with --mode restir (that frame has its own reuse passes)
 //                   [--gpus N [--devices 0,1,..] [--gather rccl|copy]]   the native N-GPU frame (MultiGpu.h): one process, N contexts, pixel tiles
 //                   round-robin, ONE RCCL all-gather per frame; `--gather copy` replaces the collective by device copies (several ranks on one GPU: tests)
 #include <algorithm>
@@ -30,12 +33,21 @@
 #include "ImageIO.h"
 #include "MultiGpu.h"
 
+static const char* kUsage =
+    "usage: rtx_render [--scene cornell|sponza|bistro|obj] [--obj a.obj,b.obj --mtl dir] [--w 1920 --h 1080]\n"
+    "                  [--spp 64] [--frames 1] [--bounces 8] [--nee 1] [--lambert] [--out image.{png,ppm,exr}] [--device 0]\n"
+    "                  [--mode pt|restir] [--literal] [--halo px] [--force-gather] [--orbit deg] [--spin deg] [--hide i[,j...]] [--blink i] [--only-rank r]\n"
+    "                  [--adaptive THRESHOLD [--min-spp N] [--step-spp N]]\n"
+    "                  [--denoise [--denoise-levels N] [--sigma-color X] [--sigma-plane X]]   write the denoised image to --out (path tracer only)\n"
+    "                  [--gpus N [--devices 0,1,..] [--gather rccl|copy]]\n";
+
 int main(int argc, char** argv) {
     std::string scene = "cornell", out, objs, mtl = "./";
     UINT w = 1920, h = 1080, spp = 1, frames = 1, bounces = 8, nee = 1; int device = 0; bool lambert = false;
     int gpus = 1; std::string devlist, gather = "rccl", mode = "pt"; bool literal = false, nee_set = false, bounces_set = false, force_gather = false; float orbit = 0.0f, spin = 0.0f; int only_rank = -1; UINT halo = 0;
     std::vector<UINT> hide; int blink = -1;
     bool adaptive = false; rtx_adaptive ad{}; ad.min_spp = 8; ad.step_spp = 8;
+    bool denoise = false; rtx_denoise_params dnp{};
     for (int i = 1; i < argc; i++) {
         auto arg = [&](const char* k) { return !strcmp(argv[i], k) && i + 1 < argc; };
         if (arg("--scene")) scene = argv[++i]; else if (arg("--obj")) { objs = argv[++i]; scene = "obj"; } else if (arg("--mtl")) mtl = argv[++i];
@@ -44,6 +56,8 @@ int main(int argc, char** argv) {
         else if (arg("--mode")) mode = argv[++i]; else if (arg("--orbit")) orbit = (float)atof(argv[++i]); else if (arg("--spin")) spin = (float)atof(argv[++i]); else if (arg("--only-rank")) only_rank = atoi(argv[++i]); else if (!strcmp(argv[i], "--literal")) literal = true; else if (!strcmp(argv[i], "--force-gather")) force_gather = true;
         else if (arg("--hide")) { std::stringstream ss(argv[++i]); std::string t; while (std::getline(ss, t, ',')) hide.push_back((UINT)atoi(t.c_str())); } else if (arg("--blink")) blink = atoi(argv[++i]);
         else if (arg("--adaptive")) { adaptive = true; ad.threshold = (float)atof(argv[++i]); } else if (arg("--min-spp")) ad.min_spp = (uint32_t)atoi(argv[++i]); else if (arg("--step-spp")) ad.step_spp = (uint32_t)atoi(argv[++i]);
+        else if (!strcmp(argv[i], "--help") || !strcmp(argv[i], "-h")) { fputs(kUsage, stdout); return 0; }
+        else if (!strcmp(argv[i], "--denoise")) denoise = true; else if (arg("--denoise-levels")) dnp.levels = (uint32_t)atoi(argv[++i]); else if (arg("--sigma-color")) dnp.sigma_color = (float)atof(argv[++i]); else if (arg("--sigma-plane")) dnp.sigma_plane = (float)atof(argv[++i]);
         else if (arg("--halo")) halo = (UINT)atoi(argv[++i]); else if (arg("--gpus")) gpus = atoi(argv[++i]); else if (arg("--devices")) devlist = argv[++i]; else if (arg("--gather")) gather = argv[++i];
         else if (arg("--out")) out = argv[++i]; else if (arg("--device")) device = atoi(argv[++i]); else if (!strcmp(argv[i], "--lambert")) lambert = true;
         else { fprintf(stderr, "unknown argument %s\n", argv[i]); return 2; }
@@ -52,6 +66,7 @@ int main(int argc, char** argv) {
     const bool restir = mode == "restir";
     if (restir) { if (!nee_set) nee = 4; if (!bounces_set) bounces = 3; }
     if (adaptive && (restir || gpus > 1 || !devlist.empty())) { fprintf(stderr, "--adaptive is the path tracer on one GPU (no --mode restir, --gpus, --devices)\n"); return 2; }
+    if (denoise && restir) { fprintf(stderr, "--denoise filters the path tracer's accumulation (no --mode restir: that frame has its own reuse passes)\n"); return 2; }
     // camera of frame f: the scene's eye rotated by f * orbit degrees about the vertical axis through the look-at point
     auto orbit_eye = [&](const Scene& sc, UINT f) {
         const float a = orbit * 3.14159265f / 180.0f * (float)f, cs = cosf(a), sn = sinf(a);
@@ -104,7 +119,9 @@ int main(int argc, char** argv) {
                 if (restir && gpus > 1) printf("  history exchange: %s, %.2f MB sent by the busiest rank, stale history reads %llu\n", halo ? "border strips (halo)" : "all-gather", (double)mg.LastExchangeBytes() / 1e6, (unsigned long long)mg.StaleHistoryReads());
             }
             const int rr = only_rank >= 0 ? only_rank : 0;
-            if (!out.empty() && !write_image(mg.ReadAccumulation(rr), mg.ReadOutput(rr))) { fprintf(stderr, "error: could not write %s\n", out.c_str()); return 1; }
+            if (denoise) { mg.Denoise(&dnp, rr); printf("denoised on rank %d\n", rr); }
+            if (denoise && !out.empty()) { if (!write_image(mg.ReadDenoised(rr), mg.ReadDenoisedOutput(rr))) { fprintf(stderr, "error: could not write %s\n", out.c_str()); return 1; } }
+            else if (!out.empty() && !write_image(mg.ReadAccumulation(rr), mg.ReadOutput(rr))) { fprintf(stderr, "error: could not write %s\n", out.c_str()); return 1; }
         } catch (const std::exception& e) { fprintf(stderr, "error: %s\n", e.what()); return 1; }
         return 0;
     }
@@ -151,11 +168,15 @@ int main(int argc, char** argv) {
             printf("frame %u: %.3f ms, %.1f Mrays/s (primary %llu, extension %llu, shadow %llu)\n", f, s.render_ms, rays / (s.render_ms * 1e3),
                    (unsigned long long)s.rays_primary, (unsigned long long)s.rays_extension, (unsigned long long)s.rays_shadow);
         }
+        if (denoise) {
+            const rtx_denoise_result dr = r.Denoise(&dnp);
+            printf("denoise: %u levels, %u pixels filtered, %u passed through\n", dr.levels, dr.pixels_filtered, dr.pixels_passed);
+        }
         if (!out.empty()) {
             const bool exr = out.size() > 4 && out.substr(out.size() - 4) == ".exr", png = out.size() > 4 && out.substr(out.size() - 4) == ".png";
             bool ok;
-            if (exr) { std::vector<float> acc = r.ReadAccumulation(); ok = WriteEXR(out, acc.data(), w, h); }
-            else { std::vector<uint8_t> px = r.ReadOutput(); ok = png ? WritePNG(out, px.data(), w, h) : WritePPM(out, px.data(), w, h); }
+            if (exr) { std::vector<float> acc = denoise ? r.ReadDenoised() : r.ReadAccumulation(); ok = WriteEXR(out, acc.data(), w, h); }
+            else { std::vector<uint8_t> px = denoise ? r.ReadDenoisedOutput() : r.ReadOutput(); ok = png ? WritePNG(out, px.data(), w, h) : WritePPM(out, px.data(), w, h); }
             if (!ok) { fprintf(stderr, "error: could not write %s\n", out.c_str()); return 1; }
         }
         r.OnDestroy();
