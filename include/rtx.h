@@ -177,8 +177,8 @@ enum { RTX_OPT_KERNEL_TIMING = 1,    /* 0/1: bracket every launch with hipEvents
                                         global memory, so that LDS (the staged top of the tree, workgroups per CU) is sized for what almost every ray needs.  0 = the whole stack in LDS (until round 5).
                                         Never changes a result.  Takes effect with the next rtx_commit_scene */
        RTX_OPT_SHARED_PRIMARY = 41,  /* 1 (default): fused tiny-scene path without RTX_FLAG_JITTER: all samples of a pixel shoot the same camera ray, so the primary hit and the surface
-                                        there are computed once per pixel and rtx_render call (k_primary_surface) instead of once per sample; raygen only enqueues the hitting paths and
-                                        bounce 0 starts from the pixel's record.  0: every sample traces and reconstructs its own.  Never changes a result.  rays_primary still counts
+                                        there are computed once per pixel and rtx_render call (k_primary_surface) instead of once per sample; raygen only enqueues the ids of the hitting paths and
+                                        bounce 0 starts from the pixel's record, with sample and seeds derived from the path id.  0: every sample traces and reconstructs its own.  Never changes a result.  rays_primary still counts
                                         one camera ray per sample */
        RTX_OPT_DENOISE_LDS_STEP = 42,/* tuning, rtx_denoise: the levels with step <= this value (0, 1, 2 or 4) stage their tile and its halo in LDS, the coarser ones read every tap from global memory.
                                         Default 4: every step that fits (measured faster than the direct form at steps 1, 2 and 4: profiles/denoise_time.md).  Never changes a result */

@@ -90,5 +90,13 @@ __device__ __forceinline__ bool dealt_chunk(const DevFrame& f, uint32_t k, uint3
     row0 += nk;
     return !(blockIdx.x >= nk || c >= nchunks);                                           // wave-uniform
 }
+// The same deal without the walk: row0 of row k in closed form, for a kernel that takes its rows in parallel (k_raygen_shared) and hands the result to dealt_chunk.  The
+// widths of the tapered deal repeat with period 2^(levels - 1) (taper_row_width looks at the low bits of k only); period_sum = the widths of one period.
+__device__ __forceinline__ uint32_t deal_width(const DevFrame& f, uint32_t k) { return f.taper_levels ? taper_row_width(k, gridDim.x, f.taper_levels) : gridDim.x; }
+__device__ __forceinline__ uint32_t deal_row0(const DevFrame& f, uint32_t k, uint32_t period, uint32_t period_sum) {
+    uint32_t r = (k / period) * period_sum;
+    for (uint32_t j = 0; j < (k & (period - 1u)); j++) r += deal_width(f, j);
+    return r;
+}
 
 }  // namespace rtx

@@ -13,7 +13,7 @@ namespace rtx {
 // LAMBERT: RTX_FLAG_LAMBERT_ONLY is a launch constant, so it is a template parameter too: the Lambert-only instantiation carries no GGX code
 // (fewer live registers, fewer SGPR spills through v_writelane / v_readlane in the loop).
 // HAVE_HIT: 0 = bounces >= 1 (the kernel traces its extension rays); bounce 0: 1 = path state and hit record come from k_raygen_trace_small, 2 = RTX_OPT_SHARED_PRIMARY: the
-// path starts from its pixel's shared record (k_primary_surface) and the (pixel slot, seeds) entry of k_raygen_shared — no surface() here, and 32 B read per path instead of 64
+// path starts from its pixel's shared record (k_primary_surface) and derives sample, slot and seeds from its id (PrimIn) — no surface() here, and nothing per path read but the queue word
 template <int WAVES, int HAVE_HIT, bool LAMBERT, bool RING>
 __global__ __launch_bounds__(kBlock, WAVES) void k_bounce_small(DevScene sc, const SmallRecPair* __restrict__ small, DevFrame f_in, DevPaths p,
                                                          uint32_t bounce_first, uint32_t bounce_end,
@@ -21,7 +21,7 @@ __global__ __launch_bounds__(kBlock, WAVES) void k_bounce_small(DevScene sc, con
                                                          uint32_t* __restrict__ qrows /* [bounce][gridDim.x] sub-queue lengths entering each bounce */,
                                                          uint32_t* __restrict__ srows /* [bounce][nee][gridDim.x]: shadow rays traced (statistics) */,
                                                          const uint32_t* __restrict__ order /* workgroup -> sub-queue, longest first (k_order_queues); may be null */,
-                                                         const F4* __restrict__ prim_rec /* HAVE_HIT 2: the per-pixel records of k_primary_surface (read by that instantiation only) */) {
+                                                         PrimIn pin /* HAVE_HIT 2: the per-pixel records of k_primary_surface and how to find a path's (read by that instantiation only) */) {
     // BOUNCE RANGE: sub-queues are workgroup-private, so bounce b + 1 of sub-queue q depends on bounce b of the SAME sub-queue only.  One
     // launch therefore runs the bounces [bounce_first, bounce_end) of its sub-queue back to back, with a workgroup barrier in between
     // (workgroup-scope release / acquire: the path state and queue entries a bounce writes are read by the same workgroup).  A frame has
@@ -102,12 +102,13 @@ __global__ __launch_bounds__(kBlock, WAVES) void k_bounce_small(DevScene sc, con
             active = i < n;
             if (active) {
                 S.pid = myq[i];
-                const F4 e = p.hit[S.pid];                                     // k_raygen_shared: (pixel slot, seed.x, seed.y, -)
-                const uint32_t pl = f2u(e.x);
-                const F4 r0 = prim_rec[pl], r1 = prim_rec[(size_t)f.npl + pl], r2 = prim_rec[(size_t)2 * f.npl + pl], ro = prim_rec[(size_t)3 * f.npl];
-                S.s0 = f2u(e.y); S.s1 = f2u(e.z);
+                // pid = sl * f.npl + v: the batch's sample, the (virtual) slot; the division is exact for every pid < 2^31 (PrimIn)
+                const uint32_t sl = __umulhi(S.pid, pin.div_mul) >> pin.div_shift, v = S.pid - sl * f.npl;
+                const uint32_t pl = f.list ? f.list[v >> 8] * (uint32_t)kBlock + (v & 255u) : v;       // real_slot: a pass of rtx_render_adaptive
+                const F4 r0 = pin.rec[pl], r1 = pin.rec[(size_t)pin.npl + pl], r2 = pin.rec[(size_t)2 * pin.npl + pl], ro = pin.rec[(size_t)3 * pin.npl];
+                seed_sample(f2u(r2.w), f2u(r1.w), f.sample_first + sl, f.frame_seed, S.s0, S.s1);     // = seed_init(x, y, sample, frame_seed): the record carries the pixel's terms
                 S.o = mk3(ro.x, ro.y, ro.z); S.d = mk3(r0.x, r0.y, r0.z); S.thr = mk3(1.0f, 1.0f, 1.0f); S.prev_pdf = 1.0f;
-                sf.pos = mk3(r1.x, r1.y, r1.z); sf.normal = mk3(r2.x, r2.y, r2.z); sf.mat = f2u(r0.w); sf.near_hull = f2u(r1.w) != 0u;
+                sf.pos = mk3(r1.x, r1.y, r1.z); sf.normal = mk3(r2.x, r2.y, r2.z); sf.mat = f2u(r0.w) & 0x7FFFFFFFu; sf.near_hull = (f2u(r0.w) >> 31) != 0u;
                 prim = 0u;                                                     // (any id but kMissPrim)
             }
         } else if (HAVE_HIT) {                            // bounce 0: the primary hit comes from k_raygen_trace_small; every queue entry is a hit

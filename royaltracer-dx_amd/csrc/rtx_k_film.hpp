@@ -11,8 +11,10 @@ namespace rtx {
 // ---------------------------------------------------------------------------------------------
 // LIST: the adaptive form (rtx_render_adaptive).  The frame's slots are the active list's (real_slot); beside u1 the samples with an odd id go — in the same place, in the same
 // order — into `half`, the second running sum the convergence criterion compares u1 with (rtx_k_adaptive.hpp); the first lane of a chunk notes the samples the chunk has now.
-template <bool LIST>
-__global__ __launch_bounds__(kBlock) void k_accumulate(DevFrame f, DevPaths p, F4* __restrict__ accum, AdaptState ad) {
+// SHARED: RTX_OPT_SHARED_PRIMARY in effect — whether a pixel's paths hold a radiance is the same for all its samples: bit (slot & 63) of prim_hits[real slot >> 6]
+// (k_primary_surface) in the place of the per-path p.hitmask, which that path no longer writes.
+template <bool LIST, bool SHARED>
+__global__ __launch_bounds__(kBlock) void k_accumulate(DevFrame f, DevPaths p, F4* __restrict__ accum, AdaptState ad, const unsigned long long* __restrict__ prim_hits) {
     const uint32_t stride = gridDim.x * kBlock;
     for (uint32_t pl = blockIdx.x * kBlock + threadIdx.x; pl < f.npl; pl += stride) {
         uint32_t x, y;
@@ -20,14 +22,18 @@ __global__ __launch_bounds__(kBlock) void k_accumulate(DevFrame f, DevPaths p, F
             uint32_t gi;
             if ((pl & 255u) == 0u && chunk_image_index(f, f.list[pl >> 8], gi)) ad.count[gi] = ad.count[gi] + f.batch_spp;      // one lane per chunk and batch; a plain store
         }
-        if (!slot_to_pixel(f, real_slot<LIST>(f, pl), x, y)) continue;
+        const uint32_t rs = real_slot<LIST>(f, pl);
+        if (!slot_to_pixel(f, rs, x, y)) continue;
+        bool lit = true;
+        if constexpr (SHARED) lit = ((prim_hits[rs >> 6] >> (rs & 63u)) & 1ull) != 0ull;
         F4 a = accum[(size_t)y * f.width + x];
         F4 h = {0.0f, 0.0f, 0.0f, 0.0f};
         if constexpr (LIST) h = ad.half[(size_t)y * f.width + x];
         for (uint32_t s = 0; s < f.batch_spp; s++) {
             const size_t pid = (size_t)s * f.npl + pl;
             F4 r = {0.0f, 0.0f, 0.0f, 0.0f};
-            if (!p.hitmask || ((p.hitmask[pid >> 6] >> (pl & 63u)) & 1ull)) r = p.rad[pid];
+            if constexpr (SHARED) { if (lit) r = p.rad[pid]; }
+            else if (!p.hitmask || ((p.hitmask[pid >> 6] >> (pl & 63u)) & 1ull)) r = p.rad[pid];
             const f3 rv = mk3(r.x, r.y, r.z);
             if (finite3(rv)) {
                 a.x = a.x + rv.x; a.y = a.y + rv.y; a.z = a.z + rv.z; a.w = a.w + 1.0f;

@@ -95,9 +95,9 @@ void launch_raygen_trace_small(hipStream_t st, const DevScene& sc, const DevFram
 void launch_primary_surface(hipStream_t st, const DevScene& sc, const DevFrame& f, const CameraGPU* cam, unsigned long long* masks, unsigned long long* hits, F4* rec) {
     hipLaunchKernelGGL(k_primary_surface, dim3(f.npl / kBlock), dim3(kBlock), trace_lds_bytes(sc), st, sc, sc.small, f, cam, masks, hits, rec);
 }
-void launch_raygen_shared(hipStream_t st, const DevFrame& f, const DevPaths& p, uint32_t* queue, uint32_t* qcount, uint32_t* gencount, const unsigned long long* hits) {
-    if (f.list) hipLaunchKernelGGL(k_raygen_shared<true>, dim3(f.nblocks), dim3(kBlock), 0, st, f, p, queue, qcount, gencount, hits);
-    else hipLaunchKernelGGL(k_raygen_shared<false>, dim3(f.nblocks), dim3(kBlock), 0, st, f, p, queue, qcount, gencount, hits);
+void launch_raygen_shared(hipStream_t st, const DevFrame& f, uint32_t* queue, uint32_t* qcount, uint32_t* gencount, const unsigned long long* hits, uint32_t rec_npl) {
+    if (f.list) hipLaunchKernelGGL(k_raygen_shared<true>, dim3(f.nblocks), dim3(kBlock), 0, st, f, queue, qcount, gencount, hits, rec_npl >> 6);
+    else hipLaunchKernelGGL(k_raygen_shared<false>, dim3(f.nblocks), dim3(kBlock), 0, st, f, queue, qcount, gencount, hits, rec_npl >> 6);
 }
 // The launch of a persistent traversal kernel (k_trace_closest, k_trace_shadow): clamps `merge`, sizes the grid and maps (sc, heads) to the instantiation — stack kind, stealing,
 // compiled-in schedule, as std::integral_constants — and its dynamic LDS.  launch(stk, steal, sched, grid, lds_bytes, heads, merge) does the launch.
@@ -132,12 +132,13 @@ void launch_trace_closest(hipStream_t st, const DevFrame& f, const DevScene& sc,
     });
 }
 void launch_bounce_small(hipStream_t st, const DevScene& sc, const DevFrame& f, const DevPaths& p, uint32_t bounce_first, uint32_t bounce_end,
-                         uint32_t* queue_a, uint32_t* queue_b, uint32_t* qrows, uint32_t* srows, const uint32_t* order, bool ring, const F4* prim_rec) {
+                         uint32_t* queue_a, uint32_t* queue_b, uint32_t* qrows, uint32_t* srows, const uint32_t* order, bool ring, const PrimIn* prim) {
     // general instantiation: 118 VGPRs, 4 waves/SIMD (5 or 6 spill and measured slower); Lambert-only: 85 VGPRs, 5 waves/SIMD (a build for 6 waves, 80 VGPRs
     // with 2 spilled, measured the same: 19.13 vs 19.03 ms).  Bounce 0 (reads the primary hits) is its own instantiation and launch.
     const bool lam = (f.flags & 1u) != 0u, have_hit = bounce_first == 0u;
-#define RTX_LAUNCH_BOUNCE(HH, LL, RR) hipLaunchKernelGGL((k_bounce_small<4, HH, LL, RR>), dim3(f.nblocks), dim3(kBlock), trace_lds_bytes(sc), st, sc, sc.small, f, p, bounce_first, bounce_end, queue_a, queue_b, qrows, srows, order, prim_rec)
-    if (have_hit && prim_rec) { if (lam) RTX_LAUNCH_BOUNCE(2, true, false); else RTX_LAUNCH_BOUNCE(2, false, false); }
+    const PrimIn pin = prim ? *prim : PrimIn{};
+#define RTX_LAUNCH_BOUNCE(HH, LL, RR) hipLaunchKernelGGL((k_bounce_small<4, HH, LL, RR>), dim3(f.nblocks), dim3(kBlock), trace_lds_bytes(sc), st, sc, sc.small, f, p, bounce_first, bounce_end, queue_a, queue_b, qrows, srows, order, pin)
+    if (have_hit && prim) { if (lam) RTX_LAUNCH_BOUNCE(2, true, false); else RTX_LAUNCH_BOUNCE(2, false, false); }
     else if (have_hit) { if (lam) RTX_LAUNCH_BOUNCE(1, true, false); else RTX_LAUNCH_BOUNCE(1, false, false); }
     else if (ring) { if (lam) RTX_LAUNCH_BOUNCE(0, true, true); else RTX_LAUNCH_BOUNCE(0, false, true); }
     else { if (lam) RTX_LAUNCH_BOUNCE(0, true, false); else RTX_LAUNCH_BOUNCE(0, false, false); }
@@ -250,11 +251,13 @@ void launch_rs_p3_merge(hipStream_t st, const DevScene& sc, const DevFrame& f, c
 void launch_rs_p3_shade(hipStream_t st, const DevScene& sc, const DevFrame& f, const RsQ& q, uint32_t* const bufs[6], F4* accum) {
     hipLaunchKernelGGL(k_rs_p3_shade, dim3(q.G), dim3(kBlock), 0, st, sc, f, q, rs_bufs(bufs), accum);
 }
-void launch_accumulate(hipStream_t st, uint32_t max_blocks, const DevFrame& f, const DevPaths& p, F4* accum) {
-    hipLaunchKernelGGL(k_accumulate<false>, dim3(grid_for(f.npl, max_blocks)), dim3(kBlock), 0, st, f, p, accum, AdaptState{});
+void launch_accumulate(hipStream_t st, uint32_t max_blocks, const DevFrame& f, const DevPaths& p, F4* accum, const unsigned long long* prim_hits) {
+    if (prim_hits) hipLaunchKernelGGL((k_accumulate<false, true>), dim3(grid_for(f.npl, max_blocks)), dim3(kBlock), 0, st, f, p, accum, AdaptState{}, prim_hits);
+    else hipLaunchKernelGGL((k_accumulate<false, false>), dim3(grid_for(f.npl, max_blocks)), dim3(kBlock), 0, st, f, p, accum, AdaptState{}, prim_hits);
 }
-void launch_accumulate_list(hipStream_t st, uint32_t max_blocks, const DevFrame& f, const DevPaths& p, F4* accum, const AdaptState& ad) {
-    hipLaunchKernelGGL(k_accumulate<true>, dim3(grid_for(f.npl, max_blocks)), dim3(kBlock), 0, st, f, p, accum, ad);
+void launch_accumulate_list(hipStream_t st, uint32_t max_blocks, const DevFrame& f, const DevPaths& p, F4* accum, const AdaptState& ad, const unsigned long long* prim_hits) {
+    if (prim_hits) hipLaunchKernelGGL((k_accumulate<true, true>), dim3(grid_for(f.npl, max_blocks)), dim3(kBlock), 0, st, f, p, accum, ad, prim_hits);
+    else hipLaunchKernelGGL((k_accumulate<true, false>), dim3(grid_for(f.npl, max_blocks)), dim3(kBlock), 0, st, f, p, accum, ad, prim_hits);
 }
 void launch_adaptive_error(hipStream_t st, const DevFrame& f, const F4* accum, const AdaptState& ad, float threshold, float dark_floor) {
     hipLaunchKernelGGL(k_adaptive_error, dim3(f.chunks_per_sample), dim3(kBlock), 0, st, f, accum, ad, threshold, dark_floor);

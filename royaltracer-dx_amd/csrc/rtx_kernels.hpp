@@ -103,9 +103,10 @@ struct DevPaths {
     F4* ray_d;   // dir.xyz, pdf of the BSDF sample that produced this ray
     F4* thr;     // throughput.xyz, seed.x bits
     F4* rad;     // radiance.xyz, -           (touched only when something is added)
-    F4* hit;     // t, u, v, global triangle id bits   (RTX_OPT_SHARED_PRIMARY, raygen -> bounce 0: pixel slot, seed.x, seed.y bits, -)
+    F4* hit;     // t, u, v, global triangle id bits
     unsigned long long* hitmask;   // fused tiny-scene path: bit (pid & 63) of word pid >> 6 = the primary ray hit something (rad is
-                                   // initialised only for those; k_accumulate treats the others as zero).  nullptr: rad is zeroed for all
+                                   // initialised only for those; k_accumulate treats the others as zero).  nullptr: rad is zeroed for all, or
+                                   // RTX_OPT_SHARED_PRIMARY: one mask per 8x8 block serves all samples (launch_accumulate: prim_hits)
     // shadow queues: [nee slot j][workgroup b][qcap] entries
     F4* sh_o;    // origin.xyz, tmin
     F4* sh_d;    // dir.xyz, tmax
@@ -121,6 +122,18 @@ struct DevPaths {
     // hold rays of one octant for long runs.  Hit records are still written at the entry's own position: k_shade reads its streams in order as before.  nullptr = off
     uint8_t* oct_out; const uint8_t* oct_in; uint32_t* perm; uint32_t key_mode;     // key_mode: RTX_OPT_OCTANT_SORT's value (1 octant, 3 origin cell)
 };
+
+// RTX_OPT_SHARED_PRIMARY, what bounce 0 starts from: the per-pixel records of k_primary_surface, their stream length (the shard's REAL slots: a pass of rtx_render_adaptive renders
+// a shorter, virtual frame, whose npl stays in DevFrame) and the division of a path id by the batch's npl as a multiplication: pid / npl = umulhi(pid, div_mul) >> div_shift,
+// exact for every pid < 2^31 (prim_in)
+struct PrimIn { const F4* rec; uint32_t npl, div_mul, div_shift; };
+// With l = ceil(log2 d) and m = floor(2^(31 + l) / d) + 1: m d = 2^(31 + l) + e, 0 < e <= d, so n m / 2^(31 + l) = n / d + n e / (d 2^(31 + l)), and for n < 2^31 the second
+// term is below 2^-l <= 1 / d: it cannot lift the fraction of n / d (at most (d - 1) / d) to 1.  m < 2^32 because d > 2^(l - 1).  npl is a multiple of 256, so l >= 8.
+inline PrimIn prim_in(const F4* rec, uint32_t rec_npl, uint32_t d) {
+    uint32_t l = 0; while ((1ull << l) < d) l++;
+    const uint64_t m = (1ull << (31u + l)) / d + 1ull;
+    return PrimIn{rec, rec_npl, (uint32_t)m, l - 1u};
+}
 
 // work area of the wavefront ReSTIR stages (rtx_restir_wave.hpp), device pointers; one pass at a time
 constexpr uint32_t kMaxMerge = 8;       // most sub-queues one workgroup of a traversal launch takes (MergedQ, rtx_traverse.hpp)
@@ -148,13 +161,13 @@ void launch_raygen(hipStream_t, const DevFrame&, const DevPaths&, const CameraGP
 void launch_trace_closest(hipStream_t, const DevFrame&, const DevScene&, const DevPaths&, uint32_t bounce, const uint32_t* queue, const uint32_t* qcount, uint32_t* heads, uint32_t merge = 1);   // merge: consecutive sub-queues per workgroup (MergedQ)
 void launch_packet_masks(hipStream_t, const DevScene&, const DevFrame&, const CameraGPU* cam, unsigned long long* masks);   // one 64-bit record mask per 8x8 pixel block of the shard
 void launch_raygen_trace_small(hipStream_t, const DevScene&, const DevFrame&, const DevPaths&, const CameraGPU* cam, uint32_t* queue, uint32_t* qcount, uint32_t* gencount, const unsigned long long* masks);
-// RTX_OPT_SHARED_PRIMARY: per pixel slot of the shard the primary hit and its surface (rec: 3 npl + 1 entries; hits: one lane mask per 8x8 block; masks as launch_packet_masks, which
-// this launch replaces), then a raygen that only enqueues the hitting paths with their pixel slot and seeds
+// RTX_OPT_SHARED_PRIMARY: per pixel slot of the shard the primary hit and its surface (rec: 3 npl + 1 entries; hits: 2 npl / 64 words, per 8x8 block the lanes that hit, then the lanes that own a pixel; masks as launch_packet_masks, which
+// this launch replaces), then a raygen that only enqueues the ids of the hitting paths
 void launch_primary_surface(hipStream_t, const DevScene&, const DevFrame&, const CameraGPU* cam, unsigned long long* masks, unsigned long long* hits, F4* rec);
-void launch_raygen_shared(hipStream_t, const DevFrame&, const DevPaths&, uint32_t* queue, uint32_t* qcount, uint32_t* gencount, const unsigned long long* hits);
+void launch_raygen_shared(hipStream_t, const DevFrame&, uint32_t* queue, uint32_t* qcount, uint32_t* gencount, const unsigned long long* hits, uint32_t rec_npl /* the real frame's slots (f: a pass of rtx_render_adaptive has fewer) */);
 void launch_bounce_small(hipStream_t, const DevScene&, const DevFrame&, const DevPaths&, uint32_t bounce_first, uint32_t bounce_end,
                          uint32_t* queue_a, uint32_t* queue_b, uint32_t* qrows, uint32_t* srows, const uint32_t* order, bool ring = true,
-                         const F4* prim_rec = nullptr);   // bounce 0 alone (reads the primary hits; prim_rec: starts from the records of launch_primary_surface instead), or a range of later bounces; ring: hits go through the LDS ring
+                         const PrimIn* prim = nullptr);   // bounce 0 alone (reads the primary hits; prim: starts from the records of launch_primary_surface instead), or a range of later bounces; ring: hits go through the LDS ring
 // general (BVH) path: trace -> shade -> shadow of a bounce range for every workgroup-private sub-queue in one launch (hitq: G * qcap indices of scratch)
 void launch_bounce_bvh(hipStream_t, const DevScene&, const DevFrame&, const DevPaths&, uint32_t bounce_first, uint32_t bounce_end,
                        uint32_t* queue_a, uint32_t* queue_b, uint32_t* hitq, uint32_t* qrows, uint32_t* srows, const uint32_t* order);
@@ -187,10 +200,11 @@ void launch_rs_p3_keys(hipStream_t, const DevFrame&, const RsQ&, uint32_t* const
 void launch_rs_p3_select(hipStream_t, const DevScene&, const DevFrame&, const RsQ&, const CameraGPU* cam, uint32_t* const bufs[6], uint32_t* shcnt, F4* key_a = nullptr, F4* key_b = nullptr);   // key_a != nullptr: select on the records
 void launch_rs_p3_merge(hipStream_t, const DevScene&, const DevFrame&, const RsQ&, uint32_t* const bufs[6], uint32_t* shcnt);
 void launch_rs_p3_shade(hipStream_t, const DevScene&, const DevFrame&, const RsQ&, uint32_t* const bufs[6], F4* accum);
-void launch_accumulate(hipStream_t, uint32_t max_blocks, const DevFrame&, const DevPaths&, F4* accum);
+// prim_hits (both forms): RTX_OPT_SHARED_PRIMARY in effect — the per-block hit masks of launch_primary_surface stand in for DevPaths::hitmask
+void launch_accumulate(hipStream_t, uint32_t max_blocks, const DevFrame&, const DevPaths&, F4* accum, const unsigned long long* prim_hits = nullptr);
 // ---- rtx_render_adaptive (rtx_k_adaptive.hpp); f is the REAL frame of the shard, state = the per-chunk words of the image (AdaptState) ----
 struct AdaptState { F4* half; uint32_t* count; uint32_t* flag; };   // half: W x H sums of the odd-id samples; per image chunk: samples taken, 0 sampling / 1 converged / 2 no valid pixel
-void launch_accumulate_list(hipStream_t, uint32_t max_blocks, const DevFrame&, const DevPaths&, F4* accum, const AdaptState&);   // the adaptive form: walks f.list, adds the odd ids into half too, bumps the chunks' counts
+void launch_accumulate_list(hipStream_t, uint32_t max_blocks, const DevFrame&, const DevPaths&, F4* accum, const AdaptState&, const unsigned long long* prim_hits = nullptr);   // the adaptive form: walks f.list, adds the odd ids into half too, bumps the chunks' counts
 void launch_adaptive_error(hipStream_t, const DevFrame&, const F4* accum, const AdaptState&, float threshold, float dark_floor);     // one workgroup per local chunk: the criterion -> flag
 // the unconverged chunks below max_spp that share the LOWEST count, in ascending order -> list; out[0] their number, [1] that count, [2] chunks converged, [3] unconverged at max_spp, [4] chunks with a valid pixel
 void launch_adaptive_compact(hipStream_t, const DevFrame&, const AdaptState&, uint32_t max_spp, uint32_t* list, uint32_t* out5);

@@ -123,6 +123,16 @@ RTX_HD void seed_init(uint32_t x, uint32_t y, uint32_t s, uint32_t frame_seed, u
     s0 = (y * 73856093u) ^ (x * 19349663u) ^ (s * 83492791u) ^ (frame_seed * 293803u);
     s1 = (x * 37623481u) ^ (y * 51964263u) ^ (s * 68250729u) ^ (frame_seed * 423977u);
 }
+// seed_init in two steps, for a caller that knows the pixel long before the sample: the pixel's terms once (seed_pixel), the rest per sample (seed_sample).  XOR is
+// associative and commutative, so seed_sample(seed_pixel(x, y), s, frame_seed) has the bits of seed_init(x, y, s, frame_seed).
+RTX_HD void seed_pixel(uint32_t x, uint32_t y, uint32_t& h0, uint32_t& h1) {
+    h0 = (y * 73856093u) ^ (x * 19349663u);
+    h1 = (x * 37623481u) ^ (y * 51964263u);
+}
+RTX_HD void seed_sample(uint32_t h0, uint32_t h1, uint32_t s, uint32_t frame_seed, uint32_t& s0, uint32_t& s1) {
+    s0 = h0 ^ (s * 83492791u) ^ (frame_seed * 293803u);
+    s1 = h1 ^ (s * 68250729u) ^ (frame_seed * 423977u);
+}
 
 // sin and cos of x in [0, 8): octant reduction (three-constant Cody-Waite split of pi/4) and
 // degree-7 / degree-8 polynomials on [-pi/4, pi/4].  Stands in for HLSL sin()/cos() in

@@ -67,14 +67,14 @@ struct FrameRun {
 int enqueue_tiny_fused(rtx_ctx* c, const FrameRun& R, const DevFrame& fb) {
     const hipStream_t st = R.st;
     uint32_t* gen_row = R.cnt + ((size_t)(R.mb + 1) + (size_t)R.mb * R.nee1) * R.G;
-    if (R.prim_rec) { Timed t(c, RTX_K_RAYGEN); launch_raygen_shared(st, fb, R.P, R.queue[0], R.Q(0), gen_row, (const unsigned long long*)c->pt.d_prim_hits.p); }
+    if (R.prim_rec) { Timed t(c, RTX_K_RAYGEN); launch_raygen_shared(st, fb, R.queue[0], R.Q(0), gen_row, (const unsigned long long*)c->pt.d_prim_hits.p, R.rec_npl); }
     else { Timed t(c, RTX_K_RAYGEN); launch_raygen_trace_small(st, c->dsc, fb, R.P, R.cam, R.queue[0], R.Q(0), gen_row, (const unsigned long long*)c->pt.d_pmask.p); }
     // dispatch order of the fused bounce kernels: longest sub-queue first, from the lengths after the primary rays (the later
     // bounces keep the ranking: survivors are a near-constant fraction)
     const uint32_t* order = nullptr;
     if (c->opt.lpt_order && R.G > 1) { launch_order_queues(st, R.Q(0), R.G, (uint32_t*)c->pt.d_order.p); order = (const uint32_t*)c->pt.d_order.p; }
-    DevFrame f0 = fb; f0.npl = R.rec_npl;                 // bounce 0 reads npl only to find the record streams, by the REAL slot that k_raygen_shared noted
-    { Timed t(c, RTX_K_BOUNCE); launch_bounce_small(st, c->dsc, f0, R.P, 0, 1, R.queue[0], R.queue[1], R.Q(0), R.S(0, 0), order, false, R.prim_rec); }
+    const PrimIn prim = prim_in(R.prim_rec, R.rec_npl, fb.npl);      // bounce 0 finds sample and slot from the path id (the batch's npl) and the record streams by the REAL slot (rec_npl)
+    { Timed t(c, RTX_K_BOUNCE); launch_bounce_small(st, c->dsc, fb, R.P, 0, 1, R.queue[0], R.queue[1], R.Q(0), R.S(0, 0), order, false, R.prim_rec ? &prim : nullptr); }
     if (R.mb > 1) { Timed t(c, RTX_K_BOUNCE); launch_bounce_small(st, c->dsc, fb, R.P, 1, R.mb, R.queue[0], R.queue[1], R.Q(0), R.S(0, 0), order, c->opt.bounce_ring); }
     return RTX_OK;
 }
@@ -216,7 +216,7 @@ int render_frame(rtx_ctx* c, const rtx_params* p, const DevFrame& f_real, uint32
     HIPCHK(c, c->pt.d_pmask.ensure(((size_t)f_real.npl / 64 + 1) * 8));        // (per real slot, like the shared-primary records: computed once per call)
     // RTX_OPT_SHARED_PRIMARY: without jitter the camera ray of a pixel is the same for every sample, so the fused tiny-scene path traces and reconstructs it once per call
     const bool shared_primary = tiny_fused && c->opt.shared_primary && !(p->flags & RTX_FLAG_JITTER);
-    if (shared_primary) { HIPCHK(c, c->pt.d_prim_rec.ensure(((size_t)f_real.npl * 3 + 1) * 16)); HIPCHK(c, c->pt.d_prim_hits.ensure(((size_t)f_real.npl / 64 + 1) * 8)); }
+    if (shared_primary) { HIPCHK(c, c->pt.d_prim_rec.ensure(((size_t)f_real.npl * 3 + 1) * 16)); HIPCHK(c, c->pt.d_prim_hits.ensure(((size_t)f_real.npl / 64 * 2 + 1) * 8)); }
     R.prim_rec = shared_primary ? (const F4*)c->pt.d_prim_rec.p : nullptr; R.rec_npl = f_real.npl;
     const size_t shn = qtot * R.nee1;
     HIPCHK(c, c->pt.d_sh_o.ensure(shn * 16)); HIPCHK(c, c->pt.d_sh_d.ensure(shn * 16)); HIPCHK(c, c->pt.d_sh_c.ensure(shn * 16));
@@ -227,7 +227,7 @@ int render_frame(rtx_ctx* c, const rtx_params* p, const DevFrame& f_real, uint32
     R.osort = c->opt.octant_sort && B.compact && !R.stealing;
     if (R.osort) { HIPCHK(c, c->pt.d_oct[0].ensure(qtot)); HIPCHK(c, c->pt.d_oct[1].ensure(qtot)); HIPCHK(c, c->pt.d_perm.ensure(qtot * 4)); }
     if (R.osort && c->opt.octant_sort == 2) { HIPCHK(c, hipMemsetAsync(c->pt.d_oct[0].p, 0, qtot, c->stream)); HIPCHK(c, hipMemsetAsync(c->pt.d_oct[1].p, 0, qtot, c->stream)); }
-    if (tiny_fused) { HIPCHK(c, c->pt.d_hitmask.ensure(((size_t)cap / 64 + 1) * 8)); P.hitmask = (unsigned long long*)c->pt.d_hitmask.p; }
+    if (tiny_fused && !shared_primary) { HIPCHK(c, c->pt.d_hitmask.ensure(((size_t)cap / 64 + 1) * 8)); P.hitmask = (unsigned long long*)c->pt.d_hitmask.p; }
     P.sh_o = (F4*)c->pt.d_sh_o.p; P.sh_d = (F4*)c->pt.d_sh_d.p; P.sh_c = (F4*)c->pt.d_sh_c.p;
     R.queue[0] = (uint32_t*)c->pt.d_queue[0].p; R.queue[1] = (uint32_t*)c->pt.d_queue[1].p;
     const uint32_t mb = R.mb, nee1 = R.nee1;
@@ -259,7 +259,8 @@ int render_frame(rtx_ctx* c, const rtx_params* p, const DevFrame& f_real, uint32
         r = tiny_fused ? enqueue_tiny_fused(c, R, fb) : fused_bvh ? enqueue_fused_bvh(c, R, fb) : enqueue_bounces(c, R, fb);
         if (r) return r;
         // ---- 5. accumulate, copy the counters ----
-        { Timed t(c, RTX_K_ACCUM); if (lp) launch_accumulate_list(st, B.max_blocks, fb, P, c->accum_ptr(), lp->state); else launch_accumulate(st, B.max_blocks, fb, P, c->accum_ptr()); }
+        { Timed t(c, RTX_K_ACCUM); const unsigned long long* ph = shared_primary ? (const unsigned long long*)c->pt.d_prim_hits.p : nullptr;      // (one hit mask per block for all samples; P.hitmask is null then)
+          if (lp) launch_accumulate_list(st, B.max_blocks, fb, P, c->accum_ptr(), lp->state, ph); else launch_accumulate(st, B.max_blocks, fb, P, c->accum_ptr(), ph); }
         HIPCHK(c, hipMemcpyAsync(c->pt.h_counters.as<uint32_t>() + (size_t)bi * ncnt, R.cnt, ncnt * 4, hipMemcpyDeviceToHost, st));
     }
     HIPCHK(c, hipEventRecord(c->ev.end, st));
