@@ -7,14 +7,9 @@ extern "C" {
 
 int rtx_render_adaptive(rtx_ctx* c, const rtx_params* p, const rtx_adaptive* a, rtx_adaptive_result* out) {
     // ---- 1. validate: a call that fails leaves image and state untouched ----
-    BIND(c);
-    if (!c->committed) { c->err = "render: scene not committed"; return RTX_ERR_STATE; }
-    if (!c->camera_set) { c->err = "render: camera not set"; return RTX_ERR_STATE; }
     DevFrame f;
-    int r = make_frame(c, p, f);
+    int r = render_checks(c, p, false, f);
     if (r) return r;
-    if (p->max_bounces == 0 || p->max_bounces > 64) { c->err = "params: max_bounces must be in [1, 64]"; return RTX_ERR_INVALID; }
-    if (p->nee_samples > 16) { c->err = "params: nee_samples must be <= 16"; return RTX_ERR_INVALID; }
     if (!a) { c->err = "render_adaptive: no rtx_adaptive"; return RTX_ERR_INVALID; }
     // the two half sums are equally large only at even counts
     if (a->min_spp < 2 || (a->min_spp & 1u) || a->step_spp < 2 || (a->step_spp & 1u)) { c->err = "render_adaptive: min_spp and step_spp must be even and >= 2"; return RTX_ERR_INVALID; }
@@ -39,11 +34,7 @@ int rtx_render_adaptive(rtx_ctx* c, const rtx_params* p, const rtx_adaptive* a, 
     const AdaptState S{(F4*)c->ad.d_half.p, (uint32_t*)c->ad.d_count.p, (uint32_t*)c->ad.d_flag.p};
     uint32_t* list = (uint32_t*)c->ad.d_list.p;
     const float dark_floor = a->dark_floor == 0.0f ? 0.01f : a->dark_floor;
-    memset(c->stats.kernel_ms, 0, sizeof(c->stats.kernel_ms));
-    memset(c->stats.kernel_launches, 0, sizeof(c->stats.kernel_launches));
-    memset(c->stats.kernel_items, 0, sizeof(c->stats.kernel_items));
-    c->stats.rays_primary = c->stats.rays_extension = c->stats.rays_shadow = c->stats.paths = c->stats.primary_hits = 0; c->stats.render_ms = 0;
-    c->ev.used = 0; c->timed.clear();
+    stats_begin(c);
 
     // ---- 3. the passes.  Synchronous whatever RTX_OPT_ASYNC says: the host sizes every pass by the list's length ----
     uint32_t h[5] = {0, 0, 0, 0, 0}, passes = 0;

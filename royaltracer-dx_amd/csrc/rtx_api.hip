@@ -16,6 +16,32 @@ void options_to_scene(rtx_ctx* c, bool committed) {
     }
 }
 
+// What every render entry point checks first, in this order: the context (joining a frame left in flight), the committed scene, the camera, the frame of `p`, the limits.
+// zero_bounces_ok: false = the path tracer (rtx_render, rtx_render_adaptive: max_bounces in [1, 64]), true = the ReSTIR entry points (pass 1 alone is a frame: [0, 64]);
+// the two kinds of call also word the error differently.  Touches no image and no state.
+int render_checks(rtx_ctx* c, const rtx_params* p, bool zero_bounces_ok, DevFrame& f) {
+    BIND(c);
+    if (!c->committed) { c->err = "render: scene not committed"; return RTX_ERR_STATE; }
+    if (!c->camera_set) { c->err = "render: camera not set"; return RTX_ERR_STATE; }
+    const int r = make_frame(c, p, f);
+    if (r) return r;
+    if (zero_bounces_ok) {
+        if (p->max_bounces > 64 || p->nee_samples > 16) { c->err = "params: max_bounces <= 64, nee_samples <= 16"; return RTX_ERR_INVALID; }
+        return RTX_OK;
+    }
+    if (p->max_bounces == 0 || p->max_bounces > 64) { c->err = "params: max_bounces must be in [1, 64]"; return RTX_ERR_INVALID; }
+    if (p->nee_samples > 16) { c->err = "params: nee_samples must be <= 16"; return RTX_ERR_INVALID; }
+    return RTX_OK;
+}
+// the one reset of a frame's statistics (stats_end_restir / finish_render fill them in) and of the timing events: the union of what the entry points used to reset
+void stats_begin(rtx_ctx* c) {
+    memset(c->stats.kernel_ms, 0, sizeof(c->stats.kernel_ms));
+    memset(c->stats.kernel_launches, 0, sizeof(c->stats.kernel_launches));
+    memset(c->stats.kernel_items, 0, sizeof(c->stats.kernel_items));
+    c->stats.rays_primary = c->stats.rays_extension = c->stats.rays_shadow = c->stats.paths = c->stats.primary_hits = 0; c->stats.render_ms = 0;
+    c->ev.used = 0; c->timed.clear();
+}
+
 int ensure_accum(rtx_ctx* c, uint32_t w, uint32_t h, bool clear) {
     const size_t need = (size_t)w * h * 16;
     if (c->ext_accum) {

@@ -1,5 +1,6 @@
 // rtx_ctx.hpp — PRIVATE header of the C-ABI's translation units: the context (struct rtx_ctx), the macros every entry point uses and the helpers they share.
-//   rtx_api.hip          create / destroy, options, stream, scene inputs, camera, accumulation, reads, statistics, tile pack / unpack, the shard tiling
+//   rtx_api.hip          create / destroy, options, stream, scene inputs, camera, accumulation, reads, statistics, tile pack / unpack, the shard tiling,
+//                        and what the render entry points share: render_checks (their preamble) and stats_begin (the one statistics reset)
 //   rtx_commit.hip       rtx_commit_scene (host or GPU build, GPU refit), the scene cache, finalise_scene
 //   rtx_render.hip       rtx_render (the wavefront path tracer), render_frame and finish_render
 //   rtx_adaptive.hip     rtx_render_adaptive: passes of render_frame over the chunks that have not converged
@@ -211,6 +212,8 @@ struct Timed {
 
 // rtx_api.hip
 void options_to_scene(rtx_ctx* c, bool committed);
+int render_checks(rtx_ctx* c, const rtx_params* p, bool zero_bounces_ok, DevFrame& f);    // the preamble of every render entry point: context, scene, camera, frame, limits
+void stats_begin(rtx_ctx* c);
 int ensure_accum(rtx_ctx* c, uint32_t w, uint32_t h, bool clear);
 const char* validate_tiling(const rtx_params* p, uint32_t& ts, uint32_t& cnt, uint64_t& npl, uint32_t* gx_out = nullptr, uint32_t* gy_out = nullptr);
 int make_frame(rtx_ctx* c, const rtx_params* p, DevFrame& f);

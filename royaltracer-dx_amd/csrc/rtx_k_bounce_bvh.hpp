@@ -1,7 +1,6 @@
 // rtx_k_bounce_bvh.hpp — the fused bounce kernel of the general (BVH) path, and the dispatch order of the fused kernels
 // One of the kernel headers of rtx_kernels.hip, the path tracer's single translation unit (see its header comment for the design and for why).
 #pragma once
-#include <type_traits>
 #include "rtx_shade.hpp"
 
 namespace rtx {
@@ -39,8 +38,7 @@ __global__ __launch_bounds__(kBlock, 5) void k_bounce_bvh(DevScene sc, DevFrame 
     const size_t qb = (size_t)qid * f.qcap;
     uint32_t* myhits = hitq + qb;
     uint32_t n = qrows[(size_t)bounce_first * G + qid];
-    typename std::conditional<STK == 1, StackPriv, StackLdsT<STK == 2>>::type stk;
-    if constexpr (STK != 1) stk.init(L);
+    TraceStack<STK> stk; stk.init(L);
     for (uint32_t bounce = bounce_first; bounce < bounce_end; bounce++) {
         const bool last = (bounce + 1u == f.max_bounces);
         const float tmin = bounce_tmin(bounce);
@@ -67,7 +65,8 @@ __global__ __launch_bounds__(kBlock, 5) void k_bounce_bvh(DevScene sc, DevFrame 
         }
         __syncthreads();
         const uint32_t nh = s_nh;
-        // ---- phase 2: shade the hits ----
+        // ---- phase 2: shade the hits.  DEFINITION: shade_item<false> (rtx_k_shade.hpp) — this is its body without the compact path state, the sort keys and the shared
+        // view terms (MixView), none of which this path uses; change the two together.  (Calling it here is the same arithmetic but slower: profiles/fold_frame_time.md) ----
         for (uint32_t base = threadIdx.x & ~63u; base < nh; base += kBlock) {
             const uint32_t i = base + (threadIdx.x & 63u);
             PathState S; S.pid = 0; S.o = mk3(0, 0, 0); S.d = mk3(0, 0, 1); S.thr = mk3(0, 0, 0); S.prev_pdf = 1.0f; S.s0 = S.s1 = 0;
@@ -119,13 +118,7 @@ __global__ __launch_bounds__(kBlock, 5) void k_bounce_bvh(DevScene sc, DevFrame 
                        })) {
                     spec_step<true>(sc, L, R, stk, sc.trace_sched);
                     if (R.has && R.done) {
-                        if (R.bprim == kMissPrim) {                            // visible
-                            const F4 c = p.sh_c[sb + R.item];
-                            const uint32_t pid = f2u(c.w);
-                            F4 r = p.rad[pid];
-                            r.x = r.x + c.x; r.y = r.y + c.y; r.z = r.z + c.z;
-                            p.rad[pid] = r;
-                        }
+                        if (R.bprim == kMissPrim) add_visible(p, p.sh_c, sb + R.item);
                         R.has = false;
                     }
                 }

@@ -29,8 +29,7 @@ __global__ __launch_bounds__(kBlock, WAVES) void k_bounce_small(DevScene sc, con
     // ramp-up between the bounces; the sparsely populated late bounces cost a few loop trips instead of a launch each.
     extern __shared__ F4 lds[];
     __shared__ uint32_t s_cnt[1 + kMaxNee];
-    DevFrame f = f_in;
-    f.flags = LAMBERT ? (f_in.flags | 1u) : (f_in.flags & ~1u);      // bit 0 known at compile time
+    const DevFrame f = frame_with_lambert<LAMBERT>(f_in);           // bit 0 of the flags known at compile time
     const uint32_t qid = order ? order[blockIdx.x] : blockIdx.x;      // the sub-queue this workgroup owns (input and output)
 #ifdef RTX_WAVE_CLOCK        // tooling build: wave start / end stamps of the launch of bounces >= 1 (tools/wave_timeline.py cornell)
     #define RTX_WAVE_STAMP_B(K) do { const uint32_t w_ = blockIdx.x * (kBlock / 64u) + (threadIdx.x >> 6); if (!HAVE_HIT && lane_id() == 0 && w_ < 65536u) g_wgt[2u * w_ + (K)] = __builtin_amdgcn_s_memrealtime(); } while (0)

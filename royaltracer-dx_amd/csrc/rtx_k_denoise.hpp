@@ -4,25 +4,17 @@
 // PARITY-CRITICAL: tests/test_denoise_ref.py replays dn_tap operation for operation in numpy float32.  Only + - * / abs max, in the written order; no dot() / madd3() here
 // (those are fused), and the tap sum is sequential in tap order.  Do not reassociate, do not split the 5 x 5 window into passes.
 #pragma once
-#include "rtx_shade.hpp"
+#include "rtx_k_film.hpp"
 
 namespace rtx {
 
 constexpr uint32_t kDnNoGeo = 0xFFFFFFFFu;          // material word of a guide record: the pixel is not filterable by geometry (miss, material out of range, emitter seen directly)
 constexpr uint32_t kDnTileW = 32, kDnTileH = 8;     // one workgroup = 32 x 8 pixels: a wave is two rows of 32 neighbouring pixels, 512 contiguous bytes of a colour row each
 
-// Guides: k_debug_layer's ray (pixel corner, jitter-free, kTMinCam) and surface(); two F4 per pixel: (P, material word) (n, 0).  A pixel that is not filterable by geometry
+// Guides: the first hit of every pixel (for_each_first_hit, as k_debug_layer) and surface(); two F4 per pixel: (P, material word) (n, 0).  A pixel that is not filterable by geometry
 // gets (0, 0, 0, kDnNoGeo) (0, 0, 0, 0), so that a tap's class test and its material test are ONE compare of the material word with the centre's.
 __global__ __launch_bounds__(kBlock) void k_denoise_guides(DevScene sc, const SmallRecPair* __restrict__ small, uint32_t width, uint32_t height, const CameraGPU* __restrict__ cam, F4* __restrict__ guides) {
-    extern __shared__ F4 lds[];
-    const TraceLds L = stage_lds(sc, lds);
-    __syncthreads();
-    const uint32_t stride = gridDim.x * kBlock;
-    for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < width * height; i += stride) {
-        const uint32_t x = i % width, y = i / width;
-        f3 o, d; primary_ray(*cam, width, height, x, y, 0.0f, 0.0f, o, d);
-        float t, u, v; uint32_t prim;
-        trace_ray<false>(sc, small, L, o, d, kTMinCam, kTMax, t, u, v, prim);
+    for_each_first_hit(sc, small, width, height, cam, [&](uint32_t i, f3 o, f3 d, float t, float u, float v, uint32_t prim) {
         F4 g0 = {0.0f, 0.0f, 0.0f, u2f(kDnNoGeo)}, g1 = {0.0f, 0.0f, 0.0f, 0.0f};
         if (prim != kMissPrim) {
             const Surf sf = surface(sc, o, d, t, u, v, prim);
@@ -35,7 +27,7 @@ __global__ __launch_bounds__(kBlock) void k_denoise_guides(DevScene sc, const Sm
             }
         }
         guides[2 * (size_t)i] = g0; guides[2 * (size_t)i + 1] = g1;
-    }
+    });
 }
 
 // the colour a level reads.  Level 0 (FIRST) reads u1 and forms the mean as k_srgb8 does, c = u1.xyz / max(u1.w, 1), with w := 1 where the pixel holds samples, else 0;

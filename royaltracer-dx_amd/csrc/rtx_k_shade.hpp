@@ -18,6 +18,7 @@ namespace rtx {
 // each stream): still slower, k_shade per frame 7.4 -> 10.6 ms (Sponza-class), 8.6 -> 9.8 ms (Bistro-class, where k_shade is VALU-bound at
 // 33 of 64 lanes).  Hence RTX_OPT_SORT_MATERIALS defaults to 0.
 // One item of k_shade / k_shade_dense: entry `qi` of the workgroup's sub-queue (valid = the lane has one).  Every lane of the wave goes through the compactions.
+// (Phase 2 of k_bounce_bvh is a copy of this body without the compact state, the sort keys and MixView — calling it there measured slower: change the two together.)
 template <bool LAMBERT>
 __device__ __forceinline__ void shade_item(const DevScene& sc, const DevFrame& f, const DevPaths& p, uint32_t bounce, uint32_t nee, bool last, size_t qb,
                                            const uint32_t* __restrict__ myq, uint32_t* __restrict__ mynext, uint32_t* s_cnt, bool valid, uint32_t qi, Prof* pf, const float* lds_cdf = nullptr, const LightGPU* lds_lights = nullptr, const MatGPU* lds_mats = nullptr) {

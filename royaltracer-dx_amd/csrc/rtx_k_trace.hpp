@@ -1,8 +1,10 @@
-// rtx_k_trace.hpp — the two persistent traversal kernels of the general path (closest hit, any hit)
+// rtx_k_trace.hpp — the two persistent traversal kernels of the general path (closest hit, any hit).  Their stack is TraceStack<STK> (rtx_traverse.hpp); a visible
+// NEE sample is added by add_visible (rtx_shade.hpp), as in phase 3 of k_bounce_bvh.  The persistent loop (refill, wave-schedule step, retire) is written out in each
+// kernel on purpose: these kernels are compiled to a 64-VGPR cap, and with one lambda-taking driver the any-hit kernel compiled to 64 instead of 62 VGPRs (LDS stack) and
+// to 2 spilled VGPRs (overflow stack).
 // One of the kernel headers of rtx_kernels.hip, the path tracer's single translation unit (see its header comment for the design and for why).
 #pragma once
-#include <type_traits>
-#include "rtx_traverse.hpp"
+#include "rtx_shade.hpp"
 
 namespace rtx {
 
@@ -48,8 +50,7 @@ __global__ __launch_bounds__(kBlock, (SCHED >= 0 ? RTX_TRACE_WAVES : 1)) void k_
         }
         return;
     }
-    typename std::conditional<STK == 1, StackPriv, StackLdsT<STK == 2>>::type stk;
-    if constexpr (STK != 1) stk.init(L);
+    TraceStack<STK> stk; stk.init(L);
     RayLane R; ray_idle(R);
     bool drained = false;
     RaySource W{heads, qcount, gridDim.x, blockIdx.x, n, 0u, 0u};
@@ -97,13 +98,7 @@ __global__ __launch_bounds__(kBlock, (SCHED >= 0 ? RTX_TRACE_WAVES : 1)) void k_
     const size_t qb = (size_t)blockIdx.x * qcap;
     auto finish = [&](size_t gi, bool occluded) {         // gi: index into the launch's shadow-ray arrays (sub-queue * qcap + entry)
         if (SINK) { occ[pay[gi]] = occluded ? 1 : 0; return; }
-        if (!occluded) {
-            const F4 c = sh_c[gi];
-            const uint32_t pid = f2u(c.w);
-            F4 r = p.rad[pid];
-            r.x = r.x + c.x; r.y = r.y + c.y; r.z = r.z + c.z;
-            p.rad[pid] = r;
-        }
+        if (!occluded) add_visible(p, sh_c, gi);
     };
     if (SCHED < 0 && sc.nsmall) {
         for (uint32_t i = threadIdx.x; i < n; i += kBlock) {
@@ -115,8 +110,7 @@ __global__ __launch_bounds__(kBlock, (SCHED >= 0 ? RTX_TRACE_WAVES : 1)) void k_
         }
         return;
     }
-    typename std::conditional<STK == 1, StackPriv, StackLdsT<STK == 2>>::type stk;
-    if constexpr (STK != 1) stk.init(L);
+    TraceStack<STK> stk; stk.init(L);
     RayLane R; ray_idle(R);
     bool drained = false;
     RaySource W{heads, shcount, gridDim.x, blockIdx.x, n, 0u, 0u};

@@ -80,30 +80,30 @@ int trace_workgroups_per_cu(const DevScene& sc) {
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k_trace_shadow<0, false, 6>, (int)kBlock, trace_lds_bytes(sc)) != hipSuccess) return 0;
     return a < b ? a : b;
 }
+// run-time choices as compile-time constants: a launcher names its kernel once, with template arguments taken from the types of std::integral_constants
+template <int V> using IntC = std::integral_constant<int, V>;
+template <bool V> using BoolC = std::integral_constant<bool, V>;
+template <class F> static void dispatch_bool(bool v, F f) { if (v) f(BoolC<true>{}); else f(BoolC<false>{}); }
+
 void launch_raygen(hipStream_t st, const DevFrame& f, const DevPaths& p, const CameraGPU* cam, uint32_t* queue, uint32_t* qcount, bool compact) {
-    if (f.list) hipLaunchKernelGGL(k_raygen<true>, dim3(f.nblocks), dim3(kBlock), 0, st, f, p, cam, queue, qcount, compact ? 1u : 0u);
-    else hipLaunchKernelGGL(k_raygen<false>, dim3(f.nblocks), dim3(kBlock), 0, st, f, p, cam, queue, qcount, compact ? 1u : 0u);
+    dispatch_bool(f.list != nullptr, [&](auto list) { hipLaunchKernelGGL(k_raygen<decltype(list)::value>, dim3(f.nblocks), dim3(kBlock), 0, st, f, p, cam, queue, qcount, compact ? 1u : 0u); });
 }
 void launch_packet_masks(hipStream_t st, const DevScene& sc, const DevFrame& f, const CameraGPU* cam, unsigned long long* masks) {
     const uint32_t nblk = f.npl / 64u;
     hipLaunchKernelGGL(k_packet_masks, dim3((nblk + 3u) / 4u), dim3(kBlock), 0, st, sc, f, cam, masks);
 }
 void launch_raygen_trace_small(hipStream_t st, const DevScene& sc, const DevFrame& f, const DevPaths& p, const CameraGPU* cam, uint32_t* queue, uint32_t* qcount, uint32_t* gencount, const unsigned long long* masks) {
-    if (f.list) hipLaunchKernelGGL(k_raygen_trace_small<true>, dim3(f.nblocks), dim3(kBlock), trace_lds_bytes(sc), st, sc, sc.small, f, p, cam, queue, qcount, gencount, masks);
-    else hipLaunchKernelGGL(k_raygen_trace_small<false>, dim3(f.nblocks), dim3(kBlock), trace_lds_bytes(sc), st, sc, sc.small, f, p, cam, queue, qcount, gencount, masks);
+    dispatch_bool(f.list != nullptr, [&](auto list) { hipLaunchKernelGGL(k_raygen_trace_small<decltype(list)::value>, dim3(f.nblocks), dim3(kBlock), trace_lds_bytes(sc), st, sc, sc.small, f, p, cam, queue, qcount, gencount, masks); });
 }
 void launch_primary_surface(hipStream_t st, const DevScene& sc, const DevFrame& f, const CameraGPU* cam, unsigned long long* masks, unsigned long long* hits, F4* rec) {
     hipLaunchKernelGGL(k_primary_surface, dim3(f.npl / kBlock), dim3(kBlock), trace_lds_bytes(sc), st, sc, sc.small, f, cam, masks, hits, rec);
 }
 void launch_raygen_shared(hipStream_t st, const DevFrame& f, uint32_t* queue, uint32_t* qcount, uint32_t* gencount, const unsigned long long* hits, uint32_t rec_npl) {
-    if (f.list) hipLaunchKernelGGL(k_raygen_shared<true>, dim3(f.nblocks), dim3(kBlock), 0, st, f, queue, qcount, gencount, hits, rec_npl >> 6);
-    else hipLaunchKernelGGL(k_raygen_shared<false>, dim3(f.nblocks), dim3(kBlock), 0, st, f, queue, qcount, gencount, hits, rec_npl >> 6);
+    dispatch_bool(f.list != nullptr, [&](auto list) { hipLaunchKernelGGL(k_raygen_shared<decltype(list)::value>, dim3(f.nblocks), dim3(kBlock), 0, st, f, queue, qcount, gencount, hits, rec_npl >> 6); });
 }
 // The launch of a persistent traversal kernel (k_trace_closest, k_trace_shadow): clamps `merge`, sizes the grid and maps (sc, heads) to the instantiation — stack kind, stealing,
-// compiled-in schedule, as std::integral_constants — and its dynamic LDS.  launch(stk, steal, sched, grid, lds_bytes, heads, merge) does the launch.
+// compiled-in schedule, as std::integral_constants (IntC / BoolC above) — and its dynamic LDS.  launch(stk, steal, sched, grid, lds_bytes, heads, merge) does the launch.
 // (launch_trace_occ has a narrower choice of its own: no private stack, no stealing.  Through this helper it would instantiate SINK-1 kernels nobody launches.)
-template <int V> using IntC = std::integral_constant<int, V>;
-template <bool V> using BoolC = std::integral_constant<bool, V>;
 template <class Launch>
 static void launch_trace_variant(const DevFrame& f, const DevScene& sc, uint32_t* heads, uint32_t merge, Launch launch) {
     if (sc.nsmall) heads = nullptr;                     // (the un-fused tiny-scene test path has no persistent waves)
@@ -137,12 +137,15 @@ void launch_bounce_small(hipStream_t st, const DevScene& sc, const DevFrame& f, 
     // with 2 spilled, measured the same: 19.13 vs 19.03 ms).  Bounce 0 (reads the primary hits) is its own instantiation and launch.
     const bool lam = (f.flags & 1u) != 0u, have_hit = bounce_first == 0u;
     const PrimIn pin = prim ? *prim : PrimIn{};
-#define RTX_LAUNCH_BOUNCE(HH, LL, RR) hipLaunchKernelGGL((k_bounce_small<4, HH, LL, RR>), dim3(f.nblocks), dim3(kBlock), trace_lds_bytes(sc), st, sc, sc.small, f, p, bounce_first, bounce_end, queue_a, queue_b, qrows, srows, order, pin)
-    if (have_hit && prim) { if (lam) RTX_LAUNCH_BOUNCE(2, true, false); else RTX_LAUNCH_BOUNCE(2, false, false); }
-    else if (have_hit) { if (lam) RTX_LAUNCH_BOUNCE(1, true, false); else RTX_LAUNCH_BOUNCE(1, false, false); }
-    else if (ring) { if (lam) RTX_LAUNCH_BOUNCE(0, true, true); else RTX_LAUNCH_BOUNCE(0, false, true); }
-    else { if (lam) RTX_LAUNCH_BOUNCE(0, true, false); else RTX_LAUNCH_BOUNCE(0, false, false); }
-#undef RTX_LAUNCH_BOUNCE
+    auto go = [&](auto hh, auto rr) {       // hh: where bounce 0's hits come from (0 = not bounce 0, 1 = the hit buffer, 2 = the shared primary records); rr: the hit ring
+        dispatch_bool(lam, [&](auto ll) {
+            hipLaunchKernelGGL((k_bounce_small<4, decltype(hh)::value, decltype(ll)::value, decltype(rr)::value>), dim3(f.nblocks), dim3(kBlock), trace_lds_bytes(sc), st,
+                               sc, sc.small, f, p, bounce_first, bounce_end, queue_a, queue_b, qrows, srows, order, pin);
+        });
+    };
+    if (have_hit && prim) go(IntC<2>{}, BoolC<false>{});
+    else if (have_hit) go(IntC<1>{}, BoolC<false>{});
+    else dispatch_bool(ring, [&](auto rr) { go(IntC<0>{}, rr); });
 }
 void launch_bounce_bvh(hipStream_t st, const DevScene& sc, const DevFrame& f, const DevPaths& p, uint32_t bounce_first, uint32_t bounce_end,
                        uint32_t* queue_a, uint32_t* queue_b, uint32_t* hitq, uint32_t* qrows, uint32_t* srows, const uint32_t* order) {
@@ -164,15 +167,14 @@ static size_t shade_lds_bytes(const DevScene& sc, bool sort) { uint32_t lb, mb; 
 void launch_shade(hipStream_t st, const DevScene& sc, const DevFrame& f, const DevPaths& p, uint32_t bounce,
                   const uint32_t* queue, const uint32_t* qcount, uint32_t* next_queue, uint32_t* next_count, uint32_t* shcounts) {
     // material-sorted variant: measured slower (see k_shade), the permutation un-coalesces the per-path state streams
-#define RTX_LAUNCH_SHADE(SS, LL) hipLaunchKernelGGL((k_shade<SS, LL>), dim3(f.nblocks), dim3(kBlock), shade_lds_bytes(sc, SS), st, sc, f, p, bounce, queue, qcount, next_queue, next_count, shcounts)
-    const bool lam = (f.flags & 1u) != 0u;
-    if (sc.shade_dense && !sc.sort_materials) {
-        if (lam) hipLaunchKernelGGL((k_shade_dense<true>), dim3(f.nblocks), dim3(kBlock), 0, st, sc, f, p, bounce, queue, qcount, next_queue, next_count, shcounts);
-        else hipLaunchKernelGGL((k_shade_dense<false>), dim3(f.nblocks), dim3(kBlock), 0, st, sc, f, p, bounce, queue, qcount, next_queue, next_count, shcounts);
-    }
-    else if (sc.sort_materials) { if (lam) RTX_LAUNCH_SHADE(true, true); else RTX_LAUNCH_SHADE(true, false); }
-    else { if (lam) RTX_LAUNCH_SHADE(false, true); else RTX_LAUNCH_SHADE(false, false); }
-#undef RTX_LAUNCH_SHADE
+    dispatch_bool((f.flags & 1u) != 0u, [&](auto lam) {
+        constexpr bool LL = decltype(lam)::value;
+        if (sc.shade_dense && !sc.sort_materials) hipLaunchKernelGGL((k_shade_dense<LL>), dim3(f.nblocks), dim3(kBlock), 0, st, sc, f, p, bounce, queue, qcount, next_queue, next_count, shcounts);
+        else dispatch_bool(sc.sort_materials != 0u, [&](auto sort) {
+            constexpr bool SS = decltype(sort)::value;
+            hipLaunchKernelGGL((k_shade<SS, LL>), dim3(f.nblocks), dim3(kBlock), shade_lds_bytes(sc, SS), st, sc, f, p, bounce, queue, qcount, next_queue, next_count, shcounts);
+        });
+    });
 }
 void launch_v6_pass1(hipStream_t st, uint32_t max_blocks, const DevScene& sc, const DevFrame& f, const CameraGPU* cam, uint32_t sample_id,
                      F4* accum, uint32_t* res_di, uint32_t* res_gi, uint32_t* sdata, unsigned long long* counters, const uint32_t* pixels, uint32_t npixels) {
@@ -194,8 +196,7 @@ void launch_restir_halo(hipStream_t st, uint32_t max_blocks, uint32_t width, boo
     HaloRects R{}; R.n = n; R.first[0] = 0;
     for (uint32_t k = 0; k < n; k++) { R.x0[k] = rects4[4 * k]; R.y0[k] = rects4[4 * k + 1]; R.w[k] = rects4[4 * k + 2]; R.first[k + 1] = R.first[k] + rects4[4 * k + 2] * rects4[4 * k + 3]; }
     if (!R.first[n]) return;
-    if (pack) hipLaunchKernelGGL(k_restir_halo<true>, dim3(grid_for(R.first[n], max_blocks)), dim3(kBlock), 0, st, width, R, rs_bufs(bufs), buf);
-    else hipLaunchKernelGGL(k_restir_halo<false>, dim3(grid_for(R.first[n], max_blocks)), dim3(kBlock), 0, st, width, R, rs_bufs(bufs), buf);
+    dispatch_bool(pack, [&](auto pk) { hipLaunchKernelGGL(k_restir_halo<decltype(pk)::value>, dim3(grid_for(R.first[n], max_blocks)), dim3(kBlock), 0, st, width, R, rs_bufs(bufs), buf); });
 }
 void launch_restir_pass3(hipStream_t st, uint32_t max_blocks, const DevScene& sc, const DevFrame& f, const CameraGPU* cam, uint32_t* const bufs[6], F4* accum, unsigned long long* counters) {
     hipLaunchKernelGGL(k_restir_pass3, dim3(grid_for(f.npl, max_blocks)), dim3(kBlock), trace_lds_bytes(sc), st, sc, sc.small, f, cam, rs_bufs(bufs), accum, counters);
@@ -206,10 +207,13 @@ void launch_trace_occ(hipStream_t st, const DevScene& sc_in, const RsQ& q, const
     // the visibility rays of the ReSTIR stages run between arbitrary scene points (reconnections, last frame's samples), not towards sampled lights: the NEE probe's
     // order does not carry over — slot order measured best on all three scenes (atrium 8.28 vs 8.38 ms, garage 6.74 vs 6.84, street 7.99 vs 8.02-8.12 per frame with orders 1 / 2)
     DevScene sc = sc_in; sc.any_order = sc_in.any_order_occ;
-#define RTX_LAUNCH_TO(CC) hipLaunchKernelGGL((k_trace_shadow<SL_, false, CC, 1>), dim3(q.G), dim3(kBlock), trace_lds_bytes(sc), st, sc, sc.small, none, q.sh_o, q.sh_d, (const F4*)nullptr, shcnt, q.rcap, sc.refill_min, sc.trace_sched, (uint32_t*)nullptr, q.G, 1u, q.sh_pay, q.occ)
-    if (sc.stack_ovf) { constexpr int SL_ = 2; if (sc.trace_sched == 6u && !sc.nsmall && !sc.trace_cnt) RTX_LAUNCH_TO(6); else RTX_LAUNCH_TO(-1); }
-    else { constexpr int SL_ = 0; if (sc.trace_sched == 6u && !sc.nsmall && !sc.trace_cnt) RTX_LAUNCH_TO(6); else RTX_LAUNCH_TO(-1); }
-#undef RTX_LAUNCH_TO
+    const bool sched6 = sc.trace_sched == 6u && !sc.nsmall && !sc.trace_cnt;        // as launch_trace_variant: the default schedule compiled in
+    dispatch_bool(sc.stack_ovf != nullptr, [&](auto ovf) {
+        dispatch_bool(sched6, [&](auto s6) {
+            hipLaunchKernelGGL((k_trace_shadow<(decltype(ovf)::value ? 2 : 0), false, (decltype(s6)::value ? 6 : -1), 1>), dim3(q.G), dim3(kBlock), trace_lds_bytes(sc), st,
+                               sc, sc.small, none, q.sh_o, q.sh_d, (const F4*)nullptr, shcnt, q.rcap, sc.refill_min, sc.trace_sched, (uint32_t*)nullptr, q.G, 1u, q.sh_pay, q.occ);
+        });
+    });
 }
 void launch_rs_raygen(hipStream_t st, const DevFrame& f, const RsQ& q, const CameraGPU* cam, uint32_t sample_id, uint32_t* cnt_out) {
     hipLaunchKernelGGL(k_rs_raygen, dim3(q.G), dim3(kBlock), 0, st, f, q, cam, sample_id, cnt_out);
@@ -252,12 +256,10 @@ void launch_rs_p3_shade(hipStream_t st, const DevScene& sc, const DevFrame& f, c
     hipLaunchKernelGGL(k_rs_p3_shade, dim3(q.G), dim3(kBlock), 0, st, sc, f, q, rs_bufs(bufs), accum);
 }
 void launch_accumulate(hipStream_t st, uint32_t max_blocks, const DevFrame& f, const DevPaths& p, F4* accum, const unsigned long long* prim_hits) {
-    if (prim_hits) hipLaunchKernelGGL((k_accumulate<false, true>), dim3(grid_for(f.npl, max_blocks)), dim3(kBlock), 0, st, f, p, accum, AdaptState{}, prim_hits);
-    else hipLaunchKernelGGL((k_accumulate<false, false>), dim3(grid_for(f.npl, max_blocks)), dim3(kBlock), 0, st, f, p, accum, AdaptState{}, prim_hits);
+    dispatch_bool(prim_hits != nullptr, [&](auto ph) { hipLaunchKernelGGL((k_accumulate<false, decltype(ph)::value>), dim3(grid_for(f.npl, max_blocks)), dim3(kBlock), 0, st, f, p, accum, AdaptState{}, prim_hits); });
 }
 void launch_accumulate_list(hipStream_t st, uint32_t max_blocks, const DevFrame& f, const DevPaths& p, F4* accum, const AdaptState& ad, const unsigned long long* prim_hits) {
-    if (prim_hits) hipLaunchKernelGGL((k_accumulate<true, true>), dim3(grid_for(f.npl, max_blocks)), dim3(kBlock), 0, st, f, p, accum, ad, prim_hits);
-    else hipLaunchKernelGGL((k_accumulate<true, false>), dim3(grid_for(f.npl, max_blocks)), dim3(kBlock), 0, st, f, p, accum, ad, prim_hits);
+    dispatch_bool(prim_hits != nullptr, [&](auto ph) { hipLaunchKernelGGL((k_accumulate<true, decltype(ph)::value>), dim3(grid_for(f.npl, max_blocks)), dim3(kBlock), 0, st, f, p, accum, ad, prim_hits); });
 }
 void launch_adaptive_error(hipStream_t st, const DevFrame& f, const F4* accum, const AdaptState& ad, float threshold, float dark_floor) {
     hipLaunchKernelGGL(k_adaptive_error, dim3(f.chunks_per_sample), dim3(kBlock), 0, st, f, accum, ad, threshold, dark_floor);
@@ -272,12 +274,11 @@ uint32_t denoise_workgroups(uint32_t width, uint32_t height) { return ((width + 
 void launch_denoise_level(hipStream_t st, DenoiseLevel a, const F4* in, const F4* guides, F4* out, uint32_t* partial, bool staged) {
     a.tiles_x = (a.width + kDnTileW - 1u) / kDnTileW;
     const dim3 grid(denoise_workgroups(a.width, a.height));
-#define RTX_LAUNCH_DN(SS, FF) hipLaunchKernelGGL((k_denoise_level<SS, FF>), grid, dim3(kBlock), 0, st, a, in, guides, out, partial)
-    if (a.first) { if (staged && a.step == 1u) RTX_LAUNCH_DN(1, true); else RTX_LAUNCH_DN(0, true); }      // (the first level is the only one with step 1)
-    else if (staged && a.step == 2u) RTX_LAUNCH_DN(2, false);
-    else if (staged && a.step == 4u) RTX_LAUNCH_DN(4, false);
-    else RTX_LAUNCH_DN(0, false);
-#undef RTX_LAUNCH_DN
+    auto go = [&](auto ss, auto first) { hipLaunchKernelGGL((k_denoise_level<decltype(ss)::value, decltype(first)::value>), grid, dim3(kBlock), 0, st, a, in, guides, out, partial); };
+    if (a.first) { if (staged && a.step == 1u) go(IntC<1>{}, BoolC<true>{}); else go(IntC<0>{}, BoolC<true>{}); }      // (the first level is the only one with step 1)
+    else if (staged && a.step == 2u) go(IntC<2>{}, BoolC<false>{});
+    else if (staged && a.step == 4u) go(IntC<4>{}, BoolC<false>{});
+    else go(IntC<0>{}, BoolC<false>{});
 }
 void launch_denoise_count(hipStream_t st, const uint32_t* partial, uint32_t n, uint32_t* out) {
     hipLaunchKernelGGL(k_denoise_count, dim3(1), dim3(kBlock), 0, st, partial, n, out);

@@ -152,19 +152,11 @@ extern "C" {
 
 int rtx_render(rtx_ctx* c, const rtx_params* p) {
     // ---- 1. validate ----
-    BIND(c);
-    if (!c->committed) { c->err = "render: scene not committed"; return RTX_ERR_STATE; }
-    if (!c->camera_set) { c->err = "render: camera not set"; return RTX_ERR_STATE; }
     DevFrame f;
-    int r = make_frame(c, p, f);
+    int r = render_checks(c, p, false, f);
     if (r) return r;
-    if (p->max_bounces == 0 || p->max_bounces > 64) { c->err = "params: max_bounces must be in [1, 64]"; return RTX_ERR_INVALID; }
-    if (p->nee_samples > 16) { c->err = "params: nee_samples must be <= 16"; return RTX_ERR_INVALID; }
     if ((r = ensure_accum(c, p->width, p->height, false))) return r;
-    memset(c->stats.kernel_ms, 0, sizeof(c->stats.kernel_ms));
-    memset(c->stats.kernel_launches, 0, sizeof(c->stats.kernel_launches));
-    memset(c->stats.kernel_items, 0, sizeof(c->stats.kernel_items));
-    c->stats.rays_primary = c->stats.rays_extension = c->stats.rays_shadow = c->stats.paths = c->stats.primary_hits = 0; c->stats.render_ms = 0;
+    stats_begin(c);
     if (p->spp == 0) return RTX_OK;
     c->ad.pure = false;                        // u1 now holds samples that `half` does not know: rtx_render_adaptive refuses until the next clear
     if ((r = render_frame(c, p, f, p->spp, nullptr))) return r;

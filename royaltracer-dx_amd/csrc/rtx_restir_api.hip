@@ -113,26 +113,18 @@ static int rs_lanes(rtx_ctx* c, const uint32_t* pixels, uint32_t npixels, F&& pa
     return RTX_OK;
 }
 }  // extern "C++"
-static void stats_begin(rtx_ctx* c) {
-    memset(c->stats.kernel_ms, 0, sizeof(c->stats.kernel_ms)); memset(c->stats.kernel_launches, 0, sizeof(c->stats.kernel_launches)); memset(c->stats.kernel_items, 0, sizeof(c->stats.kernel_items));
-    c->ev.used = 0; c->timed.clear();
-}
 static void stats_end_restir(rtx_ctx* c, const unsigned long long cnt[3]) {
     float ms = 0.0f;
     if (hipEventElapsedTime(&ms, c->ev.begin, c->ev.end) == hipSuccess) c->stats.render_ms = ms;
-    for (const TimedLaunch& t : c->timed) { float m = 0.0f; if (hipEventElapsedTime(&m, t.a, t.b) == hipSuccess) c->stats.kernel_ms[t.cls] += m; }
+    collect_timed(c);
     c->stats.rays_primary = cnt[0]; c->stats.rays_extension = cnt[1]; c->stats.rays_shadow = cnt[2]; c->stats.paths = cnt[0]; c->stats.primary_hits = 0;
     c->stats.kernel_items[RTX_K_RAYGEN] = cnt[0]; c->stats.kernel_items[RTX_K_TRACE] = cnt[0] + cnt[1]; c->stats.kernel_items[RTX_K_SHADOW] = cnt[2];
 }
 
 int rtx_render_v6_pass1(rtx_ctx* c, const rtx_params* p) {
-    BIND(c);
-    if (!c->committed) { c->err = "render: scene not committed"; return RTX_ERR_STATE; }
-    if (!c->camera_set) { c->err = "render: camera not set"; return RTX_ERR_STATE; }
     DevFrame f;
-    int r = make_frame(c, p, f);
+    int r = render_checks(c, p, true, f);
     if (r) return r;
-    if (p->max_bounces > 64 || p->nee_samples > 16) { c->err = "params: max_bounces <= 64, nee_samples <= 16"; return RTX_ERR_INVALID; }
     if ((r = ensure_accum(c, p->width, p->height, false))) return r;
     c->ad.pure = false;                        // (rtx_render_adaptive: u1 gets samples its second sum does not hold)
     const size_t slots = rtx_pass1_slots(p->width, p->height);
@@ -174,13 +166,9 @@ int rtx_restir_reset(rtx_ctx* c) {
 }
 
 int rtx_render_restir(rtx_ctx* c, const rtx_params* p) {
-    BIND(c);
-    if (!c->committed) { c->err = "render: scene not committed"; return RTX_ERR_STATE; }
-    if (!c->camera_set) { c->err = "render: camera not set"; return RTX_ERR_STATE; }
     DevFrame f;
-    int r = make_frame(c, p, f);
+    int r = render_checks(c, p, true, f);
     if (r) return r;
-    if (p->max_bounces > 64 || p->nee_samples > 16) { c->err = "params: max_bounces <= 64, nee_samples <= 16"; return RTX_ERR_INVALID; }
     // ReSTIR ON SHARDS (shard_count > 1).  The spatial pass of a pixel reads this frame's pass-1 / pass-2 records of neighbours within 20 px
     // (RayGen_v6_pass3.hlsl:46-372) and the temporal pass reads last frame's history at an arbitrary reprojected pixel (RayGen_v6_pass2.hlsl:46-204).  So a shard
     //   * runs passes 1 and 2 on its tiles DILATED by 20 px (the halo is recomputed: seeds depend on the pixel only, results are what the owner computes),

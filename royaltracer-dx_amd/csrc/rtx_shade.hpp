@@ -99,6 +99,15 @@ __device__ __forceinline__ void add_emissive(const DevScene& sc, const DevPaths&
     }
     p.rad[S.pid] = radv;
 }
+// a visible NEE sample: its contribution sh_c[gi] = (rgb, path id bits) is added to that path's radiance.  A path appears at most once per NEE slot, so the
+// read-modify-write needs no atomic and the order of additions per path is fixed (k_trace_shadow, phase 3 of k_bounce_bvh)
+__device__ __forceinline__ void add_visible(const DevPaths& p, const F4* __restrict__ sh_c, size_t gi) {
+    const F4 c = sh_c[gi];
+    const uint32_t pid = f2u(c.w);
+    F4 r = p.rad[pid];
+    r.x = r.x + c.x; r.y = r.y + c.y; r.z = r.z + c.z;
+    p.rad[pid] = r;
+}
 
 // one NEE sample: SampleLightNEE_GI, Sampler_v6.hlsl:508-647.  Returns true when a shadow ray is needed.
 // mv: the view terms of the shading point (mix_view), shared with the continuation's mixture by k_shade; nullptr = computed here

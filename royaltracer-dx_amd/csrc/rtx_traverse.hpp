@@ -1,6 +1,9 @@
 // rtx_traverse.hpp — ray traversal on the device: LDS staging, the exact triangle test, the compressed 8-wide BVH (node step, simple and
-// persistent-wave traversal with the while-while / voted / speculative schedules), the tiny-scene pre-test path, packet culling
+// persistent-wave traversal with the while-while / voted / speculative schedules), the tiny-scene pre-test path, packet culling.
+// The rules every traversal shares are written once: safe_idir, root_group, load_tri, closer (the tie rule of the closest hit); traverse<ANY, COUNT> is
+// the one simple traversal (COUNT: with the statistics counters), TraceStack<STK> the stack of the persistent kernels.
 #pragma once
+#include <type_traits>
 #include "rtx_dev_common.hpp"
 
 namespace rtx {
@@ -229,7 +232,9 @@ struct StackLdsT { lds_u32* cb; lds_u16* ck; unsigned long long* ov; int cap; ui
                    } };
 using StackLds = StackLdsT<true>;          // the general-purpose paths (debug queries, literal ReSTIR kernels, fused experiments): always safe, whatever the scene's cap
 constexpr int kPrivStack = 32;
-struct StackPriv { Grp a[kPrivStack]; __device__ __forceinline__ void put(int i, Grp g) { a[i] = g; } __device__ __forceinline__ Grp get(int i) const { return a[i]; } };
+struct StackPriv { Grp a[kPrivStack]; __device__ __forceinline__ void init(const TraceLds&) {} __device__ __forceinline__ void put(int i, Grp g) { a[i] = g; } __device__ __forceinline__ Grp get(int i) const { return a[i]; } };
+// the stack of the persistent traversal kernels by their STK parameter: 0 = LDS column (tree within the cap), 1 = private (scratch), 2 = LDS column with overflow
+template <int STK> using TraceStack = typename std::conditional<STK == 1, StackPriv, StackLdsT<STK == 2>>::type;
 
 // pick the first child of group G (which has internal hits), keep the remaining siblings on the stack, test the child's
 // eight children: G / T become the child's groups
@@ -254,73 +259,52 @@ __device__ __forceinline__ void descend8(const DevScene& sc, const TraceLds& L, 
 // index of the triangle behind bit `bit` of a triangle group
 __device__ __forceinline__ uint32_t tri_slot8(const TriGrp& T, uint32_t bit) { return T.base + (uint32_t)__builtin_popcount(T.valid & ((1u << bit) - 1u)); }
 
-template <bool ANY>
+// ---- the rules every traversal shares, each written once ---------------------------------------------------------
+// reciprocal direction; zero direction components -> huge finite reciprocal (keeps the slab test NaN-free and conservative)
+__device__ __forceinline__ f3 safe_idir(f3 d) {
+    const float dxs = fabsf(d.x) < 1e-30f ? copysignf(1e-30f, d.x) : d.x;
+    const float dys = fabsf(d.y) < 1e-30f ? copysignf(1e-30f, d.y) : d.y;
+    const float dzs = fabsf(d.z) < 1e-30f ? copysignf(1e-30f, d.z) : d.z;
+    return mk3(__builtin_amdgcn_rcpf(dxs), __builtin_amdgcn_rcpf(dys), __builtin_amdgcn_rcpf(dzs));
+}
+// group of a new ray: the root as slot 0 of a virtual parent.  The set bit is the one descend8 maps back to slot 0 (ordered: k ^ oct; any-hit rays: DevScene::any_order)
+__device__ __forceinline__ Grp root_group(uint32_t oct, bool ordered, uint32_t aord) {
+    return Grp{0u, (ordered ? (1u << oct) : (aord ? 1u << (oct ^ (aord == 2u ? 7u : 0u)) : 1u)) | (1u << 8)};
+}
+// triangle record `slot`: from the staged copy in LDS, or from global memory
+__device__ __forceinline__ void load_tri(const DevScene& sc, const TraceLds& L, uint32_t slot, v4f& v0, v4f& e1, v4f& e2) {
+    if (slot < sc.lds_tris) { const lds_v4f* t = L.tris + slot * 3u; v0 = t[0]; e1 = t[1]; e2 = t[2]; }
+    else { const v4f* t = (const v4f*)(sc.tris + slot); v0 = t[0]; e1 = t[1]; e2 = t[2]; }
+}
+// THE definition of "closest hit": the smaller t, and among equal t the lower global triangle id (the oracle's rule, independent of the order of the tests)
+// (the best hit by reference: as when written out at the call site, bprim is only read on a tie)
+__device__ __forceinline__ bool closer(float t, uint32_t gid, const float& bt, const uint32_t& bprim) { return t < bt || (t == bt && gid < bprim); }
+
+// COUNT: also counts node steps and triangle tests and returns them in bu / bv at every exit instead of the barycentrics (rtx_debug_trace_stats: tree-quality
+// measurements; ANY: the any-hit order probe of a GPU-built tree, rtx_commit.hip).  bt and bprim are what the plain traversal returns.
+template <bool ANY, bool COUNT = false>
 __device__ __forceinline__ void traverse(const DevScene& sc, const TraceLds& L, f3 o, f3 d, float tmin, float tmax,
                                          float& bt, float& bu, float& bv, uint32_t& bprim) {
-    // zero direction components -> huge finite reciprocal (keeps the slab test NaN-free and conservative)
-    const float dxs = fabsf(d.x) < 1e-30f ? copysignf(1e-30f, d.x) : d.x;
-    const float dys = fabsf(d.y) < 1e-30f ? copysignf(1e-30f, d.y) : d.y;
-    const float dzs = fabsf(d.z) < 1e-30f ? copysignf(1e-30f, d.z) : d.z;
-    const f3 idir = mk3(__builtin_amdgcn_rcpf(dxs), __builtin_amdgcn_rcpf(dys), __builtin_amdgcn_rcpf(dzs));
-    const uint32_t oct = ray_octant(idir);
-    bt = tmax; bu = 0.0f; bv = 0.0f; bprim = kMissPrim;
-    StackLds stk; stk.init(L);
-    int sp = 0;
-    Grp G{0u, (ANY ? (sc.any_order ? 1u << (oct ^ (sc.any_order == 2u ? 7u : 0u)) : 1u) : (1u << oct)) | (1u << 8)};    // the root as slot 0 of a virtual parent (any-hit rays: DevScene::any_order)
-    TriGrp T{0u, 0u, 0u};
-    while (true) {
-        if (G.bits & 0xffu) descend8<!ANY>(sc, L, o, idir, oct, tmin, bt, G, T, stk, sp);
-        while (T.bits) {
-            const uint32_t bit = (uint32_t)__builtin_ctz(T.bits);
-            T.bits &= T.bits - 1u;
-            const uint32_t slot = tri_slot8(T, bit);
-            v4f v0, e1, e2;
-            if (slot < sc.lds_tris) { const lds_v4f* t = L.tris + slot * 3u; v0 = t[0]; e1 = t[1]; e2 = t[2]; }
-            else { const v4f* t = (const v4f*)(sc.tris + slot); v0 = t[0]; e1 = t[1]; e2 = t[2]; }
-            float t, u, w;
-            if (tri_test(o, d, v0, e1, e2, tmin, tmax, t, u, w)) {
-                if (ANY) { bprim = 0u; return; }
-                const uint32_t gid = f2u(v0.w);
-                if (t < bt || (t == bt && gid < bprim)) { bt = t; bu = u; bv = w; bprim = gid; }
-            }
-        }
-        if (!(G.bits & 0xffu)) {
-            if (sp == 0) break;
-            sp--; G = stk.get(sp);
-        }
-    }
-}
-
-// traversal that also counts node steps and triangle tests (rtx_debug_trace_stats: tree-quality measurements; ANY: the any-hit order probe of a GPU-built tree, rtx_commit.hip)
-template <bool ANY = false>
-__device__ __forceinline__ void traverse_stats(const DevScene& sc, const TraceLds& L, f3 o, f3 d, float tmin, float tmax,
-                                         float& bt, float& bu, float& bv, uint32_t& bprim) {
     uint32_t nsteps = 0, ntris = 0;
-    // zero direction components -> huge finite reciprocal (keeps the slab test NaN-free and conservative)
-    const float dxs = fabsf(d.x) < 1e-30f ? copysignf(1e-30f, d.x) : d.x;
-    const float dys = fabsf(d.y) < 1e-30f ? copysignf(1e-30f, d.y) : d.y;
-    const float dzs = fabsf(d.z) < 1e-30f ? copysignf(1e-30f, d.z) : d.z;
-    const f3 idir = mk3(__builtin_amdgcn_rcpf(dxs), __builtin_amdgcn_rcpf(dys), __builtin_amdgcn_rcpf(dzs));
+    const f3 idir = safe_idir(d);
     const uint32_t oct = ray_octant(idir);
     bt = tmax; bu = 0.0f; bv = 0.0f; bprim = kMissPrim;
     StackLds stk; stk.init(L);
     int sp = 0;
-    Grp G{0u, (ANY ? (sc.any_order ? 1u << (oct ^ (sc.any_order == 2u ? 7u : 0u)) : 1u) : (1u << oct)) | (1u << 8)};    // the root as slot 0 of a virtual parent (any-hit rays: DevScene::any_order)
+    Grp G = root_group(oct, !ANY, sc.any_order);
     TriGrp T{0u, 0u, 0u};
     while (true) {
-        if (G.bits & 0xffu) { descend8<!ANY>(sc, L, o, idir, oct, tmin, bt, G, T, stk, sp); nsteps++; }
+        if (G.bits & 0xffu) { descend8<!ANY>(sc, L, o, idir, oct, tmin, bt, G, T, stk, sp); if (COUNT) nsteps++; }
         while (T.bits) {
             const uint32_t bit = (uint32_t)__builtin_ctz(T.bits);
-            T.bits &= T.bits - 1u; ntris++;
-            const uint32_t slot = tri_slot8(T, bit);
+            T.bits &= T.bits - 1u; if (COUNT) ntris++;
             v4f v0, e1, e2;
-            if (slot < sc.lds_tris) { const lds_v4f* t = L.tris + slot * 3u; v0 = t[0]; e1 = t[1]; e2 = t[2]; }
-            else { const v4f* t = (const v4f*)(sc.tris + slot); v0 = t[0]; e1 = t[1]; e2 = t[2]; }
+            load_tri(sc, L, tri_slot8(T, bit), v0, e1, e2);
             float t, u, w;
             if (tri_test(o, d, v0, e1, e2, tmin, tmax, t, u, w)) {
-                if (ANY) { bprim = 0u; bu = (float)nsteps; bv = (float)ntris; return; }
+                if (ANY) { bprim = 0u; if (COUNT) { bu = (float)nsteps; bv = (float)ntris; } return; }
                 const uint32_t gid = f2u(v0.w);
-                if (t < bt || (t == bt && gid < bprim)) { bt = t; bu = u; bv = w; bprim = gid; }
+                if (closer(t, gid, bt, bprim)) { bt = t; bu = u; bv = w; bprim = gid; }
             }
         }
         if (!(G.bits & 0xffu)) {
@@ -328,7 +312,7 @@ __device__ __forceinline__ void traverse_stats(const DevScene& sc, const TraceLd
             sp--; G = stk.get(sp);
         }
     }
-    bu = (float)nsteps; bv = (float)ntris;
+    if (COUNT) { bu = (float)nsteps; bv = (float)ntris; }
 }
 
 // Tiny-scene path (sc.nsmall != 0, all triangles staged in LDS): no BVH.  Phase 1 runs a CONSERVATIVE plane-form
@@ -414,7 +398,7 @@ __device__ __forceinline__ void traverse_small(const DevScene& sc, const SmallRe
             if (tri_test(o, d, v0, e1, e2, tmin, tmax, t, u, w)) {
                 if (ANY) { bprim = 0u; return true; }
                 const uint32_t gid = f2u(v0.w);
-                if (t < bt || (t == bt && gid < bprim)) { bt = t; bu = u; bv = w; bprim = gid; }
+                if (closer(t, gid, bt, bprim)) { bt = t; bu = u; bv = w; bprim = gid; }
             }
         }
         return false;
@@ -543,13 +527,10 @@ __device__ __forceinline__ void pend_clear(RayLane& R) {
 }
 __device__ __forceinline__ void ray_begin(RayLane& R, f3 o, f3 d, float tmin, float tmax, uint32_t item, bool ordered, bool occluder_cache = false, uint32_t aord = 0u) {
     R.o = o; R.d = d; R.tmin = tmin; R.tmax = tmax; R.item = item;
-    const float dxs = fabsf(d.x) < 1e-30f ? copysignf(1e-30f, d.x) : d.x;
-    const float dys = fabsf(d.y) < 1e-30f ? copysignf(1e-30f, d.y) : d.y;
-    const float dzs = fabsf(d.z) < 1e-30f ? copysignf(1e-30f, d.z) : d.z;
-    R.idir = mk3(__builtin_amdgcn_rcpf(dxs), __builtin_amdgcn_rcpf(dys), __builtin_amdgcn_rcpf(dzs));
+    R.idir = safe_idir(d);
     R.oct = ray_octant(R.idir);
     R.bt = tmax; R.bu = 0.0f; R.bv = 0.0f; R.bprim = kMissPrim; R.sp = 0; R.has = true; R.done = false;
-    R.G = Grp{0u, (ordered ? (1u << R.oct) : (aord ? 1u << (R.oct ^ (aord == 2u ? 7u : 0u)) : 1u)) | (1u << 8)}; R.T = TriGrp{0u, 0u, 0u}; pend_clear(R);      // the root as slot 0 of a virtual parent
+    R.G = root_group(R.oct, ordered, aord); R.T = TriGrp{0u, 0u, 0u}; pend_clear(R);
     // OCCLUDER CACHE (any-hit rays).  A lane's consecutive rays come from neighbouring queue entries — shadow rays of neighbouring pixels towards the same light, or
     // visibility rays between neighbouring ReSTIR samples — and what blocked the last one often blocks the next.  So the lane's last occluder is handed to the new
     // ray as its first triangle group: it is tested by the first triangle step the wave takes, and a hit ends the ray before (most of) its traversal.  Any-hit is
@@ -584,16 +565,14 @@ template <bool ANY>
 __device__ __forceinline__ void tri_step(const DevScene& sc, const TraceLds& L, RayLane& R) {
     const uint32_t bit = (uint32_t)__builtin_ctz(R.T.bits);
     R.T.bits &= R.T.bits - 1u;
-    const uint32_t slot = tri_slot8(R.T, bit);
     v4f v0, e1, e2;
-    if (slot < sc.lds_tris) { const lds_v4f* t = L.tris + slot * 3u; v0 = t[0]; e1 = t[1]; e2 = t[2]; }
-    else { const v4f* t = (const v4f*)(sc.tris + slot); v0 = t[0]; e1 = t[1]; e2 = t[2]; }
+    load_tri(sc, L, tri_slot8(R.T, bit), v0, e1, e2);
     float t, u, w;
     if (tri_test(R.o, R.d, v0, e1, e2, R.tmin, R.tmax, t, u, w)) {
         if (ANY) { R.bprim = 0u; R.done = true; R.T.bits = 0u; }
         else {
             const uint32_t gid = f2u(v0.w);
-            if (t < R.bt || (t == R.bt && gid < R.bprim)) { R.bt = t; R.bu = u; R.bv = w; R.bprim = gid; }
+            if (closer(t, gid, R.bt, R.bprim)) { R.bt = t; R.bu = u; R.bv = w; R.bprim = gid; }
         }
     }
 }
@@ -607,12 +586,11 @@ __device__ __forceinline__ bool tri_candidate(const DevScene& sc, const TraceLds
     R.T.bits &= R.T.bits - 1u;
     const uint32_t slot = tri_slot8(R.T, bit);
     v4f v0, e1, e2;
-    if (slot < sc.lds_tris) { const lds_v4f* tp = L.tris + slot * 3u; v0 = tp[0]; e1 = tp[1]; e2 = tp[2]; }
-    else { const v4f* tp = (const v4f*)(sc.tris + slot); v0 = tp[0]; e1 = tp[1]; e2 = tp[2]; }
+    load_tri(sc, L, slot, v0, e1, e2);
     const bool hit = tri_test_flat(R.o, R.d, v0, e1, e2, R.tmin, R.tmax, t, u, w);
     gid = ANY ? slot : f2u(v0.w);                      // any-hit: the occluder's slot (occluder cache); closest hit: the global triangle id
     if (ANY) return hit;
-    return hit & ((t < R.bt) | ((t == R.bt) & (gid < R.bprim)));
+    return hit & ((t < R.bt) | ((t == R.bt) & (gid < R.bprim)));      // closer(), the definition of the tie rule, in the branch-free form this step needs (see above)
 }
 template <bool ANY, class STK>
 __device__ __forceinline__ void process_leaf(const DevScene& sc, const TraceLds& L, RayLane& R, STK& stk) {

@@ -1078,6 +1078,22 @@ def test_trace_counters_report_work_per_ray_and_change_nothing(rt):
     c.close()
 
 
+def test_counting_traversal_changes_nothing_but_the_counters(rt):
+    """The statistics traversal (rtx_debug_trace_stats) is the plain closest-hit traversal with two counters: t and the primitive are the same bits as rtx_debug_trace_closest's,
+    and a ray that reports a hit took at least one node step and one triangle test.  A tree of a few hundred wide nodes: rays pop the stack, and triangles come from the
+    staged copy as well as from global memory."""
+    sc = rt.Scene.sponza_class(40000, 260)
+    W, H = 160, 90
+    c = rt.Context(0); c.upload(sc, W / H)
+    rays = np.concatenate([c.primary_rays(rt.Params(width=W, height=H)), random_rays(4096, 5, -1.5, 1.5)])
+    st, hit = c.trace_stats(rays), c.trace_closest(rays)
+    c.close()
+    assert np.array_equal(bits(st)[:, 0], bits(hit)[:, 0]) and np.array_equal(bits(st)[:, 3], bits(hit)[:, 3])
+    found = bits(hit)[:, 3] != 0xFFFFFFFF
+    assert found.sum() > 1000                                                      # (the camera is inside the atrium)
+    assert (st[found, 1] >= 1).all() and (st[found, 2] >= 1).all()
+
+
 @pytest.mark.parametrize("lanes", [1, 2, 3, 4])
 def test_restir_pipeline_lanes_equal_the_literal_form(rt, orc, golden_dir, lanes):
     """RTX_OPT_RESTIR_LANES: the pixel list of a ReSTIR frame as 1 .. 4 independent parts on as many streams (passes 1 + 2, join, pass 3).  The lanes only engage for lists
