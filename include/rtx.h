@@ -229,6 +229,51 @@ int  rtx_set_instance_visible(rtx_ctx*, uint32_t inst, int visible);
    RTX_ERR_INVALID (unknown mesh, other vertex count, changed normal.w, null pointer) leaves the scene untouched and committed.  The ReSTIR history is
    left alone (the temporal pass reprojects through prevObjectToWorld only): call rtx_restir_reset for a frame without ghosting. */
 int  rtx_update_mesh_vertices(rtx_ctx*, uint32_t mesh, const void* verts28, uint32_t nverts);
+/* DIFFUSE TEXTURE MAPS (new; the reference parses map_Kd and samples nothing: an extension, unpinned by definition like strategy 3 and pinned by its own properties
+   in tests/test_texture.py).  rtx_render and rtx_render_adaptive only; rtx_render_v6_pass1 and rtx_render_restir ignore maps, as they ignore RTX_FLAG_TRANSMISSION.
+   DATA.  Per mesh an optional array of one (u, v) float pair per INDEX entry, parallel to `indices` and `material_ids`: per corner, not per vertex (the 28-byte Vertex
+   stays as it is); a mesh without the array has (0, 0) at every corner.  Per context a table of textures, each width x height RGBA8 (r in the first byte), row 0 on
+   top, alpha ignored, 1 <= width, height <= 16384 (and at most 2^31 texels in the whole table); RTX_TEX_SRGB says the bytes are sRGB-encoded.  Per material the
+   slot RTX_MAP_KD: a texture id or -1.
+   BYTE -> FLOAT.  A 256-entry float32 table per encoding, filled on the host.  Linear: T[b] = (float)b / 255.0f.  sRGB, in double: c = b / 255.0;
+   c <= 0.04045 ? c / 12.92 : pow((c + 0.055) / 1.055, 2.4); rounded to float32 once.
+   Sample(tex, s, t), float32 in exactly this order, no contraction, W x H the texture's size:
+       fs = s - floorf(s);  ft = t - floorf(t)                                            (repeat wrap)
+       x  = fs * (float)W - 0.5f;  y = (1.0f - ft) * (float)H - 0.5f                      (OBJ's v runs upward)
+       x0 = floorf(x);  y0 = floorf(y);  fx = x - x0;  fy = y - y0
+       ix0 = wrap((int)x0, W);  ix1 = wrap((int)x0 + 1, W);  iy0, iy1 likewise;  wrap(i, n) = ((i % n) + n) % n
+       per channel k = r, g, b, with cab = T[texel(ixa, iyb).k]:
+       top = c00 + fx * (c10 - c00);  bot = c01 + fx * (c11 - c01);  c = top + fy * (bot - top)
+   There are NO MIP LEVELS: a path tracer integrates the pixel footprint by sampling, and every sample reads the full-resolution image.
+   PER HIT on a surface whose material m has RTX_MAP_KD = tex >= 0, with (u, v) the hit record's barycentrics and uv0, uv1, uv2 the triangle's corner pairs:
+       b0 = 1.0f - u - v
+       s  = (b0 * uv0.x + u * uv1.x) + v * uv2.x ;  t likewise with .y
+       tl = Sample(tex, s, t)
+       Kd'[k]   = half_round(m.Kd[k] * tl[k])                                             (binary16 round trip, the MaterialOptimized rounding of the table's Kd)
+       KdPi'[k] = Kd'[k] / PI                                                             (IEEE division, as for the table)
+   KdPi' replaces the material's Kd / PI wherever the shading reads the diffuse colour at that hit: the Lambert term of the mixture BSDF, for the NEE samples and for the
+   continuation.  Everything else stays the material's: Ks, Ke, Pr, Pm, dissolve, the light list, the strategy probabilities, the random-number sequence.  An emissive
+   material's map has no effect (emitters are not shaded).  CONSEQUENCE: a scene in which every textured triangle sees one value tl is, bit for bit, the untextured scene
+   whose triangles carry materials with Kd = Kd'.  rtx_denoise is unchanged (its colour edge-stop now sees texture detail); debug layer 13 shows Kd'.
+   CALLS.  rtx_set_mesh_uvs: nidx pairs, nidx = the mesh's index count; NULL clears.  rtx_set_texture: tex <= the current count, == count appends; the texels are copied.
+   rtx_set_material_map: slot RTX_MAP_KD, tex -1 = none.  RTX_ERR_INVALID — unknown mesh, material, texture or slot; nidx other than the mesh's; a non-finite UV; a size
+   outside the limits; unknown flag bits; a NULL pixel pointer — leaves the scene untouched and committed.  rtx_set_materials resets every map to -1 (the table is
+   replaced).  Like rtx_set_instance_visible the three are valid before the first commit and on a resident scene, and need rtx_commit_scene again (rendering in between is
+   RTX_ERR_STATE).  On a resident general scene a commit after these calls alone uploads tables only: no rebuild, no refit, rtx_stats.bvh_refits and rtx_debug_tree_hash
+   unchanged; it may share a commit with transform, visibility and vertex edits.  rtx_update_mesh_vertices keeps a mesh's UVs; geometry-changing commits and
+   RTX_OPT_GPU_BUILD keep everything (global triangle ids do not depend on the tree).  rtx_save_scene_cache while any material has a map is RTX_ERR_STATE (the file holds
+   no texels); a loaded cache has no maps and no textures.  A tiny scene (<= 64 triangles) runs on the general BVH path while a material that a triangle uses has a map;
+   the commit that crosses that line, either way, is a rebuild.  With such a map active rtx_render runs the default separate kernels whatever RTX_OPT_FUSED_BVH,
+   RTX_OPT_SHADE_DENSE and RTX_OPT_SORT_MATERIALS say (measured-and-rejected variants get no textured copy); RTX_OPT_COMPACT_STATE 0 and 1 both work. */
+#define RTX_TEX_SRGB 1u
+enum { RTX_MAP_KD = 0 };
+int  rtx_set_mesh_uvs(rtx_ctx*, uint32_t mesh, const float* uv2 /* nidx pairs; NULL clears */, uint32_t nidx);
+int  rtx_set_texture(rtx_ctx*, uint32_t tex /* <= current count; == count appends */, const void* rgba8, uint32_t width, uint32_t height, uint32_t flags);
+int  rtx_set_material_map(rtx_ctx*, uint32_t material, uint32_t slot, int32_t tex /* -1 = none */);
+/* tests: the device's sampler — n (s, t) pairs -> (r, g, b, 0) — and the device's per-hit albedo — hits4 as rtx_debug_trace_closest writes them -> (Kd' (m.Kd where the
+   material has no map), texture id as uint bits or 0xFFFFFFFF); a miss gives (0, 0, 0, 0xFFFFFFFF).  rays8 may be NULL: the albedo depends on the hit record alone */
+int  rtx_debug_texture_sample(rtx_ctx*, uint32_t tex, const float* uv2, uint32_t n, float* out4);
+int  rtx_debug_albedo(rtx_ctx*, const float* rays8, const float* hits4, uint32_t n, float* out4);
 /* CreateAccelerationStructures (Renderer.cpp:893-946) + CollectEmissiveTriangles (:2123-2213) +
    CreateEmissiveTrianglesBuffer (:2237-2280): BVH build, emissive CDF, upload */
 int  rtx_commit_scene(rtx_ctx*);

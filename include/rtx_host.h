@@ -38,13 +38,22 @@ const void* rtxh_scene_materials(const rtxh_scene*);                       /* 12
 /* SURVEY 8(f3) "full MTL PBR extension coverage": what tinyobj's material_t holds beyond the 128-byte Material (ObjLoader.h:428-435 copies
    Kd, d, Ks, Ke, Pr, Pm, Ps, Pc only; Vertex.h:21 "ADD MAP IDs LATER"): Ni, Ns, illum, Ka, Tf / Kt, Pcr, aniso, anisor and one texture id per map
    statement (-1 = none; ids index rtxh_scene_texture).  Only scenes loaded from OBJ / MTL files carry it (index-aligned with the
-   material table, default materials included); no kernel reads it — the reference's shaders sample no textures. */
+   material table, default materials included).  Of all of it the kernels read ONE thing: the diffuse map, map[RTXH_MAP_KD], once its image is decoded and bound
+   (rtx_set_material_map, include/rtx.h) — the reference's shaders sample no textures, this library's k_shade samples map_Kd; every other slot stays a name. */
 #define RTXH_NUM_MAP_SLOTS 13
 enum { RTXH_MAP_KA = 0, RTXH_MAP_KD, RTXH_MAP_KS, RTXH_MAP_KE, RTXH_MAP_NS, RTXH_MAP_BUMP, RTXH_MAP_D, RTXH_MAP_DISP, RTXH_MAP_REFL, RTXH_MAP_PR, RTXH_MAP_PM, RTXH_MAP_PS, RTXH_MAP_NORM };
 typedef struct rtxh_material_ext { float Ni, Ns, Pcr, aniso, anisor; int32_t illum; float Ka[3], Tf[3]; int32_t map[RTXH_NUM_MAP_SLOTS]; } rtxh_material_ext;
 int         rtxh_scene_material_ext(const rtxh_scene*, uint32_t material, rtxh_material_ext* out);   /* RTX_ERR_INVALID: no such record */
 uint32_t    rtxh_scene_num_textures(const rtxh_scene*);
 const char* rtxh_scene_texture(const rtxh_scene*, uint32_t i);                                      /* file name as written in the .mtl */
+/* the decoded image of texture i — top-down RGBA8, taken as sRGB — or NULL / 0 x 0 where the scene holds none: only the files a map_Kd names are read (binary PPM / PGM and
+   uncompressed or RLE 24- / 32-bit TGA: host/ImageIO.h), and a file that is missing or in another format is skipped with one line on stderr and the scene loads as
+   without it.  rtxh_scene_upload, the Renderer and the N-GPU frame bind the decoded ones (rtx_set_texture, rtx_set_material_map) to every context they upload to. */
+int         rtxh_scene_texture_pixels(const rtxh_scene*, uint32_t i, const void** rgba8, uint32_t* width, uint32_t* height);
+/* the per-corner texture coordinates of mesh i (the OBJ's vt): one (u, v) pair per index entry, parallel to rtxh_scene_mesh's indices; NULL / 0 for a mesh without any */
+int         rtxh_scene_mesh_uvs(const rtxh_scene*, uint32_t i, const float** uv2, uint32_t* nidx);
+/* the image readers alone: width / height always, the pixels when capacity holds width * height * 4 bytes; RTX_ERR_INVALID + rtxh_last_error for a file they cannot read */
+int         rtxh_read_image(const char* path, void* rgba8, uint64_t capacity, uint32_t* width, uint32_t* height);
 uint32_t    rtxh_scene_num_meshes(const rtxh_scene*);
 int         rtxh_scene_mesh(const rtxh_scene*, uint32_t i, const void** verts28, uint32_t* nverts,
                             const uint32_t** indices, uint32_t* nidx, const uint32_t** material_ids);

@@ -46,6 +46,8 @@ OPT_STACK_CAP = 39
 OPT_DEFORM_REBUILD = 40
 OPT_SHARED_PRIMARY = 41
 OPT_DENOISE_LDS_STEP = 42
+TEX_SRGB = 1          # rtx_set_texture flag: the bytes are sRGB-encoded
+MAP_KD = 0            # rtx_set_material_map slot
 
 
 class RtxError(RuntimeError):
@@ -105,6 +107,11 @@ _sig("rtx_set_instance_transform", C.c_int, _vp, _u32, _fp)
 _sig("rtx_set_instance_visible", C.c_int, _vp, _u32, C.c_int)
 _sig("rtx_update_mesh_vertices", C.c_int, _vp, _u32, _vp, _u32)
 _sig("rtx_commit_scene", C.c_int, _vp)
+_sig("rtx_set_mesh_uvs", C.c_int, _vp, _u32, _vp, _u32)
+_sig("rtx_set_texture", C.c_int, _vp, _u32, _vp, _u32, _u32, _u32)
+_sig("rtx_set_material_map", C.c_int, _vp, _u32, _u32, C.c_int32)
+_sig("rtx_debug_texture_sample", C.c_int, _vp, _u32, _vp, _u32, _vp)
+_sig("rtx_debug_albedo", C.c_int, _vp, _vp, _vp, _u32, _vp)
 _sig("rtx_set_camera", C.c_int, _vp, _fp, _fp)
 _sig("rtx_save_scene_cache", C.c_int, _vp, C.c_char_p)
 _sig("rtx_load_scene_cache", C.c_int, _vp, C.c_char_p)
@@ -201,6 +208,9 @@ MAP_SLOTS = ("Ka", "Kd", "Ks", "Ke", "Ns", "bump", "d", "disp", "refl", "Pr", "P
 _sig("rtxh_scene_material_ext", C.c_int, _vp, _u32, C.POINTER(MaterialExt))
 _sig("rtxh_scene_num_textures", _u32, _vp)
 _sig("rtxh_scene_texture", C.c_char_p, _vp, _u32)
+_sig("rtxh_scene_texture_pixels", C.c_int, _vp, _u32, C.POINTER(_vp), _u32p, _u32p)
+_sig("rtxh_scene_mesh_uvs", C.c_int, _vp, _u32, C.POINTER(_vp), _u32p)
+_sig("rtxh_read_image", C.c_int, C.c_char_p, _vp, C.c_uint64, _u32p, _u32p)
 _sig("rtxh_scene_num_meshes", _u32, _vp)
 _sig("rtxh_scene_mesh", C.c_int, _vp, _u32, C.POINTER(_vp), _u32p, C.POINTER(_vp), _u32p, C.POINTER(_vp))
 _sig("rtxh_scene_num_instances", _u32, _vp)
@@ -281,7 +291,14 @@ class Scene:
                 break
             self.material_ext.append(dict(Ni=x.Ni, Ns=x.Ns, Pcr=x.Pcr, aniso=x.aniso, anisor=x.anisor, illum=x.illum, Ka=list(x.Ka), Tf=list(x.Tf),
                                           maps={MAP_SLOTS[k]: self.textures[x.map[k]] for k in range(13) if x.map[k] >= 0}))
-        self.meshes = []
+        # what the host loaded for the diffuse maps (Context.upload binds it): per texture the decoded (H, W, 4) uint8 image or None; per material the texture id of its map_Kd or -1
+        self.texture_pixels = []
+        for i in range(len(self.textures)):
+            px, tw, th = _vp(), _u32(), _u32()
+            lib.rtxh_scene_texture_pixels(handle, i, C.byref(px), C.byref(tw), C.byref(th))
+            self.texture_pixels.append(np.array((C.c_uint8 * (tw.value * th.value * 4)).from_address(px.value), dtype=np.uint8).reshape(th.value, tw.value, 4) if px.value else None)
+        self.material_maps = [self.textures.index(e["maps"]["Kd"]) if "Kd" in e["maps"] else -1 for e in self.material_ext]
+        self.meshes, self.uvs = [], []
         for i in range(lib.rtxh_scene_num_meshes(handle)):
             v, idx, mid = _vp(), _vp(), _vp()
             nv, ni = _u32(), _u32()
@@ -290,6 +307,9 @@ class Scene:
             indices = np.array((C.c_uint32 * ni.value).from_address(idx.value), dtype=np.uint32) if ni.value else np.zeros(0, np.uint32)
             matids = np.array((C.c_uint32 * ni.value).from_address(mid.value), dtype=np.uint32) if ni.value else np.zeros(0, np.uint32)
             self.meshes.append((verts, indices, matids))
+            uv, nuv = _vp(), _u32()
+            lib.rtxh_scene_mesh_uvs(handle, i, C.byref(uv), C.byref(nuv))
+            self.uvs.append(np.array((C.c_float * (nuv.value * 2)).from_address(uv.value), dtype=np.float32).reshape(-1, 2) if uv.value else None)      # per corner (index entry), or None
         self.instances = []
         for i in range(lib.rtxh_scene_num_instances(handle)):
             mesh = _u32()
@@ -429,6 +449,16 @@ def half_round(x):
     return lib.rtxh_half_round(C.c_float(x))
 
 
+def read_image(path):
+    """the host layer's texture readers (binary PPM / PGM, uncompressed or RLE 24- / 32-bit TGA) -> (H, W, 4) uint8, row 0 on top"""
+    w, h = _u32(), _u32()
+    if lib.rtxh_read_image(str(path).encode(), None, 0, C.byref(w), C.byref(h)) != RTX_OK:
+        raise RtxError("read_image: " + lib.rtxh_last_error().decode())
+    out = np.zeros((h.value, w.value, 4), np.uint8)
+    lib.rtxh_read_image(str(path).encode(), _ptr(out), out.nbytes, C.byref(w), C.byref(h))
+    return out
+
+
 def bvh_refit_check(before, after):
     a, b = _f32(before).reshape(-1, 9), _f32(after).reshape(-1, 9)
     return lib.rtxh_bvh_refit_check(_ptr(a), _ptr(b), len(a))
@@ -556,6 +586,58 @@ class Context:
         v = _f32(verts).reshape(-1, 7)
         self._ck(lib.rtx_update_mesh_vertices(self._h, int(mesh), _ptr(v), len(v)), "rtx_update_mesh_vertices")
 
+    def set_mesh_uvs(self, mesh, uvs):
+        """per-corner texture coordinates of a mesh: (index count, 2) float32, one (u, v) per index entry; None clears (every corner then has (0, 0))"""
+        if uvs is None:
+            self._ck(lib.rtx_set_mesh_uvs(self._h, int(mesh), None, 0), "rtx_set_mesh_uvs")
+            return
+        a = _f32(uvs).reshape(-1, 2)
+        self._ck(lib.rtx_set_mesh_uvs(self._h, int(mesh), _ptr(a), len(a)), "rtx_set_mesh_uvs")
+
+    def set_texture(self, tex, rgba8, srgb=True):
+        """texture `tex` of the context's table (== the current count appends) := rgba8 (H, W, 4) uint8, row 0 on top, alpha ignored"""
+        a = np.ascontiguousarray(rgba8, dtype=np.uint8)
+        if a.ndim != 3 or a.shape[2] != 4:
+            raise RtxError("set_texture: pixels must be (H, W, 4) uint8")
+        self._ck(lib.rtx_set_texture(self._h, int(tex), _ptr(a), a.shape[1], a.shape[0], TEX_SRGB if srgb else 0), "rtx_set_texture")
+
+    def set_material_map(self, material, tex, slot=MAP_KD):
+        """the material's map in `slot` (MAP_KD) := texture id `tex`, -1 / None = none"""
+        self._ck(lib.rtx_set_material_map(self._h, int(material), int(slot), -1 if tex is None else int(tex)), "rtx_set_material_map")
+
+    def texture_sample(self, tex, uvs):
+        """the device's sampler at (n, 2) texture coordinates -> (n, 4) float32: r, g, b, 0"""
+        a = _f32(uvs).reshape(-1, 2)
+        out = np.zeros((len(a), 4), np.float32)
+        self._ck(lib.rtx_debug_texture_sample(self._h, int(tex), _ptr(a), len(a), _ptr(out)), "rtx_debug_texture_sample")
+        return out
+
+    def albedo(self, hits4, rays8=None):
+        """the device's per-hit diffuse colour at hit records (trace_closest) -> (n, 4) float32: Kd' (the material's Kd where it has no map), texture id bits or 0xFFFFFFFF"""
+        h = _f32(hits4).reshape(-1, 4)
+        r = _f32(rays8).reshape(-1, 8) if rays8 is not None else None
+        out = np.zeros((len(h), 4), np.float32)
+        self._ck(lib.rtx_debug_albedo(self._h, _ptr(r) if r is not None else None, _ptr(h), len(h), _ptr(out)), "rtx_debug_albedo")
+        return out
+
+    def bind_maps(self, scene):
+        """the optional texture attributes of a scene (duck-typed): `uvs` — per mesh an (index count, 2) array or None; `textures` — a list whose entries are (H, W, 4)
+        uint8 arrays or (array, srgb) pairs, anything else (a file name without pixels) is skipped; `material_maps` — per material an index into `textures` or -1 / None.
+        A map whose texture was skipped is not bound."""
+        for mesh, uv in enumerate(getattr(scene, "uvs", None) or []):
+            if uv is not None and len(uv):
+                self.set_mesh_uvs(mesh, uv)
+        ids = {}
+        texs = getattr(scene, "texture_pixels", None)            # (a host-loaded Scene keeps the file names in `textures` and the decoded images here)
+        for i, t in enumerate((getattr(scene, "textures", None) if texs is None else texs) or []):
+            px, srgb = t if isinstance(t, tuple) else (t, True)
+            if isinstance(px, np.ndarray) and px.ndim == 3:
+                ids[i] = len(ids)
+                self.set_texture(ids[i], px, srgb)
+        for mat, t in enumerate(getattr(scene, "material_maps", None) or []):
+            if t is not None and t >= 0 and t in ids:
+                self.set_material_map(mat, ids[t])
+
     def commit(self):
         self._ck(lib.rtx_commit_scene(self._h), "rtx_commit_scene")
 
@@ -581,6 +663,7 @@ class Context:
             self.add_mesh(v, i, m)
         for mesh, o2w in scene.instances:
             self.add_instance(mesh, o2w)
+        self.bind_maps(scene)
         self.commit()
         self.set_camera(*scene.view_proj(aspect))
 

@@ -152,10 +152,11 @@ RTX_HD uint32_t select_strategy(const MatGPU& m, f3 outgoing, f3 normal, uint32_
 }
 // F = p_d f_lambert + p_s f_ggx, P = p_d pdf_lambert + p_s pdf_ggx
 // (Sampler_v6.hlsl:443-457, Path_Sampler_v6.hlsl:66-80); with eta_p != 0 a direction on the far side of the interface gets p_t f_t, p_t pdf_t alone
-RTX_HD void bsdf_mixture(const MatGPU& m, uint32_t flags, f3 normal, f3 L, f3 outgoing, f3& F, float& P, float& pd, float& ps, float eta_p = 0.0f) {
+// kdpi (both forms): the diffuse colour / PI of THIS shading point where a texture map modulates it (k_shade<.., TEX>: tex_kdpi, rtx_texture.hpp); nullptr = the material's own
+RTX_HD void bsdf_mixture(const MatGPU& m, uint32_t flags, f3 normal, f3 L, f3 outgoing, f3& F, float& P, float& pd, float& ps, float eta_p = 0.0f, const f3* kdpi = nullptr) {
     float pt;
     strategy_probs(m, outgoing, normal, flags, pd, ps, eta_p, pt);
-    f3 f0 = lambert_eval(m); float q0 = lambert_pdf(normal, L);
+    f3 f0 = kdpi ? *kdpi : lambert_eval(m); float q0 = lambert_pdf(normal, L);
     if (flags & 1u) { F = safe_mul(pd, f0); P = safe_mul(pd, q0); return; }
     if (eta_p != 0.0f && dot(normal, L) < 0.0f) {
         float q3; f3 f3_ = btdf_eval(m, normal, L, outgoing, eta_p, q3);
@@ -203,8 +204,8 @@ RTX_HD void ggx_eval_pdf_v(const MatGPU& m, const MixView& mv, f3 Lin, f3& f1, f
     const f3 r = mk3(spec.x * (1.0f + Ks.x * mv.kms), spec.y * (1.0f + Ks.y * mv.kms), spec.z * (1.0f + Ks.z * mv.kms));
     f1 = finite3(r) ? r : mk3(0.0f, 0.0f, 0.0f);
 }
-RTX_HD void bsdf_mixture_v(const MatGPU& m, uint32_t flags, const MixView& mv, f3 normal, f3 L, f3 outgoing, f3& F, float& P, float eta_p = 0.0f) {
-    f3 f0 = lambert_eval(m); float q0 = lambert_pdf(normal, L);
+RTX_HD void bsdf_mixture_v(const MatGPU& m, uint32_t flags, const MixView& mv, f3 normal, f3 L, f3 outgoing, f3& F, float& P, float eta_p = 0.0f, const f3* kdpi = nullptr) {
+    f3 f0 = kdpi ? *kdpi : lambert_eval(m); float q0 = lambert_pdf(normal, L);
     if (flags & 1u) { F = safe_mul(mv.pd, f0); P = safe_mul(mv.pd, q0); return; }
     if (eta_p != 0.0f && dot(normal, L) < 0.0f) {
         float q3; f3 f3_ = btdf_eval(m, normal, L, outgoing, eta_p, q3);

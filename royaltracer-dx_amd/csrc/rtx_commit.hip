@@ -52,6 +52,44 @@ static int upload_built(rtx_ctx* c) {          // every device array of a freshl
 }
 static int finalise_scene(rtx_ctx* c);
 
+// byte -> float of a texel channel (include/rtx.h, rtx_set_texture): [0, 256) linear, [256, 512) sRGB decoded in double and rounded once
+static void fill_tex_lut(std::vector<float>& lut) {
+    lut.resize(512);
+    for (int b = 0; b < 256; b++) {
+        lut[b] = (float)b / 255.0f;
+        const double cs = b / 255.0;
+        lut[256 + b] = (float)(cs <= 0.04045 ? cs / 12.92 : pow((cs + 0.055) / 1.055, 2.4));
+    }
+}
+// The device's texture tables follow the host's (SceneHost::textures / map_kd / MeshHost::uvs): tables only, no kernel runs.  renumbered: this commit numbered the global
+// triangle ids anew (a build).  What the kernels see of it is set by finalise_scene.
+static int sync_textures(rtx_ctx* c, bool renumbered) {
+    SceneHost& H = c->host; rtx_ctx::Scene& S = c->scene;
+    const bool active = S.built.maps_active = H.maps_active();
+    int r;
+    if (H.tex_dirty) {                                       // (a scene that never saw one of the three setters allocates nothing here)
+        std::vector<TexDesc> desc(H.textures.size()); std::vector<uint32_t> pool;
+        for (size_t i = 0; i < H.textures.size(); i++) {
+            const TexHost& t = H.textures[i];
+            desc[i] = TexDesc{(uint32_t)pool.size(), t.width, t.height, t.flags};
+            pool.insert(pool.end(), t.rgba.begin(), t.rgba.end());
+        }
+        std::vector<int32_t> maps(H.mats128.size() / 32, -1);
+        for (size_t m = 0; m < maps.size() && m < H.map_kd.size(); m++) maps[m] = H.map_kd[m];
+        if ((r = upload(c, S.d_tex_desc, desc)) || (r = upload(c, S.d_texels, pool)) || (r = upload(c, S.d_map_kd, maps))) return r;
+        if (!S.d_tex_lut.p) { std::vector<float> lut; fill_tex_lut(lut); if ((r = upload(c, S.d_tex_lut, lut))) return r; }
+        S.ntex = (uint32_t)desc.size();
+    }
+    if (active && (H.tex_dirty || renumbered || !S.tri_uv_valid)) {
+        std::vector<float> uv; H.fill_tri_uv(uv);
+        if ((r = upload(c, S.d_tri_uv, uv))) return r;
+        S.tri_uv_valid = true;
+    }
+    if (!active && S.tri_uv_valid) { S.d_tri_uv.release(); S.tri_uv_valid = false; }       // (allocated only while a map is active)
+    H.tex_dirty = false;
+    return RTX_OK;
+}
+
 // a device array that only grows at its end: capacity in steps of 1.5 x, the `used` bytes survive a reallocation
 static int grow_keep(rtx_ctx* c, DevBuf& b, size_t used, size_t need) {
     if (need <= b.bytes && b.p) return RTX_OK;
@@ -337,14 +375,19 @@ int rtx_commit_scene(rtx_ctx* c) {
     c->scene.committed_once = true;
     int r;
     // On the GPU: a scene that is already resident and not a tiny one (whose pre-test records depend on world positions).
+    // a tiny scene leaves its pre-test records for the general path while a texture map is active and returns to them afterwards: the commit that crosses that line rebuilds
+    {   size_t ntri_all = 0; for (const InstHost& in : c->host.insts) ntri_all += c->host.meshes[in.mesh].idx.size() / 3;
+        if (c->host.tex_dirty && ntri_all <= kSmallSceneMaxTris && c->host.maps_active() != c->scene.built.maps_active) c->host.topo_dirty = true; }
     bool build = !(c->opt.gpu_refit && gpu_refittable(c) && !c->host.topo_dirty);
     // a tiny scene whose last instance was just shown again returns to its pre-test records: a host refit (SceneHost::build derives them from world positions)
     const BuiltScene& B0 = c->scene.built;
     if (!build && !c->scene.dev_built && !B0.leaf_order.empty() && B0.leaf_order.size() <= kSmallSceneMaxTris && B0.any_hidden && !c->host.any_hidden()) build = true;
     bool flipped = false;                                  // a resident scene's visibility differs from the caller's
     for (size_t ii = 0; ii < c->host.insts.size() && !flipped; ii++) flipped = (ii < B0.inst_hidden.size() && B0.inst_hidden[ii] != 0u) != c->host.is_hidden(ii);
-    const bool probe = build || !flipped;                  // the any-hit order is a property of the tree and the lights' whereabouts: not re-probed because something was hidden or shown
-    if (!build) {
+    // only UVs, textures or map ids changed on a resident general scene: tables are uploaded, nothing is refitted (rtx_stats.bvh_refits and the tree stay)
+    const bool tex_only = !build && c->host.tex_dirty && c->host.only_maps_changed(B0);
+    const bool probe = (build || !flipped) && !tex_only;   // the any-hit order is a property of the tree and the lights' whereabouts: not re-probed because something was hidden or shown
+    if (!build && !tex_only) {
         if ((r = refit_resident(c, deform))) return r;
         c->scene.cost_now_state = 0;
         if (deform && c->opt.deform_rebuild >= 2) {
@@ -358,6 +401,7 @@ int rtx_commit_scene(rtx_ctx* c) {
         if ((r = build_and_upload(c))) return r;
     }
     c->host.dirty_meshes.clear();
+    if ((r = sync_textures(c, build))) return r;
     r = finalise_scene(c);
     if (r == RTX_OK && c->scene.dev_built && c->scene.n_nodes8 && probe) {          // the visiting order of any-hit rays, probed on the device (the host probe replays its mirror of the tree)
         uint32_t best = 0;
@@ -375,6 +419,7 @@ int rtx_save_scene_cache(rtx_ctx* c, const char* path) {
     if (!c->committed) { c->err = "save_scene_cache: scene not committed"; return RTX_ERR_STATE; }
     if (c->scene.host_mirror_stale) { c->err = "save_scene_cache: the per-triangle records were re-derived on the GPU after rtx_update_mesh_vertices and the host holds no current copy; commit with RTX_OPT_DEFORM_REBUILD 1 (host builder) to save a cache"; return RTX_ERR_STATE; }
     if (c->scene.built.any_hidden) { c->err = "save_scene_cache: an instance is hidden (rtx_set_instance_visible): the device's boxes and triangle records leave it out and the file format holds no visibility; show every instance and commit to save a cache"; return RTX_ERR_STATE; }
+    if (c->host.any_map()) { c->err = "save_scene_cache: a material has a texture map (rtx_set_material_map) and the file format holds no texels; unmap every material and commit to save a cache"; return RTX_ERR_STATE; }
     if (c->scene.dev_built) { c->err = "save_scene_cache: the tree was built on the GPU (RTX_OPT_GPU_BUILD) and has no host mirror; commit with the host builder to save a cache"; return RTX_ERR_STATE; }
     if (!save_scene_cache(c->host, c->scene.built, path, c->err)) return RTX_ERR_INVALID;
     return RTX_OK;
@@ -387,6 +432,8 @@ int rtx_load_scene_cache(rtx_ctx* c, const char* path) {
     c->scene.pool_meshes = 0; c->scene.pool_verts = c->scene.pool_idx = c->scene.pool_matids = 0; c->scene.pool_vert_base.clear(); c->scene.pool_idx_base.clear(); c->scene.pool_dirty.clear();     // (another scene)
     int r = upload_built(c);
     if (r) return r;
+    c->host.tex_dirty = true;                  // (another scene: no textures, no maps)
+    if ((r = sync_textures(c, true))) return r;
     return finalise_scene(c);
 }
 
@@ -417,6 +464,9 @@ static int finalise_scene(rtx_ctx* c) {
     s.insts = (const InstGPU*)c->scene.d_insts.p; s.ninst = (uint32_t)B.insts.size();
     s.lights = (const LightGPU*)c->scene.d_lights.p; s.nlights = (uint32_t)B.lights.size(); s.cdf = (const float*)c->scene.d_cdf.p;
     s.total_weight = B.total_weight;
+    // texture maps: the sampler's tables whenever there are textures; UVs and map ids only while a map is active (then k_shade<.., TEX> runs, rtx_render.hip)
+    s.tex_desc = (const TexDesc*)c->scene.d_tex_desc.p; s.ntex = c->scene.ntex; s.texels = (const uint32_t*)c->scene.d_texels.p; s.tex_lut = (const float*)c->scene.d_tex_lut.p;
+    s.tri_uv = B.maps_active ? (const float*)c->scene.d_tri_uv.p : nullptr; s.map_kd = B.maps_active ? (const int32_t*)c->scene.d_map_kd.p : nullptr;
     // LDS budget per workgroup: stack + top of tree + first triangles, kept <= 64 KiB
     // exact bound of the 8-wide tree, no slack: a level adds ONE entry (the rest of its hit siblings) and only where a node has >= 2 internal
     // children (collapse_bvh8: need[]); a pop precedes every descent from an exhausted group.  Each entry costs 1.5 KB of LDS per workgroup (6 B per lane: kStackEntryBytes), and

@@ -5,6 +5,7 @@
 //   rtx_render.hip       rtx_render (the wavefront path tracer), render_frame and finish_render
 //   rtx_adaptive.hip     rtx_render_adaptive: passes of render_frame over the chunks that have not converged
 //   rtx_denoise.hip      rtx_denoise and the reads of the denoised image
+//   rtx_texture.hip      texture maps: rtx_set_mesh_uvs, rtx_set_texture, rtx_set_material_map and their two debug probes
 //   rtx_restir_api.hip   the ReSTIR frames, their work lists and lanes, the history / halo exchange between shards
 //   rtx_debug.hip        the rtx_debug_* entry points
 // Ownership: every resource of a context is a member of an owning type (rtx_devmem.hpp, rtx_staging.hpp), so `delete c` releases it all.
@@ -118,6 +119,9 @@ struct rtx_ctx {
         DevBuf d_nodes_wide; bool wide_nodes = false;    // the copy with one node per 128-B line (RTX_OPT_NODE_STRIDE)
         uint32_t lds_nodes_closest = 0;                  // staged nodes of the closest-hit launches (pick_lds_closest)
         DevBuf d_stack_ovf;                              // the traversal stack's overflow columns of deeper trees (RTX_OPT_STACK_CAP)
+        // diffuse texture maps (sync_textures, rtx_commit.hip): descriptors, the texel pool and the per-material map ids follow the host's tables at every commit that
+        // changed them; the two byte -> float tables once; tri_uv only while a map is active (BuiltScene::maps_active), rebuilt when UVs or the triangle numbering changed
+        DevBuf d_tri_uv, d_map_kd, d_tex_desc, d_texels, d_tex_lut; bool tri_uv_valid = false; uint32_t ntex = 0;
     } scene;
 
     // ---- the path tracer's frame (rtx_render.hip) ----

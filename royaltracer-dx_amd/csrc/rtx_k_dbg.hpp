@@ -62,6 +62,27 @@ __global__ __launch_bounds__(kBlock) void k_dbg_bsdf_sample(DevScene sc, uint32_
     const f3 wi = sample_bsdf(sc.mats[mat], st, wo, nrm, s0, s1, eta_p);
     o[0] = wi.x; o[1] = wi.y; o[2] = wi.z; o[3] = u2f(st); o[4] = u2f(s0); o[5] = u2f(s1); o[6] = 0.0f; o[7] = 0.0f;
 }
+// the sampler and the per-hit albedo of the texture maps (rtx_texture.hpp), as k_shade<.., TEX> and debug layer 13 run them
+__global__ __launch_bounds__(kBlock) void k_dbg_tex_sample(DevScene sc, uint32_t tex, const float* __restrict__ uv2, uint32_t n, F4* __restrict__ out) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const f3 c = tex_sample(sc, tex, uv2[2 * (size_t)i], uv2[2 * (size_t)i + 1]);
+    out[i] = {c.x, c.y, c.z, 0.0f};
+}
+__global__ __launch_bounds__(kBlock) void k_dbg_albedo(DevScene sc, const F4* __restrict__ hits, uint32_t n, F4* __restrict__ out) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const F4 h = hits[i];
+    const uint32_t prim = f2u(h.w);
+    F4 r = {0.0f, 0.0f, 0.0f, u2f(0xFFFFFFFFu)};
+    const uint32_t mat = prim != kMissPrim ? sc.shade[prim].mat : kMissMat;
+    if (mat < sc.nmat) {
+        int32_t tex;
+        const f3 kd = tex_albedo(sc, sc.mats[mat], mat, prim, h.y, h.z, &tex);
+        r = {kd.x, kd.y, kd.z, u2f((uint32_t)tex)};
+    }
+    out[i] = r;
+}
 __global__ void k_dbg_tea(uint32_t s0, uint32_t s1, uint32_t n, float* __restrict__ out, uint32_t* __restrict__ seed_out) {
     if (threadIdx.x || blockIdx.x) return;
     for (uint32_t i = 0; i < n; i++) out[i] = tea_next(s0, s1);

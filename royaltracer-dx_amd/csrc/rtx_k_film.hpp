@@ -66,7 +66,7 @@ __global__ __launch_bounds__(kBlock) void k_srgb8(const F4* __restrict__ accum, 
 // Debug output layers (the reference's gOutput is a 30-layer texture array and 'C' cycles m_displayLevels = {0, 10..17, 20..28}: Renderer.h:298-299,
 // Renderer.cpp:690-698, 748-754; its live shaders only ever write layer 0, the others show whatever was left there).  Here layers 10-17 are
 // DEFINED: first-hit attributes of the pixel-corner primary ray (jitter-free, RayGen_v6_pass1.hlsl:80-95), one thread per pixel:
-//   10 shading normal n/2 + 1/2   11 depth t / (1 + t)   12 material id (hashed colour)   13 Kd (fp16-rounded, as shaded)
+//   10 shading normal n/2 + 1/2   11 depth t / (1 + t)   12 material id (hashed colour)   13 Kd (fp16-rounded, as shaded; Kd' where the material has a texture map)
 //   14 instance id (hashed colour)   15 barycentrics (1-u-v, u, v)   16 Ke / (1 + Ke)   17 (roughness, metallic, dissolve)
 // a miss is black; layers 20-28 stay black (never written by the reference either).  Linear values, quantised like layer 0's alpha: v * 255 + 0.5.
 __device__ __forceinline__ uint32_t hash_colour(uint32_t id) {
@@ -95,6 +95,7 @@ __device__ __forceinline__ void for_each_first_hit(const DevScene& sc, const Sma
         body(i, o, d, t, u, v, prim);
     }
 }
+template <bool TEX>      // TEX: a texture map is active, layer 13 shows Kd' (rtx_texture.hpp); scenes without one run the instantiation they always ran
 __global__ __launch_bounds__(kBlock) void k_debug_layer(DevScene sc, const SmallRecPair* __restrict__ small, uint32_t width, uint32_t height, const CameraGPU* __restrict__ cam, uint32_t layer, uint32_t* __restrict__ out) {
     for_each_first_hit(sc, small, width, height, cam, [&](uint32_t i, f3 o, f3 d, float t, float u, float v, uint32_t prim) {
         uint32_t px = 0xFF000000u;
@@ -106,7 +107,9 @@ __global__ __launch_bounds__(kBlock) void k_debug_layer(DevScene sc, const Small
             case 10u: px = pack_rgb8(sf.normal.x * 0.5f + 0.5f, sf.normal.y * 0.5f + 0.5f, sf.normal.z * 0.5f + 0.5f); break;
             case 11u: { const float z = t / (1.0f + t); px = pack_rgb8(z, z, z); break; }
             case 12u: px = hash_colour(sf.mat); break;
-            case 13u: px = hm ? pack_rgb8(m.Kd[0], m.Kd[1], m.Kd[2]) : px; break;
+            case 13u: if (TEX && hm) { const f3 kd = tex_albedo(sc, m, sf.mat, prim, u, v); px = pack_rgb8(kd.x, kd.y, kd.z); }      // (Kd' under a texture map)
+                      else px = hm ? pack_rgb8(m.Kd[0], m.Kd[1], m.Kd[2]) : px;
+                      break;
             case 14u: px = hash_colour(sf.inst + 0x51ED27u); break;
             case 15u: px = pack_rgb8(1.0f - u - v, u, v); break;
             case 16u: px = hm ? pack_rgb8(m.Ke[0] / (1.0f + m.Ke[0]), m.Ke[1] / (1.0f + m.Ke[1]), m.Ke[2] / (1.0f + m.Ke[2])) : px; break;

@@ -19,12 +19,15 @@ namespace rtx {
 // 33 of 64 lanes).  Hence RTX_OPT_SORT_MATERIALS defaults to 0.
 // One item of k_shade / k_shade_dense: entry `qi` of the workgroup's sub-queue (valid = the lane has one).  Every lane of the wave goes through the compactions.
 // (Phase 2 of k_bounce_bvh is a copy of this body without the compact state, the sort keys and MixView — calling it there measured slower: change the two together.)
-template <bool LAMBERT>
+// TEX: some material has a diffuse texture map (rtx_texture.hpp): Kd' / PI of the hit is formed once, after surface(), and handed to the mixture of the NEE samples and of the
+// continuation — three floats live across them, no per-lane copy of the material.  Lanes whose material has no map keep its KdPi.
+template <bool LAMBERT, bool TEX = false>
 __device__ __forceinline__ void shade_item(const DevScene& sc, const DevFrame& f, const DevPaths& p, uint32_t bounce, uint32_t nee, bool last, size_t qb,
                                            const uint32_t* __restrict__ myq, uint32_t* __restrict__ mynext, uint32_t* s_cnt, bool valid, uint32_t qi, Prof* pf, const float* lds_cdf = nullptr, const LightGPU* lds_lights = nullptr, const MatGPU* lds_mats = nullptr) {
     PathState S; S.pid = 0; S.o = mk3(0, 0, 0); S.d = mk3(0, 0, 1); S.thr = mk3(0, 0, 0); S.prev_pdf = 1.0f; S.s0 = S.s1 = 0;
     Surf sf; sf.mat = 0; sf.normal = mk3(0, 0, 1); sf.pos = mk3(0, 0, 0);
     bool shading = false;
+    f3 kdv = mk3(0, 0, 0); const f3* kdpi = TEX ? &kdv : nullptr;
 #ifndef RTX_NO_LDS_MATS
     const MatGPU* mats = lds_mats ? lds_mats : sc.mats;      // (uniform; k_shade stages a short material table beside the light list)
 #else
@@ -43,7 +46,7 @@ __device__ __forceinline__ void shade_item(const DevScene& sc, const DevFrame& f
             if (sf.mat < sc.nmat) {
                 const MatGPU& m = mats[sf.mat];
                 if (m.Ke_len > 0.0f) add_emissive(sc, p, S, sf, m, bounce, nee);   // Hit.hlsl:126, Sampler_v6.hlsl:457
-                else shading = true;
+                else { shading = true; if (TEX) kdv = tex_kdpi(sc, m, sf.mat, prim, h.y, h.z); }
             }
         }
     }
@@ -61,7 +64,7 @@ __device__ __forceinline__ void shade_item(const DevScene& sc, const DevFrame& f
         bool push = false;
         F4 so = {0, 0, 0, 0}, sd = {0, 0, 0, 0}; f3 con = mk3(0, 0, 0);
         if (shading) { PF_COUNT(3); }
-        if (shading) push = nee_sample(sc, *mp, f.flags, nee, S, pos, normal, outgoing, so, sd, con, sc.nsmall != 0u && sf.near_hull, eta_p, mv, lds_cdf, lds_lights);
+        if (shading) push = nee_sample(sc, *mp, f.flags, nee, S, pos, normal, outgoing, so, sd, con, sc.nsmall != 0u && sf.near_hull, eta_p, mv, lds_cdf, lds_lights, kdpi);
         PF_MARK(3);
         if (push) { PF_COUNT(4); }
         const size_t seg = (size_t)j * f.qcap * gridDim.x + qb;           // NEE slot j, this workgroup's sub-queue
@@ -72,7 +75,7 @@ __device__ __forceinline__ void shade_item(const DevScene& sc, const DevFrame& f
     bool alive = false;
     f3 smp = mk3(0, 0, 1); float P = 0.0f;
     if (shading && !last) { PF_COUNT(5); }
-    if (shading && !last) alive = bsdf_continue(*mp, f, bounce, S, normal, outgoing, smp, P, eta_p, mv);
+    if (shading && !last) alive = bsdf_continue(*mp, f, bounce, S, normal, outgoing, smp, P, eta_p, mv, kdpi);
     PF_MARK(5);
     if (alive) { PF_COUNT(6); }
     const uint32_t slot = block_push(alive, &s_cnt[0]);
@@ -118,7 +121,7 @@ __host__ __device__ inline void shade_lds_plan(uint32_t nlights, uint32_t nmat, 
 #define RTX_SHADE_WAVES 7          // waves per SIMD k_shade is compiled for: 7 = 72 VGPRs + 1 spilled (GGX) / 66 (Lambert); uncapped: 94 VGPRs, 5 waves; 6: 80, no spills; 8: 64, 9 spilled.
                                    // k_shade per frame, C3 / C5: 7.42 / 8.77 ms uncapped, 6.93 / 8.54 at 6, 7.50 / 8.83 at 8 (round 2); round 4: 6.27 / 6.85 at 6, 6.28 / 6.72 at 7
 #endif
-template <bool SORT, bool LAMBERT>     // LAMBERT: RTX_FLAG_LAMBERT_ONLY as a compile-time constant (no GGX / transmission code in that instantiation)
+template <bool SORT, bool LAMBERT, bool TEX = false>     // LAMBERT: RTX_FLAG_LAMBERT_ONLY as a compile-time constant (no GGX / transmission code in that instantiation); TEX: texture maps (shade_item)
 __global__ __launch_bounds__(kBlock, RTX_SHADE_WAVES) void k_shade(DevScene sc, DevFrame f_in, DevPaths p, uint32_t bounce,
                                                   const uint32_t* __restrict__ queue, const uint32_t* __restrict__ qcount,
                                                   uint32_t* __restrict__ next_queue, uint32_t* __restrict__ next_count,
@@ -181,7 +184,7 @@ __global__ __launch_bounds__(kBlock, RTX_SHADE_WAVES) void k_shade(DevScene sc, 
         }
         for (uint32_t base = threadIdx.x & ~63u; base < cn; base += kBlock) {
             const uint32_t i = base + (threadIdx.x & 63u);
-            shade_item<LAMBERT>(sc, f, p, bounce, nee, last, qb, myq, mynext, s_cnt, i < cn, cb + (SORT ? s_sorted[i] : i), pf, lds_cdf, lds_lights, lds_mats);
+            shade_item<LAMBERT, TEX>(sc, f, p, bounce, nee, last, qb, myq, mynext, s_cnt, i < cn, cb + (SORT ? s_sorted[i] : i), pf, lds_cdf, lds_lights, lds_mats);
         }
         if (SORT) __syncthreads();                              // the next chunk overwrites the LDS buffers
     }

@@ -169,6 +169,8 @@ void launch_shade(hipStream_t st, const DevScene& sc, const DevFrame& f, const D
     // material-sorted variant: measured slower (see k_shade), the permutation un-coalesces the per-path state streams
     dispatch_bool((f.flags & 1u) != 0u, [&](auto lam) {
         constexpr bool LL = decltype(lam)::value;
+        // a texture map is active: the default kernel's TEX form, whatever RTX_OPT_SHADE_DENSE / RTX_OPT_SORT_MATERIALS say (the rejected variants get no textured copy)
+        if (sc.tri_uv) { hipLaunchKernelGGL((k_shade<false, LL, true>), dim3(f.nblocks), dim3(kBlock), shade_lds_bytes(sc, false), st, sc, f, p, bounce, queue, qcount, next_queue, next_count, shcounts); return; }
         if (sc.shade_dense && !sc.sort_materials) hipLaunchKernelGGL((k_shade_dense<LL>), dim3(f.nblocks), dim3(kBlock), 0, st, sc, f, p, bounce, queue, qcount, next_queue, next_count, shcounts);
         else dispatch_bool(sc.sort_materials != 0u, [&](auto sort) {
             constexpr bool SS = decltype(sort)::value;
@@ -287,7 +289,7 @@ void launch_srgb8(hipStream_t st, const F4* accum, uint32_t npix, uint32_t* out)
     hipLaunchKernelGGL(k_srgb8, dim3((npix + kBlock - 1) / kBlock), dim3(kBlock), 0, st, accum, npix, out);
 }
 void launch_debug_layer(hipStream_t st, uint32_t max_blocks, const DevScene& sc, uint32_t width, uint32_t height, const CameraGPU* cam, uint32_t layer, uint32_t* out) {
-    hipLaunchKernelGGL(k_debug_layer, dim3(grid_for(width * height, max_blocks)), dim3(kBlock), trace_lds_bytes(sc), st, sc, sc.small, width, height, cam, layer, out);
+    dispatch_bool(sc.tri_uv != nullptr, [&](auto tex) { hipLaunchKernelGGL(k_debug_layer<decltype(tex)::value>, dim3(grid_for(width * height, max_blocks)), dim3(kBlock), trace_lds_bytes(sc), st, sc, sc.small, width, height, cam, layer, out); });
 }
 void launch_pack_tiles(hipStream_t st, uint32_t max_blocks, const DevFrame& f, const F4* accum, F4* slab) {
     hipLaunchKernelGGL(k_pack_tiles, dim3(grid_for(f.npl, max_blocks)), dim3(kBlock), 0, st, f, accum, slab);
@@ -306,6 +308,12 @@ void launch_dbg_bsdf_eval(hipStream_t st, const DevScene& sc, uint32_t mat, uint
 }
 void launch_dbg_bsdf_sample(hipStream_t st, const DevScene& sc, uint32_t mat, uint32_t flags, const float* in8, uint32_t n, float* out8) {
     hipLaunchKernelGGL(k_dbg_bsdf_sample, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, sc, mat, flags, in8, n, out8);
+}
+void launch_dbg_tex_sample(hipStream_t st, const DevScene& sc, uint32_t tex, const float* uv2, uint32_t n, F4* out) {
+    hipLaunchKernelGGL(k_dbg_tex_sample, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, sc, tex, uv2, n, out);
+}
+void launch_dbg_albedo(hipStream_t st, const DevScene& sc, const F4* hits, uint32_t n, F4* out) {
+    hipLaunchKernelGGL(k_dbg_albedo, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, sc, hits, n, out);
 }
 void launch_dbg_tea(hipStream_t st, uint32_t s0, uint32_t s1, uint32_t n, float* out, uint32_t* seed_out) {
     hipLaunchKernelGGL(k_dbg_tea, dim3(1), dim3(64), 0, st, s0, s1, n, out, seed_out);

@@ -33,6 +33,12 @@ struct DevScene {
     uint32_t any_order_occ;             // ... of the ReSTIR stages' visibility rays (k_trace_shadow<.., SINK 1>): 0 unless RTX_OPT_ANYHIT_ORDER forces an order
     unsigned long long* trace_cnt;      // RTX_OPT_TRACE_COUNTERS: [0] node steps, [1] triangle tests of closest-hit rays, [2], [3] of any-hit rays, summed by the generic traversal instantiations; nullptr = off
     uint32_t occluder_cache;            // any-hit rays: a lane tests the triangle that occluded its previous ray first (rtx_traverse.hpp: ray_begin)
+    // diffuse texture maps (rtx_texture.hpp).  tri_uv / map_kd are nullptr unless a material that some triangle uses has a map: such scenes launch what they always launched
+    const float* tri_uv;                // 6 floats per GLOBAL triangle id (indexed like `shade`): the (u, v) of its three corners
+    const int32_t* map_kd;              // per material: texture id of RTX_MAP_KD, or -1
+    const TexDesc* tex_desc; uint32_t ntex;
+    const uint32_t* texels;             // the texel pool, RGBA8 (r in the low byte)
+    const float* tex_lut;               // byte -> float: [0, 256) linear, [256, 512) sRGB
 };
 
 // one sample batch of one frame
@@ -233,6 +239,8 @@ void launch_dbg_trace(hipStream_t, const DevScene&, const F4* rays, uint32_t n, 
 void launch_dbg_surface(hipStream_t, const DevScene&, const F4* rays, const F4* hits, uint32_t n, F4* out);
 void launch_dbg_bsdf_eval(hipStream_t, const DevScene&, uint32_t mat, uint32_t flags, const float* in9, uint32_t n, float* out8);
 void launch_dbg_bsdf_sample(hipStream_t, const DevScene&, uint32_t mat, uint32_t flags, const float* in8, uint32_t n, float* out8);
+void launch_dbg_tex_sample(hipStream_t, const DevScene&, uint32_t tex, const float* uv2, uint32_t n, F4* out);      // tex_sample at n (s, t) pairs -> (r, g, b, 0)
+void launch_dbg_albedo(hipStream_t, const DevScene&, const F4* hits, uint32_t n, F4* out);                         // tex_albedo at n hit records -> (Kd', texture id bits or 0xFFFFFFFF)
 void launch_dbg_tea(hipStream_t, uint32_t s0, uint32_t s1, uint32_t n, float* out, uint32_t* seed_out);
 void launch_dbg_primary(hipStream_t, const DevFrame&, const CameraGPU* cam, uint32_t sample_id, F4* rays);
 

@@ -179,7 +179,8 @@ int render_frame(rtx_ctx* c, const rtx_params* p, const DevFrame& f_real, uint32
     // ---- 2. plan the batches ----
     const uint32_t nee = c->dsc.nlights ? p->nee_samples : 0;
     const bool tiny_fused = c->dsc.nsmall && c->opt.fused;
-    const bool fused_bvh = !c->dsc.nsmall && c->opt.fused_bvh && c->opt.trace_sched >= 5u;      // (the other wave schedules are experiment knobs of the separate kernels)
+    // (the other wave schedules are experiment knobs of the separate kernels; with a texture map active the separate kernels run whatever the option says: k_bounce_bvh samples no image)
+    const bool fused_bvh = !c->dsc.nsmall && c->opt.fused_bvh && c->opt.trace_sched >= 5u && !c->dsc.tri_uv;
     const BatchPlan B = plan_batches(c, spp, f, fused_bvh);
     const uint32_t bspp = B.bspp, G = B.G;
     const uint64_t cap64 = (uint64_t)f.npl * bspp;

@@ -14,16 +14,7 @@ namespace rtx {
 // the only deviations: a miss ends the estimator at that point, frame_seed / sample id are explicit.
 // Statement order = oracle/rt_oracle.c:orc_render_v6_pass1.
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ float half_round_dev(float x) {          // float -> binary16 (RNE) -> float
-    const uint32_t u = f2u(x), sign = u & 0x80000000u, a = u & 0x7FFFFFFFu;
-    if (a >= 0x7F800000u) return x;
-    if (a >= 0x477FF000u) return u2f(sign | 0x7F800000u);
-    if (a < 0x33000001u) return u2f(sign);
-    if (a < 0x38800000u) { const float r = rintf(u2f(a) * 16777216.0f); return u2f(sign | f2u(r * (1.0f / 16777216.0f))); }
-    const uint32_t rem = a & 0x1FFFu; uint32_t base = a & ~0x1FFFu;
-    if (rem > 0x1000u || (rem == 0x1000u && (base & 0x2000u))) base += 0x2000u;
-    return u2f(sign | base);
-}
+// (half_round_dev: rtx_texture.hpp)
 __device__ __forceinline__ uint32_t half_bits_dev(float x) {
     const float r = half_round_dev(x);
     const uint32_t u = f2u(r), sign = (u >> 16) & 0x8000u, a = u & 0x7FFFFFFFu;

@@ -70,6 +70,8 @@ bool SceneHost::set_materials(const void* mats, uint32_t count) {
     if (!mats && count) { err = "materials pointer is null"; return false; }
     mats128.assign((const float*)mats, (const float*)mats + (size_t)count * 32);
     mats_dirty = true;
+    if (any_map()) tex_dirty = true;
+    map_kd.clear();                             // the table is replaced: no material of the new one has a map
     return true;
 }
 
@@ -131,6 +133,62 @@ bool SceneHost::update_mesh_vertices(uint32_t mesh, const void* verts28, uint32_
     m.verts.assign(v, v + (size_t)nverts * 7);
     if (!mesh_is_dirty(mesh)) dirty_meshes.push_back(mesh);
     return true;
+}
+
+bool SceneHost::set_mesh_uvs(uint32_t mesh, const float* uv2, uint32_t nidx) {
+    if (mesh >= meshes.size()) { err = "set_mesh_uvs: unknown mesh"; return false; }
+    MeshHost& m = meshes[mesh];
+    if (!uv2) { if (!m.uvs.empty()) { m.uvs.clear(); tex_dirty = true; } return true; }
+    if (nidx != m.idx.size()) { err = "set_mesh_uvs: one (u, v) pair per index entry of the mesh"; return false; }
+    for (size_t i = 0; i < (size_t)nidx * 2; i++) if (!std::isfinite(uv2[i])) { err = "set_mesh_uvs: non-finite coordinate"; return false; }
+    m.uvs.assign(uv2, uv2 + (size_t)nidx * 2);
+    tex_dirty = true;
+    return true;
+}
+bool SceneHost::set_texture(uint32_t tex, const void* rgba8, uint32_t width, uint32_t height, uint32_t flags) {
+    if (tex > textures.size()) { err = "set_texture: texture id beyond the end of the table (the current count appends)"; return false; }
+    if (!rgba8) { err = "set_texture: null pixel pointer"; return false; }
+    if (width < 1 || width > 16384 || height < 1 || height > 16384) { err = "set_texture: width and height must be in [1, 16384]"; return false; }
+    if (flags & ~1u) { err = "set_texture: unknown flag bits"; return false; }
+    uint64_t total = (uint64_t)width * height;
+    for (size_t i = 0; i < textures.size(); i++) if (i != tex) total += textures[i].rgba.size();
+    if (total > 0x7FFFFFFFull) { err = "set_texture: more than 2^31 texels in the table"; return false; }
+    if (tex == textures.size()) textures.emplace_back();
+    TexHost& t = textures[tex];
+    t.width = width; t.height = height; t.flags = flags;
+    t.rgba.assign((const uint32_t*)rgba8, (const uint32_t*)rgba8 + (size_t)width * height);
+    tex_dirty = true;
+    return true;
+}
+bool SceneHost::set_material_map(uint32_t material, uint32_t slot, int32_t tex) {
+    if (material >= mats128.size() / 32) { err = "set_material_map: unknown material"; return false; }
+    if (slot != 0u) { err = "set_material_map: unknown slot (RTX_MAP_KD is the only one)"; return false; }
+    if (tex < -1 || (tex >= 0 && (size_t)tex >= textures.size())) { err = "set_material_map: unknown texture"; return false; }
+    if (map_kd.size() < mats128.size() / 32) map_kd.resize(mats128.size() / 32, -1);
+    map_kd[material] = tex;
+    tex_dirty = true;
+    return true;
+}
+bool SceneHost::maps_active() const {
+    if (!any_map()) return false;
+    for (size_t i = 0; i < matids.size(); i += 3) if (matids[i] < map_kd.size() && map_kd[matids[i]] >= 0) return true;      // (a triangle's material is the id of its first index entry: flatten_range)
+    return false;
+}
+bool SceneHost::only_maps_changed(const BuiltScene& b) const {
+    if (topo_dirty || mats_dirty || !dirty_meshes.empty() || b.insts.size() != insts.size()) return false;
+    for (size_t ii = 0; ii < insts.size(); ii++) {
+        if (memcmp(b.insts[ii].o2w, insts[ii].o2w, 64) != 0 || memcmp(b.insts[ii].prev_o2w, insts[ii].prev_o2w, 64) != 0) return false;
+        if ((ii < b.inst_hidden.size() && b.inst_hidden[ii] != 0u) != is_hidden(ii)) return false;
+    }
+    return true;
+}
+void SceneHost::fill_tri_uv(std::vector<float>& out) const {
+    size_t nt = 0; for (const InstHost& in : insts) nt += meshes[in.mesh].idx.size() / 3;
+    out.assign(nt * 6, 0.0f);
+    for (const InstHost& in : insts) {
+        const MeshHost& m = meshes[in.mesh];
+        if (!m.uvs.empty()) memcpy(&out[(size_t)in.tri_base * 6], m.uvs.data(), m.uvs.size() * 4);      // corner k of triangle t = index entry 3 t + k
+    }
 }
 
 static bool mesh_emits(const SceneHost& H, const MeshHost& m) {
@@ -383,7 +441,9 @@ bool SceneHost::build(BuiltScene& B) {
     sw.lap("collapse_bvh8");
     // a tiny scene with a hidden instance takes the general BVH path until everything is visible again: its pre-test records, merged quads, hull faces and the NEE hull
     // shortcut are derived from geometry, and a hidden triangle may take part in none of them (identical results by the parity contract)
-    if (B.any_hidden) { B.small_recs.clear(); B.small_tris.clear(); B.small_poly.clear(); B.small_nrec = 0; B.small_nocc = 0; }
+    // ... and so does one with an active texture map (k_bounce_small and k_primary_surface sample no image)
+    B.maps_active = maps_active();
+    if (B.any_hidden || B.maps_active) { B.small_recs.clear(); B.small_tris.clear(); B.small_poly.clear(); B.small_nrec = 0; B.small_nocc = 0; }
     else build_small_scene(B, wtri, scale);
     sw.lap("tris8 / small scene");
     B.any_order = probe_anyhit_order(B);

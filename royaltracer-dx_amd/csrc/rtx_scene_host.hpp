@@ -14,7 +14,8 @@ float half_round(float x);                               // binary16 round trip 
 void  mat4_inverse(const float* m16, float* out16);      // XMMatrixInverse stand-in
 void  normal_matrix(const float* o2w16, float* out16);   // Renderer.cpp:2104-2116
 
-struct MeshHost { std::vector<float> verts; std::vector<uint32_t> idx; uint32_t matid_base = 0; };
+struct MeshHost { std::vector<float> verts; std::vector<uint32_t> idx; uint32_t matid_base = 0; std::vector<float> uvs; };      // uvs: (u, v) per INDEX entry (rtx_set_mesh_uvs), or empty = (0, 0) everywhere
+struct TexHost { uint32_t width = 0, height = 0, flags = 0; std::vector<uint32_t> rgba; };      // rtx_set_texture: width x height RGBA8, row 0 on top
 struct InstHost { uint32_t mesh; float o2w[16]; float nrm[16]; float o2w_inv[16]; float prev_o2w[16]; uint32_t tri_base; };
 
 struct BuiltScene {
@@ -46,6 +47,7 @@ struct BuiltScene {
     uint32_t refit_count = 0;           // commits since the last full build that only refitted the boxes
     std::vector<uint32_t> inst_hidden;  // one word per instance, non-zero = hidden, AS COMMITTED: what the resident tree's boxes, the never-hit triangle records and the light list reflect (the refit kernels read it)
     bool any_hidden = false;            // ... and whether any word of it is set
+    bool maps_active = false;           // SceneHost::maps_active() AS COMMITTED: a tiny scene then runs on the general path, DevScene::tri_uv / map_kd are set
     std::vector<uint32_t> inst_moved;   // refresh_transforms: 1 = the instance's objectToWorld differs from the last commit's, or its mesh's vertices do, or its visibility does (the GPU refit touches the triangles and nodes of these only)
 };
 
@@ -59,6 +61,10 @@ struct SceneHost {
     bool mats_dirty = true;                     // rtx_set_materials since the material table was last derived
     std::vector<uint32_t> dirty_meshes;         // rtx_update_mesh_vertices since the last commit: meshes whose vertices changed (topology kept; the commit clears the list)
     std::vector<uint8_t> inst_hidden;           // rtx_set_instance_visible: 1 = hidden, as the caller wants it from the next commit on; shorter than insts = the rest is visible (every instance starts visible)
+    // diffuse texture maps (include/rtx.h: rtx_set_mesh_uvs, rtx_set_texture, rtx_set_material_map)
+    std::vector<TexHost> textures;
+    std::vector<int32_t> map_kd;                // per material: texture id of RTX_MAP_KD or -1; shorter than the table = the rest has none (rtx_set_materials empties it)
+    bool tex_dirty = false;                     // one of the three setters since the last commit
     BvhBuildOptions bvh = bvh_build_options();  // builder knobs of this scene (rtx_set_option RTX_OPT_BVH_*)
 
     bool set_materials(const void* mats, uint32_t count);
@@ -75,6 +81,14 @@ struct SceneHost {
     bool update_mesh_vertices(uint32_t mesh, const void* verts28, uint32_t nverts);
     bool mesh_is_dirty(uint32_t mesh) const { for (uint32_t m : dirty_meshes) if (m == mesh) return true; return false; }
     bool dirty_mesh_emits() const;              // a dirty mesh carries a triangle that emits under the current material table (the light list then needs the full scan: weights and order depend on areas)
+    // each returns false, with `err` set and NOTHING changed, for the RTX_ERR_INVALID cases of include/rtx.h
+    bool set_mesh_uvs(uint32_t mesh, const float* uv2, uint32_t nidx);
+    bool set_texture(uint32_t tex, const void* rgba8, uint32_t width, uint32_t height, uint32_t flags);
+    bool set_material_map(uint32_t material, uint32_t slot, int32_t tex);
+    bool any_map() const { for (int32_t t : map_kd) if (t >= 0) return true; return false; }
+    bool maps_active() const;                   // a material that some triangle uses has a map
+    bool only_maps_changed(const BuiltScene& b) const;      // against the committed scene b: no instance moved, was hidden or shown, no mesh got new vertices, same topology and material table
+    void fill_tri_uv(std::vector<float>& out) const;        // 6 floats per global triangle id (InstHost::tri_base as the last geometry-changing commit numbered them)
     bool build(BuiltScene& out);                // the host's whole commit: materials, flattening + shade records, lights, the tree (built, or refitted after a transform-only change), its wide form, tiny-scene records, any-hit probe
     void build_materials(BuiltScene& out);      // mats128 -> MatGPU table (clears mats_dirty)
     // transform- or vertex-only update of the records the GPU refit does not derive itself: instance matrices and the light list; inst_moved also names the instances of dirty meshes

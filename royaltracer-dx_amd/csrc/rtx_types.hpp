@@ -71,6 +71,10 @@ struct alignas(16) LightGPU {
 };
 static_assert(sizeof(LightGPU) == 80, "LightGPU must be 80 bytes");
 
+// a texture of the context's table (rtx_set_texture): where its width x height RGBA8 texels (row 0 on top) start in the one texel pool, and RTX_TEX_* flags
+struct alignas(16) TexDesc { uint32_t offset, width, height, flags; };
+static_assert(sizeof(TexDesc) == 16, "TexDesc must be 16 bytes");
+
 struct CameraGPU { float viewI[16]; float projI[16]; float prev_view[16]; float prev_proj[16]; };   // a7 (+ prevView / prevProjection for the temporal pass)
 
 }  // namespace rtx

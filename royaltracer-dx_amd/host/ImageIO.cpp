@@ -81,3 +81,92 @@ bool WriteEXR(const std::string& path, const float* acc, uint32_t w, uint32_t h)
     }
     return write_file(path, o.data(), o.size());
 }
+
+// ------------------------------------------------------------------------------------------------
+// readers (texture maps)
+// ------------------------------------------------------------------------------------------------
+namespace {
+constexpr uint32_t kMaxImageSide = 16384;                  // rtx_set_texture's limit
+bool read_file(const std::string& path, std::vector<uint8_t>& out, std::string& err) {
+    FILE* f = fopen(path.c_str(), "rb");
+    if (!f) { err = "cannot open " + path; return false; }
+    uint8_t buf[65536]; size_t n;
+    while ((n = fread(buf, 1, sizeof(buf), f)) > 0) out.insert(out.end(), buf, buf + n);
+    fclose(f);
+    return true;
+}
+bool pnm_from(const std::vector<uint8_t>& b, const std::string& path, std::vector<uint8_t>& rgba, uint32_t& w, uint32_t& h, std::string& err) {
+    if (b.size() < 2 || b[0] != 'P' || (b[1] != '5' && b[1] != '6')) { err = path + ": not a binary PPM / PGM (P6 / P5)"; return false; }
+    const int ch = b[1] == '6' ? 3 : 1;
+    size_t at = 2; uint32_t val[3] = {0, 0, 0};
+    for (int k = 0; k < 3; k++) {                          // width, height, maxval: decimal, separated by white space; '#' starts a comment up to the end of the line
+        while (at < b.size() && (b[at] == ' ' || b[at] == '\t' || b[at] == '\n' || b[at] == '\r' || b[at] == '#')) { if (b[at] == '#') while (at < b.size() && b[at] != '\n') at++; else at++; }
+        bool digit = false;
+        while (at < b.size() && b[at] >= '0' && b[at] <= '9' && val[k] < 100000000u) { val[k] = val[k] * 10 + (uint32_t)(b[at] - '0'); at++; digit = true; }
+        if (!digit) { err = path + ": bad PNM header"; return false; }
+    }
+    at++;                                                  // the single white-space byte behind maxval
+    if (val[2] != 255) { err = path + ": PNM maxval must be 255"; return false; }
+    w = val[0]; h = val[1];
+    if (!w || !h || w > kMaxImageSide || h > kMaxImageSide) { err = path + ": image size out of range"; return false; }
+    const size_t need = (size_t)w * h * ch;
+    if (at > b.size() || b.size() - at < need) { err = path + ": truncated PNM"; return false; }
+    rgba.resize((size_t)w * h * 4);
+    for (size_t i = 0; i < (size_t)w * h; i++) { const uint8_t* q = &b[at + i * ch]; rgba[i * 4] = q[0]; rgba[i * 4 + 1] = q[ch == 3 ? 1 : 0]; rgba[i * 4 + 2] = q[ch == 3 ? 2 : 0]; rgba[i * 4 + 3] = 255; }
+    return true;
+}
+bool tga_from(const std::vector<uint8_t>& b, const std::string& path, std::vector<uint8_t>& rgba, uint32_t& w, uint32_t& h, std::string& err) {
+    if (b.size() < 18) { err = path + ": not a TGA file"; return false; }
+    const uint32_t idlen = b[0], cmap = b[1], type = b[2], bpp = b[16], desc = b[17];
+    w = b[12] | (b[13] << 8); h = b[14] | (b[15] << 8);
+    if (cmap != 0 || (type != 2 && type != 10) || (bpp != 24 && bpp != 32)) { err = path + ": unsupported TGA (true colour, 24 or 32 bits, uncompressed or RLE only)"; return false; }
+    if (!w || !h || w > kMaxImageSide || h > kMaxImageSide) { err = path + ": image size out of range"; return false; }
+    const size_t cmap_bytes = (size_t)(b[5] | (b[6] << 8)) * ((b[7] + 7u) / 8u);
+    size_t at = 18 + (size_t)idlen + cmap_bytes;
+    const uint32_t bytes = bpp / 8; const size_t npix = (size_t)w * h;
+    rgba.resize(npix * 4);
+    const bool top_down = (desc & 0x20u) != 0, right_left = (desc & 0x10u) != 0;
+    auto put = [&](size_t i, const uint8_t* q) {           // pixel i in FILE order (b, g, r[, a]) -> its place in the top-down image
+        const size_t fy = i / w, fx = i % w, y = top_down ? fy : h - 1 - fy, x = right_left ? w - 1 - fx : fx;
+        uint8_t* o = &rgba[(y * w + x) * 4]; o[0] = q[2]; o[1] = q[1]; o[2] = q[0]; o[3] = bytes == 4 ? q[3] : 255;
+    };
+    if (type == 2) {
+        if (at > b.size() || b.size() - at < npix * bytes) { err = path + ": truncated TGA"; return false; }
+        for (size_t i = 0; i < npix; i++) put(i, &b[at + i * bytes]);
+        return true;
+    }
+    size_t i = 0;
+    while (i < npix) {                                     // packets: header byte, then one pixel repeated (bit 7) or count raw pixels; a packet may cross a row
+        if (at >= b.size()) { err = path + ": truncated TGA"; return false; }
+        const uint8_t hd = b[at++]; const size_t count = (size_t)(hd & 127u) + 1;
+        if (count > npix - i) { err = path + ": TGA packet runs past the image"; return false; }
+        if (hd & 128u) {
+            if (b.size() - at < bytes) { err = path + ": truncated TGA"; return false; }
+            for (size_t k = 0; k < count; k++) put(i + k, &b[at]);
+            at += bytes;
+        } else {
+            if (b.size() - at < count * bytes) { err = path + ": truncated TGA"; return false; }
+            for (size_t k = 0; k < count; k++) put(i + k, &b[at + k * bytes]);
+            at += count * bytes;
+        }
+        i += count;
+    }
+    return true;
+}
+}  // namespace
+
+bool ReadPNM(const std::string& path, std::vector<uint8_t>& rgba8, uint32_t& w, uint32_t& h, std::string& err) {
+    std::vector<uint8_t> b;
+    return read_file(path, b, err) && pnm_from(b, path, rgba8, w, h, err);
+}
+bool ReadTGA(const std::string& path, std::vector<uint8_t>& rgba8, uint32_t& w, uint32_t& h, std::string& err) {
+    std::vector<uint8_t> b;
+    return read_file(path, b, err) && tga_from(b, path, rgba8, w, h, err);
+}
+bool ReadImage(const std::string& path, std::vector<uint8_t>& rgba8, uint32_t& w, uint32_t& h, std::string& err) {
+    std::vector<uint8_t> b;
+    if (!read_file(path, b, err)) return false;
+    if (b.size() >= 2 && b[0] == 'P' && (b[1] == '5' || b[1] == '6')) return pnm_from(b, path, rgba8, w, h, err);
+    if (!tga_from(b, path, rgba8, w, h, err)) { err = path + ": neither a binary PPM / PGM nor a true-colour TGA (" + err + ")"; return false; }
+    return true;
+}

@@ -126,8 +126,8 @@ std::string parse_texname(const char* p) {
     while (!name.empty() && (name.back() == ' ' || name.back() == '\t')) name.pop_back();
     return name;
 }
-struct ObjIdx { int v, vn; };
-struct ObjParsed { std::vector<float> v, vn; std::vector<ObjIdx> idx; std::vector<int> face_mat; std::vector<MtlRec> mats; };
+struct ObjIdx { int v, vn, vt; };
+struct ObjParsed { std::vector<float> v, vn, vt; std::vector<ObjIdx> idx; std::vector<int> face_mat; std::vector<MtlRec> mats; };
 
 
 void load_mtl(const std::string& path, std::vector<MtlRec>& mats, std::unordered_map<std::string, int>& map) {
@@ -243,17 +243,19 @@ bool parse_obj(const std::string& file, const std::string& mtl_dir, ObjParsed& o
         if (!*p || *p == '#') continue;
         if (p[0] == 'v' && (p[1] == ' ' || p[1] == '\t')) { p += 2; float a[3] = {0, 0, 0}; for (int i = 0; i < 3; i++) parse_float(p, a[i]); out.v.insert(out.v.end(), a, a + 3); }
         else if (p[0] == 'v' && p[1] == 'n' && (p[2] == ' ' || p[2] == '\t')) { p += 3; float a[3] = {0, 0, 0}; for (int i = 0; i < 3; i++) parse_float(p, a[i]); out.vn.insert(out.vn.end(), a, a + 3); }
+        else if (p[0] == 'v' && p[1] == 't' && (p[2] == ' ' || p[2] == '\t')) { p += 3; float a[2] = {0, 0}; for (int i = 0; i < 2; i++) parse_float(p, a[i]); out.vt.insert(out.vt.end(), a, a + 2); }
         else if (p[0] == 'f' && (p[1] == ' ' || p[1] == '\t')) {
             p += 2; face.clear();
-            const int nv = (int)(out.v.size() / 3), nn = (int)(out.vn.size() / 3);
+            const int nv = (int)(out.v.size() / 3), nn = (int)(out.vn.size() / 3), nt = (int)(out.vt.size() / 2);
             while (true) {
                 p = skip_ws(p);
                 if (!*p) break;
                 char* e; long vi = strtol(p, &e, 10);
                 if (e == p) break;
-                p = e; long ni = 0; bool has_n = false;
-                if (*p == '/') { p++; if (*p != '/') { (void)strtol(p, &e, 10); p = e; } if (*p == '/') { p++; ni = strtol(p, &e, 10); has_n = e != p; p = e; } }
+                p = e; long ni = 0, ti = 0; bool has_n = false, has_t = false;
+                if (*p == '/') { p++; if (*p != '/') { ti = strtol(p, &e, 10); has_t = e != p; p = e; } if (*p == '/') { p++; ni = strtol(p, &e, 10); has_n = e != p; p = e; } }
                 ObjIdx ix; ix.v = vi > 0 ? (int)vi - 1 : nv + (int)vi; ix.vn = has_n ? (ni > 0 ? (int)ni - 1 : nn + (int)ni) : -1;
+                ix.vt = (has_t && ti != 0) ? (ti > 0 ? (int)ti - 1 : nt + (int)ti) : -1;       // tinyobj's fixIndex: 1-based, negative = relative to the vt lines read so far
                 face.push_back(ix);
             }
             const int n = (int)face.size();
@@ -291,13 +293,13 @@ bool parse_obj(const std::string& file, const std::string& mtl_dir, ObjParsed& o
 void ObjLoader::loadObjFile(const std::string& inputfile, std::vector<Vertex>* vertices, std::vector<UINT>* indices,
                             std::vector<Material>* mats, std::vector<UINT>* materialIDs, UINT* materialOffset,
                             UINT* materialVertexOffset, const std::string& material_search_path) {
-    loadObjFileEx(inputfile, vertices, indices, mats, materialIDs, materialOffset, materialVertexOffset, nullptr, nullptr, material_search_path);
+    loadObjFileEx(inputfile, vertices, indices, mats, materialIDs, materialOffset, materialVertexOffset, nullptr, nullptr, material_search_path, nullptr);
 }
 
 void ObjLoader::loadObjFileEx(const std::string& inputfile, std::vector<Vertex>* vertices, std::vector<UINT>* indices,
                               std::vector<Material>* mats, std::vector<UINT>* materialIDs, UINT* materialOffset,
                               UINT* materialVertexOffset, std::vector<MaterialExt>* ext, std::vector<std::string>* textures,
-                              const std::string& material_search_path) {
+                              const std::string& material_search_path, std::vector<float>* corner_uvs) {
     ObjParsed P; std::string err;
     if (!parse_obj(inputfile, material_search_path, P, err)) throw std::runtime_error("ObjLoader: " + err);   // ObjLoader.h:399-404
     // default material for faces without one (ObjLoader.h:415-417)
@@ -337,6 +339,10 @@ void ObjLoader::loadObjFileEx(const std::string& inputfile, std::vector<Vertex>*
             auto it = unique.find(vert);
             if (it == unique.end()) { it = unique.emplace(vert, (uint32_t)vertices->size()).first; vertices->push_back(vert); }
             indices->push_back(it->second);
+            if (corner_uvs) {                  // per CORNER, aligned with *indices: the de-duplication above never sees them
+                const bool has = ix.vt >= 0 && (size_t)ix.vt * 2 + 1 < P.vt.size();
+                corner_uvs->push_back(has ? P.vt[(size_t)ix.vt * 2] : 0.0f); corner_uvs->push_back(has ? P.vt[(size_t)ix.vt * 2 + 1] : 0.0f);
+            }
         }
     }
     *materialOffset += (UINT)P.mats.size();                                                                 // :494

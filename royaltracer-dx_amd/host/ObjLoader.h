@@ -25,7 +25,8 @@ float ComputeEss(const XMFLOAT3& N, const XMFLOAT3& V, float roughness, XMFLOAT3
 
 // What tinyobj's material_t holds beyond the reference's 128-byte Material ("ADD MAP IDs LATER", Vertex.h:21): the remaining
 // MTL scalars (Ni is parsed by the reference's loader too but never copied into Material.Ni, ObjLoader.h:428-435) and one texture id per
-// map statement.  Carried beside the material table, index-aligned with it; no shader reads any of it.
+// map statement.  Carried beside the material table, index-aligned with it; the diffuse map (MAP_KD) is the one entry a kernel ends up reading, once its image is decoded
+// and bound (Scenes.h: BindSceneMaps); everything else is carried only.
 enum MapSlot { MAP_KA = 0, MAP_KD, MAP_KS, MAP_KE, MAP_NS, MAP_BUMP, MAP_D, MAP_DISP, MAP_REFL, MAP_PR, MAP_PM, MAP_PS, MAP_NORM, kNumMapSlots };
 struct MaterialExt {
     float Ni = 1.0f, Ns = 1.0f;               // ior, shininess
@@ -37,11 +38,13 @@ struct MaterialExt {
 
 class ObjLoader {
 public:
-    // the same call with the extra outputs: *ext grows in step with *mats (default material first), *textures collects distinct file names
+    // the same call with the extra outputs: *ext grows in step with *mats (default material first), *textures collects distinct file names, *corner_uvs gets one (u, v)
+    // pair per entry of *indices — the `vt` a face corner names (1-based or negative, tinyobj's rule), (0, 0) for a corner without one — for triangles, split quads and
+    // ear-clipped polygons alike; vertices, indices and material ids do not depend on it
     static void loadObjFileEx(const std::string& inputfile, std::vector<Vertex>* vertices, std::vector<UINT>* indices,
                               std::vector<Material>* mats, std::vector<UINT>* materialIDs, UINT* materialOffset,
                               UINT* materialVertexOffset, std::vector<MaterialExt>* ext, std::vector<std::string>* textures,
-                              const std::string& material_search_path = "./");
+                              const std::string& material_search_path = "./", std::vector<float>* corner_uvs = nullptr);
     // throws std::runtime_error where the reference calls exit(1) (ObjLoader.h:399-404)
     static void loadObjFile(const std::string& inputfile, std::vector<Vertex>* vertices, std::vector<UINT>* indices,
                             std::vector<Material>* mats, std::vector<UINT>* materialIDs, UINT* materialOffset,

@@ -29,7 +29,7 @@ void Renderer::Check(int rc, const char* what) {
 void Renderer::OnInit() {
     if (!m_haveScene) {
         if (m_models.empty()) throw std::logic_error("Renderer::OnInit: no models (SetModels) and no scene (SetScene)");
-        m_scene = LoadObjScene(m_models, m_mtlDir);                                 // CreateVB per model, Renderer.cpp:363-370
+        m_scene = LoadObjScene(m_models, m_mtlDir, m_loadTextures);                                 // CreateVB per model, Renderer.cpp:363-370
         m_haveScene = true;
     }
     CameraManip.setWindowSize((int)m_width, (int)m_height);                         // Renderer.cpp:45
@@ -41,6 +41,7 @@ void Renderer::OnInit() {
         Check(rtx_add_mesh(m_ctx, m.vertices.data(), (uint32_t)m.vertices.size(), m.indices.data(), (uint32_t)m.indices.size(), m.materialIDs.data(), &id), "rtx_add_mesh");
     }
     for (const SceneInstance& in : m_scene.instances) { uint32_t id; Check(rtx_add_instance(m_ctx, in.model, in.transform.data(), &id), "rtx_add_instance"); }
+    Check(BindSceneMaps(m_scene, m_ctx), "BindSceneMaps");                         // the decoded map_Kd images, per-corner UVs and map ids (nothing for a scene without them)
     Check(rtx_commit_scene(m_ctx), "rtx_commit_scene");                             // CreateAccelerationStructures, Renderer.cpp:893-946
     Check(rtx_clear_accum(m_ctx, m_width, m_height), "rtx_clear_accum");
 }

@@ -1,6 +1,9 @@
 // Scenes.cpp — deterministic synthetic scenes in the reference's data model (see Scenes.h).
 #include "Scenes.h"
+#include "ImageIO.h"
+#include <algorithm>
 #include <cmath>
+#include <cstdio>
 #include <cstring>
 #include <functional>
 #include "ObjLoader.h"
@@ -538,13 +541,13 @@ Scene MakeBistroClass(uint32_t target, uint32_t seed, bool hard) {
 }
 
 // the reference's startup scene (Renderer.cpp:363-407, 444-449, 46-48)
-Scene LoadObjScene(const std::vector<std::string>& files, const std::string& mtl_dir) {
+Scene LoadObjScene(const std::vector<std::string>& files, const std::string& mtl_dir, bool load_textures) {
     Scene s; s.name = "obj";
     UINT materialIDOffset = 0, materialVertexOffset = 0;       // Renderer members of the same name
     size_t total_ids = 0;
     for (size_t i = 0; i < files.size(); i++) {
         SceneModel m;
-        ObjLoader::loadObjFileEx(files[i], &m.vertices, &m.indices, &s.materials, &m.materialIDs, &materialIDOffset, &materialVertexOffset, &s.materialExt, &s.textures, mtl_dir);
+        ObjLoader::loadObjFileEx(files[i], &m.vertices, &m.indices, &s.materials, &m.materialIDs, &materialIDOffset, &materialVertexOffset, &s.materialExt, &s.textures, mtl_dir, &m.uvs);
         total_ids += m.materialIDs.size();
         materialVertexOffset = (UINT)total_ids;                // Renderer.cpp:1997
         s.models.push_back(std::move(m));
@@ -553,6 +556,18 @@ Scene LoadObjScene(const std::vector<std::string>& files, const std::string& mtl
         s.instances.push_back({(UINT)i, t});
     }
     s.eye = XMFLOAT3(-1.5f, 1.5f, 3.5f); s.center = XMFLOAT3(0, 1, 0); s.up = XMFLOAT3(0, 1, 0);   // Renderer.cpp:46-48
+    s.images.resize(s.textures.size());
+    std::vector<char> tried(s.textures.size(), 0);
+    for (const MaterialExt& x : s.materialExt) {               // the diffuse maps only: no kernel samples another slot
+        const int t = x.map[MAP_KD];
+        if (!load_textures || t < 0 || (size_t)t >= s.textures.size() || tried[t]) continue;
+        tried[t] = 1;
+        std::string dir = mtl_dir; if (!dir.empty() && dir.back() != '/') dir += '/';
+        std::string name = s.textures[t]; std::replace(name.begin(), name.end(), '\\', '/');
+        std::string err; SceneImage img;
+        if (ReadImage((!name.empty() && name[0] == '/') ? name : dir + name, img.rgba, img.width, img.height, err)) s.images[t] = std::move(img);
+        else fprintf(stderr, "map_Kd skipped: %s\n", err.c_str());
+    }
     return s;
 }
 
@@ -576,6 +591,31 @@ bool SetSceneMeshVertices(Scene& s, UINT model, const void* verts28, uint32_t nv
     return true;
 }
 
+// (weak: the host layer is also linked against a fixed list of stand-ins for the C-ABI, where these resolve to null and nothing is bound)
+extern "C" int rtx_set_mesh_uvs(rtx_ctx*, uint32_t mesh, const float* uv2, uint32_t nidx) __attribute__((weak));
+extern "C" int rtx_set_texture(rtx_ctx*, uint32_t tex, const void* rgba8, uint32_t width, uint32_t height, uint32_t flags) __attribute__((weak));
+extern "C" int rtx_set_material_map(rtx_ctx*, uint32_t material, uint32_t slot, int32_t tex) __attribute__((weak));
+
+int BindSceneMaps(const Scene& s, rtx_ctx* ctx) {
+    if (!rtx_set_mesh_uvs || !rtx_set_texture || !rtx_set_material_map) return RTX_OK;
+    std::vector<int> id(s.textures.size(), -1); uint32_t n = 0;        // scene texture -> the context's table: the decoded ones, in order
+    int r;
+    for (size_t t = 0; t < s.images.size() && t < id.size(); t++) {
+        const SceneImage& im = s.images[t];
+        if (!im.width) continue;
+        if ((r = rtx_set_texture(ctx, n, im.rgba.data(), im.width, im.height, RTX_TEX_SRGB))) return r;      // map_Kd images are taken as sRGB
+        id[t] = (int)n++;
+    }
+    if (!n) return RTX_OK;
+    for (size_t m = 0; m < s.models.size(); m++)
+        if (!s.models[m].uvs.empty() && (r = rtx_set_mesh_uvs(ctx, (uint32_t)m, s.models[m].uvs.data(), (uint32_t)s.models[m].indices.size()))) return r;
+    for (size_t m = 0; m < s.materialExt.size() && m < s.materials.size(); m++) {
+        const int t = s.materialExt[m].map[MAP_KD];
+        if (t >= 0 && (size_t)t < id.size() && id[t] >= 0 && (r = rtx_set_material_map(ctx, (uint32_t)m, RTX_MAP_KD, id[t]))) return r;
+    }
+    return RTX_OK;
+}
+
 int UploadScene(const Scene& s, rtx_ctx* ctx, float aspect) {
     int r;
     if ((r = rtx_set_materials(ctx, s.materials.data(), (uint32_t)s.materials.size()))) return r;
@@ -584,6 +624,7 @@ int UploadScene(const Scene& s, rtx_ctx* ctx, float aspect) {
         if ((r = rtx_add_mesh(ctx, m.vertices.data(), (uint32_t)m.vertices.size(), m.indices.data(), (uint32_t)m.indices.size(), m.materialIDs.data(), &id))) return r;
     }
     for (const SceneInstance& in : s.instances) { uint32_t id; if ((r = rtx_add_instance(ctx, in.model, in.transform.data(), &id))) return r; }
+    if ((r = BindSceneMaps(s, ctx))) return r;
     if ((r = rtx_commit_scene(ctx))) return r;
     float view[16], proj[16];
     SceneViewProj(s, aspect, view, proj);

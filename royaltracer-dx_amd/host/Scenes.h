@@ -9,13 +9,17 @@
 #include "ObjLoader.h"
 #include "../../include/rtx.h"
 
-struct SceneModel { std::vector<Vertex> vertices; std::vector<UINT> indices; std::vector<UINT> materialIDs; };
+struct SceneModel { std::vector<Vertex> vertices; std::vector<UINT> indices; std::vector<UINT> materialIDs;
+                    std::vector<float> uvs; };      // one (u, v) per entry of `indices` (the OBJ's vt, per corner), or empty
+struct SceneImage { uint32_t width = 0, height = 0; std::vector<uint8_t> rgba; };      // a decoded texture, top-down RGBA8; width 0 = not loaded
 struct SceneInstance { UINT model; XMMATRIX transform; };
 struct Scene {
     std::string name;
     std::vector<Material> materials;         // [default_0, mats of model 0..., default_1, ...]  (ObjLoader.h:415-417,494)
     std::vector<MaterialExt> materialExt;    // index-aligned with `materials` when the scene came from OBJ / MTL files (empty otherwise): the MTL fields and
     std::vector<std::string> textures;       // texture map ids the 128-byte record has no room for (Vertex.h:21 "ADD MAP IDs LATER"), and the distinct map file names
+    std::vector<SceneImage> images;          // index-aligned with `textures`: the decoded map_Kd files (host/ImageIO readers); an entry that no map_Kd names, or whose file
+                                             // is missing or in another format, stays empty.  BindSceneMaps hands the loaded ones to a context, sRGB-encoded
     std::vector<SceneModel> models;
     std::vector<SceneInstance> instances;
     XMFLOAT3 eye{0, 0, 1}, center{0, 0, 0}, up{0, 1, 0};
@@ -31,7 +35,10 @@ Scene MakeSponzaClass(uint32_t target_tris = 262144, uint32_t seed = 260, bool h
 Scene MakeBistroClass(uint32_t target_tris = 3800000, uint32_t seed = 3800, bool hard = false);
 // the reference's own startup scene: each file through ObjLoader::loadObjFile, one instance per model,
 // instance 1 rotated 1.57 rad about Y (Renderer.cpp:363-407, 444-449)
-Scene LoadObjScene(const std::vector<std::string>& files, const std::string& mtl_dir);
+// load_textures: decode every file a map_Kd names, relative to mtl_dir (a file that cannot be read is skipped with one line on stderr)
+Scene LoadObjScene(const std::vector<std::string>& files, const std::string& mtl_dir, bool load_textures = true);
+// rtx_set_mesh_uvs / rtx_set_texture / rtx_set_material_map for what the scene carries; a scene without a decoded image binds nothing.  Before rtx_commit_scene
+int BindSceneMaps(const Scene&, rtx_ctx*);
 // new vertices for a model whose topology stays (the scene-level twin of rtx_update_mesh_vertices, same checks: the model exists, same vertex count, Vertex.normal.w — the
 // model's base in materialIDs[] — unchanged, non-null); false + err leaves the scene as it was
 bool SetSceneMeshVertices(Scene&, UINT model, const void* verts28, uint32_t nverts, std::string& err);

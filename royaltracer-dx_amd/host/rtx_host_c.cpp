@@ -52,6 +52,13 @@ rtxh_scene* rtxh_scene_sponza_class(uint32_t t, uint32_t seed) { return guarded(
 rtxh_scene* rtxh_scene_bistro_class(uint32_t t, uint32_t seed) { return guarded([=] { return MakeBistroClass(t, seed); }); }
 rtxh_scene* rtxh_scene_sponza_class_hard(uint32_t t, uint32_t seed) { return guarded([=] { return MakeSponzaClass(t, seed, true); }); }
 rtxh_scene* rtxh_scene_bistro_class_hard(uint32_t t, uint32_t seed) { return guarded([=] { return MakeBistroClass(t, seed, true); }); }
+int rtxh_read_image(const char* path, void* rgba8, uint64_t capacity, uint32_t* width, uint32_t* height) {
+    if (!path || !width || !height) return RTX_ERR_INVALID;
+    std::vector<uint8_t> px; std::string err;
+    if (!ReadImage(path, px, *width, *height, err)) { g_err = err; return RTX_ERR_INVALID; }
+    if (rgba8 && capacity >= px.size()) memcpy(rgba8, px.data(), px.size());
+    return RTX_OK;
+}
 rtxh_scene* rtxh_scene_from_obj(const char* const* files, uint32_t n, const char* mtl_dir) {
     std::vector<std::string> f; for (uint32_t i = 0; i < n; i++) f.emplace_back(files[i]);
     std::string dir = mtl_dir ? mtl_dir : "./";
@@ -71,6 +78,18 @@ int rtxh_scene_material_ext(const rtxh_scene* s, uint32_t i, rtxh_material_ext* 
     out->Ni = x.Ni; out->Ns = x.Ns; out->Pcr = x.Pcr; out->aniso = x.aniso; out->anisor = x.anisor; out->illum = x.illum;
     for (int k = 0; k < 3; k++) { out->Ka[k] = x.Ka[k]; out->Tf[k] = x.Tf[k]; }
     for (int k = 0; k < kNumMapSlots; k++) out->map[k] = x.map[k];
+    return RTX_OK;
+}
+int rtxh_scene_texture_pixels(const rtxh_scene* s, uint32_t i, const void** rgba8, uint32_t* width, uint32_t* height) {
+    if (!rgba8 || !width || !height || i >= s->s.textures.size()) return RTX_ERR_INVALID;
+    const bool have = i < s->s.images.size() && s->s.images[i].width != 0;
+    *rgba8 = have ? s->s.images[i].rgba.data() : nullptr; *width = have ? s->s.images[i].width : 0; *height = have ? s->s.images[i].height : 0;
+    return RTX_OK;
+}
+int rtxh_scene_mesh_uvs(const rtxh_scene* s, uint32_t i, const float** uv2, uint32_t* nidx) {
+    if (!uv2 || !nidx || i >= s->s.models.size()) return RTX_ERR_INVALID;
+    const SceneModel& m = s->s.models[i];
+    *uv2 = m.uvs.empty() ? nullptr : m.uvs.data(); *nidx = (uint32_t)(m.uvs.size() / 2);
     return RTX_OK;
 }
 uint32_t rtxh_scene_num_meshes(const rtxh_scene* s) { return (uint32_t)s->s.models.size(); }

@@ -18,6 +18,7 @@
 //                   [--denoise [--denoise-levels N] [--sigma-color X] [--sigma-plane X]]   after the last frame rtx_denoise filters the accumulated image (edge-avoiding a-trous,
 //                   guided by first-hit position, normal and material; defaults: 5 levels, 0.5, 2^-6 of the scene's extent) and --out gets the DENOISED image; works with
 //                   --adaptive and with --gpus N (on rank 0, after the gather); refused with --mode restir (that frame has its own reuse passes)
+//                   [--no-textures]   OBJ scenes: do not read the images their map_Kd statements name (binary PPM / PGM, 24- / 32-bit TGA): the image without diffuse maps
 //                   [--gpus N [--devices 0,1,..] [--gather rccl|copy]]   the native N-GPU frame (MultiGpu.h): one process, N contexts, pixel tiles
 //                   round-robin, ONE RCCL all-gather per frame; `--gather copy` replaces the collective by device copies (several ranks on one GPU: tests)
 #include <algorithm>
@@ -39,6 +40,7 @@ static const char* kUsage =
     "                  [--mode pt|restir] [--literal] [--halo px] [--force-gather] [--orbit deg] [--spin deg] [--hide i[,j...]] [--blink i] [--only-rank r]\n"
     "                  [--adaptive THRESHOLD [--min-spp N] [--step-spp N]]\n"
     "                  [--denoise [--denoise-levels N] [--sigma-color X] [--sigma-plane X]]   write the denoised image to --out (path tracer only)\n"
+    "                  [--no-textures]   OBJ scenes: ignore map_Kd images\n"
     "                  [--gpus N [--devices 0,1,..] [--gather rccl|copy]]\n";
 
 int main(int argc, char** argv) {
@@ -48,6 +50,7 @@ int main(int argc, char** argv) {
     std::vector<UINT> hide; int blink = -1;
     bool adaptive = false; rtx_adaptive ad{}; ad.min_spp = 8; ad.step_spp = 8;
     bool denoise = false; rtx_denoise_params dnp{};
+    bool textures = true;
     for (int i = 1; i < argc; i++) {
         auto arg = [&](const char* k) { return !strcmp(argv[i], k) && i + 1 < argc; };
         if (arg("--scene")) scene = argv[++i]; else if (arg("--obj")) { objs = argv[++i]; scene = "obj"; } else if (arg("--mtl")) mtl = argv[++i];
@@ -57,6 +60,7 @@ int main(int argc, char** argv) {
         else if (arg("--hide")) { std::stringstream ss(argv[++i]); std::string t; while (std::getline(ss, t, ',')) hide.push_back((UINT)atoi(t.c_str())); } else if (arg("--blink")) blink = atoi(argv[++i]);
         else if (arg("--adaptive")) { adaptive = true; ad.threshold = (float)atof(argv[++i]); } else if (arg("--min-spp")) ad.min_spp = (uint32_t)atoi(argv[++i]); else if (arg("--step-spp")) ad.step_spp = (uint32_t)atoi(argv[++i]);
         else if (!strcmp(argv[i], "--help") || !strcmp(argv[i], "-h")) { fputs(kUsage, stdout); return 0; }
+        else if (!strcmp(argv[i], "--no-textures")) textures = false;
         else if (!strcmp(argv[i], "--denoise")) denoise = true; else if (arg("--denoise-levels")) dnp.levels = (uint32_t)atoi(argv[++i]); else if (arg("--sigma-color")) dnp.sigma_color = (float)atof(argv[++i]); else if (arg("--sigma-plane")) dnp.sigma_plane = (float)atof(argv[++i]);
         else if (arg("--halo")) halo = (UINT)atoi(argv[++i]); else if (arg("--gpus")) gpus = atoi(argv[++i]); else if (arg("--devices")) devlist = argv[++i]; else if (arg("--gather")) gather = argv[++i];
         else if (arg("--out")) out = argv[++i]; else if (arg("--device")) device = atoi(argv[++i]); else if (!strcmp(argv[i], "--lambert")) lambert = true;
@@ -86,7 +90,7 @@ int main(int argc, char** argv) {
             else { std::stringstream ss(devlist); std::string t; while (std::getline(ss, t, ',')) devs.push_back(atoi(t.c_str())); }
             if ((int)devs.size() != gpus) { fprintf(stderr, "--devices must list %d ordinals\n", gpus); return 2; }
             Scene sc = scene == "cornell" ? MakeCornellBox() : scene == "sponza" ? MakeSponzaClass() : scene == "bistro" ? MakeBistroClass() : Scene();
-            if (scene == "obj") { std::vector<std::string> f; std::stringstream ss(objs); std::string t; while (std::getline(ss, t, ',')) f.push_back(t); sc = LoadObjScene(f, mtl); }
+            if (scene == "obj") { std::vector<std::string> f; std::stringstream ss(objs); std::string t; while (std::getline(ss, t, ',')) f.push_back(t); sc = LoadObjScene(f, mtl, textures); }
             if (scene == "cornell") lambert = true;
             MultiGpuFrame mg(devs, gather == "copy" ? MultiGpuFrame::Gather::COPY : MultiGpuFrame::Gather::RCCL, force_gather, only_rank);      // --force-gather: the collective also with one rank
             mg.SetScene(sc, (float)w / (float)h);
@@ -131,7 +135,7 @@ int main(int argc, char** argv) {
         if (scene == "cornell") { r.SetScene(MakeCornellBox()); lambert = true; }
         else if (scene == "sponza") r.SetScene(MakeSponzaClass());
         else if (scene == "bistro") r.SetScene(MakeBistroClass());
-        else { std::vector<std::string> f; std::stringstream ss(objs); std::string t; while (std::getline(ss, t, ',')) f.push_back(t); r.SetModels(f, mtl); }
+        else { std::vector<std::string> f; std::stringstream ss(objs); std::string t; while (std::getline(ss, t, ',')) f.push_back(t); r.SetLoadTextures(textures); r.SetModels(f, mtl); }
         r.Params().spp = spp; r.Params().max_bounces = bounces; r.Params().nee_samples = nee; r.Params().flags = lambert ? RTX_FLAG_LAMBERT_ONLY : (scene == "bistro" ? RTX_FLAG_TRANSMISSION : 0);
         if (restir) {
             r.SetMode(Renderer::Mode::ReSTIR);
@@ -145,7 +149,7 @@ int main(int argc, char** argv) {
         Scene inst0; bool have_inst0 = false;
         for (UINT f = 0; f < frames; f++) {
             if (spin != 0.0f && f > 0) {
-                if (!have_inst0) { inst0 = scene == "cornell" ? MakeCornellBox() : scene == "sponza" ? MakeSponzaClass() : scene == "bistro" ? MakeBistroClass() : Scene(); if (scene == "obj") { std::vector<std::string> fl; std::stringstream ss(objs); std::string t; while (std::getline(ss, t, ',')) fl.push_back(t); inst0 = LoadObjScene(fl, mtl); } have_inst0 = true; }
+                if (!have_inst0) { inst0 = scene == "cornell" ? MakeCornellBox() : scene == "sponza" ? MakeSponzaClass() : scene == "bistro" ? MakeBistroClass() : Scene(); if (scene == "obj") { std::vector<std::string> fl; std::stringstream ss(objs); std::string t; while (std::getline(ss, t, ',')) fl.push_back(t); inst0 = LoadObjScene(fl, mtl, false); } have_inst0 = true; }
                 if (inst0.instances.size() < 2) { fprintf(stderr, "--spin needs a scene with an instance 1\n"); return 2; }
                 r.SetInstanceTransform(1, spun(inst0, f));
                 if (!restir) rtx_clear_accum(r.Context(), w, h);               // a moved scene restarts the progressive accumulation (the ReSTIR frame reprojects instead)
