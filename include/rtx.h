@@ -274,6 +274,63 @@ int  rtx_set_material_map(rtx_ctx*, uint32_t material, uint32_t slot, int32_t te
    material has no map), texture id as uint bits or 0xFFFFFFFF); a miss gives (0, 0, 0, 0xFFFFFFFF).  rays8 may be NULL: the albedo depends on the hit record alone */
 int  rtx_debug_texture_sample(rtx_ctx*, uint32_t tex, const float* uv2, uint32_t n, float* out4);
 int  rtx_debug_albedo(rtx_ctx*, const float* rays8, const float* hits4, uint32_t n, float* out4);
+/* ENVIRONMENT LIGHTING (new; the reference's Miss.hlsl:3-11 returns black, so a ray that leaves the scene ends dark and only emissive triangles light anything: an extension,
+   unpinned by definition like strategy 3 and map_Kd, pinned by its own definition and properties in tests/test_env_ref.py / tests/test_env.py).  rtx_render and
+   rtx_render_adaptive only; rtx_render_v6_pass1 and rtx_render_restir ignore the environment, as they ignore maps and RTX_FLAG_TRANSMISSION.  With no environment bound every
+   launch, image, statistic and random-number sequence is what it was.
+   DATA.  Per context at most one environment: an N x N OCTAHEDRAL map of linear float32 RGB radiance, 1 <= N <= 2048 (N = 1: the constant sky), row j = v, column i = u, row-major;
+   a rotation env_to_world (the 16-float convention above, only the upper 3x3 R is used, its columns orthonormal within 1e-4 else RTX_ERR_INVALID, NULL = identity); a scale,
+   finite and >= 0, multiplied into the texels once on the host (float32 product, which must stay finite); flags: RTX_ENV_HIDDEN = primary rays that miss stay black (lighting without
+   a visible backdrop).  A texel component that is negative or not finite is RTX_ERR_INVALID.
+   MAPPING.  Y is up.  sgn(x) = x >= 0 ? 1 : -1 (so sgn(-0) = 1).  All arithmetic float32 in exactly the written order, no contraction; R[r][c] = env_to_world[c * 4 + r].
+   Direction d -> map:
+       e.x = (R[0][0] * d.x + R[1][0] * d.y) + R[2][0] * d.z ;  e.y, e.z likewise with R[.][1], R[.][2]                        (e = R^T d)
+       s = (|e.x| + |e.y|) + |e.z| ;  q = (e.x / s, e.y / s, e.z / s)
+       q.y >= 0 ?  (a, b) = (q.x, q.z)  :  a = (1 - |q.z|) * sgn(q.x), b = (1 - |q.x|) * sgn(q.z)
+       u = a * 0.5f + 0.5f ;  v = b * 0.5f + 0.5f
+       i = min((int)(u * (float)N), N - 1) ;  j = min((int)(v * (float)N), N - 1) ;  texel t = j * N + i
+       r2 = (q.x * q.x + q.y * q.y) + q.z * q.z ;  r3 = r2 * sqrtf(r2)
+   Map (u, v) -> direction, the inverse fold:
+       a = u * 2 - 1 ;  b = v * 2 - 1 ;  y = (1 - |a|) - |b|
+       y < 0 ?  a' = (1 - |b|) * sgn(a), b' = (1 - |a|) * sgn(b)  :  (a', b') = (a, b)
+       r2 = (a' * a' + y * y) + b' * b' ;  sr = sqrtf(r2) ;  r3 = r2 * sr ;  inv = 1 / sr ;  q = (a' * inv, y * inv, b' * inv)
+       d.x = (R[0][0] * q.x + R[0][1] * q.y) + R[0][2] * q.z ;  d.y, d.z likewise with R[1][.], R[2][.]                        (d = R q)
+   On this mapping d_omega = 4 du dv / r^3 with r = |q|, q on the L1 unit sphere (the midpoint sum of 4 / r^3 over a 2048^2 grid is 12.56637061 = 4 pi; r^3 lies in [0.192, 1]),
+   so the solid-angle pdf of a direction in texel t is
+       pdf = ((pmf[t] * (float)(N * N)) * 0.25f) * r3                                   (r3 of THAT DIRECTION, not of the texel centre)
+   Lookup is NEAREST: radiance is constant over a texel, so the pdf follows the radiance exactly up to r3.  Bilinear lookup is not part of this.
+   TABLES, built on the host at rtx_commit_scene, in double, sequentially in row-major order, each value rounded to float32 once.  With c = the texel after the scale:
+       rc3[j][i]: the inverse fold above in double at (u, v) = ((i + 0.5) / N, (j + 0.5) / N): r2 * sqrt(r2)
+       w[j][i] = (((c.r + c.g) + c.b) / 3) / rc3[j][i]
+       total = the running sum of w over all texels, row-major from 0 ;  pmf[j][i] = w[j][i] / total
+       rowacc[j][i] = the running sum of w[j][0 .. i] from 0 ;  rowsum[j] = rowacc[j][N - 1] ;  acc[j] = acc[j - 1] + rowsum[j] from 0
+       conditional[j][i] = rowacc[j][i] / rowsum[j] ;  marginal[j] = acc[j] / total
+   and then in each CDF the entries AT AND AFTER the last index with nonzero mass are 2.0f (a row of zero mass: all of its conditional entries).  The device texel is
+   (r, g, b, pmf), one 16-byte record: one read gives radiance and pdf.  Selection is "first index with xi < C[index]", the light CDF's binary search: a zero-mass texel is
+   never chosen and xi == 1.0f (RandomFloat can return it) lands on the last nonzero one.  An environment whose total weight is 0 has no NEE slot and its misses add zero: such a
+   scene runs the kernels and draws the random numbers of the scene without it.
+   TRANSPORT.  Environment NEE: ONE extra sample per shaded bounce in NEE slot index nee (after the nee = nee_samples triangle-light samples — 0 without lights —, before the
+   continuation).  Four draws in this order: row (marginal), column (that row's conditional), xi_u, xi_v;  u = ((float)i + xi_u) / (float)N, v = ((float)j + xi_v) / (float)N;
+   Ln = the direction of (u, v);  L and pmf are the CHOSEN texel's (i, j), r3 the decoded point's, pdf_env as above.  Rejected when dot(normal, Ln) < EPS or not pdf_env > 0.
+       mi = pdf_env / (pdf_env + P)   (P = the mixture pdf of Ln: balance heuristic, one sample each) ;  con_k = L_k * (thr_k * F_k) * (cos_x / pdf_env * mi), dropped if not finite or zero
+   Shadow ray: origin and tmin of the triangle-light sample, tmax = 10000 (the camera rays' "no limit").  Its rays count in rtx_stats.rays_shadow.
+   Miss at bounce b, d = the ray's direction:  b == 0: rad += L(d), or nothing with RTX_ENV_HIDDEN;  b >= 1: mi = prev_pdf / (pdf_env(d) + prev_pdf), mi = 1 when prev_pdf < 0
+   (the ray came through a transmission lobe), e_k = (L_k * thr_k) * mi, added if finite.  Triangle-light NEE and the emissive hit are untouched.
+   CALLS.  rtx_set_environment with rgb32f == NULL clears the environment (the other arguments are ignored).  Valid before the first commit and on a resident scene; needs
+   rtx_commit_scene again (rendering in between is RTX_ERR_STATE).  RTX_ERR_INVALID leaves the scene untouched and committed.  On a resident general scene a commit after this
+   call alone uploads tables only: no rebuild, no refit, rtx_stats.bvh_refits and rtx_debug_tree_hash unchanged.  A tiny scene (<= 64 triangles) runs on the general BVH path
+   while an environment is bound; the commit that crosses that line, either way, is a rebuild.  With an environment bound rtx_render runs the default separate kernels whatever
+   RTX_OPT_FUSED_BVH, RTX_OPT_SHADE_DENSE and RTX_OPT_SORT_MATERIALS say; RTX_OPT_COMPACT_STATE 0 and 1 both work.  rtx_save_scene_cache with an environment bound is
+   RTX_ERR_STATE (the file holds none); a loaded cache has no environment.  rtx_denoise is unchanged: misses pass through.  rtx_stats keeps its layout. */
+#define RTX_ENV_HIDDEN 1u
+int  rtx_set_environment(rtx_ctx*, const float* rgb32f /* N * N * 3; NULL clears */, uint32_t n, const float env_to_world[16] /* NULL = identity */, float scale, uint32_t flags);
+/* tests: the device's sampler and lookup, the functions k_shade runs.  RTX_ERR_STATE without a committed environment.
+   rtx_debug_env_sample: n seeds (2 uint32 each) -> 12 floats each: world direction(3), pdf, L(3), texel j * N + i as uint bits, the seed after the four draws (2 uint bits), 0, 0
+   (RTX_ERR_STATE for an environment without weight: nothing samples it).  rtx_debug_env_eval: n world directions -> 8 floats each: L(3), pdf, texel bits, r3, 0, 0.
+   rtx_debug_env_tables: the tables as the device holds them, N * N * 4 | N | N * N floats; any pointer may be NULL */
+int  rtx_debug_env_sample(rtx_ctx*, const uint32_t* seeds2, uint32_t n, float* out12);
+int  rtx_debug_env_eval(rtx_ctx*, const float* dirs3, uint32_t n, float* out8);
+int  rtx_debug_env_tables(rtx_ctx*, float* texels4, float* marginal, float* conditional);
 /* CreateAccelerationStructures (Renderer.cpp:893-946) + CollectEmissiveTriangles (:2123-2213) +
    CreateEmissiveTrianglesBuffer (:2237-2280): BVH build, emissive CDF, upload */
 int  rtx_commit_scene(rtx_ctx*);

@@ -54,6 +54,11 @@ int         rtxh_scene_texture_pixels(const rtxh_scene*, uint32_t i, const void*
 int         rtxh_scene_mesh_uvs(const rtxh_scene*, uint32_t i, const float** uv2, uint32_t* nidx);
 /* the image readers alone: width / height always, the pixels when capacity holds width * height * 4 bytes; RTX_ERR_INVALID + rtxh_last_error for a file they cannot read */
 int         rtxh_read_image(const char* path, void* rgba8, uint64_t capacity, uint32_t* width, uint32_t* height);
+/* high-dynamic-range images for rtx_set_environment (host/ImageIO.h): Radiance .hdr (RGBE, flat or new-style RLE, -Y H +X W) and colour .pfm, by content, as top-down float
+   RGB.  width / height always, the pixels when capacity holds width * height * 12 bytes; RTX_ERR_INVALID + rtxh_last_error for a missing, truncated or corrupt file */
+int         rtxh_read_hdr_image(const char* path, float* rgb32f, uint64_t capacity, uint32_t* width, uint32_t* height);
+/* a latitude-longitude image (width x height float RGB, row 0 = +Y) as the n x n octahedral map of rtx_set_environment: out holds n * n * 3 floats (LatLongToOctahedral) */
+int         rtxh_env_from_latlong(const float* rgb32f, uint32_t width, uint32_t height, uint32_t n, float* out);
 uint32_t    rtxh_scene_num_meshes(const rtxh_scene*);
 int         rtxh_scene_mesh(const rtxh_scene*, uint32_t i, const void** verts28, uint32_t* nverts,
                             const uint32_t** indices, uint32_t* nidx, const uint32_t** material_ids);

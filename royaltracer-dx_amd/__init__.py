@@ -48,6 +48,7 @@ OPT_SHARED_PRIMARY = 41
 OPT_DENOISE_LDS_STEP = 42
 TEX_SRGB = 1          # rtx_set_texture flag: the bytes are sRGB-encoded
 MAP_KD = 0            # rtx_set_material_map slot
+ENV_HIDDEN = 1        # rtx_set_environment flag: primary rays that miss stay black
 
 
 class RtxError(RuntimeError):
@@ -112,6 +113,10 @@ _sig("rtx_set_texture", C.c_int, _vp, _u32, _vp, _u32, _u32, _u32)
 _sig("rtx_set_material_map", C.c_int, _vp, _u32, _u32, C.c_int32)
 _sig("rtx_debug_texture_sample", C.c_int, _vp, _u32, _vp, _u32, _vp)
 _sig("rtx_debug_albedo", C.c_int, _vp, _vp, _vp, _u32, _vp)
+_sig("rtx_set_environment", C.c_int, _vp, _vp, _u32, _vp, C.c_float, _u32)
+_sig("rtx_debug_env_sample", C.c_int, _vp, _vp, _u32, _vp)
+_sig("rtx_debug_env_eval", C.c_int, _vp, _vp, _u32, _vp)
+_sig("rtx_debug_env_tables", C.c_int, _vp, _vp, _vp, _vp)
 _sig("rtx_set_camera", C.c_int, _vp, _fp, _fp)
 _sig("rtx_save_scene_cache", C.c_int, _vp, C.c_char_p)
 _sig("rtx_load_scene_cache", C.c_int, _vp, C.c_char_p)
@@ -211,6 +216,8 @@ _sig("rtxh_scene_texture", C.c_char_p, _vp, _u32)
 _sig("rtxh_scene_texture_pixels", C.c_int, _vp, _u32, C.POINTER(_vp), _u32p, _u32p)
 _sig("rtxh_scene_mesh_uvs", C.c_int, _vp, _u32, C.POINTER(_vp), _u32p)
 _sig("rtxh_read_image", C.c_int, C.c_char_p, _vp, C.c_uint64, _u32p, _u32p)
+_sig("rtxh_read_hdr_image", C.c_int, C.c_char_p, _vp, C.c_uint64, _u32p, _u32p)
+_sig("rtxh_env_from_latlong", C.c_int, _vp, _u32, _u32, _u32, _vp)
 _sig("rtxh_scene_num_meshes", _u32, _vp)
 _sig("rtxh_scene_mesh", C.c_int, _vp, _u32, C.POINTER(_vp), _u32p, C.POINTER(_vp), _u32p, C.POINTER(_vp))
 _sig("rtxh_scene_num_instances", _u32, _vp)
@@ -459,6 +466,28 @@ def read_image(path):
     return out
 
 
+def read_hdr_image(path):
+    """the host layer's high-dynamic-range readers (Radiance .hdr: RGBE, flat or new-style RLE, -Y H +X W; colour .pfm, either byte order) -> (H, W, 3) float32, row 0 on top"""
+    w, h = _u32(), _u32()
+    if lib.rtxh_read_hdr_image(str(path).encode(), None, 0, C.byref(w), C.byref(h)) != RTX_OK:
+        raise RtxError("read_hdr_image: " + lib.rtxh_last_error().decode())
+    out = np.zeros((h.value, w.value, 3), np.float32)
+    lib.rtxh_read_hdr_image(str(path).encode(), _ptr(out), out.nbytes, C.byref(w), C.byref(h))
+    return out
+
+
+def latlong_to_octahedral(img, n):
+    """a latitude-longitude image (H, W, 3) float32 — row 0 = +Y, column centre phi = 2 pi (x + 0.5) / W, direction (sin t sin p, cos t, -sin t cos p) — as the (n, n, 3)
+    octahedral map Context.set_environment takes: every texel the mean of S x S nearest lookups, S = clamp(ceil(W / (2 n)), 2, 16)"""
+    a = _f32(img)
+    if a.ndim != 3 or a.shape[2] != 3:
+        raise RtxError("latlong_to_octahedral: the image must be (H, W, 3) float32")
+    out = np.zeros((int(n), int(n), 3), np.float32)
+    if lib.rtxh_env_from_latlong(_ptr(a), a.shape[1], a.shape[0], int(n), _ptr(out)) != RTX_OK:
+        raise RtxError("latlong_to_octahedral: " + lib.rtxh_last_error().decode())
+    return out
+
+
 def bvh_refit_check(before, after):
     a, b = _f32(before).reshape(-1, 9), _f32(after).reshape(-1, 9)
     return lib.rtxh_bvh_refit_check(_ptr(a), _ptr(b), len(a))
@@ -638,6 +667,44 @@ class Context:
             if t is not None and t >= 0 and t in ids:
                 self.set_material_map(mat, ids[t])
 
+    def set_environment(self, img, to_world=None, scale=1.0, hidden=False):
+        """environment lighting: img = (N, N, 3) float32 octahedral map of linear radiance (row = v, column = u; latlong_to_octahedral makes one), or None to clear;
+        to_world = 16 floats (column-vector matrix, only its orthonormal upper 3x3 is used) or None = identity; scale multiplies the radiance; hidden: camera rays that
+        miss stay black.  Needs commit()"""
+        if img is None:
+            self._ck(lib.rtx_set_environment(self._h, None, 0, None, 1.0, 0), "rtx_set_environment")
+            self._env_n = 0
+            return
+        a = _f32(img)
+        if a.ndim != 3 or a.shape[0] != a.shape[1] or a.shape[2] != 3:
+            raise RtxError("set_environment: the map must be (N, N, 3) float32")
+        m = _f32(to_world).reshape(16) if to_world is not None else None
+        self._ck(lib.rtx_set_environment(self._h, _ptr(a), a.shape[0], _ptr(m) if m is not None else None, float(scale), ENV_HIDDEN if hidden else 0), "rtx_set_environment")
+        self._env_n = a.shape[0]
+
+    def env_tables(self):
+        """the environment's tables as the device holds them -> texels (N, N, 4) float32 (r, g, b, pmf), marginal (N,), conditional (N, N)"""
+        n = getattr(self, "_env_n", 0)
+        if not n:
+            raise RtxError("env_tables: no environment set through this Context")
+        tex, marg, cond = np.zeros((n, n, 4), np.float32), np.zeros(n, np.float32), np.zeros((n, n), np.float32)
+        self._ck(lib.rtx_debug_env_tables(self._h, _ptr(tex), _ptr(marg), _ptr(cond)), "rtx_debug_env_tables")
+        return tex, marg, cond
+
+    def env_sample(self, seeds):
+        """the device's environment sampler at (n, 2) uint32 seeds -> (n, 12) float32: world direction, pdf, L, texel bits, seed after the four draws (bits), 0, 0"""
+        s = np.ascontiguousarray(seeds, dtype=np.uint32).reshape(-1, 2)
+        out = np.zeros((len(s), 12), np.float32)
+        self._ck(lib.rtx_debug_env_sample(self._h, _ptr(s), len(s), _ptr(out)), "rtx_debug_env_sample")
+        return out
+
+    def env_eval(self, dirs):
+        """the device's environment lookup at (n, 3) world directions -> (n, 8) float32: L, pdf, texel bits, r3, 0, 0"""
+        d = _f32(dirs).reshape(-1, 3)
+        out = np.zeros((len(d), 8), np.float32)
+        self._ck(lib.rtx_debug_env_eval(self._h, _ptr(d), len(d), _ptr(out)), "rtx_debug_env_eval")
+        return out
+
     def commit(self):
         self._ck(lib.rtx_commit_scene(self._h), "rtx_commit_scene")
 
@@ -664,6 +731,9 @@ class Context:
         for mesh, o2w in scene.instances:
             self.add_instance(mesh, o2w)
         self.bind_maps(scene)
+        env = getattr(scene, "environment", None)                 # an (N, N, 3) map, or a dict of set_environment's arguments (img, to_world, scale, hidden)
+        if env is not None:
+            self.set_environment(**env) if isinstance(env, dict) else self.set_environment(env)
         self.commit()
         self.set_camera(*scene.view_proj(aspect))
 

@@ -90,6 +90,21 @@ static int sync_textures(rtx_ctx* c, bool renumbered) {
     return RTX_OK;
 }
 
+// The environment's tables follow the host's map (SceneHost::env): built in double on the host (rtx_env_host.cpp), uploaded; no kernel runs.  What the kernels see of
+// them is set by finalise_scene.
+static int sync_environment(rtx_ctx* c) {
+    SceneHost& H = c->host; rtx_ctx::Scene& S = c->scene;
+    S.built.env_active = H.env.n != 0;
+    if (!H.env_dirty) return RTX_OK;
+    H.env_dirty = false;
+    if (!H.env.n) { S.d_env_tex.release(); S.d_env_marg.release(); S.d_env_cond.release(); S.env_total = 0.0; return RTX_OK; }
+    EnvTables T; env_build_tables(H.env, T);
+    int r;
+    if ((r = upload(c, S.d_env_tex, T.texels4)) || (r = upload(c, S.d_env_marg, T.marginal)) || (r = upload(c, S.d_env_cond, T.conditional))) return r;
+    S.env_total = T.total;
+    return RTX_OK;
+}
+
 // a device array that only grows at its end: capacity in steps of 1.5 x, the `used` bytes survive a reallocation
 static int grow_keep(rtx_ctx* c, DevBuf& b, size_t used, size_t need) {
     if (need <= b.bytes && b.p) return RTX_OK;
@@ -377,7 +392,9 @@ int rtx_commit_scene(rtx_ctx* c) {
     // On the GPU: a scene that is already resident and not a tiny one (whose pre-test records depend on world positions).
     // a tiny scene leaves its pre-test records for the general path while a texture map is active and returns to them afterwards: the commit that crosses that line rebuilds
     {   size_t ntri_all = 0; for (const InstHost& in : c->host.insts) ntri_all += c->host.meshes[in.mesh].idx.size() / 3;
-        if (c->host.tex_dirty && ntri_all <= kSmallSceneMaxTris && c->host.maps_active() != c->scene.built.maps_active) c->host.topo_dirty = true; }
+        if (c->host.tex_dirty && ntri_all <= kSmallSceneMaxTris && c->host.maps_active() != c->scene.built.maps_active) c->host.topo_dirty = true;
+        // ... and so it does while an environment is bound
+        if (c->host.env_dirty && ntri_all <= kSmallSceneMaxTris && (c->host.env.n != 0) != c->scene.built.env_active) c->host.topo_dirty = true; }
     bool build = !(c->opt.gpu_refit && gpu_refittable(c) && !c->host.topo_dirty);
     // a tiny scene whose last instance was just shown again returns to its pre-test records: a host refit (SceneHost::build derives them from world positions)
     const BuiltScene& B0 = c->scene.built;
@@ -385,7 +402,8 @@ int rtx_commit_scene(rtx_ctx* c) {
     bool flipped = false;                                  // a resident scene's visibility differs from the caller's
     for (size_t ii = 0; ii < c->host.insts.size() && !flipped; ii++) flipped = (ii < B0.inst_hidden.size() && B0.inst_hidden[ii] != 0u) != c->host.is_hidden(ii);
     // only UVs, textures or map ids changed on a resident general scene: tables are uploaded, nothing is refitted (rtx_stats.bvh_refits and the tree stay)
-    const bool tex_only = !build && c->host.tex_dirty && c->host.only_maps_changed(B0);
+    // ... and likewise when only the environment changed
+    const bool tex_only = !build && (c->host.tex_dirty || c->host.env_dirty) && c->host.only_maps_changed(B0);
     const bool probe = (build || !flipped) && !tex_only;   // the any-hit order is a property of the tree and the lights' whereabouts: not re-probed because something was hidden or shown
     if (!build && !tex_only) {
         if ((r = refit_resident(c, deform))) return r;
@@ -402,6 +420,7 @@ int rtx_commit_scene(rtx_ctx* c) {
     }
     c->host.dirty_meshes.clear();
     if ((r = sync_textures(c, build))) return r;
+    if ((r = sync_environment(c))) return r;
     r = finalise_scene(c);
     if (r == RTX_OK && c->scene.dev_built && c->scene.n_nodes8 && probe) {          // the visiting order of any-hit rays, probed on the device (the host probe replays its mirror of the tree)
         uint32_t best = 0;
@@ -419,6 +438,7 @@ int rtx_save_scene_cache(rtx_ctx* c, const char* path) {
     if (!c->committed) { c->err = "save_scene_cache: scene not committed"; return RTX_ERR_STATE; }
     if (c->scene.host_mirror_stale) { c->err = "save_scene_cache: the per-triangle records were re-derived on the GPU after rtx_update_mesh_vertices and the host holds no current copy; commit with RTX_OPT_DEFORM_REBUILD 1 (host builder) to save a cache"; return RTX_ERR_STATE; }
     if (c->scene.built.any_hidden) { c->err = "save_scene_cache: an instance is hidden (rtx_set_instance_visible): the device's boxes and triangle records leave it out and the file format holds no visibility; show every instance and commit to save a cache"; return RTX_ERR_STATE; }
+    if (c->host.env.n) { c->err = "save_scene_cache: an environment is bound (rtx_set_environment) and the file format holds no environment; clear it and commit to save a cache"; return RTX_ERR_STATE; }
     if (c->host.any_map()) { c->err = "save_scene_cache: a material has a texture map (rtx_set_material_map) and the file format holds no texels; unmap every material and commit to save a cache"; return RTX_ERR_STATE; }
     if (c->scene.dev_built) { c->err = "save_scene_cache: the tree was built on the GPU (RTX_OPT_GPU_BUILD) and has no host mirror; commit with the host builder to save a cache"; return RTX_ERR_STATE; }
     if (!save_scene_cache(c->host, c->scene.built, path, c->err)) return RTX_ERR_INVALID;
@@ -434,6 +454,8 @@ int rtx_load_scene_cache(rtx_ctx* c, const char* path) {
     if (r) return r;
     c->host.tex_dirty = true;                  // (another scene: no textures, no maps)
     if ((r = sync_textures(c, true))) return r;
+    c->host.env = EnvHost{}; c->host.env_dirty = true;      // (another scene: no environment)
+    if ((r = sync_environment(c))) return r;
     return finalise_scene(c);
 }
 
@@ -466,6 +488,10 @@ static int finalise_scene(rtx_ctx* c) {
     s.total_weight = B.total_weight;
     // texture maps: the sampler's tables whenever there are textures; UVs and map ids only while a map is active (then k_shade<.., TEX> runs, rtx_render.hip)
     s.tex_desc = (const TexDesc*)c->scene.d_tex_desc.p; s.ntex = c->scene.ntex; s.texels = (const uint32_t*)c->scene.d_texels.p; s.tex_lut = (const float*)c->scene.d_tex_lut.p;
+    // environment lighting: env_n says one is bound (the separate default kernels run), env_tex that it has weight (k_shade<.., ENV> runs)
+    s.env_n = c->host.env.n; s.env_flags = c->host.env.flags; memcpy(s.env_rot, c->host.env.rot, sizeof(s.env_rot));
+    const bool env_lit = s.env_n && c->scene.env_total > 0.0;
+    s.env_tex = env_lit ? (const F4*)c->scene.d_env_tex.p : nullptr; s.env_marg = env_lit ? (const float*)c->scene.d_env_marg.p : nullptr; s.env_cond = env_lit ? (const float*)c->scene.d_env_cond.p : nullptr;
     s.tri_uv = B.maps_active ? (const float*)c->scene.d_tri_uv.p : nullptr; s.map_kd = B.maps_active ? (const int32_t*)c->scene.d_map_kd.p : nullptr;
     // LDS budget per workgroup: stack + top of tree + first triangles, kept <= 64 KiB
     // exact bound of the 8-wide tree, no slack: a level adds ONE entry (the rest of its hit siblings) and only where a node has >= 2 internal

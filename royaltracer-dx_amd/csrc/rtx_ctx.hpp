@@ -5,6 +5,7 @@
 //   rtx_render.hip       rtx_render (the wavefront path tracer), render_frame and finish_render
 //   rtx_adaptive.hip     rtx_render_adaptive: passes of render_frame over the chunks that have not converged
 //   rtx_denoise.hip      rtx_denoise and the reads of the denoised image
+//   rtx_env.hip          environment lighting: rtx_set_environment and its three debug probes
 //   rtx_texture.hip      texture maps: rtx_set_mesh_uvs, rtx_set_texture, rtx_set_material_map and their two debug probes
 //   rtx_restir_api.hip   the ReSTIR frames, their work lists and lanes, the history / halo exchange between shards
 //   rtx_debug.hip        the rtx_debug_* entry points
@@ -122,6 +123,8 @@ struct rtx_ctx {
         // diffuse texture maps (sync_textures, rtx_commit.hip): descriptors, the texel pool and the per-material map ids follow the host's tables at every commit that
         // changed them; the two byte -> float tables once; tri_uv only while a map is active (BuiltScene::maps_active), rebuilt when UVs or the triangle numbering changed
         DevBuf d_tri_uv, d_map_kd, d_tex_desc, d_texels, d_tex_lut; bool tri_uv_valid = false; uint32_t ntex = 0;
+        // environment lighting (sync_environment, rtx_commit.hip): the tables of the bound map, rebuilt by the commit after rtx_set_environment; env_total = their weight sum
+        DevBuf d_env_tex, d_env_marg, d_env_cond; double env_total = 0.0;
     } scene;
 
     // ---- the path tracer's frame (rtx_render.hip) ----

@@ -83,6 +83,24 @@ __global__ __launch_bounds__(kBlock) void k_dbg_albedo(DevScene sc, const F4* __
     }
     out[i] = r;
 }
+// the environment's sampler and lookup (rtx_env.hpp), as k_shade<.., ENV> runs them (the marginal CDF from global memory: the same values as its LDS copy)
+__global__ __launch_bounds__(kBlock) void k_dbg_env_sample(DevScene sc, const uint32_t* __restrict__ seeds2, uint32_t n, F4* __restrict__ out) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    uint32_t s0 = seeds2[2 * (size_t)i], s1 = seeds2[2 * (size_t)i + 1];
+    f3 Ln;
+    const EnvEval E = env_sample(sc, sc.env_marg, s0, s1, Ln);
+    out[3 * (size_t)i] = {Ln.x, Ln.y, Ln.z, E.pdf};
+    out[3 * (size_t)i + 1] = {E.L.x, E.L.y, E.L.z, u2f(E.texel)};
+    out[3 * (size_t)i + 2] = {u2f(s0), u2f(s1), 0.0f, 0.0f};
+}
+__global__ __launch_bounds__(kBlock) void k_dbg_env_eval(DevScene sc, const float* __restrict__ dirs3, uint32_t n, F4* __restrict__ out) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const EnvEval E = env_eval(sc, mk3(dirs3[3 * (size_t)i], dirs3[3 * (size_t)i + 1], dirs3[3 * (size_t)i + 2]));
+    out[2 * (size_t)i] = {E.L.x, E.L.y, E.L.z, E.pdf};
+    out[2 * (size_t)i + 1] = {u2f(E.texel), E.r3, 0.0f, 0.0f};
+}
 __global__ void k_dbg_tea(uint32_t s0, uint32_t s1, uint32_t n, float* __restrict__ out, uint32_t* __restrict__ seed_out) {
     if (threadIdx.x || blockIdx.x) return;
     for (uint32_t i = 0; i < n; i++) out[i] = tea_next(s0, s1);

@@ -21,9 +21,11 @@ namespace rtx {
 // (Phase 2 of k_bounce_bvh is a copy of this body without the compact state, the sort keys and MixView — calling it there measured slower: change the two together.)
 // TEX: some material has a diffuse texture map (rtx_texture.hpp): Kd' / PI of the hit is formed once, after surface(), and handed to the mixture of the NEE samples and of the
 // continuation — three floats live across them, no per-lane copy of the material.  Lanes whose material has no map keep its KdPi.
-template <bool LAMBERT, bool TEX = false>
+// ENV: an environment with weight is committed (rtx_env.hpp): a lane whose ray missed loads its path state and adds the map's radiance (env_miss), and every shading
+// point casts one more NEE sample, towards the map, into shadow queue `nee` (env_marg: the marginal CDF, in LDS where k_shade found room).  ENV = false is the code as it was.
+template <bool LAMBERT, bool TEX = false, bool ENV = false>
 __device__ __forceinline__ void shade_item(const DevScene& sc, const DevFrame& f, const DevPaths& p, uint32_t bounce, uint32_t nee, bool last, size_t qb,
-                                           const uint32_t* __restrict__ myq, uint32_t* __restrict__ mynext, uint32_t* s_cnt, bool valid, uint32_t qi, Prof* pf, const float* lds_cdf = nullptr, const LightGPU* lds_lights = nullptr, const MatGPU* lds_mats = nullptr) {
+                                           const uint32_t* __restrict__ myq, uint32_t* __restrict__ mynext, uint32_t* s_cnt, bool valid, uint32_t qi, Prof* pf, const float* lds_cdf = nullptr, const LightGPU* lds_lights = nullptr, const MatGPU* lds_mats = nullptr, const float* env_marg = nullptr) {
     PathState S; S.pid = 0; S.o = mk3(0, 0, 0); S.d = mk3(0, 0, 1); S.thr = mk3(0, 0, 0); S.prev_pdf = 1.0f; S.s0 = S.s1 = 0;
     Surf sf; sf.mat = 0; sf.normal = mk3(0, 0, 1); sf.pos = mk3(0, 0, 0);
     bool shading = false;
@@ -49,6 +51,7 @@ __device__ __forceinline__ void shade_item(const DevScene& sc, const DevFrame& f
                 else { shading = true; if (TEX) kdv = tex_kdpi(sc, m, sf.mat, prim, h.y, h.z); }
             }
         }
+        else if (ENV) { PathState M = load_path_stream(p, src); M.pid = pid; env_miss(sc, p, M, bounce); }      // the ray left the scene
     }
     const f3 outgoing = -S.d, pos = sf.pos;
     const MatGPU* mp = mats + (shading ? sf.mat : 0u);
@@ -69,6 +72,14 @@ __device__ __forceinline__ void shade_item(const DevScene& sc, const DevFrame& f
         if (push) { PF_COUNT(4); }
         const size_t seg = (size_t)j * f.qcap * gridDim.x + qb;           // NEE slot j, this workgroup's sub-queue
         const uint32_t slot = block_push(push, &s_cnt[1 + j]);
+        if (push) { st_stream(p.sh_o + seg + slot, so); st_stream(p.sh_d + seg + slot, sd); st_stream(p.sh_c + seg + slot, F4{con.x, con.y, con.z, u2f(S.pid)}); }
+    }
+    if (ENV) {                                                            // the environment's sample: NEE slot `nee`, after the triangle lights'
+        bool push = false;
+        F4 so = {0, 0, 0, 0}, sd = {0, 0, 0, 0}; f3 con = mk3(0, 0, 0);
+        if (shading) push = env_nee_sample(sc, env_marg, *mp, f.flags, S, pos, normal, outgoing, so, sd, con, eta_p, mv, kdpi);
+        const size_t seg = (size_t)nee * f.qcap * gridDim.x + qb;
+        const uint32_t slot = block_push(push, &s_cnt[1 + nee]);
         if (push) { st_stream(p.sh_o + seg + slot, so); st_stream(p.sh_d + seg + slot, sd); st_stream(p.sh_c + seg + slot, F4{con.x, con.y, con.z, u2f(S.pid)}); }
     }
     PF_MARK(4);
@@ -121,13 +132,26 @@ __host__ __device__ inline void shade_lds_plan(uint32_t nlights, uint32_t nmat, 
 #define RTX_SHADE_WAVES 7          // waves per SIMD k_shade is compiled for: 7 = 72 VGPRs + 1 spilled (GGX) / 66 (Lambert); uncapped: 94 VGPRs, 5 waves; 6: 80, no spills; 8: 64, 9 spilled.
                                    // k_shade per frame, C3 / C5: 7.42 / 8.77 ms uncapped, 6.93 / 8.54 at 6, 7.50 / 8.83 at 8 (round 2); round 4: 6.27 / 6.85 at 6, 6.28 / 6.72 at 7
 #endif
-template <bool SORT, bool LAMBERT, bool TEX = false>     // LAMBERT: RTX_FLAG_LAMBERT_ONLY as a compile-time constant (no GGX / transmission code in that instantiation); TEX: texture maps (shade_item)
-__global__ __launch_bounds__(kBlock, RTX_SHADE_WAVES) void k_shade(DevScene sc, DevFrame f_in, DevPaths p, uint32_t bounce,
+// the marginal CDF of the environment (<= 8 KB) behind the light list and the material table in k_shade<.., ENV>'s dynamic LDS, where the three stay within kShadeLds; else it is
+// read from global memory like the conditional rows.  (A/B build: -DRTX_ENV_MARG_GLOBAL keeps it in global memory always.)
+__host__ __device__ inline uint32_t shade_env_lds(uint32_t lights_bytes, uint32_t mats_bytes, uint32_t env_n) {
+#ifdef RTX_ENV_MARG_GLOBAL
+    return 0u;
+#else
+    return (env_n && lights_bytes + mats_bytes + env_n * 4u <= kShadeLds) ? ((env_n * 4u + 15u) & ~15u) : 0u;
+#endif
+}
+#ifndef RTX_SHADE_WAVES_ENV
+#define RTX_SHADE_WAVES_ENV 6      // ... of the ENV instantiations: the environment's sample lives beside the view terms of the mixture, and at 7 waves (72 VGPRs) the GGX forms spill 4 / 8 registers to scratch
+#endif
+template <bool SORT, bool LAMBERT, bool TEX = false, bool ENV = false>     // LAMBERT: RTX_FLAG_LAMBERT_ONLY as a compile-time constant (no GGX / transmission code in that instantiation); TEX: texture maps, ENV: environment lighting (shade_item)
+__global__ __launch_bounds__(kBlock, (ENV ? RTX_SHADE_WAVES_ENV : RTX_SHADE_WAVES)) void k_shade(DevScene sc, DevFrame f_in, DevPaths p, uint32_t bounce,
                                                   const uint32_t* __restrict__ queue, const uint32_t* __restrict__ qcount,
                                                   uint32_t* __restrict__ next_queue, uint32_t* __restrict__ next_count,
                                                   uint32_t* __restrict__ shcounts /* [nee][gridDim.x] */) {
     const DevFrame f = frame_with_lambert<LAMBERT>(f_in);
-    __shared__ uint32_t s_cnt[1 + kMaxNee];                 // [0] next-queue length, [1 + j] shadow queue j length
+    constexpr uint32_t kSlots = kMaxNee + (ENV ? 1u : 0u);  // (the environment's slot follows the nee_samples <= kMaxNee triangle-light slots)
+    __shared__ uint32_t s_cnt[1 + kMaxNee + (ENV ? 4u : 0u)];     // [0] next-queue length, [1 + j] shadow queue j length (ENV: one slot more, in a 16-byte step: the static LDS precedes the dynamic region, whose float4 reads need their alignment)
     __shared__ uint32_t s_pid[SORT ? kSortChunk : 1], s_sorted[SORT ? kSortChunk : 1], s_hist[SORT ? kSortKeys : 1];
     __shared__ uint8_t s_key[SORT ? kSortChunk : 1];
     // (round 5) a light list of <= 256 entries in LDS — the records (80 B each) and behind them the CDF: NEE's binary search is 1-8 DEPENDENT reads per sample (street scene:
@@ -140,7 +164,7 @@ __global__ __launch_bounds__(kBlock, RTX_SHADE_WAVES) void k_shade(DevScene sc, 
         for (uint32_t i = threadIdx.x; i < sc.nlights * 5u; i += kBlock) s_lights[i] = ((const F4*)sc.lights)[i];
         for (uint32_t i = threadIdx.x; i < sc.nlights; i += kBlock) s_cdf[i] = sc.cdf[i];
     }
-    if (threadIdx.x <= kMaxNee) s_cnt[threadIdx.x] = 0;
+    if (threadIdx.x <= kSlots) s_cnt[threadIdx.x] = 0;
     __syncthreads();
     const float* lds_cdf = cdf_in_lds ? s_cdf : nullptr;
     const LightGPU* lds_lights = cdf_in_lds ? (const LightGPU*)s_lights : nullptr;
@@ -150,6 +174,16 @@ __global__ __launch_bounds__(kBlock, RTX_SHADE_WAVES) void k_shade(DevScene sc, 
         F4* dst = (F4*)((char*)s_lights + lights_bytes);
         for (uint32_t i = threadIdx.x; i < sc.nmat * 10u; i += kBlock) dst[i] = ((const F4*)sc.mats)[i];
         lds_mats = (const MatGPU*)dst;
+    }
+    const float* env_marg = nullptr;
+    if (ENV) {
+        env_marg = sc.env_marg;
+        if (shade_env_lds(lights_bytes, mats_bytes, sc.env_n)) {
+            float* dst = (float*)((char*)s_lights + lights_bytes + mats_bytes);
+            for (uint32_t i = threadIdx.x; i < sc.env_n; i += kBlock) dst[i] = sc.env_marg[i];
+            env_marg = dst;
+        }
+        __syncthreads();                                    // the copy (and the material table's above) is read by every wave
     }
     const uint32_t n = qcount[blockIdx.x];
     const uint32_t nee = sc.nlights ? f.nee_samples : 0u;
@@ -184,7 +218,7 @@ __global__ __launch_bounds__(kBlock, RTX_SHADE_WAVES) void k_shade(DevScene sc, 
         }
         for (uint32_t base = threadIdx.x & ~63u; base < cn; base += kBlock) {
             const uint32_t i = base + (threadIdx.x & 63u);
-            shade_item<LAMBERT, TEX>(sc, f, p, bounce, nee, last, qb, myq, mynext, s_cnt, i < cn, cb + (SORT ? s_sorted[i] : i), pf, lds_cdf, lds_lights, lds_mats);
+            shade_item<LAMBERT, TEX, ENV>(sc, f, p, bounce, nee, last, qb, myq, mynext, s_cnt, i < cn, cb + (SORT ? s_sorted[i] : i), pf, lds_cdf, lds_lights, lds_mats, env_marg);
         }
         if (SORT) __syncthreads();                              // the next chunk overwrites the LDS buffers
     }
@@ -192,7 +226,7 @@ __global__ __launch_bounds__(kBlock, RTX_SHADE_WAVES) void k_shade(DevScene sc, 
     PF_FLUSH;
     __syncthreads();
     if (threadIdx.x == 0) next_count[blockIdx.x] = s_cnt[0];
-    if (threadIdx.x >= 1 && threadIdx.x <= nee) shcounts[(size_t)(threadIdx.x - 1) * gridDim.x + blockIdx.x] = s_cnt[threadIdx.x];
+    if (threadIdx.x >= 1 && threadIdx.x <= nee + (ENV ? 1u : 0u)) shcounts[(size_t)(threadIdx.x - 1) * gridDim.x + blockIdx.x] = s_cnt[threadIdx.x];
 }
 
 // k_shade with the HITS of the sub-queue compacted before they are shaded (RTX_OPT_SHADE_DENSE).  In an open scene a large part of a bounce's rays leaves the scene

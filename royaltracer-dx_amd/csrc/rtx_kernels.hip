@@ -170,6 +170,15 @@ void launch_shade(hipStream_t st, const DevScene& sc, const DevFrame& f, const D
     dispatch_bool((f.flags & 1u) != 0u, [&](auto lam) {
         constexpr bool LL = decltype(lam)::value;
         // a texture map is active: the default kernel's TEX form, whatever RTX_OPT_SHADE_DENSE / RTX_OPT_SORT_MATERIALS say (the rejected variants get no textured copy)
+        // an environment is bound: the default kernel too, in its ENV form when the map has weight (a black map adds nothing and casts nothing: the kernels without it)
+        if (sc.env_n) {
+            uint32_t lb, mb; shade_lds_plan(sc.nlights, sc.nmat, false, lb, mb);
+            dispatch_bool(sc.tri_uv != nullptr, [&](auto tex) { dispatch_bool(sc.env_tex != nullptr, [&](auto env) {
+                constexpr bool EE = decltype(env)::value;
+                hipLaunchKernelGGL((k_shade<false, LL, decltype(tex)::value, EE>), dim3(f.nblocks), dim3(kBlock), (size_t)lb + mb + (EE ? shade_env_lds(lb, mb, sc.env_n) : 0u), st, sc, f, p, bounce, queue, qcount, next_queue, next_count, shcounts);
+            }); });
+            return;
+        }
         if (sc.tri_uv) { hipLaunchKernelGGL((k_shade<false, LL, true>), dim3(f.nblocks), dim3(kBlock), shade_lds_bytes(sc, false), st, sc, f, p, bounce, queue, qcount, next_queue, next_count, shcounts); return; }
         if (sc.shade_dense && !sc.sort_materials) hipLaunchKernelGGL((k_shade_dense<LL>), dim3(f.nblocks), dim3(kBlock), 0, st, sc, f, p, bounce, queue, qcount, next_queue, next_count, shcounts);
         else dispatch_bool(sc.sort_materials != 0u, [&](auto sort) {
@@ -314,6 +323,12 @@ void launch_dbg_tex_sample(hipStream_t st, const DevScene& sc, uint32_t tex, con
 }
 void launch_dbg_albedo(hipStream_t st, const DevScene& sc, const F4* hits, uint32_t n, F4* out) {
     hipLaunchKernelGGL(k_dbg_albedo, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, sc, hits, n, out);
+}
+void launch_dbg_env_sample(hipStream_t st, const DevScene& sc, const uint32_t* seeds2, uint32_t n, F4* out) {
+    hipLaunchKernelGGL(k_dbg_env_sample, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, sc, seeds2, n, out);
+}
+void launch_dbg_env_eval(hipStream_t st, const DevScene& sc, const float* dirs3, uint32_t n, F4* out) {
+    hipLaunchKernelGGL(k_dbg_env_eval, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, sc, dirs3, n, out);
 }
 void launch_dbg_tea(hipStream_t st, uint32_t s0, uint32_t s1, uint32_t n, float* out, uint32_t* seed_out) {
     hipLaunchKernelGGL(k_dbg_tea, dim3(1), dim3(64), 0, st, s0, s1, n, out, seed_out);

@@ -39,6 +39,13 @@ struct DevScene {
     const TexDesc* tex_desc; uint32_t ntex;
     const uint32_t* texels;             // the texel pool, RGBA8 (r in the low byte)
     const float* tex_lut;               // byte -> float: [0, 256) linear, [256, 512) sRGB
+    // environment lighting (rtx_env.hpp).  env_n = 0: none bound.  env_tex is nullptr unless the bound map has weight: a scene without one, or with an all-black one, launches the
+    // kernels it always launched (launch_shade picks k_shade<.., ENV> by this pointer)
+    const F4* env_tex;                  // N x N texels (r, g, b, pmf), row-major
+    const float* env_marg;              // marginal CDF, N rows
+    const float* env_cond;              // conditional CDF, N entries per row
+    uint32_t env_n, env_flags;          // RTX_ENV_*
+    float env_rot[9];                   // env_to_world's upper 3x3, [row * 3 + column]
 };
 
 // one sample batch of one frame
@@ -241,6 +248,10 @@ void launch_dbg_bsdf_eval(hipStream_t, const DevScene&, uint32_t mat, uint32_t f
 void launch_dbg_bsdf_sample(hipStream_t, const DevScene&, uint32_t mat, uint32_t flags, const float* in8, uint32_t n, float* out8);
 void launch_dbg_tex_sample(hipStream_t, const DevScene&, uint32_t tex, const float* uv2, uint32_t n, F4* out);      // tex_sample at n (s, t) pairs -> (r, g, b, 0)
 void launch_dbg_albedo(hipStream_t, const DevScene&, const F4* hits, uint32_t n, F4* out);                         // tex_albedo at n hit records -> (Kd', texture id bits or 0xFFFFFFFF)
+// the environment's device functions (rtx_env.hpp): env_sample at n seeds -> 3 F4 per seed (world direction, pdf | L, texel bits | seed after the four draws, 0, 0);
+// env_eval at n directions -> 2 F4 per direction (L, pdf | texel bits, r3, 0, 0).  sc.env_* must be set (the probes set them for a black map too)
+void launch_dbg_env_sample(hipStream_t, const DevScene&, const uint32_t* seeds2, uint32_t n, F4* out);
+void launch_dbg_env_eval(hipStream_t, const DevScene&, const float* dirs3, uint32_t n, F4* out);
 void launch_dbg_tea(hipStream_t, uint32_t s0, uint32_t s1, uint32_t n, float* out, uint32_t* seed_out);
 void launch_dbg_primary(hipStream_t, const DevFrame&, const CameraGPU* cam, uint32_t sample_id, F4* rays);
 

@@ -177,10 +177,11 @@ int render_frame(rtx_ctx* c, const rtx_params* p, const DevFrame& f_real, uint32
     const uint32_t sample_first = lp ? lp->sample_first : p->sample_base;
 
     // ---- 2. plan the batches ----
-    const uint32_t nee = c->dsc.nlights ? p->nee_samples : 0;
+    // NEE slots: nee_samples towards the triangle lights, then one towards an environment that has weight (k_shade<.., ENV>: shadow queue, counters and launch follow the others')
+    const uint32_t nee = (c->dsc.nlights ? p->nee_samples : 0) + (c->dsc.env_tex ? 1u : 0u);
     const bool tiny_fused = c->dsc.nsmall && c->opt.fused;
     // (the other wave schedules are experiment knobs of the separate kernels; with a texture map active the separate kernels run whatever the option says: k_bounce_bvh samples no image)
-    const bool fused_bvh = !c->dsc.nsmall && c->opt.fused_bvh && c->opt.trace_sched >= 5u && !c->dsc.tri_uv;
+    const bool fused_bvh = !c->dsc.nsmall && c->opt.fused_bvh && c->opt.trace_sched >= 5u && !c->dsc.tri_uv && !c->dsc.env_n;
     const BatchPlan B = plan_batches(c, spp, f, fused_bvh);
     const uint32_t bspp = B.bspp, G = B.G;
     const uint64_t cap64 = (uint64_t)f.npl * bspp;

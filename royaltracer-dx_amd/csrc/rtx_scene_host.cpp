@@ -442,8 +442,9 @@ bool SceneHost::build(BuiltScene& B) {
     // a tiny scene with a hidden instance takes the general BVH path until everything is visible again: its pre-test records, merged quads, hull faces and the NEE hull
     // shortcut are derived from geometry, and a hidden triangle may take part in none of them (identical results by the parity contract)
     // ... and so does one with an active texture map (k_bounce_small and k_primary_surface sample no image)
-    B.maps_active = maps_active();
-    if (B.any_hidden || B.maps_active) { B.small_recs.clear(); B.small_tris.clear(); B.small_poly.clear(); B.small_nrec = 0; B.small_nocc = 0; }
+    // ... and one with an environment bound (k_bounce_small's misses end black)
+    B.maps_active = maps_active(); B.env_active = env.n != 0;
+    if (B.any_hidden || B.maps_active || B.env_active) { B.small_recs.clear(); B.small_tris.clear(); B.small_poly.clear(); B.small_nrec = 0; B.small_nocc = 0; }
     else build_small_scene(B, wtri, scale);
     sw.lap("tris8 / small scene");
     B.any_order = probe_anyhit_order(B);

@@ -7,6 +7,7 @@
 #include <stdint.h>
 #include "rtx_types.hpp"
 #include "rtx_bvh_host.hpp"
+#include "rtx_env_host.hpp"
 
 namespace rtx {
 
@@ -48,6 +49,7 @@ struct BuiltScene {
     std::vector<uint32_t> inst_hidden;  // one word per instance, non-zero = hidden, AS COMMITTED: what the resident tree's boxes, the never-hit triangle records and the light list reflect (the refit kernels read it)
     bool any_hidden = false;            // ... and whether any word of it is set
     bool maps_active = false;           // SceneHost::maps_active() AS COMMITTED: a tiny scene then runs on the general path, DevScene::tri_uv / map_kd are set
+    bool env_active = false;            // an environment is bound (SceneHost::env.n != 0) AS COMMITTED: a tiny scene then runs on the general path
     std::vector<uint32_t> inst_moved;   // refresh_transforms: 1 = the instance's objectToWorld differs from the last commit's, or its mesh's vertices do, or its visibility does (the GPU refit touches the triangles and nodes of these only)
 };
 
@@ -65,6 +67,9 @@ struct SceneHost {
     std::vector<TexHost> textures;
     std::vector<int32_t> map_kd;                // per material: texture id of RTX_MAP_KD or -1; shorter than the table = the rest has none (rtx_set_materials empties it)
     bool tex_dirty = false;                     // one of the three setters since the last commit
+    // environment lighting (include/rtx.h: rtx_set_environment; rtx_env_host.hpp)
+    EnvHost env;
+    bool env_dirty = false;                     // rtx_set_environment since the last commit
     BvhBuildOptions bvh = bvh_build_options();  // builder knobs of this scene (rtx_set_option RTX_OPT_BVH_*)
 
     bool set_materials(const void* mats, uint32_t count);

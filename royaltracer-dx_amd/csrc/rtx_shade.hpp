@@ -2,6 +2,7 @@
 #pragma once
 #include "rtx_traverse.hpp"
 #include "rtx_texture.hpp"
+#include "rtx_env.hpp"
 
 namespace rtx {
 
@@ -159,6 +160,44 @@ __device__ __forceinline__ bool nee_sample(const DevScene& sc, const MatGPU& m, 
     const f3 sorg = madd3(normalize(normal), kSBias, pos);    // :616-621
     so = {sorg.x, sorg.y, sorg.z, near_hull ? -0.5f * kSBias : 0.5f * kSBias};     // tmin; its sign carries the hull-guard flag of the tiny-scene path
     sd = {Ln.x, Ln.y, Ln.z, maxf_(kSBias, dist - kSBias * 5.0f)};
+    return true;
+}
+
+// ---- environment lighting (EXTENSION, include/rtx.h: rtx_set_environment; the reference's Miss.hlsl returns black) ----
+// a ray of bounce `bounce` that left the scene: bounce 0 sees the map itself (unless RTX_ENV_HIDDEN), later bounces add it weighted against the environment NEE sample of
+// the vertex the ray came from (balance heuristic, one sample each); prev_pdf < 0: the ray came through a transmission lobe, which NEE never samples (add_emissive)
+__device__ __forceinline__ void env_miss(const DevScene& sc, const DevPaths& p, const PathState& S, uint32_t bounce) {
+    if (bounce == 0 && (sc.env_flags & 1u)) return;
+    const EnvEval E = env_eval(sc, S.d);
+    f3 e = E.L;
+    if (bounce != 0) {
+        float mi = S.prev_pdf / (E.pdf + S.prev_pdf);
+        if (S.prev_pdf < 0.0f) mi = 1.0f;
+        e = mk3((E.L.x * S.thr.x) * mi, (E.L.y * S.thr.y) * mi, (E.L.z * S.thr.z) * mi);
+        if (!finite3(e)) return;
+    }
+    F4 radv = p.rad[S.pid];
+    radv.x = radv.x + e.x; radv.y = radv.y + e.y; radv.z = radv.z + e.z;
+    p.rad[S.pid] = radv;
+}
+// the environment's NEE sample of a shading point (slot index `nee`, after the triangle-light samples).  Returns true when a shadow ray is needed: same origin and tmin as
+// nee_sample's, tmax = the camera rays' "no limit"
+__device__ __forceinline__ bool env_nee_sample(const DevScene& sc, const float* __restrict__ marg, const MatGPU& m, uint32_t flags, PathState& S, f3 pos, f3 normal, f3 outgoing,
+                                               F4& so, F4& sd, f3& con, float eta_p, const MixView* mv, const f3* kdpi) {
+    f3 Ln;
+    const EnvEval E = env_sample(sc, marg, S.s0, S.s1, Ln);
+    const float cos_x = dot(normal, Ln);
+    if (cos_x < kEps || !(E.pdf > 0.0f)) return false;
+    f3 F; float P, pd, ps;
+    if (mv) bsdf_mixture_v(m, flags, *mv, normal, Ln, outgoing, F, P, eta_p, kdpi);
+    else bsdf_mixture(m, flags, normal, Ln, outgoing, F, P, pd, ps, eta_p, kdpi);
+    const float mi = E.pdf / (E.pdf + P);
+    const float g = cos_x / E.pdf * mi;
+    con = mk3(E.L.x * (S.thr.x * F.x) * g, E.L.y * (S.thr.y * F.y) * g, E.L.z * (S.thr.z * F.z) * g);
+    if (!finite3(con) || is_zero3(con)) return false;
+    const f3 sorg = madd3(normalize(normal), kSBias, pos);
+    so = {sorg.x, sorg.y, sorg.z, 0.5f * kSBias};
+    sd = {Ln.x, Ln.y, Ln.z, kTMax};
     return true;
 }
 

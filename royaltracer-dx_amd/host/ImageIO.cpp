@@ -1,5 +1,6 @@
 // ImageIO.cpp — see ImageIO.h
 #include "ImageIO.h"
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -153,6 +154,95 @@ bool tga_from(const std::vector<uint8_t>& b, const std::string& path, std::vecto
     }
     return true;
 }
+
+// ---- high-dynamic-range readers (environment maps): Radiance RGBE and PFM, to top-down float RGB ----
+// a header line ending in '\n' starting at `at`; false at the end of the data
+bool text_line(const std::vector<uint8_t>& b, size_t& at, std::string& line) {
+    line.clear();
+    while (at < b.size() && b[at] != '\n') { if (line.size() > 4096) return false; line.push_back((char)b[at++]); }
+    if (at >= b.size()) return false;
+    at++;
+    if (!line.empty() && line.back() == '\r') line.pop_back();
+    return true;
+}
+bool hdr_from(const std::vector<uint8_t>& b, const std::string& path, std::vector<float>& rgb, uint32_t& w, uint32_t& h, std::string& err) {
+    size_t at = 0; std::string line;
+    if (!text_line(b, at, line) || line.compare(0, 2, "#?") != 0) { err = path + ": not a Radiance picture (no #? signature)"; return false; }
+    bool format = false;
+    for (;;) {
+        if (!text_line(b, at, line)) { err = path + ": truncated Radiance header"; return false; }
+        if (line.empty()) break;
+        if (line.compare(0, 7, "FORMAT=") == 0) { if (line != "FORMAT=32-bit_rle_rgbe") { err = path + ": Radiance FORMAT other than 32-bit_rle_rgbe"; return false; } format = true; }
+    }
+    if (!format) { err = path + ": Radiance header without FORMAT=32-bit_rle_rgbe"; return false; }
+    if (!text_line(b, at, line)) { err = path + ": truncated Radiance header"; return false; }
+    unsigned long hh = 0, ww = 0; char tail = 0;
+    if (sscanf(line.c_str(), "-Y %lu +X %lu%c", &hh, &ww, &tail) != 2) { err = path + ": only the -Y H +X W orientation is read"; return false; }
+    if (hh < 1 || ww < 1 || hh > 32768 || ww > 32768) { err = path + ": Radiance picture size out of range"; return false; }
+    w = (uint32_t)ww; h = (uint32_t)hh;
+    rgb.assign((size_t)w * h * 3, 0.0f);
+    std::vector<uint8_t> scan((size_t)w * 4);
+    for (uint32_t y = 0; y < h; y++) {
+        const bool rle = w >= 8 && w < 32768 && b.size() - at >= 4 && b[at] == 2 && b[at + 1] == 2 && (b[at + 2] & 128u) == 0;
+        if (rle) {                                            // new-style run-length encoding: the four channels one after the other
+            if ((((uint32_t)b[at + 2] << 8) | b[at + 3]) != w) { err = path + ": Radiance scanline length differs from the width"; return false; }
+            at += 4;
+            for (int ch = 0; ch < 4; ch++) {
+                uint32_t x = 0;
+                while (x < w) {
+                    if (at >= b.size()) { err = path + ": truncated Radiance picture"; return false; }
+                    uint32_t count = b[at++];
+                    if (count > 128u) {                       // a run
+                        count -= 128u;
+                        if (count > w - x || at >= b.size()) { err = path + ": corrupt Radiance run"; return false; }
+                        const uint8_t v = b[at++];
+                        for (uint32_t k = 0; k < count; k++) scan[(size_t)(x + k) * 4 + ch] = v;
+                    } else {                                  // literals
+                        if (count == 0 || count > w - x || b.size() - at < count) { err = path + ": corrupt Radiance run"; return false; }
+                        for (uint32_t k = 0; k < count; k++) scan[(size_t)(x + k) * 4 + ch] = b[at + k];
+                        at += count;
+                    }
+                    x += count;
+                }
+            }
+        } else {                                              // flat: four bytes per pixel
+            if (b.size() - at < (size_t)w * 4) { err = path + ": truncated Radiance picture"; return false; }
+            memcpy(scan.data(), &b[at], (size_t)w * 4);
+            at += (size_t)w * 4;
+        }
+        for (uint32_t x = 0; x < w; x++) {
+            const uint8_t* q = &scan[(size_t)x * 4];
+            if (!q[3]) continue;
+            const float f = ldexpf(1.0f, (int)q[3] - 136);    // mantissa byte m, exponent byte e: m * 2^(e - 128 - 8)
+            float* o = &rgb[((size_t)y * w + x) * 3];
+            o[0] = (float)q[0] * f; o[1] = (float)q[1] * f; o[2] = (float)q[2] * f;
+        }
+    }
+    return true;
+}
+bool pfm_from(const std::vector<uint8_t>& b, const std::string& path, std::vector<float>& rgb, uint32_t& w, uint32_t& h, std::string& err) {
+    size_t at = 0; std::string line;
+    if (!text_line(b, at, line) || line != "PF") { err = path + ": not a colour PFM (no PF signature)"; return false; }
+    unsigned long ww = 0, hh = 0; char tail = 0;
+    if (!text_line(b, at, line) || sscanf(line.c_str(), "%lu %lu%c", &ww, &hh, &tail) != 2) { err = path + ": PFM size line"; return false; }
+    if (hh < 1 || ww < 1 || hh > 32768 || ww > 32768) { err = path + ": PFM size out of range"; return false; }
+    double scale = 0.0;
+    if (!text_line(b, at, line) || sscanf(line.c_str(), "%lf%c", &scale, &tail) != 1 || scale == 0.0 || !std::isfinite(scale)) { err = path + ": PFM scale line"; return false; }
+    w = (uint32_t)ww; h = (uint32_t)hh;
+    const size_t n = (size_t)w * h * 3;
+    if (b.size() - at < n * 4) { err = path + ": truncated PFM"; return false; }
+    rgb.resize(n);
+    const bool little = scale < 0.0;                          // the sign of the scale is the byte order; its magnitude is not applied
+    for (uint32_t y = 0; y < h; y++) {                        // rows bottom-up in the file
+        const uint8_t* src = &b[at + (size_t)(h - 1u - y) * w * 12];
+        for (size_t k = 0; k < (size_t)w * 3; k++) {
+            const uint8_t* q = src + k * 4;
+            const uint32_t u = little ? ((uint32_t)q[0] | (uint32_t)q[1] << 8 | (uint32_t)q[2] << 16 | (uint32_t)q[3] << 24) : ((uint32_t)q[3] | (uint32_t)q[2] << 8 | (uint32_t)q[1] << 16 | (uint32_t)q[0] << 24);
+            memcpy(&rgb[(size_t)y * w * 3 + k], &u, 4);
+        }
+    }
+    return true;
+}
 }  // namespace
 
 bool ReadPNM(const std::string& path, std::vector<uint8_t>& rgba8, uint32_t& w, uint32_t& h, std::string& err) {
@@ -168,5 +258,54 @@ bool ReadImage(const std::string& path, std::vector<uint8_t>& rgba8, uint32_t& w
     if (!read_file(path, b, err)) return false;
     if (b.size() >= 2 && b[0] == 'P' && (b[1] == '5' || b[1] == '6')) return pnm_from(b, path, rgba8, w, h, err);
     if (!tga_from(b, path, rgba8, w, h, err)) { err = path + ": neither a binary PPM / PGM nor a true-colour TGA (" + err + ")"; return false; }
+    return true;
+}
+
+bool ReadHDR(const std::string& path, std::vector<float>& rgb32f, uint32_t& w, uint32_t& h, std::string& err) {
+    std::vector<uint8_t> b;
+    return read_file(path, b, err) && hdr_from(b, path, rgb32f, w, h, err);
+}
+bool ReadPFM(const std::string& path, std::vector<float>& rgb32f, uint32_t& w, uint32_t& h, std::string& err) {
+    std::vector<uint8_t> b;
+    return read_file(path, b, err) && pfm_from(b, path, rgb32f, w, h, err);
+}
+bool ReadHDRImage(const std::string& path, std::vector<float>& rgb32f, uint32_t& w, uint32_t& h, std::string& err) {
+    std::vector<uint8_t> b;
+    if (!read_file(path, b, err)) return false;
+    if (b.size() >= 2 && b[0] == 'P' && b[1] == 'F') return pfm_from(b, path, rgb32f, w, h, err);
+    if (b.size() >= 2 && b[0] == '#' && b[1] == '?') return hdr_from(b, path, rgb32f, w, h, err);
+    err = path + ": neither a Radiance .hdr nor a colour .pfm";
+    return false;
+}
+
+uint32_t LatLongSubSamples(uint32_t W, uint32_t N) {
+    const double s = std::ceil((double)W / (2.0 * (double)N));
+    return (uint32_t)(s < 2.0 ? 2.0 : s > 16.0 ? 16.0 : s);
+}
+bool LatLongToOctahedral(const float* rgb, uint32_t W, uint32_t H, uint32_t N, float* out) {
+    if (!rgb || !out || W < 1 || H < 1 || N < 1 || N > 2048) return false;
+    const double kPi = 3.14159265358979323846;
+    const uint32_t S = LatLongSubSamples(W, N);
+    for (uint32_t j = 0; j < N; j++) for (uint32_t i = 0; i < N; i++) {
+        double sum[3] = {0.0, 0.0, 0.0};
+        for (uint32_t sb = 0; sb < S; sb++) for (uint32_t sa = 0; sa < S; sa++) {
+            const double u = ((double)i + ((double)sa + 0.5) / (double)S) / (double)N, v = ((double)j + ((double)sb + 0.5) / (double)S) / (double)N;
+            double a = 2.0 * u - 1.0, b = 2.0 * v - 1.0;                   // the inverse fold of include/rtx.h, in double
+            const double y = (1.0 - std::fabs(a)) - std::fabs(b);
+            if (y < 0.0) { const double fa = (1.0 - std::fabs(b)) * (a >= 0.0 ? 1.0 : -1.0), fb = (1.0 - std::fabs(a)) * (b >= 0.0 ? 1.0 : -1.0); a = fa; b = fb; }
+            const double inv = 1.0 / std::sqrt((a * a + y * y) + b * b);
+            const double dx = a * inv, dy = y * inv, dz = b * inv;
+            // (sin t sin p, cos t, -sin t cos p)  ->  t = acos(y), p = atan2(x, -z) in [0, 2 pi)
+            const double t = std::acos(dy < -1.0 ? -1.0 : dy > 1.0 ? 1.0 : dy);
+            double p = std::atan2(dx, -dz);
+            if (p < 0.0) p += 2.0 * kPi;
+            long px = (long)std::floor(p / (2.0 * kPi) * (double)W), py = (long)std::floor(t / kPi * (double)H);
+            px = px < 0 ? 0 : px > (long)W - 1 ? (long)W - 1 : px; py = py < 0 ? 0 : py > (long)H - 1 ? (long)H - 1 : py;
+            const float* q = &rgb[((size_t)py * W + (size_t)px) * 3];
+            sum[0] += (double)q[0]; sum[1] += (double)q[1]; sum[2] += (double)q[2];
+        }
+        float* o = &out[((size_t)j * N + i) * 3];
+        for (int k = 0; k < 3; k++) o[k] = (float)(sum[k] / (double)(S * S));
+    }
     return true;
 }

@@ -20,3 +20,16 @@ bool ReadPNM(const std::string& path, std::vector<uint8_t>& rgba8, uint32_t& wid
 bool ReadTGA(const std::string& path, std::vector<uint8_t>& rgba8, uint32_t& width, uint32_t& height, std::string& err);
 // by content (P5 / P6 magic, else a TGA header that makes sense)
 bool ReadImage(const std::string& path, std::vector<uint8_t>& rgba8, uint32_t& width, uint32_t& height, std::string& err);
+
+// HIGH-DYNAMIC-RANGE images (environment maps), as top-down float RGB (width * height * 3):
+//   HDR : Radiance RGBE, FORMAT=32-bit_rle_rgbe, flat or new-style run-length encoded scanlines, the -Y H +X W orientation only; (m, e) -> m * 2^(e - 136), e = 0 -> 0
+//   PFM : the colour type "PF", either byte order by the sign of the scale line (its magnitude is not applied), rows bottom-up in the file
+bool ReadHDR(const std::string& path, std::vector<float>& rgb32f, uint32_t& width, uint32_t& height, std::string& err);
+bool ReadPFM(const std::string& path, std::vector<float>& rgb32f, uint32_t& width, uint32_t& height, std::string& err);
+bool ReadHDRImage(const std::string& path, std::vector<float>& rgb32f, uint32_t& width, uint32_t& height, std::string& err);      // by content ("PF" / "#?")
+// A latitude-longitude image as the N x N octahedral map of include/rtx.h (rtx_set_environment).  Lat-long convention: column centre phi = 2 pi (x + 0.5) / W, row centre
+// theta = pi (y + 0.5) / H from +Y, direction (sin t sin p, cos t, -sin t cos p).  Each octahedral texel is the mean of S x S stratified sub-positions
+// ((i + (a + 0.5) / S) / N, (j + (b + 0.5) / S) / N), each looked up NEAREST in the lat-long image (x = floor(p / 2 pi * W), y = floor(t / pi * H), clamped), summed in double
+// with b outer and a inner; S = clamp(ceil(W / (2 N)), 2, 16) in double.  out: N * N * 3 floats.  false: a null pointer or a size out of range (N in [1, 2048])
+uint32_t LatLongSubSamples(uint32_t W, uint32_t N);
+bool LatLongToOctahedral(const float* rgb, uint32_t W, uint32_t H, uint32_t N, float* out);

@@ -200,6 +200,16 @@ void MultiGpuFrame::SetInstanceVisible(uint32_t instance, bool visible) {
     m_refitMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
+void MultiGpuFrame::SetEnvironment(const SceneEnvironment& env) {
+    const auto t0 = std::chrono::steady_clock::now();
+    RunOnRanks([&](int r) {
+        if (BindSceneEnvironment(env, m->ctx[r]) != RTX_OK || rtx_commit_scene(m->ctx[r]) != RTX_OK)
+            throw std::runtime_error(std::string("MultiGpuFrame::SetEnvironment: ") + rtx_last_error(m->ctx[r]));
+    });
+    for (size_t r = 0; r < m->ctx.size(); r++) { if (!m->ctx[r]) continue; hipck(hipSetDevice(m_devices[r]), "hipSetDevice"); hipck(hipStreamSynchronize(m->stream[r]), "sync commit"); }
+    m_refitMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
 void MultiGpuFrame::SetMeshVertices(uint32_t mesh, const void* verts28, uint32_t nverts) {
     const auto t0 = std::chrono::steady_clock::now();
     RunOnRanks([&](int r) {

@@ -43,6 +43,9 @@ public:
     void SetMeshVertices(uint32_t mesh, const void* verts28, uint32_t nverts);
     // a hidden or shown instance (InstanceMask 0 / 0xFF, TopLevelASGenerator.cpp:198): rtx_set_instance_visible + the commit, a refit, on EVERY rank
     void SetInstanceVisible(uint32_t instance, bool visible);
+    // environment lighting on a resident scene: rtx_set_environment + the commit (tables only) on EVERY rank — every rank binds the same map, as SetScene does for the
+    // scene's own (Scene::environment); n = 0 clears it
+    void SetEnvironment(const SceneEnvironment& env);
     double LastRefitMs() const { return m_refitMs; }        // wall time of the last SetInstanceTransform / SetMeshVertices / SetInstanceVisible: max over ranks
     void SetCamera(const float view[16], const float proj[16]);   // every rank (rtx_set_camera keeps the previous matrices for the reprojection)
     void ResetRestir();                                   // forget the ReSTIR history on every rank

@@ -41,6 +41,9 @@ void Renderer::OnInit() {
         Check(rtx_add_mesh(m_ctx, m.vertices.data(), (uint32_t)m.vertices.size(), m.indices.data(), (uint32_t)m.indices.size(), m.materialIDs.data(), &id), "rtx_add_mesh");
     }
     for (const SceneInstance& in : m_scene.instances) { uint32_t id; Check(rtx_add_instance(m_ctx, in.model, in.transform.data(), &id), "rtx_add_instance"); }
+    if (m_haveEnv) m_scene.environment = m_env;
+    if (m_scene.environment.n) Check(BindSceneEnvironment(m_scene.environment, m_ctx), "rtx_set_environment");
+    m_envDirty = false;
     Check(BindSceneMaps(m_scene, m_ctx), "BindSceneMaps");                         // the decoded map_Kd images, per-corner UVs and map ids (nothing for a scene without them)
     Check(rtx_commit_scene(m_ctx), "rtx_commit_scene");                             // CreateAccelerationStructures, Renderer.cpp:893-946
     Check(rtx_clear_accum(m_ctx, m_width, m_height), "rtx_clear_accum");
@@ -74,6 +77,11 @@ void Renderer::SetInstanceVisible(UINT instance, bool visible) {
     m_flippedInstances.push_back(instance);
 }
 
+void Renderer::SetEnvironment(const SceneEnvironment& env) {
+    m_env = env; m_haveEnv = true;
+    if (m_ctx) { m_scene.environment = env; m_envDirty = true; }
+}
+
 void Renderer::SetMeshVertices(UINT mesh, const std::vector<Vertex>& vertices) {
     std::string err;
     if (!SetSceneMeshVertices(m_scene, mesh, vertices.data(), (uint32_t)vertices.size(), err)) throw std::invalid_argument("Renderer::SetMeshVertices: " + err);
@@ -88,13 +96,14 @@ void Renderer::OnUpdate() {
     // moves when SetInstanceTransform was called since the last update: its matrix goes to the context (which keeps the old one as prevObjectToWorld for the temporal
     // pass) and ONE transform-only commit refits the resident tree (k_refit_tris / k_refit_nodes).  Nothing moved: nothing to do.  The models SetMeshVertices changed go the
     // same way, in the same commit, and so do the instances SetInstanceVisible hid or showed.
-    if (!m_movedInstances.empty() || !m_changedMeshes.empty() || !m_flippedInstances.empty()) {
+    if (!m_movedInstances.empty() || !m_changedMeshes.empty() || !m_flippedInstances.empty() || m_envDirty) {
         const auto t0 = std::chrono::steady_clock::now();
         for (UINT i : m_movedInstances) Check(rtx_set_instance_transform(m_ctx, i, m_scene.instances[i].transform.data()), "rtx_set_instance_transform");
         if (!m_changedMeshes.empty() && !rtx_update_mesh_vertices) throw std::runtime_error("Renderer::OnUpdate: this build has no device library (rtx_update_mesh_vertices)");
         for (UINT i : m_changedMeshes) Check(rtx_update_mesh_vertices(m_ctx, i, m_scene.models[i].vertices.data(), (uint32_t)m_scene.models[i].vertices.size()), "rtx_update_mesh_vertices");
         if (!m_flippedInstances.empty() && !rtx_set_instance_visible) throw std::runtime_error("Renderer::OnUpdate: this build has no device library (rtx_set_instance_visible)");
         for (UINT i : m_flippedInstances) Check(rtx_set_instance_visible(m_ctx, i, m_hidden[i] ? 0 : 1), "rtx_set_instance_visible");
+        if (m_envDirty) { Check(BindSceneEnvironment(m_scene.environment, m_ctx), "rtx_set_environment"); m_envDirty = false; }
         Check(rtx_commit_scene(m_ctx), "rtx_commit_scene");
         m_movedInstances.clear(); m_changedMeshes.clear(); m_flippedInstances.clear();
         m_refitMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();

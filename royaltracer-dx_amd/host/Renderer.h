@@ -34,6 +34,9 @@ public:
     // instanceDescs[i].InstanceMask (TopLevelASGenerator.cpp:198) as all or nothing: the instance exists for no ray from the next OnUpdate on (rtx_set_instance_visible), whose
     // commit refits the resident tree; ids stay.  The value the instance already has changes nothing.  Throws std::out_of_range for an unknown instance
     void SetInstanceVisible(UINT instance, bool visible);
+    // environment lighting (rtx_set_environment): before OnInit it is bound with the scene; afterwards the next OnUpdate hands it to the context and re-commits (tables only).
+    // An environment with n = 0 clears it
+    void SetEnvironment(const SceneEnvironment& env);
     double LastRefitMs() const { return m_refitMs; }
 
     void OnInit();      // Renderer.cpp:44-103: camera lookat, load models, build acceleration structures, upload
@@ -72,5 +75,6 @@ private:
     std::vector<UINT> m_displayLevels = {0, 10, 11, 12, 13, 14, 15, 16, 17, 20, 21, 22, 23, 24, 25, 26, 27, 28};   // Renderer.h:299
     float m_prevView[16]; bool m_havePrev = false;   // m_prevViewMatrix
     std::vector<UINT> m_movedInstances, m_changedMeshes; double m_refitMs = 0.0;
+    SceneEnvironment m_env; bool m_haveEnv = false, m_envDirty = false;       // SetEnvironment: what it set (replaces the scene's own), and whether the context has yet to see it
     std::vector<uint8_t> m_hidden; std::vector<UINT> m_flippedInstances;      // visibility per instance as last asked for; the instances whose value changed since the last OnUpdate
 };

@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <cstring>
 #include <functional>
+#include <stdexcept>
 #include "ObjLoader.h"
 #include "manipulator.h"
 
@@ -616,6 +617,31 @@ int BindSceneMaps(const Scene& s, rtx_ctx* ctx) {
     return RTX_OK;
 }
 
+extern "C" int rtx_set_environment(rtx_ctx*, const float* rgb32f, uint32_t n, const float* env_to_world, float scale, uint32_t flags) __attribute__((weak));
+int BindSceneEnvironment(const SceneEnvironment& e, rtx_ctx* ctx) {
+    if (!rtx_set_environment) return e.n ? RTX_ERR_INVALID : RTX_OK;
+    if (!e.n) return rtx_set_environment(ctx, nullptr, 0, nullptr, 1.0f, 0);
+    if (e.rgb.size() != (size_t)e.n * e.n * 3) return RTX_ERR_INVALID;
+    return rtx_set_environment(ctx, e.rgb.data(), e.n, e.haveRotation ? e.toWorld : nullptr, e.scale, e.flags);
+}
+SceneEnvironment MakeSkyEnvironment(float r, float g, float b) {
+    SceneEnvironment e; e.n = 1; e.rgb = {r, g, b};
+    return e;
+}
+SceneEnvironment LoadEnvironment(const std::string& file, uint32_t n, float yaw_deg, float scale, bool hidden) {
+    std::vector<float> img; uint32_t w = 0, h = 0; std::string err;
+    if (!ReadHDRImage(file, img, w, h, err)) throw std::runtime_error(err);
+    SceneEnvironment e; e.n = n; e.rgb.resize((size_t)n * n * 3); e.scale = scale; e.flags = hidden ? RTX_ENV_HIDDEN : 0u;
+    if (!LatLongToOctahedral(img.data(), w, h, n, e.rgb.data())) throw std::runtime_error(file + ": environment resolution must be in [1, 2048]");
+    if (yaw_deg != 0.0f) {                                     // a turn about +Y (column-vector matrix, element (r, c) at [c * 4 + r])
+        const double a = (double)yaw_deg * 3.14159265358979323846 / 180.0;
+        const float cs = (float)cos(a), sn = (float)sin(a);
+        e.haveRotation = true;
+        e.toWorld[0] = cs; e.toWorld[8] = sn; e.toWorld[2] = -sn; e.toWorld[10] = cs;
+    }
+    return e;
+}
+
 int UploadScene(const Scene& s, rtx_ctx* ctx, float aspect) {
     int r;
     if ((r = rtx_set_materials(ctx, s.materials.data(), (uint32_t)s.materials.size()))) return r;
@@ -625,6 +651,7 @@ int UploadScene(const Scene& s, rtx_ctx* ctx, float aspect) {
     }
     for (const SceneInstance& in : s.instances) { uint32_t id; if ((r = rtx_add_instance(ctx, in.model, in.transform.data(), &id))) return r; }
     if ((r = BindSceneMaps(s, ctx))) return r;
+    if (s.environment.n && (r = BindSceneEnvironment(s.environment, ctx))) return r;
     if ((r = rtx_commit_scene(ctx))) return r;
     float view[16], proj[16];
     SceneViewProj(s, aspect, view, proj);

@@ -13,6 +13,12 @@ struct SceneModel { std::vector<Vertex> vertices; std::vector<UINT> indices; std
                     std::vector<float> uvs; };      // one (u, v) per entry of `indices` (the OBJ's vt, per corner), or empty
 struct SceneImage { uint32_t width = 0, height = 0; std::vector<uint8_t> rgba; };      // a decoded texture, top-down RGBA8; width 0 = not loaded
 struct SceneInstance { UINT model; XMMATRIX transform; };
+// an environment map for rtx_set_environment: n x n octahedral float RGB (n = 0: none), the 16-float env_to_world (haveRotation false: identity), scale, RTX_ENV_* flags
+struct SceneEnvironment { uint32_t n = 0; std::vector<float> rgb; bool haveRotation = false; float toWorld[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}; float scale = 1.0f; uint32_t flags = 0; };
+// the two ways the command line makes one: a constant sky, and a latitude-longitude image file (Radiance .hdr / colour .pfm: host/ImageIO.h) resampled to n x n and turned by
+// yaw degrees about +Y; the second throws std::runtime_error for a file that cannot be read
+SceneEnvironment MakeSkyEnvironment(float r, float g, float b);
+SceneEnvironment LoadEnvironment(const std::string& file, uint32_t n, float yaw_deg, float scale, bool hidden);
 struct Scene {
     std::string name;
     std::vector<Material> materials;         // [default_0, mats of model 0..., default_1, ...]  (ObjLoader.h:415-417,494)
@@ -24,6 +30,7 @@ struct Scene {
     std::vector<SceneInstance> instances;
     XMFLOAT3 eye{0, 0, 1}, center{0, 0, 0}, up{0, 1, 0};
     float fovY_deg = 60.0f, zn = 0.1f, zf = 1000.0f;     // Renderer.cpp:1730-1731
+    SceneEnvironment environment;            // bound by UploadScene, the Renderer and the N-GPU frame (every rank binds the same map); n = 0: the scene has none
     size_t triangles() const { size_t n = 0; for (auto& i : instances) n += models[i.model].indices.size() / 3; return n; }
 };
 
@@ -39,6 +46,8 @@ Scene MakeBistroClass(uint32_t target_tris = 3800000, uint32_t seed = 3800, bool
 Scene LoadObjScene(const std::vector<std::string>& files, const std::string& mtl_dir, bool load_textures = true);
 // rtx_set_mesh_uvs / rtx_set_texture / rtx_set_material_map for what the scene carries; a scene without a decoded image binds nothing.  Before rtx_commit_scene
 int BindSceneMaps(const Scene&, rtx_ctx*);
+// rtx_set_environment for what the scene carries (n = 0: clears the context's).  Before rtx_commit_scene
+int BindSceneEnvironment(const SceneEnvironment&, rtx_ctx*);
 // new vertices for a model whose topology stays (the scene-level twin of rtx_update_mesh_vertices, same checks: the model exists, same vertex count, Vertex.normal.w — the
 // model's base in materialIDs[] — unchanged, non-null); false + err leaves the scene as it was
 bool SetSceneMeshVertices(Scene&, UINT model, const void* verts28, uint32_t nverts, std::string& err);

@@ -59,6 +59,17 @@ int rtxh_read_image(const char* path, void* rgba8, uint64_t capacity, uint32_t* 
     if (rgba8 && capacity >= px.size()) memcpy(rgba8, px.data(), px.size());
     return RTX_OK;
 }
+int rtxh_read_hdr_image(const char* path, float* rgb32f, uint64_t capacity, uint32_t* width, uint32_t* height) {
+    if (!path || !width || !height) return RTX_ERR_INVALID;
+    std::vector<float> px; std::string err;
+    if (!ReadHDRImage(path, px, *width, *height, err)) { g_err = err; return RTX_ERR_INVALID; }
+    if (rgb32f && capacity >= px.size() * sizeof(float)) memcpy(rgb32f, px.data(), px.size() * sizeof(float));
+    return RTX_OK;
+}
+int rtxh_env_from_latlong(const float* rgb32f, uint32_t width, uint32_t height, uint32_t n, float* out) {
+    if (!LatLongToOctahedral(rgb32f, width, height, n, out)) { g_err = "env_from_latlong: null array, empty image or N outside [1, 2048]"; return RTX_ERR_INVALID; }
+    return RTX_OK;
+}
 rtxh_scene* rtxh_scene_from_obj(const char* const* files, uint32_t n, const char* mtl_dir) {
     std::vector<std::string> f; for (uint32_t i = 0; i < n; i++) f.emplace_back(files[i]);
     std::string dir = mtl_dir ? mtl_dir : "./";

@@ -19,6 +19,9 @@
 //                   guided by first-hit position, normal and material; defaults: 5 levels, 0.5, 2^-6 of the scene's extent) and --out gets the DENOISED image; works with
 //                   --adaptive and with --gpus N (on rank 0, after the gather); refused with --mode restir (that frame has its own reuse passes)
 //                   [--no-textures]   OBJ scenes: do not read the images their map_Kd statements name (binary PPM / PGM, 24- / 32-bit TGA): the image without diffuse maps
+//                   [--env FILE [--env-res N] [--env-yaw DEG] [--env-scale S] [--env-hidden]]   environment lighting (rtx_set_environment): FILE is a latitude-longitude Radiance .hdr or
+//                   colour .pfm, resampled to an N x N octahedral map (default 512), turned by DEG degrees about +Y, radiance times S; --env-hidden: camera rays that miss stay black
+//                   [--sky R,G,B]   a constant sky of that radiance instead of a file; both work with --gpus N (every rank binds the same map) and are ignored by --mode restir
 //                   [--gpus N [--devices 0,1,..] [--gather rccl|copy]]   the native N-GPU frame (MultiGpu.h): one process, N contexts, pixel tiles
 //                   round-robin, ONE RCCL all-gather per frame; `--gather copy` replaces the collective by device copies (several ranks on one GPU: tests)
 #include <algorithm>
@@ -41,6 +44,7 @@ static const char* kUsage =
     "                  [--adaptive THRESHOLD [--min-spp N] [--step-spp N]]\n"
     "                  [--denoise [--denoise-levels N] [--sigma-color X] [--sigma-plane X]]   write the denoised image to --out (path tracer only)\n"
     "                  [--no-textures]   OBJ scenes: ignore map_Kd images\n"
+    "                  [--env FILE [--env-res N] [--env-yaw DEG] [--env-scale S] [--env-hidden]] [--sky R,G,B]   environment lighting\n"
     "                  [--gpus N [--devices 0,1,..] [--gather rccl|copy]]\n";
 
 int main(int argc, char** argv) {
@@ -51,6 +55,7 @@ int main(int argc, char** argv) {
     bool adaptive = false; rtx_adaptive ad{}; ad.min_spp = 8; ad.step_spp = 8;
     bool denoise = false; rtx_denoise_params dnp{};
     bool textures = true;
+    std::string env_file, sky; UINT env_res = 512; float env_yaw = 0.0f, env_scale = 1.0f; bool env_hidden = false;
     for (int i = 1; i < argc; i++) {
         auto arg = [&](const char* k) { return !strcmp(argv[i], k) && i + 1 < argc; };
         if (arg("--scene")) scene = argv[++i]; else if (arg("--obj")) { objs = argv[++i]; scene = "obj"; } else if (arg("--mtl")) mtl = argv[++i];
@@ -61,6 +66,8 @@ int main(int argc, char** argv) {
         else if (arg("--adaptive")) { adaptive = true; ad.threshold = (float)atof(argv[++i]); } else if (arg("--min-spp")) ad.min_spp = (uint32_t)atoi(argv[++i]); else if (arg("--step-spp")) ad.step_spp = (uint32_t)atoi(argv[++i]);
         else if (!strcmp(argv[i], "--help") || !strcmp(argv[i], "-h")) { fputs(kUsage, stdout); return 0; }
         else if (!strcmp(argv[i], "--no-textures")) textures = false;
+        else if (arg("--env")) env_file = argv[++i]; else if (arg("--env-res")) env_res = (UINT)atoi(argv[++i]); else if (arg("--env-yaw")) env_yaw = (float)atof(argv[++i]);
+        else if (arg("--env-scale")) env_scale = (float)atof(argv[++i]); else if (!strcmp(argv[i], "--env-hidden")) env_hidden = true; else if (arg("--sky")) sky = argv[++i];
         else if (!strcmp(argv[i], "--denoise")) denoise = true; else if (arg("--denoise-levels")) dnp.levels = (uint32_t)atoi(argv[++i]); else if (arg("--sigma-color")) dnp.sigma_color = (float)atof(argv[++i]); else if (arg("--sigma-plane")) dnp.sigma_plane = (float)atof(argv[++i]);
         else if (arg("--halo")) halo = (UINT)atoi(argv[++i]); else if (arg("--gpus")) gpus = atoi(argv[++i]); else if (arg("--devices")) devlist = argv[++i]; else if (arg("--gather")) gather = argv[++i];
         else if (arg("--out")) out = argv[++i]; else if (arg("--device")) device = atoi(argv[++i]); else if (!strcmp(argv[i], "--lambert")) lambert = true;
@@ -71,6 +78,16 @@ int main(int argc, char** argv) {
     if (restir) { if (!nee_set) nee = 4; if (!bounces_set) bounces = 3; }
     if (adaptive && (restir || gpus > 1 || !devlist.empty())) { fprintf(stderr, "--adaptive is the path tracer on one GPU (no --mode restir, --gpus, --devices)\n"); return 2; }
     if (denoise && restir) { fprintf(stderr, "--denoise filters the path tracer's accumulation (no --mode restir: that frame has its own reuse passes)\n"); return 2; }
+    if (!env_file.empty() && !sky.empty()) { fprintf(stderr, "--env and --sky exclude each other\n"); return 2; }
+    SceneEnvironment env;
+    try {
+        if (!env_file.empty()) env = LoadEnvironment(env_file, env_res, env_yaw, env_scale, env_hidden);
+        else if (!sky.empty()) {
+            float c[3]; char tail = 0;
+            if (sscanf(sky.c_str(), "%f,%f,%f%c", &c[0], &c[1], &c[2], &tail) != 3) { fprintf(stderr, "--sky takes R,G,B\n"); return 2; }
+            env = MakeSkyEnvironment(c[0], c[1], c[2]); env.scale = env_scale; env.flags = env_hidden ? RTX_ENV_HIDDEN : 0u;
+        }
+    } catch (const std::exception& e) { fprintf(stderr, "error: %s\n", e.what()); return 1; }
     // camera of frame f: the scene's eye rotated by f * orbit degrees about the vertical axis through the look-at point
     auto orbit_eye = [&](const Scene& sc, UINT f) {
         const float a = orbit * 3.14159265f / 180.0f * (float)f, cs = cosf(a), sn = sinf(a);
@@ -92,6 +109,7 @@ int main(int argc, char** argv) {
             Scene sc = scene == "cornell" ? MakeCornellBox() : scene == "sponza" ? MakeSponzaClass() : scene == "bistro" ? MakeBistroClass() : Scene();
             if (scene == "obj") { std::vector<std::string> f; std::stringstream ss(objs); std::string t; while (std::getline(ss, t, ',')) f.push_back(t); sc = LoadObjScene(f, mtl, textures); }
             if (scene == "cornell") lambert = true;
+            if (env.n) sc.environment = env;
             MultiGpuFrame mg(devs, gather == "copy" ? MultiGpuFrame::Gather::COPY : MultiGpuFrame::Gather::RCCL, force_gather, only_rank);      // --force-gather: the collective also with one rank
             mg.SetScene(sc, (float)w / (float)h);
             mg.Clear(w, h);
@@ -136,6 +154,7 @@ int main(int argc, char** argv) {
         else if (scene == "sponza") r.SetScene(MakeSponzaClass());
         else if (scene == "bistro") r.SetScene(MakeBistroClass());
         else { std::vector<std::string> f; std::stringstream ss(objs); std::string t; while (std::getline(ss, t, ',')) f.push_back(t); r.SetLoadTextures(textures); r.SetModels(f, mtl); }
+        if (env.n) r.SetEnvironment(env);
         r.Params().spp = spp; r.Params().max_bounces = bounces; r.Params().nee_samples = nee; r.Params().flags = lambert ? RTX_FLAG_LAMBERT_ONLY : (scene == "bistro" ? RTX_FLAG_TRANSMISSION : 0);
         if (restir) {
             r.SetMode(Renderer::Mode::ReSTIR);
