@@ -233,7 +233,7 @@ int  rtx_update_mesh_vertices(rtx_ctx*, uint32_t mesh, const void* verts28, uint
    in tests/test_texture.py).  rtx_render and rtx_render_adaptive only; rtx_render_v6_pass1 and rtx_render_restir ignore maps, as they ignore RTX_FLAG_TRANSMISSION.
    DATA.  Per mesh an optional array of one (u, v) float pair per INDEX entry, parallel to `indices` and `material_ids`: per corner, not per vertex (the 28-byte Vertex
    stays as it is); a mesh without the array has (0, 0) at every corner.  Per context a table of textures, each width x height RGBA8 (r in the first byte), row 0 on
-   top, alpha ignored, 1 <= width, height <= 16384 (and at most 2^31 texels in the whole table); RTX_TEX_SRGB says the bytes are sRGB-encoded.  Per material the
+   top, alpha read by the opacity slot only (ALPHA CUT-OUTS below), 1 <= width, height <= 16384 (and at most 2^31 texels in the whole table); RTX_TEX_SRGB says the bytes are sRGB-encoded.  Per material the
    slot RTX_MAP_KD: a texture id or -1.
    BYTE -> FLOAT.  A 256-entry float32 table per encoding, filled on the host.  Linear: T[b] = (float)b / 255.0f.  sRGB, in double: c = b / 255.0;
    c <= 0.04045 ? c / 12.92 : pow((c + 0.055) / 1.055, 2.4); rounded to float32 once.
@@ -256,7 +256,7 @@ int  rtx_update_mesh_vertices(rtx_ctx*, uint32_t mesh, const void* verts28, uint
    material's map has no effect (emitters are not shaded).  CONSEQUENCE: a scene in which every textured triangle sees one value tl is, bit for bit, the untextured scene
    whose triangles carry materials with Kd = Kd'.  rtx_denoise is unchanged (its colour edge-stop now sees texture detail); debug layer 13 shows Kd'.
    CALLS.  rtx_set_mesh_uvs: nidx pairs, nidx = the mesh's index count; NULL clears.  rtx_set_texture: tex <= the current count, == count appends; the texels are copied.
-   rtx_set_material_map: slot RTX_MAP_KD, tex -1 = none.  RTX_ERR_INVALID — unknown mesh, material, texture or slot; nidx other than the mesh's; a non-finite UV; a size
+   rtx_set_material_map: slot RTX_MAP_KD (or RTX_MAP_OPACITY, below), tex -1 = none.  RTX_ERR_INVALID — unknown mesh, material, texture or slot; nidx other than the mesh's; a non-finite UV; a size
    outside the limits; unknown flag bits; a NULL pixel pointer — leaves the scene untouched and committed.  rtx_set_materials resets every map to -1 (the table is
    replaced).  Like rtx_set_instance_visible the three are valid before the first commit and on a resident scene, and need rtx_commit_scene again (rendering in between is
    RTX_ERR_STATE).  On a resident general scene a commit after these calls alone uploads tables only: no rebuild, no refit, rtx_stats.bvh_refits and rtx_debug_tree_hash
@@ -265,8 +265,37 @@ int  rtx_update_mesh_vertices(rtx_ctx*, uint32_t mesh, const void* verts28, uint
    no texels); a loaded cache has no maps and no textures.  A tiny scene (<= 64 triangles) runs on the general BVH path while a material that a triangle uses has a map;
    the commit that crosses that line, either way, is a rebuild.  With such a map active rtx_render runs the default separate kernels whatever RTX_OPT_FUSED_BVH,
    RTX_OPT_SHADE_DENSE and RTX_OPT_SORT_MATERIALS say (measured-and-rejected variants get no textured copy); RTX_OPT_COMPACT_STATE 0 and 1 both work. */
+/* ALPHA CUT-OUTS (new; the reference parses map_d and samples nothing: an extension like map_Kd, pinned by its own definition and properties in tests/test_cutout_ref.py /
+   tests/test_cutout.py).  Foliage, chains, fences and decals are quads whose shape lives in the alpha channel of a texture: whether a ray HIT depends on a texel, so the
+   test runs inside the traversal.
+   SLOT.  rtx_set_material_map(ctx, material, RTX_MAP_OPACITY, tex) binds a texture of the table above (RTX_MAP_OPACITY = 2; the value 1 was an unknown slot before this
+   slot existed and stays one, so that no call that was refused is accepted now).  The opacity slot reads that texture's ALPHA BYTE (the 4th byte of a
+   texel); one RGBA8 texture may serve both slots of a material.
+   CUT-OUT TRIANGLE.  A triangle whose material (the id of its first index entry) has RTX_MAP_OPACITY >= 0 and no component of Ke > 0.  An emitter's opacity map has no effect,
+   as its map_Kd has none: the light list, its CDF and rtx_get_lights are untouched.
+   ALPHA AT A GEOMETRIC HIT with barycentrics (u, v) on global triangle prim, uv0..2 its corner pairs; float32 in exactly this order, no contraction:
+       b0, s, t exactly as in PER HIT above;  x0, y0, fx, fy, ixa, iyb exactly as in Sample(tex, s, t) (repeat wrap, v upward, wrap())
+       a_ab = T_linear[alpha byte of texel(ixa, iyb)]                                     (the LINEAR table (float)b / 255.0f, whatever RTX_TEX_SRGB says)
+       top = a00 + fx * (a10 - a00);  bot = a01 + fx * (a11 - a01);  a = top + fy * (bot - top)
+   The hit is ACCEPTED iff a >= 0.5f.  The cut-off is fixed: there is no per-material cut-off, and no fractional (stochastic) opacity.
+   HIT RULE.  A candidate counts for a ray iff the triangle test passes (determinant floor, exclusive (tmin, tmax)) AND the triangle is not a cut-out triangle or its alpha
+   is accepted.  Closest hit stays "minimum t, ties to the lower global triangle id", now over accepted candidates only; any hit is the existence of an accepted candidate.
+   CONSEQUENCE: a scene in which every cut-out triangle sees alpha on one side of 0.5 over its whole area is, bit for bit, the scene in which the rejected triangles do not
+   exist — image, ray counts and hit records, ids keeping their meaning.
+   WHO SEES CUT-OUTS.  rtx_render, rtx_render_adaptive, the guides of rtx_denoise, debug layers 10-17, rtx_debug_trace_closest / rtx_debug_trace_any, and rtx_debug_surface /
+   rtx_debug_albedo through the hits they are given.  IGNORED BY rtx_render_v6_pass1, rtx_render_restir (their visibility rays included), rtx_debug_trace_stats, the
+   commit-time any-hit order probe and the meaning of RTX_OPT_TRACE_COUNTERS' tallies (geometric tests) — as they ignore map_Kd, the environment and RTX_FLAG_TRANSMISSION.
+   A hidden instance stays hidden (its geometric test fails first); dissolve and transmission are unrelated and unchanged.
+   CALLS AND COMMITS follow the map_Kd rules word for word: valid before the first commit and on a resident scene; rtx_commit_scene again (rendering in between is
+   RTX_ERR_STATE); RTX_ERR_INVALID (unknown slot, material or texture) leaves the scene committed and untouched; rtx_set_materials resets the opacity maps to -1; on a resident
+   general scene a commit after map calls alone uploads tables only (no rebuild, no refit, rtx_stats.bvh_refits and rtx_debug_tree_hash unchanged: the per-triangle opacity
+   table lives beside the leaf records, not in them); vertex updates, transform / visibility edits, geometry-changing commits and RTX_OPT_GPU_BUILD keep cut-outs on their
+   triangles; a tiny scene (<= 64 triangles) runs on the general BVH path while any triangle is a cut-out triangle, and the commit that crosses that line is a rebuild;
+   rtx_save_scene_cache with an opacity map bound is RTX_ERR_STATE.
+   OPTIONS while a cut-out is active: RTX_OPT_FUSED_BVH, RTX_OPT_SHADE_DENSE, RTX_OPT_SORT_MATERIALS, RTX_OPT_WORK_STEALING and RTX_OPT_OCCLUDER_CACHE are ignored (the default
+   form runs); RTX_OPT_COMPACT_STATE 0 / 1, RTX_OPT_STACK_PRIVATE, RTX_OPT_STACK_CAP and RTX_OPT_TRACE_SCHED 0-7 all work. */
 #define RTX_TEX_SRGB 1u
-enum { RTX_MAP_KD = 0 };
+enum { RTX_MAP_KD = 0, RTX_MAP_OPACITY = 2 };      /* 1 is not a slot: it stays RTX_ERR_INVALID, as it always was */
 int  rtx_set_mesh_uvs(rtx_ctx*, uint32_t mesh, const float* uv2 /* nidx pairs; NULL clears */, uint32_t nidx);
 int  rtx_set_texture(rtx_ctx*, uint32_t tex /* <= current count; == count appends */, const void* rgba8, uint32_t width, uint32_t height, uint32_t flags);
 int  rtx_set_material_map(rtx_ctx*, uint32_t material, uint32_t slot, int32_t tex /* -1 = none */);
@@ -274,6 +303,9 @@ int  rtx_set_material_map(rtx_ctx*, uint32_t material, uint32_t slot, int32_t te
    material has no map), texture id as uint bits or 0xFFFFFFFF); a miss gives (0, 0, 0, 0xFFFFFFFF).  rays8 may be NULL: the albedo depends on the hit record alone */
 int  rtx_debug_texture_sample(rtx_ctx*, uint32_t tex, const float* uv2, uint32_t n, float* out4);
 int  rtx_debug_albedo(rtx_ctx*, const float* rays8, const float* hits4, uint32_t n, float* out4);
+/* tests: the alpha test of the cut-outs, by the device function the traversal runs — hits4 as rtx_debug_trace_closest writes them -> per record (alpha, opacity texture id
+   as uint bits); (1.0f, 0xFFFFFFFF) for a miss, for a triangle that is not a cut-out triangle, and for every hit while no cut-out is active */
+int  rtx_debug_opacity(rtx_ctx*, const float* hits4, uint32_t n, float* out2);
 /* ENVIRONMENT LIGHTING (new; the reference's Miss.hlsl:3-11 returns black, so a ray that leaves the scene ends dark and only emissive triangles light anything: an extension,
    unpinned by definition like strategy 3 and map_Kd, pinned by its own definition and properties in tests/test_env_ref.py / tests/test_env.py).  rtx_render and
    rtx_render_adaptive only; rtx_render_v6_pass1 and rtx_render_restir ignore the environment, as they ignore maps and RTX_FLAG_TRANSMISSION.  With no environment bound every

@@ -24,6 +24,12 @@ rtxh_scene* rtxh_scene_bistro_class_hard(uint32_t target_tris, uint32_t seed);
 /* files: nfiles OBJ paths, each loaded through ObjLoader::loadObjFile (ObjLoader.h:393-495) as the reference's
    Renderer does (Renderer.cpp:363-407); returns NULL on parse error (message via rtxh_last_error) */
 rtxh_scene* rtxh_scene_from_obj(const char* const* files, uint32_t nfiles, const char* mtl_dir);
+/* ... with flags: RTXH_OBJ_NO_TEXTURES = decode no image (implies NO_CUTOUTS); RTXH_OBJ_NO_CUTOUTS = no opacity maps; RTXH_OBJ_KD_ALPHA = a material without a map_d whose
+   map_Kd file has an alpha channel of its own (32-bit TGA) gets that texture as its opacity map too.  0 = rtxh_scene_from_obj */
+#define RTXH_OBJ_NO_TEXTURES 1u
+#define RTXH_OBJ_NO_CUTOUTS  2u
+#define RTXH_OBJ_KD_ALPHA    4u
+rtxh_scene* rtxh_scene_from_obj_ex(const char* const* files, uint32_t nfiles, const char* mtl_dir, uint32_t flags);
 /* SURVEY 8(f3) binary scene cache at the host level: the scene (materials, meshes, instances, camera) AND everything rtx_commit_scene
    derives from it (BVH, shading records, LUTs, light CDF); versioned + checksummed (csrc/rtx_scene_cache.cpp).  Saving needs no GPU.
    A loaded scene answers the accessors below like any other and rtxh_scene_upload hands the file's prebuilt arrays to the context
@@ -50,6 +56,8 @@ const char* rtxh_scene_texture(const rtxh_scene*, uint32_t i);                  
    uncompressed or RLE 24- / 32-bit TGA: host/ImageIO.h), and a file that is missing or in another format is skipped with one line on stderr and the scene loads as
    without it.  rtxh_scene_upload, the Renderer and the N-GPU frame bind the decoded ones (rtx_set_texture, rtx_set_material_map) to every context they upload to. */
 int         rtxh_scene_texture_pixels(const rtxh_scene*, uint32_t i, const void** rgba8, uint32_t* width, uint32_t* height);
+/* the texture the scene binds as the material's opacity map (RTX_MAP_OPACITY: its map_d; alpha byte = the file's alpha channel for a 32-bit TGA, else its first channel), or -1 */
+int         rtxh_scene_opacity_map(const rtxh_scene*, uint32_t material);
 /* the per-corner texture coordinates of mesh i (the OBJ's vt): one (u, v) pair per index entry, parallel to rtxh_scene_mesh's indices; NULL / 0 for a mesh without any */
 int         rtxh_scene_mesh_uvs(const rtxh_scene*, uint32_t i, const float** uv2, uint32_t* nidx);
 /* the image readers alone: width / height always, the pixels when capacity holds width * height * 4 bytes; RTX_ERR_INVALID + rtxh_last_error for a file they cannot read */

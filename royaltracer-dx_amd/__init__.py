@@ -48,6 +48,7 @@ OPT_SHARED_PRIMARY = 41
 OPT_DENOISE_LDS_STEP = 42
 TEX_SRGB = 1          # rtx_set_texture flag: the bytes are sRGB-encoded
 MAP_KD = 0            # rtx_set_material_map slot
+MAP_OPACITY = 2       # ... the alpha cut-out slot: reads the texture's alpha byte (1 is not a slot)
 ENV_HIDDEN = 1        # rtx_set_environment flag: primary rays that miss stay black
 
 
@@ -113,6 +114,7 @@ _sig("rtx_set_texture", C.c_int, _vp, _u32, _vp, _u32, _u32, _u32)
 _sig("rtx_set_material_map", C.c_int, _vp, _u32, _u32, C.c_int32)
 _sig("rtx_debug_texture_sample", C.c_int, _vp, _u32, _vp, _u32, _vp)
 _sig("rtx_debug_albedo", C.c_int, _vp, _vp, _vp, _u32, _vp)
+_sig("rtx_debug_opacity", C.c_int, _vp, _vp, _u32, _vp)
 _sig("rtx_set_environment", C.c_int, _vp, _vp, _u32, _vp, C.c_float, _u32)
 _sig("rtx_debug_env_sample", C.c_int, _vp, _vp, _u32, _vp)
 _sig("rtx_debug_env_eval", C.c_int, _vp, _vp, _u32, _vp)
@@ -197,6 +199,8 @@ _sig("rtxh_scene_bistro_class", _vp, _u32, _u32)
 _sig("rtxh_scene_sponza_class_hard", _vp, _u32, _u32)
 _sig("rtxh_scene_bistro_class_hard", _vp, _u32, _u32)
 _sig("rtxh_scene_from_obj", _vp, C.POINTER(C.c_char_p), _u32, C.c_char_p)
+_sig("rtxh_scene_from_obj_ex", _vp, C.POINTER(C.c_char_p), _u32, C.c_char_p, _u32)
+_sig("rtxh_scene_opacity_map", C.c_int, _vp, _u32)
 _sig("rtxh_scene_free", None, _vp)
 _sig("rtxh_scene_save", C.c_int, _vp, C.c_char_p)
 _sig("rtxh_scene_load", _vp, C.c_char_p)
@@ -305,6 +309,8 @@ class Scene:
             lib.rtxh_scene_texture_pixels(handle, i, C.byref(px), C.byref(tw), C.byref(th))
             self.texture_pixels.append(np.array((C.c_uint8 * (tw.value * th.value * 4)).from_address(px.value), dtype=np.uint8).reshape(th.value, tw.value, 4) if px.value else None)
         self.material_maps = [self.textures.index(e["maps"]["Kd"]) if "Kd" in e["maps"] else -1 for e in self.material_ext]
+        # ... and for the opacity maps (map_d; alpha byte = the file's alpha channel for a 32-bit TGA, else its first channel): per material the texture id or -1
+        self.opacity_maps = [int(lib.rtxh_scene_opacity_map(handle, i)) for i in range(n)]
         self.meshes, self.uvs = [], []
         for i in range(lib.rtxh_scene_num_meshes(handle)):
             v, idx, mid = _vp(), _vp(), _vp()
@@ -348,9 +354,12 @@ class Scene:
         return cls((lib.rtxh_scene_bistro_class_hard if hard else lib.rtxh_scene_bistro_class)(target_tris, seed))
 
     @classmethod
-    def from_obj(cls, files, mtl_dir):
+    def from_obj(cls, files, mtl_dir, textures=True, cutouts=True, kd_alpha=False):
+        """textures=False: decode no image; cutouts=False: bind no map_d image as an opacity map; kd_alpha=True: a material without a map_d whose map_Kd file is a
+        32-bit TGA gets that texture as its opacity map too (rtx_render --no-textures / --no-cutouts / --kd-alpha)"""
         arr = (C.c_char_p * len(files))(*[f.encode() for f in files])
-        return cls(lib.rtxh_scene_from_obj(arr, len(files), mtl_dir.encode()))
+        flags = (0 if textures else 1) | (0 if cutouts else 2) | (4 if kd_alpha else 0)
+        return cls(lib.rtxh_scene_from_obj_ex(arr, len(files), mtl_dir.encode(), flags))
 
     def set_camera(self, eye, center, up=(0.0, 1.0, 0.0)):
         e, c, u = (np.asarray(v, np.float32) for v in (eye, center, up))
@@ -631,7 +640,7 @@ class Context:
         self._ck(lib.rtx_set_texture(self._h, int(tex), _ptr(a), a.shape[1], a.shape[0], TEX_SRGB if srgb else 0), "rtx_set_texture")
 
     def set_material_map(self, material, tex, slot=MAP_KD):
-        """the material's map in `slot` (MAP_KD) := texture id `tex`, -1 / None = none"""
+        """the material's map in `slot` (MAP_KD, MAP_OPACITY) := texture id `tex`, -1 / None = none"""
         self._ck(lib.rtx_set_material_map(self._h, int(material), int(slot), -1 if tex is None else int(tex)), "rtx_set_material_map")
 
     def texture_sample(self, tex, uvs):
@@ -649,10 +658,18 @@ class Context:
         self._ck(lib.rtx_debug_albedo(self._h, _ptr(r) if r is not None else None, _ptr(h), len(h), _ptr(out)), "rtx_debug_albedo")
         return out
 
+    def opacity(self, hits4):
+        """the alpha test of the cut-outs at hit records (trace_closest), by the device function the traversal runs -> (n, 2) float32: alpha, opacity texture id bits;
+        (1.0, 0xFFFFFFFF) for a miss, a triangle that is not a cut-out triangle, and every hit while no cut-out is active"""
+        h = _f32(hits4).reshape(-1, 4)
+        out = np.zeros((len(h), 2), np.float32)
+        self._ck(lib.rtx_debug_opacity(self._h, _ptr(h), len(h), _ptr(out)), "rtx_debug_opacity")
+        return out
+
     def bind_maps(self, scene):
         """the optional texture attributes of a scene (duck-typed): `uvs` — per mesh an (index count, 2) array or None; `textures` — a list whose entries are (H, W, 4)
-        uint8 arrays or (array, srgb) pairs, anything else (a file name without pixels) is skipped; `material_maps` — per material an index into `textures` or -1 / None.
-        A map whose texture was skipped is not bound."""
+        uint8 arrays or (array, srgb) pairs, anything else (a file name without pixels) is skipped; `material_maps` — per material an index into `textures` or -1 / None;
+        `opacity_maps` — likewise for the MAP_OPACITY slot.  A map whose texture was skipped is not bound."""
         for mesh, uv in enumerate(getattr(scene, "uvs", None) or []):
             if uv is not None and len(uv):
                 self.set_mesh_uvs(mesh, uv)
@@ -666,6 +683,9 @@ class Context:
         for mat, t in enumerate(getattr(scene, "material_maps", None) or []):
             if t is not None and t >= 0 and t in ids:
                 self.set_material_map(mat, ids[t])
+        for mat, t in enumerate(getattr(scene, "opacity_maps", None) or []):
+            if t is not None and t >= 0 and t in ids:
+                self.set_material_map(mat, ids[t], MAP_OPACITY)
 
     def set_environment(self, img, to_world=None, scale=1.0, hidden=False):
         """environment lighting: img = (N, N, 3) float32 octahedral map of linear radiance (row = v, column = u; latlong_to_octahedral makes one), or None to clear;

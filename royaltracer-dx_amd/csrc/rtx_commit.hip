@@ -65,7 +65,9 @@ static void fill_tex_lut(std::vector<float>& lut) {
 // triangle ids anew (a build).  What the kernels see of it is set by finalise_scene.
 static int sync_textures(rtx_ctx* c, bool renumbered) {
     SceneHost& H = c->host; rtx_ctx::Scene& S = c->scene;
-    const bool active = S.built.maps_active = H.maps_active();
+    S.built.maps_active = H.maps_active();
+    const bool cut = S.built.cutouts_active = H.cutouts_active();
+    const bool active = S.built.maps_active || cut;          // the UVs serve both
     int r;
     if (H.tex_dirty) {                                       // (a scene that never saw one of the three setters allocates nothing here)
         std::vector<TexDesc> desc(H.textures.size()); std::vector<uint32_t> pool;
@@ -86,6 +88,13 @@ static int sync_textures(rtx_ctx* c, bool renumbered) {
         S.tri_uv_valid = true;
     }
     if (!active && S.tri_uv_valid) { S.d_tri_uv.release(); S.tri_uv_valid = false; }       // (allocated only while a map is active)
+    // alpha cut-outs: the opacity texture per GLOBAL triangle id — from map_opacity, the material ids and the emitter test, numbered like tri_uv; never part of the leaf records
+    if (cut && (H.tex_dirty || renumbered || !S.tri_cut_valid)) {
+        std::vector<int32_t> tc; H.fill_tri_cut(tc);
+        if ((r = upload(c, S.d_tri_cut, tc))) return r;
+        S.tri_cut_valid = true;
+    }
+    if (!cut && S.tri_cut_valid) { S.d_tri_cut.release(); S.tri_cut_valid = false; }
     H.tex_dirty = false;
     return RTX_OK;
 }
@@ -392,7 +401,7 @@ int rtx_commit_scene(rtx_ctx* c) {
     // On the GPU: a scene that is already resident and not a tiny one (whose pre-test records depend on world positions).
     // a tiny scene leaves its pre-test records for the general path while a texture map is active and returns to them afterwards: the commit that crosses that line rebuilds
     {   size_t ntri_all = 0; for (const InstHost& in : c->host.insts) ntri_all += c->host.meshes[in.mesh].idx.size() / 3;
-        if (c->host.tex_dirty && ntri_all <= kSmallSceneMaxTris && c->host.maps_active() != c->scene.built.maps_active) c->host.topo_dirty = true;
+        if (c->host.tex_dirty && ntri_all <= kSmallSceneMaxTris && (c->host.maps_active() != c->scene.built.maps_active || c->host.cutouts_active() != c->scene.built.cutouts_active)) c->host.topo_dirty = true;
         // ... and so it does while an environment is bound
         if (c->host.env_dirty && ntri_all <= kSmallSceneMaxTris && (c->host.env.n != 0) != c->scene.built.env_active) c->host.topo_dirty = true; }
     bool build = !(c->opt.gpu_refit && gpu_refittable(c) && !c->host.topo_dirty);
@@ -439,6 +448,7 @@ int rtx_save_scene_cache(rtx_ctx* c, const char* path) {
     if (c->scene.host_mirror_stale) { c->err = "save_scene_cache: the per-triangle records were re-derived on the GPU after rtx_update_mesh_vertices and the host holds no current copy; commit with RTX_OPT_DEFORM_REBUILD 1 (host builder) to save a cache"; return RTX_ERR_STATE; }
     if (c->scene.built.any_hidden) { c->err = "save_scene_cache: an instance is hidden (rtx_set_instance_visible): the device's boxes and triangle records leave it out and the file format holds no visibility; show every instance and commit to save a cache"; return RTX_ERR_STATE; }
     if (c->host.env.n) { c->err = "save_scene_cache: an environment is bound (rtx_set_environment) and the file format holds no environment; clear it and commit to save a cache"; return RTX_ERR_STATE; }
+    if (c->host.any_opacity_map()) { c->err = "save_scene_cache: a material has an opacity map (rtx_set_material_map, RTX_MAP_OPACITY) and the file format holds no texels; unmap every material and commit to save a cache"; return RTX_ERR_STATE; }
     if (c->host.any_map()) { c->err = "save_scene_cache: a material has a texture map (rtx_set_material_map) and the file format holds no texels; unmap every material and commit to save a cache"; return RTX_ERR_STATE; }
     if (c->scene.dev_built) { c->err = "save_scene_cache: the tree was built on the GPU (RTX_OPT_GPU_BUILD) and has no host mirror; commit with the host builder to save a cache"; return RTX_ERR_STATE; }
     if (!save_scene_cache(c->host, c->scene.built, path, c->err)) return RTX_ERR_INVALID;
@@ -492,7 +502,10 @@ static int finalise_scene(rtx_ctx* c) {
     s.env_n = c->host.env.n; s.env_flags = c->host.env.flags; memcpy(s.env_rot, c->host.env.rot, sizeof(s.env_rot));
     const bool env_lit = s.env_n && c->scene.env_total > 0.0;
     s.env_tex = env_lit ? (const F4*)c->scene.d_env_tex.p : nullptr; s.env_marg = env_lit ? (const float*)c->scene.d_env_marg.p : nullptr; s.env_cond = env_lit ? (const float*)c->scene.d_env_cond.p : nullptr;
-    s.tri_uv = B.maps_active ? (const float*)c->scene.d_tri_uv.p : nullptr; s.map_kd = B.maps_active ? (const int32_t*)c->scene.d_map_kd.p : nullptr;
+    // (a scene with cut-outs and no diffuse map: k_shade<.., TEX> runs all the same, selected by tri_uv, and reads a map_kd table of -1s — every material keeps its own Kd)
+    const bool uv_active = B.maps_active || B.cutouts_active;
+    s.tri_uv = uv_active ? (const float*)c->scene.d_tri_uv.p : nullptr; s.map_kd = uv_active ? (const int32_t*)c->scene.d_map_kd.p : nullptr;
+    s.tri_cut = B.cutouts_active ? (const int32_t*)c->scene.d_tri_cut.p : nullptr;
     // LDS budget per workgroup: stack + top of tree + first triangles, kept <= 64 KiB
     // exact bound of the 8-wide tree, no slack: a level adds ONE entry (the rest of its hit siblings) and only where a node has >= 2 internal
     // children (collapse_bvh8: need[]); a pop precedes every descent from an exhausted group.  Each entry costs 1.5 KB of LDS per workgroup (6 B per lane: kStackEntryBytes), and

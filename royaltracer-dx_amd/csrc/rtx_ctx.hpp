@@ -122,7 +122,9 @@ struct rtx_ctx {
         DevBuf d_stack_ovf;                              // the traversal stack's overflow columns of deeper trees (RTX_OPT_STACK_CAP)
         // diffuse texture maps (sync_textures, rtx_commit.hip): descriptors, the texel pool and the per-material map ids follow the host's tables at every commit that
         // changed them; the two byte -> float tables once; tri_uv only while a map is active (BuiltScene::maps_active), rebuilt when UVs or the triangle numbering changed
+        // (or a cut-out is: BuiltScene::cutouts_active), rebuilt when UVs or the triangle numbering changed; tri_cut only while a cut-out is active, rebuilt with it
         DevBuf d_tri_uv, d_map_kd, d_tex_desc, d_texels, d_tex_lut; bool tri_uv_valid = false; uint32_t ntex = 0;
+        DevBuf d_tri_cut; bool tri_cut_valid = false;
         // environment lighting (sync_environment, rtx_commit.hip): the tables of the bound map, rebuilt by the commit after rtx_set_environment; env_total = their weight sum
         DevBuf d_env_tex, d_env_marg, d_env_cond; double env_total = 0.0;
     } scene;

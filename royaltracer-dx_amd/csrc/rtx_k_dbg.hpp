@@ -8,6 +8,7 @@ namespace rtx {
 // ---------------------------------------------------------------------------------------------
 // kernel-level debug entry points (parity tests): same device functions as the render loop
 // ---------------------------------------------------------------------------------------------
+template <bool CUT>      // CUT: the scene has a cut-out triangle — closest hit and any hit (modes 0 / 1) run the alpha test; the counted forms (modes 2 / 3: tree statistics, the any-hit order probe) never do
 __global__ __launch_bounds__(kBlock) void k_dbg_trace(DevScene sc, const SmallRecPair* __restrict__ small, const F4* __restrict__ rays, uint32_t n, int any, F4* __restrict__ hits) {
     extern __shared__ F4 lds[];
     const TraceLds L = stage_lds(sc, lds);
@@ -18,8 +19,8 @@ __global__ __launch_bounds__(kBlock) void k_dbg_trace(DevScene sc, const SmallRe
         float t, u, v; uint32_t prim;
         if (any == 2) traverse<false, true>(sc, L, mk3(ro.x, ro.y, ro.z), mk3(rd.x, rd.y, rd.z), ro.w, rd.w, t, u, v, prim);
         else if (any == 3) traverse<true, true>(sc, L, mk3(ro.x, ro.y, ro.z), mk3(rd.x, rd.y, rd.z), ro.w, rd.w, t, u, v, prim);      // any-hit in the order sc.any_order, counted (u = node steps, v = triangle tests)
-        else if (any) trace_ray<true>(sc, small, L, mk3(ro.x, ro.y, ro.z), mk3(rd.x, rd.y, rd.z), ro.w, rd.w, t, u, v, prim);
-        else trace_ray<false>(sc, small, L, mk3(ro.x, ro.y, ro.z), mk3(rd.x, rd.y, rd.z), ro.w, rd.w, t, u, v, prim);
+        else if (any) trace_ray<true, CUT>(sc, small, L, mk3(ro.x, ro.y, ro.z), mk3(rd.x, rd.y, rd.z), ro.w, rd.w, t, u, v, prim);
+        else trace_ray<false, CUT>(sc, small, L, mk3(ro.x, ro.y, ro.z), mk3(rd.x, rd.y, rd.z), ro.w, rd.w, t, u, v, prim);
         hits[i] = {t, u, v, u2f(prim)};
     }
 }
@@ -82,6 +83,20 @@ __global__ __launch_bounds__(kBlock) void k_dbg_albedo(DevScene sc, const F4* __
         r = {kd.x, kd.y, kd.z, u2f((uint32_t)tex)};
     }
     out[i] = r;
+}
+// the alpha test of the cut-outs (rtx_cutout.hpp: cut_alpha, the function cut_accept compares with the cut-off) at n hit records -> (alpha, opacity texture id bits); (1, 0xFFFFFFFF)
+// for a miss, for a triangle that is not a cut-out triangle and while no cut-out is active
+__global__ __launch_bounds__(kBlock) void k_dbg_opacity(DevScene sc, const F4* __restrict__ hits, uint32_t n, float* __restrict__ out2) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const F4 h = hits[i];
+    const uint32_t prim = f2u(h.w);
+    float a = 1.0f; uint32_t id = 0xFFFFFFFFu;
+    if (prim != kMissPrim && sc.tri_cut) {
+        const int32_t tex = sc.tri_cut[prim];
+        if (tex >= 0) { a = cut_alpha(sc, (uint32_t)tex, prim, h.y, h.z); id = (uint32_t)tex; }
+    }
+    out2[2 * (size_t)i] = a; out2[2 * (size_t)i + 1] = u2f(id);
 }
 // the environment's sampler and lookup (rtx_env.hpp), as k_shade<.., ENV> runs them (the marginal CDF from global memory: the same values as its LDS copy)
 __global__ __launch_bounds__(kBlock) void k_dbg_env_sample(DevScene sc, const uint32_t* __restrict__ seeds2, uint32_t n, F4* __restrict__ out) {

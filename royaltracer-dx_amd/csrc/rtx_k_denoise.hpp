@@ -13,8 +13,9 @@ constexpr uint32_t kDnTileW = 32, kDnTileH = 8;     // one workgroup = 32 x 8 pi
 
 // Guides: the first hit of every pixel (for_each_first_hit, as k_debug_layer) and surface(); two F4 per pixel: (P, material word) (n, 0).  A pixel that is not filterable by geometry
 // gets (0, 0, 0, kDnNoGeo) (0, 0, 0, 0), so that a tap's class test and its material test are ONE compare of the material word with the centre's.
+template <bool CUT>
 __global__ __launch_bounds__(kBlock) void k_denoise_guides(DevScene sc, const SmallRecPair* __restrict__ small, uint32_t width, uint32_t height, const CameraGPU* __restrict__ cam, F4* __restrict__ guides) {
-    for_each_first_hit(sc, small, width, height, cam, [&](uint32_t i, f3 o, f3 d, float t, float u, float v, uint32_t prim) {
+    for_each_first_hit<CUT>(sc, small, width, height, cam, [&](uint32_t i, f3 o, f3 d, float t, float u, float v, uint32_t prim) {
         F4 g0 = {0.0f, 0.0f, 0.0f, u2f(kDnNoGeo)}, g1 = {0.0f, 0.0f, 0.0f, 0.0f};
         if (prim != kMissPrim) {
             const Surf sf = surface(sc, o, d, t, u, v, prim);

@@ -81,7 +81,8 @@ __device__ __forceinline__ uint32_t pack_rgb8(float r, float g, float b) {
 }
 // The first hit of every pixel (debug layers, denoiser guides): the whole workgroup stages the scene's LDS, then a grid-stride loop traces the pixel-corner primary ray
 // (jitter-free, kTMinCam) and hands pixel index, ray and hit record to body(i, o, d, t, u, v, prim).  Called once, by every thread of the kernel.
-template <class Body>
+// CUT: the scene has a cut-out triangle: the first ACCEPTED hit (rtx_cutout.hpp)
+template <bool CUT, class Body>
 __device__ __forceinline__ void for_each_first_hit(const DevScene& sc, const SmallRecPair* __restrict__ small, uint32_t width, uint32_t height, const CameraGPU* __restrict__ cam, Body body) {
     extern __shared__ F4 lds[];
     const TraceLds L = stage_lds(sc, lds);
@@ -91,13 +92,13 @@ __device__ __forceinline__ void for_each_first_hit(const DevScene& sc, const Sma
         const uint32_t x = i % width, y = i / width;
         f3 o, d; primary_ray(*cam, width, height, x, y, 0.0f, 0.0f, o, d);
         float t, u, v; uint32_t prim;
-        trace_ray<false>(sc, small, L, o, d, kTMinCam, kTMax, t, u, v, prim);
+        trace_ray<false, CUT>(sc, small, L, o, d, kTMinCam, kTMax, t, u, v, prim);
         body(i, o, d, t, u, v, prim);
     }
 }
-template <bool TEX>      // TEX: a texture map is active, layer 13 shows Kd' (rtx_texture.hpp); scenes without one run the instantiation they always ran
+template <bool TEX, bool CUT = false>      // TEX: a texture map is active, layer 13 shows Kd' (rtx_texture.hpp); scenes without one run the instantiation they always ran
 __global__ __launch_bounds__(kBlock) void k_debug_layer(DevScene sc, const SmallRecPair* __restrict__ small, uint32_t width, uint32_t height, const CameraGPU* __restrict__ cam, uint32_t layer, uint32_t* __restrict__ out) {
-    for_each_first_hit(sc, small, width, height, cam, [&](uint32_t i, f3 o, f3 d, float t, float u, float v, uint32_t prim) {
+    for_each_first_hit<CUT>(sc, small, width, height, cam, [&](uint32_t i, f3 o, f3 d, float t, float u, float v, uint32_t prim) {
         uint32_t px = 0xFF000000u;
         if (prim != kMissPrim && layer >= 10u && layer <= 17u) {
             const Surf sf = surface(sc, o, d, t, u, v, prim);

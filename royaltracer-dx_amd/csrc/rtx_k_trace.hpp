@@ -20,10 +20,15 @@ __device__ __forceinline__ void trace_count_flush(unsigned long long* cnt, uint3
                                   // closest-hit kernel took 69 VGPRs = 7 waves once the 6-B stack entries let eight workgroups fit a CU's LDS.)  The generic instantiations (SCHED -1: experiment
                                   // knobs, work counters) stay uncapped: capped they spill
 #endif
+#ifndef RTX_TRACE_WAVES_CUT
+#define RTX_TRACE_WAVES_CUT 8      // ... and their CUT forms (profiles/cutout_kernel_resources.md)
+#endif
 // closest hit for every path in this workgroup's sub-queue: reads ray_o/ray_d, writes hit
-template <int STK, bool STEAL, int SCHED>   // traversal stack: 0 = LDS column, 1 = private (scratch); STEAL: work stealing between sub-queues (refill_steal);
+// CUT (both kernels): the scene has a cut-out triangle (sc.tri_cut != nullptr) and every geometric candidate goes through cut_accept (rtx_cutout.hpp); scenes without one launch
+// the CUT = false instantiations, which are the code they always were.  No STEAL instantiation has a CUT form (RTX_OPT_WORK_STEALING is ignored while cut-outs are active).
+template <int STK, bool STEAL, int SCHED, bool CUT = false>   // traversal stack: 0 = LDS column, 1 = private (scratch); STEAL: work stealing between sub-queues (refill_steal);
                                             // SCHED: the wave schedule as a compile-time constant (the default, 6), or -1 = the run-time parameter (experiment knobs)
-__global__ __launch_bounds__(kBlock, (SCHED >= 0 ? RTX_TRACE_WAVES : 1)) void k_trace_closest(DevScene sc, const SmallRecPair* __restrict__ small, DevPaths p, const uint32_t* __restrict__ queue, const uint32_t* __restrict__ qcount, uint32_t qcap, float tmin, uint32_t refill_min, uint32_t sched, uint32_t* heads,
+__global__ __launch_bounds__(kBlock, (SCHED >= 0 ? (CUT ? RTX_TRACE_WAVES_CUT : RTX_TRACE_WAVES) : 1)) void k_trace_closest(DevScene sc, const SmallRecPair* __restrict__ small, DevPaths p, const uint32_t* __restrict__ queue, const uint32_t* __restrict__ qcount, uint32_t qcap, float tmin, uint32_t refill_min, uint32_t sched, uint32_t* heads,
                                                                        uint32_t nq, uint32_t merge) {           // nq sub-queues in the launch, `merge` of them per workgroup (MergedQ; 1 with STEAL and on the tiny-scene test path)
     extern __shared__ F4 lds[];
     __shared__ uint32_t s_head;
@@ -63,10 +68,10 @@ __global__ __launch_bounds__(kBlock, (SCHED >= 0 ? RTX_TRACE_WAVES : 1)) void k_
         ray_begin(R, mk3(ro.x, ro.y, ro.z), mk3(rd.x, rd.y, rd.z), tmin, kTMax, pid, true);
     };
     while (STEAL ? refill_steal<true>(R, W, drained, refill_min, rng, fetch) : refill<true>(R, &s_head, n, drained, refill_min, [&](uint32_t idx) { uint32_t q, off; M.locate(idx, q, off); fetch(q, off); })) {
-        if (SCHED >= 5) spec_step<false>(sc, L, R, stk, (uint32_t)SCHED);
-        else if (sched >= 5u) spec_step<false, decltype(stk), true>(sc, L, R, stk, sched, &cnt_nodes, &cnt_tris);
-        else if (sched) voted_step<false>(sc, L, R, stk, sched);
-        else { walk_internal<false>(sc, L, R, stk); process_leaf<false>(sc, L, R, stk); }
+        if (SCHED >= 5) spec_step<false, decltype(stk), false, CUT>(sc, L, R, stk, (uint32_t)SCHED);
+        else if (sched >= 5u) spec_step<false, decltype(stk), true, CUT>(sc, L, R, stk, sched, &cnt_nodes, &cnt_tris);
+        else if (sched) voted_step<false, decltype(stk), CUT>(sc, L, R, stk, sched);
+        else { walk_internal<false>(sc, L, R, stk); process_leaf<false, decltype(stk), CUT>(sc, L, R, stk); }
         if (R.has && R.done) { st_stream(p.hit + R.item, F4{R.bt, R.bu, R.bv, u2f(R.bprim)}); R.has = false; }
     }
     if (SCHED < 0 && sc.trace_cnt) trace_count_flush(sc.trace_cnt, cnt_nodes, cnt_tris);      // RTX_OPT_TRACE_COUNTERS (generic instantiation only)
@@ -79,8 +84,8 @@ __global__ __launch_bounds__(kBlock, (SCHED >= 0 ? RTX_TRACE_WAVES : 1)) void k_
 // per slot, so the read-modify-write needs no atomic and the order of additions per path is fixed)
 // SINK 0: the path tracer's NEE rays (visible contributions are added to the path's radiance).  SINK 1: visibility rays of the ReSTIR stages (rtx_restir_wave.hpp):
 // the answer goes to occ[pay[entry]] as a byte, 1 = occluded; end points may be anywhere (last frame's samples), so the tiny-scene path tests every record.
-template <int STK, bool STEAL, int SCHED, int SINK = 0>
-__global__ __launch_bounds__(kBlock, (SCHED >= 0 ? RTX_TRACE_WAVES : 1)) void k_trace_shadow(DevScene sc, const SmallRecPair* __restrict__ small, DevPaths p, const F4* __restrict__ sh_o, const F4* __restrict__ sh_d,
+template <int STK, bool STEAL, int SCHED, int SINK = 0, bool CUT = false>
+__global__ __launch_bounds__(kBlock, (SCHED >= 0 ? (CUT ? RTX_TRACE_WAVES_CUT : RTX_TRACE_WAVES) : 1)) void k_trace_shadow(DevScene sc, const SmallRecPair* __restrict__ small, DevPaths p, const F4* __restrict__ sh_o, const F4* __restrict__ sh_d,
                                                          const F4* __restrict__ sh_c, const uint32_t* __restrict__ shcount, uint32_t qcap, uint32_t refill_min, uint32_t sched, uint32_t* heads,
                                                          uint32_t nq, uint32_t merge, const uint32_t* __restrict__ pay = nullptr, uint8_t* __restrict__ occ = nullptr) {
     extern __shared__ F4 lds[];
@@ -119,13 +124,13 @@ __global__ __launch_bounds__(kBlock, (SCHED >= 0 ? RTX_TRACE_WAVES : 1)) void k_
     auto fetch = [&](uint32_t q, uint32_t idx) {
         const uint32_t gi = q * qcap + idx;                               // (< 2^32: the batch cap)
         const F4 so = sh_o[gi], sd = sh_d[gi];
-        ray_begin(R, mk3(so.x, so.y, so.z), mk3(sd.x, sd.y, sd.z), so.w, sd.w, gi, false, sc.occluder_cache != 0u, sc.any_order);
+        ray_begin(R, mk3(so.x, so.y, so.z), mk3(sd.x, sd.y, sd.z), so.w, sd.w, gi, false, !CUT && sc.occluder_cache != 0u, sc.any_order);      // (RTX_OPT_OCCLUDER_CACHE is ignored while cut-outs are active)
     };
     while (STEAL ? refill_steal<false>(R, W, drained, refill_min, rng, fetch) : refill<false>(R, &s_head, n, drained, refill_min, [&](uint32_t idx) { uint32_t q, off; M.locate(idx, q, off); fetch(q, off); })) {
-        if (SCHED >= 5) spec_step<true>(sc, L, R, stk, (uint32_t)SCHED);
-        else if (sched >= 5u) spec_step<true, decltype(stk), true>(sc, L, R, stk, sched, &cnt_nodes, &cnt_tris);
-        else if (sched) voted_step<true>(sc, L, R, stk, sched);
-        else { walk_internal<true>(sc, L, R, stk); process_leaf<true>(sc, L, R, stk); }
+        if (SCHED >= 5) spec_step<true, decltype(stk), false, CUT>(sc, L, R, stk, (uint32_t)SCHED);
+        else if (sched >= 5u) spec_step<true, decltype(stk), true, CUT>(sc, L, R, stk, sched, &cnt_nodes, &cnt_tris);
+        else if (sched) voted_step<true, decltype(stk), CUT>(sc, L, R, stk, sched);
+        else { walk_internal<true>(sc, L, R, stk); process_leaf<true, decltype(stk), CUT>(sc, L, R, stk); }
         if (R.has && R.done) { finish(R.item, R.bprim != kMissPrim); R.has = false; }
     }
     if (SCHED < 0 && sc.trace_cnt) trace_count_flush(sc.trace_cnt + 2, cnt_nodes, cnt_tris);

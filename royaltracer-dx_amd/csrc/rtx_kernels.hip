@@ -73,9 +73,14 @@ size_t trace_lds_bytes_queue(const DevScene& sc) {   // queue kernels with a pri
     return (size_t)sc.lds_nodes * 80 + (size_t)sc.lds_tris * 48 + small_planes_bytes(sc) + stack;
 }
 
-// workgroups of the two persistent traversal kernels (default instantiations) that fit on a CU with this scene's LDS layout; 0 = query failed
+// workgroups of the two persistent traversal kernels (default instantiations; their CUT forms when the scene launches those) that fit on a CU with this scene's LDS layout; 0 = query failed
 int trace_workgroups_per_cu(const DevScene& sc) {
     int a = 0, b = 0;
+    if (sc.tri_cut) {
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, k_trace_closest<0, false, 6, true>, (int)kBlock, trace_lds_bytes(sc)) != hipSuccess) return 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k_trace_shadow<0, false, 6, 0, true>, (int)kBlock, trace_lds_bytes(sc)) != hipSuccess) return 0;
+        return a < b ? a : b;
+    }
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, k_trace_closest<0, false, 6>, (int)kBlock, trace_lds_bytes(sc)) != hipSuccess) return 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, k_trace_shadow<0, false, 6>, (int)kBlock, trace_lds_bytes(sc)) != hipSuccess) return 0;
     return a < b ? a : b;
@@ -104,9 +109,10 @@ void launch_raygen_shared(hipStream_t st, const DevFrame& f, uint32_t* queue, ui
 // The launch of a persistent traversal kernel (k_trace_closest, k_trace_shadow): clamps `merge`, sizes the grid and maps (sc, heads) to the instantiation — stack kind, stealing,
 // compiled-in schedule, as std::integral_constants (IntC / BoolC above) — and its dynamic LDS.  launch(stk, steal, sched, grid, lds_bytes, heads, merge) does the launch.
 // (launch_trace_occ has a narrower choice of its own: no private stack, no stealing.  Through this helper it would instantiate SINK-1 kernels nobody launches.)
+// A scene with a cut-out triangle (sc.tri_cut) never steals, so that the callers' CUT instantiations exist for the other five combinations only (with_cut below).
 template <class Launch>
 static void launch_trace_variant(const DevFrame& f, const DevScene& sc, uint32_t* heads, uint32_t merge, Launch launch) {
-    if (sc.nsmall) heads = nullptr;                     // (the un-fused tiny-scene test path has no persistent waves)
+    if (sc.nsmall || sc.tri_cut) heads = nullptr;                     // (the un-fused tiny-scene test path has no persistent waves)
     if (heads || sc.nsmall || merge < 1u) merge = 1u;
     if (merge > kMaxMerge) merge = kMaxMerge;
     const uint32_t grid = (f.nblocks + merge - 1u) / merge;
@@ -124,11 +130,17 @@ static void launch_trace_variant(const DevFrame& f, const DevScene& sc, uint32_t
 #endif
     else go(IntC<0>{}, BoolC<false>{}, IntC<-1>{}, trace_lds_bytes(sc));
 }
+// the CUT argument of a traversal launch: go(BoolC<sc.tri_cut != nullptr>) — except for the stealing combinations, which have no CUT instantiation (and are never chosen with cut-outs)
+template <bool STEAL, class Go> static void with_cut(const DevScene& sc, Go go) {
+    if constexpr (STEAL) go(BoolC<false>{}); else dispatch_bool(sc.tri_cut != nullptr, go);
+}
 void launch_trace_closest(hipStream_t st, const DevFrame& f, const DevScene& sc, const DevPaths& p, uint32_t bounce, const uint32_t* queue, const uint32_t* qcount, uint32_t* heads, uint32_t merge) {
     const float tmin = bounce == 0 ? kTMinCam : kSBias;
     launch_trace_variant(f, sc, heads, merge, [&](auto stk, auto steal, auto sched, uint32_t grid, size_t lds_bytes, uint32_t* hd, uint32_t mg) {
-        hipLaunchKernelGGL((k_trace_closest<decltype(stk)::value, decltype(steal)::value, decltype(sched)::value>), dim3(grid), dim3(kBlock), lds_bytes, st,
-                           sc, sc.small, p, queue, qcount, f.qcap, tmin, sc.refill_min, sc.trace_sched, hd, f.nblocks, mg);
+        with_cut<decltype(steal)::value>(sc, [&](auto cut) {
+            hipLaunchKernelGGL((k_trace_closest<decltype(stk)::value, decltype(steal)::value, decltype(sched)::value, decltype(cut)::value>), dim3(grid), dim3(kBlock), lds_bytes, st,
+                               sc, sc.small, p, queue, qcount, f.qcap, tmin, sc.refill_min, sc.trace_sched, hd, f.nblocks, mg);
+        });
     });
 }
 void launch_bounce_small(hipStream_t st, const DevScene& sc, const DevFrame& f, const DevPaths& p, uint32_t bounce_first, uint32_t bounce_end,
@@ -159,8 +171,10 @@ void launch_order_queues(hipStream_t st, const uint32_t* qcount, uint32_t G, uin
 void launch_trace_shadow(hipStream_t st, const DevFrame& f, const DevScene& sc, const DevPaths& p, uint32_t j, const uint32_t* shcount, uint32_t* heads, uint32_t merge) {
     const size_t seg = (size_t)j * f.qcap * f.nblocks;
     launch_trace_variant(f, sc, heads, merge, [&](auto stk, auto steal, auto sched, uint32_t grid, size_t lds_bytes, uint32_t* hd, uint32_t mg) {
-        hipLaunchKernelGGL((k_trace_shadow<decltype(stk)::value, decltype(steal)::value, decltype(sched)::value>), dim3(grid), dim3(kBlock), lds_bytes, st,
-                           sc, sc.small, p, p.sh_o + seg, p.sh_d + seg, p.sh_c + seg, shcount, f.qcap, sc.refill_min, sc.trace_sched, hd, f.nblocks, mg);
+        with_cut<decltype(steal)::value>(sc, [&](auto cut) {
+            hipLaunchKernelGGL((k_trace_shadow<decltype(stk)::value, decltype(steal)::value, decltype(sched)::value, 0, decltype(cut)::value>), dim3(grid), dim3(kBlock), lds_bytes, st,
+                               sc, sc.small, p, p.sh_o + seg, p.sh_d + seg, p.sh_c + seg, shcount, f.qcap, sc.refill_min, sc.trace_sched, hd, f.nblocks, mg);
+        });
     });
 }
 static size_t shade_lds_bytes(const DevScene& sc, bool sort) { uint32_t lb, mb; shade_lds_plan(sc.nlights, sc.nmat, sort, lb, mb); return (size_t)lb + mb; }
@@ -279,7 +293,7 @@ void launch_adaptive_compact(hipStream_t st, const DevFrame& f, const AdaptState
     hipLaunchKernelGGL(k_adaptive_compact, dim3(1), dim3(kCompactBlock), 0, st, f, ad, max_spp, list, out5);
 }
 void launch_denoise_guides(hipStream_t st, uint32_t max_blocks, const DevScene& sc, uint32_t width, uint32_t height, const CameraGPU* cam, F4* guides) {
-    hipLaunchKernelGGL(k_denoise_guides, dim3(grid_for(width * height, max_blocks)), dim3(kBlock), trace_lds_bytes(sc), st, sc, sc.small, width, height, cam, guides);
+    dispatch_bool(sc.tri_cut != nullptr, [&](auto cut) { hipLaunchKernelGGL(k_denoise_guides<decltype(cut)::value>, dim3(grid_for(width * height, max_blocks)), dim3(kBlock), trace_lds_bytes(sc), st, sc, sc.small, width, height, cam, guides); });
 }
 uint32_t denoise_workgroups(uint32_t width, uint32_t height) { return ((width + kDnTileW - 1u) / kDnTileW) * ((height + kDnTileH - 1u) / kDnTileH); }
 void launch_denoise_level(hipStream_t st, DenoiseLevel a, const F4* in, const F4* guides, F4* out, uint32_t* partial, bool staged) {
@@ -298,6 +312,8 @@ void launch_srgb8(hipStream_t st, const F4* accum, uint32_t npix, uint32_t* out)
     hipLaunchKernelGGL(k_srgb8, dim3((npix + kBlock - 1) / kBlock), dim3(kBlock), 0, st, accum, npix, out);
 }
 void launch_debug_layer(hipStream_t st, uint32_t max_blocks, const DevScene& sc, uint32_t width, uint32_t height, const CameraGPU* cam, uint32_t layer, uint32_t* out) {
+    // (a scene with a cut-out triangle has tri_uv set: the one CUT form is the TEX one)
+    if (sc.tri_cut) { hipLaunchKernelGGL((k_debug_layer<true, true>), dim3(grid_for(width * height, max_blocks)), dim3(kBlock), trace_lds_bytes(sc), st, sc, sc.small, width, height, cam, layer, out); return; }
     dispatch_bool(sc.tri_uv != nullptr, [&](auto tex) { hipLaunchKernelGGL(k_debug_layer<decltype(tex)::value>, dim3(grid_for(width * height, max_blocks)), dim3(kBlock), trace_lds_bytes(sc), st, sc, sc.small, width, height, cam, layer, out); });
 }
 void launch_pack_tiles(hipStream_t st, uint32_t max_blocks, const DevFrame& f, const F4* accum, F4* slab) {
@@ -307,7 +323,7 @@ void launch_unpack_tiles(hipStream_t st, uint32_t max_blocks, const DevFrame& f,
     hipLaunchKernelGGL(k_unpack_tiles, dim3(grid_for(f.npl * nshards, max_blocks)), dim3(kBlock), 0, st, f, nshards, slabs, accum);
 }
 void launch_dbg_trace(hipStream_t st, const DevScene& sc, const F4* rays, uint32_t n, int any, F4* hits) {
-    hipLaunchKernelGGL(k_dbg_trace, dim3(grid_for(n, 2048)), dim3(kBlock), trace_lds_bytes(sc), st, sc, sc.small, rays, n, any, hits);
+    dispatch_bool(sc.tri_cut != nullptr && (any == 0 || any == 1), [&](auto cut) { hipLaunchKernelGGL(k_dbg_trace<decltype(cut)::value>, dim3(grid_for(n, 2048)), dim3(kBlock), trace_lds_bytes(sc), st, sc, sc.small, rays, n, any, hits); });
 }
 void launch_dbg_surface(hipStream_t st, const DevScene& sc, const F4* rays, const F4* hits, uint32_t n, F4* out) {
     hipLaunchKernelGGL(k_dbg_surface, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, sc, rays, hits, n, out);
@@ -323,6 +339,9 @@ void launch_dbg_tex_sample(hipStream_t st, const DevScene& sc, uint32_t tex, con
 }
 void launch_dbg_albedo(hipStream_t st, const DevScene& sc, const F4* hits, uint32_t n, F4* out) {
     hipLaunchKernelGGL(k_dbg_albedo, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, sc, hits, n, out);
+}
+void launch_dbg_opacity(hipStream_t st, const DevScene& sc, const F4* hits, uint32_t n, float* out2) {
+    hipLaunchKernelGGL(k_dbg_opacity, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, sc, hits, n, out2);
 }
 void launch_dbg_env_sample(hipStream_t st, const DevScene& sc, const uint32_t* seeds2, uint32_t n, F4* out) {
     hipLaunchKernelGGL(k_dbg_env_sample, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, sc, seeds2, n, out);

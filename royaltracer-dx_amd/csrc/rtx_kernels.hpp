@@ -37,7 +37,7 @@ struct DevScene {
     const float* tri_uv;                // 6 floats per GLOBAL triangle id (indexed like `shade`): the (u, v) of its three corners
     const int32_t* map_kd;              // per material: texture id of RTX_MAP_KD, or -1
     const TexDesc* tex_desc; uint32_t ntex;
-    const uint32_t* texels;             // the texel pool, RGBA8 (r in the low byte)
+    const uint32_t* texels;             // the texel pool, RGBA8 (r in the low byte, alpha in the high byte)
     const float* tex_lut;               // byte -> float: [0, 256) linear, [256, 512) sRGB
     // environment lighting (rtx_env.hpp).  env_n = 0: none bound.  env_tex is nullptr unless the bound map has weight: a scene without one, or with an all-black one, launches the
     // kernels it always launched (launch_shade picks k_shade<.., ENV> by this pointer)
@@ -46,6 +46,9 @@ struct DevScene {
     const float* env_cond;              // conditional CDF, N entries per row
     uint32_t env_n, env_flags;          // RTX_ENV_*
     float env_rot[9];                   // env_to_world's upper 3x3, [row * 3 + column]
+    // alpha cut-outs (rtx_cutout.hpp; the LAST member: every other one keeps its place in the kernel arguments).  nullptr unless some triangle is a cut-out triangle: such scenes launch what they always launched; otherwise tri_uv and map_kd are set too
+    // (map_kd all -1 where no material has a diffuse map) and the traversal kernels' CUT instantiations run
+    const int32_t* tri_cut;             // per GLOBAL triangle id (indexed like tri_uv): the opacity texture of a cut-out triangle, or -1
 };
 
 // one sample batch of one frame
@@ -250,6 +253,7 @@ void launch_dbg_tex_sample(hipStream_t, const DevScene&, uint32_t tex, const flo
 void launch_dbg_albedo(hipStream_t, const DevScene&, const F4* hits, uint32_t n, F4* out);                         // tex_albedo at n hit records -> (Kd', texture id bits or 0xFFFFFFFF)
 // the environment's device functions (rtx_env.hpp): env_sample at n seeds -> 3 F4 per seed (world direction, pdf | L, texel bits | seed after the four draws, 0, 0);
 // env_eval at n directions -> 2 F4 per direction (L, pdf | texel bits, r3, 0, 0).  sc.env_* must be set (the probes set them for a black map too)
+void launch_dbg_opacity(hipStream_t, const DevScene&, const F4* hits, uint32_t n, float* out2);                    // cut_alpha at n hit records -> (alpha, opacity texture id bits or 0xFFFFFFFF)
 void launch_dbg_env_sample(hipStream_t, const DevScene&, const uint32_t* seeds2, uint32_t n, F4* out);
 void launch_dbg_env_eval(hipStream_t, const DevScene&, const float* dirs3, uint32_t n, F4* out);
 void launch_dbg_tea(hipStream_t, uint32_t s0, uint32_t s1, uint32_t n, float* out, uint32_t* seed_out);

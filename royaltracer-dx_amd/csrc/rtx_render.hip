@@ -181,7 +181,7 @@ int render_frame(rtx_ctx* c, const rtx_params* p, const DevFrame& f_real, uint32
     const uint32_t nee = (c->dsc.nlights ? p->nee_samples : 0) + (c->dsc.env_tex ? 1u : 0u);
     const bool tiny_fused = c->dsc.nsmall && c->opt.fused;
     // (the other wave schedules are experiment knobs of the separate kernels; with a texture map active the separate kernels run whatever the option says: k_bounce_bvh samples no image)
-    const bool fused_bvh = !c->dsc.nsmall && c->opt.fused_bvh && c->opt.trace_sched >= 5u && !c->dsc.tri_uv && !c->dsc.env_n;
+    const bool fused_bvh = !c->dsc.nsmall && c->opt.fused_bvh && c->opt.trace_sched >= 5u && !c->dsc.tri_uv && !c->dsc.tri_cut && !c->dsc.env_n;
     const BatchPlan B = plan_batches(c, spp, f, fused_bvh);
     const uint32_t bspp = B.bspp, G = B.G;
     const uint64_t cap64 = (uint64_t)f.npl * bspp;
@@ -203,7 +203,7 @@ int render_frame(rtx_ctx* c, const rtx_params* p, const DevFrame& f_real, uint32
     if (fused_bvh) HIPCHK(c, c->pt.d_hitq.ensure(qtot * 4));
     FrameRun R{};
     R.G = G; R.mb = p->max_bounces; R.nee = nee; R.nee1 = std::max<uint32_t>(nee, 1); R.compact = B.compact;
-    R.stealing = !c->dsc.nsmall && !fused_bvh && c->opt.work_stealing && p->max_bounces > 0;
+    R.stealing = !c->dsc.nsmall && !fused_bvh && c->opt.work_stealing && !c->dsc.tri_cut && p->max_bounces > 0;      // (no stealing instantiation has a CUT form)
     R.hstride = (size_t)G + (G + 31) / 32;                                   // per trace launch: G fetch cursors + the exhausted bitmap
     R.nheads = R.stealing ? (size_t)p->max_bounces * (1 + std::max<uint32_t>(nee, 1)) * R.hstride : 0;
     if (R.stealing) HIPCHK(c, c->pt.d_heads.ensure(R.nheads * 4));

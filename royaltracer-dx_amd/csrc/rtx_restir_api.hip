@@ -51,7 +51,7 @@ static int rs_plan(rtx_ctx* c, const DevFrame& f, uint32_t nitems, const uint32_
 static int rs_pass1(rtx_ctx* c, const DevFrame& f, uint32_t sample_id, F4* accum, const uint32_t* pixels, uint32_t npixels, uint32_t* const* bufs, uint32_t lane, hipStream_t st) {
     const uint32_t mb = f.max_bounces, rows = 4u + mb + 1u;
     RsPlan R; int r = rs_plan(c, f, pixels ? npixels : f.npl, pixels, rows, R, lane); if (r) return r;
-    const DevScene& sc = c->dsc; const RsQ& q = R.q;
+    DevScene sc = c->dsc; sc.tri_cut = nullptr; const RsQ& q = R.q;      // (the ReSTIR frame ignores alpha cut-outs, as it ignores map_Kd: its closest-hit launches are the plain instantiations)
     const CameraGPU* cam = (const CameraGPU*)c->d_cam.p;
     auto row = [&](uint32_t k) { return R.cnt + (size_t)k * R.G; };
     uint32_t* res_di = (uint32_t*)c->rs.d_res_di.p; uint32_t* res_gi = (uint32_t*)c->rs.d_res_gi.p; uint32_t* sdata = (uint32_t*)c->rs.d_sdata.p;

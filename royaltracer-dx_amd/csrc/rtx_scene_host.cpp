@@ -71,7 +71,7 @@ bool SceneHost::set_materials(const void* mats, uint32_t count) {
     mats128.assign((const float*)mats, (const float*)mats + (size_t)count * 32);
     mats_dirty = true;
     if (any_map()) tex_dirty = true;
-    map_kd.clear();                             // the table is replaced: no material of the new one has a map
+    map_kd.clear(); map_opacity.clear();        // the table is replaced: no material of the new one has a map
     return true;
 }
 
@@ -162,10 +162,11 @@ bool SceneHost::set_texture(uint32_t tex, const void* rgba8, uint32_t width, uin
 }
 bool SceneHost::set_material_map(uint32_t material, uint32_t slot, int32_t tex) {
     if (material >= mats128.size() / 32) { err = "set_material_map: unknown material"; return false; }
-    if (slot != 0u) { err = "set_material_map: unknown slot (RTX_MAP_KD is the only one)"; return false; }
+    if (slot != 0u && slot != 2u) { err = "set_material_map: unknown slot (RTX_MAP_KD = 0 or RTX_MAP_OPACITY = 2)"; return false; }
     if (tex < -1 || (tex >= 0 && (size_t)tex >= textures.size())) { err = "set_material_map: unknown texture"; return false; }
-    if (map_kd.size() < mats128.size() / 32) map_kd.resize(mats128.size() / 32, -1);
-    map_kd[material] = tex;
+    std::vector<int32_t>& map = slot == 2u ? map_opacity : map_kd;
+    if (map.size() < mats128.size() / 32) map.resize(mats128.size() / 32, -1);
+    map[material] = tex;
     tex_dirty = true;
     return true;
 }
@@ -173,6 +174,19 @@ bool SceneHost::maps_active() const {
     if (!any_map()) return false;
     for (size_t i = 0; i < matids.size(); i += 3) if (matids[i] < map_kd.size() && map_kd[matids[i]] >= 0) return true;      // (a triangle's material is the id of its first index entry: flatten_range)
     return false;
+}
+bool SceneHost::cutouts_active() const {
+    if (!any_opacity_map()) return false;
+    for (size_t i = 0; i < matids.size(); i += 3) if (cut_texture(matids[i]) >= 0) return true;
+    return false;
+}
+void SceneHost::fill_tri_cut(std::vector<int32_t>& out) const {
+    size_t nt = 0; for (const InstHost& in : insts) nt += meshes[in.mesh].idx.size() / 3;
+    out.assign(nt, -1);
+    for (const InstHost& in : insts) {
+        const MeshHost& m = meshes[in.mesh];
+        for (size_t t = 0; t < m.idx.size() / 3; t++) out[(size_t)in.tri_base + t] = cut_texture(matids[m.matid_base + 3 * t]);
+    }
 }
 bool SceneHost::only_maps_changed(const BuiltScene& b) const {
     if (topo_dirty || mats_dirty || !dirty_meshes.empty() || b.insts.size() != insts.size()) return false;
@@ -443,8 +457,9 @@ bool SceneHost::build(BuiltScene& B) {
     // shortcut are derived from geometry, and a hidden triangle may take part in none of them (identical results by the parity contract)
     // ... and so does one with an active texture map (k_bounce_small and k_primary_surface sample no image)
     // ... and one with an environment bound (k_bounce_small's misses end black)
-    B.maps_active = maps_active(); B.env_active = env.n != 0;
-    if (B.any_hidden || B.maps_active || B.env_active) { B.small_recs.clear(); B.small_tris.clear(); B.small_poly.clear(); B.small_nrec = 0; B.small_nocc = 0; }
+    // ... and one with a cut-out triangle (the pre-test path runs no alpha test)
+    B.maps_active = maps_active(); B.cutouts_active = cutouts_active(); B.env_active = env.n != 0;
+    if (B.any_hidden || B.maps_active || B.cutouts_active || B.env_active) { B.small_recs.clear(); B.small_tris.clear(); B.small_poly.clear(); B.small_nrec = 0; B.small_nocc = 0; }
     else build_small_scene(B, wtri, scale);
     sw.lap("tris8 / small scene");
     B.any_order = probe_anyhit_order(B);

@@ -58,4 +58,24 @@ int rtx_debug_albedo(rtx_ctx* c, const float* rays8, const float* hits4, uint32_
     return RTX_OK;
 }
 
+// hits4 as rtx_debug_trace_closest writes them -> (alpha as the traversal computes it, opacity texture id as uint bits): cut_alpha of rtx_cutout.hpp, the function cut_accept compares
+int rtx_debug_opacity(rtx_ctx* c, const float* hits4, uint32_t n, float* out2) {
+    BIND(c);
+    if (!c->committed) { c->err = "scene not committed"; return RTX_ERR_STATE; }
+    if (!n) return RTX_OK;
+    if (!hits4 || !out2) { c->err = "opacity: null array"; return RTX_ERR_INVALID; }
+    for (uint32_t i = 0; i < n; i++) {                       // a triangle id the scene does not have would index past the per-triangle tables
+        uint32_t prim; memcpy(&prim, &hits4[(size_t)i * 4 + 3], 4);
+        if (prim != kMissPrim && prim >= c->stats.triangles) { c->err = "opacity: triangle id out of range"; return RTX_ERR_INVALID; }
+    }
+    DevBuf d_hits, d_out;
+    HIPCHK(c, d_hits.ensure((size_t)n * 16)); HIPCHK(c, d_out.ensure((size_t)n * 8));
+    TO_DEVICE(c, d_hits.p, hits4, (size_t)n * 16);
+    launch_dbg_opacity(c->stream, c->dsc, (const F4*)d_hits.p, n, (float*)d_out.p);
+    HIPCHK(c, hipGetLastError());
+    TO_HOST(c, out2, d_out.p, (size_t)n * 8);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RTX_OK;
+}
+
 }  // extern "C"

@@ -6,23 +6,17 @@
 #pragma once
 #include "rtx_kernels.hpp"
 #include "rtx_bsdf.hpp"
+#include "rtx_cutout.hpp"
 
 namespace rtx {
 
-__device__ __forceinline__ int tex_wrap(int i, int n) { return ((i % n) + n) % n; }
-
-// Sample(tex, s, t): repeat wrap, OBJ's v upward (row 0 of the image is its top), bilinear over the four nearest texel centres, no mip levels
+// Sample(tex, s, t): repeat wrap, OBJ's v upward (row 0 of the image is its top), bilinear over the four nearest texel centres, no mip levels (the addressing: tex_taps, rtx_cutout.hpp)
 __device__ __forceinline__ f3 tex_sample(const DevScene& sc, uint32_t tex, float s, float t) {
     const TexDesc td = sc.tex_desc[tex];
     const float* T = sc.tex_lut + ((td.flags & 1u) ? 256u : 0u);
-    const int W = (int)td.width, H = (int)td.height;
-    const float fs = s - floorf(s), ft = t - floorf(t);
-    const float x = fs * (float)W - 0.5f, y = (1.0f - ft) * (float)H - 0.5f;
-    const float x0 = floorf(x), y0 = floorf(y);
-    const float fx = x - x0, fy = y - y0;
-    const int ix0 = tex_wrap((int)x0, W), ix1 = tex_wrap((int)x0 + 1, W), iy0 = tex_wrap((int)y0, H), iy1 = tex_wrap((int)y0 + 1, H);
-    const uint32_t* px = sc.texels + td.offset;
-    const uint32_t p00 = px[(size_t)iy0 * W + ix0], p10 = px[(size_t)iy0 * W + ix1], p01 = px[(size_t)iy1 * W + ix0], p11 = px[(size_t)iy1 * W + ix1];
+    const TexTaps P = tex_taps(sc, td, s, t);
+    const float fx = P.fx, fy = P.fy;
+    const uint32_t p00 = P.p00, p10 = P.p10, p01 = P.p01, p11 = P.p11;
     float c[3];
 #pragma unroll
     for (int k = 0; k < 3; k++) {

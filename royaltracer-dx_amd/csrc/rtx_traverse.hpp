@@ -1,10 +1,11 @@
 // rtx_traverse.hpp — ray traversal on the device: LDS staging, the exact triangle test, the compressed 8-wide BVH (node step, simple and
 // persistent-wave traversal with the while-while / voted / speculative schedules), the tiny-scene pre-test path, packet culling.
 // The rules every traversal shares are written once: safe_idir, root_group, load_tri, closer (the tie rule of the closest hit); traverse<ANY, COUNT> is
-// the one simple traversal (COUNT: with the statistics counters), TraceStack<STK> the stack of the persistent kernels.
+// the one simple traversal (COUNT: with the statistics counters; CUT: with the alpha test of cut-out triangles, rtx_cutout.hpp), TraceStack<STK> the stack of the persistent kernels.
 #pragma once
 #include <type_traits>
 #include "rtx_dev_common.hpp"
+#include "rtx_cutout.hpp"       // cut_accept: the alpha test of the CUT instantiations
 
 namespace rtx {
 
@@ -282,7 +283,9 @@ __device__ __forceinline__ bool closer(float t, uint32_t gid, const float& bt, c
 
 // COUNT: also counts node steps and triangle tests and returns them in bu / bv at every exit instead of the barycentrics (rtx_debug_trace_stats: tree-quality
 // measurements; ANY: the any-hit order probe of a GPU-built tree, rtx_commit.hip).  bt and bprim are what the plain traversal returns.
-template <bool ANY, bool COUNT = false>
+// CUT (every traversal below alike; scenes with a cut-out triangle only, sc.tri_cut != nullptr): a geometric candidate on a cut-out triangle counts only if its alpha is accepted
+// (cut_accept); a rejected one leaves the best record untouched.  CUT = false is the code it always was.
+template <bool ANY, bool COUNT = false, bool CUT = false>
 __device__ __forceinline__ void traverse(const DevScene& sc, const TraceLds& L, f3 o, f3 d, float tmin, float tmax,
                                          float& bt, float& bu, float& bv, uint32_t& bprim) {
     uint32_t nsteps = 0, ntris = 0;
@@ -302,6 +305,7 @@ __device__ __forceinline__ void traverse(const DevScene& sc, const TraceLds& L, 
             load_tri(sc, L, tri_slot8(T, bit), v0, e1, e2);
             float t, u, w;
             if (tri_test(o, d, v0, e1, e2, tmin, tmax, t, u, w)) {
+                if (CUT && !cut_accept(sc, f2u(v0.w), u, w)) continue;
                 if (ANY) { bprim = 0u; if (COUNT) { bu = (float)nsteps; bv = (float)ntris; } return; }
                 const uint32_t gid = f2u(v0.w);
                 if (closer(t, gid, bt, bprim)) { bt = t; bu = u; bv = w; bprim = gid; }
@@ -438,11 +442,11 @@ __device__ __forceinline__ void traverse_small(const DevScene& sc, const SmallRe
     }
 }
 
-template <bool ANY>
+template <bool ANY, bool CUT = false>      // (a scene with a cut-out triangle has no pre-test records: it runs on the general path)
 __device__ __forceinline__ void trace_ray(const DevScene& sc, const SmallRecPair* __restrict__ small, const TraceLds& L, f3 o, f3 d, float tmin, float tmax,
                                           float& bt, float& bu, float& bv, uint32_t& bprim) {
-    if (sc.nsmall) traverse_small<ANY>(sc, small, L, o, d, tmin, tmax, bt, bu, bv, bprim, sc.nsmall);
-    else traverse<ANY>(sc, L, o, d, tmin, tmax, bt, bu, bv, bprim);
+    if (!CUT && sc.nsmall) traverse_small<ANY>(sc, small, L, o, d, tmin, tmax, bt, bu, bv, bprim, sc.nsmall);
+    else traverse<ANY, false, CUT>(sc, L, o, d, tmin, tmax, bt, bu, bv, bprim);
 }
 
 // Tiny-scene bounce 0: generate the primary ray AND trace it; only paths that hit something are enqueued (their
@@ -561,14 +565,14 @@ __device__ __forceinline__ void walk_internal(const DevScene& sc, const TraceLds
         next_group(R, stk);
     }
 }
-template <bool ANY>
+template <bool ANY, bool CUT = false>
 __device__ __forceinline__ void tri_step(const DevScene& sc, const TraceLds& L, RayLane& R) {
     const uint32_t bit = (uint32_t)__builtin_ctz(R.T.bits);
     R.T.bits &= R.T.bits - 1u;
     v4f v0, e1, e2;
     load_tri(sc, L, tri_slot8(R.T, bit), v0, e1, e2);
     float t, u, w;
-    if (tri_test(R.o, R.d, v0, e1, e2, R.tmin, R.tmax, t, u, w)) {
+    if (tri_test(R.o, R.d, v0, e1, e2, R.tmin, R.tmax, t, u, w) && (!CUT || cut_accept(sc, f2u(v0.w), u, w))) {
         if (ANY) { R.bprim = 0u; R.done = true; R.T.bits = 0u; }
         else {
             const uint32_t gid = f2u(v0.w);
@@ -580,8 +584,9 @@ __device__ __forceinline__ void tri_step(const DevScene& sc, const TraceLds& L, 
 // beats the lane's best; any hit: a hit) — the caller applies it after the wave-uniform node / triangle branch has merged.  Updating the
 // lane's best record inside the branch made the compiler keep it in a second register set there and copy it on every edge of the
 // (nested) control flow: 12-24 v_mov per iteration, ~10 % of the loop's VALU instructions.
-template <bool ANY>
-__device__ __forceinline__ bool tri_candidate(const DevScene& sc, const TraceLds& L, RayLane& R, float& t, float& u, float& w, uint32_t& gid) {
+// CUT: also reports the candidate's GLOBAL triangle id (cut_gid) — the caller runs the alpha test where it applies the candidate, for the same reason.
+template <bool ANY, bool CUT = false>
+__device__ __forceinline__ bool tri_candidate(const DevScene& sc, const TraceLds& L, RayLane& R, float& t, float& u, float& w, uint32_t& gid, uint32_t* cut_gid = nullptr) {
     const uint32_t bit = (uint32_t)__builtin_ctz(R.T.bits);
     R.T.bits &= R.T.bits - 1u;
     const uint32_t slot = tri_slot8(R.T, bit);
@@ -589,17 +594,18 @@ __device__ __forceinline__ bool tri_candidate(const DevScene& sc, const TraceLds
     load_tri(sc, L, slot, v0, e1, e2);
     const bool hit = tri_test_flat(R.o, R.d, v0, e1, e2, R.tmin, R.tmax, t, u, w);
     gid = ANY ? slot : f2u(v0.w);                      // any-hit: the occluder's slot (occluder cache); closest hit: the global triangle id
+    if (CUT) *cut_gid = f2u(v0.w);
     if (ANY) return hit;
     return hit & ((t < R.bt) | ((t == R.bt) & (gid < R.bprim)));      // closer(), the definition of the tie rule, in the branch-free form this step needs (see above)
 }
-template <bool ANY, class STK>
+template <bool ANY, class STK, bool CUT = false>
 __device__ __forceinline__ void process_leaf(const DevScene& sc, const TraceLds& L, RayLane& R, STK& stk) {
-    while (R.has && !R.done && R.T.bits) tri_step<ANY>(sc, L, R);
+    while (R.has && !R.done && R.T.bits) tri_step<ANY, CUT>(sc, L, R);
     if (R.has && !R.done) next_group(R, stk);
 }
 // Voted schedule (trace_sched 1-4): instead of "walk until EVERY lane holds triangles, then test every lane's triangles"
 // each iteration the wave votes for the step most of its busy lanes are waiting for: one node step, or one triangle test.
-template <bool ANY, class STK>
+template <bool ANY, class STK, bool CUT = false>
 __device__ __forceinline__ void voted_step(const DevScene& sc, const TraceLds& L, RayLane& R, STK& stk, uint32_t sched) {
     const bool busy = R.has && !R.done;
     const bool in_tri = busy && R.T.bits != 0u;
@@ -609,7 +615,7 @@ __device__ __forceinline__ void voted_step(const DevScene& sc, const TraceLds& L
     if (ni * wn >= nl * wl) {
         if (in_node) { descend8<!ANY>(sc, L, R.o, R.idir, R.oct, R.tmin, R.bt, R.G, R.T, stk, R.sp); next_group(R, stk); }
     } else if (in_tri) {
-        tri_step<ANY>(sc, L, R);
+        tri_step<ANY, CUT>(sc, L, R);
         if (!R.done) next_group(R, stk);
     }
 }
@@ -626,7 +632,7 @@ __device__ unsigned long long g_wgt[2 * 65536];
 __device__ unsigned long long g_trv[8];      // tooling (PROFILE build): node iterations, lanes in them, triangle iterations, lanes in them, busy lanes summed over iterations, iterations
 #endif
 // COUNT (the generic instantiations with RTX_OPT_TRACE_COUNTERS): the lane's node steps and triangle tests are tallied in cnt_nodes / cnt_tris (work per ray for the bench record)
-template <bool ANY, class STK, bool COUNT = false>
+template <bool ANY, class STK, bool COUNT = false, bool CUT = false>
 __device__ __forceinline__ void spec_step(const DevScene& sc, const TraceLds& L, RayLane& R, STK& stk, uint32_t sched, uint32_t* cnt_nodes = nullptr, uint32_t* cnt_tris = nullptr) {
     const bool busy = R.has && !R.done;
     const bool has_tri = busy && R.T.bits != 0u;
@@ -651,17 +657,17 @@ __device__ __forceinline__ void spec_step(const DevScene& sc, const TraceLds& L,
     // place after both moves P up when T is empty.  (Placing the new group into "T if empty, else P" inside the node branch and shifting inside
     // the triangle branch is the same state machine, but the compiler then kept two register copies of both groups and paid 12-20 v_mov per
     // iteration to shuttle between them.)
-    bool upd = false; float ct, cu, cw; uint32_t cg;                        // (set by the triangle branch only)
+    bool upd = false; float ct, cu, cw; uint32_t cg, cgg = 0u;              // (set by the triangle branch only; cgg: the candidate's global id, CUT only)
     if (ni * wn >= nl * wl && ni) {
         if (can_node) {
             if (!(R.G.bits & 0xffu)) { R.sp--; R.G = stk.get(R.sp); }
             descend8<!ANY>(sc, L, R.o, R.idir, R.oct, R.tmin, R.bt, R.G, R.P[0], stk, R.sp, ANY ? nullptr : &R.om);
             if (COUNT) *cnt_nodes += 1u;
         }
-    } else if (has_tri) { upd = tri_candidate<ANY>(sc, L, R, ct, cu, cw, cg); if (COUNT) *cnt_tris += 1u; }
+    } else if (has_tri) { upd = tri_candidate<ANY, CUT>(sc, L, R, ct, cu, cw, cg, CUT ? &cgg : nullptr); if (COUNT) *cnt_tris += 1u; }
     uint32_t updv = upd ? 1u : 0u;
     asm volatile("" : "+v"(updv));                                          // opaque: keeps the update below OUT of the branch above (the optimiser would thread it back in)
-    if (updv) {
+    if (updv && (!CUT || cut_accept(sc, cgg, cu, cw))) {                    // (CUT: a rejected candidate leaves the best record untouched)
         if (ANY) { R.bprim = 0u; R.done = true; R.T.bits = 0u; R.occluder = cg; }
         else { R.bt = ct; R.bu = cu; R.bv = cw; R.bprim = cg; }
     }
@@ -680,7 +686,7 @@ __device__ __forceinline__ void spec_step(const DevScene& sc, const TraceLds& L,
             }
         }
     } else if (has_tri) {
-        tri_step<ANY>(sc, L, R);
+        tri_step<ANY, CUT>(sc, L, R);
         if (!R.T.bits) {
             R.T = R.P[0];
 #pragma unroll

@@ -253,12 +253,25 @@ bool ReadTGA(const std::string& path, std::vector<uint8_t>& rgba8, uint32_t& w, 
     std::vector<uint8_t> b;
     return read_file(path, b, err) && tga_from(b, path, rgba8, w, h, err);
 }
-bool ReadImage(const std::string& path, std::vector<uint8_t>& rgba8, uint32_t& w, uint32_t& h, std::string& err) {
+bool ReadImage(const std::string& path, std::vector<uint8_t>& rgba8, uint32_t& w, uint32_t& h, uint32_t& channels, std::string& err) {
     std::vector<uint8_t> b;
     if (!read_file(path, b, err)) return false;
-    if (b.size() >= 2 && b[0] == 'P' && (b[1] == '5' || b[1] == '6')) return pnm_from(b, path, rgba8, w, h, err);
+    if (b.size() >= 2 && b[0] == 'P' && (b[1] == '5' || b[1] == '6')) {
+        if (!pnm_from(b, path, rgba8, w, h, err)) return false;
+        channels = b[1] == '6' ? 3u : 1u;
+        return true;
+    }
     if (!tga_from(b, path, rgba8, w, h, err)) { err = path + ": neither a binary PPM / PGM nor a true-colour TGA (" + err + ")"; return false; }
+    channels = b[16] / 8u;                                  // (tga_from accepted the header: 24 or 32 bits)
     return true;
+}
+bool ReadImage(const std::string& path, std::vector<uint8_t>& rgba8, uint32_t& w, uint32_t& h, std::string& err) {
+    uint32_t channels = 0;
+    return ReadImage(path, rgba8, w, h, channels, err);
+}
+void OpacityAlphaFromChannels(std::vector<uint8_t>& rgba8, uint32_t channels) {
+    if (channels == 4u) return;
+    for (size_t i = 0; i + 3 < rgba8.size(); i += 4) rgba8[i + 3] = rgba8[i];
 }
 
 bool ReadHDR(const std::string& path, std::vector<float>& rgb32f, uint32_t& w, uint32_t& h, std::string& err) {

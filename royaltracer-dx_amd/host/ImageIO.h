@@ -20,6 +20,11 @@ bool ReadPNM(const std::string& path, std::vector<uint8_t>& rgba8, uint32_t& wid
 bool ReadTGA(const std::string& path, std::vector<uint8_t>& rgba8, uint32_t& width, uint32_t& height, std::string& err);
 // by content (P5 / P6 magic, else a TGA header that makes sense)
 bool ReadImage(const std::string& path, std::vector<uint8_t>& rgba8, uint32_t& width, uint32_t& height, std::string& err);
+// ... and the file's own channel count: 1 (PGM), 3 (PPM, 24-bit TGA) or 4 (32-bit TGA); untouched on failure
+bool ReadImage(const std::string& path, std::vector<uint8_t>& rgba8, uint32_t& width, uint32_t& height, uint32_t& channels, std::string& err);
+// The alpha byte of an image that serves as an OPACITY map (map_d; include/rtx.h, ALPHA CUT-OUTS): a file with an alpha channel of its own (channels == 4) keeps it, any other
+// gets its first (grey / red) channel as alpha.  rgba8: whole RGBA8 pixels (a trailing partial pixel is left alone)
+void OpacityAlphaFromChannels(std::vector<uint8_t>& rgba8, uint32_t channels);
 
 // HIGH-DYNAMIC-RANGE images (environment maps), as top-down float RGB (width * height * 3):
 //   HDR : Radiance RGBE, FORMAT=32-bit_rle_rgbe, flat or new-style run-length encoded scanlines, the -Y H +X W orientation only; (m, e) -> m * 2^(e - 136), e = 0 -> 0

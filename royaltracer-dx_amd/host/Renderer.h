@@ -14,6 +14,7 @@ public:
     // headless configuration (the reference hard-codes these: Renderer.cpp:363, 46-48; Common_v6.hlsl:8-12)
     void SetModels(const std::vector<std::string>& obj_files, const std::string& mtl_dir) { m_models = obj_files; m_mtlDir = mtl_dir; m_haveScene = false; }
     void SetScene(const Scene& s) { m_scene = s; m_haveScene = true; }
+    void SetCutouts(SceneCutouts c) { m_cutouts = c; }          // which opacity maps SetModels' OBJ files load (rtx_render --no-cutouts / --kd-alpha); the default is their map_d images
     void SetLoadTextures(bool on) { m_loadTextures = on; }      // false: SetModels' OBJ files load without their map_Kd images (rtx_render --no-textures)
     void SetDevice(int ordinal) { m_device = ordinal; }
     rtx_params& Params() { return m_params; }
@@ -65,7 +66,7 @@ private:
     void Check(int rc, const char* what);
     UINT m_width, m_height; float m_aspectRatio; std::string m_title;
     std::vector<std::string> m_models; std::string m_mtlDir;
-    Scene m_scene; bool m_haveScene = false, m_loadTextures = true;
+    Scene m_scene; bool m_haveScene = false, m_loadTextures = true; SceneCutouts m_cutouts = kCutoutsMapD;
     int m_device = 0;
     rtx_ctx* m_ctx = nullptr;
     rtx_params m_params{}, m_restir{};

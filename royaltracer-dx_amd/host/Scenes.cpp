@@ -542,7 +542,7 @@ Scene MakeBistroClass(uint32_t target, uint32_t seed, bool hard) {
 }
 
 // the reference's startup scene (Renderer.cpp:363-407, 444-449, 46-48)
-Scene LoadObjScene(const std::vector<std::string>& files, const std::string& mtl_dir, bool load_textures) {
+Scene LoadObjScene(const std::vector<std::string>& files, const std::string& mtl_dir, bool load_textures, SceneCutouts cutouts) {
     Scene s; s.name = "obj";
     UINT materialIDOffset = 0, materialVertexOffset = 0;       // Renderer members of the same name
     size_t total_ids = 0;
@@ -559,15 +559,28 @@ Scene LoadObjScene(const std::vector<std::string>& files, const std::string& mtl
     s.eye = XMFLOAT3(-1.5f, 1.5f, 3.5f); s.center = XMFLOAT3(0, 1, 0); s.up = XMFLOAT3(0, 1, 0);   // Renderer.cpp:46-48
     s.images.resize(s.textures.size());
     std::vector<char> tried(s.textures.size(), 0);
-    for (const MaterialExt& x : s.materialExt) {               // the diffuse maps only: no kernel samples another slot
-        const int t = x.map[MAP_KD];
-        if (!load_textures || t < 0 || (size_t)t >= s.textures.size() || tried[t]) continue;
+    auto load = [&](int t, const char* what) {                 // the diffuse and the opacity maps only: no kernel samples another slot
+        if (!load_textures || t < 0 || (size_t)t >= s.textures.size() || tried[t]) return;
         tried[t] = 1;
         std::string dir = mtl_dir; if (!dir.empty() && dir.back() != '/') dir += '/';
         std::string name = s.textures[t]; std::replace(name.begin(), name.end(), '\\', '/');
         std::string err; SceneImage img;
-        if (ReadImage((!name.empty() && name[0] == '/') ? name : dir + name, img.rgba, img.width, img.height, err)) s.images[t] = std::move(img);
-        else fprintf(stderr, "map_Kd skipped: %s\n", err.c_str());
+        if (ReadImage((!name.empty() && name[0] == '/') ? name : dir + name, img.rgba, img.width, img.height, img.channels, err)) s.images[t] = std::move(img);
+        else fprintf(stderr, "%s skipped: %s\n", what, err.c_str());
+    };
+    for (const MaterialExt& x : s.materialExt) load(x.map[MAP_KD], "map_Kd");
+    if (load_textures && cutouts != kCutoutsOff) {
+        s.opacityMaps.assign(s.materialExt.size(), -1);
+        std::vector<char> opacity(s.textures.size(), 0);       // images some material reads its alpha from
+        for (size_t m = 0; m < s.materialExt.size(); m++) {
+            const MaterialExt& x = s.materialExt[m];
+            int t = x.map[MAP_D];
+            if (t >= 0) load(t, "map_d");
+            else if (cutouts == kCutoutsKdAlpha) { t = x.map[MAP_KD]; if (t < 0 || (size_t)t >= s.images.size() || s.images[t].channels != 4u) t = -1; }
+            if (t < 0 || (size_t)t >= s.images.size() || !s.images[t].width) continue;
+            s.opacityMaps[m] = t; opacity[t] = 1;
+        }
+        for (size_t t = 0; t < s.images.size(); t++) if (opacity[t]) OpacityAlphaFromChannels(s.images[t].rgba, s.images[t].channels);
     }
     return s;
 }
@@ -613,6 +626,10 @@ int BindSceneMaps(const Scene& s, rtx_ctx* ctx) {
     for (size_t m = 0; m < s.materialExt.size() && m < s.materials.size(); m++) {
         const int t = s.materialExt[m].map[MAP_KD];
         if (t >= 0 && (size_t)t < id.size() && id[t] >= 0 && (r = rtx_set_material_map(ctx, (uint32_t)m, RTX_MAP_KD, id[t]))) return r;
+    }
+    for (size_t m = 0; m < s.opacityMaps.size() && m < s.materials.size(); m++) {
+        const int t = s.opacityMaps[m];
+        if (t >= 0 && (size_t)t < id.size() && id[t] >= 0 && (r = rtx_set_material_map(ctx, (uint32_t)m, RTX_MAP_OPACITY, id[t]))) return r;
     }
     return RTX_OK;
 }

@@ -11,7 +11,7 @@
 
 struct SceneModel { std::vector<Vertex> vertices; std::vector<UINT> indices; std::vector<UINT> materialIDs;
                     std::vector<float> uvs; };      // one (u, v) per entry of `indices` (the OBJ's vt, per corner), or empty
-struct SceneImage { uint32_t width = 0, height = 0; std::vector<uint8_t> rgba; };      // a decoded texture, top-down RGBA8; width 0 = not loaded
+struct SceneImage { uint32_t width = 0, height = 0; std::vector<uint8_t> rgba; uint32_t channels = 0; };      // a decoded texture, top-down RGBA8; width 0 = not loaded; channels: the file's own (1, 3 or 4)
 struct SceneInstance { UINT model; XMMATRIX transform; };
 // an environment map for rtx_set_environment: n x n octahedral float RGB (n = 0: none), the 16-float env_to_world (haveRotation false: identity), scale, RTX_ENV_* flags
 struct SceneEnvironment { uint32_t n = 0; std::vector<float> rgb; bool haveRotation = false; float toWorld[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}; float scale = 1.0f; uint32_t flags = 0; };
@@ -26,6 +26,8 @@ struct Scene {
     std::vector<std::string> textures;       // texture map ids the 128-byte record has no room for (Vertex.h:21 "ADD MAP IDs LATER"), and the distinct map file names
     std::vector<SceneImage> images;          // index-aligned with `textures`: the decoded map_Kd files (host/ImageIO readers); an entry that no map_Kd names, or whose file
                                              // is missing or in another format, stays empty.  BindSceneMaps hands the loaded ones to a context, sRGB-encoded
+    std::vector<int> opacityMaps;            // per material: the entry of `textures` bound as its opacity map (RTX_MAP_OPACITY: its map_d, or with kCutoutsKdAlpha its 32-bit map_Kd), or
+                                             // -1; empty = none.  The alpha byte of such an image is the file's own alpha channel (32-bit TGA) or its first channel (PGM / PPM / 24-bit TGA)
     std::vector<SceneModel> models;
     std::vector<SceneInstance> instances;
     XMFLOAT3 eye{0, 0, 1}, center{0, 0, 0}, up{0, 1, 0};
@@ -43,8 +45,12 @@ Scene MakeBistroClass(uint32_t target_tris = 3800000, uint32_t seed = 3800, bool
 // the reference's own startup scene: each file through ObjLoader::loadObjFile, one instance per model,
 // instance 1 rotated 1.57 rad about Y (Renderer.cpp:363-407, 444-449)
 // load_textures: decode every file a map_Kd names, relative to mtl_dir (a file that cannot be read is skipped with one line on stderr)
-Scene LoadObjScene(const std::vector<std::string>& files, const std::string& mtl_dir, bool load_textures = true);
-// rtx_set_mesh_uvs / rtx_set_texture / rtx_set_material_map for what the scene carries; a scene without a decoded image binds nothing.  Before rtx_commit_scene
+// cutouts (ignored without load_textures): kCutoutsOff = no opacity maps (the scene as it was before cut-outs existed); kCutoutsMapD = the images the map_d statements name —
+// a map_d that names its material's map_Kd file is ONE texture in both slots; kCutoutsKdAlpha = additionally a material WITHOUT a map_d whose map_Kd file has an alpha channel of its
+// own (32-bit TGA) gets that texture as its opacity map (opt-in: no existing scene changes)
+enum SceneCutouts { kCutoutsOff = 0, kCutoutsMapD = 1, kCutoutsKdAlpha = 2 };
+Scene LoadObjScene(const std::vector<std::string>& files, const std::string& mtl_dir, bool load_textures = true, SceneCutouts cutouts = kCutoutsMapD);
+// rtx_set_mesh_uvs / rtx_set_texture / rtx_set_material_map (both slots) for what the scene carries; a scene without a decoded image binds nothing.  Before rtx_commit_scene
 int BindSceneMaps(const Scene&, rtx_ctx*);
 // rtx_set_environment for what the scene carries (n = 0: clears the context's).  Before rtx_commit_scene
 int BindSceneEnvironment(const SceneEnvironment&, rtx_ctx*);

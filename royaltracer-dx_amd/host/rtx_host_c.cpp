@@ -75,6 +75,12 @@ rtxh_scene* rtxh_scene_from_obj(const char* const* files, uint32_t n, const char
     std::string dir = mtl_dir ? mtl_dir : "./";
     return guarded([&] { return LoadObjScene(f, dir); });
 }
+rtxh_scene* rtxh_scene_from_obj_ex(const char* const* files, uint32_t n, const char* mtl_dir, uint32_t flags) {
+    std::vector<std::string> f; for (uint32_t i = 0; i < n; i++) f.emplace_back(files[i]);
+    std::string dir = mtl_dir ? mtl_dir : "./";
+    const SceneCutouts cut = (flags & RTXH_OBJ_NO_CUTOUTS) ? kCutoutsOff : (flags & RTXH_OBJ_KD_ALPHA) ? kCutoutsKdAlpha : kCutoutsMapD;
+    return guarded([&] { return LoadObjScene(f, dir, !(flags & RTXH_OBJ_NO_TEXTURES), cut); });
+}
 void rtxh_scene_free(rtxh_scene* s) { delete s; }
 const char* rtxh_last_error(void) { return g_err.c_str(); }
 
@@ -97,6 +103,7 @@ int rtxh_scene_texture_pixels(const rtxh_scene* s, uint32_t i, const void** rgba
     *rgba8 = have ? s->s.images[i].rgba.data() : nullptr; *width = have ? s->s.images[i].width : 0; *height = have ? s->s.images[i].height : 0;
     return RTX_OK;
 }
+int rtxh_scene_opacity_map(const rtxh_scene* s, uint32_t material) { return material < s->s.opacityMaps.size() ? s->s.opacityMaps[material] : -1; }
 int rtxh_scene_mesh_uvs(const rtxh_scene* s, uint32_t i, const float** uv2, uint32_t* nidx) {
     if (!uv2 || !nidx || i >= s->s.models.size()) return RTX_ERR_INVALID;
     const SceneModel& m = s->s.models[i];

@@ -19,6 +19,8 @@
 //                   guided by first-hit position, normal and material; defaults: 5 levels, 0.5, 2^-6 of the scene's extent) and --out gets the DENOISED image; works with
 //                   --adaptive and with --gpus N (on rank 0, after the gather); refused with --mode restir (that frame has its own reuse passes)
 //                   [--no-textures]   OBJ scenes: do not read the images their map_Kd statements name (binary PPM / PGM, 24- / 32-bit TGA): the image without diffuse maps
+//                   [--no-cutouts]    OBJ scenes: do not bind the images their map_d statements name as opacity maps (alpha cut-outs): the image with every card opaque
+//                   [--kd-alpha]      OBJ scenes: a material without a map_d whose map_Kd is a 32-bit TGA gets that texture's alpha as its opacity map too
 //                   [--env FILE [--env-res N] [--env-yaw DEG] [--env-scale S] [--env-hidden]]   environment lighting (rtx_set_environment): FILE is a latitude-longitude Radiance .hdr or
 //                   colour .pfm, resampled to an N x N octahedral map (default 512), turned by DEG degrees about +Y, radiance times S; --env-hidden: camera rays that miss stay black
 //                   [--sky R,G,B]   a constant sky of that radiance instead of a file; both work with --gpus N (every rank binds the same map) and are ignored by --mode restir
@@ -43,7 +45,8 @@ static const char* kUsage =
     "                  [--mode pt|restir] [--literal] [--halo px] [--force-gather] [--orbit deg] [--spin deg] [--hide i[,j...]] [--blink i] [--only-rank r]\n"
     "                  [--adaptive THRESHOLD [--min-spp N] [--step-spp N]]\n"
     "                  [--denoise [--denoise-levels N] [--sigma-color X] [--sigma-plane X]]   write the denoised image to --out (path tracer only)\n"
-    "                  [--no-textures]   OBJ scenes: ignore map_Kd images\n"
+    "                  [--no-textures]   OBJ scenes: ignore map_Kd images (implies --no-cutouts)\n"
+    "                  [--no-cutouts]    OBJ scenes: ignore map_d images (no alpha cut-outs)   [--kd-alpha]   a 32-bit map_Kd without a map_d is its material's opacity map too\n"
     "                  [--env FILE [--env-res N] [--env-yaw DEG] [--env-scale S] [--env-hidden]] [--sky R,G,B]   environment lighting\n"
     "                  [--gpus N [--devices 0,1,..] [--gather rccl|copy]]\n";
 
@@ -54,7 +57,7 @@ int main(int argc, char** argv) {
     std::vector<UINT> hide; int blink = -1;
     bool adaptive = false; rtx_adaptive ad{}; ad.min_spp = 8; ad.step_spp = 8;
     bool denoise = false; rtx_denoise_params dnp{};
-    bool textures = true;
+    bool textures = true; SceneCutouts cutouts = kCutoutsMapD; bool kd_alpha = false;
     std::string env_file, sky; UINT env_res = 512; float env_yaw = 0.0f, env_scale = 1.0f; bool env_hidden = false;
     for (int i = 1; i < argc; i++) {
         auto arg = [&](const char* k) { return !strcmp(argv[i], k) && i + 1 < argc; };
@@ -65,7 +68,7 @@ int main(int argc, char** argv) {
         else if (arg("--hide")) { std::stringstream ss(argv[++i]); std::string t; while (std::getline(ss, t, ',')) hide.push_back((UINT)atoi(t.c_str())); } else if (arg("--blink")) blink = atoi(argv[++i]);
         else if (arg("--adaptive")) { adaptive = true; ad.threshold = (float)atof(argv[++i]); } else if (arg("--min-spp")) ad.min_spp = (uint32_t)atoi(argv[++i]); else if (arg("--step-spp")) ad.step_spp = (uint32_t)atoi(argv[++i]);
         else if (!strcmp(argv[i], "--help") || !strcmp(argv[i], "-h")) { fputs(kUsage, stdout); return 0; }
-        else if (!strcmp(argv[i], "--no-textures")) textures = false;
+        else if (!strcmp(argv[i], "--no-textures")) textures = false; else if (!strcmp(argv[i], "--no-cutouts")) cutouts = kCutoutsOff; else if (!strcmp(argv[i], "--kd-alpha")) kd_alpha = true;
         else if (arg("--env")) env_file = argv[++i]; else if (arg("--env-res")) env_res = (UINT)atoi(argv[++i]); else if (arg("--env-yaw")) env_yaw = (float)atof(argv[++i]);
         else if (arg("--env-scale")) env_scale = (float)atof(argv[++i]); else if (!strcmp(argv[i], "--env-hidden")) env_hidden = true; else if (arg("--sky")) sky = argv[++i];
         else if (!strcmp(argv[i], "--denoise")) denoise = true; else if (arg("--denoise-levels")) dnp.levels = (uint32_t)atoi(argv[++i]); else if (arg("--sigma-color")) dnp.sigma_color = (float)atof(argv[++i]); else if (arg("--sigma-plane")) dnp.sigma_plane = (float)atof(argv[++i]);
@@ -73,6 +76,7 @@ int main(int argc, char** argv) {
         else if (arg("--out")) out = argv[++i]; else if (arg("--device")) device = atoi(argv[++i]); else if (!strcmp(argv[i], "--lambert")) lambert = true;
         else { fprintf(stderr, "unknown argument %s\n", argv[i]); return 2; }
     }
+    if (kd_alpha && cutouts != kCutoutsOff) cutouts = kCutoutsKdAlpha;
     if (mode != "pt" && mode != "restir") { fprintf(stderr, "--mode must be pt or restir\n"); return 2; }
     const bool restir = mode == "restir";
     if (restir) { if (!nee_set) nee = 4; if (!bounces_set) bounces = 3; }
@@ -107,7 +111,7 @@ int main(int argc, char** argv) {
             else { std::stringstream ss(devlist); std::string t; while (std::getline(ss, t, ',')) devs.push_back(atoi(t.c_str())); }
             if ((int)devs.size() != gpus) { fprintf(stderr, "--devices must list %d ordinals\n", gpus); return 2; }
             Scene sc = scene == "cornell" ? MakeCornellBox() : scene == "sponza" ? MakeSponzaClass() : scene == "bistro" ? MakeBistroClass() : Scene();
-            if (scene == "obj") { std::vector<std::string> f; std::stringstream ss(objs); std::string t; while (std::getline(ss, t, ',')) f.push_back(t); sc = LoadObjScene(f, mtl, textures); }
+            if (scene == "obj") { std::vector<std::string> f; std::stringstream ss(objs); std::string t; while (std::getline(ss, t, ',')) f.push_back(t); sc = LoadObjScene(f, mtl, textures, cutouts); }
             if (scene == "cornell") lambert = true;
             if (env.n) sc.environment = env;
             MultiGpuFrame mg(devs, gather == "copy" ? MultiGpuFrame::Gather::COPY : MultiGpuFrame::Gather::RCCL, force_gather, only_rank);      // --force-gather: the collective also with one rank
@@ -153,7 +157,7 @@ int main(int argc, char** argv) {
         if (scene == "cornell") { r.SetScene(MakeCornellBox()); lambert = true; }
         else if (scene == "sponza") r.SetScene(MakeSponzaClass());
         else if (scene == "bistro") r.SetScene(MakeBistroClass());
-        else { std::vector<std::string> f; std::stringstream ss(objs); std::string t; while (std::getline(ss, t, ',')) f.push_back(t); r.SetLoadTextures(textures); r.SetModels(f, mtl); }
+        else { std::vector<std::string> f; std::stringstream ss(objs); std::string t; while (std::getline(ss, t, ',')) f.push_back(t); r.SetLoadTextures(textures); r.SetCutouts(cutouts); r.SetModels(f, mtl); }
         if (env.n) r.SetEnvironment(env);
         r.Params().spp = spp; r.Params().max_bounces = bounces; r.Params().nee_samples = nee; r.Params().flags = lambert ? RTX_FLAG_LAMBERT_ONLY : (scene == "bistro" ? RTX_FLAG_TRANSMISSION : 0);
         if (restir) {
