@@ -174,7 +174,7 @@ int rtx_set_option(rtx_ctx* c, int option, int64_t value) {
     case RTX_OPT_LDS_NODES_CLOSEST: c->opt.lds_closest_opt = (int)value; if (c->committed) pick_lds_closest(c); return RTX_OK;
     case RTX_OPT_SMALL_SCENE: c->opt.small_scene = value != 0; c->committed = false; return RTX_OK;
     case RTX_OPT_FUSED_BOUNCE: c->opt.fused = value != 0; return RTX_OK;
-    case RTX_OPT_BOUNCE_VARIANT: c->opt.bounce_ring = value == 0; return RTX_OK;     // 0 (default): LDS hit ring between trace and shading; 1: trace and shade the same 256 entries
+    case RTX_OPT_BOUNCE_VARIANT: c->opt.bounce_variant = value == 2 ? 2 : (value != 0 ? 1 : 0); return RTX_OK;     // 0: workgroup-wide LDS hit ring between trace and shading; 1: trace and shade the same 256 entries; 2: wave-private rings, no barrier inside a bounce
     case RTX_OPT_SHARED_PRIMARY: c->opt.shared_primary = value != 0; return RTX_OK;
     case RTX_OPT_STACK_PRIVATE: c->opt.stack_private = (int)value; c->committed = false; return RTX_OK;
     case RTX_OPT_LPT_ORDER: c->opt.lpt_order = value != 0; return RTX_OK;

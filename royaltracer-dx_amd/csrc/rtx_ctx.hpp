@@ -62,7 +62,7 @@ struct rtx_ctx {
         int lds_closest_opt = -1;                   // RTX_OPT_LDS_NODES_CLOSEST
         bool small_scene = true;                    // RTX_OPT_SMALL_SCENE
         bool fused = true;                          // RTX_OPT_FUSED_BOUNCE
-        bool bounce_ring = true;                    // RTX_OPT_BOUNCE_VARIANT
+        int bounce_variant = 2;                     // RTX_OPT_BOUNCE_VARIANT: 0 workgroup hit ring, 1 no ring, 2 wave-private rings
         bool shared_primary = true;                 // RTX_OPT_SHARED_PRIMARY
         int stack_private = -1;                     // RTX_OPT_STACK_PRIVATE
         bool lpt_order = true;                      // RTX_OPT_LPT_ORDER: fused kernels take their sub-queues longest first

@@ -3,6 +3,7 @@
 // Uses the PF_* section-profile macros that rtx_kernels.hip defines before it includes this file.
 #pragma once
 #include "rtx_shade.hpp"
+#include "rtx_k_bounce_wave.hpp"   // the body of RING == 2
 
 namespace rtx {
 
@@ -14,7 +15,9 @@ namespace rtx {
 // (fewer live registers, fewer SGPR spills through v_writelane / v_readlane in the loop).
 // HAVE_HIT: 0 = bounces >= 1 (the kernel traces its extension rays); bounce 0: 1 = path state and hit record come from k_raygen_trace_small, 2 = RTX_OPT_SHARED_PRIMARY: the
 // path starts from its pixel's shared record (k_primary_surface) and derives sample, slot and seeds from its id (PrimIn) — no surface() here, and nothing per path read but the queue word
-template <int WAVES, int HAVE_HIT, bool LAMBERT, bool RING>
+// RING (bounces >= 1, RTX_OPT_BOUNCE_VARIANT): 1 = workgroup-wide LDS hit ring between trace and shading (variant 0); 0 = trace and shade the same 256 entries (variant 1);
+// 2 = wave-private rings, no barrier inside a bounce (variant 2): its body is bounce_small_wave(), rtx_k_bounce_wave.hpp
+template <int WAVES, int HAVE_HIT, bool LAMBERT, int RING>
 __global__ __launch_bounds__(kBlock, WAVES) void k_bounce_small(DevScene sc, const SmallRecPair* __restrict__ small, DevFrame f_in, DevPaths p,
                                                          uint32_t bounce_first, uint32_t bounce_end,
                                                          uint32_t* __restrict__ queue_a, uint32_t* __restrict__ queue_b /* bounce b reads (b & 1 ? b : a), writes the other */,
@@ -27,6 +30,8 @@ __global__ __launch_bounds__(kBlock, WAVES) void k_bounce_small(DevScene sc, con
     // (workgroup-scope release / acquire: the path state and queue entries a bounce writes are read by the same workgroup).  A frame has
     // two fused launches (bounce 0, which reads the primary hits, and bounces 1 .. max_bounces - 1) instead of eight, and no drain /
     // ramp-up between the bounces; the sparsely populated late bounces cost a few loop trips instead of a launch each.
+    if constexpr (RING == 2) { bounce_small_wave<LAMBERT>(sc, small, f_in, p, bounce_first, bounce_end, queue_a, queue_b, qrows, srows, order); return; }
+    else {
     extern __shared__ F4 lds[];
     __shared__ uint32_t s_cnt[1 + kMaxNee];
     const DevFrame f = frame_with_lambert<LAMBERT>(f_in);           // bit 0 of the flags known at compile time
@@ -219,6 +224,7 @@ __global__ __launch_bounds__(kBlock, WAVES) void k_bounce_small(DevScene sc, con
 #ifdef RTX_WAVE_CLOCK
     RTX_WAVE_STAMP_B(1u);
 #endif
+    }
 }
 
 }  // namespace rtx

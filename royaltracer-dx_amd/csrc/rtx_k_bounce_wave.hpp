@@ -1,0 +1,207 @@
+// rtx_k_bounce_wave.hpp — the wave-private form of the fused tiny-scene bounce kernel (k_bounce_small<.., 0, .., RING = 2>, RTX_OPT_BOUNCE_VARIANT = 2)
+// One of the kernel headers of rtx_kernels.hip; included by rtx_k_bounce_small.hpp, whose kernel calls bounce_small_wave() as its whole body for RING == 2.
+// Uses the PF_* section-profile macros that rtx_kernels.hip defines before it includes the kernel headers.
+#pragma once
+#include "rtx_shade.hpp"
+
+namespace rtx {
+
+// LDS written by some lanes of a wave and read by others of the SAME wave: the hardware executes a wave's LDS instructions in order, so all that is needed is that the
+// compiler keeps the program order of the accesses (wavefront-scope fences emit no instruction)
+__device__ __forceinline__ void wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// Bounces [bounce_first, bounce_end), bounce_first >= 1, of the workgroup's sub-queue — the same work, arithmetic and radiance order as the RING == 1 body of k_bounce_small,
+// scheduled per WAVE instead of per workgroup: inside a bounce no wave ever waits for another.
+//   input     a wave takes the next 64 queue entries from an LDS cursor (s_in, one atomic per chunk): the four waves stay balanced whatever their rays cost
+//   hit buffer  per wave, 64 entries (path id + hit record) in LDS that only this wave touches; a trace pass pushes its hits with ballot + mbcnt at a wave-uniform
+//             count held in a register (no LDS atomic).  The wave traces until it has >= 64 hits or the input is exhausted, then shades min(64, avail) entries.  A pass that
+//             takes the count to 64 + r keeps its last r hits in registers until the 64 buffered ones are popped (a few instructions later) and then writes them to slots 0 .. r - 1:
+//             what a 128-entry ring would hold, in half the LDS — with 64-entry buffers the Lambert instantiation keeps five workgroups per CU, with 128-entry rings it would run three
+//   shadow    nee_sample's rays go into a second wave-private buffer of 64 entries (origin + tmin flag, direction + tmax, contribution + path id), filled the same
+//             way; when a push takes it to 64 the wave traces one FULL block and every lane whose ray is unoccluded adds its entry's contribution to that path's radiance (a plain
+//             read-modify-write), then the rest of the push goes to the front of the emptied buffer.
+//             A path has at most one pending entry per block: with nee_samples == 1 by construction (one push per path and bounce); with nee_samples > 1 the buffer is drained after
+//             every NEE slot's push, before slot j + 1 pushes, so a path's slots are added in order and never by two lanes at once.  The buffer is drained, as a partial block,
+//             before the wave leaves the bounce: with the bounce-end barrier, a path's additions of bounce b are complete before bounce b + 1 reads its radiance — the oracle's
+//             order (emissive, NEE slot 0, 1, ..., next bounce).  An emissive hit and an NEE entry of the same path cannot coexist within a bounce (add_emissive XOR shading).
+//             (An immediate form — no shadow buffer, the wave traces its shadow rays right after nee_sample at the 2/3 of the lanes that pushed — measured slower: docs/REJECTED.md.)
+// INVARIANTS.  (1) Barriers: the only workgroup barriers are the table-staging one and the three at each bounce boundary (end of bounce, counters published, counters reset);
+// every wave executes each exactly once per bounce, outside every data-dependent loop.  There is no producer / consumer protocol between waves.  (2) Termination: every loop ends
+// because the input cursor only grows (a wave that reads a cursor >= n never asks again in this bounce) and a buffer only drains once the input is exhausted (each trip of the
+// outer loop pops >= 1 entry of the hit buffer or ends the bounce; a shadow block empties the shadow buffer).
+template <bool LAMBERT>
+__device__ __forceinline__ void bounce_small_wave(const DevScene& sc, const SmallRecPair* __restrict__ small, const DevFrame& f_in, const DevPaths& p, uint32_t bounce_first, uint32_t bounce_end,
+                                                  uint32_t* __restrict__ queue_a, uint32_t* __restrict__ queue_b, uint32_t* __restrict__ qrows, uint32_t* __restrict__ srows, const uint32_t* __restrict__ order) {
+    extern __shared__ F4 lds[];
+    constexpr uint32_t kWaves = kBlock / 64u, kHitBuf = 64u, kShBuf = 64u;
+    __shared__ uint32_t s_cnt[1 + kMaxNee];
+    __shared__ uint32_t s_in;                                          // input cursor of the bounce: next unclaimed queue entry
+    __shared__ uint32_t s_hpid[kWaves * kHitBuf];
+    __shared__ F4 s_hhit[kWaves * kHitBuf];
+    __shared__ F4 s_so[kWaves * kShBuf], s_sd[kWaves * kShBuf], s_sc[kWaves * kShBuf];
+    const DevFrame f = frame_with_lambert<LAMBERT>(f_in);
+    const uint32_t qid = order ? order[blockIdx.x] : blockIdx.x;
+#ifdef RTX_WAVE_CLOCK
+    #define RTX_WAVE_STAMP_W(K) do { const uint32_t w_ = blockIdx.x * (kBlock / 64u) + (threadIdx.x >> 6); if (lane_id() == 0 && w_ < 65536u) g_wgt[2u * w_ + (K)] = __builtin_amdgcn_s_memrealtime(); } while (0)
+    RTX_WAVE_STAMP_W(0u);
+#endif
+    if (threadIdx.x <= kMaxNee) s_cnt[threadIdx.x] = 0;
+    if (threadIdx.x == 0) s_in = 0;
+    // the light list and the material table in LDS, as in k_bounce_small
+#ifndef RTX_NO_SMALL_LDS_TABLES
+    constexpr uint32_t kSmallLights = 32, kSmallMats = 16;
+    __shared__ F4 s_lt[kSmallLights * 5]; __shared__ float s_ltcdf[kSmallLights]; __shared__ F4 s_mt[kSmallMats * 10];
+    const bool lt_lds = sc.nlights && sc.nlights <= kSmallLights, mt_lds = sc.nmat && sc.nmat <= kSmallMats;
+    if (lt_lds) { for (uint32_t i = threadIdx.x; i < sc.nlights * 5u; i += kBlock) s_lt[i] = ((const F4*)sc.lights)[i]; if (threadIdx.x < sc.nlights) s_ltcdf[threadIdx.x] = sc.cdf[threadIdx.x]; }
+    if (mt_lds) for (uint32_t i = threadIdx.x; i < sc.nmat * 10u; i += kBlock) s_mt[i] = ((const F4*)sc.mats)[i];
+    const MatGPU* mats = mt_lds ? (const MatGPU*)s_mt : sc.mats;
+    const LightGPU* lds_lights = lt_lds ? (const LightGPU*)s_lt : nullptr; const float* lds_cdf = lt_lds ? s_ltcdf : nullptr;
+#else
+    const MatGPU* mats = sc.mats; const LightGPU* lds_lights = nullptr; const float* lds_cdf = nullptr;
+#endif
+    const uint32_t G = gridDim.x;
+    uint32_t n = qrows[(size_t)bounce_first * G + qid];
+    const uint32_t nee = sc.nlights ? f.nee_samples : 0u;
+    const uint32_t nee1 = nee ? nee : 1u;
+    const TraceLds L = stage_lds(sc, lds);
+    __syncthreads();
+    const size_t qb = (size_t)qid * f.qcap;
+    const uint32_t lane = lane_id();
+    const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    uint32_t* const hpid = s_hpid + wv * kHitBuf; F4* const hhit = s_hhit + wv * kHitBuf;      // this wave's buffers
+    F4* const sho = s_so + wv * kShBuf; F4* const shd = s_sd + wv * kShBuf; F4* const shc = s_sc + wv * kShBuf;
+    PF_BEGIN;
+    for (uint32_t bounce = bounce_first; bounce < bounce_end; bounce++) {
+        const bool last = (bounce + 1u == f.max_bounces);
+        const float tmin = bounce_tmin(bounce);
+        const uint32_t* myq = ((bounce & 1u) ? queue_b : queue_a) + qb;
+        uint32_t* mynext = ((bounce & 1u) ? queue_a : queue_b) + qb;
+        uint32_t hcnt = 0;                                          // hit buffer: entries waiting (wave-uniform register; < 64 between trace passes)
+        uint32_t shcnt = 0;                                         // lane j: shadow rays this wave pushed for NEE slot j in this bounce
+        bool in_done = false;                                       // this wave has seen the cursor at or past n
+        uint32_t scnt = 0;                                          // shadow buffer, likewise
+        // trace the first k <= 64 entries of the shadow buffer (all it holds) and add the unoccluded contributions
+        auto shadow_block = [&](uint32_t k) {
+            wave_lds_sync();                                        // the pushes are visible to the lanes that trace them
+            const bool mine = lane < k;
+            const uint32_t e = lane;
+            const F4 ro = mine ? sho[e] : F4{0, 0, 0, 0}, rd = mine ? shd[e] : F4{0, 0, 1, 0};
+            float st_, su_, sv_; uint32_t sprim;
+            // hull-face shortcut only if no ray of this block starts near a hull plane (flag in the sign of tmin, TriShade::guard_tau)
+            const uint32_t nrec_sh = __builtin_amdgcn_ballot_w64(mine && ro.w < 0.0f) != 0ull ? sc.nsmall : sc.nsmall_occ;
+            traverse_small<true>(sc, small, L, mk3(ro.x, ro.y, ro.z), mk3(rd.x, rd.y, rd.z), fabsf(ro.w), mine ? rd.w : 0.0f, st_, su_, sv_, sprim, nrec_sh, ~0ull, pf, 6);
+            if (mine && sprim == kMissPrim) {
+                const F4 c = shc[e];
+                const uint32_t pid = f2u(c.w);
+                F4 radv = p.rad[pid];      // (issued before the traversal instead, for every lane of the block: 4 more live VGPRs, measured the same — docs/REJECTED.md)
+                radv.x = radv.x + c.x; radv.y = radv.y + c.y; radv.z = radv.z + c.z;
+                p.rad[pid] = radv;
+            }
+            wave_lds_sync();                                        // the entries are read before a later push reuses their slots
+            PF_MARK(8);
+        };
+        for (;;) {
+            PF_MARK(0);
+            // ---- trace phase: trace input chunks until this wave has a full wave of hits (or the input runs out) ----
+            bool full = false, carry = false;                        // full (uniform): the last pass took the count to 64 or more; carry: this lane's hit of that pass is beyond slot 63
+            uint32_t cpid = 0, cprim = kMissPrim, ce = 0, hnext = 0; float ct = 0.0f, cu = 0.0f, cv = 0.0f;
+            while (!in_done && !full) {
+                uint32_t c0 = 0;
+                if (lane == 0) c0 = atomicAdd(&s_in, 64u);
+                c0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)c0);
+                if (c0 >= n) { in_done = true; break; }
+                const uint32_t i = c0 + lane;
+                const bool act = i < n;
+                uint32_t pid = 0; f3 ro = mk3(0, 0, 0), rd = mk3(0, 0, 1);
+                if (act) { pid = myq[i]; const F4 a = p.ray_o[pid], b = p.ray_d[pid]; ro = mk3(a.x, a.y, a.z); rd = mk3(b.x, b.y, b.z); }
+                float ht, hu, hv; uint32_t hp;
+                traverse_small<false>(sc, small, L, ro, rd, tmin, act ? kTMax : 0.0f, ht, hu, hv, hp, sc.nsmall, ~0ull, pf, 1);   // inactive lanes: empty interval
+                const bool hit = act && hp != kMissPrim;
+                const unsigned long long hmask = __ballot(hit);
+                const uint32_t e = hcnt + __builtin_amdgcn_mbcnt_hi((uint32_t)(hmask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)hmask, 0u));
+                if (hit && e < kHitBuf) { hpid[e] = pid; hhit[e] = {ht, hu, hv, u2f(hp)}; }
+                const uint32_t tot = hcnt + (uint32_t)__popcll(hmask);        // < 64 waiting + <= 64 pushed
+                if (tot >= kHitBuf) { full = true; hnext = tot - kHitBuf; carry = hit && e >= kHitBuf; ce = e - kHitBuf; cpid = pid; ct = ht; cu = hu; cv = hv; cprim = hp; }
+                else hcnt = tot;
+            }
+            const uint32_t take = full ? 64u : hcnt;
+            if (take == 0u) break;                                  // input exhausted and buffer drained: this wave is done with the bounce
+            const bool active = lane < take;
+            PathState S; S.pid = 0; S.o = mk3(0, 0, 0); S.d = mk3(0, 0, 1); S.thr = mk3(0, 0, 0); S.prev_pdf = 1.0f; S.s0 = S.s1 = 0;
+            float t = 0.0f, u = 0.0f, v = 0.0f; uint32_t prim = kMissPrim;
+            wave_lds_sync();                                        // the pushes above are visible to the lanes that pop them
+            if (active) {
+                S = load_path(p, hpid[lane]);
+                const F4 h = hhit[lane]; t = h.x; u = h.y; v = h.z; prim = f2u(h.w);
+            }
+            wave_lds_sync();                                        // every lane has read its entry before the slots are written again
+            if (carry) { hpid[ce] = cpid; hhit[ce] = {ct, cu, cv, u2f(cprim)}; }      // the hits of the last pass beyond the 64 just popped: the front of the emptied buffer
+            hcnt = full ? hnext : 0u;
+            PF_MARK(2);
+            // ---- shading: as k_bounce_small ----
+            Surf sf; sf.mat = 0; sf.normal = mk3(0, 0, 1); sf.pos = mk3(0, 0, 0);
+            bool shading = false;
+            if (active && prim != kMissPrim) {
+                PF_COUNT(3);
+                sf = surface(sc, S.o, S.d, t, u, v, prim);
+                if (sf.mat < sc.nmat) {
+                    const MatGPU& m = mats[sf.mat];
+                    if (m.Ke_len > 0.0f) add_emissive(sc, p, S, sf, m, bounce, nee, false);
+                    else shading = true;
+                }
+            }
+            const f3 outgoing = -S.d, pos = sf.pos;
+            const MatGPU* mp = mats + (shading ? sf.mat : 0u);
+            f3 normal = sf.normal;
+            const float eta_p = LAMBERT ? 0.0f : transmission_eta(*mp, f.flags, outgoing, normal);
+            PF_MARK(3);
+            for (uint32_t j = 0; j < nee; j++) {
+                bool push = false;
+                F4 so = {0, 0, 0, 0}, sd = {0, 0, 1, 0}; f3 con = mk3(0, 0, 0);
+                if (shading) { PF_COUNT(4); push = nee_sample(sc, *mp, f.flags, nee, S, pos, normal, outgoing, so, sd, con, sf.near_hull, eta_p, nullptr, lds_cdf, lds_lights); }
+                PF_MARK(4);
+                const unsigned long long pmask = __ballot(push);
+                const uint32_t npush = (uint32_t)__popcll(pmask);
+                if (lane == j) shcnt += npush;
+                const uint32_t e = scnt + __builtin_amdgcn_mbcnt_hi((uint32_t)(pmask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)pmask, 0u));
+                if (push && e < kShBuf) { sho[e] = so; shd[e] = sd; shc[e] = {con.x, con.y, con.z, u2f(S.pid)}; }
+                const uint32_t tot = scnt + npush;                  // < 64 waiting + <= 64 pushed
+                PF_MARK(5);
+                if (tot >= kShBuf) {                               // a full block: trace it, then the rest of this push goes to the front of the emptied buffer
+                    shadow_block(kShBuf);
+                    if (push && e >= kShBuf) { sho[e - kShBuf] = so; shd[e - kShBuf] = sd; shc[e - kShBuf] = {con.x, con.y, con.z, u2f(S.pid)}; }
+                    scnt = tot - kShBuf;
+                } else scnt = tot;
+                if (nee > 1u && scnt) { shadow_block(scnt); scnt = 0; }        // drain per slot: slot j + 1 of a path is pushed after slot j was added
+            }
+            bool alive = false;
+            f3 smp = mk3(0, 0, 1); float P = 0.0f;
+            if (shading && !last) { PF_COUNT(9); alive = bsdf_continue(*mp, f, bounce, S, normal, outgoing, smp, P, eta_p); }
+            if (alive) { PF_COUNT(10); store_path(p, S, pos, smp, P); }
+            const uint32_t slot = block_push(alive, &s_cnt[0]);
+            if (alive) mynext[slot] = S.pid;
+            PF_MARK(9);
+        }
+        if (scnt) { shadow_block(scnt); scnt = 0; }                 // the partial block: nothing of this bounce stays pending
+        if (lane < nee && shcnt) atomicAdd(&s_cnt[1u + lane], shcnt);
+        // end of this bounce of the sub-queue: publish its counters; what it wrote (path state, radiance, next queue) becomes visible to the workgroup
+        __syncthreads();
+        n = s_cnt[0];
+        if (threadIdx.x == 0) qrows[(size_t)(bounce + 1u) * G + qid] = n;
+        if (threadIdx.x >= 1 && threadIdx.x <= nee) srows[((size_t)bounce * nee1 + (threadIdx.x - 1)) * G + qid] = s_cnt[threadIdx.x];
+        __syncthreads();
+        if (threadIdx.x <= kMaxNee) s_cnt[threadIdx.x] = 0;
+        if (threadIdx.x == 0) s_in = 0;
+        __syncthreads();
+    }
+    PF_FLUSH;
+#ifdef RTX_WAVE_CLOCK
+    RTX_WAVE_STAMP_W(1u);
+#endif
+}
+
+}  // namespace rtx

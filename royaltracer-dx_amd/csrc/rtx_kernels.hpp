@@ -182,8 +182,8 @@ void launch_raygen_trace_small(hipStream_t, const DevScene&, const DevFrame&, co
 void launch_primary_surface(hipStream_t, const DevScene&, const DevFrame&, const CameraGPU* cam, unsigned long long* masks, unsigned long long* hits, F4* rec);
 void launch_raygen_shared(hipStream_t, const DevFrame&, uint32_t* queue, uint32_t* qcount, uint32_t* gencount, const unsigned long long* hits, uint32_t rec_npl /* the real frame's slots (f: a pass of rtx_render_adaptive has fewer) */);
 void launch_bounce_small(hipStream_t, const DevScene&, const DevFrame&, const DevPaths&, uint32_t bounce_first, uint32_t bounce_end,
-                         uint32_t* queue_a, uint32_t* queue_b, uint32_t* qrows, uint32_t* srows, const uint32_t* order, bool ring = true,
-                         const PrimIn* prim = nullptr);   // bounce 0 alone (reads the primary hits; prim: starts from the records of launch_primary_surface instead), or a range of later bounces; ring: hits go through the LDS ring
+                         uint32_t* queue_a, uint32_t* queue_b, uint32_t* qrows, uint32_t* srows, const uint32_t* order, int variant = 0,
+                         const PrimIn* prim = nullptr);   // bounce 0 alone (reads the primary hits; prim: starts from the records of launch_primary_surface instead), or a range of later bounces; variant: RTX_OPT_BOUNCE_VARIANT, the form of bounces >= 1
 // general (BVH) path: trace -> shade -> shadow of a bounce range for every workgroup-private sub-queue in one launch (hitq: G * qcap indices of scratch)
 void launch_bounce_bvh(hipStream_t, const DevScene&, const DevFrame&, const DevPaths&, uint32_t bounce_first, uint32_t bounce_end,
                        uint32_t* queue_a, uint32_t* queue_b, uint32_t* hitq, uint32_t* qrows, uint32_t* srows, const uint32_t* order);

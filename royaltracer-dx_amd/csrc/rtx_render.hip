@@ -74,8 +74,8 @@ int enqueue_tiny_fused(rtx_ctx* c, const FrameRun& R, const DevFrame& fb) {
     const uint32_t* order = nullptr;
     if (c->opt.lpt_order && R.G > 1) { launch_order_queues(st, R.Q(0), R.G, (uint32_t*)c->pt.d_order.p); order = (const uint32_t*)c->pt.d_order.p; }
     const PrimIn prim = prim_in(R.prim_rec, R.rec_npl, fb.npl);      // bounce 0 finds sample and slot from the path id (the batch's npl) and the record streams by the REAL slot (rec_npl)
-    { Timed t(c, RTX_K_BOUNCE); launch_bounce_small(st, c->dsc, fb, R.P, 0, 1, R.queue[0], R.queue[1], R.Q(0), R.S(0, 0), order, false, R.prim_rec ? &prim : nullptr); }
-    if (R.mb > 1) { Timed t(c, RTX_K_BOUNCE); launch_bounce_small(st, c->dsc, fb, R.P, 1, R.mb, R.queue[0], R.queue[1], R.Q(0), R.S(0, 0), order, c->opt.bounce_ring); }
+    { Timed t(c, RTX_K_BOUNCE); launch_bounce_small(st, c->dsc, fb, R.P, 0, 1, R.queue[0], R.queue[1], R.Q(0), R.S(0, 0), order, 0, R.prim_rec ? &prim : nullptr); }
+    if (R.mb > 1) { Timed t(c, RTX_K_BOUNCE); launch_bounce_small(st, c->dsc, fb, R.P, 1, R.mb, R.queue[0], R.queue[1], R.Q(0), R.S(0, 0), order, c->opt.bounce_variant); }
     return RTX_OK;
 }
 

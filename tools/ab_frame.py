@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Same-box, same-process alternating A/B of rtx options on one workload: the scene is built once, the option values alternate round by round.
-usage: python tools/ab_frame.py <sponza|bistro|garage|cornell> <pt|restir> <opt>=<a>,<b>[,...] [rounds=3] [frames=3] [timing=0] [same=0] [fixed <opt>=<v> ...]
+usage: python tools/ab_frame.py <sponza|bistro|garage|cornell> <pt|restir> <opt>=<a>,<b>[,...] [rounds=3] [frames=3] [timing=0] [same=0] [flags=<RTX_FLAG_* bits, default: the scene's>] [fixed <opt>=<v> ...]
 prints per setting: ms per frame (wall, all rounds), per-kernel-class ms (last round, only with timing=1: launches serialised; the default timing=0 leaves the frame as a caller gets it) and the image checksum"""
 import hashlib, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -36,7 +36,7 @@ if mode == "restir":
     p = rt.Params(width=W, height=H, spp=1, max_bounces=3, nee_samples=4, flags=0)
 else:
     p = rt.Params(width=W, height=H, spp=16 if kind != "cornell" else 64, max_bounces=8, nee_samples=1, rr_start=3, sample_base=1,
-                  flags=1 if kind in ("sponza", "cornell") else (4 if kind == "bistro" else 0))
+                  flags=named.get("flags", 1 if kind in ("sponza", "cornell") else (4 if kind == "bistro" else 0)))
 
 
 def run(c, seed0):

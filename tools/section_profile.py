@@ -3,7 +3,9 @@
 
 Needs the PROFILE build (`make -C royaltracer-dx_amd PROFILE=1` -> librtx_hip_prof.so: s_memtime deltas per section, summed per
 wave).  Renders Cornell frames of configs[1] and prints each section's share.  Tooling only; the product library has no counters.
-usage: python tools/section_profile.py [frames]
+usage: python tools/section_profile.py [frames] [option_id=value ...]
+With RTX_OPT_BOUNCE_VARIANT 2 (the wave-private form) "shadow push + barrier" is the push into the wave's shadow buffer (no barrier) and "barrier 2" the deferred radiance
+additions after a shadow block; the shadow sections are then those of full 64-ray blocks.
 """
 import ctypes as C
 import os
@@ -15,16 +17,22 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 import __graft_entry__ as graft  # noqa: E402
 
+DEFAULT_VARIANT = 2          # the library's default RTX_OPT_BOUNCE_VARIANT
 NAMES = ["load state", "closest: pre-test", "closest: exact tests", "surface + emissive", "NEE sample", "shadow push + barrier",
          "shadow: pre-test", "shadow: exact tests", "barrier 2", "radiance + BSDF sample + store", "-", "-"]
 
 
 def main():
-    frames = int(sys.argv[1]) if len(sys.argv) > 1 else 1
+    frames = next((int(a) for a in sys.argv[1:] if a.isdigit()), 1)
+    opts = [tuple(int(x) for x in a.split("=")) for a in sys.argv[1:] if "=" in a]
     rt = graft.load_package()
     dev = torch.device("cuda", 0)
     scene = rt.Scene.cornell()
     ctx = rt.Context(0)
+    for k, v in opts:
+        ctx.set_option(k, v)
+    if dict(opts).get(rt.OPT_BOUNCE_VARIANT, DEFAULT_VARIANT) == 2:
+        NAMES[5], NAMES[8] = "shadow push (wave buffer)", "deferred radiance add"
     W, H = 1920, 1080
     ctx.upload(scene, W / H)
     accum = torch.zeros((H, W, 4), dtype=torch.float32, device=dev)
