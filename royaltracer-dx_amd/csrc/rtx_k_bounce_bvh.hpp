@@ -66,11 +66,13 @@ __global__ __launch_bounds__(kBlock, 5) void k_bounce_bvh(DevScene sc, DevFrame 
         __syncthreads();
         const uint32_t nh = s_nh;
         // ---- phase 2: shade the hits.  DEFINITION: shade_item<false> (rtx_k_shade.hpp) — this is its body without the compact path state, the sort keys and the shared
-        // view terms (MixView), none of which this path uses; change the two together.  (Calling it here is the same arithmetic but slower: profiles/fold_frame_time.md) ----
+        // view terms (MixView), none of which this path uses; change the two together.  (Calling it here is the same arithmetic but slower: profiles/fold_frame_time.md.)  The tiny-scene
+        // kernel has the same step twice, once per schedule — shade_block (rtx_k_bounce_small.hpp) and the shading of bounce_small_wave — both built from the parts of
+        // rtx_bounce_small_parts.hpp: a change to the decision or the continuation there reaches both; one to the order of the steps has to be made in these four places ----
         for (uint32_t base = threadIdx.x & ~63u; base < nh; base += kBlock) {
             const uint32_t i = base + (threadIdx.x & 63u);
-            PathState S; S.pid = 0; S.o = mk3(0, 0, 0); S.d = mk3(0, 0, 1); S.thr = mk3(0, 0, 0); S.prev_pdf = 1.0f; S.s0 = S.s1 = 0;
-            Surf sf; sf.mat = 0; sf.normal = mk3(0, 0, 1); sf.pos = mk3(0, 0, 0);
+            PathState S = idle_path();
+            Surf sf = idle_surf();
             bool shading = false;
             if (i < nh) {
                 const uint32_t pid = myhits[i];

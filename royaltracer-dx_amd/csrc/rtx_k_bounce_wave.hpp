@@ -1,8 +1,9 @@
 // rtx_k_bounce_wave.hpp — the wave-private form of the fused tiny-scene bounce kernel (k_bounce_small<.., 0, .., RING = 2>, RTX_OPT_BOUNCE_VARIANT = 2)
 // One of the kernel headers of rtx_kernels.hip; included by rtx_k_bounce_small.hpp, whose kernel calls bounce_small_wave() as its whole body for RING == 2.
+// What it shares with the other two bodies (table staging, hit -> shading decision, continuation, bounce end, ...) is defined once, in rtx_bounce_small_parts.hpp.
 // Uses the PF_* section-profile macros that rtx_kernels.hip defines before it includes the kernel headers.
 #pragma once
-#include "rtx_shade.hpp"
+#include "rtx_bounce_small_parts.hpp"
 
 namespace rtx {
 
@@ -14,7 +15,7 @@ __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// Bounces [bounce_first, bounce_end), bounce_first >= 1, of the workgroup's sub-queue — the same work, arithmetic and radiance order as the RING == 1 body of k_bounce_small,
+// Bounces [bounce_first, bounce_end), bounce_first >= 1, of the workgroup's sub-queue — the same work, arithmetic and radiance order as bounce_small_block<.., 1> (rtx_k_bounce_small.hpp),
 // scheduled per WAVE instead of per workgroup: inside a bounce no wave ever waits for another.
 //   input     a wave takes the next 64 queue entries from an LDS cursor (s_in, one atomic per chunk): the four waves stay balanced whatever their rays cost
 //   hit buffer  per wave, 64 entries (path id + hit record) in LDS that only this wave touches; a trace pass pushes its hits with ballot + mbcnt at a wave-uniform
@@ -29,7 +30,7 @@ __device__ __forceinline__ void wave_lds_sync() {
 //             before the wave leaves the bounce: with the bounce-end barrier, a path's additions of bounce b are complete before bounce b + 1 reads its radiance — the oracle's
 //             order (emissive, NEE slot 0, 1, ..., next bounce).  An emissive hit and an NEE entry of the same path cannot coexist within a bounce (add_emissive XOR shading).
 //             (An immediate form — no shadow buffer, the wave traces its shadow rays right after nee_sample at the 2/3 of the lanes that pushed — measured slower: docs/REJECTED.md.)
-// INVARIANTS.  (1) Barriers: the only workgroup barriers are the table-staging one and the three at each bounce boundary (end of bounce, counters published, counters reset);
+// INVARIANTS.  (1) Barriers: the only workgroup barriers are the table-staging one and the three at each bounce boundary (end_bounce: end of bounce, counters published, counters reset);
 // every wave executes each exactly once per bounce, outside every data-dependent loop.  There is no producer / consumer protocol between waves.  (2) Termination: every loop ends
 // because the input cursor only grows (a wave that reads a cursor >= n never asks again in this bounce) and a buffer only drains once the input is exhausted (each trip of the
 // outer loop pops >= 1 entry of the hit buffer or ends the bounce; a shadow block empties the shadow buffer).
@@ -45,28 +46,13 @@ __device__ __forceinline__ void bounce_small_wave(const DevScene& sc, const Smal
     __shared__ F4 s_so[kWaves * kShBuf], s_sd[kWaves * kShBuf], s_sc[kWaves * kShBuf];
     const DevFrame f = frame_with_lambert<LAMBERT>(f_in);
     const uint32_t qid = order ? order[blockIdx.x] : blockIdx.x;
-#ifdef RTX_WAVE_CLOCK
-    #define RTX_WAVE_STAMP_W(K) do { const uint32_t w_ = blockIdx.x * (kBlock / 64u) + (threadIdx.x >> 6); if (lane_id() == 0 && w_ < 65536u) g_wgt[2u * w_ + (K)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-    RTX_WAVE_STAMP_W(0u);
-#endif
+    wave_stamp(0u);
     if (threadIdx.x <= kMaxNee) s_cnt[threadIdx.x] = 0;
     if (threadIdx.x == 0) s_in = 0;
-    // the light list and the material table in LDS, as in k_bounce_small
-#ifndef RTX_NO_SMALL_LDS_TABLES
-    constexpr uint32_t kSmallLights = 32, kSmallMats = 16;
-    __shared__ F4 s_lt[kSmallLights * 5]; __shared__ float s_ltcdf[kSmallLights]; __shared__ F4 s_mt[kSmallMats * 10];
-    const bool lt_lds = sc.nlights && sc.nlights <= kSmallLights, mt_lds = sc.nmat && sc.nmat <= kSmallMats;
-    if (lt_lds) { for (uint32_t i = threadIdx.x; i < sc.nlights * 5u; i += kBlock) s_lt[i] = ((const F4*)sc.lights)[i]; if (threadIdx.x < sc.nlights) s_ltcdf[threadIdx.x] = sc.cdf[threadIdx.x]; }
-    if (mt_lds) for (uint32_t i = threadIdx.x; i < sc.nmat * 10u; i += kBlock) s_mt[i] = ((const F4*)sc.mats)[i];
-    const MatGPU* mats = mt_lds ? (const MatGPU*)s_mt : sc.mats;
-    const LightGPU* lds_lights = lt_lds ? (const LightGPU*)s_lt : nullptr; const float* lds_cdf = lt_lds ? s_ltcdf : nullptr;
-#else
-    const MatGPU* mats = sc.mats; const LightGPU* lds_lights = nullptr; const float* lds_cdf = nullptr;
-#endif
+    STAGE_SMALL_TABLES(T, sc);
     const uint32_t G = gridDim.x;
     uint32_t n = qrows[(size_t)bounce_first * G + qid];
     const uint32_t nee = sc.nlights ? f.nee_samples : 0u;
-    const uint32_t nee1 = nee ? nee : 1u;
     const TraceLds L = stage_lds(sc, lds);
     __syncthreads();
     const size_t qb = (size_t)qid * f.qcap;
@@ -91,9 +77,7 @@ __device__ __forceinline__ void bounce_small_wave(const DevScene& sc, const Smal
             const uint32_t e = lane;
             const F4 ro = mine ? sho[e] : F4{0, 0, 0, 0}, rd = mine ? shd[e] : F4{0, 0, 1, 0};
             float st_, su_, sv_; uint32_t sprim;
-            // hull-face shortcut only if no ray of this block starts near a hull plane (flag in the sign of tmin, TriShade::guard_tau)
-            const uint32_t nrec_sh = __builtin_amdgcn_ballot_w64(mine && ro.w < 0.0f) != 0ull ? sc.nsmall : sc.nsmall_occ;
-            traverse_small<true>(sc, small, L, mk3(ro.x, ro.y, ro.z), mk3(rd.x, rd.y, rd.z), fabsf(ro.w), mine ? rd.w : 0.0f, st_, su_, sv_, sprim, nrec_sh, ~0ull, pf, 6);
+            traverse_small<true>(sc, small, L, mk3(ro.x, ro.y, ro.z), mk3(rd.x, rd.y, rd.z), fabsf(ro.w), mine ? rd.w : 0.0f, st_, su_, sv_, sprim, shadow_records(sc, mine, ro.w), ~0ull, pf, 6);
             if (mine && sprim == kMissPrim) {
                 const F4 c = shc[e];
                 const uint32_t pid = f2u(c.w);
@@ -131,7 +115,7 @@ __device__ __forceinline__ void bounce_small_wave(const DevScene& sc, const Smal
             const uint32_t take = full ? 64u : hcnt;
             if (take == 0u) break;                                  // input exhausted and buffer drained: this wave is done with the bounce
             const bool active = lane < take;
-            PathState S; S.pid = 0; S.o = mk3(0, 0, 0); S.d = mk3(0, 0, 1); S.thr = mk3(0, 0, 0); S.prev_pdf = 1.0f; S.s0 = S.s1 = 0;
+            PathState S = idle_path();
             float t = 0.0f, u = 0.0f, v = 0.0f; uint32_t prim = kMissPrim;
             wave_lds_sync();                                        // the pushes above are visible to the lanes that pop them
             if (active) {
@@ -142,27 +126,19 @@ __device__ __forceinline__ void bounce_small_wave(const DevScene& sc, const Smal
             if (carry) { hpid[ce] = cpid; hhit[ce] = {ct, cu, cv, u2f(cprim)}; }      // the hits of the last pass beyond the 64 just popped: the front of the emptied buffer
             hcnt = full ? hnext : 0u;
             PF_MARK(2);
-            // ---- shading: as k_bounce_small ----
-            Surf sf; sf.mat = 0; sf.normal = mk3(0, 0, 1); sf.pos = mk3(0, 0, 0);
+            // ---- shading: the steps of shade_block (rtx_k_bounce_small.hpp), the shadow rays into this wave's buffer ----
+            Surf sf = idle_surf();
             bool shading = false;
-            if (active && prim != kMissPrim) {
-                PF_COUNT(3);
-                sf = surface(sc, S.o, S.d, t, u, v, prim);
-                if (sf.mat < sc.nmat) {
-                    const MatGPU& m = mats[sf.mat];
-                    if (m.Ke_len > 0.0f) add_emissive(sc, p, S, sf, m, bounce, nee, false);
-                    else shading = true;
-                }
-            }
+            if (active && prim != kMissPrim) { PF_COUNT(3); shading = hit_to_shading<0>(sc, p, T.mats, S, sf, t, u, v, prim, bounce, nee); }
             const f3 outgoing = -S.d, pos = sf.pos;
-            const MatGPU* mp = mats + (shading ? sf.mat : 0u);
+            const MatGPU* mp = T.mats + (shading ? sf.mat : 0u);
             f3 normal = sf.normal;
             const float eta_p = LAMBERT ? 0.0f : transmission_eta(*mp, f.flags, outgoing, normal);
             PF_MARK(3);
             for (uint32_t j = 0; j < nee; j++) {
                 bool push = false;
                 F4 so = {0, 0, 0, 0}, sd = {0, 0, 1, 0}; f3 con = mk3(0, 0, 0);
-                if (shading) { PF_COUNT(4); push = nee_sample(sc, *mp, f.flags, nee, S, pos, normal, outgoing, so, sd, con, sf.near_hull, eta_p, nullptr, lds_cdf, lds_lights); }
+                if (shading) { PF_COUNT(4); push = nee_sample(sc, *mp, f.flags, nee, S, pos, normal, outgoing, so, sd, con, sf.near_hull, eta_p, nullptr, T.cdf, T.lights); }
                 PF_MARK(4);
                 const unsigned long long pmask = __ballot(push);
                 const uint32_t npush = (uint32_t)__popcll(pmask);
@@ -178,30 +154,15 @@ __device__ __forceinline__ void bounce_small_wave(const DevScene& sc, const Smal
                 } else scnt = tot;
                 if (nee > 1u && scnt) { shadow_block(scnt); scnt = 0; }        // drain per slot: slot j + 1 of a path is pushed after slot j was added
             }
-            bool alive = false;
-            f3 smp = mk3(0, 0, 1); float P = 0.0f;
-            if (shading && !last) { PF_COUNT(9); alive = bsdf_continue(*mp, f, bounce, S, normal, outgoing, smp, P, eta_p); }
-            if (alive) { PF_COUNT(10); store_path(p, S, pos, smp, P); }
-            const uint32_t slot = block_push(alive, &s_cnt[0]);
-            if (alive) mynext[slot] = S.pid;
+            continue_path(*mp, f, p, bounce, shading && !last, S, pos, normal, outgoing, eta_p, &s_cnt[0], mynext, pf);
             PF_MARK(9);
         }
         if (scnt) { shadow_block(scnt); scnt = 0; }                 // the partial block: nothing of this bounce stays pending
         if (lane < nee && shcnt) atomicAdd(&s_cnt[1u + lane], shcnt);
-        // end of this bounce of the sub-queue: publish its counters; what it wrote (path state, radiance, next queue) becomes visible to the workgroup
-        __syncthreads();
-        n = s_cnt[0];
-        if (threadIdx.x == 0) qrows[(size_t)(bounce + 1u) * G + qid] = n;
-        if (threadIdx.x >= 1 && threadIdx.x <= nee) srows[((size_t)bounce * nee1 + (threadIdx.x - 1)) * G + qid] = s_cnt[threadIdx.x];
-        __syncthreads();
-        if (threadIdx.x <= kMaxNee) s_cnt[threadIdx.x] = 0;
-        if (threadIdx.x == 0) s_in = 0;
-        __syncthreads();
+        n = end_bounce<true>(s_cnt, &s_in, qrows, srows, bounce, G, qid, nee);
     }
     PF_FLUSH;
-#ifdef RTX_WAVE_CLOCK
-    RTX_WAVE_STAMP_W(1u);
-#endif
+    wave_stamp(1u);
 }
 
 }  // namespace rtx

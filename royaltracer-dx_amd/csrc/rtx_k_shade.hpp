@@ -26,8 +26,8 @@ namespace rtx {
 template <bool LAMBERT, bool TEX = false, bool ENV = false>
 __device__ __forceinline__ void shade_item(const DevScene& sc, const DevFrame& f, const DevPaths& p, uint32_t bounce, uint32_t nee, bool last, size_t qb,
                                            const uint32_t* __restrict__ myq, uint32_t* __restrict__ mynext, uint32_t* s_cnt, bool valid, uint32_t qi, Prof* pf, const float* lds_cdf = nullptr, const LightGPU* lds_lights = nullptr, const MatGPU* lds_mats = nullptr, const float* env_marg = nullptr) {
-    PathState S; S.pid = 0; S.o = mk3(0, 0, 0); S.d = mk3(0, 0, 1); S.thr = mk3(0, 0, 0); S.prev_pdf = 1.0f; S.s0 = S.s1 = 0;
-    Surf sf; sf.mat = 0; sf.normal = mk3(0, 0, 1); sf.pos = mk3(0, 0, 0);
+    PathState S = idle_path();
+    Surf sf = idle_surf();
     bool shading = false;
     f3 kdv = mk3(0, 0, 0); const f3* kdpi = TEX ? &kdv : nullptr;
 #ifndef RTX_NO_LDS_MATS
@@ -107,14 +107,6 @@ __device__ __forceinline__ void shade_item(const DevScene& sc, const DevFrame& f
         }
         mynext[slot] = S.pid;
     }
-}
-
-// RTX_FLAG_LAMBERT_ONLY is a launch constant, so k_shade / k_shade_dense take it as a template parameter: bit 0 of the flags their code sees is known at compile time
-template <bool LAMBERT>
-__device__ __forceinline__ DevFrame frame_with_lambert(const DevFrame& f_in) {
-    DevFrame f = f_in;
-    f.flags = LAMBERT ? (f_in.flags | 1u) : (f_in.flags & ~1u);
-    return f;
 }
 
 constexpr uint32_t kSortChunk = 2048, kSortKeys = 64, kLdsCdf = 256;

@@ -89,11 +89,11 @@ __global__ __launch_bounds__(kBlock) void k_rs_raygen(DevFrame f, RsQ q, const C
 #ifndef RTX_RS_P1_WAVES
 #define RTX_RS_P1_WAVES 5      // k_rs_p1_first / _loop: 96 VGPRs (5 waves / SIMD) before the LDS tables, 101-105 with them unless asked for 5
 #endif
-struct RsTables { F4 mats[16 * 10]; F4 lights[32 * 5]; float cdf[32]; };
+struct RsTables { F4 mats[kSmallMats * 10]; F4 lights[kSmallLights * 5]; float cdf[kSmallLights]; };
 __device__ __forceinline__ DevScene rs_stage_tables(const DevScene& in, RsTables& T) {
     DevScene sc = in;
-    if (in.nmat && in.nmat <= 16u) { for (uint32_t i = threadIdx.x; i < in.nmat * 10u; i += kBlock) T.mats[i] = ((const F4*)in.mats)[i]; sc.mats = (const MatGPU*)T.mats; }
-    if (in.nlights && in.nlights <= 32u) {
+    if (in.nmat && in.nmat <= kSmallMats) { for (uint32_t i = threadIdx.x; i < in.nmat * 10u; i += kBlock) T.mats[i] = ((const F4*)in.mats)[i]; sc.mats = (const MatGPU*)T.mats; }
+    if (in.nlights && in.nlights <= kSmallLights) {
         for (uint32_t i = threadIdx.x; i < in.nlights * 5u; i += kBlock) T.lights[i] = ((const F4*)in.lights)[i];
         if (threadIdx.x < in.nlights) T.cdf[threadIdx.x] = in.cdf[threadIdx.x];
         sc.lights = (const LightGPU*)T.lights; sc.cdf = T.cdf;

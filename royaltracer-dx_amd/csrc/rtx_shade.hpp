@@ -1,4 +1,4 @@
-// rtx_shade.hpp — surface reconstruction and the per-bounce shading functions shared by k_shade and k_bounce_small
+// rtx_shade.hpp — surface reconstruction and the per-bounce shading functions shared by k_shade, k_bounce_bvh and k_bounce_small
 #pragma once
 #include "rtx_traverse.hpp"
 #include "rtx_texture.hpp"
@@ -28,6 +28,8 @@ __device__ __forceinline__ Surf surface(const DevScene& sc, f3 o, f3 d, float t,
     s.normal = normalize(xform_dir(sc.insts[s.inst].nrm, n));                 // :56
     return s;
 }
+// the surface of a lane without a hit: what the code after the hit test may read of it
+__device__ __forceinline__ Surf idle_surf() { Surf sf; sf.mat = 0; sf.normal = mk3(0, 0, 1); sf.pos = mk3(0, 0, 0); return sf; }
 
 // ---------------------------------------------------------------------------------------------
 // shading building blocks.  Loop body of RayGen.hlsl:99-133 + Hit.hlsl:126-174,340-369 with the v6 leaf math,
@@ -40,6 +42,20 @@ __device__ __forceinline__ Surf surface(const DevScene& sc, f3 o, f3 d, float t,
 // rad = (radiance.xyz, -) is only touched when something is added.
 // ---------------------------------------------------------------------------------------------
 struct PathState { uint32_t pid; f3 o, d; float prev_pdf; f3 thr; uint32_t s0, s1; };
+
+// the path state of a lane without an item: it runs through the shading code with every branch off
+__device__ __forceinline__ PathState idle_path() { PathState S; S.pid = 0; S.o = mk3(0, 0, 0); S.d = mk3(0, 0, 1); S.thr = mk3(0, 0, 0); S.prev_pdf = 1.0f; S.s0 = S.s1 = 0; return S; }
+
+// RTX_FLAG_LAMBERT_ONLY is a launch constant, so k_shade / k_shade_dense / k_bounce_small take it as a template parameter: bit 0 of the flags their code sees is known at compile time
+template <bool LAMBERT>
+__device__ __forceinline__ DevFrame frame_with_lambert(const DevFrame& f_in) {
+    DevFrame f = f_in;
+    f.flags = LAMBERT ? (f_in.flags | 1u) : (f_in.flags & ~1u);
+    return f;
+}
+
+// the longest light list / material table that the tiny-scene kernels and the ReSTIR stages stage in LDS (stage_small_tables, RsTables)
+constexpr uint32_t kSmallLights = 32, kSmallMats = 16;
 
 __device__ __forceinline__ float bounce_tmin(uint32_t bounce) { return bounce == 0 ? kTMinCam : kSBias; }
 

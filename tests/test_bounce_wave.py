@@ -48,12 +48,13 @@ def set_view(rt, ctx, o, aspect):
 RAGGED = dict(width=100, height=50, spp=3, sample_base=5, frame_seed=99)
 
 
-@pytest.mark.parametrize("flags", [0, 1])
+@pytest.mark.parametrize("flags", [0, 1, 2, 3])
 @pytest.mark.parametrize("nee", [0, 1, 4])
 @pytest.mark.parametrize("bounces", [2, 8])
 def test_cornell_ragged_frame_equals_other_variants_and_oracle(rt, pair, bounces, nee, flags):
     """bounces = 2: a launch with a single bounce; 8: Russian roulette and sub-queues shorter than 64 (partial chunks, buffers drained below 64);
-    nee = 4: the drain after every NEE slot; nee = 0: no shadow ray at all"""
+    nee = 4: the drain after every NEE slot; nee = 0: no shadow ray at all;
+    flags 2, 3 (FLAG_JITTER without / with Lambert-only): no shared primary record, so bounce 0 shades the hits of k_raygen_trace_small — the one form that calls surface() in bounce 0"""
     ctx, o = pair
     p = rt.Params(max_bounces=bounces, nee_samples=nee, flags=flags, **RAGGED)
     set_view(rt, ctx, o, 2.0)
