@@ -378,6 +378,37 @@ int  rtx_save_scene_cache(rtx_ctx*, const char* path);
 int  rtx_load_scene_cache(rtx_ctx*, const char* path);
 /* b0 `CameraParams` (UpdateCameraBuffer, Renderer.cpp:1722-1768): view + projection; inverses computed inside */
 int  rtx_set_camera(rtx_ctx*, const float view[16], const float proj[16]);
+/* THIN LENS (new; the reference's camera is a pinhole: every primary ray starts at viewI[12..14], RayGen_v6_pass1.hlsl:51-95 — an extension, unpinned by definition like the
+   environment, pinned by its own definition and properties in tests/test_lens_ref.py / tests/test_lens.py).  Depth of field costs no extra ray: it is another primary ray per
+   sample, decided in ray generation.  With no lens set (or radius 0) every launch, image, statistic and random-number sequence is what it was.
+   PER PATH.  R = aperture_radius > 0, F = focus_distance, Vi = viewI; (o, d) = the pinhole ray of the path's pixel, computed after the two jitter draws if RTX_FLAG_JITTER is
+   set.  All arithmetic float32 in exactly the written order, no contraction; sqrtf and / are IEEE; sincos_ is the one of csrc/rtx_math.hpp:
+       xi1 = RandomFloat ;  xi2 = RandomFloat                  (after jitter's draws, before anything of the path: the path starts from the seed state after them)
+       r  = sqrtf(xi1) ;  (sn, cs) = sincos_(kTwoPi * xi2)
+       lx = (R * r) * cs ;  ly = (R * r) * sn
+       cz = |(d.x * Vi[8] + d.y * Vi[9]) + d.z * Vi[10]|        (cosine to the view axis, sign-free: left- and right-handed views alike)
+       ft = F / cz
+       P.k  = o.k + d.k * ft                                    (k = x, y, z: the point in focus)
+       o'.k = (o.k + Vi[0 + k] * lx) + Vi[4 + k] * ly           (the lens point: camera right / up, the first two columns of viewI)
+       v = P - o' ;  r2 = (v.x * v.x + v.y * v.y) + v.z * v.z ;  inv = 1.0f / sqrtf(r2) ;  d' = v * inv
+   The path starts as (o', d'); if not cz > 0 or a component of d' is not finite it keeps (o, d) — the two draws are consumed either way.  tmin and tmax stay the camera rays'.
+   With R = 0 nothing is drawn, the ray is the pinhole ray and the kernels that always ran run.
+   WHO SEES IT: rtx_render, rtx_render_adaptive, rtx_debug_primary_rays (which returns (o', d')) and rtx_debug_primary_seeds.  WHO IGNORES IT, keeping the pixel-corner pinhole
+   ray as they ignore maps and the environment: rtx_render_v6_pass1, rtx_render_restir, the guides of rtx_denoise, rtx_read_layer's layers 10-17, rtx_focus_distance_at.
+   Under a lens the fused tiny-scene path neither shares a pixel's primary hit among its samples (RTX_OPT_SHARED_PRIMARY is ignored) nor culls records per 8x8 block.
+   CALLS.  rtx_set_lens is camera state: valid at any time after rtx_create, needs no rtx_commit_scene and never dirties the scene (rtx_stats.bvh_refits and rtx_debug_tree_hash
+   unchanged), survives rtx_set_camera, is not part of a scene cache.  NULL = the pinhole.  RTX_ERR_INVALID — a negative or non-finite radius, a focus distance that is not
+   finite, or not > 0 while the radius is > 0, a nonzero reserved word — leaves the previous lens in place.  Like a camera move it does not clear the accumulation: that is
+   the caller's decision.
+   rtx_focus_distance_at is autofocus: it traces the jitter-free pinhole ray of pixel (x, y) of a width x height image exactly as layers 10-17 do (cut-outs and hidden instances
+   count) and writes t * cz (a float32 product, cz as above), 0.0f on a miss.  RTX_ERR_STATE before a commit or a camera, RTX_ERR_INVALID for a pixel outside the image. */
+typedef struct rtx_lens {
+    float    aperture_radius;   /* world units, finite, >= 0; 0 = pinhole (the default) */
+    float    focus_distance;    /* world units along the view axis, finite, > 0 (ignored, but still validated as finite, when the radius is 0) */
+    uint32_t reserved[2];       /* 0 */
+} rtx_lens;
+int  rtx_set_lens(rtx_ctx*, const rtx_lens* /* NULL = pinhole */);
+int  rtx_focus_distance_at(rtx_ctx*, uint32_t width, uint32_t height, uint32_t x, uint32_t y, float* distance_out);
 
 /* u1 `gPermanentData` RGBA32F W x H (Renderer.cpp:1167-1186): xyz running sum, w sample count.
    rtx_bind_accum lets the caller own the device buffer (W*H*16 bytes, e.g. a torch tensor); NULL = internal. */
@@ -531,6 +562,8 @@ int  rtx_unpack_tiles(rtx_ctx*, const rtx_params*, const void* device_slabs_all_
    the render loop uses).  rays8 = (ox,oy,oz,tmin, dx,dy,dz,tmax) per ray.
    hits4 = (t,u,v, global triangle id as uint bits; 0xFFFFFFFF = miss) — TraceRay closest hit, a11. */
 int  rtx_debug_primary_rays(rtx_ctx*, const rtx_params*, uint32_t sample_id, float* rays8 /* W*H*8 */);
+/* ... and the seed state (s0, s1) those paths start from: after RTX_FLAG_JITTER's two draws and the lens's two (THIN LENS above) */
+int  rtx_debug_primary_seeds(rtx_ctx*, const rtx_params*, uint32_t sample_id, uint32_t* seeds2 /* W*H*2 */);
 int  rtx_debug_trace_closest(rtx_ctx*, const float* rays8, uint32_t n, float* hits4);
 int  rtx_debug_trace_any(rtx_ctx*, const float* rays8, uint32_t n, uint8_t* occluded);
 /* closest-hit traversal of the BVH (never the tiny-scene path) that reports its work: stats4 = n * (t, node steps, triangle tests,

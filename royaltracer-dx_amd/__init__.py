@@ -120,6 +120,13 @@ _sig("rtx_debug_env_sample", C.c_int, _vp, _vp, _u32, _vp)
 _sig("rtx_debug_env_eval", C.c_int, _vp, _vp, _u32, _vp)
 _sig("rtx_debug_env_tables", C.c_int, _vp, _vp, _vp, _vp)
 _sig("rtx_set_camera", C.c_int, _vp, _fp, _fp)
+class Lens(C.Structure):
+    """rtx_lens (include/rtx.h): the thin-lens camera"""
+    _fields_ = [("aperture_radius", C.c_float), ("focus_distance", C.c_float), ("reserved", C.c_uint32 * 2)]
+
+
+_sig("rtx_set_lens", C.c_int, _vp, C.POINTER(Lens))
+_sig("rtx_focus_distance_at", C.c_int, _vp, _u32, _u32, _u32, _u32, _fp)
 _sig("rtx_save_scene_cache", C.c_int, _vp, C.c_char_p)
 _sig("rtx_load_scene_cache", C.c_int, _vp, C.c_char_p)
 _sig("rtx_bind_accum", C.c_int, _vp, _vp, C.c_size_t)
@@ -183,6 +190,7 @@ _sig("rtx_shard_slab_bytes", C.c_int, C.POINTER(Params), C.POINTER(C.c_size_t))
 _sig("rtx_pack_tiles", C.c_int, _vp, C.POINTER(Params), _vp)
 _sig("rtx_unpack_tiles", C.c_int, _vp, C.POINTER(Params), _vp)
 _sig("rtx_debug_primary_rays", C.c_int, _vp, C.POINTER(Params), _u32, _vp)
+_sig("rtx_debug_primary_seeds", C.c_int, _vp, C.POINTER(Params), _u32, _vp)
 _sig("rtx_debug_trace_closest", C.c_int, _vp, _vp, _u32, _vp)
 _sig("rtx_debug_trace_any", C.c_int, _vp, _vp, _u32, _vp)
 _sig("rtx_debug_trace_stats", C.c_int, _vp, _vp, _u32, _vp)
@@ -732,6 +740,21 @@ class Context:
         v, p = _f32(view).reshape(16), _f32(proj).reshape(16)
         self._ck(lib.rtx_set_camera(self._h, _fptr(v), _fptr(p)), "rtx_set_camera")
 
+    def set_lens(self, radius, focus=1.0):
+        """the thin-lens camera (rtx_set_lens): aperture radius and focus distance along the view axis, world units; radius 0 or set_lens(None) = the pinhole; a Lens is
+        passed as it is.  Camera state: no commit, survives set_camera, clears nothing"""
+        if radius is None:
+            self._ck(lib.rtx_set_lens(self._h, None), "rtx_set_lens")
+            return
+        lens = radius if isinstance(radius, Lens) else Lens(float(radius), float(focus))
+        self._ck(lib.rtx_set_lens(self._h, C.byref(lens)), "rtx_set_lens")
+
+    def focus_distance_at(self, width, height, x, y):
+        """autofocus (rtx_focus_distance_at): the view-axis depth of the first hit of pixel (x, y)'s pinhole ray in a width x height image; 0.0 = a miss"""
+        d = C.c_float()
+        self._ck(lib.rtx_focus_distance_at(self._h, width, height, x, y, C.byref(d)), "rtx_focus_distance_at")
+        return np.float32(d.value)
+
     def save_scene_cache(self, path):
         self._ck(lib.rtx_save_scene_cache(self._h, str(path).encode()), "rtx_save_scene_cache")
 
@@ -888,6 +911,12 @@ class Context:
     def primary_rays(self, params, sample_id=1):
         out = np.zeros((params.height * params.width, 8), np.float32)
         self._ck(lib.rtx_debug_primary_rays(self._h, C.byref(params), sample_id, _ptr(out)), "rtx_debug_primary_rays")
+        return out
+
+    def primary_seeds(self, params, sample_id=1):
+        """the seed state (s0, s1) the paths of primary_rays start from: after the jitter's draws and the lens's -> (H * W, 2) uint32"""
+        out = np.zeros((params.height * params.width, 2), np.uint32)
+        self._ck(lib.rtx_debug_primary_seeds(self._h, C.byref(params), sample_id, _ptr(out)), "rtx_debug_primary_seeds")
         return out
 
     def trace_closest(self, rays8):

@@ -1,6 +1,7 @@
 // rtx_api.hip — the C-ABI of include/rtx.h: the context, its options and stream, scene inputs, camera, accumulation, image reads, statistics, the shard tiling.
 // Host code only (kernels: the headers rtx_kernels.hip includes, and rtx_refit.hip).  No CPU rendering path exists here by design.  The context and the other parts of the C-ABI: rtx_ctx.hpp.
 #include "rtx_ctx.hpp"
+#include <cmath>
 
 thread_local std::string g_create_err;
 
@@ -102,6 +103,7 @@ int make_frame(rtx_ctx* c, const rtx_params* p, DevFrame& f) {
     f.frame_seed = p->frame_seed; f.flags = p->flags;
     f.hist_x0 = f.hist_y0 = 0; f.hist_x1 = p->width; f.hist_y1 = p->height; f.hist_stale = nullptr;
     f.list = nullptr;
+    f.lens_radius = c->lens.aperture_radius; f.lens_focus = c->lens.focus_distance;
     return RTX_OK;
 }
 // pixel rectangle [x0, x1) x [y0, y1) of rank r in the RTX_FLAG_BLOCK_TILES deal (shard_tile's rule, clipped to the image)
@@ -260,6 +262,31 @@ int rtx_set_camera(rtx_ctx* c, const float view[16], const float proj[16]) {
     TO_DEVICE(c, c->d_cam.p, &cam, sizeof(cam));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->camera_set = true;
+    return RTX_OK;
+}
+
+// camera state like the matrices: no commit, nothing of the scene is touched; every later frame of rtx_render / rtx_render_adaptive reads it through make_frame
+int rtx_set_lens(rtx_ctx* c, const rtx_lens* lens) {
+    BIND(c);
+    if (!lens) { c->lens = rtx_lens{}; return RTX_OK; }
+    const float R = lens->aperture_radius, F = lens->focus_distance;
+    if (!std::isfinite(R) || R < 0.0f) { c->err = "set_lens: aperture_radius must be finite and >= 0"; return RTX_ERR_INVALID; }
+    if (!std::isfinite(F) || (R > 0.0f && !(F > 0.0f))) { c->err = "set_lens: focus_distance must be finite, and > 0 with an open aperture"; return RTX_ERR_INVALID; }
+    if (lens->reserved[0] || lens->reserved[1]) { c->err = "set_lens: reserved words must be 0"; return RTX_ERR_INVALID; }
+    c->lens = *lens;
+    return RTX_OK;
+}
+// autofocus: the view-axis depth of what pixel (x, y)'s pinhole ray sees first (k_focus_distance: the ray and trace of the debug layers)
+int rtx_focus_distance_at(rtx_ctx* c, uint32_t width, uint32_t height, uint32_t x, uint32_t y, float* distance_out) {
+    BIND(c);
+    if (!c->committed || !c->camera_set) { c->err = "focus_distance_at: scene not committed or camera not set"; return RTX_ERR_STATE; }
+    if (!distance_out || !width || !height || x >= width || y >= height) { c->err = "focus_distance_at: pixel outside the image"; return RTX_ERR_INVALID; }
+    DevBuf d_out;
+    HIPCHK(c, d_out.ensure(4));
+    launch_focus_distance(c->stream, c->dsc, width, height, (const CameraGPU*)c->d_cam.p, x, y, (float*)d_out.p);
+    HIPCHK(c, hipGetLastError());
+    TO_HOST(c, distance_out, d_out.p, 4);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return RTX_OK;
 }
 

@@ -92,6 +92,7 @@ struct rtx_ctx {
     SceneHost host;
     bool committed = false;                         // cleared by every input or layout option that changes the scene; set by finalise_scene
     float view[16], proj[16], prev_view[16], prev_proj[16]; bool camera_set = false; DevBuf d_cam;
+    rtx_lens lens{};                                // rtx_set_lens: camera state beside the matrices (make_frame hands it to the raygen kernels); all zero = the pinhole
     DevBuf d_accum; void* ext_accum = nullptr; size_t ext_accum_bytes = 0; uint32_t acc_w = 0, acc_h = 0;
     DevBuf d_srgb;                                  // rtx_read_srgb8 / rtx_read_layer
     F4* accum_ptr() { return (F4*)(ext_accum ? ext_accum : d_accum.p); }

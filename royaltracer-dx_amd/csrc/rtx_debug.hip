@@ -15,6 +15,19 @@ int rtx_debug_primary_rays(rtx_ctx* c, const rtx_params* p, uint32_t sample_id, 
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return RTX_OK;
 }
+int rtx_debug_primary_seeds(rtx_ctx* c, const rtx_params* p, uint32_t sample_id, uint32_t* seeds2) {
+    BIND(c);
+    if (!c->camera_set) { c->err = "camera not set"; return RTX_ERR_STATE; }
+    if (!seeds2) { c->err = "primary_seeds: null array"; return RTX_ERR_INVALID; }
+    DevFrame f; int r = make_frame(c, p, f); if (r) return r;
+    DevBuf d_seeds; const size_t n = (size_t)p->width * p->height;
+    HIPCHK(c, d_seeds.ensure(n * 8));
+    launch_dbg_primary_seeds(c->stream, f, (const CameraGPU*)c->d_cam.p, sample_id, (uint32_t*)d_seeds.p);
+    HIPCHK(c, hipGetLastError());
+    TO_HOST(c, seeds2, d_seeds.p, n * 8);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RTX_OK;
+}
 static int dbg_trace(rtx_ctx* c, const float* rays8, uint32_t n, int any, float* hits4, uint8_t* occ) {
     BIND(c);
     if (!c->committed) { c->err = "scene not committed"; return RTX_ERR_STATE; }

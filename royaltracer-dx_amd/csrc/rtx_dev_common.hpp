@@ -78,6 +78,39 @@ __device__ __forceinline__ void stage_camera(CameraGPU& cam, const CameraGPU* __
     if (threadIdx.x < 64) ((float*)&cam)[threadIdx.x] = ((const float*)cam_p)[threadIdx.x];
 }
 
+// |cosine| between a primary ray and the view axis (the third column of viewI), sign-free: left- and right-handed views alike (include/rtx.h, THIN LENS: cz)
+__device__ __forceinline__ float view_axis_cos(const CameraGPU& cam, f3 d) {
+    const float* Vi = cam.viewI;
+    return fabsf((d.x * Vi[8] + d.y * Vi[9]) + d.z * Vi[10]);
+}
+// PIXEL, SAMPLE -> PRIMARY RAY AND STARTING SEED of a path of rtx_render / rtx_render_adaptive: the sample's seed, RTX_FLAG_JITTER's two draws, the pinhole ray (primary_ray).
+// LENS (rtx_set_lens with a radius > 0; include/rtx.h, THIN LENS, operation for operation): two more draws choose a point of the aperture disk, and the ray runs from there
+// through the pinhole ray's point at view-axis depth f.lens_focus.  The path starts from the seed state after the draws.  Called by both raygen kernels and by the two debug
+// probes (k_dbg_primary, k_dbg_primary_seeds); LENS = false reads neither lens member of the frame.
+template <bool LENS>
+__device__ __forceinline__ void camera_sample(const CameraGPU& cam, const DevFrame& f, uint32_t x, uint32_t y, uint32_t sample, f3& o, f3& d, uint32_t& s0, uint32_t& s1) {
+    seed_init(x, y, sample, f.frame_seed, s0, s1);
+    float jx = 0.0f, jy = 0.0f;
+    if (f.flags & 2u) { jx = tea_next(s0, s1); jy = tea_next(s0, s1); }   // RayGen.hlsl:84-85
+    primary_ray(cam, f.width, f.height, x, y, jx, jy, o, d);
+    if constexpr (LENS) {
+        const float* Vi = cam.viewI;
+        const float xi1 = tea_next(s0, s1), xi2 = tea_next(s0, s1);
+        const float r = sqrtf(xi1);
+        float sn, cs; sincos_(kTwoPi * xi2, sn, cs);
+        const float lx = (f.lens_radius * r) * cs, ly = (f.lens_radius * r) * sn;
+        const float cz = view_axis_cos(cam, d);
+        const float ft = f.lens_focus / cz;
+        const f3 P = mk3(o.x + d.x * ft, o.y + d.y * ft, o.z + d.z * ft);                                                              // the point in focus
+        const f3 ol = mk3((o.x + Vi[0] * lx) + Vi[4] * ly, (o.y + Vi[1] * lx) + Vi[5] * ly, (o.z + Vi[2] * lx) + Vi[6] * ly);          // the lens point: camera right / up
+        const f3 v = mk3(P.x - ol.x, P.y - ol.y, P.z - ol.z);
+        const float r2 = (v.x * v.x + v.y * v.y) + v.z * v.z;
+        const float inv = 1.0f / sqrtf(r2);
+        const f3 dl = mk3(v.x * inv, v.y * inv, v.z * inv);
+        if (cz > 0.0f && finite3(dl)) { o = ol; d = dl; }                  // (else the path keeps the pinhole ray; the two draws are consumed either way)
+    }
+}
+
 // THE CHUNK DEAL of the raygen kernels, one row of it: a kernel walks the rows k = 0, 1, ... with `for (uint32_t k = 0, row0 = 0, c; row0 < nchunks; k++)`, nchunks =
 // f.chunks_per_sample * f.batch_spp; this returns whether row k holds a chunk for this workgroup's sub-queue, and which (c), and advances row0.  Chunk c = 256 consecutive path
 // slots of ONE sample; chunks are dealt round-robin to workgroups so that every workgroup's sub-queue holds a representative sample of the image (load balance across bounces).

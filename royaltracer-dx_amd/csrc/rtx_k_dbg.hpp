@@ -121,16 +121,37 @@ __global__ void k_dbg_tea(uint32_t s0, uint32_t s1, uint32_t n, float* __restric
     for (uint32_t i = 0; i < n; i++) out[i] = tea_next(s0, s1);
     seed_out[0] = s0; seed_out[1] = s1;
 }
+// what the raygen kernels start a path with (camera_sample): the ray, resp. the seed state after its draws
+template <bool LENS>
 __global__ __launch_bounds__(kBlock) void k_dbg_primary(DevFrame f, const CameraGPU* __restrict__ cam, uint32_t sample_id, F4* __restrict__ rays) {
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= f.width * f.height) return;
     const uint32_t x = i % f.width, y = i / f.width;
-    uint32_t s0, s1; seed_init(x, y, sample_id, f.frame_seed, s0, s1);
-    float jx = 0.0f, jy = 0.0f;
-    if (f.flags & 2u) { jx = tea_next(s0, s1); jy = tea_next(s0, s1); }
-    f3 o, d; primary_ray(*cam, f.width, f.height, x, y, jx, jy, o, d);
+    uint32_t s0, s1; f3 o, d;
+    camera_sample<LENS>(*cam, f, x, y, sample_id, o, d, s0, s1);
     rays[2 * i] = {o.x, o.y, o.z, kTMinCam};
     rays[2 * i + 1] = {d.x, d.y, d.z, kTMax};
+}
+template <bool LENS>
+__global__ __launch_bounds__(kBlock) void k_dbg_primary_seeds(DevFrame f, const CameraGPU* __restrict__ cam, uint32_t sample_id, uint32_t* __restrict__ seeds2) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= f.width * f.height) return;
+    const uint32_t x = i % f.width, y = i / f.width;
+    uint32_t s0, s1; f3 o, d;
+    camera_sample<LENS>(*cam, f, x, y, sample_id, o, d, s0, s1);
+    seeds2[2 * (size_t)i] = s0; seeds2[2 * (size_t)i + 1] = s1;
+}
+// rtx_focus_distance_at: the first hit of pixel (x, y)'s pixel-corner pinhole ray, as the debug layers trace it (for_each_first_hit, rtx_k_film.hpp), as a depth along the view
+// axis: t * cz, 0 on a miss.  One workgroup (it stages the scene's LDS); every lane traces the same ray, lane 0 stores
+template <bool CUT>
+__global__ __launch_bounds__(kBlock) void k_focus_distance(DevScene sc, const SmallRecPair* __restrict__ small, uint32_t width, uint32_t height, const CameraGPU* __restrict__ cam, uint32_t x, uint32_t y, float* __restrict__ out) {
+    extern __shared__ F4 lds[];
+    const TraceLds L = stage_lds(sc, lds);
+    __syncthreads();
+    f3 o, d; primary_ray(*cam, width, height, x, y, 0.0f, 0.0f, o, d);
+    float t, u, v; uint32_t prim;
+    trace_ray<false, CUT>(sc, small, L, o, d, kTMinCam, kTMax, t, u, v, prim);
+    if (threadIdx.x == 0) out[0] = prim != kMissPrim ? t * view_axis_cos(*cam, d) : 0.0f;
 }
 
 }  // namespace rtx

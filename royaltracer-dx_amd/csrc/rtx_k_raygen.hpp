@@ -9,7 +9,8 @@ namespace rtx {
 // raygen: one thread per path slot of the batch
 // ---------------------------------------------------------------------------------------------
 // LIST (all three raygen kernels): the frame's slot space is the active list of rtx_render_adaptive (real_slot, rtx_dev_common.hpp)
-template <bool LIST>
+// LENS (the two that shoot camera rays): the thin-lens camera (camera_sample, rtx_dev_common.hpp); false = the pinhole, the kernels as they always were
+template <bool LIST, bool LENS>
 __global__ __launch_bounds__(kBlock) void k_raygen(DevFrame f, DevPaths p, const CameraGPU* __restrict__ cam_p, uint32_t* __restrict__ queue, uint32_t* __restrict__ qcount, uint32_t compact) {
     __shared__ CameraGPU cam;
     __shared__ uint32_t s_n;
@@ -33,10 +34,8 @@ __global__ __launch_bounds__(kBlock) void k_raygen(DevFrame f, DevPaths p, const
         const bool valid = slot_to_pixel(f, real_slot<LIST>(f, pl), x, y);
         const uint32_t slot = block_push(valid, &s_n);
         if (valid) {
-            uint32_t s0, s1; seed_init(x, y, f.sample_first + sl, f.frame_seed, s0, s1);
-            float jx = 0.0f, jy = 0.0f;
-            if (f.flags & 2u) { jx = tea_next(s0, s1); jy = tea_next(s0, s1); }   // RayGen.hlsl:84-85
-            f3 o, d; primary_ray(cam, f.width, f.height, x, y, jx, jy, o, d);
+            uint32_t s0, s1; f3 o, d;
+            camera_sample<LENS>(cam, f, x, y, f.sample_first + sl, o, d, s0, s1);
             const uint32_t dst = compact ? blockIdx.x * f.qcap + slot : pid;      // compact state: indexed by the queue position
             p.ray_o[dst] = {o.x, o.y, o.z, u2f(s1)};
             p.ray_d[dst] = {d.x, d.y, d.z, 1.0f};
@@ -64,7 +63,7 @@ __global__ __launch_bounds__(kBlock) void k_packet_masks(DevScene sc, DevFrame f
     if (lane_id() == 0) masks[blk] = keep;
 }
 
-template <bool LIST>
+template <bool LIST, bool LENS>
 __global__ __launch_bounds__(kBlock) void k_raygen_trace_small(DevScene sc, const SmallRecPair* __restrict__ small, DevFrame f, DevPaths p, const CameraGPU* __restrict__ cam_p,
                                                                uint32_t* __restrict__ queue, uint32_t* __restrict__ qcount, uint32_t* __restrict__ gencount,
                                                                const unsigned long long* __restrict__ masks /* k_packet_masks */) {
@@ -94,13 +93,11 @@ __global__ __launch_bounds__(kBlock) void k_raygen_trace_small(DevScene sc, cons
         const bool valid = slot_to_pixel(f, pl, x, y);
         f3 o = mk3(0, 0, 0), d = mk3(0, 0, 1);
         if (valid) {
-            seed_init(x, y, f.sample_first + sl, f.frame_seed, s0, s1);
-            float jx = 0.0f, jy = 0.0f;
-            if (f.flags & 2u) { jx = tea_next(s0, s1); jy = tea_next(s0, s1); }
-            primary_ray(cam, f.width, f.height, x, y, jx, jy, o, d);
+            camera_sample<LENS>(cam, f, x, y, f.sample_first + sl, o, d, s0, s1);
             generated++;
         }
-        // records that some ray of this wave's 8x8 pixel block can touch (slot_to_pixel lays one block out per wave): precomputed per block
+        // records that some ray of this wave's 8x8 pixel block can touch (slot_to_pixel lays one block out per wave): precomputed per block (LENS: all of them — the block's
+        // pyramid from the camera origin does not bound rays that start elsewhere on the aperture, so the host fills the masks with ones instead of launching k_packet_masks)
         const unsigned long long km = masks[pl >> 6];
         const unsigned long long keep = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(km >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)km);
         float t, u, v; uint32_t prim;

@@ -44,7 +44,7 @@ __device__ unsigned long long g_sec[36];          // [0,12) cycles, [12,24) acti
 }  // namespace rtx
 
 // the kernels, by concern
-#include "rtx_k_raygen.hpp"         // k_raygen, k_packet_masks, k_raygen_trace_small, k_primary_surface, k_raygen_shared
+#include "rtx_k_raygen.hpp"         // k_raygen, k_packet_masks, k_raygen_trace_small, k_primary_surface, k_raygen_shared (the pixel -> ray step of the first and third: camera_sample, rtx_dev_common.hpp)
 #include "rtx_k_trace.hpp"          // k_trace_closest, k_trace_shadow
 #include "rtx_k_shade.hpp"          // k_shade, k_shade_dense
 #include "rtx_k_bounce_small.hpp"   // k_bounce_small
@@ -91,14 +91,18 @@ template <bool V> using BoolC = std::integral_constant<bool, V>;
 template <class F> static void dispatch_bool(bool v, F f) { if (v) f(BoolC<true>{}); else f(BoolC<false>{}); }
 
 void launch_raygen(hipStream_t st, const DevFrame& f, const DevPaths& p, const CameraGPU* cam, uint32_t* queue, uint32_t* qcount, bool compact) {
-    dispatch_bool(f.list != nullptr, [&](auto list) { hipLaunchKernelGGL(k_raygen<decltype(list)::value>, dim3(f.nblocks), dim3(kBlock), 0, st, f, p, cam, queue, qcount, compact ? 1u : 0u); });
+    dispatch_bool(f.list != nullptr, [&](auto list) { dispatch_bool(f.lens_radius > 0.0f, [&](auto lens) {
+        hipLaunchKernelGGL((k_raygen<decltype(list)::value, decltype(lens)::value>), dim3(f.nblocks), dim3(kBlock), 0, st, f, p, cam, queue, qcount, compact ? 1u : 0u);
+    }); });
 }
 void launch_packet_masks(hipStream_t st, const DevScene& sc, const DevFrame& f, const CameraGPU* cam, unsigned long long* masks) {
     const uint32_t nblk = f.npl / 64u;
     hipLaunchKernelGGL(k_packet_masks, dim3((nblk + 3u) / 4u), dim3(kBlock), 0, st, sc, f, cam, masks);
 }
 void launch_raygen_trace_small(hipStream_t st, const DevScene& sc, const DevFrame& f, const DevPaths& p, const CameraGPU* cam, uint32_t* queue, uint32_t* qcount, uint32_t* gencount, const unsigned long long* masks) {
-    dispatch_bool(f.list != nullptr, [&](auto list) { hipLaunchKernelGGL(k_raygen_trace_small<decltype(list)::value>, dim3(f.nblocks), dim3(kBlock), trace_lds_bytes(sc), st, sc, sc.small, f, p, cam, queue, qcount, gencount, masks); });
+    dispatch_bool(f.list != nullptr, [&](auto list) { dispatch_bool(f.lens_radius > 0.0f, [&](auto lens) {
+        hipLaunchKernelGGL((k_raygen_trace_small<decltype(list)::value, decltype(lens)::value>), dim3(f.nblocks), dim3(kBlock), trace_lds_bytes(sc), st, sc, sc.small, f, p, cam, queue, qcount, gencount, masks);
+    }); });
 }
 void launch_primary_surface(hipStream_t st, const DevScene& sc, const DevFrame& f, const CameraGPU* cam, unsigned long long* masks, unsigned long long* hits, F4* rec) {
     hipLaunchKernelGGL(k_primary_surface, dim3(f.npl / kBlock), dim3(kBlock), trace_lds_bytes(sc), st, sc, sc.small, f, cam, masks, hits, rec);
@@ -355,7 +359,13 @@ void launch_dbg_tea(hipStream_t st, uint32_t s0, uint32_t s1, uint32_t n, float*
     hipLaunchKernelGGL(k_dbg_tea, dim3(1), dim3(64), 0, st, s0, s1, n, out, seed_out);
 }
 void launch_dbg_primary(hipStream_t st, const DevFrame& f, const CameraGPU* cam, uint32_t sample_id, F4* rays) {
-    hipLaunchKernelGGL(k_dbg_primary, dim3((f.width * f.height + kBlock - 1) / kBlock), dim3(kBlock), 0, st, f, cam, sample_id, rays);
+    dispatch_bool(f.lens_radius > 0.0f, [&](auto lens) { hipLaunchKernelGGL(k_dbg_primary<decltype(lens)::value>, dim3((f.width * f.height + kBlock - 1) / kBlock), dim3(kBlock), 0, st, f, cam, sample_id, rays); });
+}
+void launch_dbg_primary_seeds(hipStream_t st, const DevFrame& f, const CameraGPU* cam, uint32_t sample_id, uint32_t* seeds2) {
+    dispatch_bool(f.lens_radius > 0.0f, [&](auto lens) { hipLaunchKernelGGL(k_dbg_primary_seeds<decltype(lens)::value>, dim3((f.width * f.height + kBlock - 1) / kBlock), dim3(kBlock), 0, st, f, cam, sample_id, seeds2); });
+}
+void launch_focus_distance(hipStream_t st, const DevScene& sc, uint32_t width, uint32_t height, const CameraGPU* cam, uint32_t x, uint32_t y, float* out) {
+    dispatch_bool(sc.tri_cut != nullptr, [&](auto cut) { hipLaunchKernelGGL(k_focus_distance<decltype(cut)::value>, dim3(1), dim3(kBlock), trace_lds_bytes(sc), st, sc, sc.small, width, height, cam, x, y, out); });
 }
 
 }  // namespace rtx

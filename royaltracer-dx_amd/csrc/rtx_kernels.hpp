@@ -71,6 +71,9 @@ struct DevFrame {
     // rtx_render_adaptive: a pass renders a frame whose slot space is the ACTIVE LIST — virtual slot v in [0, 256 n_active) is the real slot list[v >> 8] * 256 + (v & 255);
     // npl and chunks_per_sample are the virtual frame's (256 n_active, n_active), pid = sl * npl + v.  Read by the list-aware instantiations only (nullptr everywhere else)
     const uint32_t* list;
+    // rtx_set_lens (the LAST members: every other one keeps its place in the kernel arguments): aperture radius and focus distance of the thin-lens camera.  Read by the LENS
+    // instantiations of the raygen kernels only (camera_sample<true>, rtx_dev_common.hpp); lens_radius == 0 is the pinhole and launches what it always launched
+    float lens_radius, lens_focus;
 };
 
 // TAPERED sub-queue sizes (RTX_OPT_TAPER).  Workgroups are dispatched in index order and every launch of a bounce ends when its LAST workgroup does; with equal sub-queues
@@ -257,6 +260,8 @@ void launch_dbg_opacity(hipStream_t, const DevScene&, const F4* hits, uint32_t n
 void launch_dbg_env_sample(hipStream_t, const DevScene&, const uint32_t* seeds2, uint32_t n, F4* out);
 void launch_dbg_env_eval(hipStream_t, const DevScene&, const float* dirs3, uint32_t n, F4* out);
 void launch_dbg_tea(hipStream_t, uint32_t s0, uint32_t s1, uint32_t n, float* out, uint32_t* seed_out);
-void launch_dbg_primary(hipStream_t, const DevFrame&, const CameraGPU* cam, uint32_t sample_id, F4* rays);
+void launch_dbg_primary(hipStream_t, const DevFrame&, const CameraGPU* cam, uint32_t sample_id, F4* rays);                                  // camera_sample at every pixel: the rays (f.lens_radius > 0: through the lens)
+void launch_dbg_primary_seeds(hipStream_t, const DevFrame&, const CameraGPU* cam, uint32_t sample_id, uint32_t* seeds2);                   // ... and the seed state the paths start from
+void launch_focus_distance(hipStream_t, const DevScene&, uint32_t width, uint32_t height, const CameraGPU* cam, uint32_t x, uint32_t y, float* out);   // rtx_focus_distance_at
 
 }  // namespace rtx

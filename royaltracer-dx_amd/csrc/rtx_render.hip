@@ -209,7 +209,10 @@ int render_frame(rtx_ctx* c, const rtx_params* p, const DevFrame& f_real, uint32
     if (R.stealing) HIPCHK(c, c->pt.d_heads.ensure(R.nheads * 4));
     HIPCHK(c, c->pt.d_pmask.ensure(((size_t)f_real.npl / 64 + 1) * 8));        // (per real slot, like the shared-primary records: computed once per call)
     // RTX_OPT_SHARED_PRIMARY: without jitter the camera ray of a pixel is the same for every sample, so the fused tiny-scene path traces and reconstructs it once per call
-    const bool shared_primary = tiny_fused && c->opt.shared_primary && !(p->flags & RTX_FLAG_JITTER);
+    // A THIN LENS (rtx_set_lens, radius > 0) ends both: every sample starts at its own point of the aperture, so no two samples of a pixel share a ray — no shared primary hit,
+    // whatever the option says — and the pyramid of a block's corner rays from the camera origin does not bound them — no packet culling: every mask word is all ones
+    const bool lens = f_real.lens_radius > 0.0f;
+    const bool shared_primary = tiny_fused && c->opt.shared_primary && !(p->flags & RTX_FLAG_JITTER) && !lens;
     if (shared_primary) { HIPCHK(c, c->pt.d_prim_rec.ensure(((size_t)f_real.npl * 3 + 1) * 16)); HIPCHK(c, c->pt.d_prim_hits.ensure(((size_t)f_real.npl / 64 * 2 + 1) * 8)); }
     R.prim_rec = shared_primary ? (const F4*)c->pt.d_prim_rec.p : nullptr; R.rec_npl = f_real.npl;
     const size_t shn = qtot * R.nee1;
@@ -243,7 +246,10 @@ int render_frame(rtx_ctx* c, const rtx_params* p, const DevFrame& f_real, uint32
     // per 8x8 block resp. per pixel, shared by all samples and batches of this call; recomputed every call (camera, scene, size and shard may all have changed)
     const bool tables_in_place = lp && !lp->first;             // a later pass of the same rtx_render_adaptive call
     if (shared_primary && !tables_in_place) { Timed t(c, RTX_K_RAYGEN); launch_primary_surface(st, c->dsc, f_real, R.cam, (unsigned long long*)c->pt.d_pmask.p, (unsigned long long*)c->pt.d_prim_hits.p, (F4*)c->pt.d_prim_rec.p); }
-    else if (tiny_fused && !shared_primary && !tables_in_place) launch_packet_masks(st, c->dsc, f_real, R.cam, (unsigned long long*)c->pt.d_pmask.p);
+    else if (tiny_fused && !tables_in_place) {
+        if (lens) HIPCHK(c, hipMemsetAsync(c->pt.d_pmask.p, 0xFF, ((size_t)f_real.npl / 64 + 1) * 8, st));      // keep every record (traverse_small masks the bits at and above nsmall itself, as for its default ~0)
+        else launch_packet_masks(st, c->dsc, f_real, R.cam, (unsigned long long*)c->pt.d_pmask.p);
+    }
     for (uint32_t bi = 0; bi < nbatches; bi++) {
         DevFrame fb = f;
         fb.sample_first = sample_first + bi * bspp;

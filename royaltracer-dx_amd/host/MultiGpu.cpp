@@ -302,6 +302,16 @@ void MultiGpuFrame::RenderRestir(const rtx_params& p0) {
 void MultiGpuFrame::SetCamera(const float view[16], const float proj[16]) {
     for (size_t r = 0; r < m->ctx.size(); r++) { if (!m->ctx[r]) continue; hipck(hipSetDevice(m_devices[r]), "hipSetDevice"); if (rtx_set_camera(m->ctx[r], view, proj) != RTX_OK) throw std::runtime_error(rtx_last_error(m->ctx[r])); }
 }
+void MultiGpuFrame::SetLens(float radius, float focus) {
+    rtx_lens l{}; l.aperture_radius = radius; l.focus_distance = focus;
+    for (size_t r = 0; r < m->ctx.size(); r++) { if (!m->ctx[r]) continue; hipck(hipSetDevice(m_devices[r]), "hipSetDevice"); if (rtx_set_lens(m->ctx[r], &l) != RTX_OK) throw std::runtime_error(rtx_last_error(m->ctx[r])); }
+}
+float MultiGpuFrame::FocusDistanceAt(uint32_t x, uint32_t y, int rank) {
+    float d = 0.0f;
+    hipck(hipSetDevice(m_devices[rank]), "hipSetDevice");
+    if (rtx_focus_distance_at(m->ctx[rank], m_w, m_h, x, y, &d) != RTX_OK) throw std::runtime_error(std::string("rtx_focus_distance_at: ") + rtx_last_error(m->ctx[rank]));
+    return d;
+}
 void MultiGpuFrame::ResetRestir() {
     for (size_t r = 0; r < m->ctx.size(); r++) { if (!m->ctx[r]) continue; hipck(hipSetDevice(m_devices[r]), "hipSetDevice"); if (rtx_restir_reset(m->ctx[r]) != RTX_OK) throw std::runtime_error(rtx_last_error(m->ctx[r])); }
 }

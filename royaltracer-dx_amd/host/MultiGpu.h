@@ -48,6 +48,8 @@ public:
     void SetEnvironment(const SceneEnvironment& env);
     double LastRefitMs() const { return m_refitMs; }        // wall time of the last SetInstanceTransform / SetMeshVertices / SetInstanceVisible: max over ranks
     void SetCamera(const float view[16], const float proj[16]);   // every rank (rtx_set_camera keeps the previous matrices for the reprojection)
+    void SetLens(float radius, float focus);              // every rank, like SetCamera (rtx_set_lens: the thin-lens camera; radius 0 = the pinhole)
+    float FocusDistanceAt(uint32_t x, uint32_t y, int rank = 0);   // autofocus (rtx_focus_distance_at) on one rank's replica, for the image size of the last Clear
     void ResetRestir();                                   // forget the ReSTIR history on every rank
     void SetOption(int option, int64_t value);            // rtx_set_option on every rank
     void Clear(uint32_t width, uint32_t height);          // zero every rank's accumulation buffer (view-change reset)

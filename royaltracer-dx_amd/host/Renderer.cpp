@@ -10,6 +10,8 @@ using nv_helpers_dx12::Manipulator;
 // this entry point resolves to null; inside librtx_hip.so it is the definition of csrc/rtx_api.hip
 extern "C" int rtx_update_mesh_vertices(rtx_ctx*, uint32_t mesh, const void* verts28, uint32_t nverts) __attribute__((weak));
 extern "C" int rtx_set_instance_visible(rtx_ctx*, uint32_t inst, int visible) __attribute__((weak));
+extern "C" int rtx_set_lens(rtx_ctx*, const rtx_lens*) __attribute__((weak));
+extern "C" int rtx_focus_distance_at(rtx_ctx*, uint32_t width, uint32_t height, uint32_t x, uint32_t y, float* distance_out) __attribute__((weak));
 
 Renderer::Renderer(UINT width, UINT height, std::string name) : m_width(width), m_height(height), m_aspectRatio((float)width / (float)height), m_title(std::move(name)) {
     m_params.width = width; m_params.height = height;
@@ -35,6 +37,7 @@ void Renderer::OnInit() {
     CameraManip.setWindowSize((int)m_width, (int)m_height);                         // Renderer.cpp:45
     CameraManip.setLookat(m_scene.eye, m_scene.center, m_scene.up);                 // Renderer.cpp:46-48
     Check(rtx_create(m_device, &m_ctx), "rtx_create");
+    if (m_lens.aperture_radius != 0.0f || m_lens.focus_distance != 0.0f) SetLens(m_lens.aperture_radius, m_lens.focus_distance);
     Check(rtx_set_materials(m_ctx, m_scene.materials.data(), (uint32_t)m_scene.materials.size()), "rtx_set_materials");
     for (const SceneModel& m : m_scene.models) {
         uint32_t id;
@@ -75,6 +78,23 @@ void Renderer::SetInstanceVisible(UINT instance, bool visible) {
     m_hidden[instance] = visible ? 0 : 1;
     for (UINT i : m_flippedInstances) if (i == instance) return;
     m_flippedInstances.push_back(instance);
+}
+
+void Renderer::SetLens(float radius, float focus) {
+    rtx_lens l{}; l.aperture_radius = radius; l.focus_distance = focus;
+    if (m_ctx) {
+        if (!rtx_set_lens) throw std::runtime_error("Renderer::SetLens: this build has no device library (rtx_set_lens)");
+        Check(rtx_set_lens(m_ctx, &l), "rtx_set_lens");
+    }
+    m_lens = l;
+}
+float Renderer::FocusDistanceAt(UINT x, UINT y) {
+    if (!m_ctx) throw std::logic_error("Renderer::FocusDistanceAt: call OnInit first");
+    if (!rtx_focus_distance_at) throw std::runtime_error("Renderer::FocusDistanceAt: this build has no device library (rtx_focus_distance_at)");
+    UpdateCameraBuffer();                                                            // the camera as the next frame will see it
+    float d = 0.0f;
+    Check(rtx_focus_distance_at(m_ctx, m_width, m_height, x, y, &d), "rtx_focus_distance_at");
+    return d;
 }
 
 void Renderer::SetEnvironment(const SceneEnvironment& env) {

@@ -38,6 +38,11 @@ public:
     // environment lighting (rtx_set_environment): before OnInit it is bound with the scene; afterwards the next OnUpdate hands it to the context and re-commits (tables only).
     // An environment with n = 0 clears it
     void SetEnvironment(const SceneEnvironment& env);
+    // the thin-lens camera (rtx_set_lens): aperture radius and focus distance in world units, radius 0 = the pinhole.  Camera state: before OnInit it is kept and set with the
+    // context, afterwards it takes effect at once — no commit, and like a camera move it leaves the accumulation to the caller
+    void SetLens(float radius, float focus);
+    // autofocus (rtx_focus_distance_at): the view-axis depth of what pixel (x, y) of the window sees first through the current camera, 0 = nothing.  After OnInit
+    float FocusDistanceAt(UINT x, UINT y);
     double LastRefitMs() const { return m_refitMs; }
 
     void OnInit();      // Renderer.cpp:44-103: camera lookat, load models, build acceleration structures, upload
@@ -77,5 +82,6 @@ private:
     float m_prevView[16]; bool m_havePrev = false;   // m_prevViewMatrix
     std::vector<UINT> m_movedInstances, m_changedMeshes; double m_refitMs = 0.0;
     SceneEnvironment m_env; bool m_haveEnv = false, m_envDirty = false;       // SetEnvironment: what it set (replaces the scene's own), and whether the context has yet to see it
+    rtx_lens m_lens{};                                                        // SetLens: what it set (all zero = the pinhole)
     std::vector<uint8_t> m_hidden; std::vector<UINT> m_flippedInstances;      // visibility per instance as last asked for; the instances whose value changed since the last OnUpdate
 };

@@ -24,6 +24,9 @@
 //                   [--env FILE [--env-res N] [--env-yaw DEG] [--env-scale S] [--env-hidden]]   environment lighting (rtx_set_environment): FILE is a latitude-longitude Radiance .hdr or
 //                   colour .pfm, resampled to an N x N octahedral map (default 512), turned by DEG degrees about +Y, radiance times S; --env-hidden: camera rays that miss stay black
 //                   [--sky R,G,B]   a constant sky of that radiance instead of a file; both work with --gpus N (every rank binds the same map) and are ignored by --mode restir
+//                   [--aperture R [--focus D | --focus-pixel X,Y]]   the thin-lens camera (rtx_set_lens): aperture radius and focus distance in world units; --focus-pixel
+//                   focuses on what that pixel sees before the first frame (rtx_focus_distance_at) and prints the distance, an explicit --focus wins; path tracer only
+//                   (--mode restir keeps its pinhole); works with --gpus N (every rank gets the lens), --adaptive and --denoise
 //                   [--gpus N [--devices 0,1,..] [--gather rccl|copy]]   the native N-GPU frame (MultiGpu.h): one process, N contexts, pixel tiles
 //                   round-robin, ONE RCCL all-gather per frame; `--gather copy` replaces the collective by device copies (several ranks on one GPU: tests)
 #include <algorithm>
@@ -32,6 +35,7 @@
 #include <cmath>
 #include <cstring>
 #include <fstream>
+#include <functional>
 #include <sstream>
 #include <stdexcept>
 #include <string>
@@ -48,6 +52,7 @@ static const char* kUsage =
     "                  [--no-textures]   OBJ scenes: ignore map_Kd images (implies --no-cutouts)\n"
     "                  [--no-cutouts]    OBJ scenes: ignore map_d images (no alpha cut-outs)   [--kd-alpha]   a 32-bit map_Kd without a map_d is its material's opacity map too\n"
     "                  [--env FILE [--env-res N] [--env-yaw DEG] [--env-scale S] [--env-hidden]] [--sky R,G,B]   environment lighting\n"
+    "                  [--aperture R [--focus D | --focus-pixel X,Y]]   thin-lens camera: depth of field (path tracer)\n"
     "                  [--gpus N [--devices 0,1,..] [--gather rccl|copy]]\n";
 
 int main(int argc, char** argv) {
@@ -58,6 +63,7 @@ int main(int argc, char** argv) {
     bool adaptive = false; rtx_adaptive ad{}; ad.min_spp = 8; ad.step_spp = 8;
     bool denoise = false; rtx_denoise_params dnp{};
     bool textures = true; SceneCutouts cutouts = kCutoutsMapD; bool kd_alpha = false;
+    float aperture = 0.0f, focus = 0.0f; bool focus_set = false; std::string focus_pixel;
     std::string env_file, sky; UINT env_res = 512; float env_yaw = 0.0f, env_scale = 1.0f; bool env_hidden = false;
     for (int i = 1; i < argc; i++) {
         auto arg = [&](const char* k) { return !strcmp(argv[i], k) && i + 1 < argc; };
@@ -72,6 +78,7 @@ int main(int argc, char** argv) {
         else if (arg("--env")) env_file = argv[++i]; else if (arg("--env-res")) env_res = (UINT)atoi(argv[++i]); else if (arg("--env-yaw")) env_yaw = (float)atof(argv[++i]);
         else if (arg("--env-scale")) env_scale = (float)atof(argv[++i]); else if (!strcmp(argv[i], "--env-hidden")) env_hidden = true; else if (arg("--sky")) sky = argv[++i];
         else if (!strcmp(argv[i], "--denoise")) denoise = true; else if (arg("--denoise-levels")) dnp.levels = (uint32_t)atoi(argv[++i]); else if (arg("--sigma-color")) dnp.sigma_color = (float)atof(argv[++i]); else if (arg("--sigma-plane")) dnp.sigma_plane = (float)atof(argv[++i]);
+        else if (arg("--aperture")) aperture = (float)atof(argv[++i]); else if (arg("--focus")) { focus = (float)atof(argv[++i]); focus_set = true; } else if (arg("--focus-pixel")) focus_pixel = argv[++i];
         else if (arg("--halo")) halo = (UINT)atoi(argv[++i]); else if (arg("--gpus")) gpus = atoi(argv[++i]); else if (arg("--devices")) devlist = argv[++i]; else if (arg("--gather")) gather = argv[++i];
         else if (arg("--out")) out = argv[++i]; else if (arg("--device")) device = atoi(argv[++i]); else if (!strcmp(argv[i], "--lambert")) lambert = true;
         else { fprintf(stderr, "unknown argument %s\n", argv[i]); return 2; }
@@ -83,6 +90,19 @@ int main(int argc, char** argv) {
     if (adaptive && (restir || gpus > 1 || !devlist.empty())) { fprintf(stderr, "--adaptive is the path tracer on one GPU (no --mode restir, --gpus, --devices)\n"); return 2; }
     if (denoise && restir) { fprintf(stderr, "--denoise filters the path tracer's accumulation (no --mode restir: that frame has its own reuse passes)\n"); return 2; }
     if (!env_file.empty() && !sky.empty()) { fprintf(stderr, "--env and --sky exclude each other\n"); return 2; }
+    UINT fpx = 0, fpy = 0;
+    if (!focus_pixel.empty()) { char tail = 0; if (sscanf(focus_pixel.c_str(), "%u,%u%c", &fpx, &fpy, &tail) != 2) { fprintf(stderr, "--focus-pixel takes X,Y\n"); return 2; } }
+    if (aperture > 0.0f && !focus_set && focus_pixel.empty()) { fprintf(stderr, "--aperture needs --focus D or --focus-pixel X,Y\n"); return 2; }
+    // the lens of the run, once the camera is in place: autofocus reports its distance; an explicit --focus wins.  measure(x, y) = rtx_focus_distance_at
+    auto lens_focus = [&](const std::function<float(UINT, UINT)>& measure) {
+        if (!focus_pixel.empty()) {
+            const float d = measure(fpx, fpy);
+            printf("autofocus: pixel %u,%u is at view depth %.9g%s\n", fpx, fpy, d, d > 0.0f ? "" : " (nothing there)");
+            if (!focus_set) focus = d;
+        }
+        if (aperture > 0.0f && !(focus > 0.0f)) throw std::runtime_error("nothing to focus on: give --focus D or another --focus-pixel");
+        return focus;
+    };
     SceneEnvironment env;
     try {
         if (!env_file.empty()) env = LoadEnvironment(env_file, env_res, env_yaw, env_scale, env_hidden);
@@ -118,6 +138,7 @@ int main(int argc, char** argv) {
             mg.SetScene(sc, (float)w / (float)h);
             mg.Clear(w, h);
             for (UINT i : hide) mg.SetInstanceVisible(i, false);
+            if (aperture > 0.0f || !focus_pixel.empty()) { const float fd = lens_focus([&](UINT x, UINT y) { return mg.FocusDistanceAt(x, y, only_rank >= 0 ? only_rank : 0); }); mg.SetLens(aperture, fd); }
             bool blink_hidden = blink >= 0 && std::find(hide.begin(), hide.end(), (UINT)blink) != hide.end();
             rtx_params p{}; p.width = w; p.height = h; p.spp = spp; p.max_bounces = bounces; p.nee_samples = nee; p.rr_start = 3;
             p.tile_size = gpus > 1 ? 32 : 64;      // round-robin deal: 32-px tiles even out the background across 8 ranks (max / mean 1.04 instead of 1.15, tools/shard_time.py)
@@ -167,6 +188,7 @@ int main(int argc, char** argv) {
         r.OnInit();
         if (restir && rtx_set_option(r.Context(), RTX_OPT_RESTIR_WAVEFRONT, literal ? 0 : 1) != RTX_OK) throw std::runtime_error(rtx_last_error(r.Context()));
         for (UINT i : hide) r.SetInstanceVisible(i, false);
+        if (aperture > 0.0f || !focus_pixel.empty()) { const float fd = lens_focus([&](UINT x, UINT y) { return r.FocusDistanceAt(x, y); }); r.SetLens(aperture, fd); }
         bool blink_hidden = blink >= 0 && std::find(hide.begin(), hide.end(), (UINT)blink) != hide.end();
         XMFLOAT3 eye0, ctr0, up0; nv_helpers_dx12::CameraManip.getLookat(eye0, ctr0, up0);
         Scene inst0; bool have_inst0 = false;
