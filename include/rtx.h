@@ -296,8 +296,46 @@ int  rtx_update_mesh_vertices(rtx_ctx*, uint32_t mesh, const void* verts28, uint
    rtx_save_scene_cache with an opacity map bound is RTX_ERR_STATE.
    OPTIONS while a cut-out is active: RTX_OPT_FUSED_BVH, RTX_OPT_SHADE_DENSE, RTX_OPT_SORT_MATERIALS, RTX_OPT_WORK_STEALING and RTX_OPT_OCCLUDER_CACHE are ignored (the default
    form runs); RTX_OPT_COMPACT_STATE 0 / 1, RTX_OPT_STACK_PRIVATE, RTX_OPT_STACK_CAP and RTX_OPT_TRACE_SCHED 0-7 all work. */
+/* NORMAL MAPS (new; the reference parses norm / map_Bump and samples nothing: an extension like map_Kd, unpinned by the reference, pinned by its own definition and properties in
+   tests/test_normalmap_ref.py / tests/test_normalmap.py).  A tangent-space normal map perturbs the SHADING normal of a hit, so that a wall shades less flat than its triangles.
+   All device arithmetic is float32 in exactly the written order, no contraction, plain * + - / and sqrtf.
+   SLOT.  rtx_set_material_map(ctx, material, RTX_MAP_NORMAL, tex) binds a texture of the table above (RTX_MAP_NORMAL = 4; the values 1 and 3 stay unknown slots).  The RGB
+   bytes are a tangent-space normal, OpenGL convention: green = +bitangent = the direction of increasing v.  RTX_TEX_SRGB is ignored for this slot, as the opacity slot ignores it.
+   DECODE TABLE.  Nt[b] = max(((float)b - 128.0f) / 127.0f, -1.0f), 256 floats filled on the host: byte 128 is exactly 0, byte 255 exactly 1.
+   TANGENT TABLE.  6 floats per GLOBAL triangle id, built on the host at rtx_commit_scene in double from the float32 inputs, each value rounded to float32 once: with p0..2 the
+   mesh's current OBJECT-space vertex positions and uv0..2 the triangle's corner pairs (zeros for a mesh without UVs)
+       e1 = p1 - p0;  e2 = p2 - p0;  du1 = uv1.x - uv0.x;  dv1 = uv1.y - uv0.y;  du2 = uv2.x - uv0.x;  dv2 = uv2.y - uv0.y;  det = du1 * dv2 - du2 * dv1
+       T.k = (e1.k * dv2 - e2.k * dv1) / det;  B.k = (e2.k * du1 - e1.k * du2) / det
+   det == 0, or any of the six values not finite after rounding: six zeros.  Object space: a transform-only commit does not touch the table, a commit after
+   rtx_update_mesh_vertices re-derives it.  The table exists only while a normal map is active.
+   NORMAL-MAPPED HIT.  The hit's material m is not an emitter (an emitter's map has no effect, as for map_Kd) and has RTX_MAP_NORMAL = tex >= 0.  n = the world shading normal of
+   the surface reconstruction, M = the instance's objectToWorld (M[4 * column + row]), wo = the ray's direction negated, (u, v) = the hit record's barycentrics:
+       b0, s, t exactly as PER HIT of map_Kd;  x0, y0, fx, fy, ixa, iyb exactly as Sample()
+       c.k (k = x, y, z from bytes r, g, b): cab = Nt[byte k of texel(ixa, iyb)];  top = c00 + fx * (c10 - c00);  bot = c01 + fx * (c11 - c01);  c.k = top + fy * (bot - top)
+       if c.x == 0 and c.y == 0: n' = n                                                  (a flat texel changes NOTHING, to the bit)
+       Tw.k = (M[0 + k] * T.x + M[4 + k] * T.y) + M[8 + k] * T.z;  Bw likewise
+       dT = (n.x * Tw.x + n.y * Tw.y) + n.z * Tw.z;  tv.k = Tw.k - n.k * dT;  l2 = (tv.x * tv.x + tv.y * tv.y) + tv.z * tv.z
+       if not (l2 > 0) or l2 is inf: n' = n
+       inv = 1.0f / sqrtf(l2);  t.k = tv.k * inv
+       bv = (n.y * t.z - n.z * t.y, n.z * t.x - n.x * t.z, n.x * t.y - n.y * t.x)
+       sg = ((bv.x * Bw.x + bv.y * Bw.y) + bv.z * Bw.z) < 0 ? -1.0f : 1.0f               (handedness from the geometry: mirrored UVs and mirrored instances alike)
+       m.k = (t.k * c.x + (bv.k * sg) * c.y) + n.k * c.z;  m2 = (m.x * m.x + m.y * m.y) + m.z * m.z
+       if not (m2 > 0) or m2 is inf: n' = n;  else n'.k = m.k * (1.0f / sqrtf(m2))
+       a = (n.x * wo.x + n.y * wo.y) + n.z * wo.z;  a' likewise with n'
+       if (a > 0 and not a' > 0) or (a < 0 and not a' < 0): n' = n                      (the map never turns the surface away from the viewer)
+   n' replaces the shading normal for everything the shading does at that hit: the transmission flip, the mixture's view terms, triangle-light and environment NEE, the
+   continuation.  Position, flat normal, area, the emissive hit, the light list and the random-number sequence are untouched.  CONSEQUENCE: a scene whose normal maps hold only
+   texels with r = g = 128 is, bit for bit, the scene with no normal map bound.
+   WHO SEES IT.  rtx_render, rtx_render_adaptive, rtx_debug_shading_normal.  IGNORED BY rtx_render_v6_pass1, rtx_render_restir, the guides of rtx_denoise, rtx_read_layer 10-17,
+   rtx_debug_surface and rtx_focus_distance_at — as they ignore map_Kd.
+   CALLS AND COMMITS follow the map_Kd rules word for word: valid before the first commit and on a resident scene; rtx_commit_scene again (rendering in between is
+   RTX_ERR_STATE); RTX_ERR_INVALID leaves the scene committed and untouched; rtx_set_materials resets the slot to -1; on a resident general scene a map-only commit uploads
+   tables only (rtx_stats.bvh_refits and rtx_debug_tree_hash unchanged); a tiny scene (<= 64 triangles) runs on the general BVH path while a non-emitting material that a
+   triangle uses has a normal map, and the commit that crosses that line is a rebuild; rtx_save_scene_cache with one bound is RTX_ERR_STATE.  RTX_OPT_FUSED_BVH,
+   RTX_OPT_SHADE_DENSE and RTX_OPT_SORT_MATERIALS are ignored while one is active; RTX_OPT_COMPACT_STATE 0 and 1 both work. */
 #define RTX_TEX_SRGB 1u
 enum { RTX_MAP_KD = 0, RTX_MAP_OPACITY = 2 };      /* 1 is not a slot: it stays RTX_ERR_INVALID, as it always was */
+enum { RTX_MAP_NORMAL = 4 };                       /* ... and neither is 3 */
 int  rtx_set_mesh_uvs(rtx_ctx*, uint32_t mesh, const float* uv2 /* nidx pairs; NULL clears */, uint32_t nidx);
 int  rtx_set_texture(rtx_ctx*, uint32_t tex /* <= current count; == count appends */, const void* rgba8, uint32_t width, uint32_t height, uint32_t flags);
 int  rtx_set_material_map(rtx_ctx*, uint32_t material, uint32_t slot, int32_t tex /* -1 = none */);
@@ -308,6 +346,11 @@ int  rtx_debug_albedo(rtx_ctx*, const float* rays8, const float* hits4, uint32_t
 /* tests: the alpha test of the cut-outs, by the device function the traversal runs — hits4 as rtx_debug_trace_closest writes them -> per record (alpha, opacity texture id
    as uint bits); (1.0f, 0xFFFFFFFF) for a miss, for a triangle that is not a cut-out triangle, and for every hit while no cut-out is active */
 int  rtx_debug_opacity(rtx_ctx*, const float* hits4, uint32_t n, float* out2);
+/* tests: the shading normal of NORMAL MAPS, by the device function k_shade runs — rays8 / hits4 as for rtx_debug_surface -> per record (n'.xyz, normal texture id as uint bits
+   or 0xFFFFFFFF: an emitter, a material without a map, no normal map active — n' is then the surface reconstruction's normal); a miss gives (0, 0, 0, 0xFFFFFFFF).
+   rtx_debug_tri_tangents: records [first, first + count) of the device's copy of the tangent table, 6 floats each; RTX_ERR_STATE while no normal map is active */
+int  rtx_debug_shading_normal(rtx_ctx*, const float* rays8, const float* hits4, uint32_t n, float* out4);
+int  rtx_debug_tri_tangents(rtx_ctx*, uint32_t first, uint32_t count, float* out6);
 /* ENVIRONMENT LIGHTING (new; the reference's Miss.hlsl:3-11 returns black, so a ray that leaves the scene ends dark and only emissive triangles light anything: an extension,
    unpinned by definition like strategy 3 and map_Kd, pinned by its own definition and properties in tests/test_env_ref.py / tests/test_env.py).  rtx_render and
    rtx_render_adaptive only; rtx_render_v6_pass1 and rtx_render_restir ignore the environment, as they ignore maps and RTX_FLAG_TRANSMISSION.  With no environment bound every

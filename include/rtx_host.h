@@ -29,7 +29,16 @@ rtxh_scene* rtxh_scene_from_obj(const char* const* files, uint32_t nfiles, const
 #define RTXH_OBJ_NO_TEXTURES 1u
 #define RTXH_OBJ_NO_CUTOUTS  2u
 #define RTXH_OBJ_KD_ALPHA    4u
+/* ... and for the normal maps (include/rtx.h, NORMAL MAPS): by default the images the `norm` statements name are bound as RTX_MAP_NORMAL.  RTXH_OBJ_NO_NORMAL_MAPS = none
+   (NO_TEXTURES implies it); RTXH_OBJ_BUMP_AS_NORMAL = a material without a norm takes its map_Bump / bump image as a tangent-space normal map; RTXH_OBJ_NORMAL_FLIP_Y = DirectX-style
+   maps, the green byte is negated on load (g' = g == 0 ? 255 : 256 - g) */
+#define RTXH_OBJ_NO_NORMAL_MAPS  8u
+#define RTXH_OBJ_BUMP_AS_NORMAL 16u
+#define RTXH_OBJ_NORMAL_FLIP_Y  32u
 rtxh_scene* rtxh_scene_from_obj_ex(const char* const* files, uint32_t nfiles, const char* mtl_dir, uint32_t flags);
+/* ... with channel 0 of the map_Bump / bump image of a material without a norm taken as a HEIGHT map and converted on load (h = byte / 255, repeat wrap, central differences times
+   bump_height, c = (-gx, -gy, 1) normalised, byte = clamp(floor(c * 127 + 128.5), 0, 255)); RTXH_OBJ_BUMP_AS_NORMAL is ignored here */
+rtxh_scene* rtxh_scene_from_obj_ex2(const char* const* files, uint32_t nfiles, const char* mtl_dir, uint32_t flags, float bump_height);
 /* SURVEY 8(f3) binary scene cache at the host level: the scene (materials, meshes, instances, camera) AND everything rtx_commit_scene
    derives from it (BVH, shading records, LUTs, light CDF); versioned + checksummed (csrc/rtx_scene_cache.cpp).  Saving needs no GPU.
    A loaded scene answers the accessors below like any other and rtxh_scene_upload hands the file's prebuilt arrays to the context
@@ -58,6 +67,9 @@ const char* rtxh_scene_texture(const rtxh_scene*, uint32_t i);                  
 int         rtxh_scene_texture_pixels(const rtxh_scene*, uint32_t i, const void** rgba8, uint32_t* width, uint32_t* height);
 /* the texture the scene binds as the material's opacity map (RTX_MAP_OPACITY: its map_d; alpha byte = the file's alpha channel for a 32-bit TGA, else its first channel), or -1 */
 int         rtxh_scene_opacity_map(const rtxh_scene*, uint32_t material);
+/* the texture the scene binds as the material's normal map (RTX_MAP_NORMAL: its norm image; on request its map_Bump / bump image, as it is or converted from a height map), or -1.
+   A converted or flipped image that another slot reads too is a copy appended behind the files' textures */
+int         rtxh_scene_normal_map(const rtxh_scene*, uint32_t material);
 /* the per-corner texture coordinates of mesh i (the OBJ's vt): one (u, v) pair per index entry, parallel to rtxh_scene_mesh's indices; NULL / 0 for a mesh without any */
 int         rtxh_scene_mesh_uvs(const rtxh_scene*, uint32_t i, const float** uv2, uint32_t* nidx);
 /* the image readers alone: width / height always, the pixels when capacity holds width * height * 4 bytes; RTX_ERR_INVALID + rtxh_last_error for a file they cannot read */

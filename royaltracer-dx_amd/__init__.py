@@ -49,6 +49,7 @@ OPT_DENOISE_LDS_STEP = 42
 TEX_SRGB = 1          # rtx_set_texture flag: the bytes are sRGB-encoded
 MAP_KD = 0            # rtx_set_material_map slot
 MAP_OPACITY = 2       # ... the alpha cut-out slot: reads the texture's alpha byte (1 is not a slot)
+MAP_NORMAL = 4        # ... the tangent-space normal map slot: reads the texture's RGB bytes through Nt (3 is not a slot)
 ENV_HIDDEN = 1        # rtx_set_environment flag: primary rays that miss stay black
 
 
@@ -115,6 +116,8 @@ _sig("rtx_set_material_map", C.c_int, _vp, _u32, _u32, C.c_int32)
 _sig("rtx_debug_texture_sample", C.c_int, _vp, _u32, _vp, _u32, _vp)
 _sig("rtx_debug_albedo", C.c_int, _vp, _vp, _vp, _u32, _vp)
 _sig("rtx_debug_opacity", C.c_int, _vp, _vp, _u32, _vp)
+_sig("rtx_debug_shading_normal", C.c_int, _vp, _vp, _vp, _u32, _vp)
+_sig("rtx_debug_tri_tangents", C.c_int, _vp, _u32, _u32, _vp)
 _sig("rtx_set_environment", C.c_int, _vp, _vp, _u32, _vp, C.c_float, _u32)
 _sig("rtx_debug_env_sample", C.c_int, _vp, _vp, _u32, _vp)
 _sig("rtx_debug_env_eval", C.c_int, _vp, _vp, _u32, _vp)
@@ -209,6 +212,8 @@ _sig("rtxh_scene_bistro_class_hard", _vp, _u32, _u32)
 _sig("rtxh_scene_from_obj", _vp, C.POINTER(C.c_char_p), _u32, C.c_char_p)
 _sig("rtxh_scene_from_obj_ex", _vp, C.POINTER(C.c_char_p), _u32, C.c_char_p, _u32)
 _sig("rtxh_scene_opacity_map", C.c_int, _vp, _u32)
+_sig("rtxh_scene_from_obj_ex2", _vp, C.POINTER(C.c_char_p), _u32, C.c_char_p, _u32, C.c_float)
+_sig("rtxh_scene_normal_map", C.c_int, _vp, _u32)
 _sig("rtxh_scene_free", None, _vp)
 _sig("rtxh_scene_save", C.c_int, _vp, C.c_char_p)
 _sig("rtxh_scene_load", _vp, C.c_char_p)
@@ -319,6 +324,8 @@ class Scene:
         self.material_maps = [self.textures.index(e["maps"]["Kd"]) if "Kd" in e["maps"] else -1 for e in self.material_ext]
         # ... and for the opacity maps (map_d; alpha byte = the file's alpha channel for a 32-bit TGA, else its first channel): per material the texture id or -1
         self.opacity_maps = [int(lib.rtxh_scene_opacity_map(handle, i)) for i in range(n)]
+        # ... and for the normal maps (norm; on request map_Bump / bump, as it is or converted from a height map)
+        self.normal_maps = [int(lib.rtxh_scene_normal_map(handle, i)) for i in range(n)]
         self.meshes, self.uvs = [], []
         for i in range(lib.rtxh_scene_num_meshes(handle)):
             v, idx, mid = _vp(), _vp(), _vp()
@@ -362,11 +369,15 @@ class Scene:
         return cls((lib.rtxh_scene_bistro_class_hard if hard else lib.rtxh_scene_bistro_class)(target_tris, seed))
 
     @classmethod
-    def from_obj(cls, files, mtl_dir, textures=True, cutouts=True, kd_alpha=False):
+    def from_obj(cls, files, mtl_dir, textures=True, cutouts=True, kd_alpha=False, normal_maps=True, bump=None, flip_y=False):
         """textures=False: decode no image; cutouts=False: bind no map_d image as an opacity map; kd_alpha=True: a material without a map_d whose map_Kd file is a
-        32-bit TGA gets that texture as its opacity map too (rtx_render --no-textures / --no-cutouts / --kd-alpha)"""
+        32-bit TGA gets that texture as its opacity map too (rtx_render --no-textures / --no-cutouts / --kd-alpha); normal_maps=False: bind no norm image as a normal
+        map; bump="normal": a material without a norm takes its map_Bump / bump image as a normal map, bump=S (a number): as a height map converted with strength S;
+        flip_y=True: DirectX-style maps, green negated on load (--no-normal-maps / --bump-as-normal / --bump-height S / --normal-flip-y)"""
         arr = (C.c_char_p * len(files))(*[f.encode() for f in files])
-        flags = (0 if textures else 1) | (0 if cutouts else 2) | (4 if kd_alpha else 0)
+        flags = (0 if textures else 1) | (0 if cutouts else 2) | (4 if kd_alpha else 0) | (0 if normal_maps else 8) | (16 if bump == "normal" else 0) | (32 if flip_y else 0)
+        if bump is not None and bump != "normal":
+            return cls(lib.rtxh_scene_from_obj_ex2(arr, len(files), mtl_dir.encode(), flags, float(bump)))
         return cls(lib.rtxh_scene_from_obj_ex(arr, len(files), mtl_dir.encode(), flags))
 
     def set_camera(self, eye, center, up=(0.0, 1.0, 0.0)):
@@ -648,7 +659,7 @@ class Context:
         self._ck(lib.rtx_set_texture(self._h, int(tex), _ptr(a), a.shape[1], a.shape[0], TEX_SRGB if srgb else 0), "rtx_set_texture")
 
     def set_material_map(self, material, tex, slot=MAP_KD):
-        """the material's map in `slot` (MAP_KD, MAP_OPACITY) := texture id `tex`, -1 / None = none"""
+        """the material's map in `slot` (MAP_KD, MAP_OPACITY, MAP_NORMAL) := texture id `tex`, -1 / None = none"""
         self._ck(lib.rtx_set_material_map(self._h, int(material), int(slot), -1 if tex is None else int(tex)), "rtx_set_material_map")
 
     def texture_sample(self, tex, uvs):
@@ -674,10 +685,26 @@ class Context:
         self._ck(lib.rtx_debug_opacity(self._h, _ptr(h), len(h), _ptr(out)), "rtx_debug_opacity")
         return out
 
+    def shading_normal(self, rays8, hits4):
+        """the shading normal under the normal maps at (ray, hit record) pairs (trace_closest), by the device functions k_shade runs -> (n, 4) float32: n', normal
+        texture id bits or 0xFFFFFFFF (an emitter, a material without a map, no normal map active: n' is surface()'s normal); a miss gives (0, 0, 0, 0xFFFFFFFF)"""
+        r = _f32(rays8).reshape(-1, 8); h = _f32(hits4).reshape(-1, 4)
+        out = np.zeros((len(h), 4), np.float32)
+        self._ck(lib.rtx_debug_shading_normal(self._h, _ptr(r), _ptr(h), len(h), _ptr(out)), "rtx_debug_shading_normal")
+        return out
+
+    def tri_tangents(self, first=0, count=None):
+        """the device's tangent table: (count, 6) float32, object-space T and B per global triangle id; RtxError (RTX_ERR_STATE) while no normal map is active"""
+        if count is None:
+            count = self.stats().triangles - first
+        out = np.zeros((count, 6), np.float32)
+        self._ck(lib.rtx_debug_tri_tangents(self._h, int(first), int(count), _ptr(out)), "rtx_debug_tri_tangents")
+        return out
+
     def bind_maps(self, scene):
         """the optional texture attributes of a scene (duck-typed): `uvs` — per mesh an (index count, 2) array or None; `textures` — a list whose entries are (H, W, 4)
         uint8 arrays or (array, srgb) pairs, anything else (a file name without pixels) is skipped; `material_maps` — per material an index into `textures` or -1 / None;
-        `opacity_maps` — likewise for the MAP_OPACITY slot.  A map whose texture was skipped is not bound."""
+        `opacity_maps`, `normal_maps` — likewise for the MAP_OPACITY and MAP_NORMAL slots.  A map whose texture was skipped is not bound."""
         for mesh, uv in enumerate(getattr(scene, "uvs", None) or []):
             if uv is not None and len(uv):
                 self.set_mesh_uvs(mesh, uv)
@@ -694,6 +721,9 @@ class Context:
         for mat, t in enumerate(getattr(scene, "opacity_maps", None) or []):
             if t is not None and t >= 0 and t in ids:
                 self.set_material_map(mat, ids[t], MAP_OPACITY)
+        for mat, t in enumerate(getattr(scene, "normal_maps", None) or []):
+            if t is not None and t >= 0 and t in ids:
+                self.set_material_map(mat, ids[t], MAP_NORMAL)
 
     def set_environment(self, img, to_world=None, scale=1.0, hidden=False):
         """environment lighting: img = (N, N, 3) float32 octahedral map of linear radiance (row = v, column = u; latlong_to_octahedral makes one), or None to clear;

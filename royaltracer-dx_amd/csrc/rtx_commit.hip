@@ -53,21 +53,24 @@ static int upload_built(rtx_ctx* c) {          // every device array of a freshl
 static int finalise_scene(rtx_ctx* c);
 
 // byte -> float of a texel channel (include/rtx.h, rtx_set_texture): [0, 256) linear, [256, 512) sRGB decoded in double and rounded once
+// ... and behind them [512, 768) the decode table of the normal maps: Nt[b] = max(((float)b - 128.0f) / 127.0f, -1.0f); byte 128 is exactly 0, byte 255 exactly 1
 static void fill_tex_lut(std::vector<float>& lut) {
-    lut.resize(512);
+    lut.resize(768);
     for (int b = 0; b < 256; b++) {
+        lut[512 + b] = std::max(((float)b - 128.0f) / 127.0f, -1.0f);
         lut[b] = (float)b / 255.0f;
         const double cs = b / 255.0;
         lut[256 + b] = (float)(cs <= 0.04045 ? cs / 12.92 : pow((cs + 0.055) / 1.055, 2.4));
     }
 }
 // The device's texture tables follow the host's (SceneHost::textures / map_kd / MeshHost::uvs): tables only, no kernel runs.  renumbered: this commit numbered the global
-// triangle ids anew (a build).  What the kernels see of it is set by finalise_scene.
-static int sync_textures(rtx_ctx* c, bool renumbered) {
+// triangle ids anew (a build); deformed: a mesh got new vertices (the tangent records are derived from them).  What the kernels see of it is set by finalise_scene.
+static int sync_textures(rtx_ctx* c, bool renumbered, bool deformed) {
     SceneHost& H = c->host; rtx_ctx::Scene& S = c->scene;
     S.built.maps_active = H.maps_active();
     const bool cut = S.built.cutouts_active = H.cutouts_active();
-    const bool active = S.built.maps_active || cut;          // the UVs serve both
+    const bool nrm = S.built.normals_active = H.normals_active();
+    const bool active = S.built.maps_active || cut || nrm;   // the UVs serve all three
     int r;
     if (H.tex_dirty) {                                       // (a scene that never saw one of the three setters allocates nothing here)
         std::vector<TexDesc> desc(H.textures.size()); std::vector<uint32_t> pool;
@@ -79,6 +82,12 @@ static int sync_textures(rtx_ctx* c, bool renumbered) {
         std::vector<int32_t> maps(H.mats128.size() / 32, -1);
         for (size_t m = 0; m < maps.size() && m < H.map_kd.size(); m++) maps[m] = H.map_kd[m];
         if ((r = upload(c, S.d_tex_desc, desc)) || (r = upload(c, S.d_texels, pool)) || (r = upload(c, S.d_map_kd, maps))) return r;
+        if (!H.any_normal_map()) S.d_map_nrm.release();
+        else {
+            std::vector<int32_t> nmaps(H.mats128.size() / 32, -1);
+            for (size_t m = 0; m < nmaps.size() && m < H.map_normal.size(); m++) nmaps[m] = H.map_normal[m];
+            if ((r = upload(c, S.d_map_nrm, nmaps))) return r;
+        }
         if (!S.d_tex_lut.p) { std::vector<float> lut; fill_tex_lut(lut); if ((r = upload(c, S.d_tex_lut, lut))) return r; }
         S.ntex = (uint32_t)desc.size();
     }
@@ -95,6 +104,13 @@ static int sync_textures(rtx_ctx* c, bool renumbered) {
         S.tri_cut_valid = true;
     }
     if (!cut && S.tri_cut_valid) { S.d_tri_cut.release(); S.tri_cut_valid = false; }
+    // normal maps: the object-space tangent record per GLOBAL triangle id, numbered like tri_uv — from the UVs and the meshes' current vertices, so a transform-only commit keeps it
+    if (nrm && (H.tex_dirty || renumbered || deformed || !S.tri_tan_valid)) {
+        std::vector<float> tt; H.fill_tri_tan(tt);
+        if ((r = upload(c, S.d_tri_tan, tt))) return r;
+        S.tri_tan_valid = true;
+    }
+    if (!nrm && S.tri_tan_valid) { S.d_tri_tan.release(); S.tri_tan_valid = false; }
     H.tex_dirty = false;
     return RTX_OK;
 }
@@ -401,7 +417,7 @@ int rtx_commit_scene(rtx_ctx* c) {
     // On the GPU: a scene that is already resident and not a tiny one (whose pre-test records depend on world positions).
     // a tiny scene leaves its pre-test records for the general path while a texture map is active and returns to them afterwards: the commit that crosses that line rebuilds
     {   size_t ntri_all = 0; for (const InstHost& in : c->host.insts) ntri_all += c->host.meshes[in.mesh].idx.size() / 3;
-        if (c->host.tex_dirty && ntri_all <= kSmallSceneMaxTris && (c->host.maps_active() != c->scene.built.maps_active || c->host.cutouts_active() != c->scene.built.cutouts_active)) c->host.topo_dirty = true;
+        if (c->host.tex_dirty && ntri_all <= kSmallSceneMaxTris && (c->host.maps_active() != c->scene.built.maps_active || c->host.cutouts_active() != c->scene.built.cutouts_active || c->host.normals_active() != c->scene.built.normals_active)) c->host.topo_dirty = true;
         // ... and so it does while an environment is bound
         if (c->host.env_dirty && ntri_all <= kSmallSceneMaxTris && (c->host.env.n != 0) != c->scene.built.env_active) c->host.topo_dirty = true; }
     bool build = !(c->opt.gpu_refit && gpu_refittable(c) && !c->host.topo_dirty);
@@ -428,7 +444,7 @@ int rtx_commit_scene(rtx_ctx* c) {
         if ((r = build_and_upload(c))) return r;
     }
     c->host.dirty_meshes.clear();
-    if ((r = sync_textures(c, build))) return r;
+    if ((r = sync_textures(c, build, deform))) return r;
     if ((r = sync_environment(c))) return r;
     r = finalise_scene(c);
     if (r == RTX_OK && c->scene.dev_built && c->scene.n_nodes8 && probe) {          // the visiting order of any-hit rays, probed on the device (the host probe replays its mirror of the tree)
@@ -448,6 +464,7 @@ int rtx_save_scene_cache(rtx_ctx* c, const char* path) {
     if (c->scene.host_mirror_stale) { c->err = "save_scene_cache: the per-triangle records were re-derived on the GPU after rtx_update_mesh_vertices and the host holds no current copy; commit with RTX_OPT_DEFORM_REBUILD 1 (host builder) to save a cache"; return RTX_ERR_STATE; }
     if (c->scene.built.any_hidden) { c->err = "save_scene_cache: an instance is hidden (rtx_set_instance_visible): the device's boxes and triangle records leave it out and the file format holds no visibility; show every instance and commit to save a cache"; return RTX_ERR_STATE; }
     if (c->host.env.n) { c->err = "save_scene_cache: an environment is bound (rtx_set_environment) and the file format holds no environment; clear it and commit to save a cache"; return RTX_ERR_STATE; }
+    if (c->host.any_normal_map()) { c->err = "save_scene_cache: a material has a normal map (rtx_set_material_map, RTX_MAP_NORMAL) and the file format holds no texels; unmap every material and commit to save a cache"; return RTX_ERR_STATE; }
     if (c->host.any_opacity_map()) { c->err = "save_scene_cache: a material has an opacity map (rtx_set_material_map, RTX_MAP_OPACITY) and the file format holds no texels; unmap every material and commit to save a cache"; return RTX_ERR_STATE; }
     if (c->host.any_map()) { c->err = "save_scene_cache: a material has a texture map (rtx_set_material_map) and the file format holds no texels; unmap every material and commit to save a cache"; return RTX_ERR_STATE; }
     if (c->scene.dev_built) { c->err = "save_scene_cache: the tree was built on the GPU (RTX_OPT_GPU_BUILD) and has no host mirror; commit with the host builder to save a cache"; return RTX_ERR_STATE; }
@@ -463,7 +480,7 @@ int rtx_load_scene_cache(rtx_ctx* c, const char* path) {
     int r = upload_built(c);
     if (r) return r;
     c->host.tex_dirty = true;                  // (another scene: no textures, no maps)
-    if ((r = sync_textures(c, true))) return r;
+    if ((r = sync_textures(c, true, false))) return r;
     c->host.env = EnvHost{}; c->host.env_dirty = true;      // (another scene: no environment)
     if ((r = sync_environment(c))) return r;
     return finalise_scene(c);
@@ -503,9 +520,10 @@ static int finalise_scene(rtx_ctx* c) {
     const bool env_lit = s.env_n && c->scene.env_total > 0.0;
     s.env_tex = env_lit ? (const F4*)c->scene.d_env_tex.p : nullptr; s.env_marg = env_lit ? (const float*)c->scene.d_env_marg.p : nullptr; s.env_cond = env_lit ? (const float*)c->scene.d_env_cond.p : nullptr;
     // (a scene with cut-outs and no diffuse map: k_shade<.., TEX> runs all the same, selected by tri_uv, and reads a map_kd table of -1s — every material keeps its own Kd)
-    const bool uv_active = B.maps_active || B.cutouts_active;
+    const bool uv_active = B.maps_active || B.cutouts_active || B.normals_active;
     s.tri_uv = uv_active ? (const float*)c->scene.d_tri_uv.p : nullptr; s.map_kd = uv_active ? (const int32_t*)c->scene.d_map_kd.p : nullptr;
     s.tri_cut = B.cutouts_active ? (const int32_t*)c->scene.d_tri_cut.p : nullptr;
+    s.tri_tan = B.normals_active ? (const float*)c->scene.d_tri_tan.p : nullptr; s.map_nrm = B.normals_active ? (const int32_t*)c->scene.d_map_nrm.p : nullptr;
     // LDS budget per workgroup: stack + top of tree + first triangles, kept <= 64 KiB
     // exact bound of the 8-wide tree, no slack: a level adds ONE entry (the rest of its hit siblings) and only where a node has >= 2 internal
     // children (collapse_bvh8: need[]); a pop precedes every descent from an exhausted group.  Each entry costs 1.5 KB of LDS per workgroup (6 B per lane: kStackEntryBytes), and

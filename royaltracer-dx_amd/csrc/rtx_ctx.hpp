@@ -126,6 +126,9 @@ struct rtx_ctx {
         // (or a cut-out is: BuiltScene::cutouts_active), rebuilt when UVs or the triangle numbering changed; tri_cut only while a cut-out is active, rebuilt with it
         DevBuf d_tri_uv, d_map_kd, d_tex_desc, d_texels, d_tex_lut; bool tri_uv_valid = false; uint32_t ntex = 0;
         DevBuf d_tri_cut; bool tri_cut_valid = false;
+        // tangent-space normal maps: the per-material map ids with the other tables; tri_tan only while a normal map is active (BuiltScene::normals_active), rebuilt when UVs, the
+        // triangle numbering or a mesh's vertices changed (object space: a transform-only commit leaves it alone)
+        DevBuf d_tri_tan, d_map_nrm; bool tri_tan_valid = false;
         // environment lighting (sync_environment, rtx_commit.hip): the tables of the bound map, rebuilt by the commit after rtx_set_environment; env_total = their weight sum
         DevBuf d_env_tex, d_env_marg, d_env_cond; double env_total = 0.0;
     } scene;

@@ -172,6 +172,37 @@ int rtx_debug_surface(rtx_ctx* c, const float* rays8, const float* hits4, uint32
     memcpy(out16, h.data(), (size_t)n * 64);
     return RTX_OK;
 }
+// the shading normal under the normal maps (rtx_normalmap.hpp), by the device functions k_shade<.., NRM> runs for a lane that shades
+int rtx_debug_shading_normal(rtx_ctx* c, const float* rays8, const float* hits4, uint32_t n, float* out4) {
+    BIND(c);
+    if (!c->committed) { c->err = "scene not committed"; return RTX_ERR_STATE; }
+    if (!n) return RTX_OK;
+    if (!rays8 || !hits4 || !out4) { c->err = "shading_normal: null array"; return RTX_ERR_INVALID; }
+    for (uint32_t i = 0; i < n; i++) {                       // a triangle id the scene does not have would index past the per-triangle tables
+        uint32_t prim; memcpy(&prim, &hits4[(size_t)i * 4 + 3], 4);
+        if (prim != kMissPrim && prim >= c->stats.triangles) { c->err = "shading_normal: triangle id out of range"; return RTX_ERR_INVALID; }
+    }
+    DevBuf d_rays, d_hits, d_out;
+    HIPCHK(c, d_rays.ensure((size_t)n * 32)); HIPCHK(c, d_hits.ensure((size_t)n * 16)); HIPCHK(c, d_out.ensure((size_t)n * 16));
+    TO_DEVICE(c, d_rays.p, rays8, (size_t)n * 32);
+    TO_DEVICE(c, d_hits.p, hits4, (size_t)n * 16);
+    launch_dbg_shading_normal(c->stream, c->dsc, (const F4*)d_rays.p, (const F4*)d_hits.p, n, (F4*)d_out.p);
+    HIPCHK(c, hipGetLastError());
+    TO_HOST(c, out4, d_out.p, (size_t)n * 16);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RTX_OK;
+}
+int rtx_debug_tri_tangents(rtx_ctx* c, uint32_t first, uint32_t count, float* out6) {
+    BIND(c);
+    if (!c->committed) { c->err = "scene not committed"; return RTX_ERR_STATE; }
+    if (!c->dsc.tri_tan) { c->err = "tri_tangents: no normal map is active"; return RTX_ERR_STATE; }
+    if ((uint64_t)first + count > c->stats.triangles) { c->err = "tri_tangents: triangle range out of bounds"; return RTX_ERR_INVALID; }
+    if (!count) return RTX_OK;
+    if (!out6) { c->err = "tri_tangents: null array"; return RTX_ERR_INVALID; }
+    TO_HOST(c, out6, (const char*)c->scene.d_tri_tan.p + (size_t)first * 24, (size_t)count * 24);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RTX_OK;
+}
 static int dbg_bsdf(rtx_ctx* c, bool sample, uint32_t mat, uint32_t flags, const float* in, uint32_t stride_in, uint32_t n, float* out8) {
     BIND(c);
     if (!c->committed) { c->err = "scene not committed"; return RTX_ERR_STATE; }

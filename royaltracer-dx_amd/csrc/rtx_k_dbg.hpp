@@ -2,6 +2,7 @@
 // One of the kernel headers of rtx_kernels.hip, the path tracer's single translation unit (see its header comment for the design and for why).
 #pragma once
 #include "rtx_shade.hpp"
+#include "rtx_normalmap.hpp"
 
 namespace rtx {
 
@@ -97,6 +98,24 @@ __global__ __launch_bounds__(kBlock) void k_dbg_opacity(DevScene sc, const F4* _
         if (tex >= 0) { a = cut_alpha(sc, (uint32_t)tex, prim, h.y, h.z); id = (uint32_t)tex; }
     }
     out2[2 * (size_t)i] = a; out2[2 * (size_t)i + 1] = u2f(id);
+}
+// the shading normal of the normal maps (rtx_normalmap.hpp: nrm_perturb after surface(), as k_shade<.., NRM> runs them for a lane that shades) at n (ray, hit record) pairs ->
+// (n', normal texture id bits); a miss gives (0, 0, 0, 0xFFFFFFFF); an emitter, a material without a map and every hit while no normal map is active give (surface()'s normal, 0xFFFFFFFF)
+__global__ __launch_bounds__(kBlock) void k_dbg_shading_normal(DevScene sc, const F4* __restrict__ rays, const F4* __restrict__ hits, uint32_t n, F4* __restrict__ out) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const F4 h = hits[i];
+    const uint32_t prim = f2u(h.w);
+    F4 r = {0.0f, 0.0f, 0.0f, u2f(0xFFFFFFFFu)};
+    if (prim != kMissPrim) {
+        const F4 ro = rays[2 * i], rd = rays[2 * i + 1];
+        const f3 d = mk3(rd.x, rd.y, rd.z);
+        Surf sf = surface(sc, mk3(ro.x, ro.y, ro.z), d, h.x, h.y, h.z, prim);
+        int32_t tex = -1;
+        if (sc.tri_tan && sf.mat < sc.nmat && !(sc.mats[sf.mat].Ke_len > 0.0f)) sf.normal = nrm_perturb(sc, sf, prim, h.y, h.z, -d, &tex);
+        r = {sf.normal.x, sf.normal.y, sf.normal.z, u2f((uint32_t)tex)};
+    }
+    out[i] = r;
 }
 // the environment's sampler and lookup (rtx_env.hpp), as k_shade<.., ENV> runs them (the marginal CDF from global memory: the same values as its LDS copy)
 __global__ __launch_bounds__(kBlock) void k_dbg_env_sample(DevScene sc, const uint32_t* __restrict__ seeds2, uint32_t n, F4* __restrict__ out) {

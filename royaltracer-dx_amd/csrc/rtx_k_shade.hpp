@@ -3,6 +3,7 @@
 // Uses the PF_* section-profile macros that rtx_kernels.hip defines before it includes this file.
 #pragma once
 #include "rtx_shade.hpp"
+#include "rtx_normalmap.hpp"
 
 namespace rtx {
 
@@ -23,7 +24,9 @@ namespace rtx {
 // continuation — three floats live across them, no per-lane copy of the material.  Lanes whose material has no map keep its KdPi.
 // ENV: an environment with weight is committed (rtx_env.hpp): a lane whose ray missed loads its path state and adds the map's radiance (env_miss), and every shading
 // point casts one more NEE sample, towards the map, into shadow queue `nee` (env_marg: the marginal CDF, in LDS where k_shade found room).  ENV = false is the code as it was.
-template <bool LAMBERT, bool TEX = false, bool ENV = false>
+// NRM (implies TEX): some material has a normal map (rtx_normalmap.hpp): the shading normal of a lane that shades is perturbed once, right after surface(), and everything
+// the lane does afterwards sees n' — three floats replaced, nothing more lives across the item.  NRM = false is the code as it was.
+template <bool LAMBERT, bool TEX = false, bool ENV = false, bool NRM = false>
 __device__ __forceinline__ void shade_item(const DevScene& sc, const DevFrame& f, const DevPaths& p, uint32_t bounce, uint32_t nee, bool last, size_t qb,
                                            const uint32_t* __restrict__ myq, uint32_t* __restrict__ mynext, uint32_t* s_cnt, bool valid, uint32_t qi, Prof* pf, const float* lds_cdf = nullptr, const LightGPU* lds_lights = nullptr, const MatGPU* lds_mats = nullptr, const float* env_marg = nullptr) {
     PathState S = idle_path();
@@ -48,7 +51,7 @@ __device__ __forceinline__ void shade_item(const DevScene& sc, const DevFrame& f
             if (sf.mat < sc.nmat) {
                 const MatGPU& m = mats[sf.mat];
                 if (m.Ke_len > 0.0f) add_emissive(sc, p, S, sf, m, bounce, nee);   // Hit.hlsl:126, Sampler_v6.hlsl:457
-                else { shading = true; if (TEX) kdv = tex_kdpi(sc, m, sf.mat, prim, h.y, h.z); }
+                else { shading = true; if (TEX) kdv = tex_kdpi(sc, m, sf.mat, prim, h.y, h.z); if (NRM) sf.normal = nrm_perturb(sc, sf, prim, h.y, h.z, -S.d); }
             }
         }
         else if (ENV) { PathState M = load_path_stream(p, src); M.pid = pid; env_miss(sc, p, M, bounce); }      // the ray left the scene
@@ -136,11 +139,15 @@ __host__ __device__ inline uint32_t shade_env_lds(uint32_t lights_bytes, uint32_
 #ifndef RTX_SHADE_WAVES_ENV
 #define RTX_SHADE_WAVES_ENV 6      // ... of the ENV instantiations: the environment's sample lives beside the view terms of the mixture, and at 7 waves (72 VGPRs) the GGX forms spill 4 / 8 registers to scratch
 #endif
-template <bool SORT, bool LAMBERT, bool TEX = false, bool ENV = false>     // LAMBERT: RTX_FLAG_LAMBERT_ONLY as a compile-time constant (no GGX / transmission code in that instantiation); TEX: texture maps, ENV: environment lighting (shade_item)
-__global__ __launch_bounds__(kBlock, (ENV ? RTX_SHADE_WAVES_ENV : RTX_SHADE_WAVES)) void k_shade(DevScene sc, DevFrame f_in, DevPaths p, uint32_t bounce,
+#ifndef RTX_SHADE_WAVES_NRM
+#define RTX_SHADE_WAVES_NRM 6      // ... of the NRM instantiations, with or without ENV (profiles/normalmap_kernel_resources.md)
+#endif
+template <bool SORT, bool LAMBERT, bool TEX = false, bool ENV = false, bool NRM = false>     // LAMBERT: RTX_FLAG_LAMBERT_ONLY as a compile-time constant (no GGX / transmission code in that instantiation); TEX: texture maps, ENV: environment lighting, NRM: normal maps (shade_item)
+__global__ __launch_bounds__(kBlock, (NRM ? RTX_SHADE_WAVES_NRM : ENV ? RTX_SHADE_WAVES_ENV : RTX_SHADE_WAVES)) void k_shade(DevScene sc, DevFrame f_in, DevPaths p, uint32_t bounce,
                                                   const uint32_t* __restrict__ queue, const uint32_t* __restrict__ qcount,
                                                   uint32_t* __restrict__ next_queue, uint32_t* __restrict__ next_count,
                                                   uint32_t* __restrict__ shcounts /* [nee][gridDim.x] */) {
+    static_assert(!NRM || (TEX && !SORT), "the normal-mapped forms are TEX forms of the default kernel");
     const DevFrame f = frame_with_lambert<LAMBERT>(f_in);
     constexpr uint32_t kSlots = kMaxNee + (ENV ? 1u : 0u);  // (the environment's slot follows the nee_samples <= kMaxNee triangle-light slots)
     __shared__ uint32_t s_cnt[1 + kMaxNee + (ENV ? 4u : 0u)];     // [0] next-queue length, [1 + j] shadow queue j length (ENV: one slot more, in a 16-byte step: the static LDS precedes the dynamic region, whose float4 reads need their alignment)
@@ -210,7 +217,7 @@ __global__ __launch_bounds__(kBlock, (ENV ? RTX_SHADE_WAVES_ENV : RTX_SHADE_WAVE
         }
         for (uint32_t base = threadIdx.x & ~63u; base < cn; base += kBlock) {
             const uint32_t i = base + (threadIdx.x & 63u);
-            shade_item<LAMBERT, TEX, ENV>(sc, f, p, bounce, nee, last, qb, myq, mynext, s_cnt, i < cn, cb + (SORT ? s_sorted[i] : i), pf, lds_cdf, lds_lights, lds_mats, env_marg);
+            shade_item<LAMBERT, TEX, ENV, NRM>(sc, f, p, bounce, nee, last, qb, myq, mynext, s_cnt, i < cn, cb + (SORT ? s_sorted[i] : i), pf, lds_cdf, lds_lights, lds_mats, env_marg);
         }
         if (SORT) __syncthreads();                              // the next chunk overwrites the LDS buffers
     }

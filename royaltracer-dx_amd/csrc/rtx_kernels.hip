@@ -193,12 +193,21 @@ void launch_shade(hipStream_t st, const DevScene& sc, const DevFrame& f, const D
         // an environment is bound: the default kernel too, in its ENV form when the map has weight (a black map adds nothing and casts nothing: the kernels without it)
         if (sc.env_n) {
             uint32_t lb, mb; shade_lds_plan(sc.nlights, sc.nmat, false, lb, mb);
+            // a normal map is active: the NRM form of the TEX kernel (tri_uv is set whenever tri_tan is), with or without the environment's sample
+            if (sc.tri_tan) {
+                dispatch_bool(sc.env_tex != nullptr, [&](auto env) {
+                    constexpr bool EE = decltype(env)::value;
+                    hipLaunchKernelGGL((k_shade<false, LL, true, EE, true>), dim3(f.nblocks), dim3(kBlock), (size_t)lb + mb + (EE ? shade_env_lds(lb, mb, sc.env_n) : 0u), st, sc, f, p, bounce, queue, qcount, next_queue, next_count, shcounts);
+                });
+                return;
+            }
             dispatch_bool(sc.tri_uv != nullptr, [&](auto tex) { dispatch_bool(sc.env_tex != nullptr, [&](auto env) {
                 constexpr bool EE = decltype(env)::value;
                 hipLaunchKernelGGL((k_shade<false, LL, decltype(tex)::value, EE>), dim3(f.nblocks), dim3(kBlock), (size_t)lb + mb + (EE ? shade_env_lds(lb, mb, sc.env_n) : 0u), st, sc, f, p, bounce, queue, qcount, next_queue, next_count, shcounts);
             }); });
             return;
         }
+        if (sc.tri_tan) { hipLaunchKernelGGL((k_shade<false, LL, true, false, true>), dim3(f.nblocks), dim3(kBlock), shade_lds_bytes(sc, false), st, sc, f, p, bounce, queue, qcount, next_queue, next_count, shcounts); return; }
         if (sc.tri_uv) { hipLaunchKernelGGL((k_shade<false, LL, true>), dim3(f.nblocks), dim3(kBlock), shade_lds_bytes(sc, false), st, sc, f, p, bounce, queue, qcount, next_queue, next_count, shcounts); return; }
         if (sc.shade_dense && !sc.sort_materials) hipLaunchKernelGGL((k_shade_dense<LL>), dim3(f.nblocks), dim3(kBlock), 0, st, sc, f, p, bounce, queue, qcount, next_queue, next_count, shcounts);
         else dispatch_bool(sc.sort_materials != 0u, [&](auto sort) {
@@ -348,6 +357,9 @@ void launch_dbg_albedo(hipStream_t st, const DevScene& sc, const F4* hits, uint3
 }
 void launch_dbg_opacity(hipStream_t st, const DevScene& sc, const F4* hits, uint32_t n, float* out2) {
     hipLaunchKernelGGL(k_dbg_opacity, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, sc, hits, n, out2);
+}
+void launch_dbg_shading_normal(hipStream_t st, const DevScene& sc, const F4* rays, const F4* hits, uint32_t n, F4* out) {
+    hipLaunchKernelGGL(k_dbg_shading_normal, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, sc, rays, hits, n, out);
 }
 void launch_dbg_env_sample(hipStream_t st, const DevScene& sc, const uint32_t* seeds2, uint32_t n, F4* out) {
     hipLaunchKernelGGL(k_dbg_env_sample, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, sc, seeds2, n, out);

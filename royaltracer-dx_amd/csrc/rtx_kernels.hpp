@@ -49,6 +49,10 @@ struct DevScene {
     // alpha cut-outs (rtx_cutout.hpp; the LAST member: every other one keeps its place in the kernel arguments).  nullptr unless some triangle is a cut-out triangle: such scenes launch what they always launched; otherwise tri_uv and map_kd are set too
     // (map_kd all -1 where no material has a diffuse map) and the traversal kernels' CUT instantiations run
     const int32_t* tri_cut;             // per GLOBAL triangle id (indexed like tri_uv): the opacity texture of a cut-out triangle, or -1
+    // tangent-space normal maps (rtx_normalmap.hpp; after tri_cut: every other member keeps its place in the kernel arguments).  Both nullptr unless a non-emitting material that
+    // some triangle uses has RTX_MAP_NORMAL: such scenes launch what they always launched; otherwise tri_uv and map_kd are set too and k_shade<.., NRM> runs
+    const float* tri_tan;               // 6 floats per GLOBAL triangle id (indexed like tri_uv): the object-space tangent T = dP/du and bitangent B = dP/dv, zeros where the UVs give none
+    const int32_t* map_nrm;             // per material: texture id of RTX_MAP_NORMAL, or -1
 };
 
 // one sample batch of one frame
@@ -257,6 +261,7 @@ void launch_dbg_albedo(hipStream_t, const DevScene&, const F4* hits, uint32_t n,
 // the environment's device functions (rtx_env.hpp): env_sample at n seeds -> 3 F4 per seed (world direction, pdf | L, texel bits | seed after the four draws, 0, 0);
 // env_eval at n directions -> 2 F4 per direction (L, pdf | texel bits, r3, 0, 0).  sc.env_* must be set (the probes set them for a black map too)
 void launch_dbg_opacity(hipStream_t, const DevScene&, const F4* hits, uint32_t n, float* out2);                    // cut_alpha at n hit records -> (alpha, opacity texture id bits or 0xFFFFFFFF)
+void launch_dbg_shading_normal(hipStream_t, const DevScene&, const F4* rays, const F4* hits, uint32_t n, F4* out);   // surface() + nrm_perturb at n (ray, hit record) pairs -> (n', normal texture id bits or 0xFFFFFFFF)
 void launch_dbg_env_sample(hipStream_t, const DevScene&, const uint32_t* seeds2, uint32_t n, F4* out);
 void launch_dbg_env_eval(hipStream_t, const DevScene&, const float* dirs3, uint32_t n, F4* out);
 void launch_dbg_tea(hipStream_t, uint32_t s0, uint32_t s1, uint32_t n, float* out, uint32_t* seed_out);

@@ -1,6 +1,7 @@
 // rtx_scene_host.cpp — host-side scene assembly: material packing, the light list with its CDF, world-space flattening and shade records, and SceneHost::build, which
 // lists the steps of a commit (tree: rtx_bvh_build.cpp / rtx_bvh_wide.cpp, tiny-scene records: rtx_small_scene.cpp, any-hit probe: rtx_bvh_replay.cpp).  No HIP calls in this file.
 #include "rtx_scene_host.hpp"
+#include "rtx_normalmap_host.hpp"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -71,7 +72,7 @@ bool SceneHost::set_materials(const void* mats, uint32_t count) {
     mats128.assign((const float*)mats, (const float*)mats + (size_t)count * 32);
     mats_dirty = true;
     if (any_map()) tex_dirty = true;
-    map_kd.clear(); map_opacity.clear();        // the table is replaced: no material of the new one has a map
+    map_kd.clear(); map_opacity.clear(); map_normal.clear();        // the table is replaced: no material of the new one has a map
     return true;
 }
 
@@ -162,9 +163,9 @@ bool SceneHost::set_texture(uint32_t tex, const void* rgba8, uint32_t width, uin
 }
 bool SceneHost::set_material_map(uint32_t material, uint32_t slot, int32_t tex) {
     if (material >= mats128.size() / 32) { err = "set_material_map: unknown material"; return false; }
-    if (slot != 0u && slot != 2u) { err = "set_material_map: unknown slot (RTX_MAP_KD = 0 or RTX_MAP_OPACITY = 2)"; return false; }
+    if (slot != 0u && slot != 2u && slot != 4u) { err = "set_material_map: unknown slot (RTX_MAP_KD = 0, RTX_MAP_OPACITY = 2 or RTX_MAP_NORMAL = 4)"; return false; }
     if (tex < -1 || (tex >= 0 && (size_t)tex >= textures.size())) { err = "set_material_map: unknown texture"; return false; }
-    std::vector<int32_t>& map = slot == 2u ? map_opacity : map_kd;
+    std::vector<int32_t>& map = slot == 4u ? map_normal : slot == 2u ? map_opacity : map_kd;
     if (map.size() < mats128.size() / 32) map.resize(mats128.size() / 32, -1);
     map[material] = tex;
     tex_dirty = true;
@@ -186,6 +187,24 @@ void SceneHost::fill_tri_cut(std::vector<int32_t>& out) const {
     for (const InstHost& in : insts) {
         const MeshHost& m = meshes[in.mesh];
         for (size_t t = 0; t < m.idx.size() / 3; t++) out[(size_t)in.tri_base + t] = cut_texture(matids[m.matid_base + 3 * t]);
+    }
+}
+bool SceneHost::normals_active() const {
+    if (!any_normal_map()) return false;
+    for (size_t i = 0; i < matids.size(); i += 3) { const uint32_t mat = matids[i]; if (mat < map_normal.size() && map_normal[mat] >= 0 && mat < mats128.size() / 32 && !material_emits(mat)) return true; }
+    return false;
+}
+void SceneHost::fill_tri_tan(std::vector<float>& out) const {
+    size_t nt = 0; for (const InstHost& in : insts) nt += meshes[in.mesh].idx.size() / 3;
+    out.assign(nt * 6, 0.0f);
+    const float zero_uv[6] = {0, 0, 0, 0, 0, 0};
+    for (const InstHost& in : insts) {
+        const MeshHost& m = meshes[in.mesh];
+        for (size_t t = 0; t < m.idx.size() / 3; t++) {
+            float p[9];
+            for (int k = 0; k < 3; k++) memcpy(p + 3 * k, &m.verts[(size_t)m.idx[t * 3 + k] * 7], 12);
+            tangent_record(p, m.uvs.empty() ? zero_uv : &m.uvs[t * 6], &out[((size_t)in.tri_base + t) * 6]);
+        }
     }
 }
 bool SceneHost::only_maps_changed(const BuiltScene& b) const {
@@ -458,8 +477,9 @@ bool SceneHost::build(BuiltScene& B) {
     // ... and so does one with an active texture map (k_bounce_small and k_primary_surface sample no image)
     // ... and one with an environment bound (k_bounce_small's misses end black)
     // ... and one with a cut-out triangle (the pre-test path runs no alpha test)
-    B.maps_active = maps_active(); B.cutouts_active = cutouts_active(); B.env_active = env.n != 0;
-    if (B.any_hidden || B.maps_active || B.cutouts_active || B.env_active) { B.small_recs.clear(); B.small_tris.clear(); B.small_poly.clear(); B.small_nrec = 0; B.small_nocc = 0; }
+    // ... and one with an active normal map (k_bounce_small perturbs no normal)
+    B.maps_active = maps_active(); B.cutouts_active = cutouts_active(); B.normals_active = normals_active(); B.env_active = env.n != 0;
+    if (B.any_hidden || B.maps_active || B.cutouts_active || B.normals_active || B.env_active) { B.small_recs.clear(); B.small_tris.clear(); B.small_poly.clear(); B.small_nrec = 0; B.small_nocc = 0; }
     else build_small_scene(B, wtri, scale);
     sw.lap("tris8 / small scene");
     B.any_order = probe_anyhit_order(B);

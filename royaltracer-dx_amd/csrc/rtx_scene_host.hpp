@@ -50,6 +50,7 @@ struct BuiltScene {
     bool any_hidden = false;            // ... and whether any word of it is set
     bool maps_active = false;           // SceneHost::maps_active() AS COMMITTED: a tiny scene then runs on the general path, DevScene::tri_uv / map_kd are set
     bool cutouts_active = false;        // SceneHost::cutouts_active() AS COMMITTED: a tiny scene then runs on the general path, DevScene::tri_cut (and tri_uv / map_kd) are set
+    bool normals_active = false;        // SceneHost::normals_active() AS COMMITTED: a tiny scene then runs on the general path, DevScene::tri_tan / map_nrm (and tri_uv / map_kd) are set
     bool env_active = false;            // an environment is bound (SceneHost::env.n != 0) AS COMMITTED: a tiny scene then runs on the general path
     std::vector<uint32_t> inst_moved;   // refresh_transforms: 1 = the instance's objectToWorld differs from the last commit's, or its mesh's vertices do, or its visibility does (the GPU refit touches the triangles and nodes of these only)
 };
@@ -68,6 +69,7 @@ struct SceneHost {
     std::vector<TexHost> textures;
     std::vector<int32_t> map_kd;                // per material: texture id of RTX_MAP_KD or -1; shorter than the table = the rest has none (rtx_set_materials empties it)
     std::vector<int32_t> map_opacity;           // ... of RTX_MAP_OPACITY (alpha cut-outs), likewise
+    std::vector<int32_t> map_normal;            // ... of RTX_MAP_NORMAL (tangent-space normal maps), likewise
     bool tex_dirty = false;                     // one of the three setters since the last commit
     // environment lighting (include/rtx.h: rtx_set_environment; rtx_env_host.hpp)
     EnvHost env;
@@ -93,13 +95,16 @@ struct SceneHost {
     bool set_texture(uint32_t tex, const void* rgba8, uint32_t width, uint32_t height, uint32_t flags);
     bool set_material_map(uint32_t material, uint32_t slot, int32_t tex);
     bool any_opacity_map() const { for (int32_t t : map_opacity) if (t >= 0) return true; return false; }
-    bool any_map() const { for (int32_t t : map_kd) if (t >= 0) return true; return any_opacity_map(); }
+    bool any_normal_map() const { for (int32_t t : map_normal) if (t >= 0) return true; return false; }
+    bool any_map() const { for (int32_t t : map_kd) if (t >= 0) return true; return any_opacity_map() || any_normal_map(); }
     bool maps_active() const;                   // a material that some triangle uses has a diffuse map
     bool material_emits(uint32_t mat) const { const float* m = &mats128[(size_t)mat * 32]; return m[8] > 0.0f || m[9] > 0.0f || m[10] > 0.0f; }      // a component of Ke is > 0
     // the opacity texture of a triangle whose material (the id of its first index entry) is `mat`, or -1: the material has RTX_MAP_OPACITY and does not emit (a CUT-OUT TRIANGLE)
     int32_t cut_texture(uint32_t mat) const { return mat < map_opacity.size() && map_opacity[mat] >= 0 && mat < mats128.size() / 32 && !material_emits(mat) ? map_opacity[mat] : -1; }
     bool cutouts_active() const;                // some triangle is a cut-out triangle
     void fill_tri_cut(std::vector<int32_t>& out) const;     // cut_texture per global triangle id (numbered like fill_tri_uv)
+    bool normals_active() const;                // a non-emitting material that some triangle uses has a normal map
+    void fill_tri_tan(std::vector<float>& out) const;       // the tangent record (rtx_normalmap_host.hpp) per global triangle id (numbered like fill_tri_uv), from the meshes' current object-space vertices
     bool only_maps_changed(const BuiltScene& b) const;      // against the committed scene b: no instance moved, was hidden or shown, no mesh got new vertices, same topology and material table
     void fill_tri_uv(std::vector<float>& out) const;        // 6 floats per global triangle id (InstHost::tri_base as the last geometry-changing commit numbered them)
     bool build(BuiltScene& out);                // the host's whole commit: materials, flattening + shade records, lights, the tree (built, or refitted after a transform-only change), its wide form, tiny-scene records, any-hit probe

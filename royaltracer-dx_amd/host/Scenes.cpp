@@ -1,6 +1,7 @@
 // Scenes.cpp — deterministic synthetic scenes in the reference's data model (see Scenes.h).
 #include "Scenes.h"
 #include "ImageIO.h"
+#include "../csrc/rtx_normalmap_host.hpp"
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -542,7 +543,7 @@ Scene MakeBistroClass(uint32_t target, uint32_t seed, bool hard) {
 }
 
 // the reference's startup scene (Renderer.cpp:363-407, 444-449, 46-48)
-Scene LoadObjScene(const std::vector<std::string>& files, const std::string& mtl_dir, bool load_textures, SceneCutouts cutouts) {
+Scene LoadObjScene(const std::vector<std::string>& files, const std::string& mtl_dir, bool load_textures, SceneCutouts cutouts, SceneNormals normals) {
     Scene s; s.name = "obj";
     UINT materialIDOffset = 0, materialVertexOffset = 0;       // Renderer members of the same name
     size_t total_ids = 0;
@@ -559,7 +560,7 @@ Scene LoadObjScene(const std::vector<std::string>& files, const std::string& mtl
     s.eye = XMFLOAT3(-1.5f, 1.5f, 3.5f); s.center = XMFLOAT3(0, 1, 0); s.up = XMFLOAT3(0, 1, 0);   // Renderer.cpp:46-48
     s.images.resize(s.textures.size());
     std::vector<char> tried(s.textures.size(), 0);
-    auto load = [&](int t, const char* what) {                 // the diffuse and the opacity maps only: no kernel samples another slot
+    auto load = [&](int t, const char* what) {                 // the diffuse, the opacity and the normal maps only: no kernel samples another slot
         if (!load_textures || t < 0 || (size_t)t >= s.textures.size() || tried[t]) return;
         tried[t] = 1;
         std::string dir = mtl_dir; if (!dir.empty() && dir.back() != '/') dir += '/';
@@ -581,6 +582,34 @@ Scene LoadObjScene(const std::vector<std::string>& files, const std::string& mtl
             s.opacityMaps[m] = t; opacity[t] = 1;
         }
         for (size_t t = 0; t < s.images.size(); t++) if (opacity[t]) OpacityAlphaFromChannels(s.images[t].rgba, s.images[t].channels);
+    }
+    if (load_textures && normals.mode != kNormalsOff) {
+        s.normalMaps.assign(s.materialExt.size(), -1);
+        const size_t nfile = s.textures.size();                // (copies are appended behind the files' entries, which keep their ids)
+        std::vector<char> other(nfile, 0);                     // images another slot reads
+        for (size_t m = 0; m < s.materialExt.size(); m++) {
+            const int kd = s.materialExt[m].map[MAP_KD]; if (kd >= 0 && (size_t)kd < nfile) other[kd] = 1;
+            const int op = m < s.opacityMaps.size() ? s.opacityMaps[m] : -1; if (op >= 0 && (size_t)op < nfile) other[op] = 1;
+        }
+        std::vector<int> as_normal(nfile, -1), as_height(nfile, -1);      // file image -> the entry that holds it as a normal map / converted from a height map
+        for (size_t m = 0; m < s.materialExt.size(); m++) {
+            const MaterialExt& x = s.materialExt[m];
+            int t = x.map[MAP_NORM]; bool height = false;
+            if (t >= 0) load(t, "norm");
+            else if (normals.mode == kNormalsBumpAsNormal || normals.mode == kNormalsBumpHeight) { t = x.map[MAP_BUMP]; height = normals.mode == kNormalsBumpHeight; if (t >= 0) load(t, "map_Bump"); }
+            if (t < 0 || (size_t)t >= nfile || !s.images[t].width) continue;
+            if (height) other[t] = other[t] || as_normal[t] >= 0; else other[t] = other[t] || as_height[t] >= 0;      // (one file as both: the second use is a copy)
+            int& slot = height ? as_height[t] : as_normal[t];
+            if (slot < 0) {
+                const bool change = height || normals.flipY;
+                if (change && other[t]) { s.textures.push_back(s.textures[t] + (height ? "#height" : "#normal")); s.images.push_back(s.images[t]); slot = (int)s.images.size() - 1; }
+                else slot = t;
+                SceneImage& im = s.images[slot];
+                if (height) { std::vector<uint8_t> nm; rtx::HeightToNormalMap(im.rgba.data(), im.width, im.height, (double)normals.strength, nm); im.rgba = std::move(nm); }
+                if (normals.flipY) rtx::FlipGreen(im.rgba.data(), (size_t)im.width * im.height);
+            }
+            s.normalMaps[m] = slot;
+        }
     }
     return s;
 }
@@ -630,6 +659,10 @@ int BindSceneMaps(const Scene& s, rtx_ctx* ctx) {
     for (size_t m = 0; m < s.opacityMaps.size() && m < s.materials.size(); m++) {
         const int t = s.opacityMaps[m];
         if (t >= 0 && (size_t)t < id.size() && id[t] >= 0 && (r = rtx_set_material_map(ctx, (uint32_t)m, RTX_MAP_OPACITY, id[t]))) return r;
+    }
+    for (size_t m = 0; m < s.normalMaps.size() && m < s.materials.size(); m++) {
+        const int t = s.normalMaps[m];
+        if (t >= 0 && (size_t)t < id.size() && id[t] >= 0 && (r = rtx_set_material_map(ctx, (uint32_t)m, RTX_MAP_NORMAL, id[t]))) return r;
     }
     return RTX_OK;
 }

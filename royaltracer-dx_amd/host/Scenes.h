@@ -28,6 +28,8 @@ struct Scene {
                                              // is missing or in another format, stays empty.  BindSceneMaps hands the loaded ones to a context, sRGB-encoded
     std::vector<int> opacityMaps;            // per material: the entry of `textures` bound as its opacity map (RTX_MAP_OPACITY: its map_d, or with kCutoutsKdAlpha its 32-bit map_Kd), or
                                              // -1; empty = none.  The alpha byte of such an image is the file's own alpha channel (32-bit TGA) or its first channel (PGM / PPM / 24-bit TGA)
+    std::vector<int> normalMaps;             // per material: the entry of `textures` bound as its normal map (RTX_MAP_NORMAL: its norm image, or on request its map_Bump / bump image,
+                                             // taken as a normal map or converted from a height map on load), or -1; empty = none
     std::vector<SceneModel> models;
     std::vector<SceneInstance> instances;
     XMFLOAT3 eye{0, 0, 1}, center{0, 0, 0}, up{0, 1, 0};
@@ -49,8 +51,14 @@ Scene MakeBistroClass(uint32_t target_tris = 3800000, uint32_t seed = 3800, bool
 // a map_d that names its material's map_Kd file is ONE texture in both slots; kCutoutsKdAlpha = additionally a material WITHOUT a map_d whose map_Kd file has an alpha channel of its
 // own (32-bit TGA) gets that texture as its opacity map (opt-in: no existing scene changes)
 enum SceneCutouts { kCutoutsOff = 0, kCutoutsMapD = 1, kCutoutsKdAlpha = 2 };
-Scene LoadObjScene(const std::vector<std::string>& files, const std::string& mtl_dir, bool load_textures = true, SceneCutouts cutouts = kCutoutsMapD);
-// rtx_set_mesh_uvs / rtx_set_texture / rtx_set_material_map (both slots) for what the scene carries; a scene without a decoded image binds nothing.  Before rtx_commit_scene
+// normals (ignored without load_textures): which images become tangent-space normal maps (include/rtx.h, NORMAL MAPS).  kNormalsOff = none (the scene as it was before normal maps
+// existed); kNormalsNorm = the images the `norm` statements name; kNormalsBumpAsNormal / kNormalsBumpHeight = additionally, for a material WITHOUT a norm, its map_Bump / bump image —
+// taken as a normal map, or its channel 0 as a height map converted on load with HeightToNormalMap(strength) (csrc/rtx_normalmap_host.hpp).  flipY: DirectX-style maps (green =
+// -bitangent): every normal map's green byte is negated on load (FlipGreen).  An image that another slot reads too is left as it is: the normal map is a copy appended to `textures`
+enum SceneNormalMode { kNormalsOff = 0, kNormalsNorm = 1, kNormalsBumpAsNormal = 2, kNormalsBumpHeight = 3 };
+struct SceneNormals { SceneNormalMode mode = kNormalsNorm; float strength = 1.0f; bool flipY = false; };
+Scene LoadObjScene(const std::vector<std::string>& files, const std::string& mtl_dir, bool load_textures = true, SceneCutouts cutouts = kCutoutsMapD, SceneNormals normals = SceneNormals());
+// rtx_set_mesh_uvs / rtx_set_texture / rtx_set_material_map (all three slots) for what the scene carries; a scene without a decoded image binds nothing.  Before rtx_commit_scene
 int BindSceneMaps(const Scene&, rtx_ctx*);
 // rtx_set_environment for what the scene carries (n = 0: clears the context's).  Before rtx_commit_scene
 int BindSceneEnvironment(const SceneEnvironment&, rtx_ctx*);

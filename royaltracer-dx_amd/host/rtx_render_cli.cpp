@@ -21,6 +21,9 @@
 //                   [--no-textures]   OBJ scenes: do not read the images their map_Kd statements name (binary PPM / PGM, 24- / 32-bit TGA): the image without diffuse maps
 //                   [--no-cutouts]    OBJ scenes: do not bind the images their map_d statements name as opacity maps (alpha cut-outs): the image with every card opaque
 //                   [--kd-alpha]      OBJ scenes: a material without a map_d whose map_Kd is a 32-bit TGA gets that texture's alpha as its opacity map too
+//                   [--no-normal-maps] OBJ scenes: do not bind the images their norm statements name as tangent-space normal maps: the image with flat-shaded walls
+//                   [--bump-as-normal] a material without a norm takes its map_Bump / bump image as a normal map   [--bump-height S] ... as a height map (channel 0), converted on load with strength S
+//                   [--normal-flip-y] DirectX-style normal maps (green = -bitangent): negate the green byte on load
 //                   [--env FILE [--env-res N] [--env-yaw DEG] [--env-scale S] [--env-hidden]]   environment lighting (rtx_set_environment): FILE is a latitude-longitude Radiance .hdr or
 //                   colour .pfm, resampled to an N x N octahedral map (default 512), turned by DEG degrees about +Y, radiance times S; --env-hidden: camera rays that miss stay black
 //                   [--sky R,G,B]   a constant sky of that radiance instead of a file; both work with --gpus N (every rank binds the same map) and are ignored by --mode restir
@@ -51,6 +54,8 @@ static const char* kUsage =
     "                  [--denoise [--denoise-levels N] [--sigma-color X] [--sigma-plane X]]   write the denoised image to --out (path tracer only)\n"
     "                  [--no-textures]   OBJ scenes: ignore map_Kd images (implies --no-cutouts)\n"
     "                  [--no-cutouts]    OBJ scenes: ignore map_d images (no alpha cut-outs)   [--kd-alpha]   a 32-bit map_Kd without a map_d is its material's opacity map too\n"
+    "                  [--no-normal-maps] OBJ scenes: ignore norm images (--no-textures implies it)   [--bump-as-normal | --bump-height S]   map_Bump / bump as a normal map / a height map of strength S\n"
+    "                  [--normal-flip-y]  DirectX-style normal maps: negate green on load\n"
     "                  [--env FILE [--env-res N] [--env-yaw DEG] [--env-scale S] [--env-hidden]] [--sky R,G,B]   environment lighting\n"
     "                  [--aperture R [--focus D | --focus-pixel X,Y]]   thin-lens camera: depth of field (path tracer)\n"
     "                  [--gpus N [--devices 0,1,..] [--gather rccl|copy]]\n";
@@ -62,7 +67,7 @@ int main(int argc, char** argv) {
     std::vector<UINT> hide; int blink = -1;
     bool adaptive = false; rtx_adaptive ad{}; ad.min_spp = 8; ad.step_spp = 8;
     bool denoise = false; rtx_denoise_params dnp{};
-    bool textures = true; SceneCutouts cutouts = kCutoutsMapD; bool kd_alpha = false;
+    bool textures = true; SceneCutouts cutouts = kCutoutsMapD; bool kd_alpha = false; SceneNormals normals; bool no_normals = false;
     float aperture = 0.0f, focus = 0.0f; bool focus_set = false; std::string focus_pixel;
     std::string env_file, sky; UINT env_res = 512; float env_yaw = 0.0f, env_scale = 1.0f; bool env_hidden = false;
     for (int i = 1; i < argc; i++) {
@@ -75,6 +80,8 @@ int main(int argc, char** argv) {
         else if (arg("--adaptive")) { adaptive = true; ad.threshold = (float)atof(argv[++i]); } else if (arg("--min-spp")) ad.min_spp = (uint32_t)atoi(argv[++i]); else if (arg("--step-spp")) ad.step_spp = (uint32_t)atoi(argv[++i]);
         else if (!strcmp(argv[i], "--help") || !strcmp(argv[i], "-h")) { fputs(kUsage, stdout); return 0; }
         else if (!strcmp(argv[i], "--no-textures")) textures = false; else if (!strcmp(argv[i], "--no-cutouts")) cutouts = kCutoutsOff; else if (!strcmp(argv[i], "--kd-alpha")) kd_alpha = true;
+        else if (!strcmp(argv[i], "--no-normal-maps")) no_normals = true; else if (!strcmp(argv[i], "--normal-flip-y")) normals.flipY = true;
+        else if (!strcmp(argv[i], "--bump-as-normal")) normals.mode = kNormalsBumpAsNormal; else if (arg("--bump-height")) { normals.strength = (float)atof(argv[++i]); normals.mode = kNormalsBumpHeight; }
         else if (arg("--env")) env_file = argv[++i]; else if (arg("--env-res")) env_res = (UINT)atoi(argv[++i]); else if (arg("--env-yaw")) env_yaw = (float)atof(argv[++i]);
         else if (arg("--env-scale")) env_scale = (float)atof(argv[++i]); else if (!strcmp(argv[i], "--env-hidden")) env_hidden = true; else if (arg("--sky")) sky = argv[++i];
         else if (!strcmp(argv[i], "--denoise")) denoise = true; else if (arg("--denoise-levels")) dnp.levels = (uint32_t)atoi(argv[++i]); else if (arg("--sigma-color")) dnp.sigma_color = (float)atof(argv[++i]); else if (arg("--sigma-plane")) dnp.sigma_plane = (float)atof(argv[++i]);
@@ -84,6 +91,7 @@ int main(int argc, char** argv) {
         else { fprintf(stderr, "unknown argument %s\n", argv[i]); return 2; }
     }
     if (kd_alpha && cutouts != kCutoutsOff) cutouts = kCutoutsKdAlpha;
+    if (no_normals) normals.mode = kNormalsOff;
     if (mode != "pt" && mode != "restir") { fprintf(stderr, "--mode must be pt or restir\n"); return 2; }
     const bool restir = mode == "restir";
     if (restir) { if (!nee_set) nee = 4; if (!bounces_set) bounces = 3; }
@@ -131,7 +139,7 @@ int main(int argc, char** argv) {
             else { std::stringstream ss(devlist); std::string t; while (std::getline(ss, t, ',')) devs.push_back(atoi(t.c_str())); }
             if ((int)devs.size() != gpus) { fprintf(stderr, "--devices must list %d ordinals\n", gpus); return 2; }
             Scene sc = scene == "cornell" ? MakeCornellBox() : scene == "sponza" ? MakeSponzaClass() : scene == "bistro" ? MakeBistroClass() : Scene();
-            if (scene == "obj") { std::vector<std::string> f; std::stringstream ss(objs); std::string t; while (std::getline(ss, t, ',')) f.push_back(t); sc = LoadObjScene(f, mtl, textures, cutouts); }
+            if (scene == "obj") { std::vector<std::string> f; std::stringstream ss(objs); std::string t; while (std::getline(ss, t, ',')) f.push_back(t); sc = LoadObjScene(f, mtl, textures, cutouts, normals); }
             if (scene == "cornell") lambert = true;
             if (env.n) sc.environment = env;
             MultiGpuFrame mg(devs, gather == "copy" ? MultiGpuFrame::Gather::COPY : MultiGpuFrame::Gather::RCCL, force_gather, only_rank);      // --force-gather: the collective also with one rank
@@ -178,7 +186,7 @@ int main(int argc, char** argv) {
         if (scene == "cornell") { r.SetScene(MakeCornellBox()); lambert = true; }
         else if (scene == "sponza") r.SetScene(MakeSponzaClass());
         else if (scene == "bistro") r.SetScene(MakeBistroClass());
-        else { std::vector<std::string> f; std::stringstream ss(objs); std::string t; while (std::getline(ss, t, ',')) f.push_back(t); r.SetLoadTextures(textures); r.SetCutouts(cutouts); r.SetModels(f, mtl); }
+        else { std::vector<std::string> f; std::stringstream ss(objs); std::string t; while (std::getline(ss, t, ',')) f.push_back(t); r.SetLoadTextures(textures); r.SetCutouts(cutouts); r.SetNormalMaps(normals.mode, normals.strength, normals.flipY); r.SetModels(f, mtl); }
         if (env.n) r.SetEnvironment(env);
         r.Params().spp = spp; r.Params().max_bounces = bounces; r.Params().nee_samples = nee; r.Params().flags = lambert ? RTX_FLAG_LAMBERT_ONLY : (scene == "bistro" ? RTX_FLAG_TRANSMISSION : 0);
         if (restir) {

@@ -1,0 +1,70 @@
+#!/usr/bin/env python3
+"""Tooling: what tangent-space normal maps cost.  The 262 k-triangle atrium at 1080p, 16 spp, 8 bounces, default flags (GGX), with procedural per-corner UVs (world x + z, y of
+the corner, one repeat per unit) in four states of ONE context: unmapped; one 1024 x 1024 noise normal map (b >= 128) on every non-emissive material; the same size of map
+with only flat texels (r = g = 128: k_shade<.., NRM> runs, every hit leaves at the flat-texel test, the image is the unmapped one); unmapped again.  Per state the wall time
+of a frame with RTX_OPT_KERNEL_TIMING off, and the per-kernel-class times (HIP events) with it on.
+The unmapped rows use nothing this feature added: tools/cutout_time.py plain runs from a checkout of the parent for the A/B against it.
+usage: python tools/normalmap_time.py [frames] [rounds]"""
+import os, sys, time
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np
+import torch  # noqa
+import __graft_entry__ as graft
+rt = graft.load_package()
+frames = int(sys.argv[1]) if len(sys.argv) > 1 else 4
+rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 3
+W, H = 1920, 1080
+print("library:", rt.LIB_PATH, flush=True)
+sc = rt.Scene.sponza_class()
+p = rt.Params(width=W, height=H, spp=16, max_bounces=8, nee_samples=1, rr_start=3, sample_base=1, flags=0)
+c = rt.Context(0)
+c.upload(sc, W / H)
+mapped = [m for m in range(len(sc.materials)) if not (np.asarray(sc.materials[m][8:11]) > 0).any()]
+
+
+def wall(n):
+    c.clear(W, H)
+    t0 = time.perf_counter()
+    for f in range(n):
+        c.render(p.copy(frame_seed=1 + f))
+    return (time.perf_counter() - t0) * 1e3 / n
+
+
+def run(tag):
+    c.set_option(rt.OPT_KERNEL_TIMING, 0)
+    wall(1)
+    ms = [wall(frames) for _ in range(rounds)]
+    c.set_option(rt.OPT_KERNEL_TIMING, 1)
+    rows = []
+    for rep in range(frames + 1):
+        c.clear(W, H); c.render(p.copy(frame_seed=1))
+        s = c.stats()
+        if rep:
+            rows.append((s.kernel_ms[rt.K_TRACE], s.kernel_ms[rt.K_SHADE], s.kernel_ms[rt.K_SHADOW]))
+    a = np.array(rows)
+    print(f"{tag}: frame " + " ".join(f"{t:.2f}" for t in ms) + f" ms (median {np.median(ms):.2f}); k_trace_closest {np.median(a[:, 0]):.2f}, k_shade {np.median(a[:, 1]):.2f} "
+          f"(min {a[:, 1].min():.2f}, max {a[:, 1].max():.2f}), k_trace_shadow {np.median(a[:, 2]):.2f} ms; shaded items {c.stats().kernel_items[rt.K_SHADE]}", flush=True)
+    return c.read_accum()
+
+
+plain = run("unmapped")
+for mesh, (v, i, m) in enumerate(sc.meshes):
+    pos = np.asarray(v, np.float32)[np.asarray(i, np.int64), :3]
+    c.set_mesh_uvs(mesh, np.stack([pos[:, 0] + pos[:, 2], pos[:, 1]], 1))
+rng = np.random.default_rng(1)
+noise = rng.integers(0, 256, (1024, 1024, 4), dtype=np.uint8); noise[..., 2] |= 128
+c.set_texture(0, noise, False)
+for m in mapped:
+    c.set_material_map(m, 0, rt.MAP_NORMAL)
+c.commit()
+bumpy = run(f"1024^2 noise normal map on {len(mapped)} materials")
+flat = noise.copy(); flat[..., 0] = 128; flat[..., 1] = 128
+c.set_texture(0, flat, False); c.commit()
+level = run("1024^2 map of flat texels")
+for m in mapped:
+    c.set_material_map(m, -1, rt.MAP_NORMAL)
+c.commit()
+again = run("unmapped again")
+print("images: unmapped == flat map:", bool(np.array_equal(plain, level)), "; == unmapped again:", bool(np.array_equal(plain, again)), "; the noise map differs:", bool(not np.array_equal(plain, bumpy)))
+c.close()
