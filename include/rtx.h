@@ -120,7 +120,12 @@ enum { RTX_OPT_KERNEL_TIMING = 1,    /* 0/1: bracket every launch with hipEvents
                                         bounce b + 1; everything is joined into the context's stream before rtx_render returns.  Off while RTX_OPT_KERNEL_TIMING is on
                                         (overlapping launches have no per-kernel time).  Results identical */
        RTX_OPT_COMPACT_STATE = 16,   /* 1 (default): the separate trace / shade kernels keep ray, throughput and hit records by QUEUE POSITION in two buffer sets (a bounce
-                                        writes its survivors densely at their place in the next queue) instead of by path id in place.  Results identical */
+                                        writes its survivors densely at their place in the next queue) instead of by path id in place.  Results identical.
+                                        The fused tiny-scene kernels do the same with their 48-B path state (origin, direction, throughput; bounce b reads set b & 1, radiance
+                                        stays by path id): bounce 0 and the wave-scheduled form of bounces >= 1 (RTX_OPT_BOUNCE_VARIANT 2) have both layouts.  The block-scheduled
+                                        forms (RTX_OPT_BOUNCE_VARIANT 0 / 1) keep the state by path id, in place: a frame rendered with one of them uses that layout throughout,
+                                        bounce 0's output included, whatever this option says.  Costs memory: two sets of G x qcap entries, about 3 x the bytes of the in-place
+                                        state on a tapered frame.  Measured in profiles/small_compact_time.md */
        RTX_OPT_WORK_STEALING = 15,   /* 1: a wave of the general-scene trace kernels whose sub-queue is exhausted continues with other sub-queues (global chunk cursors + an
                                         exhausted bitmap, pseudo-random victims) instead of draining.  Bit-identical; wave iterations fall 8 % (busy lanes 50.3 -> 55.7 of 64)
                                         but the frame is SLOWER (C3 56.6 vs 47.4 ms, C5 51.0 vs 44.7 ms): the tail iterations it removes are latency-bound and cost few issue

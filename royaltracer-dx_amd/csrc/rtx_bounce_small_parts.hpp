@@ -44,15 +44,29 @@ __device__ __forceinline__ uint32_t shadow_records(const DevScene& sc, bool mine
     return __builtin_amdgcn_ballot_w64(mine && tmin_flag < 0.0f) != 0ull ? sc.nsmall : sc.nsmall_occ;
 }
 
+// PATH STATE BY QUEUE POSITION (COMPACT, RTX_OPT_COMPACT_STATE; DevPaths::out_o != nullptr is the flag, as for the separate kernels).  ray_o / ray_d / thr hold TWO sets of
+// G * qcap entries each, set 1 the same distance behind set 0 in all three streams (state_set_stride).  Bounce b reads the state of queue entry i of sub-queue q at
+// (b & 1) * stride + q * qcap + i and writes a survivor's state into the OTHER set at the slot it takes in the next queue: a wave's state accesses are one contiguous run however
+// many paths died before, and the extension trace fetches its rays without reading the queue first.  The queues still carry the path id, read where it is needed: the
+// radiance additions (rad stays by path id) and the next queue's entry.  Bounce 0 is a launch of its own: with the hit buffer as input (HAVE_HIT 1) it reads set 0 by PATH ID,
+// where k_raygen_trace_small wrote it, and writes set 1 by position.  !COMPACT: by path id, updated in place.
+__device__ __forceinline__ uint32_t state_set_stride(const DevPaths& p) { return (uint32_t)(p.out_o - p.ray_o); }
+// first entry of sub-queue base `qb` in the set that bounce `bounce` reads (state_in) / writes (state_out)
+__device__ __forceinline__ uint32_t state_in(uint32_t qb, uint32_t stride, uint32_t bounce) { return qb + ((bounce & 1u) ? stride : 0u); }
+__device__ __forceinline__ uint32_t state_out(uint32_t qb, uint32_t stride, uint32_t bounce) { return qb + ((bounce & 1u) ? 0u : stride); }
+
 // continuation of one item (go = it was shaded and this is not the last bounce): BSDF sample, throughput, Russian roulette; a surviving path stores its state and takes a slot of
 // the sub-queue's next queue (s_cnt0 = its length so far).  Every lane of the workgroup's waves goes through the compaction.
+// COMPACT: the state goes to out0 + slot (out0 = state_out of this bounce), else to the path's own record.
+template <bool COMPACT>
 __device__ __forceinline__ void continue_path(const MatGPU& m, const DevFrame& f, const DevPaths& p, uint32_t bounce, bool go, PathState& S, f3 pos, f3 normal, f3 outgoing, float eta_p,
-                                              uint32_t* s_cnt0, uint32_t* mynext, Prof* pf) {
+                                              uint32_t* s_cnt0, uint32_t* mynext, uint32_t out0, Prof* pf) {
     bool alive = false;
     f3 smp = mk3(0, 0, 1); float P = 0.0f;
     if (go) { PF_COUNT(9); alive = bsdf_continue(m, f, bounce, S, normal, outgoing, smp, P, eta_p); }
-    if (alive) { PF_COUNT(10); store_path(p, S, pos, smp, P); }
+    if (!COMPACT && alive) { PF_COUNT(10); store_path(p, S, pos, smp, P); }
     const uint32_t slot = block_push(alive, s_cnt0);
+    if (COMPACT && alive) { PF_COUNT(10); store_path_at(p.ray_o, p.ray_d, p.thr, out0 + slot, S, pos, smp, P); }
     if (alive) mynext[slot] = S.pid;
 }
 

@@ -68,7 +68,7 @@ struct rtx_ctx {
         bool lpt_order = true;                      // RTX_OPT_LPT_ORDER: fused kernels take their sub-queues longest first
         bool fused_bvh = false;                     // RTX_OPT_FUSED_BVH: general path = one k_bounce_bvh launch per batch (trace -> shade -> shadow per sub-queue and bounce); measured SLOWER, default off
         bool work_stealing = false;                 // RTX_OPT_WORK_STEALING: trace kernels of general scenes continue with other sub-queues instead of draining (refill_steal); measured SLOWER, default off
-        bool compact_state = true;                  // RTX_OPT_COMPACT_STATE: separate-kernel path keeps ray / throughput / hit records by queue position, ping-pong (DevPaths::out_*)
+        bool compact_state = true;                  // RTX_OPT_COMPACT_STATE: the separate kernels and the fused tiny-scene kernels keep ray / throughput (/ hit) records by queue position, ping-pong (DevPaths::out_*)
         bool overlap_shadow = true;                 // RTX_OPT_OVERLAP_SHADOW: k_trace_shadow of bounce b on a second stream, beside k_trace_closest of bounce b + 1 (not while kernels are timed)
         uint32_t blocks_per_cu = 0;                 // RTX_OPT_BLOCKS_PER_CU (0 = auto)
         bool taper = true; uint32_t taper_levels = 4;   // RTX_OPT_TAPER
@@ -136,7 +136,7 @@ struct rtx_ctx {
     // ---- the path tracer's frame (rtx_render.hip) ----
     struct PathFrame {
         DevBuf d_ray_o, d_ray_d, d_thr, d_rad, d_hit, d_sh_o, d_sh_d, d_sh_c, d_queue[2], d_counters;
-        DevBuf d_alt_o, d_alt_d, d_alt_thr;              // the second path-state set of the compact state
+        DevBuf d_alt_o, d_alt_d, d_alt_thr;              // the second path-state set of the compact state (separate kernels; the fused tiny-scene kernels keep both sets in d_ray_o / d_ray_d / d_thr)
         DevBuf d_hitmask, d_order, d_pmask;
         DevBuf d_prim_rec, d_prim_hits;                  // RTX_OPT_SHARED_PRIMARY: the per-pixel primary surface records and per-block hit masks of the current call (k_primary_surface)
         DevBuf d_oct[2], d_perm;                         // RTX_OPT_OCTANT_SORT

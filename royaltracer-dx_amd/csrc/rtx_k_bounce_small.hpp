@@ -47,9 +47,10 @@ __device__ __forceinline__ bool block_shadow(const DevScene& sc, const SmallRecP
 // Radiance additions happen in the oracle's order (emissive, then NEE slot 0, 1, ...).  Every lane of the workgroup goes through the barriers and compactions.
 // HAVE_HIT != 0 (bounce 0): nothing has written this path's radiance slot yet: it starts from zero here and is always stored
 // (T, sh and sf by value, S by reference: of the shapes tried, the one at which no instantiation spills more SGPRs than with the step written out — profiles/bounce_parts_kernel_resources.md)
-template <int HAVE_HIT, bool LAMBERT>
+// COMPACT / out0: where a survivor's state goes (continue_path)
+template <int HAVE_HIT, bool LAMBERT, bool COMPACT>
 __device__ __forceinline__ void shade_block(const DevScene& sc, const SmallRecPair* small, const TraceLds& L, const DevFrame& f, const DevPaths& p, SmallTables T, ShadowLds sh, uint32_t& par,
-                                            PathState& S, Surf sf, float t, float u, float v, uint32_t prim, bool active, uint32_t bounce, uint32_t nee, bool last, uint32_t* s_cnt, uint32_t* mynext, Prof* pf) {
+                                            PathState& S, Surf sf, float t, float u, float v, uint32_t prim, bool active, uint32_t bounce, uint32_t nee, bool last, uint32_t* s_cnt, uint32_t* mynext, uint32_t out0, Prof* pf) {
     bool shading = false;
     if (active && prim != kMissPrim) { PF_COUNT(3); shading = hit_to_shading<HAVE_HIT>(sc, p, T.mats, S, sf, t, u, v, prim, bounce, nee); }
     const f3 outgoing = -S.d, pos = sf.pos;
@@ -69,14 +70,15 @@ __device__ __forceinline__ void shade_block(const DevScene& sc, const SmallRecPa
         }
     }
     if (loaded) p.rad[S.pid] = radv;
-    continue_path(*mp, f, p, bounce, shading && !last, S, pos, normal, outgoing, eta_p, &s_cnt[0], mynext, pf);
+    continue_path<COMPACT>(*mp, f, p, bounce, shading && !last, S, pos, normal, outgoing, eta_p, &s_cnt[0], mynext, out0, pf);
     PF_MARK(9);
 }
 
 // ---- bounce 0 ----
 // Every queue entry is a primary hit; there is no extension trace.  HAVE_HIT: 1 = path state and hit record come from k_raygen_trace_small; 2 = RTX_OPT_SHARED_PRIMARY: the
 // path starts from its pixel's shared record (k_primary_surface) and derives sample, slot and seeds from its id (PrimIn) — no surface() here, and nothing per path read but the queue word
-template <int HAVE_HIT, bool LAMBERT>
+// COMPACT (rtx_bounce_small_parts.hpp): the survivors' state is written by queue position into set 1; the input (HAVE_HIT 1) is read by path id from set 0 either way
+template <int HAVE_HIT, bool LAMBERT, bool COMPACT>
 __device__ __forceinline__ void bounce_small_first(const DevScene& sc, const SmallRecPair* small, const DevFrame& f_in, const DevPaths& p, uint32_t bounce_first, uint32_t bounce_end,
                                                    uint32_t* queue_a, uint32_t* queue_b, uint32_t* qrows, uint32_t* srows, const uint32_t* order, const PrimIn& pin) {
     extern __shared__ F4 lds[];
@@ -92,6 +94,7 @@ __device__ __forceinline__ void bounce_small_first(const DevScene& sc, const Sma
     const TraceLds L = stage_lds(sc, lds);
     __syncthreads();
     const size_t qb = (size_t)qid * f.qcap;
+    const uint32_t stride = COMPACT ? state_set_stride(p) : 0u;
     uint32_t par = 0;
     PF_BEGIN;
     for (uint32_t bounce = bounce_first; bounce < bounce_end; bounce++) {      // (launched for bounce 0 alone)
@@ -121,7 +124,7 @@ __device__ __forceinline__ void bounce_small_first(const DevScene& sc, const Sma
                 if (active) { S = load_path(p, myq[i]); const F4 h = p.hit[S.pid]; t = h.x; u = h.y; v = h.z; prim = f2u(h.w); }
             }
             PF_MARK(2);
-            shade_block<HAVE_HIT, LAMBERT>(sc, small, L, f, p, T, sh, par, S, sf, t, u, v, prim, active, sbounce, nee, last, s_cnt, mynext, pf);
+            shade_block<HAVE_HIT, LAMBERT, COMPACT>(sc, small, L, f, p, T, sh, par, S, sf, t, u, v, prim, active, sbounce, nee, last, s_cnt, mynext, state_out((uint32_t)qb, stride, bounce), pf);
         }
         n = end_bounce<false>(s_cnt, nullptr, qrows, srows, bounce, G, qid, nee);
     }
@@ -129,6 +132,7 @@ __device__ __forceinline__ void bounce_small_first(const DevScene& sc, const Sma
 }
 
 // ---- bounces >= 1, scheduled per workgroup (RTX_OPT_BOUNCE_VARIANT 0 / 1) ----
+// These two bodies keep the path state by path id, in place: a frame that runs one of them uses that layout throughout, bounce 0 included (plan_batches, rtx_render.hip).
 // RING: 1 = workgroup-wide LDS hit ring between trace and shading (variant 0); 0 = trace and shade the same 256 entries (variant 1)
 template <bool LAMBERT, int RING>
 __device__ __forceinline__ void bounce_small_block(const DevScene& sc, const SmallRecPair* small, const DevFrame& f_in, const DevPaths& p, uint32_t bounce_first, uint32_t bounce_end,
@@ -164,7 +168,7 @@ __device__ __forceinline__ void bounce_small_block(const DevScene& sc, const Sma
                 if (active) S = load_path(p, myq[i]);
                 traverse_small<false>(sc, small, L, S.o, S.d, tmin, active ? kTMax : 0.0f, t, u, v, prim, sc.nsmall, ~0ull, pf, 1);   // inactive lanes: empty interval
                 PF_MARK(2);
-                shade_block<0, LAMBERT>(sc, small, L, f, p, T, sh, par, S, sf, t, u, v, prim, active, bounce, nee, last, s_cnt, mynext, pf);
+                shade_block<0, LAMBERT, false>(sc, small, L, f, p, T, sh, par, S, sf, t, u, v, prim, active, bounce, nee, last, s_cnt, mynext, 0u, pf);
             }
         } else {
             // HIT RING.  20-25 % of the extension rays of a bounce leave the open front of the box or end on the light, and their lanes used to idle
@@ -221,7 +225,7 @@ __device__ __forceinline__ void bounce_small_block(const DevScene& sc, const Sma
                 __syncthreads();                                                    // every lane has read its entry before the slots are released
                 if (threadIdx.x == 0) s_ring[0] = head + take;
                 PF_MARK(2);
-                shade_block<0, LAMBERT>(sc, small, L, f, p, T, sh, par, S, sf, t, u, v, prim, active, bounce, nee, last, s_cnt, mynext, pf);
+                shade_block<0, LAMBERT, false>(sc, small, L, f, p, T, sh, par, S, sf, t, u, v, prim, active, bounce, nee, last, s_cnt, mynext, 0u, pf);
                 __syncthreads();                                    // the released ring slots (s_ring[0]) are visible to the next trip's trace phase
             }
         }
@@ -235,6 +239,7 @@ __device__ __forceinline__ void bounce_small_block(const DevScene& sc, const Sma
 // rays and add their contributions, sample the BSDF, compact — all in one pass over the workgroup's sub-queue.
 // Nothing but the 48-B path state and the queue index moves through HBM; hit records and shadow-ray entries
 // stay in registers.
+// COMPACT: the path state lives by queue position in two sets instead of by path id (rtx_bounce_small_parts.hpp); bounce 0 and the wave-scheduled body (RING 2) have both forms.
 // BOUNCE RANGE: sub-queues are workgroup-private, so bounce b + 1 of sub-queue q depends on bounce b of the SAME sub-queue only.  One
 // launch therefore runs the bounces [bounce_first, bounce_end) of its sub-queue back to back, with a workgroup barrier in between
 // (workgroup-scope release / acquire: the path state and queue entries a bounce writes are read by the same workgroup: end_bounce).  A frame has
@@ -244,7 +249,7 @@ __device__ __forceinline__ void bounce_small_block(const DevScene& sc, const Sma
 // (fewer live registers, fewer SGPR spills through v_writelane / v_readlane in the loop).
 // HAVE_HIT: 0 = bounces >= 1 (the kernel traces its extension rays); 1 / 2 = bounce 0, the two inputs of bounce_small_first
 // RING (bounces >= 1, RTX_OPT_BOUNCE_VARIANT 0 / 1 / 2 = RING 1 / 0 / 2): 0 / 1 = the two forms of bounce_small_block; 2 = bounce_small_wave: wave-private buffers, no barrier inside a bounce
-template <int WAVES, int HAVE_HIT, bool LAMBERT, int RING>
+template <int WAVES, int HAVE_HIT, bool LAMBERT, int RING, bool COMPACT>
 __global__ __launch_bounds__(kBlock, WAVES) void k_bounce_small(DevScene sc, const SmallRecPair* __restrict__ small, DevFrame f_in, DevPaths p,
                                                          uint32_t bounce_first, uint32_t bounce_end,
                                                          uint32_t* __restrict__ queue_a, uint32_t* __restrict__ queue_b /* bounce b reads (b & 1 ? b : a), writes the other */,
@@ -253,8 +258,9 @@ __global__ __launch_bounds__(kBlock, WAVES) void k_bounce_small(DevScene sc, con
                                                          const uint32_t* __restrict__ order /* workgroup -> sub-queue, longest first (k_order_queues); may be null */,
                                                          PrimIn pin /* HAVE_HIT 2: the per-pixel records of k_primary_surface and how to find a path's (read by that instantiation only) */) {
     static_assert(HAVE_HIT == 0 || RING == 0, "bounce 0 has no extension trace, hence no ring: launch_bounce_small");
-    if constexpr (HAVE_HIT != 0) bounce_small_first<HAVE_HIT, LAMBERT>(sc, small, f_in, p, bounce_first, bounce_end, queue_a, queue_b, qrows, srows, order, pin);
-    else if constexpr (RING == 2) bounce_small_wave<LAMBERT>(sc, small, f_in, p, bounce_first, bounce_end, queue_a, queue_b, qrows, srows, order);
+    static_assert(!COMPACT || HAVE_HIT != 0 || RING == 2, "the block-scheduled bodies keep the path state in place: launch_bounce_small");
+    if constexpr (HAVE_HIT != 0) bounce_small_first<HAVE_HIT, LAMBERT, COMPACT>(sc, small, f_in, p, bounce_first, bounce_end, queue_a, queue_b, qrows, srows, order, pin);
+    else if constexpr (RING == 2) bounce_small_wave<LAMBERT, COMPACT>(sc, small, f_in, p, bounce_first, bounce_end, queue_a, queue_b, qrows, srows, order);
     else bounce_small_block<LAMBERT, RING>(sc, small, f_in, p, bounce_first, bounce_end, queue_a, queue_b, qrows, srows, order);
 }
 

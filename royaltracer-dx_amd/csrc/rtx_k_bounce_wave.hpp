@@ -18,7 +18,7 @@ __device__ __forceinline__ void wave_lds_sync() {
 // Bounces [bounce_first, bounce_end), bounce_first >= 1, of the workgroup's sub-queue — the same work, arithmetic and radiance order as bounce_small_block<.., 1> (rtx_k_bounce_small.hpp),
 // scheduled per WAVE instead of per workgroup: inside a bounce no wave ever waits for another.
 //   input     a wave takes the next 64 queue entries from an LDS cursor (s_in, one atomic per chunk): the four waves stay balanced whatever their rays cost
-//   hit buffer  per wave, 64 entries (path id + hit record) in LDS that only this wave touches; a trace pass pushes its hits with ballot + mbcnt at a wave-uniform
+//   hit buffer  per wave, 64 entries (path id — COMPACT: the entry's place in the input queue — + hit record) in LDS that only this wave touches; a trace pass pushes its hits with ballot + mbcnt at a wave-uniform
 //             count held in a register (no LDS atomic).  The wave traces until it has >= 64 hits or the input is exhausted, then shades min(64, avail) entries.  A pass that
 //             takes the count to 64 + r keeps its last r hits in registers until the 64 buffered ones are popped (a few instructions later) and then writes them to slots 0 .. r - 1:
 //             what a 128-entry ring would hold, in half the LDS — with 64-entry buffers the Lambert instantiation keeps five workgroups per CU, with 128-entry rings it would run three
@@ -34,7 +34,10 @@ __device__ __forceinline__ void wave_lds_sync() {
 // every wave executes each exactly once per bounce, outside every data-dependent loop.  There is no producer / consumer protocol between waves.  (2) Termination: every loop ends
 // because the input cursor only grows (a wave that reads a cursor >= n never asks again in this bounce) and a buffer only drains once the input is exhausted (each trip of the
 // outer loop pops >= 1 entry of the hit buffer or ends the bounce; a shadow block empties the shadow buffer).
-template <bool LAMBERT>
+// COMPACT (rtx_bounce_small_parts.hpp): the path state lives by queue position in two sets.  The trace phase fetches origin and direction of entry i at in0 + i — no queue read
+// before the ray fetch — and the hit buffer carries i; the shading phase loads the 48-B state at in0 + i and the path id, myq[i], which the radiance additions and the next
+// queue's entry need; a survivor's state goes to out0 + its slot in the next queue.
+template <bool LAMBERT, bool COMPACT>
 __device__ __forceinline__ void bounce_small_wave(const DevScene& sc, const SmallRecPair* __restrict__ small, const DevFrame& f_in, const DevPaths& p, uint32_t bounce_first, uint32_t bounce_end,
                                                   uint32_t* __restrict__ queue_a, uint32_t* __restrict__ queue_b, uint32_t* __restrict__ qrows, uint32_t* __restrict__ srows, const uint32_t* __restrict__ order) {
     extern __shared__ F4 lds[];
@@ -56,6 +59,7 @@ __device__ __forceinline__ void bounce_small_wave(const DevScene& sc, const Smal
     const TraceLds L = stage_lds(sc, lds);
     __syncthreads();
     const size_t qb = (size_t)qid * f.qcap;
+    const uint32_t stride = COMPACT ? state_set_stride(p) : 0u;
     const uint32_t lane = lane_id();
     const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     uint32_t* const hpid = s_hpid + wv * kHitBuf; F4* const hhit = s_hhit + wv * kHitBuf;      // this wave's buffers
@@ -66,6 +70,7 @@ __device__ __forceinline__ void bounce_small_wave(const DevScene& sc, const Smal
         const float tmin = bounce_tmin(bounce);
         const uint32_t* myq = ((bounce & 1u) ? queue_b : queue_a) + qb;
         uint32_t* mynext = ((bounce & 1u) ? queue_a : queue_b) + qb;
+        const uint32_t in0 = state_in((uint32_t)qb, stride, bounce), out0 = state_out((uint32_t)qb, stride, bounce);      // COMPACT: this sub-queue's first entry in the set read / written
         uint32_t hcnt = 0;                                          // hit buffer: entries waiting (wave-uniform register; < 64 between trace passes)
         uint32_t shcnt = 0;                                         // lane j: shadow rays this wave pushed for NEE slot j in this bounce
         bool in_done = false;                                       // this wave has seen the cursor at or past n
@@ -100,8 +105,8 @@ __device__ __forceinline__ void bounce_small_wave(const DevScene& sc, const Smal
                 if (c0 >= n) { in_done = true; break; }
                 const uint32_t i = c0 + lane;
                 const bool act = i < n;
-                uint32_t pid = 0; f3 ro = mk3(0, 0, 0), rd = mk3(0, 0, 1);
-                if (act) { pid = myq[i]; const F4 a = p.ray_o[pid], b = p.ray_d[pid]; ro = mk3(a.x, a.y, a.z); rd = mk3(b.x, b.y, b.z); }
+                uint32_t pid = 0; f3 ro = mk3(0, 0, 0), rd = mk3(0, 0, 1);      // pid: what the hit buffer carries — the path id, or (COMPACT) the entry's place in the queue
+                if (act) { pid = COMPACT ? i : myq[i]; const uint32_t src = COMPACT ? in0 + i : pid; const F4 a = p.ray_o[src], b = p.ray_d[src]; ro = mk3(a.x, a.y, a.z); rd = mk3(b.x, b.y, b.z); }
                 float ht, hu, hv; uint32_t hp;
                 traverse_small<false>(sc, small, L, ro, rd, tmin, act ? kTMax : 0.0f, ht, hu, hv, hp, sc.nsmall, ~0ull, pf, 1);   // inactive lanes: empty interval
                 const bool hit = act && hp != kMissPrim;
@@ -119,7 +124,9 @@ __device__ __forceinline__ void bounce_small_wave(const DevScene& sc, const Smal
             float t = 0.0f, u = 0.0f, v = 0.0f; uint32_t prim = kMissPrim;
             wave_lds_sync();                                        // the pushes above are visible to the lanes that pop them
             if (active) {
-                S = load_path(p, hpid[lane]);
+                const uint32_t e = hpid[lane];
+                S = load_path(p, COMPACT ? in0 + e : e);
+                if (COMPACT) S.pid = myq[e];
                 const F4 h = hhit[lane]; t = h.x; u = h.y; v = h.z; prim = f2u(h.w);
             }
             wave_lds_sync();                                        // every lane has read its entry before the slots are written again
@@ -154,7 +161,7 @@ __device__ __forceinline__ void bounce_small_wave(const DevScene& sc, const Smal
                 } else scnt = tot;
                 if (nee > 1u && scnt) { shadow_block(scnt); scnt = 0; }        // drain per slot: slot j + 1 of a path is pushed after slot j was added
             }
-            continue_path(*mp, f, p, bounce, shading && !last, S, pos, normal, outgoing, eta_p, &s_cnt[0], mynext, pf);
+            continue_path<COMPACT>(*mp, f, p, bounce, shading && !last, S, pos, normal, outgoing, eta_p, &s_cnt[0], mynext, out0, pf);
             PF_MARK(9);
         }
         if (scnt) { shadow_block(scnt); scnt = 0; }                 // the partial block: nothing of this bounce stays pending

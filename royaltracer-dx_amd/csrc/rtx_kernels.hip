@@ -153,17 +153,20 @@ void launch_bounce_small(hipStream_t st, const DevScene& sc, const DevFrame& f, 
     // with 2 spilled, measured the same: 19.13 vs 19.03 ms).  Bounce 0 (reads the primary hits) is its own instantiation and launch.
     const bool lam = (f.flags & 1u) != 0u, have_hit = bounce_first == 0u;
     const PrimIn pin = prim ? *prim : PrimIn{};
-    auto go = [&](auto hh, auto rr) {       // hh: where bounce 0's hits come from (0 = not bounce 0, 1 = the hit buffer, 2 = the shared primary records); rr: RING — the form of bounces >= 1 (RTX_OPT_BOUNCE_VARIANT 0 / 1 / 2 = RING 1 / 0 / 2)
+    // cc: the path state by queue position in two sets (p.out_o != nullptr, RTX_OPT_COMPACT_STATE).  The block-scheduled forms of bounces >= 1 have no such instantiation:
+    // the host plans a frame that runs one of them in place (plan_batches), and DevPaths says so
+    auto go = [&](auto hh, auto rr, auto cc) {       // hh: where bounce 0's hits come from (0 = not bounce 0, 1 = the hit buffer, 2 = the shared primary records); rr: RING — the form of bounces >= 1 (RTX_OPT_BOUNCE_VARIANT 0 / 1 / 2 = RING 1 / 0 / 2)
         dispatch_bool(lam, [&](auto ll) {
-            hipLaunchKernelGGL((k_bounce_small<4, decltype(hh)::value, decltype(ll)::value, decltype(rr)::value>), dim3(f.nblocks), dim3(kBlock), trace_lds_bytes(sc), st,
+            hipLaunchKernelGGL((k_bounce_small<4, decltype(hh)::value, decltype(ll)::value, decltype(rr)::value, decltype(cc)::value>), dim3(f.nblocks), dim3(kBlock), trace_lds_bytes(sc), st,
                                sc, sc.small, f, p, bounce_first, bounce_end, queue_a, queue_b, qrows, srows, order, pin);
         });
     };
-    if (have_hit && prim) go(IntC<2>{}, IntC<0>{});
-    else if (have_hit) go(IntC<1>{}, IntC<0>{});
-    else if (variant == 2) go(IntC<0>{}, IntC<2>{});
-    else if (variant == 1) go(IntC<0>{}, IntC<0>{});
-    else go(IntC<0>{}, IntC<1>{});
+    const bool compact = p.out_o != nullptr;
+    if (have_hit && prim) dispatch_bool(compact, [&](auto cc) { go(IntC<2>{}, IntC<0>{}, cc); });
+    else if (have_hit) dispatch_bool(compact, [&](auto cc) { go(IntC<1>{}, IntC<0>{}, cc); });
+    else if (variant == 2) dispatch_bool(compact, [&](auto cc) { go(IntC<0>{}, IntC<2>{}, cc); });
+    else if (variant == 1) go(IntC<0>{}, IntC<0>{}, BoolC<false>{});
+    else go(IntC<0>{}, IntC<1>{}, BoolC<false>{});
 }
 void launch_bounce_bvh(hipStream_t st, const DevScene& sc, const DevFrame& f, const DevPaths& p, uint32_t bounce_first, uint32_t bounce_end,
                        uint32_t* queue_a, uint32_t* queue_b, uint32_t* hitq, uint32_t* qrows, uint32_t* srows, const uint32_t* order) {

@@ -139,6 +139,9 @@ struct DevPaths {
     // into the other buffer set (out_*).  A wave's state accesses stay one contiguous run however many paths died before (by path id the
     // bounces after Russian roulette touched one 16-B record per 128-B line), and the trace kernels need no queue read before they can
     // fetch a ray.  rad stays indexed by path id.
+    // The fused tiny-scene kernels (k_bounce_small: bounce 0 and the wave-scheduled form of bounces >= 1) take the same flag; they run a range of bounces per launch, so they
+    // get BOTH sets at once: ray_o / ray_d / thr = set 0, out_* = set 1, the same number of entries behind set 0 in all three streams, and bounce b reads set b & 1
+    // (rtx_bounce_small_parts.hpp).  Their hit records (bounce 0 of jittered / thin-lens frames) stay by path id.
     F4* out_o; F4* out_d; F4* out_thr;        // nullptr: state indexed by path id, updated in place
     // RTX_OPT_OCTANT_SORT (compact state only): k_shade notes the direction octant of every survivor at its place in the next queue (oct_out); the closest-hit kernel of the
     // next bounce sorts its sub-queue's entries by that byte in a prologue (perm: entry order -> queue position) and fetches its rays through perm, so that a wave's lanes

@@ -41,10 +41,14 @@ BatchPlan plan_batches(const rtx_ctx* c, uint32_t spp, const DevFrame& f, bool f
     // MEMORY of the taper: every per-queue-position buffer has the uniform stride G * qcap with qcap = the LONGEST sub-queue, so the weights 8 | 4 | 2 | 1 cost
     // 8 / 5.375 = 1.49 x the entries of the even deal (both compact path-state sets, hit records, both queues, nee x 3 shadow streams: ~ +10 GB at the 128 Mi-path cap).
     // Where the path state lives by queue position (the general path: 176 B + 48 B per NEE slot and entry) RTX_OPT_PATHS_PER_BATCH therefore caps the ENTRIES: the batch shrinks
-    // until the tapered layout fits it, so a frame that fitted before the taper fits now.  The fused tiny-scene kernels keep their state by path id and only
-    // the two 4-byte queues grow (1.06 -> 1.58 GB at the cap): their batch stays whole — the headline frame is one batch of 132.7 M paths.
-    B.compact = c->opt.compact_state && !tiny_fused && !fused_bvh;
-    while (B.taper_levels && B.compact && B.bspp > 1u && (uint64_t)B.G * B.qchunks * 256u > c->opt.paths_per_batch) {
+    // until the tapered layout fits it, so a frame that fitted before the taper fits now.  The fused tiny-scene kernels keep 48 B per entry (two sets by queue
+    // position) and their batch stays WHOLE, whatever the taper adds: the headline frame is one batch of 132.7 M paths, and a second batch would change the order of the float
+    // additions in k_accumulate, hence the image's bits.  Its 196.6 M entries (10 240 sub-queues of 75 chunks) are 18.9 GB of path state (by path id, RTX_OPT_COMPACT_STATE 0:
+    // 6.4 GB); a batch at the 128 Mi-path cap has 199.2 M entries, 19.1 GB.
+    // The fused tiny-scene path has the by-position layout in bounce 0 and in the wave-scheduled form of bounces >= 1 (RTX_OPT_BOUNCE_VARIANT 2, the default); a frame that
+    // runs a block-scheduled form keeps its state by path id throughout.
+    B.compact = c->opt.compact_state && !fused_bvh && (!tiny_fused || c->opt.bounce_variant == 2);
+    while (B.taper_levels && B.compact && !tiny_fused && B.bspp > 1u && (uint64_t)B.G * B.qchunks * 256u > c->opt.paths_per_batch) {
         const uint32_t next = (uint32_t)std::max<uint64_t>(1, (uint64_t)B.bspp * c->opt.paths_per_batch / ((uint64_t)B.G * B.qchunks * 256u));
         B.bspp = next < B.bspp ? next : B.bspp - 1u;
         plan(B.bspp);
@@ -193,11 +197,16 @@ int render_frame(rtx_ctx* c, const rtx_params* p, const DevFrame& f_real, uint32
     const uint32_t qcap = B.qchunks * 256u;
     f.nblocks = G; f.qcap = qcap; f.taper_levels = B.taper_levels;
     const size_t qtot = (size_t)G * qcap;
-    // path state: by path id (cap entries), or — separate kernels of the default configuration — by queue position (qtot >= cap entries) in two sets
+    // path state: by path id (cap entries), or — the default configuration — by queue position (qtot >= cap entries) in two sets.  The separate kernels get their second set
+    // in buffers of its own (d_alt_*, handed over per bounce: enqueue_bounces); the fused tiny-scene kernels, which run all bounces >= 1 in one launch, find it `nstate` entries
+    // behind the first in the SAME three allocations: one scalar toggles per bounce instead of six pointers (k_bounce_small spills SGPRs as it is)
     const size_t nstate = B.compact ? qtot : (size_t)cap;
-    if (nstate > 0xFFFFFFFFull) { c->err = "render: batch too large"; return RTX_ERR_INVALID; }
-    HIPCHK(c, c->pt.d_ray_o.ensure(nstate * 16)); HIPCHK(c, c->pt.d_ray_d.ensure(nstate * 16)); HIPCHK(c, c->pt.d_thr.ensure(nstate * 16)); HIPCHK(c, c->pt.d_hit.ensure(nstate * 16));
-    if (B.compact) { HIPCHK(c, c->pt.d_alt_o.ensure(nstate * 16)); HIPCHK(c, c->pt.d_alt_d.ensure(nstate * 16)); HIPCHK(c, c->pt.d_alt_thr.ensure(nstate * 16)); }
+    const bool tiny_compact = tiny_fused && B.compact;
+    const size_t nsets = tiny_compact ? 2 : 1;
+    if (nstate * nsets > 0xFFFFFFFFull) { c->err = "render: batch too large"; return RTX_ERR_INVALID; }
+    HIPCHK(c, c->pt.d_ray_o.ensure(nstate * nsets * 16)); HIPCHK(c, c->pt.d_ray_d.ensure(nstate * nsets * 16)); HIPCHK(c, c->pt.d_thr.ensure(nstate * nsets * 16));
+    HIPCHK(c, c->pt.d_hit.ensure((tiny_fused ? (size_t)cap : nstate) * 16));          // (tiny scenes: the primary hits, by path id)
+    if (B.compact && !tiny_fused) { HIPCHK(c, c->pt.d_alt_o.ensure(nstate * 16)); HIPCHK(c, c->pt.d_alt_d.ensure(nstate * 16)); HIPCHK(c, c->pt.d_alt_thr.ensure(nstate * 16)); }
     HIPCHK(c, c->pt.d_queue[0].ensure(qtot * 4)); HIPCHK(c, c->pt.d_queue[1].ensure(qtot * 4));
     HIPCHK(c, c->pt.d_order.ensure((size_t)G * 4));
     if (fused_bvh) HIPCHK(c, c->pt.d_hitq.ensure(qtot * 4));
@@ -220,8 +229,10 @@ int render_frame(rtx_ctx* c, const rtx_params* p, const DevFrame& f_real, uint32
     DevPaths& P = R.P;
     P.ray_o = (F4*)c->pt.d_ray_o.p; P.ray_d = (F4*)c->pt.d_ray_d.p; P.thr = (F4*)c->pt.d_thr.p; P.rad = (F4*)c->pt.d_rad.p; P.hit = (F4*)c->pt.d_hit.p;
     P.hitmask = nullptr;
-    P.out_o = P.out_d = P.out_thr = nullptr; P.oct_out = nullptr; P.oct_in = nullptr; P.perm = nullptr; P.key_mode = (uint32_t)c->opt.octant_sort;
-    R.osort = c->opt.octant_sort && B.compact && !R.stealing;
+    P.out_o = P.out_d = P.out_thr = nullptr;
+    if (tiny_compact) { P.out_o = P.ray_o + nstate; P.out_d = P.ray_d + nstate; P.out_thr = P.thr + nstate; }      // the same distance in all three streams (state_set_stride)
+    P.oct_out = nullptr; P.oct_in = nullptr; P.perm = nullptr; P.key_mode = (uint32_t)c->opt.octant_sort;
+    R.osort = c->opt.octant_sort && B.compact && !tiny_fused && !R.stealing;
     if (R.osort) { HIPCHK(c, c->pt.d_oct[0].ensure(qtot)); HIPCHK(c, c->pt.d_oct[1].ensure(qtot)); HIPCHK(c, c->pt.d_perm.ensure(qtot * 4)); }
     if (R.osort && c->opt.octant_sort == 2) { HIPCHK(c, hipMemsetAsync(c->pt.d_oct[0].p, 0, qtot, c->stream)); HIPCHK(c, hipMemsetAsync(c->pt.d_oct[1].p, 0, qtot, c->stream)); }
     if (tiny_fused && !shared_primary) { HIPCHK(c, c->pt.d_hitmask.ensure(((size_t)cap / 64 + 1) * 8)); P.hitmask = (unsigned long long*)c->pt.d_hitmask.p; }
