@@ -189,6 +189,9 @@ enum { RTX_OPT_KERNEL_TIMING = 1,    /* 0/1: bracket every launch with hipEvents
                                         one camera ray per sample */
        RTX_OPT_DENOISE_LDS_STEP = 42,/* tuning, rtx_denoise: the levels with step <= this value (0, 1, 2 or 4) stage their tile and its halo in LDS, the coarser ones read every tap from global memory.
                                         Default 4: every step that fits (measured faster than the direct form at steps 1, 2 and 4: profiles/denoise_time.md).  Never changes a result */
+       RTX_OPT_SMALL_SLABS = 43,     /* 1 (default): tiny scenes: a pair of pre-test records that are both (near-)parallelograms is tested by two slabs per record, |w . P - c| <= h, instead of four edge
+                                        planes (fewer packed instructions per pair; csrc/rtx_small_scene.cpp has the proof that it is as conservative).  0: every pair by its edge planes — the same
+                                        kernels, a wave-uniform branch never taken.  Never changes a result; takes effect with the next frame */
        RTX_OPT_BLOCKS_PER_CU = 12    /* tuning: workgroups (= private sub-queues) per compute unit; default 0 = auto: 40 (tiny scenes) / 32 at full frame size (8 measured 4-7 % slower there: tail imbalance), fewer — down to 8 — when a batch is so
                                         small (a shard) that a sub-queue would start with fewer than ~16 / ~8 chunks of 256 paths */ };
 

@@ -128,6 +128,9 @@ int  rtxh_scene_small_records(const rtxh_scene*, float* recs20, int32_t* tri_ids
 /* of those records, [0, *nocc_out) can lie between two scene points; the rest are faces of the scene's convex hull, which NEE
    shadow segments skip */
 int  rtxh_scene_small_occluders(const rtxh_scene*, uint32_t* nocc_out);
+/* the slab form of those records: per record 10 floats (w1 xyz, c1, h1, w2 xyz, c2, h2: |w . P - c| <= h, the distance tolerance folded into h) and the excess area of its bounding
+   parallelogram over the quad as a fraction (-1: not a quad); *pair_mask_out: bit kp set = records 2kp, 2kp+1 are tested in this form */
+int  rtxh_scene_small_slabs(const rtxh_scene*, float* slabs10, float* excess, uint32_t max_recs, uint32_t* nrec_out, uint32_t* pair_mask_out);
 /* the visiting order of any-hit rays rtx_commit_scene's probe picks for this scene (RTX_OPT_ANYHIT_ORDER -1): 0 slot order, 1 nearest octant first, 2 farthest first; no GPU needed */
 int  rtxh_scene_anyhit_order(const rtxh_scene*, uint32_t* order_out);
 

@@ -46,6 +46,7 @@ OPT_STACK_CAP = 39
 OPT_DEFORM_REBUILD = 40
 OPT_SHARED_PRIMARY = 41
 OPT_DENOISE_LDS_STEP = 42
+OPT_SMALL_SLABS = 43
 TEX_SRGB = 1          # rtx_set_texture flag: the bytes are sRGB-encoded
 MAP_KD = 0            # rtx_set_material_map slot
 MAP_OPACITY = 2       # ... the alpha cut-out slot: reads the texture's alpha byte (1 is not a slot)
@@ -260,6 +261,7 @@ _sig("rtxh_write_png", C.c_int, C.c_char_p, _vp, _u32, _u32)
 _sig("rtxh_write_ppm", C.c_int, C.c_char_p, _vp, _u32, _u32)
 _sig("rtxh_write_exr", C.c_int, C.c_char_p, _vp, _u32, _u32)
 _sig("rtxh_scene_small_records", C.c_int, _vp, _vp, _vp, _u32, _u32p, _fp, _fp)
+_sig("rtxh_scene_small_slabs", C.c_int, _vp, _vp, _vp, _u32, _u32p, _u32p)
 _sig("rtxh_scene_set_camera", C.c_int, _vp, _fp, _fp, _fp)
 _sig("rtxh_scene_set_mesh_vertices", C.c_int, _vp, _u32, _vp, _u32)
 _sig("rtxh_renderer_set_mesh_vertices", C.c_int, _vp, _u32, _vp, _u32)
@@ -435,6 +437,14 @@ class Scene:
         if lib.rtxh_scene_small_records(self._h, _ptr(recs), _ptr(ids), 64, C.byref(n), C.byref(d), C.byref(cm)) != RTX_OK or n.value == 0:
             return None
         return recs[:n.value], ids[:n.value], d.value, cm.value
+
+    def small_slabs(self):
+        """-> (slabs (n,10) f32: w1 xyz, c1, h1, w2 xyz, c2, h2; excess (n,) f32, -1 = not a quad; pair mask) of the tiny-scene pre-test's slab form, or None"""
+        slabs, ex = np.zeros((64, 10), np.float32), np.zeros(64, np.float32)
+        n, m = _u32(), _u32()
+        if lib.rtxh_scene_small_slabs(self._h, _ptr(slabs), _ptr(ex), 64, C.byref(n), C.byref(m)) != RTX_OK or n.value == 0:
+            return None
+        return slabs[:n.value], ex[:n.value], m.value
 
     def small_occluders(self):
         """number of leading tiny-scene records that are NOT faces of the scene's convex hull"""

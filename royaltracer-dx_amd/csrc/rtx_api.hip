@@ -14,6 +14,7 @@ void options_to_scene(rtx_ctx* c, bool committed) {
     if (committed) {
         s.any_order = o.any_order_opt < 0 ? c->scene.built.any_order : (uint32_t)o.any_order_opt;
         s.any_order_occ = o.any_order_opt < 0 ? 0u : (uint32_t)o.any_order_opt;
+        s.small_slab_mask = o.small_slabs ? c->scene.built.small_slab_mask : 0u;      // 0: every pair generic — the same kernels, their wave-uniform branch never taken
     }
 }
 
@@ -175,6 +176,7 @@ int rtx_set_option(rtx_ctx* c, int option, int64_t value) {
     case RTX_OPT_PARTIAL_REFIT: c->opt.partial_refit = value != 0; return RTX_OK;
     case RTX_OPT_LDS_NODES_CLOSEST: c->opt.lds_closest_opt = (int)value; if (c->committed) pick_lds_closest(c); return RTX_OK;
     case RTX_OPT_SMALL_SCENE: c->opt.small_scene = value != 0; c->committed = false; return RTX_OK;
+    case RTX_OPT_SMALL_SLABS: c->opt.small_slabs = value != 0; options_to_scene(c, c->committed); return RTX_OK;
     case RTX_OPT_FUSED_BOUNCE: c->opt.fused = value != 0; return RTX_OK;
     case RTX_OPT_BOUNCE_VARIANT: c->opt.bounce_variant = value == 2 ? 2 : (value != 0 ? 1 : 0); return RTX_OK;     // 0: workgroup-wide LDS hit ring between trace and shading; 1: trace and shade the same 256 entries; 2: wave-private rings, no barrier inside a bounce
     case RTX_OPT_SHARED_PRIMARY: c->opt.shared_primary = value != 0; return RTX_OK;

@@ -46,6 +46,7 @@ static int upload_built(rtx_ctx* c) {          // every device array of a freshl
     if ((r = upload(c, c->scene.d_small, B.small_recs))) return r;
     if ((r = upload(c, c->scene.d_small_tris, B.small_tris))) return r;
     if ((r = upload(c, c->scene.d_small_poly, B.small_poly))) return r;
+    if ((r = upload(c, c->scene.d_small_slabs, B.small_slabs))) return r;
     if ((r = upload(c, c->scene.d_mats, B.mats))) return r;
     if ((r = upload(c, c->scene.d_insts, B.insts))) return r;
     return upload_lights(c);
@@ -381,7 +382,7 @@ static int build_and_upload(rtx_ctx* c) {
     if ((r = upload(c, c->scene.d_insts, B.insts))) return r;
     if ((r = upload_lights(c))) return r;
     if ((r = flatten_on_device(c, nt))) return r; c->scene.objtris_uploaded = true;          // object-space triangles + shade records, from the resident meshes
-    for (DevBuf* b : {&c->scene.d_small, &c->scene.d_small_tris, &c->scene.d_small_poly}) HIPCHK(c, b->ensure(16));
+    for (DevBuf* b : {&c->scene.d_small, &c->scene.d_small_tris, &c->scene.d_small_poly, &c->scene.d_small_slabs}) HIPCHK(c, b->ensure(16));
     HIPCHK(c, c->scene.d_tris.ensure((size_t)nt * sizeof(TriGPU)));
     if (!c->scene.builder) c->scene.builder.reset(new GpuBvhBuilder());
     BvhBuildOptions bo = c->host.bvh; if (bo.ploc_radius <= 0) bo.ploc_radius = 16;
@@ -508,7 +509,7 @@ static int finalise_scene(rtx_ctx* c) {
     if (c->scene.wide_nodes && c->opt.node_stride == 128) { s.nodes_f = (const F4*)c->scene.d_nodes_wide.p; s.node_v4 = 8u; }
     s.tris = (const TriGPU*)c->scene.d_tris.p; s.ntris = c->scene.n_tris8;
     s.shade = (const TriShade*)c->scene.d_shade.p;
-    s.small = (const SmallRecPair*)c->scene.d_small.p; s.small_tris = (const TriGPU*)c->scene.d_small_tris.p; s.small_poly = (const F4*)c->scene.d_small_poly.p; s.small_cm = B.small_cm; s.small_delta = B.small_delta;
+    s.small = (const SmallRecPair*)c->scene.d_small.p; s.small_tris = (const TriGPU*)c->scene.d_small_tris.p; s.small_poly = (const F4*)c->scene.d_small_poly.p; s.small_slabs = (const SmallSlabPair*)c->scene.d_small_slabs.p; s.small_cm = B.small_cm; s.small_delta = B.small_delta;
     s.mats = (const MatGPU*)c->scene.d_mats.p; s.nmat = (uint32_t)B.mats.size();
     s.insts = (const InstGPU*)c->scene.d_insts.p; s.ninst = (uint32_t)B.insts.size();
     s.lights = (const LightGPU*)c->scene.d_lights.p; s.nlights = (uint32_t)B.lights.size(); s.cdf = (const float*)c->scene.d_cdf.p;

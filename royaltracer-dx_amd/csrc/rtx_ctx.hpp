@@ -61,6 +61,7 @@ struct rtx_ctx {
         int partial_refit = 1;                      // RTX_OPT_PARTIAL_REFIT: partial GPU refit (node_aabb / d_scale hold the last full refit's state)
         int lds_closest_opt = -1;                   // RTX_OPT_LDS_NODES_CLOSEST
         bool small_scene = true;                    // RTX_OPT_SMALL_SCENE
+        bool small_slabs = true;                    // RTX_OPT_SMALL_SLABS: near-parallelogram record pairs are pre-tested by two slabs per record (DevScene::small_slab_mask)
         bool fused = true;                          // RTX_OPT_FUSED_BOUNCE
         int bounce_variant = 2;                     // RTX_OPT_BOUNCE_VARIANT: 0 workgroup hit ring, 1 no ring, 2 wave-private rings
         bool shared_primary = true;                 // RTX_OPT_SHARED_PRIMARY
@@ -102,7 +103,7 @@ struct rtx_ctx {
     struct Scene {
         BuiltScene built;
         bool committed_once = false;
-        DevBuf d_nodes, d_tris, d_small, d_small_tris, d_small_poly, d_shade, d_mats, d_insts, d_lights, d_cdf;
+        DevBuf d_nodes, d_tris, d_small, d_small_tris, d_small_poly, d_small_slabs, d_shade, d_mats, d_insts, d_lights, d_cdf;
         std::vector<float> h_cdf; std::vector<uint32_t> h_one;     // host sources of small asynchronous uploads
         // the wide tree as the DEVICE holds it (the host mirror B.nodes8 / B.tris8 is empty after a GPU build): counts, the root record (octant-sort grid), who built it
         uint32_t n_nodes8 = 0, n_tris8 = 0; Node8GPU root8{}; bool dev_built = false; std::unique_ptr<GpuBvhBuilder> builder; GpuBuildResult build_info;

@@ -166,7 +166,7 @@ __device__ __forceinline__ void bounce_small_block(const DevScene& sc, const Sma
                 const uint32_t i = base + threadIdx.x;
                 const bool active = i < n;
                 if (active) S = load_path(p, myq[i]);
-                traverse_small<false>(sc, small, L, S.o, S.d, tmin, active ? kTMax : 0.0f, t, u, v, prim, sc.nsmall, ~0ull, pf, 1);   // inactive lanes: empty interval
+                traverse_small<false, true>(sc, small, L, S.o, S.d, tmin, active ? kTMax : 0.0f, t, u, v, prim, sc.nsmall, ~0ull, pf, 1);   // inactive lanes: empty interval
                 PF_MARK(2);
                 shade_block<0, LAMBERT, false>(sc, small, L, f, p, T, sh, par, S, sf, t, u, v, prim, active, bounce, nee, last, s_cnt, mynext, 0u, pf);
             }
@@ -203,7 +203,7 @@ __device__ __forceinline__ void bounce_small_block(const DevScene& sc, const Sma
                     uint32_t pid = 0; f3 ro = mk3(0, 0, 0), rd = mk3(0, 0, 1);
                     if (act) { pid = myq[i]; const F4 a = p.ray_o[pid], b = p.ray_d[pid]; ro = mk3(a.x, a.y, a.z); rd = mk3(b.x, b.y, b.z); }
                     float ht, hu, hv; uint32_t hp;
-                    traverse_small<false>(sc, small, L, ro, rd, tmin, act ? kTMax : 0.0f, ht, hu, hv, hp, sc.nsmall, ~0ull, pf, 1);   // inactive lanes: empty interval
+                    traverse_small<false, true>(sc, small, L, ro, rd, tmin, act ? kTMax : 0.0f, ht, hu, hv, hp, sc.nsmall, ~0ull, pf, 1);   // inactive lanes: empty interval
                     const bool hit = act && hp != kMissPrim;
                     const uint32_t slot = prod + block_push(hit, &s_rc[rk]);
                     if (hit) { s_rpid[slot & (kRing - 1u)] = pid; s_rhit[slot & (kRing - 1u)] = {ht, hu, hv, u2f(hp)}; }

@@ -108,7 +108,7 @@ __device__ __forceinline__ void bounce_small_wave(const DevScene& sc, const Smal
                 uint32_t pid = 0; f3 ro = mk3(0, 0, 0), rd = mk3(0, 0, 1);      // pid: what the hit buffer carries — the path id, or (COMPACT) the entry's place in the queue
                 if (act) { pid = COMPACT ? i : myq[i]; const uint32_t src = COMPACT ? in0 + i : pid; const F4 a = p.ray_o[src], b = p.ray_d[src]; ro = mk3(a.x, a.y, a.z); rd = mk3(b.x, b.y, b.z); }
                 float ht, hu, hv; uint32_t hp;
-                traverse_small<false>(sc, small, L, ro, rd, tmin, act ? kTMax : 0.0f, ht, hu, hv, hp, sc.nsmall, ~0ull, pf, 1);   // inactive lanes: empty interval
+                traverse_small<false, true>(sc, small, L, ro, rd, tmin, act ? kTMax : 0.0f, ht, hu, hv, hp, sc.nsmall, ~0ull, pf, 1);   // inactive lanes: empty interval
                 const bool hit = act && hp != kMissPrim;
                 const unsigned long long hmask = __ballot(hit);
                 const uint32_t e = hcnt + __builtin_amdgcn_mbcnt_hi((uint32_t)(hmask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)hmask, 0u));

@@ -101,7 +101,7 @@ __global__ __launch_bounds__(kBlock) void k_raygen_trace_small(DevScene sc, cons
         const unsigned long long km = masks[pl >> 6];
         const unsigned long long keep = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(km >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)km);
         float t, u, v; uint32_t prim;
-        traverse_small<false>(sc, small, L, o, d, kTMinCam, valid ? kTMax : 0.0f, t, u, v, prim, sc.nsmall, keep);
+        traverse_small<false, true>(sc, small, L, o, d, kTMinCam, valid ? kTMax : 0.0f, t, u, v, prim, sc.nsmall, keep);
         const bool hit = valid && prim != kMissPrim;
         // 43 % of the Cornell camera rays leave the box: their radiance stays zero, so only a hit bit is recorded for them
         const unsigned long long hm = __ballot(hit);
@@ -144,7 +144,7 @@ __global__ __launch_bounds__(kBlock) void k_primary_surface(DevScene sc, const S
     f3 o = mk3(0, 0, 0), d = mk3(0, 0, 1);
     if (valid) primary_ray(cam, f.width, f.height, x, y, 0.0f, 0.0f, o, d);
     float t, u, v; uint32_t prim;
-    traverse_small<false>(sc, small, L, o, d, kTMinCam, valid ? kTMax : 0.0f, t, u, v, prim, sc.nsmall, keep);
+    traverse_small<false, true>(sc, small, L, o, d, kTMinCam, valid ? kTMax : 0.0f, t, u, v, prim, sc.nsmall, keep);
     const bool hit = valid && prim != kMissPrim;
     const unsigned long long hm = __ballot(hit);
     const unsigned long long vm = __ballot(valid);

@@ -53,6 +53,9 @@ struct DevScene {
     // some triangle uses has RTX_MAP_NORMAL: such scenes launch what they always launched; otherwise tri_uv and map_kd are set too and k_shade<.., NRM> runs
     const float* tri_tan;               // 6 floats per GLOBAL triangle id (indexed like tri_uv): the object-space tangent T = dP/du and bitangent B = dP/dv, zeros where the UVs give none
     const int32_t* map_nrm;             // per material: texture id of RTX_MAP_NORMAL, or -1
+    // slab form of the tiny-scene record pairs (rtx_types.hpp: SmallSlabPair; the last members: every other one keeps its place in the kernel arguments)
+    const SmallSlabPair* small_slabs;   // one entry per SmallRecPair
+    uint32_t small_slab_mask;           // bit kp set: traverse_small tests pair kp by its two slabs per record; clear: by its four edge planes (RTX_OPT_SMALL_SLABS 0: all clear)
 };
 
 // one sample batch of one frame

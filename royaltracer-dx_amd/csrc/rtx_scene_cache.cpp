@@ -32,7 +32,7 @@ namespace rtx {
 namespace {
 
 constexpr char kMagic[8] = {'R', 'T', 'X', 'S', 'C', 'N', '0', '1'};
-constexpr uint32_t kVersion = 3;              // 2: + the host layer's MaterialExt records and texture names (two sections at the end); 3: TriGPU::e1.w carries the determinant floor of the hit definition
+constexpr uint32_t kVersion = 4;              // 4: + the slab table of the tiny-scene records (SmallSlabPair, the pairs' kind mask in the scalar block); 2: + the host layer's MaterialExt records and texture names (two sections at the end); 3: TriGPU::e1.w carries the determinant floor of the hit definition
 struct Header { char magic[8]; uint32_t version, endian; uint32_t layout[8]; uint64_t payload, checksum, nsections; };
 struct SecHead { uint32_t tag, elem; uint64_t count; };
 static_assert(sizeof(Header) == 72 && sizeof(SecHead) == 16, "cache header layout");
@@ -40,7 +40,7 @@ constexpr size_t kHeaderBytes = 80;            // Header padded to 16
 
 void fill_layout(uint32_t l[8]) {
     l[0] = sizeof(Node8GPU); l[1] = sizeof(TriGPU); l[2] = sizeof(TriShade); l[3] = sizeof(MatGPU);
-    l[4] = sizeof(InstGPU); l[5] = sizeof(LightGPU); l[6] = sizeof(SmallRecPair); l[7] = sizeof(InstHost);
+    l[4] = sizeof(InstGPU); l[5] = sizeof(LightGPU); l[6] = sizeof(SmallRecPair) | (uint32_t)(sizeof(SmallSlabPair) << 16); l[7] = sizeof(InstHost);
 }
 
 // ---- checksum: per-chunk 4-lane word hash, chunks folded in order (so it can be computed by several threads) ----
@@ -95,7 +95,7 @@ struct Writer {
     }
     template <class T> void vec(uint32_t tag, const std::vector<T>& v) { raw(tag, (uint32_t)sizeof(T), v.size(), v.data()); }
 };
-struct Scalars { uint32_t stack8, small_nrec, small_nocc, max_depth, nmesh, has_cam, pad1, pad2; float bvh_pad, small_cm, small_delta, small_hull_margin, total_weight, f0, f1, f2;
+struct Scalars { uint32_t stack8, small_nrec, small_nocc, max_depth, nmesh, has_cam, small_slab_mask, pad2; float bvh_pad, small_cm, small_delta, small_hull_margin, total_weight, f0, f1, f2;
                  float cam[12]; };       // cam: eye, center, up, fovY (degrees), znear, zfar — the host layer's scene camera (Renderer.cpp:46-48, 1730-1731); has_cam = 0 for a context-level save
 
 // ---- reader -------------------------------------------------------------------------------------------------------------------
@@ -118,7 +118,7 @@ struct Reader {
 };
 
 enum : uint32_t { T_SCAL = 1, T_MATS128, T_MATIDS, T_INSTH, T_MESHV, T_MESHI, T_MESHB, T_BMATS, T_NODES8, T_SLOTS8, T_TRIS8, T_LEVELS, T_SMALLR, T_SMALLT, T_SMALLP,
-                T_SHADE, T_BINST, T_LIGHTS, T_LIGHTS80, T_AUXREC, T_AUXTXT };
+                T_SHADE, T_BINST, T_LIGHTS, T_LIGHTS80, T_AUXREC, T_AUXTXT, T_SMALLS, T_SMALLX };
 
 }  // namespace
 
@@ -126,14 +126,14 @@ bool save_scene_cache(const SceneHost& H, const BuiltScene& B, const char* path,
     if (!path || !*path) { err = "scene cache: empty path"; return false; }
     if (H.topo_dirty || H.mats_dirty || B.tris8.size() < B.shade.size() || B.tris8.size() != B.tri_slots8.size() || (!B.tris8.empty() && B.nodes8.empty())) { err = "scene cache: scene not built"; return false; }
     Writer w;
-    Scalars sc{}; sc.stack8 = B.stack8; sc.small_nrec = B.small_nrec; sc.small_nocc = B.small_nocc; sc.max_depth = B.max_depth; sc.nmesh = (uint32_t)H.meshes.size();
+    Scalars sc{}; sc.stack8 = B.stack8; sc.small_nrec = B.small_nrec; sc.small_nocc = B.small_nocc; sc.max_depth = B.max_depth; sc.nmesh = (uint32_t)H.meshes.size(); sc.small_slab_mask = B.small_slab_mask;
     sc.bvh_pad = B.bvh_pad; sc.small_cm = B.small_cm; sc.small_delta = B.small_delta; sc.small_hull_margin = B.small_hull_margin; sc.total_weight = B.total_weight;
     if (cam12) { sc.has_cam = 1; memcpy(sc.cam, cam12, sizeof(sc.cam)); }
     w.raw(T_SCAL, sizeof(Scalars), 1, &sc);
     w.vec(T_MATS128, H.mats128); w.vec(T_MATIDS, H.matids); w.vec(T_INSTH, H.insts);
     for (const MeshHost& m : H.meshes) { w.vec(T_MESHV, m.verts); w.vec(T_MESHI, m.idx); w.raw(T_MESHB, 4, 1, &m.matid_base); }
     w.vec(T_BMATS, B.mats); w.vec(T_NODES8, B.nodes8); w.vec(T_SLOTS8, B.tri_slots8); w.vec(T_TRIS8, B.tris8); w.vec(T_LEVELS, B.level_start8);
-    w.vec(T_SMALLR, B.small_recs); w.vec(T_SMALLT, B.small_tris); w.vec(T_SMALLP, B.small_poly);
+    w.vec(T_SMALLR, B.small_recs); w.vec(T_SMALLT, B.small_tris); w.vec(T_SMALLP, B.small_poly); w.vec(T_SMALLS, B.small_slabs); w.vec(T_SMALLX, B.small_excess);
     w.vec(T_SHADE, B.shade); w.vec(T_BINST, B.insts); w.vec(T_LIGHTS, B.lights); w.vec(T_LIGHTS80, B.lights80);
     const CacheAux none;                                                       // what rides beside the material table in the host layer (MaterialExt, texture names); empty for a context-level save
     const CacheAux& ax = aux ? *aux : none;
@@ -185,7 +185,7 @@ static bool load_scene_cache_impl(const char* path, SceneHost& H, BuiltScene& B,
         memcpy(&m.matid_base, r.p + r.at, 4); r.at += 16;
     }
     if (!r.vec(T_BMATS, Bn.mats) || !r.vec(T_NODES8, Bn.nodes8) || !r.vec(T_SLOTS8, Bn.tri_slots8) || !r.vec(T_TRIS8, Bn.tris8) || !r.vec(T_LEVELS, Bn.level_start8) ||
-        !r.vec(T_SMALLR, Bn.small_recs) || !r.vec(T_SMALLT, Bn.small_tris) || !r.vec(T_SMALLP, Bn.small_poly) || !r.vec(T_SHADE, Bn.shade) || !r.vec(T_BINST, Bn.insts) ||
+        !r.vec(T_SMALLR, Bn.small_recs) || !r.vec(T_SMALLT, Bn.small_tris) || !r.vec(T_SMALLP, Bn.small_poly) || !r.vec(T_SMALLS, Bn.small_slabs) || !r.vec(T_SMALLX, Bn.small_excess) || !r.vec(T_SHADE, Bn.shade) || !r.vec(T_BINST, Bn.insts) ||
         !r.vec(T_LIGHTS, Bn.lights) || !r.vec(T_LIGHTS80, Bn.lights80)) return false;
     CacheAux ax;
     {   // opaque to this layer: fixed-size records + a text blob (the host layer checks their shape against its own structs)
@@ -204,6 +204,7 @@ static bool load_scene_cache_impl(const char* path, SceneHost& H, BuiltScene& B,
     bool ok = nrefs >= nt && Bn.tri_slots8.size() == nrefs && Bn.mats.size() == nmat && Bn.insts.size() == Hn.insts.size() && Bn.lights80.size() == Bn.lights.size() * 20 &&
               Hn.mats128.size() % 32 == 0 && (Bn.nodes8.empty() || Bn.level_start8.size() >= 2) && sc.small_nocc <= sc.small_nrec && sc.small_nrec <= kSmallSceneMaxTris &&
               Bn.small_recs.size() * 2 >= nrec_pad && (sc.small_nrec == 0 || (Bn.small_tris.size() >= nrec_pad * 2 && Bn.small_poly.size() >= nrec_pad * 4)) &&
+              Bn.small_slabs.size() == Bn.small_recs.size() && (nrec_pad >= 64 || (sc.small_slab_mask >> (nrec_pad / 2)) == 0u) &&      // one slab entry per record pair, no kind bit beyond the pairs
               nrefs < (1u << 31);
     for (uint32_t id : Hn.matids) ok = ok && id < nmat;                       // (what rtx_commit_scene checks before a build)
     for (const MeshHost& m : Hn.meshes) {
@@ -252,7 +253,7 @@ static bool load_scene_cache_impl(const char* path, SceneHost& H, BuiltScene& B,
         if (nn) levels.push_back((uint32_t)nn);
         if (stack8 != sc.stack8 || (nn && levels != Bn.level_start8)) { err = "scene cache: stack depth / level table do not match the nodes"; return false; }
     }
-    Bn.stack8 = sc.stack8; Bn.small_nrec = sc.small_nrec; Bn.small_nocc = sc.small_nocc; Bn.max_depth = sc.max_depth; Bn.bvh_pad = sc.bvh_pad;
+    Bn.stack8 = sc.stack8; Bn.small_nrec = sc.small_nrec; Bn.small_nocc = sc.small_nocc; Bn.small_slab_mask = sc.small_slab_mask; Bn.max_depth = sc.max_depth; Bn.bvh_pad = sc.bvh_pad;
     Bn.small_cm = sc.small_cm; Bn.small_delta = sc.small_delta; Bn.small_hull_margin = sc.small_hull_margin; Bn.total_weight = sc.total_weight; Bn.refit_count = 0;
     Bn.any_order = probe_anyhit_order(Bn);                                   // derived, like the stack depth: not taken from the file
     Hn.topo_dirty = false; Hn.mats_dirty = false;

@@ -362,7 +362,7 @@ static uint32_t number_triangle_ranges(SceneHost& H, BuiltScene& B) {
 static void forget_tree(BuiltScene& B, uint32_t nt) {
     B.shade.clear(); B.shade.shrink_to_fit(); B.objtris.clear(); B.objtris.shrink_to_fit();
     B.bvh_pad = 2e-6f; B.nodes.clear(); B.nodes8.clear(); B.tri_slots8.clear(); B.tris8.clear(); B.tris.clear(); B.leaf_order.clear(); B.level_start8.clear();
-    B.small_recs.clear(); B.small_tris.clear(); B.small_poly.clear(); B.small_nrec = 0; B.small_nocc = 0; B.built_tris = nt; B.refit_count = 0; B.any_order = 0;
+    B.small_recs.clear(); B.small_tris.clear(); B.small_poly.clear(); B.small_slabs.clear(); B.small_excess.clear(); B.small_slab_mask = 0; B.small_nrec = 0; B.small_nocc = 0; B.built_tris = nt; B.refit_count = 0; B.any_order = 0;
 }
 
 bool SceneHost::prepare_device_build(BuiltScene& B) {
@@ -479,7 +479,7 @@ bool SceneHost::build(BuiltScene& B) {
     // ... and one with a cut-out triangle (the pre-test path runs no alpha test)
     // ... and one with an active normal map (k_bounce_small perturbs no normal)
     B.maps_active = maps_active(); B.cutouts_active = cutouts_active(); B.normals_active = normals_active(); B.env_active = env.n != 0;
-    if (B.any_hidden || B.maps_active || B.cutouts_active || B.normals_active || B.env_active) { B.small_recs.clear(); B.small_tris.clear(); B.small_poly.clear(); B.small_nrec = 0; B.small_nocc = 0; }
+    if (B.any_hidden || B.maps_active || B.cutouts_active || B.normals_active || B.env_active) { B.small_recs.clear(); B.small_tris.clear(); B.small_poly.clear(); B.small_slabs.clear(); B.small_excess.clear(); B.small_slab_mask = 0; B.small_nrec = 0; B.small_nocc = 0; }
     else build_small_scene(B, wtri, scale);
     sw.lap("tris8 / small scene");
     B.any_order = probe_anyhit_order(B);

@@ -33,6 +33,8 @@ struct BuiltScene {
     // tiny-scene path (only when the scene has <= kSmallSceneMaxTris triangles): pre-test records + their triangles
     std::vector<SmallRecPair> small_recs; std::vector<TriGPU> small_tris; uint32_t small_nrec = 0;
     std::vector<F4> small_poly;       // 4 corners per record (world space; a triangle repeats its last corner)
+    std::vector<SmallSlabPair> small_slabs; uint32_t small_slab_mask = 0;   // slab form of the record pairs, one entry per SmallRecPair; bit kp set = pair kp is a slab pair (RTX_OPT_SMALL_SLABS)
+    std::vector<float> small_excess;  // per record: excess area of its bounding parallelogram over the quad (fraction); -1 = not a quad
     uint32_t small_nocc = 0;          // records [0, small_nocc) can lie between two scene points; [small_nocc, small_nrec) are faces of the scene's convex hull
     float small_cm = 0.0f, small_delta = 0.0f;   // margin coefficient for t, distance tolerance of the edge planes
     float small_hull_margin = 0.0f;              // NEE origins must lie this far inside every hull-face plane to use the hull-face shortcut (TriShade::guard_tau)

@@ -153,6 +153,60 @@ void hull_faces_last(BuiltScene& B, const TriVerts& V, double tol, float scale, 
     recs = occ; recs.insert(recs.end(), hull.begin(), hull.end());
 }
 
+// ---- slab form of a quad record (SmallSlabPair, rtx_types.hpp) ----
+// CONSERVATIVENESS.  The pre-test may only drop a record whose exact test rejects the ray, and the argument for the edge planes is: the exact test accepts only plane points P
+// within r = delta + mt of the polygon (delta: the fixed distance tolerance, mt: the per-ray margin of rtx_traverse.hpp), and ANY half-plane that contains the polygon, moved
+// outward by r, contains every point within r of the polygon.  That argument never uses that the half-plane is an EDGE of the polygon.  A slab lo <= w . P <= hi with
+// lo = min and hi = max of w . v over the corners is two such half-planes (|w| = 1, so r is a distance along w), hence  h + delta - |w . P - c| >= -mt  with c the slab's centre
+// and h its half-width is as conservative as  m . P + c_k + delta >= -mt  for two opposite edges at once.  Two slabs along two adjacent edge normals bound the quad by a
+// parallelogram: the same region for a parallelogram, slightly more (`excess`) for a near-parallelogram — and more only ever forwards more rays to the exact test.  Which
+// records take this form (kSlabTau) is therefore a COST choice, never a correctness condition.
+// Float evaluation: centre and half-width are taken over the corners with the directions and the centre AS ROUNDED TO FLOAT, so the float coefficients bound the polygon exactly;
+// the device's three products, three sums and the final subtraction err by at most 7 x 2^-24 of (sum |w_i P_i| + |c| + h) for P near the polygon, covered by `pad`
+// (2e-6 of that magnitude, 30 x 2^-24), and h is rounded upward.
+constexpr double kSlabTau = 0.02;             // a quad whose bounding parallelogram exceeds its area by more than this keeps its four edge planes
+struct Slab { bool quad = false; double excess = -1.0; float w[2][3] = {{0, 0, 0}, {0, 0, 0}}, c[2] = {0, 0}, h[2] = {-1e30f, -1e30f}; };     // default: never inside (padding record)
+Slab slab_of_quad(const Rec& R, double delta) {
+    Slab S;
+    if (R.s1 < 0) return S;                                   // a single triangle (or a zero-area one): no slab form
+    D3 p[4]; for (int k = 0; k < 4; k++) p[k] = D3{R.pv[k][0], R.pv[k][1], R.pv[k][2]};
+    const D3 nu{R.pl[0], R.pl[1], R.pl[2]};
+    const double area = 0.5 * fabs(dt(crs(sub(p[2], p[0]), sub(p[3], p[1])), nu));
+    if (!(area > 0.0)) return S;
+    int best_k = -1; double best = 0.0;
+    for (int k = 0; k < 4; k++) {                             // the bounding parallelogram along each pair of ADJACENT edge normals: the smallest one
+        double width[2];
+        for (int s = 0; s < 2; s++) {
+            const double* m = R.e[(k + s) & 3];
+            double lo = 1e300, hi = -1e300;
+            for (int v = 0; v < 4; v++) { const double q = m[0] * p[v].x + m[1] * p[v].y + m[2] * p[v].z; lo = std::min(lo, q); hi = std::max(hi, q); }
+            width[s] = hi - lo;
+        }
+        const double* m0 = R.e[k]; const double* m1 = R.e[(k + 1) & 3];
+        const double sn = fabs(dt(crs(D3{m0[0], m0[1], m0[2]}, D3{m1[0], m1[1], m1[2]}), nu));
+        if (!(sn > 1e-9)) continue;
+        const double ex = width[0] * width[1] / sn / area - 1.0;
+        if (best_k < 0 || ex < best) { best_k = k; best = ex; }
+    }
+    if (best_k < 0) return S;
+    S.quad = true; S.excess = std::max(best, 0.0);
+    for (int s = 0; s < 2; s++) {
+        const double* m = R.e[(best_k + s) & 3];
+        for (int a = 0; a < 3; a++) S.w[s][a] = (float)m[a];
+        double lo = 1e300, hi = -1e300, mag = 0.0;
+        for (int v = 0; v < 4; v++) {
+            const double q = (double)S.w[s][0] * p[v].x + (double)S.w[s][1] * p[v].y + (double)S.w[s][2] * p[v].z;
+            lo = std::min(lo, q); hi = std::max(hi, q);
+            mag = std::max(mag, fabs((double)S.w[s][0] * p[v].x) + fabs((double)S.w[s][1] * p[v].y) + fabs((double)S.w[s][2] * p[v].z));
+        }
+        S.c[s] = (float)(0.5 * (lo + hi));
+        const double half = std::max(hi - (double)S.c[s], (double)S.c[s] - lo);          // about the ROUNDED centre
+        const double pad = 2e-6 * (mag + fabs((double)S.c[s]) + half + delta);
+        S.h[s] = std::nextafterf((float)(half + delta + pad), INFINITY);
+    }
+    return S;
+}
+
 // the device form of the records: their triangles, their polygon corners, and the plane / edge coefficients two records to a SmallRecPair
 void pack_records(BuiltScene& B, const std::vector<Rec>& recs, double delta) {
     B.small_nrec = (uint32_t)recs.size();
@@ -175,13 +229,26 @@ void pack_records(BuiltScene& B, const std::vector<Rec>& recs, double delta) {
         }
         B.small_recs.push_back(P);
     }
+    // the slab table: a pair is a slab pair when BOTH its records are quads within kSlabTau (the padding record of an odd count qualifies: its slabs are never inside)
+    B.small_excess.assign(recs.size(), -1.0f);
+    for (size_t r = 0; r < recs.size(); r += 2) {
+        SmallSlabPair Q; bool both = true;
+        for (int e = 0; e < 2; e++) {
+            const bool have = r + e < recs.size();
+            const Slab S = have ? slab_of_quad(recs[r + e], delta) : Slab{};
+            if (have) { B.small_excess[r + e] = (float)S.excess; both = both && S.quad && S.excess <= kSlabTau; }
+            for (int s = 0; s < 2; s++) { for (int a = 0; a < 3; a++) Q.r[5 * s + a][e] = S.w[s][a]; Q.r[5 * s + 3][e] = S.c[s]; Q.r[5 * s + 4][e] = S.h[s]; }
+        }
+        if (both) B.small_slab_mask |= 1u << (r / 2);
+        B.small_slabs.push_back(Q);
+    }
 }
 }  // namespace
 
 // ---- tiny scenes: merge triangles into planar convex quads and build the conservative pre-test records ----
 void build_small_scene(BuiltScene& B, const std::vector<float>& wtri, float scale) {
     const std::vector<uint32_t>& leaf_order = B.leaf_order;
-    B.small_recs.clear(); B.small_tris.clear(); B.small_poly.clear(); B.small_nrec = 0; B.small_nocc = 0;
+    B.small_recs.clear(); B.small_tris.clear(); B.small_poly.clear(); B.small_slabs.clear(); B.small_excess.clear(); B.small_slab_mask = 0; B.small_nrec = 0; B.small_nocc = 0;
     if (leaf_order.empty() || leaf_order.size() > kSmallSceneMaxTris) return;
     const double delta = 2e-5 * (double)scale, tol = 1e-6 * (double)scale;
     B.small_delta = (float)delta; B.small_cm = 4e-6f * scale; B.small_hull_margin = 2e-6f * scale;     // how far inside every hull plane an NEE origin must lie (20 x the float error of a hit position)

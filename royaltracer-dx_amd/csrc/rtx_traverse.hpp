@@ -54,6 +54,12 @@ __device__ __forceinline__ float margin_t(float cm, float ind, float t) {
     asm("v_fma_f32 %0, |%1|, %2, %3" : "=v"(r) : "v"(ind), "s"(cm), "v"(a));
     return r;
 }
+// h - |a|, the slack of a slab |a| <= h: one v_sub_f32 with the half-width from an SGPR and |x| as a source modifier (plain C++ here: the compiler folds the modifier into an
+// unpacked subtract, and knows the result canonical, so the min that follows needs no v_max x, x)
+__device__ __forceinline__ float slab_slack(float h, float a) { return h - fabsf(a); }
+// the slab table is read through the constant address space: behind a pointer that is a MEMBER of the scene descriptor the compiler cannot prove the table unwritten by the
+// kernel's own stores and fetches it with per-lane global loads (16 VGPRs); constant-space loads at a wave-uniform address are scalar loads, like those of the records
+typedef const __attribute__((address_space(4))) f2v const_f2v;
 typedef uint32_t v2u __attribute__((ext_vector_type(2)));
 typedef uint32_t v4u __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) v2u lds_u2;
@@ -327,7 +333,13 @@ __device__ __forceinline__ void traverse(const DevScene& sc, const TraceLds& L, 
 // brute force: phase 1 only removes triangles that the exact test would reject (tolerances: the edge-plane distance
 // delta and the t margin, built in rtx_small_scene.cpp).
 
-template <bool ANY>
+// SLAB PAIRS (sc.small_slab_mask, wave-uniform per pair): both records are (near-)parallelograms, and the four edge slacks of each are replaced by the slacks of the two slabs
+// that bound it, h - |w . P - c| (SmallSlabPair; the proof that a slab is as conservative as an edge plane is where the table is built, rtx_small_scene.cpp).  8 packed and 4
+// unpacked instructions and one min per record instead of 16 packed and two; 28 scalar dwords per pair instead of 40.
+// OPEN (closest-hit callers whose tmax is kTMax, or 0 for a lane without a ray): the far-end slack (tmax + mt) - t is dropped.  With tmax = kTMax it can reject no finite t that the
+// exact test accepts, and a lane with tmax = 0 gets its candidate word cleared after the loops instead (its exact tests could only miss: t < 0 is no hit).  An infinite or NaN t
+// arises only from nd == 0 — |no| is bounded by the scene's size and |ind| by 1e3 wherever |nd| >= 1e-3 — and that is below the grazing bound, so the record is forwarded as before.
+template <bool ANY, bool OPEN = false>
 __device__ __forceinline__ void traverse_small(const DevScene& sc, const SmallRecPair* __restrict__ sp, const TraceLds& L, f3 o, f3 d, float tmin, float tmax,
                                                float& bt, float& bu, float& bv, uint32_t& bprim, uint32_t nrec, unsigned long long keep = ~0ull, Prof* pf = nullptr, int pf_sec = 0) {
     // keep (wave-uniform): bit r clear = no ray of this wave can touch record r (primary-ray packet culling); nrec = sc.nsmall, or sc.nsmall_occ for NEE shadow segments (both end points inside the scene's convex hull: the records
@@ -338,6 +350,7 @@ __device__ __forceinline__ void traverse_small(const DevScene& sc, const SmallRe
     const f2v dx = splat2(d.x), dy = splat2(d.y), dz = splat2(d.z), ox = splat2(o.x), oy = splat2(o.y), oz = splat2(o.z);
     const f2v vtmin = splat2(tmin), vtmax = splat2(tmax);
     const float cm = sc.small_cm;
+    const uint32_t slabs = sc.small_slab_mask;
     // One record pair.  Instruction budget (the loop is the hottest code of the tiny-scene kernels, ~48 VALU per pair): the edge
     // constants are ADDED from SGPRs after the three FMAs (a VOP3P instruction takes one scalar operand, so an FMA addend from
     // SGPRs costs two v_mov), |x| rides on source modifiers of unpacked instructions, six slacks reduce through two min3 + one
@@ -350,19 +363,28 @@ __device__ __forceinline__ void traverse_small(const DevScene& sc, const SmallRe
         f2v ind; ind.x = __builtin_amdgcn_rcpf(nd.x); ind.y = __builtin_amdgcn_rcpf(nd.y);
         const f2v t = no * ind;
         const f2v px = fma2(t, dx, ox), py = fma2(t, dy, oy), pz = fma2(t, dz, oz);
-        const f2v e0 = fma2(R[6], pz, fma2(R[5], py, R[4] * px)) + R[7];
-        const f2v e1 = fma2(R[10], pz, fma2(R[9], py, R[8] * px)) + R[11];
-        const f2v e2 = fma2(R[14], pz, fma2(R[13], py, R[12] * px)) + R[15];
-        const f2v e3 = fma2(R[18], pz, fma2(R[17], py, R[16] * px)) + R[19];
         f2v mt; mt.x = margin_t(cm, ind.x, t.x); mt.y = margin_t(cm, ind.y, t.y);
+        float me0, me1;                                    // the smallest in-plane slack of each record
+        if ((slabs >> kp) & 1u) {                          // wave-uniform: a slab pair
+            const const_f2v* S = (const const_f2v*)sc.small_slabs[kp].r;
+            const f2v a = fma2(S[2], pz, fma2(S[1], py, S[0] * px)) - S[3];
+            const f2v b = fma2(S[7], pz, fma2(S[6], py, S[5] * px)) - S[8];
+            me0 = fminf(slab_slack(S[4].x, a.x), slab_slack(S[9].x, b.x)); me1 = fminf(slab_slack(S[4].y, a.y), slab_slack(S[9].y, b.y));
+        } else {
+            const f2v e0 = fma2(R[6], pz, fma2(R[5], py, R[4] * px)) + R[7];
+            const f2v e1 = fma2(R[10], pz, fma2(R[9], py, R[8] * px)) + R[11];
+            const f2v e2 = fma2(R[14], pz, fma2(R[13], py, R[12] * px)) + R[15];
+            const f2v e3 = fma2(R[18], pz, fma2(R[17], py, R[16] * px)) + R[19];
+            me0 = fminf(e0.x, fminf(fminf(e1.x, e2.x), e3.x)); me1 = fminf(e0.y, fminf(fminf(e1.y, e2.y), e3.y));
+        }
         // all slack values must be >= 0: t in [tmin - mt, tmax + mt] and P within delta of the inside of every edge (e_k carries + delta)
         // (the distance tolerance delta of the edge planes is folded into their constants at build time: e_k >= 0 means "within delta")
         // The EDGE slacks get the margin mt as well (e_k >= -mt): the exact test's barycentrics carry an in-plane error of about
         // eps * scale / |n.d|, which for a ray a few milliradians off the plane exceeds the fixed tolerance delta folded into e_k (a shadow ray
         // at |n.d| = 1.1e-3 past the edge of a lamp flush with a wall: accepted by the float test 1e-4 outside, 1 pixel in 5000 random scenes).
-        const f2v a0 = (t + mt) - vtmin, a1 = (vtmax + mt) - t;
-        const float ma0 = fminf(a0.x, a1.x), ma1 = fminf(a0.y, a1.y);
-        const float me0 = fminf(e0.x, fminf(fminf(e1.x, e2.x), e3.x)), me1 = fminf(e0.y, fminf(fminf(e1.y, e2.y), e3.y));
+        const f2v a0 = (t + mt) - vtmin;
+        float ma0 = a0.x, ma1 = a0.y;
+        if (!OPEN) { const f2v a1 = (vtmax + mt) - t; ma0 = fminf(a0.x, a1.x); ma1 = fminf(a0.y, a1.y); }
         const unsigned long long c0 = (__builtin_amdgcn_ballot_w64(ma0 >= 0.0f) & __builtin_amdgcn_ballot_w64(me0 >= -mt.x)) | __builtin_amdgcn_ballot_w64(fabsf(nd.x) < 1e-3f);   // grazing rays always go to the exact test
         const unsigned long long c1 = (__builtin_amdgcn_ballot_w64(ma1 >= 0.0f) & __builtin_amdgcn_ballot_w64(me1 >= -mt.y)) | __builtin_amdgcn_ballot_w64(fabsf(nd.y) < 1e-3f);
         acc = shift_in(shift_in(acc, c1), c0);                        // records run downwards, so record r ends up at bit r (mod 32)
@@ -385,6 +407,7 @@ __device__ __forceinline__ void traverse_small(const DevScene& sc, const SmallRe
     }
     RTX_PROF_MARK(pf, pf_sec);
     unsigned long long cand = ((unsigned long long)cand_hi << 32) | cand_lo;
+    if (OPEN && !(tmax > 0.0f)) cand = 0ull;             // a lane without a ray (the far-end slack that used to reject its records is not computed)
     // bits >= nrec: the padding record of an odd count (zero plane: "grazing", always forwarded) or, for NEE segments, the first hull face
     cand &= nrec >= 64u ? ~0ull : ((1ull << nrec) - 1ull);
     // (Testing only the triangle on the ray's side of a quad's diagonal would save one exact test per candidate; measured slower

@@ -44,6 +44,11 @@ struct alignas(16) TriGPU { F4 v0, e1, e2; };
 // Record r owns triangles 2r and 2r+1 of `small_tris` (a missing partner is a zero-area triangle).
 struct alignas(16) SmallRecPair { float r[20][2]; };
 static_assert(sizeof(SmallRecPair) == 160, "SmallRecPair must be 160 bytes");
+// Slab form of a record pair (rtx_small_scene.cpp: slab_of_quad): a convex quad lies inside two in-plane slabs |w . P - c| <= h — for a parallelogram exactly, for a
+// near-parallelogram with a little excess area — so two centred coordinates per record stand in for its four edge planes.  A table of its own beside the records, one entry per
+// pair, rows: 0-2 w1 | 3 c1 | 4 h1 | 5-7 w2 | 8 c2 | 9 h2.  Only the pairs whose bit is set in BuiltScene::small_slab_mask (both records near-parallelograms) are read that way.
+struct alignas(16) SmallSlabPair { float r[10][2]; };
+static_assert(sizeof(SmallSlabPair) == 80, "SmallSlabPair must be 80 bytes");
 constexpr uint32_t kSmallSceneMaxTris = 64;
 
 // What ClosestHit (Hit_v6.hlsl:12-61) needs about a triangle, pre-gathered per GLOBAL triangle id:

@@ -374,6 +374,18 @@ int rtxh_scene_small_records(const rtxh_scene* sc, float* recs20, int32_t* tri_i
     }
     return RTX_OK;
 }
+// ... and their slab form (csrc/rtx_small_scene.cpp: slab_of_quad)
+int rtxh_scene_small_slabs(const rtxh_scene* sc, float* slabs10, float* excess, uint32_t max_recs, uint32_t* nrec_out, uint32_t* pair_mask_out) {
+    rtx::BuiltScene B;
+    if (!slabs10 || !excess || !build_for_inspection(sc, B)) return RTX_ERR_INVALID;
+    if (nrec_out) *nrec_out = B.small_nrec;
+    if (pair_mask_out) *pair_mask_out = B.small_slab_mask;
+    for (uint32_t r = 0; r < B.small_nrec && r < max_recs; r++) {
+        for (int row = 0; row < 10; row++) slabs10[(size_t)r * 10 + row] = B.small_slabs[r / 2].r[row][r & 1];
+        excess[r] = B.small_excess[r];
+    }
+    return RTX_OK;
+}
 
 rtxh_renderer* rtxh_renderer_create(uint32_t w, uint32_t h, const char* name, int device) {
     rtxh_renderer* r = new rtxh_renderer(); r->r = new Renderer(w, h, name ? name : "rtx"); r->r->SetDevice(device); return r;
