@@ -62,7 +62,7 @@ template <bool COMPACT>
 __device__ __forceinline__ void continue_path(const MatGPU& m, const DevFrame& f, const DevPaths& p, uint32_t bounce, bool go, PathState& S, f3 pos, f3 normal, f3 outgoing, float eta_p,
                                               uint32_t* s_cnt0, uint32_t* mynext, uint32_t out0, Prof* pf) {
     bool alive = false;
-    f3 smp = mk3(0, 0, 1); float P = 0.0f;
+    f3 smp; float P;                                              // no initialiser: read under `alive` only, and bsdf_continue assigns both before it returns true
     if (go) { PF_COUNT(9); alive = bsdf_continue(m, f, bounce, S, normal, outgoing, smp, P, eta_p); }
     if (!COMPACT && alive) { PF_COUNT(10); store_path(p, S, pos, smp, P); }
     const uint32_t slot = block_push(alive, s_cnt0);

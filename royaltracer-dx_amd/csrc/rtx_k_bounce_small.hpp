@@ -28,9 +28,10 @@ __device__ __forceinline__ bool block_shadow(const DevScene& sc, const SmallRecP
     const uint32_t ns = sh.n[par];
     if ((threadIdx.x & ~63u) < ns) {                                   // wave-uniform: this wave has rays to trace
         const bool mine = threadIdx.x < ns;
-        const F4 ro = mine ? sh.o[threadIdx.x] : F4{0, 0, 0, 0}, rd = mine ? sh.d[threadIdx.x] : F4{0, 0, 1, 0};
+        F4 ro = unspecified4(), rd = unspecified4();            // a lane beyond the rays: any ray, with an empty interval (its candidates are cleared) and no say in the record count
+        if (mine) { ro = sh.o[threadIdx.x]; rd = sh.d[threadIdx.x]; }
         float st_, su_, sv_; uint32_t sprim;
-        traverse_small<true>(sc, small, L, mk3(ro.x, ro.y, ro.z), mk3(rd.x, rd.y, rd.z), fabsf(ro.w), mine ? rd.w : 0.0f, st_, su_, sv_, sprim, shadow_records(sc, mine, ro.w), ~0ull, pf, 6);
+        traverse_small<true, false, true>(sc, small, L, mk3(ro.x, ro.y, ro.z), mk3(rd.x, rd.y, rd.z), fabsf(ro.w), mine ? rd.w : 0.0f, st_, su_, sv_, sprim, shadow_records(sc, mine, ro.w), ~0ull, pf, 6);
         if (mine) sh.occ[threadIdx.x] = sprim != kMissPrim ? 1 : 0;
     }
     PF_MARK(7);
@@ -61,7 +62,7 @@ __device__ __forceinline__ void shade_block(const DevScene& sc, const SmallRecPa
     PF_MARK(3);
     for (uint32_t j = 0; j < nee; j++) {
         bool push = false;
-        F4 so = {0, 0, 0, 0}, sd = {0, 0, 1, 0}; f3 con = mk3(0, 0, 0);
+        F4 so, sd; f3 con;                                         // no initialiser: every read is under `push` (block_shadow returns push && ...), and nee_sample assigns all three before it returns true
         if (shading) { PF_COUNT(4); push = nee_sample(sc, *mp, f.flags, nee, S, pos, normal, outgoing, so, sd, con, sf.near_hull, eta_p, nullptr, T.cdf, T.lights); }
         PF_MARK(4);
         if (block_shadow(sc, small, L, sh, par, push, so, sd, &s_cnt[1 + j], pf)) {
@@ -104,8 +105,8 @@ __device__ __forceinline__ void bounce_small_first(const DevScene& sc, const Sma
         uint32_t* mynext = ((bounce & 1u) ? queue_a : queue_b) + qb;
         for (uint32_t base = 0; base < n; base += kBlock) {       // one trip per 256 queue entries
             PF_MARK(0);
-            PathState S = idle_path(); Surf sf = idle_surf();            // the lane's item: path, surface, hit
-            float t = 0.0f, u = 0.0f, v = 0.0f; uint32_t prim = kMissPrim;
+            PathState S = unspecified_path(); Surf sf = unspecified_surf();            // the lane's item: path, surface, hit (prim marks a lane without one: the rest is read beside a real prim only)
+            float t = unspecified<float>(), u = unspecified<float>(), v = unspecified<float>(); uint32_t prim = kMissPrim;
             const uint32_t i = base + threadIdx.x;
             const bool active = i < n;
             if constexpr (HAVE_HIT == 2) {
@@ -161,8 +162,8 @@ __device__ __forceinline__ void bounce_small_block(const DevScene& sc, const Sma
         if constexpr (!RING) {
             for (uint32_t base = 0; base < n; base += kBlock) {   // one trip per 256 queue entries: lanes whose ray missed idle through the shading
                 PF_MARK(0);
-                PathState S = idle_path(); Surf sf = idle_surf();            // the lane's item: path, surface, hit
-                float t = 0.0f, u = 0.0f, v = 0.0f; uint32_t prim = kMissPrim;
+                PathState S = unspecified_path(); Surf sf = unspecified_surf();            // the lane's item: path, surface, hit (prim marks a lane without one: the rest is read beside a real prim only)
+                float t = unspecified<float>(), u = unspecified<float>(), v = unspecified<float>(); uint32_t prim = kMissPrim;
                 const uint32_t i = base + threadIdx.x;
                 const bool active = i < n;
                 if (active) S = load_path(p, myq[i]);
@@ -194,13 +195,13 @@ __device__ __forceinline__ void bounce_small_block(const DevScene& sc, const Sma
             uint32_t prod = 0, rk = 0;                              // hits pushed by the completed trace passes of this bounce; pass number mod 3 (both uniform)
             for (;;) {                                              // one trip per 256 ring entries, until input and ring are empty
                 PF_MARK(0);
-                PathState S = idle_path(); Surf sf = idle_surf();            // the lane's item: path, surface, hit
-                float t = 0.0f, u = 0.0f, v = 0.0f; uint32_t prim = kMissPrim;
+                PathState S = unspecified_path(); Surf sf = unspecified_surf();            // the lane's item: path, surface, hit (prim marks a lane without one: the rest is read beside a real prim only)
+                float t = unspecified<float>(), u = unspecified<float>(), v = unspecified<float>(); uint32_t prim = kMissPrim;
                 // ---- trace phase: fill the ring until it holds a full workgroup of hits (or the input runs out) ----
                 while (next_in < n && prod - s_ring[0] < kBlock) {                // uniform: `prod` is a register, s_ring[0] was written before the last barrier
                     const uint32_t i = next_in + threadIdx.x;
                     const bool act = i < n;
-                    uint32_t pid = 0; f3 ro = mk3(0, 0, 0), rd = mk3(0, 0, 1);
+                    uint32_t pid = unspecified<uint32_t>(); f3 ro = unspecified3(), rd = unspecified3();      // a lane without an entry: pid is read under `hit` only, its ray has tmax = 0
                     if (act) { pid = myq[i]; const F4 a = p.ray_o[pid], b = p.ray_d[pid]; ro = mk3(a.x, a.y, a.z); rd = mk3(b.x, b.y, b.z); }
                     float ht, hu, hv; uint32_t hp;
                     traverse_small<false, true>(sc, small, L, ro, rd, tmin, act ? kTMax : 0.0f, ht, hu, hv, hp, sc.nsmall, ~0ull, pf, 1);   // inactive lanes: empty interval

@@ -80,9 +80,10 @@ __device__ __forceinline__ void bounce_small_wave(const DevScene& sc, const Smal
             wave_lds_sync();                                        // the pushes are visible to the lanes that trace them
             const bool mine = lane < k;
             const uint32_t e = lane;
-            const F4 ro = mine ? sho[e] : F4{0, 0, 0, 0}, rd = mine ? shd[e] : F4{0, 0, 1, 0};
+            F4 ro = unspecified4(), rd = unspecified4();         // a lane beyond the block: any ray, with an empty interval (its candidates are cleared) and no say in the record count
+            if (mine) { ro = sho[e]; rd = shd[e]; }
             float st_, su_, sv_; uint32_t sprim;
-            traverse_small<true>(sc, small, L, mk3(ro.x, ro.y, ro.z), mk3(rd.x, rd.y, rd.z), fabsf(ro.w), mine ? rd.w : 0.0f, st_, su_, sv_, sprim, shadow_records(sc, mine, ro.w), ~0ull, pf, 6);
+            traverse_small<true, false, true>(sc, small, L, mk3(ro.x, ro.y, ro.z), mk3(rd.x, rd.y, rd.z), fabsf(ro.w), mine ? rd.w : 0.0f, st_, su_, sv_, sprim, shadow_records(sc, mine, ro.w), ~0ull, pf, 6);
             if (mine && sprim == kMissPrim) {
                 const F4 c = shc[e];
                 const uint32_t pid = f2u(c.w);
@@ -97,7 +98,8 @@ __device__ __forceinline__ void bounce_small_wave(const DevScene& sc, const Smal
             PF_MARK(0);
             // ---- trace phase: trace input chunks until this wave has a full wave of hits (or the input runs out) ----
             bool full = false, carry = false;                        // full (uniform): the last pass took the count to 64 or more; carry: this lane's hit of that pass is beyond slot 63
-            uint32_t cpid = 0, cprim = kMissPrim, ce = 0, hnext = 0; float ct = 0.0f, cu = 0.0f, cv = 0.0f;
+            // the carried hit is read under `carry` only, and a pass that sets carry writes all six
+            uint32_t cpid = unspecified<uint32_t>(), cprim = unspecified<uint32_t>(), ce = unspecified<uint32_t>(), hnext = 0; float ct = unspecified<float>(), cu = unspecified<float>(), cv = unspecified<float>();
             while (!in_done && !full) {
                 uint32_t c0 = 0;
                 if (lane == 0) c0 = atomicAdd(&s_in, 64u);
@@ -105,7 +107,7 @@ __device__ __forceinline__ void bounce_small_wave(const DevScene& sc, const Smal
                 if (c0 >= n) { in_done = true; break; }
                 const uint32_t i = c0 + lane;
                 const bool act = i < n;
-                uint32_t pid = 0; f3 ro = mk3(0, 0, 0), rd = mk3(0, 0, 1);      // pid: what the hit buffer carries — the path id, or (COMPACT) the entry's place in the queue
+                uint32_t pid = unspecified<uint32_t>(); f3 ro = unspecified3(), rd = unspecified3();      // pid: what the hit buffer carries — the path id, or (COMPACT) the entry's place in the queue; a lane without an entry: read under `hit` only, its ray has tmax = 0
                 if (act) { pid = COMPACT ? i : myq[i]; const uint32_t src = COMPACT ? in0 + i : pid; const F4 a = p.ray_o[src], b = p.ray_d[src]; ro = mk3(a.x, a.y, a.z); rd = mk3(b.x, b.y, b.z); }
                 float ht, hu, hv; uint32_t hp;
                 traverse_small<false, true>(sc, small, L, ro, rd, tmin, act ? kTMax : 0.0f, ht, hu, hv, hp, sc.nsmall, ~0ull, pf, 1);   // inactive lanes: empty interval
@@ -120,8 +122,8 @@ __device__ __forceinline__ void bounce_small_wave(const DevScene& sc, const Smal
             const uint32_t take = full ? 64u : hcnt;
             if (take == 0u) break;                                  // input exhausted and buffer drained: this wave is done with the bounce
             const bool active = lane < take;
-            PathState S = idle_path();
-            float t = 0.0f, u = 0.0f, v = 0.0f; uint32_t prim = kMissPrim;
+            PathState S = unspecified_path();
+            float t = unspecified<float>(), u = unspecified<float>(), v = unspecified<float>(); uint32_t prim = kMissPrim;      // prim marks the lane idle; the rest is read beside a real prim only
             wave_lds_sync();                                        // the pushes above are visible to the lanes that pop them
             if (active) {
                 const uint32_t e = hpid[lane];
@@ -134,7 +136,7 @@ __device__ __forceinline__ void bounce_small_wave(const DevScene& sc, const Smal
             hcnt = full ? hnext : 0u;
             PF_MARK(2);
             // ---- shading: the steps of shade_block (rtx_k_bounce_small.hpp), the shadow rays into this wave's buffer ----
-            Surf sf = idle_surf();
+            Surf sf = unspecified_surf();
             bool shading = false;
             if (active && prim != kMissPrim) { PF_COUNT(3); shading = hit_to_shading<0>(sc, p, T.mats, S, sf, t, u, v, prim, bounce, nee); }
             const f3 outgoing = -S.d, pos = sf.pos;
@@ -144,7 +146,7 @@ __device__ __forceinline__ void bounce_small_wave(const DevScene& sc, const Smal
             PF_MARK(3);
             for (uint32_t j = 0; j < nee; j++) {
                 bool push = false;
-                F4 so = {0, 0, 0, 0}, sd = {0, 0, 1, 0}; f3 con = mk3(0, 0, 0);
+                F4 so, sd; f3 con;                                 // no initialiser: every read is under `push`, and nee_sample assigns all three before it returns true
                 if (shading) { PF_COUNT(4); push = nee_sample(sc, *mp, f.flags, nee, S, pos, normal, outgoing, so, sd, con, sf.near_hull, eta_p, nullptr, T.cdf, T.lights); }
                 PF_MARK(4);
                 const unsigned long long pmask = __ballot(push);

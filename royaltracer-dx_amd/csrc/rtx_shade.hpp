@@ -28,8 +28,19 @@ __device__ __forceinline__ Surf surface(const DevScene& sc, f3 o, f3 d, float t,
     s.normal = normalize(xform_dir(sc.insts[s.inst].nrm, n));                 // :56
     return s;
 }
+// UNSPECIFIED VALUES.  A lane without an item runs through wave-uniform code (the pre-test loop, ballots, compactions) beside the lanes that have one, so its variables must hold
+// SOME value, but no result depends on which.  A constant initialiser costs a v_mov per register in front of the exec-masked loads that fill the other lanes;
+// unspecified<T>() (T of 32 bits) is "whatever the register holds": a fixed, arbitrary bit pattern, possibly a NaN, and not undefined behaviour.  Arithmetic on it is harmless;
+// anything that steers control flow or an address — a loop bound, an index, a ballot that is counted — must not read it unguarded.
+// An empty asm statement that defines a VGPR, not __builtin_nondeterministic_value: the optimiser folds that builtin (a freeze of undef) to the constant 0 wherever it meets a
+// phi, which is the v_mov this is meant to remove; volatile keeps the definition where it is written (hoisted out of a loop it would hold a register across it).
+template <class T> __device__ __forceinline__ T unspecified() { static_assert(sizeof(T) == 4, "one VGPR"); T x; asm volatile("; unspecified %0" : "=v"(x)); return x; }
+__device__ __forceinline__ F4 unspecified4() { return F4{unspecified<float>(), unspecified<float>(), unspecified<float>(), unspecified<float>()}; }
+__device__ __forceinline__ f3 unspecified3() { return mk3(unspecified<float>(), unspecified<float>(), unspecified<float>()); }
 // the surface of a lane without a hit: what the code after the hit test may read of it
 __device__ __forceinline__ Surf idle_surf() { Surf sf; sf.mat = 0; sf.normal = mk3(0, 0, 1); sf.pos = mk3(0, 0, 0); return sf; }
+// the same for the fused tiny-scene kernels, which read mat only under `shading`; pos and normal flow into arithmetic whose results are used under `shading`
+__device__ __forceinline__ Surf unspecified_surf() { Surf sf; sf.mat = unspecified<uint32_t>(); sf.normal = unspecified3(); sf.pos = unspecified3(); return sf; }
 
 // ---------------------------------------------------------------------------------------------
 // shading building blocks.  Loop body of RayGen.hlsl:99-133 + Hit.hlsl:126-174,340-369 with the v6 leaf math,
@@ -45,6 +56,12 @@ struct PathState { uint32_t pid; f3 o, d; float prev_pdf; f3 thr; uint32_t s0, s
 
 // the path state of a lane without an item: it runs through the shading code with every branch off
 __device__ __forceinline__ PathState idle_path() { PathState S; S.pid = 0; S.o = mk3(0, 0, 0); S.d = mk3(0, 0, 1); S.thr = mk3(0, 0, 0); S.prev_pdf = 1.0f; S.s0 = S.s1 = 0; return S; }
+// the same for the fused tiny-scene kernels: `active`, `shading`, `push` and `alive` are false in such a lane and guard every store, index and counted ballot, so every member is
+// unspecified; o and d may be traced, with an empty interval (tmax = 0: traverse_small clears the lane's candidates)
+__device__ __forceinline__ PathState unspecified_path() {
+    PathState S; S.pid = unspecified<uint32_t>(); S.o = unspecified3(); S.d = unspecified3(); S.thr = unspecified3(); S.prev_pdf = unspecified<float>();
+    S.s0 = unspecified<uint32_t>(); S.s1 = unspecified<uint32_t>(); return S;
+}
 
 // RTX_FLAG_LAMBERT_ONLY is a launch constant, so k_shade / k_shade_dense / k_bounce_small take it as a template parameter: bit 0 of the flags their code sees is known at compile time
 template <bool LAMBERT>

@@ -339,7 +339,9 @@ __device__ __forceinline__ void traverse(const DevScene& sc, const TraceLds& L, 
 // OPEN (closest-hit callers whose tmax is kTMax, or 0 for a lane without a ray): the far-end slack (tmax + mt) - t is dropped.  With tmax = kTMax it can reject no finite t that the
 // exact test accepts, and a lane with tmax = 0 gets its candidate word cleared after the loops instead (its exact tests could only miss: t < 0 is no hit).  An infinite or NaN t
 // arises only from nd == 0 — |no| is bounded by the scene's size and |ind| by 1e3 wherever |nd| >= 1e-3 — and that is below the grazing bound, so the record is forwarded as before.
-template <bool ANY, bool OPEN = false>
+// RAYLESS (OPEN implies it; the shadow blocks of the fused kernels ask for it): a lane with tmax <= 0 has no ray, whatever its origin and direction hold — they may be
+// unspecified (rtx_shade.hpp) — and gets its candidate word cleared after the loops, so it never enters the exact tests (t > tmin >= 0 and t < tmax <= 0 cannot both hold).
+template <bool ANY, bool OPEN = false, bool RAYLESS = OPEN>
 __device__ __forceinline__ void traverse_small(const DevScene& sc, const SmallRecPair* __restrict__ sp, const TraceLds& L, f3 o, f3 d, float tmin, float tmax,
                                                float& bt, float& bu, float& bv, uint32_t& bprim, uint32_t nrec, unsigned long long keep = ~0ull, Prof* pf = nullptr, int pf_sec = 0) {
     // keep (wave-uniform): bit r clear = no ray of this wave can touch record r (primary-ray packet culling); nrec = sc.nsmall, or sc.nsmall_occ for NEE shadow segments (both end points inside the scene's convex hull: the records
@@ -407,7 +409,7 @@ __device__ __forceinline__ void traverse_small(const DevScene& sc, const SmallRe
     }
     RTX_PROF_MARK(pf, pf_sec);
     unsigned long long cand = ((unsigned long long)cand_hi << 32) | cand_lo;
-    if (OPEN && !(tmax > 0.0f)) cand = 0ull;             // a lane without a ray (the far-end slack that used to reject its records is not computed)
+    if ((OPEN || RAYLESS) && !(tmax > 0.0f)) cand = 0ull;      // a lane without a ray (OPEN: the far-end slack that used to reject its records is not computed)
     // bits >= nrec: the padding record of an odd count (zero plane: "grazing", always forwarded) or, for NEE segments, the first hull face
     cand &= nrec >= 64u ? ~0ull : ((1ull << nrec) - 1ull);
     // (Testing only the triangle on the ray's side of a quad's diagonal would save one exact test per candidate; measured slower
