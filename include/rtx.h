@@ -264,7 +264,7 @@ int  rtx_update_mesh_vertices(rtx_ctx*, uint32_t mesh, const void* verts28, uint
    KdPi' replaces the material's Kd / PI wherever the shading reads the diffuse colour at that hit: the Lambert term of the mixture BSDF, for the NEE samples and for the
    continuation.  Everything else stays the material's: Ks, Ke, Pr, Pm, dissolve, the light list, the strategy probabilities, the random-number sequence.  An emissive
    material's map has no effect (emitters are not shaded).  CONSEQUENCE: a scene in which every textured triangle sees one value tl is, bit for bit, the untextured scene
-   whose triangles carry materials with Kd = Kd'.  rtx_denoise is unchanged (its colour edge-stop now sees texture detail); debug layer 13 shows Kd'.
+   whose triangles carry materials with Kd = Kd'.  rtx_denoise is unchanged (its colour edge-stop now sees texture detail, unless RTX_DENOISE_ALBEDO demodulates by Kd': DENOISING, MAP GUIDES); debug layer 13 shows Kd'.
    CALLS.  rtx_set_mesh_uvs: nidx pairs, nidx = the mesh's index count; NULL clears.  rtx_set_texture: tex <= the current count, == count appends; the texels are copied.
    rtx_set_material_map: slot RTX_MAP_KD (or RTX_MAP_OPACITY, below), tex -1 = none.  RTX_ERR_INVALID — unknown mesh, material, texture or slot; nidx other than the mesh's; a non-finite UV; a size
    outside the limits; unknown flag bits; a NULL pixel pointer — leaves the scene untouched and committed.  rtx_set_materials resets every map to -1 (the table is
@@ -334,8 +334,8 @@ int  rtx_update_mesh_vertices(rtx_ctx*, uint32_t mesh, const void* verts28, uint
    n' replaces the shading normal for everything the shading does at that hit: the transmission flip, the mixture's view terms, triangle-light and environment NEE, the
    continuation.  Position, flat normal, area, the emissive hit, the light list and the random-number sequence are untouched.  CONSEQUENCE: a scene whose normal maps hold only
    texels with r = g = 128 is, bit for bit, the scene with no normal map bound.
-   WHO SEES IT.  rtx_render, rtx_render_adaptive, rtx_debug_shading_normal.  IGNORED BY rtx_render_v6_pass1, rtx_render_restir, the guides of rtx_denoise, rtx_read_layer 10-17,
-   rtx_debug_surface and rtx_focus_distance_at — as they ignore map_Kd.
+   WHO SEES IT.  rtx_render, rtx_render_adaptive, rtx_debug_shading_normal.  IGNORED BY rtx_render_v6_pass1, rtx_render_restir, the guides of rtx_denoise (its opt-in
+   map guides see it: RTX_DENOISE_MAPPED_NORMALS), rtx_read_layer 10-17, rtx_debug_surface and rtx_focus_distance_at — as they ignore map_Kd.
    CALLS AND COMMITS follow the map_Kd rules word for word: valid before the first commit and on a resident scene; rtx_commit_scene again (rendering in between is
    RTX_ERR_STATE); RTX_ERR_INVALID leaves the scene committed and untouched; rtx_set_materials resets the slot to -1; on a resident general scene a map-only commit uploads
    tables only (rtx_stats.bvh_refits and rtx_debug_tree_hash unchanged); a tiny scene (<= 64 triangles) runs on the general BVH path while a non-emitting material that a
@@ -520,17 +520,41 @@ int  rtx_render_adaptive(rtx_ctx*, const rtx_params*, const rtx_adaptive*, rtx_a
    stream and only ENQUEUES on a caller-bound one, behind a frame that RTX_OPT_ASYNC left in flight, by stream order — unless `out` is given: the counts are read back, which joins
    the stream up to the denoise.  The guides are recomputed by every call (one primary ray per pixel).
    Errors: RTX_ERR_STATE before commit (also: a scene edit not yet committed), camera or any accumulation; RTX_ERR_INVALID for a size other than the accumulation buffer's, for
-   levels > 8, normal_power_log2 > 7, a sigma that is negative, not finite or whose reciprocal is not finite, or a nonzero reserved word.  A failed call leaves u1 and the
+   levels > 8, normal_power_log2 > 7, a sigma that is negative, not finite or whose reciprocal is not finite, an unknown bit in flags, or a nonzero reserved word.  A failed call leaves u1 and the
    previous denoised image untouched.  rtx_read_denoised* is RTX_ERR_STATE before a successful rtx_denoise and once the accumulation buffer has another size than the denoised image.
    DEFAULT sigma_plane = 2^-6 * the largest extent of the committed scene's bounding box, defined by these float32 operations: for every instance (hidden ones included) and every vertex v
    of its mesh, world_k = ((v.x * m[k] + v.y * m[4+k]) + v.z * m[8+k]) + m[12+k], k = 0, 1, 2, m = the instance's objectToWorld; lo / hi = min / max over all of them;
-   extent_k = hi_k - lo_k; sigma_plane = 0.015625f * max(extent). */
+   extent_k = hi_k - lo_k; sigma_plane = 0.015625f * max(extent).
+   MAP GUIDES (opt-in, rtx_denoise_params.flags; with flags == 0 every kernel launched, every buffer allocated and every bit of the result is what it was).  Diffuse texture maps,
+   cut-outs and normal maps leave detail INSIDE one material id on geometry that is flat as far as the guides above can tell, and the colour stop alone treats it like noise.  Two
+   more guides per pixel, from the same ray, tmin and trace as the guides above (pixel corner, no jitter, no lens; cut-outs and hidden instances count).  For a pixel that is
+   filterable by geometry, with hit record (t, u, v, prim), material m and the surface reconstruction sf:
+       K  = the Kd' of PER HIT under DIFFUSE TEXTURE MAPS (the value rtx_debug_albedo returns; m.Kd where the material has no map or no map is active)
+       A.k = max(K.k, 0.015625f)                                                 (k = x, y, z.  The floor 2^-6 is part of the definition: below it the division would amplify by
+                                                                                  more than 64 and the binary16-rounded Kd' gets coarse; the bias it leaves on such a texel is
+                                                                                  at most 1/64 of the filtered irradiance)
+       nm = the n' of NORMAL-MAPPED HIT with wo = the guide ray's direction negated (sf.normal where no normal map is active or the material has none)
+   A pixel that is not filterable by geometry has A = (1, 1, 1) and nm = (0, 0, 0).
+   RTX_DENOISE_ALBEDO.  Only FILTERABLE pixels (filterable by geometry and u1.w > 0) are demodulated.  Level 0's input colour of such a pixel is
+       c.k = (u1.k / max(u1.w, 1)) / A.k                                         (two IEEE divisions, in this order)
+   every level then runs as defined above on those colours, and the LAST level's output of such a pixel is
+       o.k = (sum.k / sumw) * A.k
+   Every other pixel passes through exactly as without the flag: its output is its input, to the bit, at every level; a tap never reads such a pixel, so the two domains never mix.
+   RTX_DENOISE_MAPPED_NORMALS.  Only the normal stop changes: dn = (nm_p.x*nm_q.x + nm_p.y*nm_q.y) + nm_p.z*nm_q.z.  The plane stop keeps n_p of the guides above: a perturbed
+   normal must not make a flat wall leave its own tangent plane.
+   CONSEQUENCES.  With no normal map active RTX_DENOISE_MAPPED_NORMALS gives the bits of flags == 0 (nm == n to the bit), and so does a scene whose normal maps hold only flat
+   texels.  RTX_DENOISE_ALBEDO changes no pass-through pixel.  Without jitter and without a lens every sample of a pixel hits the guide's texel, so A is the samples' own albedo;
+   under RTX_FLAG_JITTER or a lens it is the pixel-corner ray's albedo (documented, not corrected).  Specular, metallic and roughness terms are not demodulated.
+   tests/denoise_maps_ref.py replays both in numpy; tests/test_denoise_maps.py holds the device to it bit for bit. */
+#define RTX_DENOISE_ALBEDO         1u
+#define RTX_DENOISE_MAPPED_NORMALS 2u
 typedef struct rtx_denoise_params {
     uint32_t levels;              /* 1..8; 0 => 5 */
     uint32_t normal_power_log2;   /* 1..7; 0 => 5 (cos^32) */
     float    sigma_color;         /* > 0; 0 => 0.5 */
     float    sigma_plane;         /* world units, > 0; 0 => 2^-6 * largest extent of the committed scene's bounding box */
-    uint32_t reserved[4];         /* 0 */
+    uint32_t flags;               /* RTX_DENOISE_* (MAP GUIDES above); 0 = the filter as it always was; any other bit is RTX_ERR_INVALID */
+    uint32_t reserved[3];         /* 0 */
 } rtx_denoise_params;
 typedef struct rtx_denoise_result {
     uint32_t levels;
@@ -544,6 +568,8 @@ int  rtx_read_denoised(rtx_ctx*, float* rgba32f, size_t bytes);
 int  rtx_read_denoised_srgb8(rtx_ctx*, uint8_t* rgba8, size_t bytes);   /* k_srgb8 over the denoised image */
 /* the guides as the filter reads them: per pixel P3, material word as uint bits (0xFFFFFFFF = not filterable by geometry; P and n are then 0), n3, 0 */
 int  rtx_debug_denoise_guides(rtx_ctx*, uint32_t width, uint32_t height, float* out8 /* W*H*8 */);
+/* the MAP GUIDES as the filter reads them under a flag: per pixel A3, 0, nm3, 0 ((1, 1, 1, 0, 0, 0, 0, 0) where the pixel is not filterable by geometry); errors as above */
+int  rtx_debug_denoise_map_guides(rtx_ctx*, uint32_t width, uint32_t height, float* out8 /* W*H*8 */);
 /* The reference's OWN first pass, literally: RayGen of RayGen_v6_pass1.hlsl:48-190 (first DispatchRays,
    Renderer.cpp:651-654): primary hit, SampleRIS (Sampler_v6.hlsl:653-736), visibility, SamplePathSimple
    (Path_Sampler_v6.hlsl:3-286).  params: nee_samples = nee_samples_DI = nee_samples (Common_v6.hlsl:8-9, reference 4),

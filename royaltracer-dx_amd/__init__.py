@@ -162,6 +162,8 @@ _sig("rtx_denoise", C.c_int, _vp, _u32, _u32, C.POINTER(DenoiseParams), C.POINTE
 _sig("rtx_read_denoised", C.c_int, _vp, _vp, C.c_size_t)
 _sig("rtx_read_denoised_srgb8", C.c_int, _vp, _vp, C.c_size_t)
 _sig("rtx_debug_denoise_guides", C.c_int, _vp, _u32, _u32, _vp)
+_sig("rtx_debug_denoise_map_guides", C.c_int, _vp, _u32, _u32, _vp)
+DENOISE_ALBEDO, DENOISE_MAPPED_NORMALS = 1, 2      # rtx_denoise_params.flags, the first of DenoiseParams.reserved's four words
 _sig("rtx_render_v6_pass1", C.c_int, _vp, C.POINTER(Params))
 _sig("rtx_render_restir", C.c_int, _vp, C.POINTER(Params))
 _sig("rtx_restir_reset", C.c_int, _vp)
@@ -843,10 +845,12 @@ class Context:
         self._ck(lib.rtx_read_accum(self._h, _ptr(out), out.nbytes), "rtx_read_accum")
         return out
 
-    def denoise(self, width, height, levels=0, sigma_color=0.0, sigma_plane=0.0, normal_power_log2=0, result=True):
+    def denoise(self, width, height, levels=0, sigma_color=0.0, sigma_plane=0.0, normal_power_log2=0, result=True, albedo=False, mapped_normals=False):
         """rtx_denoise: the edge-avoiding a-trous filter over the mean of u1, guided by first-hit position, normal and material (0 = a field's default) -> DenoiseResult.
-        result=False passes no result struct: on a caller-bound stream the call then only enqueues (no host join) and returns None"""
-        dp = DenoiseParams(int(levels), int(normal_power_log2), float(sigma_color), float(sigma_plane))
+        albedo: RTX_DENOISE_ALBEDO, filter the image divided by the first hit's Kd' so that texture detail survives; mapped_normals: RTX_DENOISE_MAPPED_NORMALS, the normal
+        stop compares normal-mapped shading normals.  result=False passes no result struct: on a caller-bound stream the call then only enqueues (no host join) and returns None"""
+        flags = (DENOISE_ALBEDO if albedo else 0) | (DENOISE_MAPPED_NORMALS if mapped_normals else 0)
+        dp = DenoiseParams(int(levels), int(normal_power_log2), float(sigma_color), float(sigma_plane), (C.c_uint32 * 4)(flags, 0, 0, 0))
         res = DenoiseResult() if result else None
         self._ck(lib.rtx_denoise(self._h, int(width), int(height), C.byref(dp), C.byref(res) if result else None), "rtx_denoise")
         return res
@@ -866,6 +870,12 @@ class Context:
         """the filter's guides (H, W, 8) float32: P3, material word as uint bits (0xFFFFFFFF = not filterable by geometry, P and n then 0), n3, 0"""
         out = np.zeros((height, width, 8), np.float32)
         self._ck(lib.rtx_debug_denoise_guides(self._h, int(width), int(height), _ptr(out)), "rtx_debug_denoise_guides")
+        return out
+
+    def denoise_map_guides(self, width, height):
+        """the filter's map guides (H, W, 8) float32: A3 = max(Kd', 2^-6), 0, nm3 = the normal-mapped shading normal, 0; (1, 1, 1, 0, 0, 0, 0, 0) where not filterable by geometry"""
+        out = np.zeros((height, width, 8), np.float32)
+        self._ck(lib.rtx_debug_denoise_map_guides(self._h, int(width), int(height), _ptr(out)), "rtx_debug_denoise_map_guides")
         return out
 
     def render_v6_pass1(self, params):

@@ -166,6 +166,7 @@ struct rtx_ctx {
     // ---- the denoiser (rtx_denoise.hip) ----
     struct Denoise {
         DevBuf d_guides, d_pp[2], d_out, d_partial, d_count;     // 32 B of guides per pixel, the two ping-pong images, the denoised image; per-workgroup counts of the first level and their sum
+        DevBuf d_mguides;                                         // 32 B of map guides per pixel (A, nm): allocated by the first call with a flag set
         uint32_t w = 0, h = 0; bool valid = false;                // size of the denoised image; a successful rtx_denoise wrote it
         Events ev;                                                // guides / filter begin and end (RTX_OPT_KERNEL_TIMING), rewound per call
         uint32_t lds_step = 4;                                    // RTX_OPT_DENOISE_LDS_STEP

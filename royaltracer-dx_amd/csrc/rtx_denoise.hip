@@ -1,5 +1,5 @@
 // rtx_denoise.hip — rtx_denoise: the edge-avoiding a-trous filter over the mean of u1, and the reads of the denoised image.  Validate, guides (k_denoise_guides, one primary
-// ray per pixel, every call), then one k_denoise_level per level between u1, two ping-pong images and the denoised image.  Part of the C-ABI of include/rtx.h (rtx_ctx.hpp);
+// ray per pixel, every call; with a flag of rtx_denoise_params set its map-guide form, k_denoise_map_guides, and the levels' *_maps forms), then one k_denoise_level per level between u1, two ping-pong images and the denoised image.  Part of the C-ABI of include/rtx.h (rtx_ctx.hpp);
 // the kernels and the tap arithmetic: rtx_k_denoise.hpp.
 #include <cmath>
 #include "rtx_ctx.hpp"
@@ -36,6 +36,7 @@ int rtx_denoise(rtx_ctx* c, uint32_t width, uint32_t height, const rtx_denoise_p
     if (c->ext_accum && c->ext_accum_bytes < npix * 16) { c->err = "bound accumulation buffer is smaller than width*height*16 bytes"; return RTX_ERR_INVALID; }
     rtx_denoise_params q{};
     if (dp) q = *dp;
+    if (q.flags & ~(RTX_DENOISE_ALBEDO | RTX_DENOISE_MAPPED_NORMALS)) { c->err = "denoise: unknown bits in flags"; return RTX_ERR_INVALID; }
     for (uint32_t r : q.reserved) if (r) { c->err = "denoise: reserved words must be 0"; return RTX_ERR_INVALID; }
     if (q.levels > 8 || q.normal_power_log2 > 7) { c->err = "denoise: levels must be in [1, 8] and normal_power_log2 in [1, 7] (0 = default)"; return RTX_ERR_INVALID; }
     if (!q.levels) q.levels = 5;
@@ -49,7 +50,8 @@ int rtx_denoise(rtx_ctx* c, uint32_t width, uint32_t height, const rtx_denoise_p
     // ---- 2. memory: allocated on first use, resized with the image ----
     rtx_ctx::Denoise& D = c->dn;
     const uint32_t nwg = denoise_workgroups(width, height);
-    HIPCHK(c, D.d_guides.ensure(npix * 32)); HIPCHK(c, D.d_partial.ensure((size_t)nwg * 4)); HIPCHK(c, D.d_count.ensure(16));
+    HIPCHK(c, D.d_guides.ensure(npix * 32)); if (q.flags) HIPCHK(c, D.d_mguides.ensure(npix * 32));
+    HIPCHK(c, D.d_partial.ensure((size_t)nwg * 4)); HIPCHK(c, D.d_count.ensure(16));
     if (q.levels > 1) HIPCHK(c, D.d_pp[0].ensure(npix * 16));
     if (q.levels > 2) HIPCHK(c, D.d_pp[1].ensure(npix * 16));
     HIPCHK(c, D.d_out.ensure(npix * 16));
@@ -63,7 +65,8 @@ int rtx_denoise(rtx_ctx* c, uint32_t width, uint32_t height, const rtx_denoise_p
     if (timing) for (hipEvent_t& e : ev) e = D.ev.take();
     const bool timed = timing && ev[0] && ev[1] && ev[2] && ev[3];
     if (timed) (void)hipEventRecord(ev[0], st);
-    launch_denoise_guides(st, (uint32_t)c->num_cus * 8u, c->dsc, width, height, (const CameraGPU*)c->d_cam.p, (F4*)D.d_guides.p);
+    if (q.flags) launch_denoise_map_guides(st, (uint32_t)c->num_cus * 8u, c->dsc, width, height, (const CameraGPU*)c->d_cam.p, (F4*)D.d_guides.p, (F4*)D.d_mguides.p);
+    else launch_denoise_guides(st, (uint32_t)c->num_cus * 8u, c->dsc, width, height, (const CameraGPU*)c->d_cam.p, (F4*)D.d_guides.p);
     if (timed) { (void)hipEventRecord(ev[1], st); (void)hipEventRecord(ev[2], st); }
     const F4* in = c->accum_ptr();
     for (uint32_t i = 0; i < q.levels; i++) {
@@ -71,7 +74,8 @@ int rtx_denoise(rtx_ctx* c, uint32_t width, uint32_t height, const rtx_denoise_p
         a.width = width; a.height = height; a.step = 1u << i; a.normal_power_log2 = q.normal_power_log2; a.first = i == 0; a.last = i + 1 == q.levels;
         a.inv_sigma_plane = inv_plane; a.inv_sigma_color_s = inv_color * (float)a.step;
         F4* dst = (F4*)(a.last ? D.d_out.p : D.d_pp[i & 1u].p);
-        launch_denoise_level(st, a, in, (const F4*)D.d_guides.p, dst, (uint32_t*)D.d_partial.p, a.step <= D.lds_step);
+        if (q.flags) launch_denoise_level_maps(st, a, q.flags, in, (const F4*)D.d_guides.p, (const F4*)D.d_mguides.p, dst, (uint32_t*)D.d_partial.p, a.step <= D.lds_step);
+        else launch_denoise_level(st, a, in, (const F4*)D.d_guides.p, dst, (uint32_t*)D.d_partial.p, a.step <= D.lds_step);
         in = dst;
     }
     if (timed) (void)hipEventRecord(ev[3], st);
@@ -125,6 +129,20 @@ int rtx_debug_denoise_guides(rtx_ctx* c, uint32_t width, uint32_t height, float*
     launch_denoise_guides(c->stream, (uint32_t)c->num_cus * 8u, c->dsc, width, height, (const CameraGPU*)c->d_cam.p, (F4*)d_g.p);
     HIPCHK(c, hipGetLastError());
     TO_HOST(c, out8, d_g.p, npix * 32);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RTX_OK;
+}
+
+int rtx_debug_denoise_map_guides(rtx_ctx* c, uint32_t width, uint32_t height, float* out8) {
+    BIND(c);
+    if (!c->committed || !c->camera_set) { c->err = "denoise_map_guides: scene not committed or camera not set"; return RTX_ERR_STATE; }
+    const size_t npix = (size_t)width * height;
+    if (!out8 || !npix || npix > 0x7FFFFFFFull) { c->err = "denoise_map_guides: bad size"; return RTX_ERR_INVALID; }
+    DevBuf d_g, d_m;                                                         // (private, as rtx_debug_denoise_guides': the kernel writes both records)
+    HIPCHK(c, d_g.ensure(npix * 32)); HIPCHK(c, d_m.ensure(npix * 32));
+    launch_denoise_map_guides(c->stream, (uint32_t)c->num_cus * 8u, c->dsc, width, height, (const CameraGPU*)c->d_cam.p, (F4*)d_g.p, (F4*)d_m.p);
+    HIPCHK(c, hipGetLastError());
+    TO_HOST(c, out8, d_m.p, npix * 32);
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return RTX_OK;
 }

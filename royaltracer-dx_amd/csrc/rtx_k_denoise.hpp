@@ -3,20 +3,30 @@
 //
 // PARITY-CRITICAL: tests/test_denoise_ref.py replays dn_tap operation for operation in numpy float32.  Only + - * / abs max, in the written order; no dot() / madd3() here
 // (those are fused), and the tap sum is sequential in tap order.  Do not reassociate, do not split the 5 x 5 window into passes.
+//
+// The two opt-in guide extensions (RTX_DENOISE_ALBEDO, RTX_DENOISE_MAPPED_NORMALS; rtx.h, MAP GUIDES) are compile-time forms of the same two bodies, launched as kernels of their own
+// (k_denoise_map_guides, k_denoise_level_maps): a call with flags == 0 launches the kernels it always launched; tests/denoise_maps_ref.py is their twin.
 #pragma once
 #include "rtx_k_film.hpp"
+#include "rtx_texture.hpp"
+#include "rtx_normalmap.hpp"
 
 namespace rtx {
 
 constexpr uint32_t kDnNoGeo = 0xFFFFFFFFu;          // material word of a guide record: the pixel is not filterable by geometry (miss, material out of range, emitter seen directly)
+constexpr uint32_t kDnAlbedo = 1u, kDnMappedNormals = 2u;   // RTX_DENOISE_ALBEDO, RTX_DENOISE_MAPPED_NORMALS
+constexpr float kDnAlbedoFloor = 0.015625f;             // 2^-6: part of the definition of A
 constexpr uint32_t kDnTileW = 32, kDnTileH = 8;     // one workgroup = 32 x 8 pixels: a wave is two rows of 32 neighbouring pixels, 512 contiguous bytes of a colour row each
 
 // Guides: the first hit of every pixel (for_each_first_hit, as k_debug_layer) and surface(); two F4 per pixel: (P, material word) (n, 0).  A pixel that is not filterable by geometry
 // gets (0, 0, 0, kDnNoGeo) (0, 0, 0, 0), so that a tap's class test and its material test are ONE compare of the material word with the centre's.
-template <bool CUT>
-__global__ __launch_bounds__(kBlock) void k_denoise_guides(DevScene sc, const SmallRecPair* __restrict__ small, uint32_t width, uint32_t height, const CameraGPU* __restrict__ cam, F4* __restrict__ guides) {
+// MAPS: also the map-guide record, two F4 per pixel: (A, 0) (nm, 0) — A = max(Kd', 2^-6) per channel (tex_albedo), nm = the normal-mapped shading normal (nrm_perturb, wo = -d);
+// (1, 1, 1, 0) (0, 0, 0, 0) for a pixel that is not filterable by geometry.  sc.map_kd, sc.map_nrm and sc.tri_tan are null while no such map is active: A = max(m.Kd, 2^-6), nm = n
+template <bool CUT, bool MAPS>
+__device__ __forceinline__ void dn_guides(const DevScene& sc, const SmallRecPair* __restrict__ small, uint32_t width, uint32_t height, const CameraGPU* __restrict__ cam, F4* __restrict__ guides, F4* __restrict__ mguides) {
     for_each_first_hit<CUT>(sc, small, width, height, cam, [&](uint32_t i, f3 o, f3 d, float t, float u, float v, uint32_t prim) {
         F4 g0 = {0.0f, 0.0f, 0.0f, u2f(kDnNoGeo)}, g1 = {0.0f, 0.0f, 0.0f, 0.0f};
+        F4 m0 = {1.0f, 1.0f, 1.0f, 0.0f}, m1 = {0.0f, 0.0f, 0.0f, 0.0f};
         if (prim != kMissPrim) {
             const Surf sf = surface(sc, o, d, t, u, v, prim);
             if (sf.mat < sc.nmat) {
@@ -24,11 +34,27 @@ __global__ __launch_bounds__(kBlock) void k_denoise_guides(DevScene sc, const Sm
                 if (!(m.KeFull[0] > 0.0f || m.KeFull[1] > 0.0f || m.KeFull[2] > 0.0f)) {
                     g0 = {sf.pos.x, sf.pos.y, sf.pos.z, u2f(sf.mat)};
                     g1 = {sf.normal.x, sf.normal.y, sf.normal.z, 0.0f};
+                    if constexpr (MAPS) {
+                        const f3 K = tex_albedo(sc, m, sf.mat, prim, u, v);
+                        m0 = {maxf_(K.x, kDnAlbedoFloor), maxf_(K.y, kDnAlbedoFloor), maxf_(K.z, kDnAlbedoFloor), 0.0f};
+                        f3 nm = sf.normal;
+                        if (sc.tri_tan && sc.map_nrm && !(m.Ke_len > 0.0f)) nm = nrm_perturb(sc, sf, prim, u, v, -d);
+                        m1 = {nm.x, nm.y, nm.z, 0.0f};
+                    }
                 }
             }
         }
         guides[2 * (size_t)i] = g0; guides[2 * (size_t)i + 1] = g1;
+        if constexpr (MAPS) { mguides[2 * (size_t)i] = m0; mguides[2 * (size_t)i + 1] = m1; }
     });
+}
+template <bool CUT>
+__global__ __launch_bounds__(kBlock) void k_denoise_guides(DevScene sc, const SmallRecPair* __restrict__ small, uint32_t width, uint32_t height, const CameraGPU* __restrict__ cam, F4* __restrict__ guides) {
+    dn_guides<CUT, false>(sc, small, width, height, cam, guides, nullptr);
+}
+template <bool CUT>
+__global__ __launch_bounds__(kBlock) void k_denoise_map_guides(DevScene sc, const SmallRecPair* __restrict__ small, uint32_t width, uint32_t height, const CameraGPU* __restrict__ cam, F4* __restrict__ guides, F4* __restrict__ mguides) {
+    dn_guides<CUT, true>(sc, small, width, height, cam, guides, mguides);
 }
 
 // the colour a level reads.  Level 0 (FIRST) reads u1 and forms the mean as k_srgb8 does, c = u1.xyz / max(u1.w, 1), with w := 1 where the pixel holds samples, else 0;
@@ -38,10 +64,14 @@ template <bool FIRST> __device__ __forceinline__ F4 dn_colour(F4 a) {
     else return a;
 }
 
-// one tap that counts (inside the image, filterable, the centre's material): rtx.h's eight lines
+// RTX_DENOISE_ALBEDO, level 0: the input colour of a FILTERABLE pixel is its mean divided by A, channel by channel (the second of the two IEEE divisions of rtx.h)
+__device__ __forceinline__ void dn_demodulate(F4& c, F4 A) { c.x = c.x / A.x; c.y = c.y / A.y; c.z = c.z / A.z; }
+
+// one tap that counts (inside the image, filterable, the centre's material): rtx.h's eight lines.  np / nq: the normals of the normal stop — g1p / g1q, or the map guides' nm
+// under RTX_DENOISE_MAPPED_NORMALS; the plane stop keeps g1p either way
 struct DnSum { float x, y, z, w; };
-__device__ __forceinline__ void dn_tap(DnSum& S, const DenoiseLevel& a, F4 g0p, F4 g1p, F4 cp, F4 g0q, F4 g1q, F4 cq, float hh) {
-    const float dn = (g1p.x * g1q.x + g1p.y * g1q.y) + g1p.z * g1q.z;
+__device__ __forceinline__ void dn_tap(DnSum& S, const DenoiseLevel& a, F4 g0p, F4 g1p, F4 np, F4 cp, F4 g0q, F4 nq, F4 cq, float hh) {
+    const float dn = (np.x * nq.x + np.y * nq.y) + np.z * nq.z;
     float wn = maxf_(dn, 0.0f);
     for (uint32_t k = 0; k < a.normal_power_log2; k++) wn = wn * wn;
     const float dx = g0q.x - g0p.x, dy = g0q.y - g0p.y, dz = g0q.z - g0p.z;
@@ -58,10 +88,14 @@ __device__ __forceinline__ float dn_h(int k) { return k == 0 ? 0.375f : ((k == 1
 // all), so the loads coalesce and the 25-fold reuse is the cache's.  S = 1, 2, 4: STAGED — the tile plus its 2 S halo (colour and both guide records, 48 B per pixel) goes
 // through LDS once, pixels outside the image as kDnNoGeo; S is the level's step and must equal a.step.  No atomics, no dependency between workgroups.
 // FIRST also counts the filterable pixels of the tile into partial[workgroup] (k_denoise_count sums them).
-template <uint32_t S, bool FIRST>
-__global__ __launch_bounds__(kBlock) void k_denoise_level(DenoiseLevel a, const F4* __restrict__ in, const F4* __restrict__ guides, F4* __restrict__ out, uint32_t* __restrict__ partial) {
+// FL, the flags word at compile time (0: mg is never read).  kDnAlbedo: level 0 divides the colour of a filterable pixel by A where it LOADS it (at staging, or per tap in the
+// direct form) and the last level multiplies the centre's result by A where it STORES it — A never enters LDS, and a pass-through pixel is neither divided nor multiplied.
+// kDnMappedNormals: nm is the normal of the normal stop; the staged forms carry it as a fourth F4 per pixel (64 B per pixel, 72 KiB at step 4: two workgroups per CU, as at 54 KiB).
+template <uint32_t S, bool FIRST, uint32_t FL>
+__device__ __forceinline__ void dn_level(const DenoiseLevel& a, const F4* __restrict__ in, const F4* __restrict__ guides, const F4* __restrict__ mg, F4* __restrict__ out, uint32_t* __restrict__ partial) {
+    constexpr bool ALB = (FL & kDnAlbedo) != 0, NM = (FL & kDnMappedNormals) != 0;
     constexpr uint32_t RW = kDnTileW + 4u * S, RH = kDnTileH + 4u * S;
-    __shared__ F4 s_c[S ? RW * RH : 1], s_g0[S ? RW * RH : 1], s_g1[S ? RW * RH : 1];
+    __shared__ F4 s_c[S ? RW * RH : 1], s_g0[S ? RW * RH : 1], s_g1[S ? RW * RH : 1], s_nm[S && NM ? RW * RH : 1];
     __shared__ uint32_t s_cnt[kBlock / 64];
     const uint32_t tx = blockIdx.x % a.tiles_x, ty = blockIdx.x / a.tiles_x;
     const uint32_t lx = threadIdx.x & (kDnTileW - 1u), ly = threadIdx.x / kDnTileW;
@@ -73,10 +107,12 @@ __global__ __launch_bounds__(kBlock) void k_denoise_level(DenoiseLevel a, const 
             // a position outside the image reads its nearest pixel (always in bounds, no divergent load) and is marked kDnNoGeo: it counts for no tap
             const bool ins = qx >= 0 && qx < W && qy >= 0 && qy < H;
             const size_t q = (size_t)(qy < 0 ? 0 : (qy >= H ? H - 1 : qy)) * a.width + (size_t)(qx < 0 ? 0 : (qx >= W ? W - 1 : qx));
-            const F4 c = dn_colour<FIRST>(in[q]), g1 = guides[2 * q + 1];
+            F4 c = dn_colour<FIRST>(in[q]); const F4 g1 = guides[2 * q + 1];
             F4 g0 = guides[2 * q];
+            if constexpr (FIRST && ALB) { if (f2u(g0.w) != kDnNoGeo && c.w != 0.0f) dn_demodulate(c, mg[2 * q]); }
             if (!ins) g0.w = u2f(kDnNoGeo);
             s_c[i] = c; s_g0[i] = g0; s_g1[i] = g1;
+            if constexpr (NM) s_nm[i] = mg[2 * q + 1];
         }
         __syncthreads();
     }
@@ -84,7 +120,7 @@ __global__ __launch_bounds__(kBlock) void k_denoise_level(DenoiseLevel a, const 
     if (x < W && y < H) {
         const size_t p = (size_t)y * a.width + (size_t)x;
         const uint32_t lp = (ly + 2u * S) * RW + lx + 2u * S;
-        F4 cp, g0p, g1p = {0.0f, 0.0f, 0.0f, 0.0f};
+        F4 cp, g0p, g1p = {0.0f, 0.0f, 0.0f, 0.0f}, np = {0.0f, 0.0f, 0.0f, 0.0f};
         if constexpr (S != 0) { cp = s_c[lp]; g0p = s_g0[lp]; }
         else { cp = dn_colour<FIRST>(in[p]); g0p = guides[2 * p]; }
         const uint32_t matp = f2u(g0p.w);
@@ -92,6 +128,8 @@ __global__ __launch_bounds__(kBlock) void k_denoise_level(DenoiseLevel a, const 
         F4 o = cp;
         if (filt) {
             if constexpr (S != 0) g1p = s_g1[lp]; else g1p = guides[2 * p + 1];
+            if constexpr (!NM) np = g1p; else if constexpr (S != 0) np = s_nm[lp]; else np = mg[2 * p + 1];
+            if constexpr (FIRST && ALB && S == 0) dn_demodulate(cp, mg[2 * p]);
             DnSum sum = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
             for (int dy = -2; dy <= 2; dy++) {
@@ -104,20 +142,24 @@ __global__ __launch_bounds__(kBlock) void k_denoise_level(DenoiseLevel a, const 
                         if (f2u(g0q.w) != matp) continue;
                         const F4 cq = s_c[lq];
                         if (cq.w == 0.0f) continue;
-                        dn_tap(sum, a, g0p, g1p, cp, g0q, s_g1[lq], cq, hh);
+                        if constexpr (NM) dn_tap(sum, a, g0p, g1p, np, cp, g0q, s_nm[lq], cq, hh);
+                        else dn_tap(sum, a, g0p, g1p, np, cp, g0q, s_g1[lq], cq, hh);
                     } else {
                         const int qx = x + s * dx, qy = y + s * dy;
                         if (qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
                         const size_t q = (size_t)qy * a.width + (size_t)qx;
                         const F4 g0q = guides[2 * q];
                         if (f2u(g0q.w) != matp) continue;
-                        const F4 cq = dn_colour<FIRST>(in[q]);
+                        F4 cq = dn_colour<FIRST>(in[q]);
                         if (cq.w == 0.0f) continue;
-                        dn_tap(sum, a, g0p, g1p, cp, g0q, guides[2 * q + 1], cq, hh);
+                        if constexpr (FIRST && ALB) dn_demodulate(cq, mg[2 * q]);
+                        if constexpr (NM) dn_tap(sum, a, g0p, g1p, np, cp, g0q, mg[2 * q + 1], cq, hh);
+                        else dn_tap(sum, a, g0p, g1p, np, cp, g0q, guides[2 * q + 1], cq, hh);
                     }
                 }
             }
             o.x = sum.x / sum.w; o.y = sum.y / sum.w; o.z = sum.z / sum.w;
+            if constexpr (ALB) { if (a.last) { const F4 A = mg[2 * p]; o.x = o.x * A.x; o.y = o.y * A.y; o.z = o.z * A.z; } }
         }
         if (a.last) o.w = 1.0f;
         out[p] = o;
@@ -128,6 +170,16 @@ __global__ __launch_bounds__(kBlock) void k_denoise_level(DenoiseLevel a, const 
         __syncthreads();
         if (threadIdx.x == 0) partial[blockIdx.x] = (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);
     }
+}
+template <uint32_t S, bool FIRST>
+__global__ __launch_bounds__(kBlock) void k_denoise_level(DenoiseLevel a, const F4* __restrict__ in, const F4* __restrict__ guides, F4* __restrict__ out, uint32_t* __restrict__ partial) {
+    dn_level<S, FIRST, 0u>(a, in, guides, nullptr, out, partial);
+}
+// the forms with a flag set (FL = 1, 2, 3); mg: the map-guide record of k_denoise_map_guides
+template <uint32_t S, bool FIRST, uint32_t FL>
+__global__ __launch_bounds__(kBlock) void k_denoise_level_maps(DenoiseLevel a, const F4* __restrict__ in, const F4* __restrict__ guides, const F4* __restrict__ mg, F4* __restrict__ out, uint32_t* __restrict__ partial) {
+    static_assert(FL >= 1u && FL <= 3u, "the flags word");
+    dn_level<S, FIRST, FL>(a, in, guides, mg, out, partial);
 }
 
 // the filterable pixels of the image: the sum of the level-0 workgroups' counts (one workgroup, a plain store)

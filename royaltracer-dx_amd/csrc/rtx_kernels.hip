@@ -313,15 +313,30 @@ void launch_adaptive_compact(hipStream_t st, const DevFrame& f, const AdaptState
 void launch_denoise_guides(hipStream_t st, uint32_t max_blocks, const DevScene& sc, uint32_t width, uint32_t height, const CameraGPU* cam, F4* guides) {
     dispatch_bool(sc.tri_cut != nullptr, [&](auto cut) { hipLaunchKernelGGL(k_denoise_guides<decltype(cut)::value>, dim3(grid_for(width * height, max_blocks)), dim3(kBlock), trace_lds_bytes(sc), st, sc, sc.small, width, height, cam, guides); });
 }
+void launch_denoise_map_guides(hipStream_t st, uint32_t max_blocks, const DevScene& sc, uint32_t width, uint32_t height, const CameraGPU* cam, F4* guides, F4* mguides) {
+    dispatch_bool(sc.tri_cut != nullptr, [&](auto cut) { hipLaunchKernelGGL(k_denoise_map_guides<decltype(cut)::value>, dim3(grid_for(width * height, max_blocks)), dim3(kBlock), trace_lds_bytes(sc), st, sc, sc.small, width, height, cam, guides, mguides); });
+}
 uint32_t denoise_workgroups(uint32_t width, uint32_t height) { return ((width + kDnTileW - 1u) / kDnTileW) * ((height + kDnTileH - 1u) / kDnTileH); }
-void launch_denoise_level(hipStream_t st, DenoiseLevel a, const F4* in, const F4* guides, F4* out, uint32_t* partial, bool staged) {
-    a.tiles_x = (a.width + kDnTileW - 1u) / kDnTileW;
-    const dim3 grid(denoise_workgroups(a.width, a.height));
-    auto go = [&](auto ss, auto first) { hipLaunchKernelGGL((k_denoise_level<decltype(ss)::value, decltype(first)::value>), grid, dim3(kBlock), 0, st, a, in, guides, out, partial); };
+// which form a level runs: go(S, FIRST) with S = the level's step where it is staged (1, 2 or 4 and `staged`), else 0
+template <class Go> static void denoise_level_form(const DenoiseLevel& a, bool staged, Go go) {
     if (a.first) { if (staged && a.step == 1u) go(IntC<1>{}, BoolC<true>{}); else go(IntC<0>{}, BoolC<true>{}); }      // (the first level is the only one with step 1)
     else if (staged && a.step == 2u) go(IntC<2>{}, BoolC<false>{});
     else if (staged && a.step == 4u) go(IntC<4>{}, BoolC<false>{});
     else go(IntC<0>{}, BoolC<false>{});
+}
+void launch_denoise_level(hipStream_t st, DenoiseLevel a, const F4* in, const F4* guides, F4* out, uint32_t* partial, bool staged) {
+    a.tiles_x = (a.width + kDnTileW - 1u) / kDnTileW;
+    const dim3 grid(denoise_workgroups(a.width, a.height));
+    denoise_level_form(a, staged, [&](auto ss, auto first) { hipLaunchKernelGGL((k_denoise_level<decltype(ss)::value, decltype(first)::value>), grid, dim3(kBlock), 0, st, a, in, guides, out, partial); });
+}
+// flags: 1, 2 or 3 (RTX_DENOISE_ALBEDO | RTX_DENOISE_MAPPED_NORMALS)
+void launch_denoise_level_maps(hipStream_t st, DenoiseLevel a, uint32_t flags, const F4* in, const F4* guides, const F4* mguides, F4* out, uint32_t* partial, bool staged) {
+    a.tiles_x = (a.width + kDnTileW - 1u) / kDnTileW;
+    const dim3 grid(denoise_workgroups(a.width, a.height));
+    auto pick = [&](auto fl) {
+        denoise_level_form(a, staged, [&](auto ss, auto first) { hipLaunchKernelGGL((k_denoise_level_maps<decltype(ss)::value, decltype(first)::value, decltype(fl)::value>), grid, dim3(kBlock), 0, st, a, in, guides, mguides, out, partial); });
+    };
+    if (flags == 1u) pick(IntC<1>{}); else if (flags == 2u) pick(IntC<2>{}); else pick(IntC<3>{});
 }
 void launch_denoise_count(hipStream_t st, const uint32_t* partial, uint32_t n, uint32_t* out) {
     hipLaunchKernelGGL(k_denoise_count, dim3(1), dim3(kBlock), 0, st, partial, n, out);

@@ -18,6 +18,9 @@
 //                   [--denoise [--denoise-levels N] [--sigma-color X] [--sigma-plane X]]   after the last frame rtx_denoise filters the accumulated image (edge-avoiding a-trous,
 //                   guided by first-hit position, normal and material; defaults: 5 levels, 0.5, 2^-6 of the scene's extent) and --out gets the DENOISED image; works with
 //                   --adaptive and with --gpus N (on rank 0, after the gather); refused with --mode restir (that frame has its own reuse passes)
+//                   [--denoise-albedo] with --denoise: RTX_DENOISE_ALBEDO, the filter works on the image divided by the first hit's Kd' (texture detail survives)
+//                   [--denoise-mapped-normals] with --denoise: RTX_DENOISE_MAPPED_NORMALS, the normal stop compares normal-mapped shading normals (shading relief survives);
+//                   either one without --denoise is a usage error
 //                   [--no-textures]   OBJ scenes: do not read the images their map_Kd statements name (binary PPM / PGM, 24- / 32-bit TGA): the image without diffuse maps
 //                   [--no-cutouts]    OBJ scenes: do not bind the images their map_d statements name as opacity maps (alpha cut-outs): the image with every card opaque
 //                   [--kd-alpha]      OBJ scenes: a material without a map_d whose map_Kd is a 32-bit TGA gets that texture's alpha as its opacity map too
@@ -52,6 +55,7 @@ static const char* kUsage =
     "                  [--mode pt|restir] [--literal] [--halo px] [--force-gather] [--orbit deg] [--spin deg] [--hide i[,j...]] [--blink i] [--only-rank r]\n"
     "                  [--adaptive THRESHOLD [--min-spp N] [--step-spp N]]\n"
     "                  [--denoise [--denoise-levels N] [--sigma-color X] [--sigma-plane X]]   write the denoised image to --out (path tracer only)\n"
+    "                  [--denoise-albedo] [--denoise-mapped-normals]   with --denoise: keep texture detail (filter the image divided by Kd') / normal-map relief\n"
     "                  [--no-textures]   OBJ scenes: ignore map_Kd images (implies --no-cutouts)\n"
     "                  [--no-cutouts]    OBJ scenes: ignore map_d images (no alpha cut-outs)   [--kd-alpha]   a 32-bit map_Kd without a map_d is its material's opacity map too\n"
     "                  [--no-normal-maps] OBJ scenes: ignore norm images (--no-textures implies it)   [--bump-as-normal | --bump-height S]   map_Bump / bump as a normal map / a height map of strength S\n"
@@ -84,6 +88,7 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--bump-as-normal")) normals.mode = kNormalsBumpAsNormal; else if (arg("--bump-height")) { normals.strength = (float)atof(argv[++i]); normals.mode = kNormalsBumpHeight; }
         else if (arg("--env")) env_file = argv[++i]; else if (arg("--env-res")) env_res = (UINT)atoi(argv[++i]); else if (arg("--env-yaw")) env_yaw = (float)atof(argv[++i]);
         else if (arg("--env-scale")) env_scale = (float)atof(argv[++i]); else if (!strcmp(argv[i], "--env-hidden")) env_hidden = true; else if (arg("--sky")) sky = argv[++i];
+        else if (!strcmp(argv[i], "--denoise-albedo")) dnp.flags |= RTX_DENOISE_ALBEDO; else if (!strcmp(argv[i], "--denoise-mapped-normals")) dnp.flags |= RTX_DENOISE_MAPPED_NORMALS;
         else if (!strcmp(argv[i], "--denoise")) denoise = true; else if (arg("--denoise-levels")) dnp.levels = (uint32_t)atoi(argv[++i]); else if (arg("--sigma-color")) dnp.sigma_color = (float)atof(argv[++i]); else if (arg("--sigma-plane")) dnp.sigma_plane = (float)atof(argv[++i]);
         else if (arg("--aperture")) aperture = (float)atof(argv[++i]); else if (arg("--focus")) { focus = (float)atof(argv[++i]); focus_set = true; } else if (arg("--focus-pixel")) focus_pixel = argv[++i];
         else if (arg("--halo")) halo = (UINT)atoi(argv[++i]); else if (arg("--gpus")) gpus = atoi(argv[++i]); else if (arg("--devices")) devlist = argv[++i]; else if (arg("--gather")) gather = argv[++i];
@@ -96,6 +101,7 @@ int main(int argc, char** argv) {
     const bool restir = mode == "restir";
     if (restir) { if (!nee_set) nee = 4; if (!bounces_set) bounces = 3; }
     if (adaptive && (restir || gpus > 1 || !devlist.empty())) { fprintf(stderr, "--adaptive is the path tracer on one GPU (no --mode restir, --gpus, --devices)\n"); return 2; }
+    if (dnp.flags && !denoise) { fprintf(stderr, "--denoise-albedo and --denoise-mapped-normals are options of --denoise\n"); return 2; }
     if (denoise && restir) { fprintf(stderr, "--denoise filters the path tracer's accumulation (no --mode restir: that frame has its own reuse passes)\n"); return 2; }
     if (!env_file.empty() && !sky.empty()) { fprintf(stderr, "--env and --sky exclude each other\n"); return 2; }
     UINT fpx = 0, fpy = 0;
