@@ -262,7 +262,7 @@ int  rtx_update_mesh_vertices(rtx_ctx*, uint32_t mesh, const void* verts28, uint
        Kd'[k]   = half_round(m.Kd[k] * tl[k])                                             (binary16 round trip, the MaterialOptimized rounding of the table's Kd)
        KdPi'[k] = Kd'[k] / PI                                                             (IEEE division, as for the table)
    KdPi' replaces the material's Kd / PI wherever the shading reads the diffuse colour at that hit: the Lambert term of the mixture BSDF, for the NEE samples and for the
-   continuation.  Everything else stays the material's: Ks, Ke, Pr, Pm, dissolve, the light list, the strategy probabilities, the random-number sequence.  An emissive
+   continuation.  Everything else stays the material's: Ks, Ke, Pr, Pm, dissolve, the light list, the strategy probabilities, the random-number sequence (unless SPECULAR MAPS, below).  An emissive
    material's map has no effect (emitters are not shaded).  CONSEQUENCE: a scene in which every textured triangle sees one value tl is, bit for bit, the untextured scene
    whose triangles carry materials with Kd = Kd'.  rtx_denoise is unchanged (its colour edge-stop now sees texture detail, unless RTX_DENOISE_ALBEDO demodulates by Kd': DENOISING, MAP GUIDES); debug layer 13 shows Kd'.
    CALLS.  rtx_set_mesh_uvs: nidx pairs, nidx = the mesh's index count; NULL clears.  rtx_set_texture: tex <= the current count, == count appends; the texels are copied.
@@ -341,12 +341,53 @@ int  rtx_update_mesh_vertices(rtx_ctx*, uint32_t mesh, const void* verts28, uint
    tables only (rtx_stats.bvh_refits and rtx_debug_tree_hash unchanged); a tiny scene (<= 64 triangles) runs on the general BVH path while a non-emitting material that a
    triangle uses has a normal map, and the commit that crosses that line is a rebuild; rtx_save_scene_cache with one bound is RTX_ERR_STATE.  RTX_OPT_FUSED_BVH,
    RTX_OPT_SHADE_DENSE and RTX_OPT_SORT_MATERIALS are ignored while one is active; RTX_OPT_COMPACT_STATE 0 and 1 both work. */
+/* SPECULAR MAPS (new; the reference parses map_Ks / map_Pr / map_Pm and samples nothing: an extension like map_Kd, unpinned by the reference, pinned by its own definition and
+   properties in tests/test_specmap_ref.py / tests/test_specmap.py).  Three more material-map slots let a texture vary the specular colour, the roughness and the metalness of
+   a material over its surface: puddles on a floor, worn metal, glossy mortar.  All device arithmetic is float32 in exactly the written order, no contraction.
+   SLOTS.  rtx_set_material_map(ctx, material, RTX_MAP_KS | RTX_MAP_PR | RTX_MAP_PM, tex) binds a texture of the table above (6, 8 and 10; the values 1, 3, 5, 7 and 9 stay
+   unknown slots).  Green is roughness and blue is metalness: one packed occlusion-roughness-metal texture serves both slots, and a grey image (r = g = b) serves either.
+   PER HIT on a non-emitting material m (an emitter's maps have no effect, as for map_Kd), with b0, s, t exactly as PER HIT of map_Kd and the taps and fx, fy exactly as Sample():
+       RTX_MAP_KS = tex >= 0:  tl = Sample(tex, s, t)  (the RGB bytes, RTX_TEX_SRGB honoured as for the Kd slot);   Ks'[k] = half_round(m.Ks[k] * tl[k])
+       RTX_MAP_PR = tex >= 0:  g_ab = T_linear[green byte of texel(ixa, iyb)]  (the LINEAR table, whatever RTX_TEX_SRGB says);
+                               top = g00 + fx * (g10 - g00);  bot = g01 + fx * (g11 - g01);  g = top + fy * (bot - top);   Pr' = half_round(m.Pr * g)
+       RTX_MAP_PM = tex >= 0:  b likewise with the blue byte;   Pm' = half_round(m.Pm * b)
+   A slot without a map keeps the table's value.  Ks', Pr', Pm' replace m.Ks, m.Pr, m.Pm wherever the shading reads them at that hit: strategy_probs, the Pr < 0.04 test of
+   select_strategy, mix_view (alpha, G1), ggx_eval / ggx_pdf, sample_ggx, and btdf_eval under RTX_FLAG_TRANSMISSION — for the triangle-light NEE, the environment NEE and the
+   continuation alike.  Untouched: Kd / Kd', Ke, dissolve, Ni, the light list, the hit, the random-number sequence.  Under RTX_FLAG_LAMBERT_ONLY none of the three is read: the
+   frame is the unmapped frame to the bit, and the Lambert kernels that frame launches are launched.
+   ENERGY TABLE.  A material's multiscatter look-up (LUT, 16 floats) is generated from ITS roughness; rtx_set_ess_table(ctx, table, rows) hands the library the look-ups of `rows`
+   roughnesses so that the energy compensation can follow Pr': row r (16 floats) is the LUT of roughness r / (rows - 1).  2 <= rows <= 256, every value finite; NULL / 0 clears
+   the table; RTX_ERR_INVALID leaves everything untouched.  A table edit like the map calls: it needs rtx_commit_scene, a commit after it alone uploads tables only, and
+   rtx_set_materials does not clear it.  At a hit whose material has RTX_MAP_PR >= 0, while a table A is set, mix_view takes Ess from the table instead of m.LUT — rows first, so
+   that a constant map equals a material:
+       fr = Pr' * (float)(rows - 1);  r0 = clamp((int)floorf(fr), 0, rows - 1);  r1 = min(r0 + 1, rows - 1);  wr = fr - (float)r0
+       i0, i1, w from NdotV exactly as ess_lut (NdotV saturated, f = NdotV * 15.0f, i0 = (int)floorf(f), i1 = min(i0 + 1, 15), w = f - (float)i0)
+       L[i] = A[r0][i] + wr * (A[r1][i] - A[r0][i])     for i = i0, i1
+       Ess  = L[i0] + w * (L[i1] - L[i0])
+   With no table set, or on a material without a roughness map, m.LUT is read as before: that is then the energy compensation of the TABLE's roughness m.Pr, not of Pr'.
+   CONSEQUENCES.  (a) A scene in which every mapped triangle sees one texel value over its whole area is, bit for bit, the unmapped scene whose triangles carry materials with
+   Ks', Pr', Pm' — and, where a table is set and the roughness is mapped, with LUT[i] = A[r0][i] + wr * (A[r1][i] - A[r0][i]) for all 16 i.  (b) An all-255 linear map with no
+   table set changes nothing, to the bit: the table's values are binary16-rounded already.
+   WHO SEES IT.  rtx_render, rtx_render_adaptive, rtx_debug_specular, rtx_debug_ess.  IGNORED BY rtx_render_v6_pass1, rtx_render_restir, rtx_denoise and its map guides,
+   rtx_read_layer and the other debug probes — as they ignore map_Kd.
+   CALLS AND COMMITS follow the map_Kd / NORMAL MAPS rules word for word: valid before the first commit and on a resident scene; rtx_commit_scene again (rendering in between is
+   RTX_ERR_STATE); RTX_ERR_INVALID leaves the scene committed and untouched; rtx_set_materials resets the three slots to -1; on a resident general scene a map-only commit
+   uploads tables only (rtx_stats.bvh_refits and rtx_debug_tree_hash unchanged); a tiny scene (<= 64 triangles) runs on the general BVH path while a non-emitting material that
+   a triangle uses has one of the three maps, and the commit that crosses that line is a rebuild; rtx_save_scene_cache with one bound is RTX_ERR_STATE.  RTX_OPT_FUSED_BVH,
+   RTX_OPT_SHADE_DENSE and RTX_OPT_SORT_MATERIALS are ignored while one is active; RTX_OPT_COMPACT_STATE 0 and 1 both work. */
 #define RTX_TEX_SRGB 1u
 enum { RTX_MAP_KD = 0, RTX_MAP_OPACITY = 2 };      /* 1 is not a slot: it stays RTX_ERR_INVALID, as it always was */
 enum { RTX_MAP_NORMAL = 4 };                       /* ... and neither is 3 */
+enum { RTX_MAP_KS = 6, RTX_MAP_PR = 8, RTX_MAP_PM = 10 };      /* ... nor 5, 7, 9 (SPECULAR MAPS) */
 int  rtx_set_mesh_uvs(rtx_ctx*, uint32_t mesh, const float* uv2 /* nidx pairs; NULL clears */, uint32_t nidx);
 int  rtx_set_texture(rtx_ctx*, uint32_t tex /* <= current count; == count appends */, const void* rgba8, uint32_t width, uint32_t height, uint32_t flags);
 int  rtx_set_material_map(rtx_ctx*, uint32_t material, uint32_t slot, int32_t tex /* -1 = none */);
+int  rtx_set_ess_table(rtx_ctx*, const float* table /* rows x 16 */, uint32_t rows);      /* SPECULAR MAPS, ENERGY TABLE; NULL / 0 clears */
+/* tests: SPECULAR MAPS by the device function k_shade runs — hits4 as rtx_debug_trace_closest writes them -> 8 words per record: Ks'.xyz, Pr', Pm', then the ks / pr / pm
+   texture id as uint bits or 0xFFFFFFFF (no map in that slot; an emitter and every hit while no specular map is active: the table's values and three 0xFFFFFFFF); a miss gives
+   five zeros and three 0xFFFFFFFF.  rtx_debug_ess: the Ess mix_view would use for `material` at n (Pr', NdotV) pairs — the table path or m.LUT, by the rule above */
+int  rtx_debug_specular(rtx_ctx*, const float* hits4, uint32_t n, float* out8);
+int  rtx_debug_ess(rtx_ctx*, uint32_t material, const float* pr, const float* ndotv, uint32_t n, float* out);
 /* tests: the device's sampler — n (s, t) pairs -> (r, g, b, 0) — and the device's per-hit albedo — hits4 as rtx_debug_trace_closest writes them -> (Kd' (m.Kd where the
    material has no map), texture id as uint bits or 0xFFFFFFFF); a miss gives (0, 0, 0, 0xFFFFFFFF).  rays8 may be NULL: the albedo depends on the hit record alone */
 int  rtx_debug_texture_sample(rtx_ctx*, uint32_t tex, const float* uv2, uint32_t n, float* out4);

@@ -35,6 +35,11 @@ rtxh_scene* rtxh_scene_from_obj(const char* const* files, uint32_t nfiles, const
 #define RTXH_OBJ_NO_NORMAL_MAPS  8u
 #define RTXH_OBJ_BUMP_AS_NORMAL 16u
 #define RTXH_OBJ_NORMAL_FLIP_Y  32u
+/* ... and for the specular maps (include/rtx.h, SPECULAR MAPS): by default the images the map_Ks / map_Pr / map_Pm statements name are bound as RTX_MAP_KS / RTX_MAP_PR / RTX_MAP_PM,
+   and a material that gets a map has a ZERO scalar set to one — Pr == 0 -> 1 (its LUT regenerated), Pm == 0 -> 1, Ks == (0, 0, 0) -> (1, 1, 1): the map multiplies the scalar, and 0
+   is what the parser records for a scalar the file does not give.  A stated deviation from the reference's record, made only where a map is bound.
+   RTXH_OBJ_NO_SPEC_MAPS = none bound, the records as parsed (NO_TEXTURES implies it) */
+#define RTXH_OBJ_NO_SPEC_MAPS   64u
 rtxh_scene* rtxh_scene_from_obj_ex(const char* const* files, uint32_t nfiles, const char* mtl_dir, uint32_t flags);
 /* ... with channel 0 of the map_Bump / bump image of a material without a norm taken as a HEIGHT map and converted on load (h = byte / 255, repeat wrap, central differences times
    bump_height, c = (-gx, -gy, 1) normalised, byte = clamp(floor(c * 127 + 128.5), 0, 255)); RTXH_OBJ_BUMP_AS_NORMAL is ignored here */
@@ -54,7 +59,8 @@ const void* rtxh_scene_materials(const rtxh_scene*);                       /* 12
    Kd, d, Ks, Ke, Pr, Pm, Ps, Pc only; Vertex.h:21 "ADD MAP IDs LATER"): Ni, Ns, illum, Ka, Tf / Kt, Pcr, aniso, anisor and one texture id per map
    statement (-1 = none; ids index rtxh_scene_texture).  Only scenes loaded from OBJ / MTL files carry it (index-aligned with the
    material table, default materials included).  Of all of it the kernels read ONE thing: the diffuse map, map[RTXH_MAP_KD], once its image is decoded and bound
-   (rtx_set_material_map, include/rtx.h) — the reference's shaders sample no textures, this library's k_shade samples map_Kd; every other slot stays a name. */
+   (rtx_set_material_map, include/rtx.h) — the reference's shaders sample no textures, this library's k_shade samples map_Kd; map_d, norm (map_Bump / bump on request), map_Ks, map_Pr and map_Pm are bound
+   by the accessors further down (rtxh_scene_opacity_map, rtxh_scene_normal_map, rtxh_scene_spec_map); every other slot stays a name. */
 #define RTXH_NUM_MAP_SLOTS 13
 enum { RTXH_MAP_KA = 0, RTXH_MAP_KD, RTXH_MAP_KS, RTXH_MAP_KE, RTXH_MAP_NS, RTXH_MAP_BUMP, RTXH_MAP_D, RTXH_MAP_DISP, RTXH_MAP_REFL, RTXH_MAP_PR, RTXH_MAP_PM, RTXH_MAP_PS, RTXH_MAP_NORM };
 typedef struct rtxh_material_ext { float Ni, Ns, Pcr, aniso, anisor; int32_t illum; float Ka[3], Tf[3]; int32_t map[RTXH_NUM_MAP_SLOTS]; } rtxh_material_ext;
@@ -70,6 +76,9 @@ int         rtxh_scene_opacity_map(const rtxh_scene*, uint32_t material);
 /* the texture the scene binds as the material's normal map (RTX_MAP_NORMAL: its norm image; on request its map_Bump / bump image, as it is or converted from a height map), or -1.
    A converted or flipped image that another slot reads too is a copy appended behind the files' textures */
 int         rtxh_scene_normal_map(const rtxh_scene*, uint32_t material);
+/* the texture the scene binds in the material's RTX_MAP_KS / RTX_MAP_PR / RTX_MAP_PM slot (its map_Ks / map_Pr / map_Pm image; one packed file may serve several), or -1; also -1 for
+   any other slot value */
+int         rtxh_scene_spec_map(const rtxh_scene*, uint32_t material, uint32_t slot);
 /* the per-corner texture coordinates of mesh i (the OBJ's vt): one (u, v) pair per index entry, parallel to rtxh_scene_mesh's indices; NULL / 0 for a mesh without any */
 int         rtxh_scene_mesh_uvs(const rtxh_scene*, uint32_t i, const float** uv2, uint32_t* nidx);
 /* the image readers alone: width / height always, the pixels when capacity holds width * height * 4 bytes; RTX_ERR_INVALID + rtxh_last_error for a file they cannot read */

@@ -51,6 +51,9 @@ TEX_SRGB = 1          # rtx_set_texture flag: the bytes are sRGB-encoded
 MAP_KD = 0            # rtx_set_material_map slot
 MAP_OPACITY = 2       # ... the alpha cut-out slot: reads the texture's alpha byte (1 is not a slot)
 MAP_NORMAL = 4        # ... the tangent-space normal map slot: reads the texture's RGB bytes through Nt (3 is not a slot)
+MAP_KS = 6            # ... the specular colour slot: reads the RGB bytes, sRGB honoured (5, 7 and 9 are not slots)
+MAP_PR = 8            # ... the roughness slot: reads the green byte through the linear table
+MAP_PM = 10           # ... the metalness slot: reads the blue byte through the linear table
 ENV_HIDDEN = 1        # rtx_set_environment flag: primary rays that miss stay black
 
 
@@ -118,6 +121,9 @@ _sig("rtx_debug_texture_sample", C.c_int, _vp, _u32, _vp, _u32, _vp)
 _sig("rtx_debug_albedo", C.c_int, _vp, _vp, _vp, _u32, _vp)
 _sig("rtx_debug_opacity", C.c_int, _vp, _vp, _u32, _vp)
 _sig("rtx_debug_shading_normal", C.c_int, _vp, _vp, _vp, _u32, _vp)
+_sig("rtx_set_ess_table", C.c_int, _vp, _vp, _u32)
+_sig("rtx_debug_specular", C.c_int, _vp, _vp, _u32, _vp)
+_sig("rtx_debug_ess", C.c_int, _vp, _u32, _vp, _vp, _u32, _vp)
 _sig("rtx_debug_tri_tangents", C.c_int, _vp, _u32, _u32, _vp)
 _sig("rtx_set_environment", C.c_int, _vp, _vp, _u32, _vp, C.c_float, _u32)
 _sig("rtx_debug_env_sample", C.c_int, _vp, _vp, _u32, _vp)
@@ -217,6 +223,7 @@ _sig("rtxh_scene_from_obj_ex", _vp, C.POINTER(C.c_char_p), _u32, C.c_char_p, _u3
 _sig("rtxh_scene_opacity_map", C.c_int, _vp, _u32)
 _sig("rtxh_scene_from_obj_ex2", _vp, C.POINTER(C.c_char_p), _u32, C.c_char_p, _u32, C.c_float)
 _sig("rtxh_scene_normal_map", C.c_int, _vp, _u32)
+_sig("rtxh_scene_spec_map", C.c_int, _vp, _u32, _u32)
 _sig("rtxh_scene_free", None, _vp)
 _sig("rtxh_scene_save", C.c_int, _vp, C.c_char_p)
 _sig("rtxh_scene_load", _vp, C.c_char_p)
@@ -330,6 +337,9 @@ class Scene:
         self.opacity_maps = [int(lib.rtxh_scene_opacity_map(handle, i)) for i in range(n)]
         # ... and for the normal maps (norm; on request map_Bump / bump, as it is or converted from a height map)
         self.normal_maps = [int(lib.rtxh_scene_normal_map(handle, i)) for i in range(n)]
+        # ... and for the specular, roughness and metalness maps (map_Ks / map_Pr / map_Pm); ess_table: the 17-row energy table that goes with a roughness map, else None
+        self.ks_maps, self.pr_maps, self.pm_maps = ([int(lib.rtxh_scene_spec_map(handle, i, slot)) for i in range(n)] for slot in (MAP_KS, MAP_PR, MAP_PM))
+        self.ess_table = ess_table_rows(17) if any(t >= 0 for t in self.pr_maps) else None
         self.meshes, self.uvs = [], []
         for i in range(lib.rtxh_scene_num_meshes(handle)):
             v, idx, mid = _vp(), _vp(), _vp()
@@ -373,13 +383,14 @@ class Scene:
         return cls((lib.rtxh_scene_bistro_class_hard if hard else lib.rtxh_scene_bistro_class)(target_tris, seed))
 
     @classmethod
-    def from_obj(cls, files, mtl_dir, textures=True, cutouts=True, kd_alpha=False, normal_maps=True, bump=None, flip_y=False):
+    def from_obj(cls, files, mtl_dir, textures=True, cutouts=True, kd_alpha=False, normal_maps=True, bump=None, flip_y=False, spec_maps=True):
         """textures=False: decode no image; cutouts=False: bind no map_d image as an opacity map; kd_alpha=True: a material without a map_d whose map_Kd file is a
         32-bit TGA gets that texture as its opacity map too (rtx_render --no-textures / --no-cutouts / --kd-alpha); normal_maps=False: bind no norm image as a normal
         map; bump="normal": a material without a norm takes its map_Bump / bump image as a normal map, bump=S (a number): as a height map converted with strength S;
-        flip_y=True: DirectX-style maps, green negated on load (--no-normal-maps / --bump-as-normal / --bump-height S / --normal-flip-y)"""
+        flip_y=True: DirectX-style maps, green negated on load (--no-normal-maps / --bump-as-normal / --bump-height S / --normal-flip-y); spec_maps=False: bind no
+        map_Ks / map_Pr / map_Pm image and leave the records as parsed (with them, a bound map sets a zero Ks / Pr / Pm to one: --no-spec-maps)"""
         arr = (C.c_char_p * len(files))(*[f.encode() for f in files])
-        flags = (0 if textures else 1) | (0 if cutouts else 2) | (4 if kd_alpha else 0) | (0 if normal_maps else 8) | (16 if bump == "normal" else 0) | (32 if flip_y else 0)
+        flags = (0 if textures else 1) | (0 if cutouts else 2) | (4 if kd_alpha else 0) | (0 if normal_maps else 8) | (16 if bump == "normal" else 0) | (32 if flip_y else 0) | (0 if spec_maps else 64)
         if bump is not None and bump != "normal":
             return cls(lib.rtxh_scene_from_obj_ex2(arr, len(files), mtl_dir.encode(), flags, float(bump)))
         return cls(lib.rtxh_scene_from_obj_ex(arr, len(files), mtl_dir.encode(), flags))
@@ -478,6 +489,11 @@ def perspective_fov_rh(fovy_rad, aspect, zn, zf):
     p = np.zeros(16, np.float32)
     lib.rtxh_perspective_fov_rh(fovy_rad, aspect, zn, zf, _fptr(p))
     return p
+
+
+def ess_table_rows(rows):
+    """an energy table for Context.set_ess_table: (rows, 16) float32, row r = generate_ess_lut(r / (rows - 1))"""
+    return np.stack([generate_ess_lut(np.float32(r) / np.float32(rows - 1)) for r in range(rows)]).astype(np.float32)
 
 
 def generate_ess_lut(roughness):
@@ -671,7 +687,7 @@ class Context:
         self._ck(lib.rtx_set_texture(self._h, int(tex), _ptr(a), a.shape[1], a.shape[0], TEX_SRGB if srgb else 0), "rtx_set_texture")
 
     def set_material_map(self, material, tex, slot=MAP_KD):
-        """the material's map in `slot` (MAP_KD, MAP_OPACITY, MAP_NORMAL) := texture id `tex`, -1 / None = none"""
+        """the material's map in `slot` (MAP_KD, MAP_OPACITY, MAP_NORMAL, MAP_KS, MAP_PR, MAP_PM) := texture id `tex`, -1 / None = none"""
         self._ck(lib.rtx_set_material_map(self._h, int(material), int(slot), -1 if tex is None else int(tex)), "rtx_set_material_map")
 
     def texture_sample(self, tex, uvs):
@@ -705,6 +721,33 @@ class Context:
         self._ck(lib.rtx_debug_shading_normal(self._h, _ptr(r), _ptr(h), len(h), _ptr(out)), "rtx_debug_shading_normal")
         return out
 
+    def set_ess_table(self, table):
+        """the energy table of the specular maps: (rows, 16) float32, row r = the multiscatter LUT of roughness r / (rows - 1), 2 <= rows <= 256; None clears.  Needs commit()"""
+        if table is None:
+            self._ck(lib.rtx_set_ess_table(self._h, None, 0), "rtx_set_ess_table")
+            return
+        a = _f32(table)
+        if a.ndim != 2 or a.shape[1] != 16:
+            raise ValueError("set_ess_table: a (rows, 16) array")
+        self._ck(lib.rtx_set_ess_table(self._h, _ptr(a), a.shape[0]), "rtx_set_ess_table")
+
+    def specular(self, hits4):
+        """Ks', Pr', Pm' under the specular maps at hit records (trace_closest), by the device function k_shade runs -> ((n, 5) float32, (n, 3) uint32: the ks / pr / pm
+        texture ids or 0xFFFFFFFF); a miss gives zeros and 0xFFFFFFFF"""
+        h = _f32(hits4).reshape(-1, 4)
+        out = np.zeros((len(h), 8), np.float32)
+        self._ck(lib.rtx_debug_specular(self._h, _ptr(h), len(h), _ptr(out)), "rtx_debug_specular")
+        return out[:, :5].copy(), out[:, 5:].copy().view(np.uint32)
+
+    def ess(self, material, pr, ndotv):
+        """the Ess the view terms would use for `material` at (Pr', NdotV) pairs: the energy table where the material has a roughness map and a table is set, else its LUT"""
+        a = _f32(pr).reshape(-1); b = _f32(ndotv).reshape(-1)
+        if len(a) != len(b):
+            raise ValueError("ess: pr and ndotv differ in length")
+        out = np.zeros(len(a), np.float32)
+        self._ck(lib.rtx_debug_ess(self._h, int(material), _ptr(a), _ptr(b), len(a), _ptr(out)), "rtx_debug_ess")
+        return out
+
     def tri_tangents(self, first=0, count=None):
         """the device's tangent table: (count, 6) float32, object-space T and B per global triangle id; RtxError (RTX_ERR_STATE) while no normal map is active"""
         if count is None:
@@ -716,7 +759,8 @@ class Context:
     def bind_maps(self, scene):
         """the optional texture attributes of a scene (duck-typed): `uvs` — per mesh an (index count, 2) array or None; `textures` — a list whose entries are (H, W, 4)
         uint8 arrays or (array, srgb) pairs, anything else (a file name without pixels) is skipped; `material_maps` — per material an index into `textures` or -1 / None;
-        `opacity_maps`, `normal_maps` — likewise for the MAP_OPACITY and MAP_NORMAL slots.  A map whose texture was skipped is not bound."""
+        `opacity_maps`, `normal_maps`, `ks_maps`, `pr_maps`, `pm_maps` — likewise for the MAP_OPACITY, MAP_NORMAL, MAP_KS, MAP_PR and MAP_PM slots; `ess_table` — a
+        (rows, 16) energy table for set_ess_table, or None.  A map whose texture was skipped is not bound."""
         for mesh, uv in enumerate(getattr(scene, "uvs", None) or []):
             if uv is not None and len(uv):
                 self.set_mesh_uvs(mesh, uv)
@@ -736,6 +780,12 @@ class Context:
         for mat, t in enumerate(getattr(scene, "normal_maps", None) or []):
             if t is not None and t >= 0 and t in ids:
                 self.set_material_map(mat, ids[t], MAP_NORMAL)
+        for attr, slot in (("ks_maps", MAP_KS), ("pr_maps", MAP_PR), ("pm_maps", MAP_PM)):
+            for mat, t in enumerate(getattr(scene, attr, None) or []):
+                if t is not None and t >= 0 and t in ids:
+                    self.set_material_map(mat, ids[t], slot)
+        if getattr(scene, "ess_table", None) is not None:
+            self.set_ess_table(scene.ess_table)
 
     def set_environment(self, img, to_world=None, scale=1.0, hidden=False):
         """environment lighting: img = (N, N, 3) float32 octahedral map of linear radiance (row = v, column = u; latlong_to_octahedral makes one), or None to clear;

@@ -18,6 +18,13 @@ struct MatGPU {
     float alpha, Ni, pad1, pad2;    // EXTENSION (strategy 3, RTX_FLAG_TRANSMISSION): dissolve = Kd.w (fp16-rounded, MaterialOptimized.Kd.w) and the full-precision Material.Ni
 };
 static_assert(sizeof(MatGPU) == 160, "MatGPU must be 160 bytes");
+// SPECULAR MAPS (include/rtx.h; rtx_specmap.hpp): Ks', Pr', Pm' of ONE shading point, formed once per hit by k_shade<.., SPC> and handed to the functions below beside the
+// material, as kdpi is — five floats by value, no per-lane copy of the 160-byte record.  Every `sp` below defaults to nullptr = the material's own values: a caller that
+// passes none compiles to what it compiled to before the parameter existed (the choice is a constant after inlining).
+struct SpecView { float Ks[3]; float Pr, Pm; };
+RTX_HD f3 spec_ks(const MatGPU& m, const SpecView* sp) { return sp ? mk3(sp->Ks[0], sp->Ks[1], sp->Ks[2]) : mk3(m.Ks[0], m.Ks[1], m.Ks[2]); }
+RTX_HD float spec_pr(const MatGPU& m, const SpecView* sp) { return sp ? sp->Pr : m.Pr; }
+RTX_HD float spec_pm(const MatGPU& m, const SpecView* sp) { return sp ? sp->Pm : m.Pm; }
 
 // GGX_v6.hlsl:26-29; pow(abs(1-c),5) written as repeated multiplication
 RTX_HD f3 schlick(f3 F0, float cosT) {
@@ -54,19 +61,38 @@ RTX_HD float ess_lut(const MatGPU& m, float NdotV) {
     float v0 = m.LUT[i0], v1 = m.LUT[i1];
     return v0 + w * (v1 - v0);
 }
+// SPECULAR MAPS, energy table (include/rtx.h: rtx_set_ess_table): Ess of roughness Pr at NdotV from `rows` LUTs of 16 (row r = roughness r / (rows - 1)) — rows first, then
+// NdotV as ess_lut, so that a constant roughness map equals a material whose LUT is the blended row.  float32 in the written order
+RTX_HD float ess_table(const float* tab, uint32_t rows, float Pr, float NdotV) {
+    const int last = (int)rows - 1;
+    const float fr = Pr * (float)last;
+    int r0 = (int)floorf(fr);
+    r0 = r0 < 0 ? 0 : (r0 > last ? last : r0);
+    const int r1 = r0 + 1 < last ? r0 + 1 : last;
+    const float wr = fr - (float)r0;
+    NdotV = saturate(NdotV);
+    const float f = NdotV * 15.0f;
+    const int i0 = (int)floorf(f);
+    const int i1 = i0 + 1 < 15 ? i0 + 1 : 15;
+    const float w = f - (float)i0;
+    const float* A0 = tab + (size_t)r0 * 16u; const float* A1 = tab + (size_t)r1 * 16u;
+    const float a0 = A0[i0], a1 = A0[i1];
+    const float L0 = a0 + wr * (A1[i0] - a0), L1 = a1 + wr * (A1[i1] - a1);
+    return L0 + w * (L1 - L0);
+}
 // Lambertian_v6.hlsl:54-58
 RTX_HD f3 lambert_eval(const MatGPU& m) { return mk3(m.KdPi[0], m.KdPi[1], m.KdPi[2]); }   // Kd / PI (Lambertian_v6.hlsl:44-50), precomputed in MatGPU
 // Lambertian_v6.hlsl:61-64 (L = -incoming)
 RTX_HD float lambert_pdf(f3 n, f3 L) { return maxf_(dot(n, L), kEps) * kInvPI; }
 // GGX_v6.hlsl:174-206 (dot products are not clamped in v6)
-RTX_HD f3 ggx_eval(const MatGPU& m, f3 normal, f3 Lin, f3 Vin) {
+RTX_HD f3 ggx_eval(const MatGPU& m, f3 normal, f3 Lin, f3 Vin, const SpecView* sp = nullptr) {
     f3 N = normalize(normal), V = normalize(Vin), L = normalize(Lin);
     f3 H = normalize(V + L);
     float NdotV = dot(N, V), NdotL = dot(N, L), NdotH = dot(N, H), VdotH = dot(V, H);
-    f3 Ks = mk3(m.Ks[0], m.Ks[1], m.Ks[2]);
+    f3 Ks = spec_ks(m, sp); const float Pr = spec_pr(m, sp);
     f3 F = schlick(Ks, VdotH);
-    float D = d_ggx(NdotH, m.Pr);
-    float G = g2_smith(NdotV, NdotL, m.Pr * m.Pr);
+    float D = d_ggx(NdotH, Pr);
+    float G = g2_smith(NdotV, NdotL, Pr * Pr);
     float den = 4.0f * NdotV * NdotL;
     if (den < kEps) return mk3(0.0f, 0.0f, 0.0f);
     f3 spec = mk3(F.x * D * G / den, F.y * D * G / den, F.z * D * G / den);
@@ -76,12 +102,13 @@ RTX_HD f3 ggx_eval(const MatGPU& m, f3 normal, f3 Lin, f3 Vin) {
     return finite3(r) ? r : mk3(0.0f, 0.0f, 0.0f);
 }
 // GGX_v6.hlsl:209-224
-RTX_HD float ggx_pdf(const MatGPU& m, f3 normal, f3 Lin, f3 Vin) {
+RTX_HD float ggx_pdf(const MatGPU& m, f3 normal, f3 Lin, f3 Vin, const SpecView* sp = nullptr) {
     f3 N = normalize(normal), V = normalize(Vin), L = normalize(Lin);
     f3 H = normalize(V + L);
     float NdotH = dot(N, H), NdotV = dot(N, V);
-    float alpha = m.Pr * m.Pr;
-    return g1_smith(NdotV, alpha) * d_ggx(NdotH, m.Pr) / (NdotV * 4.0f);
+    const float Pr = spec_pr(m, sp);
+    float alpha = Pr * Pr;
+    return g1_smith(NdotV, alpha) * d_ggx(NdotH, Pr) / (NdotV * 4.0f);
 }
 // ---- EXTENSION: strategy 3, rough dielectric transmission (RTX_FLAG_TRANSMISSION = 4) ----------------------------------------------------
 // The reference names the strategy and leaves it a stub: "3 - Refraction", `//p_d *= alpha;` ("Adjust for translucency"), `// Refraction,
@@ -102,7 +129,7 @@ RTX_HD float transmission_eta(const MatGPU& m, uint32_t flags, f3 outgoing, f3& 
     if (dot(normal, outgoing) < 0.0f) normal = -normal;
     return m.Ni;
 }
-RTX_HD f3 btdf_eval(const MatGPU& m, f3 normal, f3 Lin, f3 Vin, float eta_p, float& pdf) {
+RTX_HD f3 btdf_eval(const MatGPU& m, f3 normal, f3 Lin, f3 Vin, float eta_p, float& pdf, const SpecView* sp = nullptr) {
     pdf = 0.0f;
     const f3 zero = mk3(0.0f, 0.0f, 0.0f);
     f3 N = normalize(normal), V = normalize(Vin), L = normalize(Lin);
@@ -115,12 +142,13 @@ RTX_HD f3 btdf_eval(const MatGPU& m, f3 normal, f3 Lin, f3 Vin, float eta_p, flo
     float sq = VdotH + eta_p * LdotH;
     float den = sq * sq;
     if (den < kEps) return zero;
-    float alpha = m.Pr * m.Pr;
-    float D = d_ggx(dot(N, H), m.Pr);
+    const float Pr = spec_pr(m, sp);
+    float alpha = Pr * Pr;
+    float D = d_ggx(dot(N, H), Pr);
     float G = g2_smith(NdotV, -NdotL, alpha);
     float e2 = eta_p * eta_p;
     float c = D * G * e2 * (-LdotH) * VdotH / (NdotV * (-NdotL) * den);
-    f3 Fr = schlick(mk3(m.Ks[0], m.Ks[1], m.Ks[2]), VdotH);
+    f3 Fr = schlick(spec_ks(m, sp), VdotH);
     float q = g1_smith(NdotV, alpha) * VdotH * D / NdotV * (e2 * (-LdotH) / den);     // D_V(h) |dh / dwi|
     f3 f = mk3((1.0f - Fr.x) * c, (1.0f - Fr.y) * c, (1.0f - Fr.z) * c);
     if (!finite3(f) || is_nan(q) || is_inf(q)) return zero;
@@ -128,22 +156,22 @@ RTX_HD f3 btdf_eval(const MatGPU& m, f3 normal, f3 Lin, f3 Vin, float eta_p, flo
     return f;
 }
 // CalculateStrategyProbabilities, BRDF_v6.hlsl:50-70 -> (p_d, p_s); pt = the transmitted share of the diffuse part (extension; 0 when eta_p = 0)
-RTX_HD void strategy_probs(const MatGPU& m, f3 outgoing, f3 normal, uint32_t flags, float& pd, float& ps, float eta_p, float& pt) {
+RTX_HD void strategy_probs(const MatGPU& m, f3 outgoing, f3 normal, uint32_t flags, float& pd, float& ps, float eta_p, float& pt, const SpecView* sp = nullptr) {
     pt = 0.0f;
     if (flags & 1u) { pd = 1.0f; ps = 0.0f; return; }
-    f3 fr = schlick(mk3(m.Ks[0], m.Ks[1], m.Ks[2]), dot(normal, outgoing));
-    float p_s = minf_(1.0f, (fr.x + fr.y + fr.z) / 3.0f + m.Pm);
+    f3 fr = schlick(spec_ks(m, sp), dot(normal, outgoing));
+    float p_s = minf_(1.0f, (fr.x + fr.y + fr.z) / 3.0f + spec_pm(m, sp));
     ps = p_s; pd = 1.0f - p_s;
     if (eta_p != 0.0f) { pt = pd * (1.0f - m.alpha); pd = pd * m.alpha; }                // BRDF_v6.hlsl:28-29 `p_d *= alpha`
 }
 RTX_HD void strategy_probs(const MatGPU& m, f3 outgoing, f3 normal, uint32_t flags, float& pd, float& ps) { float pt; strategy_probs(m, outgoing, normal, flags, pd, ps, 0.0f, pt); }
 // SelectSamplingStrategy, BRDF_v6.hlsl:7-48.  RTX_FLAG_LAMBERT_ONLY draws no random number.
-RTX_HD uint32_t select_strategy(const MatGPU& m, f3 outgoing, f3 normal, uint32_t flags, uint32_t& s0, uint32_t& s1, float eta_p = 0.0f) {
+RTX_HD uint32_t select_strategy(const MatGPU& m, f3 outgoing, f3 normal, uint32_t flags, uint32_t& s0, uint32_t& s1, float eta_p = 0.0f, const SpecView* sp = nullptr) {
     if (flags & 1u) return 0u;
     float r = tea_next(s0, s1);
-    f3 fr = schlick(mk3(m.Ks[0], m.Ks[1], m.Ks[2]), dot(normal, outgoing));
-    float p_s = minf_(1.0f, (fr.x + fr.y + fr.z) / 3.0f + m.Pm);
-    if (r <= p_s) return m.Pr < 0.04f ? 0u : 1u;
+    f3 fr = schlick(spec_ks(m, sp), dot(normal, outgoing));
+    float p_s = minf_(1.0f, (fr.x + fr.y + fr.z) / 3.0f + spec_pm(m, sp));
+    if (r <= p_s) return spec_pr(m, sp) < 0.04f ? 0u : 1u;
     if (eta_p != 0.0f) {                                                                  // :41-47 with `p_d *= alpha` un-commented
         float p_d = (1.0f - p_s) * m.alpha;
         return r <= p_s + p_d ? 0u : 3u;
@@ -153,18 +181,18 @@ RTX_HD uint32_t select_strategy(const MatGPU& m, f3 outgoing, f3 normal, uint32_
 // F = p_d f_lambert + p_s f_ggx, P = p_d pdf_lambert + p_s pdf_ggx
 // (Sampler_v6.hlsl:443-457, Path_Sampler_v6.hlsl:66-80); with eta_p != 0 a direction on the far side of the interface gets p_t f_t, p_t pdf_t alone
 // kdpi (both forms): the diffuse colour / PI of THIS shading point where a texture map modulates it (k_shade<.., TEX>: tex_kdpi, rtx_texture.hpp); nullptr = the material's own
-RTX_HD void bsdf_mixture(const MatGPU& m, uint32_t flags, f3 normal, f3 L, f3 outgoing, f3& F, float& P, float& pd, float& ps, float eta_p = 0.0f, const f3* kdpi = nullptr) {
+RTX_HD void bsdf_mixture(const MatGPU& m, uint32_t flags, f3 normal, f3 L, f3 outgoing, f3& F, float& P, float& pd, float& ps, float eta_p = 0.0f, const f3* kdpi = nullptr, const SpecView* sp = nullptr) {
     float pt;
-    strategy_probs(m, outgoing, normal, flags, pd, ps, eta_p, pt);
+    strategy_probs(m, outgoing, normal, flags, pd, ps, eta_p, pt, sp);
     f3 f0 = kdpi ? *kdpi : lambert_eval(m); float q0 = lambert_pdf(normal, L);
     if (flags & 1u) { F = safe_mul(pd, f0); P = safe_mul(pd, q0); return; }
     if (eta_p != 0.0f && dot(normal, L) < 0.0f) {
-        float q3; f3 f3_ = btdf_eval(m, normal, L, outgoing, eta_p, q3);
+        float q3; f3 f3_ = btdf_eval(m, normal, L, outgoing, eta_p, q3, sp);
         F = safe_mul(pt, f3_); P = safe_mul(pt, q3);
         return;
     }
-    f3 f1 = ggx_eval(m, normal, L, outgoing);
-    float q1 = ggx_pdf(m, normal, L, outgoing);
+    f3 f1 = ggx_eval(m, normal, L, outgoing, sp);
+    float q1 = ggx_pdf(m, normal, L, outgoing, sp);
     F = safe_mul(pd, f0) + safe_mul(ps, f1);
     P = safe_mul(pd, q0) + safe_mul(ps, q1);
 }
@@ -175,28 +203,30 @@ RTX_HD void bsdf_mixture(const MatGPU& m, uint32_t flags, f3 normal, f3 L, f3 ou
 // select_strategy with those terms handed in: the SAME operations on the same operands in the same order, so every result is the same bits
 // (tests: test_bsdf_eval_and_sample_bit_exact runs the *_v forms; full-size frames unchanged).
 struct MixView { float pd, ps, pt; f3 N, V; float NdotV, alpha, g1v, kms; };
-RTX_HD MixView mix_view(const MatGPU& m, uint32_t flags, f3 normal, f3 outgoing, float eta_p = 0.0f) {
+// sp: SPECULAR MAPS; ess_tab / ess_rows: the energy table of rtx_set_ess_table where THIS hit takes its Ess from it (its material has a roughness map and a table is set), else nullptr
+RTX_HD MixView mix_view(const MatGPU& m, uint32_t flags, f3 normal, f3 outgoing, float eta_p = 0.0f, const SpecView* sp = nullptr, const float* ess_tab = nullptr, uint32_t ess_rows = 0u) {
     MixView mv;
-    strategy_probs(m, outgoing, normal, flags, mv.pd, mv.ps, eta_p, mv.pt);
+    strategy_probs(m, outgoing, normal, flags, mv.pd, mv.ps, eta_p, mv.pt, sp);
     mv.N = mk3(0.0f, 0.0f, 1.0f); mv.V = mv.N; mv.NdotV = 0.0f; mv.alpha = 0.0f; mv.g1v = 0.0f; mv.kms = 0.0f;
     if (flags & 1u) return mv;
     mv.N = normalize(normal); mv.V = normalize(outgoing);
     mv.NdotV = dot(mv.N, mv.V);
-    mv.alpha = m.Pr * m.Pr;
+    const float Pr = spec_pr(m, sp);
+    mv.alpha = Pr * Pr;
     mv.g1v = g1_smith(mv.NdotV, mv.alpha);
-    const float Ess = ess_lut(m, mv.NdotV);
+    const float Ess = ess_tab ? ess_table(ess_tab, ess_rows, Pr, mv.NdotV) : ess_lut(m, mv.NdotV);
     mv.kms = (1.0f - Ess) / Ess;
     return mv;
 }
 // ggx_eval / ggx_pdf with the view terms of mv (GGX_v6.hlsl:174-224)
-RTX_HD void ggx_eval_pdf_v(const MatGPU& m, const MixView& mv, f3 Lin, f3& f1, float& q1) {
+RTX_HD void ggx_eval_pdf_v(const MatGPU& m, const MixView& mv, f3 Lin, f3& f1, float& q1, const SpecView* sp = nullptr) {
     const f3 L = normalize(Lin);
     const f3 H = normalize(mv.V + L);
     const float NdotL = dot(mv.N, L), NdotH = dot(mv.N, H), VdotH = dot(mv.V, H);
-    const f3 Ks = mk3(m.Ks[0], m.Ks[1], m.Ks[2]);
+    const f3 Ks = spec_ks(m, sp); const float Pr = spec_pr(m, sp);
     const f3 F = schlick(Ks, VdotH);
-    const float D = d_ggx(NdotH, m.Pr);
-    const float G = g2_smith(mv.NdotV, NdotL, m.Pr * m.Pr);
+    const float D = d_ggx(NdotH, Pr);
+    const float G = g2_smith(mv.NdotV, NdotL, Pr * Pr);
     const float den = 4.0f * mv.NdotV * NdotL;
     q1 = mv.g1v * D / (mv.NdotV * 4.0f);
     if (den < kEps) { f1 = mk3(0.0f, 0.0f, 0.0f); return; }
@@ -204,23 +234,23 @@ RTX_HD void ggx_eval_pdf_v(const MatGPU& m, const MixView& mv, f3 Lin, f3& f1, f
     const f3 r = mk3(spec.x * (1.0f + Ks.x * mv.kms), spec.y * (1.0f + Ks.y * mv.kms), spec.z * (1.0f + Ks.z * mv.kms));
     f1 = finite3(r) ? r : mk3(0.0f, 0.0f, 0.0f);
 }
-RTX_HD void bsdf_mixture_v(const MatGPU& m, uint32_t flags, const MixView& mv, f3 normal, f3 L, f3 outgoing, f3& F, float& P, float eta_p = 0.0f, const f3* kdpi = nullptr) {
+RTX_HD void bsdf_mixture_v(const MatGPU& m, uint32_t flags, const MixView& mv, f3 normal, f3 L, f3 outgoing, f3& F, float& P, float eta_p = 0.0f, const f3* kdpi = nullptr, const SpecView* sp = nullptr) {
     f3 f0 = kdpi ? *kdpi : lambert_eval(m); float q0 = lambert_pdf(normal, L);
     if (flags & 1u) { F = safe_mul(mv.pd, f0); P = safe_mul(mv.pd, q0); return; }
     if (eta_p != 0.0f && dot(normal, L) < 0.0f) {
-        float q3; f3 f3_ = btdf_eval(m, normal, L, outgoing, eta_p, q3);
+        float q3; f3 f3_ = btdf_eval(m, normal, L, outgoing, eta_p, q3, sp);
         F = safe_mul(mv.pt, f3_); P = safe_mul(mv.pt, q3);
         return;
     }
-    f3 f1; float q1; ggx_eval_pdf_v(m, mv, L, f1, q1);
+    f3 f1; float q1; ggx_eval_pdf_v(m, mv, L, f1, q1, sp);
     F = safe_mul(mv.pd, f0) + safe_mul(mv.ps, f1);
     P = safe_mul(mv.pd, q0) + safe_mul(mv.ps, q1);
 }
-RTX_HD uint32_t select_strategy_v(const MatGPU& m, const MixView& mv, uint32_t flags, uint32_t& s0, uint32_t& s1, float eta_p = 0.0f) {
+RTX_HD uint32_t select_strategy_v(const MatGPU& m, const MixView& mv, uint32_t flags, uint32_t& s0, uint32_t& s1, float eta_p = 0.0f, const SpecView* sp = nullptr) {
     if (flags & 1u) return 0u;
     const float r = tea_next(s0, s1);
     const float p_s = mv.ps;
-    if (r <= p_s) return m.Pr < 0.04f ? 0u : 1u;
+    if (r <= p_s) return spec_pr(m, sp) < 0.04f ? 0u : 1u;
     if (eta_p != 0.0f) return r <= p_s + mv.pd ? 0u : 3u;             // mv.pd = (1 - p_s) alpha here (strategy_probs with eta_p != 0)
     return 0u;
 }
@@ -253,8 +283,9 @@ RTX_HD void coord_system(f3 N, f3& T, f3& B) {
     B = cross(N, T);
 }
 // SampleBRDF_GGX (Heitz 2018 VNDF), GGX_v6.hlsl:93-169: the visible half vector H (:104-157) ...
-RTX_HD f3 sample_ggx_h_disk(const MatGPU& m, f3 outgoing, f3 normal, float r, float sn, float cs, f3& V) {
-    float alpha = m.Pr * m.Pr;
+RTX_HD f3 sample_ggx_h_disk(const MatGPU& m, f3 outgoing, f3 normal, float r, float sn, float cs, f3& V, const SpecView* sp = nullptr) {
+    const float Pr = spec_pr(m, sp);
+    float alpha = Pr * Pr;
     f3 N = normalize(normal), T1, T2;
     V = normalize(outgoing);
     coord_system(N, T1, T2);
@@ -273,12 +304,12 @@ RTX_HD f3 sample_ggx_h_disk(const MatGPU& m, f3 outgoing, f3 normal, float r, fl
     f3 Ne = normalize(mk3(alpha * Nh.x, alpha * Nh.y, maxf_(0.0f, Nh.z)));
     return mk3(Ne.x * T1.x + Ne.y * T2.x + Ne.z * N.x, Ne.x * T1.y + Ne.y * T2.y + Ne.z * N.y, Ne.x * T1.z + Ne.y * T2.z + Ne.z * N.z);
 }
-RTX_HD f3 sample_ggx_h(const MatGPU& m, f3 outgoing, f3 normal, uint32_t& s0, uint32_t& s1, f3& V) {
+RTX_HD f3 sample_ggx_h(const MatGPU& m, f3 outgoing, f3 normal, uint32_t& s0, uint32_t& s1, f3& V, const SpecView* sp = nullptr) {
     float U1 = tea_next(s0, s1), U2 = tea_next(s0, s1);
     float r = sqrtf(U1);
     float phi = 2.0f * kPI * U2;
     float sn, cs; sincos_(phi, sn, cs);
-    return sample_ggx_h_disk(m, outgoing, normal, r, sn, cs, V);
+    return sample_ggx_h_disk(m, outgoing, normal, r, sn, cs, V, sp);
 }
 // ... and the direction reflected about it (:159-165)
 RTX_HD f3 ggx_reflect(f3 H, f3 V, f3 normal) {
@@ -288,8 +319,8 @@ RTX_HD f3 ggx_reflect(f3 H, f3 V, f3 normal) {
     if (dot(smp, normal) < 0.0f) smp = -smp;   // :164-165: flipped, not rejected
     return smp;
 }
-RTX_HD f3 sample_ggx(const MatGPU& m, f3 outgoing, f3 normal, uint32_t& s0, uint32_t& s1) {
-    f3 V; f3 H = sample_ggx_h(m, outgoing, normal, s0, s1, V);
+RTX_HD f3 sample_ggx(const MatGPU& m, f3 outgoing, f3 normal, uint32_t& s0, uint32_t& s1, const SpecView* sp = nullptr) {
+    f3 V; f3 H = sample_ggx_h(m, outgoing, normal, s0, s1, V, sp);
     f3 I = -V;
     float k = 2.0f * dot(H, I);
     f3 smp = mk3(I.x - k * H.x, I.y - k * H.y, I.z - k * H.z);
@@ -305,8 +336,8 @@ RTX_HD f3 btdf_refract(f3 H, f3 V, float eta_p) {
     float k = eta * c - sqrtf(1.0f - s2);
     return normalize(mk3(k * H.x - eta * V.x, k * H.y - eta * V.y, k * H.z - eta * V.z));
 }
-RTX_HD f3 sample_btdf(const MatGPU& m, f3 outgoing, f3 normal, float eta_p, uint32_t& s0, uint32_t& s1) {
-    f3 V; f3 H = sample_ggx_h(m, outgoing, normal, s0, s1, V);
+RTX_HD f3 sample_btdf(const MatGPU& m, f3 outgoing, f3 normal, float eta_p, uint32_t& s0, uint32_t& s1, const SpecView* sp = nullptr) {
+    f3 V; f3 H = sample_ggx_h(m, outgoing, normal, s0, s1, V, sp);
     float eta = 1.0f / eta_p;
     float c = dot(V, H);
     float s2 = eta * eta * (1.0f - c * c);
@@ -315,10 +346,10 @@ RTX_HD f3 sample_btdf(const MatGPU& m, f3 outgoing, f3 normal, float eta_p, uint
     return normalize(mk3(k * H.x - eta * V.x, k * H.y - eta * V.y, k * H.z - eta * V.z));
 }
 // SampleBRDF, BRDF_v6.hlsl:74-88
-RTX_HD f3 sample_bsdf(const MatGPU& m, uint32_t strategy, f3 outgoing, f3 normal, uint32_t& s0, uint32_t& s1, float eta_p = 0.0f) {
+RTX_HD f3 sample_bsdf(const MatGPU& m, uint32_t strategy, f3 outgoing, f3 normal, uint32_t& s0, uint32_t& s1, float eta_p = 0.0f, const SpecView* sp = nullptr) {
 #ifdef RTX_SAMPLE_PER_BRANCH    // (A/B build: every strategy branch with its own draws, as until round 4)
-    if (strategy == 3u) return sample_btdf(m, outgoing, normal, eta_p, s0, s1);
-    return strategy == 1u ? sample_ggx(m, outgoing, normal, s0, s1) : sample_lambert(normal, s0, s1);
+    if (strategy == 3u) return sample_btdf(m, outgoing, normal, eta_p, s0, s1, sp);
+    return strategy == 1u ? sample_ggx(m, outgoing, normal, s0, s1, sp) : sample_lambert(normal, s0, s1);
 #else
     // every strategy starts from the same disk sample: two draws, r = sqrt(U1), sine and cosine of 2 pi U2 — with the reference's two different values of "2 pi"
     // (Lambertian_v6.hlsl:10 against GGX_v6.hlsl's 2 * PI with PI = 3.1415), selected per lane before the one evaluation
@@ -328,7 +359,7 @@ RTX_HD f3 sample_bsdf(const MatGPU& m, uint32_t strategy, f3 outgoing, f3 normal
     const float ang = lambert ? kTwoPi * U2 : 2.0f * kPI * U2;
     float sn, cs; sincos_(ang, sn, cs);
     if (lambert) return sample_lambert_disk(normal, r, sn, cs);
-    f3 V; const f3 H = sample_ggx_h_disk(m, outgoing, normal, r, sn, cs, V);       // strategies 1 and 3 share the visible half vector
+    f3 V; const f3 H = sample_ggx_h_disk(m, outgoing, normal, r, sn, cs, V, sp);   // strategies 1 and 3 share the visible half vector
     return strategy == 3u ? btdf_refract(H, V, eta_p) : ggx_reflect(H, V, normal);
 #endif
 }

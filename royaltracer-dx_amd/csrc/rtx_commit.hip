@@ -71,7 +71,8 @@ static int sync_textures(rtx_ctx* c, bool renumbered, bool deformed) {
     S.built.maps_active = H.maps_active();
     const bool cut = S.built.cutouts_active = H.cutouts_active();
     const bool nrm = S.built.normals_active = H.normals_active();
-    const bool active = S.built.maps_active || cut || nrm;   // the UVs serve all three
+    const bool spc = S.built.spec_active = H.spec_active();
+    const bool active = S.built.maps_active || cut || nrm || spc;   // the UVs serve all four
     int r;
     if (H.tex_dirty) {                                       // (a scene that never saw one of the three setters allocates nothing here)
         std::vector<TexDesc> desc(H.textures.size()); std::vector<uint32_t> pool;
@@ -89,6 +90,15 @@ static int sync_textures(rtx_ctx* c, bool renumbered, bool deformed) {
             for (size_t m = 0; m < nmaps.size() && m < H.map_normal.size(); m++) nmaps[m] = H.map_normal[m];
             if ((r = upload(c, S.d_map_nrm, nmaps))) return r;
         }
+        if (!H.any_spec_map()) S.d_map_spec.release();
+        else {
+            const size_t nm = H.mats128.size() / 32;
+            std::vector<int32_t> smaps(nm * 3, -1);
+            for (int k = 0; k < 3; k++) for (size_t m = 0; m < nm && m < H.map_spec[k].size(); m++) smaps[k * nm + m] = H.map_spec[k][m];
+            if ((r = upload(c, S.d_map_spec, smaps))) return r;
+        }
+        if (!H.ess_rows) S.d_ess_tab.release();
+        else if ((r = upload(c, S.d_ess_tab, H.ess_table))) return r;
         if (!S.d_tex_lut.p) { std::vector<float> lut; fill_tex_lut(lut); if ((r = upload(c, S.d_tex_lut, lut))) return r; }
         S.ntex = (uint32_t)desc.size();
     }
@@ -418,7 +428,7 @@ int rtx_commit_scene(rtx_ctx* c) {
     // On the GPU: a scene that is already resident and not a tiny one (whose pre-test records depend on world positions).
     // a tiny scene leaves its pre-test records for the general path while a texture map is active and returns to them afterwards: the commit that crosses that line rebuilds
     {   size_t ntri_all = 0; for (const InstHost& in : c->host.insts) ntri_all += c->host.meshes[in.mesh].idx.size() / 3;
-        if (c->host.tex_dirty && ntri_all <= kSmallSceneMaxTris && (c->host.maps_active() != c->scene.built.maps_active || c->host.cutouts_active() != c->scene.built.cutouts_active || c->host.normals_active() != c->scene.built.normals_active)) c->host.topo_dirty = true;
+        if (c->host.tex_dirty && ntri_all <= kSmallSceneMaxTris && (c->host.maps_active() != c->scene.built.maps_active || c->host.cutouts_active() != c->scene.built.cutouts_active || c->host.normals_active() != c->scene.built.normals_active || c->host.spec_active() != c->scene.built.spec_active)) c->host.topo_dirty = true;
         // ... and so it does while an environment is bound
         if (c->host.env_dirty && ntri_all <= kSmallSceneMaxTris && (c->host.env.n != 0) != c->scene.built.env_active) c->host.topo_dirty = true; }
     bool build = !(c->opt.gpu_refit && gpu_refittable(c) && !c->host.topo_dirty);
@@ -465,6 +475,7 @@ int rtx_save_scene_cache(rtx_ctx* c, const char* path) {
     if (c->scene.host_mirror_stale) { c->err = "save_scene_cache: the per-triangle records were re-derived on the GPU after rtx_update_mesh_vertices and the host holds no current copy; commit with RTX_OPT_DEFORM_REBUILD 1 (host builder) to save a cache"; return RTX_ERR_STATE; }
     if (c->scene.built.any_hidden) { c->err = "save_scene_cache: an instance is hidden (rtx_set_instance_visible): the device's boxes and triangle records leave it out and the file format holds no visibility; show every instance and commit to save a cache"; return RTX_ERR_STATE; }
     if (c->host.env.n) { c->err = "save_scene_cache: an environment is bound (rtx_set_environment) and the file format holds no environment; clear it and commit to save a cache"; return RTX_ERR_STATE; }
+    if (c->host.any_spec_map()) { c->err = "save_scene_cache: a material has a specular, roughness or metalness map (rtx_set_material_map, RTX_MAP_KS / RTX_MAP_PR / RTX_MAP_PM) and the file format holds no texels; unmap every material and commit to save a cache"; return RTX_ERR_STATE; }
     if (c->host.any_normal_map()) { c->err = "save_scene_cache: a material has a normal map (rtx_set_material_map, RTX_MAP_NORMAL) and the file format holds no texels; unmap every material and commit to save a cache"; return RTX_ERR_STATE; }
     if (c->host.any_opacity_map()) { c->err = "save_scene_cache: a material has an opacity map (rtx_set_material_map, RTX_MAP_OPACITY) and the file format holds no texels; unmap every material and commit to save a cache"; return RTX_ERR_STATE; }
     if (c->host.any_map()) { c->err = "save_scene_cache: a material has a texture map (rtx_set_material_map) and the file format holds no texels; unmap every material and commit to save a cache"; return RTX_ERR_STATE; }
@@ -521,9 +532,12 @@ static int finalise_scene(rtx_ctx* c) {
     const bool env_lit = s.env_n && c->scene.env_total > 0.0;
     s.env_tex = env_lit ? (const F4*)c->scene.d_env_tex.p : nullptr; s.env_marg = env_lit ? (const float*)c->scene.d_env_marg.p : nullptr; s.env_cond = env_lit ? (const float*)c->scene.d_env_cond.p : nullptr;
     // (a scene with cut-outs and no diffuse map: k_shade<.., TEX> runs all the same, selected by tri_uv, and reads a map_kd table of -1s — every material keeps its own Kd)
-    const bool uv_active = B.maps_active || B.cutouts_active || B.normals_active;
+    const bool uv_active = B.maps_active || B.cutouts_active || B.normals_active || B.spec_active;
     s.tri_uv = uv_active ? (const float*)c->scene.d_tri_uv.p : nullptr; s.map_kd = uv_active ? (const int32_t*)c->scene.d_map_kd.p : nullptr;
     s.tri_cut = B.cutouts_active ? (const int32_t*)c->scene.d_tri_cut.p : nullptr;
+    {   const int32_t* ms = B.spec_active ? (const int32_t*)c->scene.d_map_spec.p : nullptr; const size_t nm = c->host.mats128.size() / 32;
+        s.map_ks = ms; s.map_pr = ms ? ms + nm : nullptr; s.map_pm = ms ? ms + 2 * nm : nullptr;
+        s.ess_tab = (B.spec_active && c->host.ess_rows) ? (const float*)c->scene.d_ess_tab.p : nullptr; s.ess_rows = s.ess_tab ? c->host.ess_rows : 0u; }
     s.tri_tan = B.normals_active ? (const float*)c->scene.d_tri_tan.p : nullptr; s.map_nrm = B.normals_active ? (const int32_t*)c->scene.d_map_nrm.p : nullptr;
     // LDS budget per workgroup: stack + top of tree + first triangles, kept <= 64 KiB
     // exact bound of the 8-wide tree, no slack: a level adds ONE entry (the rest of its hit siblings) and only where a node has >= 2 internal

@@ -130,6 +130,9 @@ struct rtx_ctx {
         // tangent-space normal maps: the per-material map ids with the other tables; tri_tan only while a normal map is active (BuiltScene::normals_active), rebuilt when UVs, the
         // triangle numbering or a mesh's vertices changed (object space: a transform-only commit leaves it alone)
         DevBuf d_tri_tan, d_map_nrm; bool tri_tan_valid = false;
+        // specular, roughness and metalness maps: the three per-material map tables back to back (ks | pr | pm, nmat entries each) and the energy table of rtx_set_ess_table,
+        // both with the other tables and only while the host holds a map resp. a table
+        DevBuf d_map_spec, d_ess_tab;
         // environment lighting (sync_environment, rtx_commit.hip): the tables of the bound map, rebuilt by the commit after rtx_set_environment; env_total = their weight sum
         DevBuf d_env_tex, d_env_marg, d_env_cond; double env_total = 0.0;
     } scene;

@@ -203,6 +203,42 @@ int rtx_debug_tri_tangents(rtx_ctx* c, uint32_t first, uint32_t count, float* ou
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return RTX_OK;
 }
+// Ks', Pr', Pm' under the specular maps (rtx_specmap.hpp), by the device function k_shade<.., SPC> runs for a lane that shades
+int rtx_debug_specular(rtx_ctx* c, const float* hits4, uint32_t n, float* out8) {
+    BIND(c);
+    if (!c->committed) { c->err = "scene not committed"; return RTX_ERR_STATE; }
+    if (!n) return RTX_OK;
+    if (!hits4 || !out8) { c->err = "specular: null array"; return RTX_ERR_INVALID; }
+    for (uint32_t i = 0; i < n; i++) {                       // a triangle id the scene does not have would index past the per-triangle tables
+        uint32_t prim; memcpy(&prim, &hits4[(size_t)i * 4 + 3], 4);
+        if (prim != kMissPrim && prim >= c->stats.triangles) { c->err = "specular: triangle id out of range"; return RTX_ERR_INVALID; }
+    }
+    DevBuf d_hits, d_out;
+    HIPCHK(c, d_hits.ensure((size_t)n * 16)); HIPCHK(c, d_out.ensure((size_t)n * 32));
+    TO_DEVICE(c, d_hits.p, hits4, (size_t)n * 16);
+    launch_dbg_specular(c->stream, c->dsc, (const F4*)d_hits.p, n, (float*)d_out.p);
+    HIPCHK(c, hipGetLastError());
+    TO_HOST(c, out8, d_out.p, (size_t)n * 32);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RTX_OK;
+}
+// the Ess the view terms take for `material` at n (Pr', NdotV) pairs: the energy table where the material has a roughness map and a table is set, else its own LUT
+int rtx_debug_ess(rtx_ctx* c, uint32_t material, const float* pr, const float* ndotv, uint32_t n, float* out) {
+    BIND(c);
+    if (!c->committed) { c->err = "scene not committed"; return RTX_ERR_STATE; }
+    if (material >= c->dsc.nmat) { c->err = "ess: unknown material"; return RTX_ERR_INVALID; }
+    if (!n) return RTX_OK;
+    if (!pr || !ndotv || !out) { c->err = "ess: null array"; return RTX_ERR_INVALID; }
+    DevBuf d_pr, d_nv, d_out;
+    HIPCHK(c, d_pr.ensure((size_t)n * 4)); HIPCHK(c, d_nv.ensure((size_t)n * 4)); HIPCHK(c, d_out.ensure((size_t)n * 4));
+    TO_DEVICE(c, d_pr.p, pr, (size_t)n * 4);
+    TO_DEVICE(c, d_nv.p, ndotv, (size_t)n * 4);
+    launch_dbg_ess(c->stream, c->dsc, material, (const float*)d_pr.p, (const float*)d_nv.p, n, (float*)d_out.p);
+    HIPCHK(c, hipGetLastError());
+    TO_HOST(c, out, d_out.p, (size_t)n * 4);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RTX_OK;
+}
 static int dbg_bsdf(rtx_ctx* c, bool sample, uint32_t mat, uint32_t flags, const float* in, uint32_t stride_in, uint32_t n, float* out8) {
     BIND(c);
     if (!c->committed) { c->err = "scene not committed"; return RTX_ERR_STATE; }

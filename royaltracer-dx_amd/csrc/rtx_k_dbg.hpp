@@ -3,6 +3,7 @@
 #pragma once
 #include "rtx_shade.hpp"
 #include "rtx_normalmap.hpp"
+#include "rtx_specmap.hpp"
 
 namespace rtx {
 
@@ -116,6 +117,36 @@ __global__ __launch_bounds__(kBlock) void k_dbg_shading_normal(DevScene sc, cons
         r = {sf.normal.x, sf.normal.y, sf.normal.z, u2f((uint32_t)tex)};
     }
     out[i] = r;
+}
+// Ks', Pr', Pm' of the specular maps (rtx_specmap.hpp: spec_view, as k_shade<.., SPC> runs it for a lane that shades) at n hit records -> 8 words per record: Ks'.xyz, Pr',
+// Pm', then the ks / pr / pm texture id bits; a miss gives five zeros and three 0xFFFFFFFF; an emitter and every hit while no specular map is active give the table's values
+// and three 0xFFFFFFFF
+__global__ __launch_bounds__(kBlock) void k_dbg_specular(DevScene sc, const F4* __restrict__ hits, uint32_t n, float* __restrict__ out8) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const F4 h = hits[i];
+    const uint32_t prim = f2u(h.w);
+    SpecView sv = {{0.0f, 0.0f, 0.0f}, 0.0f, 0.0f};
+    int32_t tex[3] = {-1, -1, -1};
+    if (prim != kMissPrim) {
+        const uint32_t mat = sc.shade[prim].mat;
+        if (mat < sc.nmat) {
+            const MatGPU& m = sc.mats[mat];
+            sv.Ks[0] = m.Ks[0]; sv.Ks[1] = m.Ks[1]; sv.Ks[2] = m.Ks[2]; sv.Pr = m.Pr; sv.Pm = m.Pm;
+            if (sc.map_pr && !(m.Ke_len > 0.0f)) sv = spec_view(sc, m, mat, prim, h.y, h.z, tex);
+        }
+    }
+    float* o = out8 + 8 * (size_t)i;
+    o[0] = sv.Ks[0]; o[1] = sv.Ks[1]; o[2] = sv.Ks[2]; o[3] = sv.Pr; o[4] = sv.Pm;
+    o[5] = u2f((uint32_t)tex[0]); o[6] = u2f((uint32_t)tex[1]); o[7] = u2f((uint32_t)tex[2]);
+}
+// the Ess the view terms of a hit on `material` take (mix_view: the energy table where spec_ess_table says so, else the material's LUT) at n (Pr', NdotV) pairs
+__global__ __launch_bounds__(kBlock) void k_dbg_ess(DevScene sc, uint32_t material, const float* __restrict__ pr, const float* __restrict__ ndotv, uint32_t n, float* __restrict__ out) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const MatGPU& m = sc.mats[material];
+    const float* tab = sc.map_pr ? spec_ess_table(sc, material) : nullptr;
+    out[i] = tab ? ess_table(tab, sc.ess_rows, pr[i], ndotv[i]) : ess_lut(m, ndotv[i]);
 }
 // the environment's sampler and lookup (rtx_env.hpp), as k_shade<.., ENV> runs them (the marginal CDF from global memory: the same values as its LDS copy)
 __global__ __launch_bounds__(kBlock) void k_dbg_env_sample(DevScene sc, const uint32_t* __restrict__ seeds2, uint32_t n, F4* __restrict__ out) {

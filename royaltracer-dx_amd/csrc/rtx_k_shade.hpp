@@ -4,6 +4,7 @@
 #pragma once
 #include "rtx_shade.hpp"
 #include "rtx_normalmap.hpp"
+#include "rtx_specmap.hpp"
 
 namespace rtx {
 
@@ -26,13 +27,18 @@ namespace rtx {
 // point casts one more NEE sample, towards the map, into shadow queue `nee` (env_marg: the marginal CDF, in LDS where k_shade found room).  ENV = false is the code as it was.
 // NRM (implies TEX): some material has a normal map (rtx_normalmap.hpp): the shading normal of a lane that shades is perturbed once, right after surface(), and everything
 // the lane does afterwards sees n' — three floats replaced, nothing more lives across the item.  NRM = false is the code as it was.
-template <bool LAMBERT, bool TEX = false, bool ENV = false, bool NRM = false>
+// SPC (implies TEX, never LAMBERT): some material has a specular, roughness or metalness map (rtx_specmap.hpp): Ks', Pr', Pm' of a lane that shades are formed once, next to
+// Kd' and n', and handed to the view terms, the NEE samples and the continuation as kdpi is — five floats live across the item, and where a roughness map meets an energy
+// table the view terms take their Ess from the table.  SPC = false is the code as it was.
+template <bool LAMBERT, bool TEX = false, bool ENV = false, bool NRM = false, bool SPC = false>
 __device__ __forceinline__ void shade_item(const DevScene& sc, const DevFrame& f, const DevPaths& p, uint32_t bounce, uint32_t nee, bool last, size_t qb,
                                            const uint32_t* __restrict__ myq, uint32_t* __restrict__ mynext, uint32_t* s_cnt, bool valid, uint32_t qi, Prof* pf, const float* lds_cdf = nullptr, const LightGPU* lds_lights = nullptr, const MatGPU* lds_mats = nullptr, const float* env_marg = nullptr) {
     PathState S = idle_path();
     Surf sf = idle_surf();
     bool shading = false;
     f3 kdv = mk3(0, 0, 0); const f3* kdpi = TEX ? &kdv : nullptr;
+    SpecView spv = {{0.0f, 0.0f, 0.0f}, 0.0f, 0.0f}; const SpecView* sp = SPC ? &spv : nullptr;
+    const float* ess_tab = nullptr;
 #ifndef RTX_NO_LDS_MATS
     const MatGPU* mats = lds_mats ? lds_mats : sc.mats;      // (uniform; k_shade stages a short material table beside the light list)
 #else
@@ -51,7 +57,8 @@ __device__ __forceinline__ void shade_item(const DevScene& sc, const DevFrame& f
             if (sf.mat < sc.nmat) {
                 const MatGPU& m = mats[sf.mat];
                 if (m.Ke_len > 0.0f) add_emissive(sc, p, S, sf, m, bounce, nee);   // Hit.hlsl:126, Sampler_v6.hlsl:457
-                else { shading = true; if (TEX) kdv = tex_kdpi(sc, m, sf.mat, prim, h.y, h.z); if (NRM) sf.normal = nrm_perturb(sc, sf, prim, h.y, h.z, -S.d); }
+                else { shading = true; if (TEX) kdv = tex_kdpi(sc, m, sf.mat, prim, h.y, h.z); if (NRM) sf.normal = nrm_perturb(sc, sf, prim, h.y, h.z, -S.d);
+                       if (SPC) { spv = spec_view(sc, m, sf.mat, prim, h.y, h.z); ess_tab = spec_ess_table(sc, sf.mat); } }
             }
         }
         else if (ENV) { PathState M = load_path_stream(p, src); M.pid = pid; env_miss(sc, p, M, bounce); }      // the ray left the scene
@@ -63,14 +70,14 @@ __device__ __forceinline__ void shade_item(const DevScene& sc, const DevFrame& f
     // the view-dependent terms of the mixture BSDF, once per shading point: the NEE samples and the continuation share them (rtx_bsdf.hpp: MixView)
     MixView mvs; const MixView* mv = nullptr;
 #ifndef RTX_NO_MIXVIEW          // (A/B build: make VARIANT=nomv VARFLAGS=-DRTX_NO_MIXVIEW)
-    if (!LAMBERT) { mvs = mix_view(*mp, f.flags, normal, outgoing, eta_p); mv = &mvs; }
+    if (!LAMBERT) { mvs = SPC ? mix_view(*mp, f.flags, normal, outgoing, eta_p, sp, ess_tab, sc.ess_rows) : mix_view(*mp, f.flags, normal, outgoing, eta_p); mv = &mvs; }
 #endif
     PF_MARK(2);
     for (uint32_t j = 0; j < nee; j++) {                                  // NEE: visibility deferred to k_trace_shadow
         bool push = false;
         F4 so = {0, 0, 0, 0}, sd = {0, 0, 0, 0}; f3 con = mk3(0, 0, 0);
         if (shading) { PF_COUNT(3); }
-        if (shading) push = nee_sample(sc, *mp, f.flags, nee, S, pos, normal, outgoing, so, sd, con, sc.nsmall != 0u && sf.near_hull, eta_p, mv, lds_cdf, lds_lights, kdpi);
+        if (shading) push = nee_sample(sc, *mp, f.flags, nee, S, pos, normal, outgoing, so, sd, con, sc.nsmall != 0u && sf.near_hull, eta_p, mv, lds_cdf, lds_lights, kdpi, sp);
         PF_MARK(3);
         if (push) { PF_COUNT(4); }
         const size_t seg = (size_t)j * f.qcap * gridDim.x + qb;           // NEE slot j, this workgroup's sub-queue
@@ -80,7 +87,7 @@ __device__ __forceinline__ void shade_item(const DevScene& sc, const DevFrame& f
     if (ENV) {                                                            // the environment's sample: NEE slot `nee`, after the triangle lights'
         bool push = false;
         F4 so = {0, 0, 0, 0}, sd = {0, 0, 0, 0}; f3 con = mk3(0, 0, 0);
-        if (shading) push = env_nee_sample(sc, env_marg, *mp, f.flags, S, pos, normal, outgoing, so, sd, con, eta_p, mv, kdpi);
+        if (shading) push = env_nee_sample(sc, env_marg, *mp, f.flags, S, pos, normal, outgoing, so, sd, con, eta_p, mv, kdpi, sp);
         const size_t seg = (size_t)nee * f.qcap * gridDim.x + qb;
         const uint32_t slot = block_push(push, &s_cnt[1 + nee]);
         if (push) { st_stream(p.sh_o + seg + slot, so); st_stream(p.sh_d + seg + slot, sd); st_stream(p.sh_c + seg + slot, F4{con.x, con.y, con.z, u2f(S.pid)}); }
@@ -89,7 +96,7 @@ __device__ __forceinline__ void shade_item(const DevScene& sc, const DevFrame& f
     bool alive = false;
     f3 smp = mk3(0, 0, 1); float P = 0.0f;
     if (shading && !last) { PF_COUNT(5); }
-    if (shading && !last) alive = bsdf_continue(*mp, f, bounce, S, normal, outgoing, smp, P, eta_p, mv, kdpi);
+    if (shading && !last) alive = bsdf_continue(*mp, f, bounce, S, normal, outgoing, smp, P, eta_p, mv, kdpi, sp);
     PF_MARK(5);
     if (alive) { PF_COUNT(6); }
     const uint32_t slot = block_push(alive, &s_cnt[0]);
@@ -142,12 +149,16 @@ __host__ __device__ inline uint32_t shade_env_lds(uint32_t lights_bytes, uint32_
 #ifndef RTX_SHADE_WAVES_NRM
 #define RTX_SHADE_WAVES_NRM 6      // ... of the NRM instantiations, with or without ENV (profiles/normalmap_kernel_resources.md)
 #endif
-template <bool SORT, bool LAMBERT, bool TEX = false, bool ENV = false, bool NRM = false>     // LAMBERT: RTX_FLAG_LAMBERT_ONLY as a compile-time constant (no GGX / transmission code in that instantiation); TEX: texture maps, ENV: environment lighting, NRM: normal maps (shade_item)
-__global__ __launch_bounds__(kBlock, (NRM ? RTX_SHADE_WAVES_NRM : ENV ? RTX_SHADE_WAVES_ENV : RTX_SHADE_WAVES)) void k_shade(DevScene sc, DevFrame f_in, DevPaths p, uint32_t bounce,
+#ifndef RTX_SHADE_WAVES_SPC
+#define RTX_SHADE_WAVES_SPC 5      // ... of the SPC instantiations, with or without ENV / NRM (profiles/specmap_kernel_resources.md)
+#endif
+template <bool SORT, bool LAMBERT, bool TEX = false, bool ENV = false, bool NRM = false, bool SPC = false>     // LAMBERT: RTX_FLAG_LAMBERT_ONLY as a compile-time constant (no GGX / transmission code in that instantiation); TEX: texture maps, ENV: environment lighting, NRM: normal maps, SPC: specular maps (shade_item)
+__global__ __launch_bounds__(kBlock, (SPC ? RTX_SHADE_WAVES_SPC : NRM ? RTX_SHADE_WAVES_NRM : ENV ? RTX_SHADE_WAVES_ENV : RTX_SHADE_WAVES)) void k_shade(DevScene sc, DevFrame f_in, DevPaths p, uint32_t bounce,
                                                   const uint32_t* __restrict__ queue, const uint32_t* __restrict__ qcount,
                                                   uint32_t* __restrict__ next_queue, uint32_t* __restrict__ next_count,
                                                   uint32_t* __restrict__ shcounts /* [nee][gridDim.x] */) {
     static_assert(!NRM || (TEX && !SORT), "the normal-mapped forms are TEX forms of the default kernel");
+    static_assert(!SPC || (TEX && !SORT && !LAMBERT), "the specular-mapped forms are GGX TEX forms of the default kernel");
     const DevFrame f = frame_with_lambert<LAMBERT>(f_in);
     constexpr uint32_t kSlots = kMaxNee + (ENV ? 1u : 0u);  // (the environment's slot follows the nee_samples <= kMaxNee triangle-light slots)
     __shared__ uint32_t s_cnt[1 + kMaxNee + (ENV ? 4u : 0u)];     // [0] next-queue length, [1 + j] shadow queue j length (ENV: one slot more, in a 16-byte step: the static LDS precedes the dynamic region, whose float4 reads need their alignment)
@@ -217,7 +228,7 @@ __global__ __launch_bounds__(kBlock, (NRM ? RTX_SHADE_WAVES_NRM : ENV ? RTX_SHAD
         }
         for (uint32_t base = threadIdx.x & ~63u; base < cn; base += kBlock) {
             const uint32_t i = base + (threadIdx.x & 63u);
-            shade_item<LAMBERT, TEX, ENV, NRM>(sc, f, p, bounce, nee, last, qb, myq, mynext, s_cnt, i < cn, cb + (SORT ? s_sorted[i] : i), pf, lds_cdf, lds_lights, lds_mats, env_marg);
+            shade_item<LAMBERT, TEX, ENV, NRM, SPC>(sc, f, p, bounce, nee, last, qb, myq, mynext, s_cnt, i < cn, cb + (SORT ? s_sorted[i] : i), pf, lds_cdf, lds_lights, lds_mats, env_marg);
         }
         if (SORT) __syncthreads();                              // the next chunk overwrites the LDS buffers
     }

@@ -194,6 +194,16 @@ void launch_shade(hipStream_t st, const DevScene& sc, const DevFrame& f, const D
         constexpr bool LL = decltype(lam)::value;
         // a texture map is active: the default kernel's TEX form, whatever RTX_OPT_SHADE_DENSE / RTX_OPT_SORT_MATERIALS say (the rejected variants get no textured copy)
         // an environment is bound: the default kernel too, in its ENV form when the map has weight (a black map adds nothing and casts nothing: the kernels without it)
+        // a specular map is active and the frame is not RTX_FLAG_LAMBERT_ONLY: the SPC form of the TEX kernel (tri_uv is set whenever map_pr is), with or without the
+        // environment's sample and the normal maps.  A Lambert-only frame reads none of the three: it falls through to the kernels below
+        if constexpr (!LL) if (sc.map_pr) {
+            uint32_t lb, mb; shade_lds_plan(sc.nlights, sc.nmat, false, lb, mb);
+            dispatch_bool(sc.env_tex != nullptr, [&](auto env) { dispatch_bool(sc.tri_tan != nullptr, [&](auto nrm) {
+                constexpr bool EE = decltype(env)::value;
+                hipLaunchKernelGGL((k_shade<false, false, true, EE, decltype(nrm)::value, true>), dim3(f.nblocks), dim3(kBlock), (size_t)lb + mb + (EE ? shade_env_lds(lb, mb, sc.env_n) : 0u), st, sc, f, p, bounce, queue, qcount, next_queue, next_count, shcounts);
+            }); });
+            return;
+        }
         if (sc.env_n) {
             uint32_t lb, mb; shade_lds_plan(sc.nlights, sc.nmat, false, lb, mb);
             // a normal map is active: the NRM form of the TEX kernel (tri_uv is set whenever tri_tan is), with or without the environment's sample
@@ -378,6 +388,12 @@ void launch_dbg_opacity(hipStream_t st, const DevScene& sc, const F4* hits, uint
 }
 void launch_dbg_shading_normal(hipStream_t st, const DevScene& sc, const F4* rays, const F4* hits, uint32_t n, F4* out) {
     hipLaunchKernelGGL(k_dbg_shading_normal, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, sc, rays, hits, n, out);
+}
+void launch_dbg_specular(hipStream_t st, const DevScene& sc, const F4* hits, uint32_t n, float* out8) {
+    hipLaunchKernelGGL(k_dbg_specular, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, sc, hits, n, out8);
+}
+void launch_dbg_ess(hipStream_t st, const DevScene& sc, uint32_t material, const float* pr, const float* ndotv, uint32_t n, float* out) {
+    hipLaunchKernelGGL(k_dbg_ess, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, sc, material, pr, ndotv, n, out);
 }
 void launch_dbg_env_sample(hipStream_t st, const DevScene& sc, const uint32_t* seeds2, uint32_t n, F4* out) {
     hipLaunchKernelGGL(k_dbg_env_sample, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, sc, seeds2, n, out);

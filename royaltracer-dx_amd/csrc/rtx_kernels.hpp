@@ -56,6 +56,14 @@ struct DevScene {
     // slab form of the tiny-scene record pairs (rtx_types.hpp: SmallSlabPair; the last members: every other one keeps its place in the kernel arguments)
     const SmallSlabPair* small_slabs;   // one entry per SmallRecPair
     uint32_t small_slab_mask;           // bit kp set: traverse_small tests pair kp by its two slabs per record; clear: by its four edge planes (RTX_OPT_SMALL_SLABS 0: all clear)
+    // specular, roughness and metalness maps (rtx_specmap.hpp; behind the last member: every other one keeps its place in the kernel arguments).  The three map tables are
+    // nullptr unless a non-emitting material that some triangle uses has one of RTX_MAP_KS / PR / PM: such scenes launch what they always launched; otherwise all three are
+    // set (-1 where a material has none), tri_uv and map_kd too, and k_shade<.., SPC> runs unless the frame is RTX_FLAG_LAMBERT_ONLY
+    const int32_t* map_ks;              // per material: texture id of RTX_MAP_KS, or -1
+    const int32_t* map_pr;              // ... of RTX_MAP_PR
+    const int32_t* map_pm;              // ... of RTX_MAP_PM
+    const float* ess_tab;               // rtx_set_ess_table: ess_rows x 16 floats, or nullptr (none set, or no specular map active)
+    uint32_t ess_rows;
 };
 
 // one sample batch of one frame
@@ -270,6 +278,8 @@ void launch_dbg_albedo(hipStream_t, const DevScene&, const F4* hits, uint32_t n,
 // env_eval at n directions -> 2 F4 per direction (L, pdf | texel bits, r3, 0, 0).  sc.env_* must be set (the probes set them for a black map too)
 void launch_dbg_opacity(hipStream_t, const DevScene&, const F4* hits, uint32_t n, float* out2);                    // cut_alpha at n hit records -> (alpha, opacity texture id bits or 0xFFFFFFFF)
 void launch_dbg_shading_normal(hipStream_t, const DevScene&, const F4* rays, const F4* hits, uint32_t n, F4* out);   // surface() + nrm_perturb at n (ray, hit record) pairs -> (n', normal texture id bits or 0xFFFFFFFF)
+void launch_dbg_specular(hipStream_t, const DevScene&, const F4* hits, uint32_t n, float* out8);                    // spec_view at n hit records -> (Ks', Pr', Pm', ks / pr / pm texture id bits or 0xFFFFFFFF)
+void launch_dbg_ess(hipStream_t, const DevScene&, uint32_t material, const float* pr, const float* ndotv, uint32_t n, float* out);     // the Ess mix_view uses for `material` at n (Pr', NdotV) pairs
 void launch_dbg_env_sample(hipStream_t, const DevScene&, const uint32_t* seeds2, uint32_t n, F4* out);
 void launch_dbg_env_eval(hipStream_t, const DevScene&, const float* dirs3, uint32_t n, F4* out);
 void launch_dbg_tea(hipStream_t, uint32_t s0, uint32_t s1, uint32_t n, float* out, uint32_t* seed_out);

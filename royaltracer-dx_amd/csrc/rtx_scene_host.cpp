@@ -2,6 +2,7 @@
 // lists the steps of a commit (tree: rtx_bvh_build.cpp / rtx_bvh_wide.cpp, tiny-scene records: rtx_small_scene.cpp, any-hit probe: rtx_bvh_replay.cpp).  No HIP calls in this file.
 #include "rtx_scene_host.hpp"
 #include "rtx_normalmap_host.hpp"
+#include "rtx_specmap_host.hpp"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -72,7 +73,7 @@ bool SceneHost::set_materials(const void* mats, uint32_t count) {
     mats128.assign((const float*)mats, (const float*)mats + (size_t)count * 32);
     mats_dirty = true;
     if (any_map()) tex_dirty = true;
-    map_kd.clear(); map_opacity.clear(); map_normal.clear();        // the table is replaced: no material of the new one has a map
+    map_kd.clear(); map_opacity.clear(); map_normal.clear(); for (std::vector<int32_t>& v : map_spec) v.clear();        // the table is replaced: no material of the new one has a map (the energy table is no material's: it stays)
     return true;
 }
 
@@ -163,13 +164,29 @@ bool SceneHost::set_texture(uint32_t tex, const void* rgba8, uint32_t width, uin
 }
 bool SceneHost::set_material_map(uint32_t material, uint32_t slot, int32_t tex) {
     if (material >= mats128.size() / 32) { err = "set_material_map: unknown material"; return false; }
-    if (slot != 0u && slot != 2u && slot != 4u) { err = "set_material_map: unknown slot (RTX_MAP_KD = 0, RTX_MAP_OPACITY = 2 or RTX_MAP_NORMAL = 4)"; return false; }
+    if (slot != 0u && slot != 2u && slot != 4u && slot != 6u && slot != 8u && slot != 10u) { err = "set_material_map: unknown slot (RTX_MAP_KD = 0, RTX_MAP_OPACITY = 2, RTX_MAP_NORMAL = 4, RTX_MAP_KS = 6, RTX_MAP_PR = 8 or RTX_MAP_PM = 10)"; return false; }
     if (tex < -1 || (tex >= 0 && (size_t)tex >= textures.size())) { err = "set_material_map: unknown texture"; return false; }
-    std::vector<int32_t>& map = slot == 4u ? map_normal : slot == 2u ? map_opacity : map_kd;
+    std::vector<int32_t>& map = slot >= 6u ? map_spec[(slot - 6u) / 2u] : slot == 4u ? map_normal : slot == 2u ? map_opacity : map_kd;
     if (map.size() < mats128.size() / 32) map.resize(mats128.size() / 32, -1);
     map[material] = tex;
     tex_dirty = true;
     return true;
+}
+bool SceneHost::set_ess_table(const float* table, uint32_t rows) {
+    if (const char* e = ess_table_error(table, rows)) { err = e; return false; }
+    if (rows) ess_table.assign(table, table + (size_t)rows * kEssCols); else ess_table.clear();
+    ess_rows = rows;
+    tex_dirty = true;
+    return true;
+}
+bool SceneHost::spec_active() const {
+    if (!any_spec_map()) return false;
+    for (size_t i = 0; i < matids.size(); i += 3) {
+        const uint32_t mat = matids[i];
+        if (mat >= mats128.size() / 32 || material_emits(mat)) continue;
+        for (const std::vector<int32_t>& v : map_spec) if (mat < v.size() && v[mat] >= 0) return true;
+    }
+    return false;
 }
 bool SceneHost::maps_active() const {
     if (!any_map()) return false;
@@ -478,8 +495,9 @@ bool SceneHost::build(BuiltScene& B) {
     // ... and one with an environment bound (k_bounce_small's misses end black)
     // ... and one with a cut-out triangle (the pre-test path runs no alpha test)
     // ... and one with an active normal map (k_bounce_small perturbs no normal)
-    B.maps_active = maps_active(); B.cutouts_active = cutouts_active(); B.normals_active = normals_active(); B.env_active = env.n != 0;
-    if (B.any_hidden || B.maps_active || B.cutouts_active || B.normals_active || B.env_active) { B.small_recs.clear(); B.small_tris.clear(); B.small_poly.clear(); B.small_slabs.clear(); B.small_excess.clear(); B.small_slab_mask = 0; B.small_nrec = 0; B.small_nocc = 0; }
+    // ... and one with an active specular, roughness or metalness map (k_bounce_small reads the material table alone)
+    B.maps_active = maps_active(); B.cutouts_active = cutouts_active(); B.normals_active = normals_active(); B.spec_active = spec_active(); B.env_active = env.n != 0;
+    if (B.any_hidden || B.maps_active || B.cutouts_active || B.normals_active || B.spec_active || B.env_active) { B.small_recs.clear(); B.small_tris.clear(); B.small_poly.clear(); B.small_slabs.clear(); B.small_excess.clear(); B.small_slab_mask = 0; B.small_nrec = 0; B.small_nocc = 0; }
     else build_small_scene(B, wtri, scale);
     sw.lap("tris8 / small scene");
     B.any_order = probe_anyhit_order(B);

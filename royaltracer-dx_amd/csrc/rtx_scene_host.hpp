@@ -53,6 +53,7 @@ struct BuiltScene {
     bool maps_active = false;           // SceneHost::maps_active() AS COMMITTED: a tiny scene then runs on the general path, DevScene::tri_uv / map_kd are set
     bool cutouts_active = false;        // SceneHost::cutouts_active() AS COMMITTED: a tiny scene then runs on the general path, DevScene::tri_cut (and tri_uv / map_kd) are set
     bool normals_active = false;        // SceneHost::normals_active() AS COMMITTED: a tiny scene then runs on the general path, DevScene::tri_tan / map_nrm (and tri_uv / map_kd) are set
+    bool spec_active = false;           // SceneHost::spec_active() AS COMMITTED: a tiny scene then runs on the general path, DevScene::map_ks / map_pr / map_pm (and tri_uv / map_kd) are set
     bool env_active = false;            // an environment is bound (SceneHost::env.n != 0) AS COMMITTED: a tiny scene then runs on the general path
     std::vector<uint32_t> inst_moved;   // refresh_transforms: 1 = the instance's objectToWorld differs from the last commit's, or its mesh's vertices do, or its visibility does (the GPU refit touches the triangles and nodes of these only)
 };
@@ -72,7 +73,9 @@ struct SceneHost {
     std::vector<int32_t> map_kd;                // per material: texture id of RTX_MAP_KD or -1; shorter than the table = the rest has none (rtx_set_materials empties it)
     std::vector<int32_t> map_opacity;           // ... of RTX_MAP_OPACITY (alpha cut-outs), likewise
     std::vector<int32_t> map_normal;            // ... of RTX_MAP_NORMAL (tangent-space normal maps), likewise
-    bool tex_dirty = false;                     // one of the three setters since the last commit
+    std::vector<int32_t> map_spec[3];           // ... of RTX_MAP_KS, RTX_MAP_PR, RTX_MAP_PM (specular, roughness and metalness maps), likewise
+    std::vector<float> ess_table; uint32_t ess_rows = 0;        // rtx_set_ess_table: rows x 16 floats, or empty / 0 (a table edit like the maps: tex_dirty; rtx_set_materials keeps it)
+    bool tex_dirty = false;                     // one of the four setters (UVs, texture, material map, energy table) since the last commit
     // environment lighting (include/rtx.h: rtx_set_environment; rtx_env_host.hpp)
     EnvHost env;
     bool env_dirty = false;                     // rtx_set_environment since the last commit
@@ -98,7 +101,10 @@ struct SceneHost {
     bool set_material_map(uint32_t material, uint32_t slot, int32_t tex);
     bool any_opacity_map() const { for (int32_t t : map_opacity) if (t >= 0) return true; return false; }
     bool any_normal_map() const { for (int32_t t : map_normal) if (t >= 0) return true; return false; }
-    bool any_map() const { for (int32_t t : map_kd) if (t >= 0) return true; return any_opacity_map() || any_normal_map(); }
+    bool any_spec_map() const { for (const std::vector<int32_t>& v : map_spec) for (int32_t t : v) if (t >= 0) return true; return false; }
+    bool any_map() const { for (int32_t t : map_kd) if (t >= 0) return true; return any_opacity_map() || any_normal_map() || any_spec_map(); }
+    bool set_ess_table(const float* table, uint32_t rows);
+    bool spec_active() const;                   // a non-emitting material that some triangle uses has a specular, roughness or metalness map
     bool maps_active() const;                   // a material that some triangle uses has a diffuse map
     bool material_emits(uint32_t mat) const { const float* m = &mats128[(size_t)mat * 32]; return m[8] > 0.0f || m[9] > 0.0f || m[10] > 0.0f; }      // a component of Ke is > 0
     // the opacity texture of a triangle whose material (the id of its first index entry) is `mat`, or -1: the material has RTX_MAP_OPACITY and does not emit (a CUT-OUT TRIANGLE)

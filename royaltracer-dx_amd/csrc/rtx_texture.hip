@@ -21,6 +21,11 @@ int rtx_set_material_map(rtx_ctx* c, uint32_t material, uint32_t slot, int32_t t
     if (!c->host.set_material_map(material, slot, tex)) { c->err = c->host.err; return RTX_ERR_INVALID; }
     c->committed = false; return RTX_OK;
 }
+int rtx_set_ess_table(rtx_ctx* c, const float* table, uint32_t rows) {
+    if (!c) return RTX_ERR_INVALID;
+    if (!c->host.set_ess_table(table, rows)) { c->err = c->host.err; return RTX_ERR_INVALID; }
+    c->committed = false; return RTX_OK;
+}
 
 int rtx_debug_texture_sample(rtx_ctx* c, uint32_t tex, const float* uv2, uint32_t n, float* out4) {
     BIND(c);

@@ -2,6 +2,7 @@
 #include "Scenes.h"
 #include "ImageIO.h"
 #include "../csrc/rtx_normalmap_host.hpp"
+#include "../csrc/rtx_specmap_host.hpp"
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -543,7 +544,7 @@ Scene MakeBistroClass(uint32_t target, uint32_t seed, bool hard) {
 }
 
 // the reference's startup scene (Renderer.cpp:363-407, 444-449, 46-48)
-Scene LoadObjScene(const std::vector<std::string>& files, const std::string& mtl_dir, bool load_textures, SceneCutouts cutouts, SceneNormals normals) {
+Scene LoadObjScene(const std::vector<std::string>& files, const std::string& mtl_dir, bool load_textures, SceneCutouts cutouts, SceneNormals normals, bool spec_maps) {
     Scene s; s.name = "obj";
     UINT materialIDOffset = 0, materialVertexOffset = 0;       // Renderer members of the same name
     size_t total_ids = 0;
@@ -560,7 +561,7 @@ Scene LoadObjScene(const std::vector<std::string>& files, const std::string& mtl
     s.eye = XMFLOAT3(-1.5f, 1.5f, 3.5f); s.center = XMFLOAT3(0, 1, 0); s.up = XMFLOAT3(0, 1, 0);   // Renderer.cpp:46-48
     s.images.resize(s.textures.size());
     std::vector<char> tried(s.textures.size(), 0);
-    auto load = [&](int t, const char* what) {                 // the diffuse, the opacity and the normal maps only: no kernel samples another slot
+    auto load = [&](int t, const char* what) {                 // the diffuse, opacity, normal, specular, roughness and metalness maps only: no kernel samples another slot
         if (!load_textures || t < 0 || (size_t)t >= s.textures.size() || tried[t]) return;
         tried[t] = 1;
         std::string dir = mtl_dir; if (!dir.empty() && dir.back() != '/') dir += '/';
@@ -583,6 +584,18 @@ Scene LoadObjScene(const std::vector<std::string>& files, const std::string& mtl
         }
         for (size_t t = 0; t < s.images.size(); t++) if (opacity[t]) OpacityAlphaFromChannels(s.images[t].rgba, s.images[t].channels);
     }
+    if (load_textures && spec_maps) {
+        s.ksMaps.assign(s.materialExt.size(), -1); s.prMaps.assign(s.materialExt.size(), -1); s.pmMaps.assign(s.materialExt.size(), -1);
+        for (size_t m = 0; m < s.materialExt.size() && m < s.materials.size(); m++) {
+            const MaterialExt& x = s.materialExt[m];
+            Material& mat = s.materials[m];
+            auto bound = [&](int t, const char* what) { load(t, what); return t >= 0 && (size_t)t < s.images.size() && s.images[t].width != 0u; };
+            // the zero-scalar rule: a bound map multiplies its scalar, and 0 is what the parser leaves for a scalar the file does not give
+            if (bound(x.map[MAP_KS], "map_Ks")) { s.ksMaps[m] = x.map[MAP_KS]; rtx::spec_unit_colour(&mat.Ks.x); }
+            if (bound(x.map[MAP_PR], "map_Pr")) { s.prMaps[m] = x.map[MAP_PR]; if (rtx::spec_unit_scalar(&mat.Pr_Pm_Ps_Pc.x)) GenerateEssLUT(mat); }
+            if (bound(x.map[MAP_PM], "map_Pm")) { s.pmMaps[m] = x.map[MAP_PM]; rtx::spec_unit_scalar(&mat.Pr_Pm_Ps_Pc.y); }
+        }
+    }
     if (load_textures && normals.mode != kNormalsOff) {
         s.normalMaps.assign(s.materialExt.size(), -1);
         const size_t nfile = s.textures.size();                // (copies are appended behind the files' entries, which keep their ids)
@@ -590,6 +603,7 @@ Scene LoadObjScene(const std::vector<std::string>& files, const std::string& mtl
         for (size_t m = 0; m < s.materialExt.size(); m++) {
             const int kd = s.materialExt[m].map[MAP_KD]; if (kd >= 0 && (size_t)kd < nfile) other[kd] = 1;
             const int op = m < s.opacityMaps.size() ? s.opacityMaps[m] : -1; if (op >= 0 && (size_t)op < nfile) other[op] = 1;
+            for (const std::vector<int>* sm : {&s.ksMaps, &s.prMaps, &s.pmMaps}) { const int t = m < sm->size() ? (*sm)[m] : -1; if (t >= 0 && (size_t)t < nfile) other[t] = 1; }
         }
         std::vector<int> as_normal(nfile, -1), as_height(nfile, -1);      // file image -> the entry that holds it as a normal map / converted from a height map
         for (size_t m = 0; m < s.materialExt.size(); m++) {
@@ -638,6 +652,17 @@ bool SetSceneMeshVertices(Scene& s, UINT model, const void* verts28, uint32_t nv
 extern "C" int rtx_set_mesh_uvs(rtx_ctx*, uint32_t mesh, const float* uv2, uint32_t nidx) __attribute__((weak));
 extern "C" int rtx_set_texture(rtx_ctx*, uint32_t tex, const void* rgba8, uint32_t width, uint32_t height, uint32_t flags) __attribute__((weak));
 extern "C" int rtx_set_material_map(rtx_ctx*, uint32_t material, uint32_t slot, int32_t tex) __attribute__((weak));
+extern "C" int rtx_set_ess_table(rtx_ctx*, const float* table, uint32_t rows) __attribute__((weak));
+
+// the energy table BindSceneMaps sets: 17 rows, row r = GenerateEssLUT at roughness r / 16.  The rows depend on the row's roughness only: generated once per process
+static const std::vector<float>& EssTable17() {
+    static const std::vector<float> rows = [] {
+        std::vector<float> t(17 * 16);
+        for (int r = 0; r < 17; r++) { Material m(XMFLOAT4(1, 1, 1, 1), XMFLOAT4((float)r / 16.0f, 0, 0, 0)); GenerateEssLUT(m); memcpy(&t[(size_t)r * 16], m.LUT, 64); }
+        return t;
+    }();
+    return rows;
+}
 
 int BindSceneMaps(const Scene& s, rtx_ctx* ctx) {
     if (!rtx_set_mesh_uvs || !rtx_set_texture || !rtx_set_material_map) return RTX_OK;
@@ -664,6 +689,16 @@ int BindSceneMaps(const Scene& s, rtx_ctx* ctx) {
         const int t = s.normalMaps[m];
         if (t >= 0 && (size_t)t < id.size() && id[t] >= 0 && (r = rtx_set_material_map(ctx, (uint32_t)m, RTX_MAP_NORMAL, id[t]))) return r;
     }
+    bool pr_bound = false;
+    const std::vector<int>* spec[3] = {&s.ksMaps, &s.prMaps, &s.pmMaps}; const uint32_t slot[3] = {RTX_MAP_KS, RTX_MAP_PR, RTX_MAP_PM};
+    for (int k = 0; k < 3; k++) for (size_t m = 0; m < spec[k]->size() && m < s.materials.size(); m++) {
+        const int t = (*spec[k])[m];
+        if (t < 0 || (size_t)t >= id.size() || id[t] < 0) continue;
+        if ((r = rtx_set_material_map(ctx, (uint32_t)m, slot[k], id[t]))) return r;
+        if (k == 1) pr_bound = true;
+    }
+    // the energy compensation follows a mapped roughness through a table of LUTs (include/rtx.h, ENERGY TABLE): set only where some roughness map was bound
+    if (pr_bound && rtx_set_ess_table && (r = rtx_set_ess_table(ctx, EssTable17().data(), 17))) return r;
     return RTX_OK;
 }
 
