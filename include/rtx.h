@@ -263,7 +263,7 @@ int  rtx_update_mesh_vertices(rtx_ctx*, uint32_t mesh, const void* verts28, uint
        KdPi'[k] = Kd'[k] / PI                                                             (IEEE division, as for the table)
    KdPi' replaces the material's Kd / PI wherever the shading reads the diffuse colour at that hit: the Lambert term of the mixture BSDF, for the NEE samples and for the
    continuation.  Everything else stays the material's: Ks, Ke, Pr, Pm, dissolve, the light list, the strategy probabilities, the random-number sequence (unless SPECULAR MAPS, below).  An emissive
-   material's map has no effect (emitters are not shaded).  CONSEQUENCE: a scene in which every textured triangle sees one value tl is, bit for bit, the untextured scene
+   material's map_Kd has no effect (emitters are not shaded; its emission is textured by EMISSION MAPS, below).  CONSEQUENCE: a scene in which every textured triangle sees one value tl is, bit for bit, the untextured scene
    whose triangles carry materials with Kd = Kd'.  rtx_denoise is unchanged (its colour edge-stop now sees texture detail, unless RTX_DENOISE_ALBEDO demodulates by Kd': DENOISING, MAP GUIDES); debug layer 13 shows Kd'.
    CALLS.  rtx_set_mesh_uvs: nidx pairs, nidx = the mesh's index count; NULL clears.  rtx_set_texture: tex <= the current count, == count appends; the texels are copied.
    rtx_set_material_map: slot RTX_MAP_KD (or RTX_MAP_OPACITY, below), tex -1 = none.  RTX_ERR_INVALID — unknown mesh, material, texture or slot; nidx other than the mesh's; a non-finite UV; a size
@@ -375,10 +375,49 @@ int  rtx_update_mesh_vertices(rtx_ctx*, uint32_t mesh, const void* verts28, uint
    uploads tables only (rtx_stats.bvh_refits and rtx_debug_tree_hash unchanged); a tiny scene (<= 64 triangles) runs on the general BVH path while a non-emitting material that
    a triangle uses has one of the three maps, and the commit that crosses that line is a rebuild; rtx_save_scene_cache with one bound is RTX_ERR_STATE.  RTX_OPT_FUSED_BVH,
    RTX_OPT_SHADE_DENSE and RTX_OPT_SORT_MATERIALS are ignored while one is active; RTX_OPT_COMPACT_STATE 0 and 1 both work. */
+/* EMISSION MAPS (new; the reference parses map_Ke and samples nothing: an extension like map_Kd, unpinned by the reference, pinned by its own definition and properties in
+   tests/test_emimap_ref.py / tests/test_emimap.py).  One more material-map slot lets a texture vary a material's emission over its surface: lanterns, shop signs, screens, lit
+   windows — an emissive material whose Ke is white and whose map is mostly black.  All device arithmetic is float32 in exactly the written order, no contraction.
+   SLOT.  rtx_set_material_map(ctx, material, RTX_MAP_KE, tex) binds a texture of the table above (12; the value 11 stays an unknown slot, like 1, 3, 5, 7 and 9).  The slot
+   reads the RGB bytes and honours RTX_TEX_SRGB, as the Kd slot does.  The map MULTIPLIES the material's Ke.
+   EMITTER.  What it always was: a material whose rounded Ke has length > 0.  The map never makes an emitter out of a non-emitter and never a non-emitter out of an emitter: a
+   hit on a black texel of an emissive material still ends the path there and adds nothing (emitters are not shaded).  On a non-emitting material the slot has no effect at all.
+   AT AN EMISSIVE HIT on global triangle prim, hit barycentrics (u, v), material m with RTX_MAP_KE = tex >= 0: b0, s, t exactly as PER HIT of map_Kd;
+       tl = Sample(tex, s, t);   Ke'[k] = half_round(m.KeFull[k] * tl[k])      (the binary16 round trip that the table's Ke is a copy of)
+   Ke' replaces Ke in the radiance the hit adds, at bounce 0 and at bounces >= 1, and the MIS weight there replaces (Ke.x + Ke.y + Ke.z) / 3 by the per-triangle q[prim] of the
+   table below: pdf_light = (q[prim] / total_weight) * dist2 / max(cos_t, EPS).
+   AT A TRIANGLE-LIGHT NEE SAMPLE.  The light record carries its global triangle id and the emission texture of its material.  With u, v, w the sample's weights of corners 0,
+   1, 2:  s = (u * uv0.x + v * uv1.x) + w * uv2.x, t likewise;  tl = Sample(tex, s, t);  the contribution uses em[k] * tl[k] where it used em[k] (em = the material's Ke, as
+   rtx_get_lights hands it out).  Selection, the three draws, pdf_l, the rejection tests and the shadow ray are unchanged in form; a zero contribution asks for no shadow ray.
+   PER-TRIANGLE MEAN AND THE LIGHT WEIGHTS.  Built on the host at rtx_commit_scene, only while an emission map is active (an emitting material that some triangle uses has the
+   map).  For each emitter triangle whose material has the map, with W x H the texture's size and uv0..2 the corner pairs:
+       n = clamp(ceil(max over the three edges of max(|du| * W, |dv| * H)), 1, 16)      (in double)
+   the triangle is cut into n^2 equal sub-triangles; "upright" ones have their centroids at hit barycentrics ((i + 1/3) / n, (j + 1/3) / n) for i + j <= n - 1, "inverted" ones
+   at ((i + 2/3) / n, (j + 2/3) / n) for i + j <= n - 2; the order is i outer, j inner, the upright one of a cell before its inverted one.  The centroid barycentrics are rounded
+   to float32, then b0, s, t and Sample() run in float32 exactly as on the device.
+       mean[k] = (sum of the samples, in double, in that order) / n^2, rounded to float32 once;   E[k] = m.KeFull[k] * mean[k]      (float32)
+       weight  = area * ((E.x + E.y + E.z) / 3)      where the light scan has area * inten;   q[prim] = (Eh.x + Eh.y + Eh.z) / 3,  Eh[k] = half_round(E[k])
+   Unmapped emitter triangles keep inten and get q[prim] = (Ke.x + Ke.y + Ke.z) / 3 of the rounded copy, so the hit reads one table whatever the material; non-emitting
+   triangles and hidden instances get 0.  The rest of the list is built as before from the new weights: sorted descending, ties by collection order, the running CDF ends in
+   1.0f; wn, total and pdf_l as before.  WHICH triangles are in the list does not change (rtx_stats.lights and rtx_get_lights' count stay; the 80-byte record keeps its layout
+   and its em = the material's Ke): only weights and order do.  A scene whose total weight is 0 (every map black) has no light list for the renderer: no NEE slots, the
+   random-number sequence of a scene without lights (rtx_get_lights then reports wn = 0).  The table depends on no transform: a transform-only commit leaves it alone.
+   CONSEQUENCES.  (a) A scene in which every mapped emitter triangle sees one texel value c over its whole area, every component of c > 0, is, bit for bit, the unmapped scene
+   whose triangles carry materials with Ke = KeFull * c (the mean of n^2 equal floats in double is that float).  (b) An all-255 linear map changes nothing, to the bit.  (c)
+   Unbiased whatever the quadrature misses: a triangle with q = 0 that still has a lit texel is found by BSDF sampling with mi = 1.
+   WHO SEES IT.  rtx_render, rtx_render_adaptive, rtx_debug_emission, rtx_debug_light_sample.  IGNORED BY rtx_render_v6_pass1, rtx_render_restir, rtx_denoise (emitters pass
+   through as ever), rtx_read_layer (layer 16 shows the table's Ke) and the other debug probes — as they ignore map_Kd.
+   CALLS AND COMMITS follow the map_Kd rules word for word: valid before the first commit and on a resident scene; rtx_commit_scene again (rendering in between is
+   RTX_ERR_STATE); RTX_ERR_INVALID leaves the scene committed and untouched; rtx_set_materials resets the slot to -1; rtx_save_scene_cache with one bound is RTX_ERR_STATE;
+   RTX_OPT_FUSED_BVH, RTX_OPT_SHADE_DENSE and RTX_OPT_SORT_MATERIALS are ignored while one is active; RTX_OPT_COMPACT_STATE 0 and 1 both work.  ONE ADDITION: while an emission
+   map is active on an emitter, or was at the previous commit, a map-only commit (a map call, rtx_set_texture, rtx_set_mesh_uvs) also rebuilds the light list — still no
+   rebuild or refit of the tree (rtx_stats.bvh_refits and rtx_debug_tree_hash unchanged).  A tiny scene (<= 64 triangles) runs on the general BVH path while an emitter that a
+   triangle uses has the map, and the commit that crosses that line is a rebuild. */
 #define RTX_TEX_SRGB 1u
 enum { RTX_MAP_KD = 0, RTX_MAP_OPACITY = 2 };      /* 1 is not a slot: it stays RTX_ERR_INVALID, as it always was */
 enum { RTX_MAP_NORMAL = 4 };                       /* ... and neither is 3 */
 enum { RTX_MAP_KS = 6, RTX_MAP_PR = 8, RTX_MAP_PM = 10 };      /* ... nor 5, 7, 9 (SPECULAR MAPS) */
+enum { RTX_MAP_KE = 12 };                          /* ... nor 11 (EMISSION MAPS) */
 int  rtx_set_mesh_uvs(rtx_ctx*, uint32_t mesh, const float* uv2 /* nidx pairs; NULL clears */, uint32_t nidx);
 int  rtx_set_texture(rtx_ctx*, uint32_t tex /* <= current count; == count appends */, const void* rgba8, uint32_t width, uint32_t height, uint32_t flags);
 int  rtx_set_material_map(rtx_ctx*, uint32_t material, uint32_t slot, int32_t tex /* -1 = none */);
@@ -388,6 +427,12 @@ int  rtx_set_ess_table(rtx_ctx*, const float* table /* rows x 16 */, uint32_t ro
    five zeros and three 0xFFFFFFFF.  rtx_debug_ess: the Ess mix_view would use for `material` at n (Pr', NdotV) pairs — the table path or m.LUT, by the rule above */
 int  rtx_debug_specular(rtx_ctx*, const float* hits4, uint32_t n, float* out8);
 int  rtx_debug_ess(rtx_ctx*, uint32_t material, const float* pr, const float* ndotv, uint32_t n, float* out);
+/* tests: EMISSION MAPS by the device functions k_shade runs.  rtx_debug_emission: hits4 as rtx_debug_trace_closest writes them -> 8 words per record: Ke'.xyz, q[prim], the
+   emission texture id as uint bits or 0xFFFFFFFF, 0, 0, 0; a non-emitter or a miss gives zeros and 0xFFFFFFFF (while no emission map is active an emitter gives the table's Ke,
+   its mean and 0xFFFFFFFF).  rtx_debug_light_sample: n seed pairs -> 12 words per seed: light index bits, sample point xyz, s, t (0, 0 for a light without the map), em * tl
+   xyz, pdf_l, the seed after the three draws (2); RTX_ERR_STATE for a scene without a light list */
+int  rtx_debug_emission(rtx_ctx*, const float* hits4, uint32_t n, float* out8);
+int  rtx_debug_light_sample(rtx_ctx*, const uint32_t* seeds2, uint32_t n, float* out12);
 /* tests: the device's sampler — n (s, t) pairs -> (r, g, b, 0) — and the device's per-hit albedo — hits4 as rtx_debug_trace_closest writes them -> (Kd' (m.Kd where the
    material has no map), texture id as uint bits or 0xFFFFFFFF); a miss gives (0, 0, 0, 0xFFFFFFFF).  rays8 may be NULL: the albedo depends on the hit record alone */
 int  rtx_debug_texture_sample(rtx_ctx*, uint32_t tex, const float* uv2, uint32_t n, float* out4);

@@ -40,6 +40,10 @@ rtxh_scene* rtxh_scene_from_obj(const char* const* files, uint32_t nfiles, const
    is what the parser records for a scalar the file does not give.  A stated deviation from the reference's record, made only where a map is bound.
    RTXH_OBJ_NO_SPEC_MAPS = none bound, the records as parsed (NO_TEXTURES implies it) */
 #define RTXH_OBJ_NO_SPEC_MAPS   64u
+/* ... and for the emission maps (include/rtx.h, EMISSION MAPS): by default the image a map_Ke statement names is bound as RTX_MAP_KE, and a material that gets the map has a Ke of
+   (0, 0, 0) set to (1, 1, 1) — the map multiplies Ke, and 0 is what the parser records for a Ke the file does not give (it would be no emitter).  The same stated deviation from the
+   reference's record, made only where a map is bound.  RTXH_OBJ_NO_EMISSION_MAPS = none bound, the records as parsed (NO_TEXTURES implies it) */
+#define RTXH_OBJ_NO_EMISSION_MAPS 128u
 rtxh_scene* rtxh_scene_from_obj_ex(const char* const* files, uint32_t nfiles, const char* mtl_dir, uint32_t flags);
 /* ... with channel 0 of the map_Bump / bump image of a material without a norm taken as a HEIGHT map and converted on load (h = byte / 255, repeat wrap, central differences times
    bump_height, c = (-gx, -gy, 1) normalised, byte = clamp(floor(c * 127 + 128.5), 0, 255)); RTXH_OBJ_BUMP_AS_NORMAL is ignored here */
@@ -60,7 +64,7 @@ const void* rtxh_scene_materials(const rtxh_scene*);                       /* 12
    statement (-1 = none; ids index rtxh_scene_texture).  Only scenes loaded from OBJ / MTL files carry it (index-aligned with the
    material table, default materials included).  Of all of it the kernels read ONE thing: the diffuse map, map[RTXH_MAP_KD], once its image is decoded and bound
    (rtx_set_material_map, include/rtx.h) — the reference's shaders sample no textures, this library's k_shade samples map_Kd; map_d, norm (map_Bump / bump on request), map_Ks, map_Pr and map_Pm are bound
-   by the accessors further down (rtxh_scene_opacity_map, rtxh_scene_normal_map, rtxh_scene_spec_map); every other slot stays a name. */
+   by the accessors further down (rtxh_scene_opacity_map, rtxh_scene_normal_map, rtxh_scene_spec_map), map_Ke by rtxh_scene_emission_map; every other slot stays a name. */
 #define RTXH_NUM_MAP_SLOTS 13
 enum { RTXH_MAP_KA = 0, RTXH_MAP_KD, RTXH_MAP_KS, RTXH_MAP_KE, RTXH_MAP_NS, RTXH_MAP_BUMP, RTXH_MAP_D, RTXH_MAP_DISP, RTXH_MAP_REFL, RTXH_MAP_PR, RTXH_MAP_PM, RTXH_MAP_PS, RTXH_MAP_NORM };
 typedef struct rtxh_material_ext { float Ni, Ns, Pcr, aniso, anisor; int32_t illum; float Ka[3], Tf[3]; int32_t map[RTXH_NUM_MAP_SLOTS]; } rtxh_material_ext;
@@ -79,6 +83,8 @@ int         rtxh_scene_normal_map(const rtxh_scene*, uint32_t material);
 /* the texture the scene binds in the material's RTX_MAP_KS / RTX_MAP_PR / RTX_MAP_PM slot (its map_Ks / map_Pr / map_Pm image; one packed file may serve several), or -1; also -1 for
    any other slot value */
 int         rtxh_scene_spec_map(const rtxh_scene*, uint32_t material, uint32_t slot);
+/* the texture the scene binds in the material's RTX_MAP_KE slot (its map_Ke image), or -1 */
+int         rtxh_scene_emission_map(const rtxh_scene*, uint32_t material);
 /* the per-corner texture coordinates of mesh i (the OBJ's vt): one (u, v) pair per index entry, parallel to rtxh_scene_mesh's indices; NULL / 0 for a mesh without any */
 int         rtxh_scene_mesh_uvs(const rtxh_scene*, uint32_t i, const float** uv2, uint32_t* nidx);
 /* the image readers alone: width / height always, the pixels when capacity holds width * height * 4 bytes; RTX_ERR_INVALID + rtxh_last_error for a file they cannot read */

@@ -54,6 +54,7 @@ MAP_NORMAL = 4        # ... the tangent-space normal map slot: reads the texture
 MAP_KS = 6            # ... the specular colour slot: reads the RGB bytes, sRGB honoured (5, 7 and 9 are not slots)
 MAP_PR = 8            # ... the roughness slot: reads the green byte through the linear table
 MAP_PM = 10           # ... the metalness slot: reads the blue byte through the linear table
+MAP_KE = 12           # the emission slot (include/rtx.h, EMISSION MAPS; 11 is not a slot): multiplies an emitter's Ke; RGB bytes, sRGB honoured
 ENV_HIDDEN = 1        # rtx_set_environment flag: primary rays that miss stay black
 
 
@@ -123,6 +124,8 @@ _sig("rtx_debug_opacity", C.c_int, _vp, _vp, _u32, _vp)
 _sig("rtx_debug_shading_normal", C.c_int, _vp, _vp, _vp, _u32, _vp)
 _sig("rtx_set_ess_table", C.c_int, _vp, _vp, _u32)
 _sig("rtx_debug_specular", C.c_int, _vp, _vp, _u32, _vp)
+_sig("rtx_debug_emission", C.c_int, _vp, _vp, _u32, _vp)
+_sig("rtx_debug_light_sample", C.c_int, _vp, _vp, _u32, _vp)
 _sig("rtx_debug_ess", C.c_int, _vp, _u32, _vp, _vp, _u32, _vp)
 _sig("rtx_debug_tri_tangents", C.c_int, _vp, _u32, _u32, _vp)
 _sig("rtx_set_environment", C.c_int, _vp, _vp, _u32, _vp, C.c_float, _u32)
@@ -224,6 +227,7 @@ _sig("rtxh_scene_opacity_map", C.c_int, _vp, _u32)
 _sig("rtxh_scene_from_obj_ex2", _vp, C.POINTER(C.c_char_p), _u32, C.c_char_p, _u32, C.c_float)
 _sig("rtxh_scene_normal_map", C.c_int, _vp, _u32)
 _sig("rtxh_scene_spec_map", C.c_int, _vp, _u32, _u32)
+_sig("rtxh_scene_emission_map", C.c_int, _vp, _u32)
 _sig("rtxh_scene_free", None, _vp)
 _sig("rtxh_scene_save", C.c_int, _vp, C.c_char_p)
 _sig("rtxh_scene_load", _vp, C.c_char_p)
@@ -340,6 +344,8 @@ class Scene:
         # ... and for the specular, roughness and metalness maps (map_Ks / map_Pr / map_Pm); ess_table: the 17-row energy table that goes with a roughness map, else None
         self.ks_maps, self.pr_maps, self.pm_maps = ([int(lib.rtxh_scene_spec_map(handle, i, slot)) for i in range(n)] for slot in (MAP_KS, MAP_PR, MAP_PM))
         self.ess_table = ess_table_rows(17) if any(t >= 0 for t in self.pr_maps) else None
+        # ... and for the emission maps (map_Ke)
+        self.ke_maps = [int(lib.rtxh_scene_emission_map(handle, i)) for i in range(n)]
         self.meshes, self.uvs = [], []
         for i in range(lib.rtxh_scene_num_meshes(handle)):
             v, idx, mid = _vp(), _vp(), _vp()
@@ -383,14 +389,15 @@ class Scene:
         return cls((lib.rtxh_scene_bistro_class_hard if hard else lib.rtxh_scene_bistro_class)(target_tris, seed))
 
     @classmethod
-    def from_obj(cls, files, mtl_dir, textures=True, cutouts=True, kd_alpha=False, normal_maps=True, bump=None, flip_y=False, spec_maps=True):
+    def from_obj(cls, files, mtl_dir, textures=True, cutouts=True, kd_alpha=False, normal_maps=True, bump=None, flip_y=False, spec_maps=True, emission_maps=True):
         """textures=False: decode no image; cutouts=False: bind no map_d image as an opacity map; kd_alpha=True: a material without a map_d whose map_Kd file is a
         32-bit TGA gets that texture as its opacity map too (rtx_render --no-textures / --no-cutouts / --kd-alpha); normal_maps=False: bind no norm image as a normal
         map; bump="normal": a material without a norm takes its map_Bump / bump image as a normal map, bump=S (a number): as a height map converted with strength S;
         flip_y=True: DirectX-style maps, green negated on load (--no-normal-maps / --bump-as-normal / --bump-height S / --normal-flip-y); spec_maps=False: bind no
-        map_Ks / map_Pr / map_Pm image and leave the records as parsed (with them, a bound map sets a zero Ks / Pr / Pm to one: --no-spec-maps)"""
+        map_Ks / map_Pr / map_Pm image and leave the records as parsed (with them, a bound map sets a zero Ks / Pr / Pm to one: --no-spec-maps); emission_maps=False: bind no map_Ke image and leave the records as parsed (with them, a bound map sets a Ke of
+        (0, 0, 0) to (1, 1, 1): --no-emission-maps)"""
         arr = (C.c_char_p * len(files))(*[f.encode() for f in files])
-        flags = (0 if textures else 1) | (0 if cutouts else 2) | (4 if kd_alpha else 0) | (0 if normal_maps else 8) | (16 if bump == "normal" else 0) | (32 if flip_y else 0) | (0 if spec_maps else 64)
+        flags = (0 if textures else 1) | (0 if cutouts else 2) | (4 if kd_alpha else 0) | (0 if normal_maps else 8) | (16 if bump == "normal" else 0) | (32 if flip_y else 0) | (0 if spec_maps else 64) | (0 if emission_maps else 128)
         if bump is not None and bump != "normal":
             return cls(lib.rtxh_scene_from_obj_ex2(arr, len(files), mtl_dir.encode(), flags, float(bump)))
         return cls(lib.rtxh_scene_from_obj_ex(arr, len(files), mtl_dir.encode(), flags))
@@ -687,7 +694,7 @@ class Context:
         self._ck(lib.rtx_set_texture(self._h, int(tex), _ptr(a), a.shape[1], a.shape[0], TEX_SRGB if srgb else 0), "rtx_set_texture")
 
     def set_material_map(self, material, tex, slot=MAP_KD):
-        """the material's map in `slot` (MAP_KD, MAP_OPACITY, MAP_NORMAL, MAP_KS, MAP_PR, MAP_PM) := texture id `tex`, -1 / None = none"""
+        """the material's map in `slot` (MAP_KD, MAP_OPACITY, MAP_NORMAL, MAP_KS, MAP_PR, MAP_PM, MAP_KE) := texture id `tex`, -1 / None = none"""
         self._ck(lib.rtx_set_material_map(self._h, int(material), int(slot), -1 if tex is None else int(tex)), "rtx_set_material_map")
 
     def texture_sample(self, tex, uvs):
@@ -739,6 +746,23 @@ class Context:
         self._ck(lib.rtx_debug_specular(self._h, _ptr(h), len(h), _ptr(out)), "rtx_debug_specular")
         return out[:, :5].copy(), out[:, 5:].copy().view(np.uint32)
 
+    def emission(self, hits4):
+        """Ke' and q under the emission maps at hit records (trace_closest), by the device function k_shade runs -> ((n, 4) float32: Ke', q[prim]; (n,) uint32: the
+        emission texture id or 0xFFFFFFFF); a non-emitter or a miss gives zeros and 0xFFFFFFFF"""
+        h = _f32(hits4).reshape(-1, 4)
+        out = np.zeros((len(h), 8), np.float32)
+        self._ck(lib.rtx_debug_emission(self._h, _ptr(h), len(h), _ptr(out)), "rtx_debug_emission")
+        return out[:, :4].copy(), out[:, 4].copy().view(np.uint32)
+
+    def light_sample(self, seeds):
+        """the first half of a triangle-light NEE sample at (n, 2) uint32 seeds, by the device functions nee_sample runs -> dict: light (n,) uint32, point (n, 3), st (n, 2),
+        em (n, 3) = em * tl, pdf_l (n,), seed (n, 2) uint32 after the three draws; RtxError (RTX_ERR_STATE) for a scene without a light list"""
+        a = np.ascontiguousarray(seeds, np.uint32).reshape(-1, 2)
+        out = np.zeros((len(a), 12), np.float32)
+        self._ck(lib.rtx_debug_light_sample(self._h, _ptr(a), len(a), _ptr(out)), "rtx_debug_light_sample")
+        return dict(light=out[:, 0].copy().view(np.uint32), point=out[:, 1:4].copy(), st=out[:, 4:6].copy(), em=out[:, 6:9].copy(), pdf_l=out[:, 9].copy(),
+                    seed=out[:, 10:12].copy().view(np.uint32))
+
     def ess(self, material, pr, ndotv):
         """the Ess the view terms would use for `material` at (Pr', NdotV) pairs: the energy table where the material has a roughness map and a table is set, else its LUT"""
         a = _f32(pr).reshape(-1); b = _f32(ndotv).reshape(-1)
@@ -759,7 +783,7 @@ class Context:
     def bind_maps(self, scene):
         """the optional texture attributes of a scene (duck-typed): `uvs` — per mesh an (index count, 2) array or None; `textures` — a list whose entries are (H, W, 4)
         uint8 arrays or (array, srgb) pairs, anything else (a file name without pixels) is skipped; `material_maps` — per material an index into `textures` or -1 / None;
-        `opacity_maps`, `normal_maps`, `ks_maps`, `pr_maps`, `pm_maps` — likewise for the MAP_OPACITY, MAP_NORMAL, MAP_KS, MAP_PR and MAP_PM slots; `ess_table` — a
+        `opacity_maps`, `normal_maps`, `ks_maps`, `pr_maps`, `pm_maps`, `ke_maps` — likewise for the MAP_OPACITY, MAP_NORMAL, MAP_KS, MAP_PR, MAP_PM and MAP_KE slots; `ess_table` — a
         (rows, 16) energy table for set_ess_table, or None.  A map whose texture was skipped is not bound."""
         for mesh, uv in enumerate(getattr(scene, "uvs", None) or []):
             if uv is not None and len(uv):
@@ -780,7 +804,7 @@ class Context:
         for mat, t in enumerate(getattr(scene, "normal_maps", None) or []):
             if t is not None and t >= 0 and t in ids:
                 self.set_material_map(mat, ids[t], MAP_NORMAL)
-        for attr, slot in (("ks_maps", MAP_KS), ("pr_maps", MAP_PR), ("pm_maps", MAP_PM)):
+        for attr, slot in (("ks_maps", MAP_KS), ("pr_maps", MAP_PR), ("pm_maps", MAP_PM), ("ke_maps", MAP_KE)):
             for mat, t in enumerate(getattr(scene, attr, None) or []):
                 if t is not None and t >= 0 and t in ids:
                     self.set_material_map(mat, ids[t], slot)

@@ -33,6 +33,15 @@ static int upload_lights(rtx_ctx* c) {         // the light records and their CD
     for (size_t i = 0; i < cdf.size(); i++) cdf[i] = B.lights[i].cdf;
     int r = upload(c, c->scene.d_lights, B.lights);
     if (r) return r;
+    if (B.emi_q.empty()) c->scene.d_emi_q.release();       // (emission maps: q per global triangle id travels with the list it was built with)
+    else if ((r = upload(c, c->scene.d_emi_q, B.emi_q))) return r;
+    if (B.lights_plain.empty()) { c->scene.d_lights_plain.release(); c->scene.d_cdf_plain.release(); }      // (... and so does the unmapped scene's list)
+    else {
+        std::vector<float>& pc = c->scene.h_cdf_plain;
+        pc.resize(B.lights_plain.size());
+        for (size_t i = 0; i < pc.size(); i++) pc[i] = B.lights_plain[i].cdf;
+        if ((r = upload(c, c->scene.d_lights_plain, B.lights_plain)) || (r = upload(c, c->scene.d_cdf_plain, pc))) return r;
+    }
     return upload(c, c->scene.d_cdf, cdf);
 }
 static int upload_built(rtx_ctx* c) {          // every device array of a freshly built (or freshly loaded) scene
@@ -72,7 +81,8 @@ static int sync_textures(rtx_ctx* c, bool renumbered, bool deformed) {
     const bool cut = S.built.cutouts_active = H.cutouts_active();
     const bool nrm = S.built.normals_active = H.normals_active();
     const bool spc = S.built.spec_active = H.spec_active();
-    const bool active = S.built.maps_active || cut || nrm || spc;   // the UVs serve all four
+    const bool emi = S.built.emi_active = H.emi_active();
+    const bool active = S.built.maps_active || cut || nrm || spc || emi;   // the UVs serve all five
     int r;
     if (H.tex_dirty) {                                       // (a scene that never saw one of the three setters allocates nothing here)
         std::vector<TexDesc> desc(H.textures.size()); std::vector<uint32_t> pool;
@@ -96,6 +106,12 @@ static int sync_textures(rtx_ctx* c, bool renumbered, bool deformed) {
             std::vector<int32_t> smaps(nm * 3, -1);
             for (int k = 0; k < 3; k++) for (size_t m = 0; m < nm && m < H.map_spec[k].size(); m++) smaps[k * nm + m] = H.map_spec[k][m];
             if ((r = upload(c, S.d_map_spec, smaps))) return r;
+        }
+        if (!H.any_emi_map()) S.d_map_ke.release();
+        else {
+            std::vector<int32_t> emaps(H.mats128.size() / 32, -1);
+            for (size_t m = 0; m < emaps.size() && m < H.map_ke.size(); m++) emaps[m] = H.map_ke[m];
+            if ((r = upload(c, S.d_map_ke, emaps))) return r;
         }
         if (!H.ess_rows) S.d_ess_tab.release();
         else if ((r = upload(c, S.d_ess_tab, H.ess_table))) return r;
@@ -428,7 +444,7 @@ int rtx_commit_scene(rtx_ctx* c) {
     // On the GPU: a scene that is already resident and not a tiny one (whose pre-test records depend on world positions).
     // a tiny scene leaves its pre-test records for the general path while a texture map is active and returns to them afterwards: the commit that crosses that line rebuilds
     {   size_t ntri_all = 0; for (const InstHost& in : c->host.insts) ntri_all += c->host.meshes[in.mesh].idx.size() / 3;
-        if (c->host.tex_dirty && ntri_all <= kSmallSceneMaxTris && (c->host.maps_active() != c->scene.built.maps_active || c->host.cutouts_active() != c->scene.built.cutouts_active || c->host.normals_active() != c->scene.built.normals_active || c->host.spec_active() != c->scene.built.spec_active)) c->host.topo_dirty = true;
+        if (c->host.tex_dirty && ntri_all <= kSmallSceneMaxTris && (c->host.maps_active() != c->scene.built.maps_active || c->host.cutouts_active() != c->scene.built.cutouts_active || c->host.normals_active() != c->scene.built.normals_active || c->host.spec_active() != c->scene.built.spec_active || c->host.emi_active() != c->scene.built.emi_active)) c->host.topo_dirty = true;
         // ... and so it does while an environment is bound
         if (c->host.env_dirty && ntri_all <= kSmallSceneMaxTris && (c->host.env.n != 0) != c->scene.built.env_active) c->host.topo_dirty = true; }
     bool build = !(c->opt.gpu_refit && gpu_refittable(c) && !c->host.topo_dirty);
@@ -440,6 +456,11 @@ int rtx_commit_scene(rtx_ctx* c) {
     // only UVs, textures or map ids changed on a resident general scene: tables are uploaded, nothing is refitted (rtx_stats.bvh_refits and the tree stay)
     // ... and likewise when only the environment changed
     const bool tex_only = !build && (c->host.tex_dirty || c->host.env_dirty) && c->host.only_maps_changed(B0);
+    // ... except that, while an emission map is active on an emitter or was at the previous commit, the light list follows the texels: rebuilt on the host, uploaded
+    if (tex_only && c->host.tex_dirty && (B0.emi_active || c->host.emi_active())) {
+        c->host.build_lights(c->scene.built);
+        if ((r = upload_lights(c))) return r;
+    }
     const bool probe = (build || !flipped) && !tex_only;   // the any-hit order is a property of the tree and the lights' whereabouts: not re-probed because something was hidden or shown
     if (!build && !tex_only) {
         if ((r = refit_resident(c, deform))) return r;
@@ -475,6 +496,7 @@ int rtx_save_scene_cache(rtx_ctx* c, const char* path) {
     if (c->scene.host_mirror_stale) { c->err = "save_scene_cache: the per-triangle records were re-derived on the GPU after rtx_update_mesh_vertices and the host holds no current copy; commit with RTX_OPT_DEFORM_REBUILD 1 (host builder) to save a cache"; return RTX_ERR_STATE; }
     if (c->scene.built.any_hidden) { c->err = "save_scene_cache: an instance is hidden (rtx_set_instance_visible): the device's boxes and triangle records leave it out and the file format holds no visibility; show every instance and commit to save a cache"; return RTX_ERR_STATE; }
     if (c->host.env.n) { c->err = "save_scene_cache: an environment is bound (rtx_set_environment) and the file format holds no environment; clear it and commit to save a cache"; return RTX_ERR_STATE; }
+    if (c->host.any_emi_map()) { c->err = "save_scene_cache: a material has an emission map (rtx_set_material_map, RTX_MAP_KE) and the file format holds no texels; unmap every material and commit to save a cache"; return RTX_ERR_STATE; }
     if (c->host.any_spec_map()) { c->err = "save_scene_cache: a material has a specular, roughness or metalness map (rtx_set_material_map, RTX_MAP_KS / RTX_MAP_PR / RTX_MAP_PM) and the file format holds no texels; unmap every material and commit to save a cache"; return RTX_ERR_STATE; }
     if (c->host.any_normal_map()) { c->err = "save_scene_cache: a material has a normal map (rtx_set_material_map, RTX_MAP_NORMAL) and the file format holds no texels; unmap every material and commit to save a cache"; return RTX_ERR_STATE; }
     if (c->host.any_opacity_map()) { c->err = "save_scene_cache: a material has an opacity map (rtx_set_material_map, RTX_MAP_OPACITY) and the file format holds no texels; unmap every material and commit to save a cache"; return RTX_ERR_STATE; }
@@ -525,6 +547,7 @@ static int finalise_scene(rtx_ctx* c) {
     s.insts = (const InstGPU*)c->scene.d_insts.p; s.ninst = (uint32_t)B.insts.size();
     s.lights = (const LightGPU*)c->scene.d_lights.p; s.nlights = (uint32_t)B.lights.size(); s.cdf = (const float*)c->scene.d_cdf.p;
     s.total_weight = B.total_weight;
+    if (B.emi_active && !(B.total_weight > 0.0f)) s.nlights = 0;      // emission maps: every map black, no emitter has weight — the renderer has no light list (rtx_stats.lights and rtx_get_lights keep the count)
     // texture maps: the sampler's tables whenever there are textures; UVs and map ids only while a map is active (then k_shade<.., TEX> runs, rtx_render.hip)
     s.tex_desc = (const TexDesc*)c->scene.d_tex_desc.p; s.ntex = c->scene.ntex; s.texels = (const uint32_t*)c->scene.d_texels.p; s.tex_lut = (const float*)c->scene.d_tex_lut.p;
     // environment lighting: env_n says one is bound (the separate default kernels run), env_tex that it has weight (k_shade<.., ENV> runs)
@@ -532,12 +555,13 @@ static int finalise_scene(rtx_ctx* c) {
     const bool env_lit = s.env_n && c->scene.env_total > 0.0;
     s.env_tex = env_lit ? (const F4*)c->scene.d_env_tex.p : nullptr; s.env_marg = env_lit ? (const float*)c->scene.d_env_marg.p : nullptr; s.env_cond = env_lit ? (const float*)c->scene.d_env_cond.p : nullptr;
     // (a scene with cut-outs and no diffuse map: k_shade<.., TEX> runs all the same, selected by tri_uv, and reads a map_kd table of -1s — every material keeps its own Kd)
-    const bool uv_active = B.maps_active || B.cutouts_active || B.normals_active || B.spec_active;
+    const bool uv_active = B.maps_active || B.cutouts_active || B.normals_active || B.spec_active || B.emi_active;
     s.tri_uv = uv_active ? (const float*)c->scene.d_tri_uv.p : nullptr; s.map_kd = uv_active ? (const int32_t*)c->scene.d_map_kd.p : nullptr;
     s.tri_cut = B.cutouts_active ? (const int32_t*)c->scene.d_tri_cut.p : nullptr;
     {   const int32_t* ms = B.spec_active ? (const int32_t*)c->scene.d_map_spec.p : nullptr; const size_t nm = c->host.mats128.size() / 32;
         s.map_ks = ms; s.map_pr = ms ? ms + nm : nullptr; s.map_pm = ms ? ms + 2 * nm : nullptr;
         s.ess_tab = (B.spec_active && c->host.ess_rows) ? (const float*)c->scene.d_ess_tab.p : nullptr; s.ess_rows = s.ess_tab ? c->host.ess_rows : 0u; }
+    s.map_ke = B.emi_active ? (const int32_t*)c->scene.d_map_ke.p : nullptr; s.emi_q = B.emi_active ? (const float*)c->scene.d_emi_q.p : nullptr;
     s.tri_tan = B.normals_active ? (const float*)c->scene.d_tri_tan.p : nullptr; s.map_nrm = B.normals_active ? (const int32_t*)c->scene.d_map_nrm.p : nullptr;
     // LDS budget per workgroup: stack + top of tree + first triangles, kept <= 64 KiB
     // exact bound of the 8-wide tree, no slack: a level adds ONE entry (the rest of its hit siblings) and only where a node has >= 2 internal
@@ -604,7 +628,7 @@ static int finalise_scene(rtx_ctx* c) {
         if (getenv("RTX_DEBUG_LDS")) fprintf(stderr, "[rtx] stack_depth %u workgroups per CU %u, %u nodes staged, %zu B of LDS\n", s.stack_depth, target, s.lds_nodes, trace_lds_bytes(s));
     }
     pick_lds_closest(c);
-    c->stats.bvh_refits = B.refit_count; c->stats.bvh_nodes = s.nnodes; c->stats.triangles = B.shade.empty() ? B.built_tris : (uint32_t)B.shade.size(); c->stats.bvh_refs = s.ntris; c->stats.lights = s.nlights; c->stats.materials = s.nmat;
+    c->stats.bvh_refits = B.refit_count; c->stats.bvh_nodes = s.nnodes; c->stats.triangles = B.shade.empty() ? B.built_tris : (uint32_t)B.shade.size(); c->stats.bvh_refs = s.ntris; c->stats.lights = (uint32_t)B.lights.size(); c->stats.materials = s.nmat;
     c->committed = true;
     return RTX_OK;
 }

@@ -133,9 +133,22 @@ struct rtx_ctx {
         // specular, roughness and metalness maps: the three per-material map tables back to back (ks | pr | pm, nmat entries each) and the energy table of rtx_set_ess_table,
         // both with the other tables and only while the host holds a map resp. a table
         DevBuf d_map_spec, d_ess_tab;
+        // emission maps: the per-material map ids with the other tables, only while the host holds one; q per global triangle id with the light list, only while one is active
+        DevBuf d_map_ke, d_emi_q;
+        DevBuf d_lights_plain, d_cdf_plain; std::vector<float> h_cdf_plain;      // ... and the unmapped scene's light list, for the renderers that ignore the maps (plain_scene())
         // environment lighting (sync_environment, rtx_commit.hip): the tables of the bound map, rebuilt by the commit after rtx_set_environment; env_total = their weight sum
         DevBuf d_env_tex, d_env_marg, d_env_cond; double env_total = 0.0;
     } scene;
+    // the scene as rtx_render_v6_pass1 and rtx_render_restir read it: they ignore the emission maps (include/rtx.h, EMISSION MAPS), so while one is active they get the
+    // light list of the unmapped scene and no emission tables; otherwise dsc as it is
+    DevScene plain_scene() const {
+        DevScene s = dsc;
+        if (scene.built.emi_active) {
+            s.lights = (const LightGPU*)scene.d_lights_plain.p; s.cdf = (const float*)scene.d_cdf_plain.p; s.nlights = (uint32_t)scene.built.lights_plain.size();
+            s.total_weight = scene.built.total_weight_plain; s.map_ke = nullptr; s.emi_q = nullptr;
+        }
+        return s;
+    }
 
     // ---- the path tracer's frame (rtx_render.hip) ----
     struct PathFrame {

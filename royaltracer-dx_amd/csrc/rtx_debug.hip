@@ -239,6 +239,41 @@ int rtx_debug_ess(rtx_ctx* c, uint32_t material, const float* pr, const float* n
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return RTX_OK;
 }
+// Ke' and q under the emission maps (rtx_emimap.hpp), by the device function k_shade<.., EMI> runs for a lane that hits an emitter
+int rtx_debug_emission(rtx_ctx* c, const float* hits4, uint32_t n, float* out8) {
+    BIND(c);
+    if (!c->committed) { c->err = "scene not committed"; return RTX_ERR_STATE; }
+    if (!n) return RTX_OK;
+    if (!hits4 || !out8) { c->err = "emission: null array"; return RTX_ERR_INVALID; }
+    for (uint32_t i = 0; i < n; i++) {                       // a triangle id the scene does not have would index past the per-triangle tables
+        uint32_t prim; memcpy(&prim, &hits4[(size_t)i * 4 + 3], 4);
+        if (prim != kMissPrim && prim >= c->stats.triangles) { c->err = "emission: triangle id out of range"; return RTX_ERR_INVALID; }
+    }
+    DevBuf d_hits, d_out;
+    HIPCHK(c, d_hits.ensure((size_t)n * 16)); HIPCHK(c, d_out.ensure((size_t)n * 32));
+    TO_DEVICE(c, d_hits.p, hits4, (size_t)n * 16);
+    launch_dbg_emission(c->stream, c->dsc, (const F4*)d_hits.p, n, (float*)d_out.p);
+    HIPCHK(c, hipGetLastError());
+    TO_HOST(c, out8, d_out.p, (size_t)n * 32);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RTX_OK;
+}
+// the first half of a triangle-light NEE sample with the texel of the emission maps, by the device functions nee_sample runs
+int rtx_debug_light_sample(rtx_ctx* c, const uint32_t* seeds2, uint32_t n, float* out12) {
+    BIND(c);
+    if (!c->committed) { c->err = "scene not committed"; return RTX_ERR_STATE; }
+    if (!c->dsc.nlights) { c->err = "light_sample: the scene has no light list (no emitter, or every emission map black)"; return RTX_ERR_STATE; }
+    if (!n) return RTX_OK;
+    if (!seeds2 || !out12) { c->err = "light_sample: null array"; return RTX_ERR_INVALID; }
+    DevBuf d_in, d_out;
+    HIPCHK(c, d_in.ensure((size_t)n * 8)); HIPCHK(c, d_out.ensure((size_t)n * 48));
+    TO_DEVICE(c, d_in.p, seeds2, (size_t)n * 8);
+    launch_dbg_light_sample(c->stream, c->dsc, (const uint32_t*)d_in.p, n, (float*)d_out.p);
+    HIPCHK(c, hipGetLastError());
+    TO_HOST(c, out12, d_out.p, (size_t)n * 48);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RTX_OK;
+}
 static int dbg_bsdf(rtx_ctx* c, bool sample, uint32_t mat, uint32_t flags, const float* in, uint32_t stride_in, uint32_t n, float* out8) {
     BIND(c);
     if (!c->committed) { c->err = "scene not committed"; return RTX_ERR_STATE; }

@@ -148,6 +148,54 @@ __global__ __launch_bounds__(kBlock) void k_dbg_ess(DevScene sc, uint32_t materi
     const float* tab = sc.map_pr ? spec_ess_table(sc, material) : nullptr;
     out[i] = tab ? ess_table(tab, sc.ess_rows, pr[i], ndotv[i]) : ess_lut(m, ndotv[i]);
 }
+// Ke' and q of the emission maps (rtx_emimap.hpp: emi_hit, as k_shade<.., EMI> runs it for a lane that hits an emitter) at n hit records -> 8 words per record: Ke'.xyz,
+// q, the emission texture id bits, 0, 0, 0.  A non-emitter or a miss gives four zeros and 0xFFFFFFFF; while no emission map is active an emitter gives the table's Ke, the
+// mean add_emissive forms of it and 0xFFFFFFFF
+__global__ __launch_bounds__(kBlock) void k_dbg_emission(DevScene sc, const F4* __restrict__ hits, uint32_t n, float* __restrict__ out8) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const F4 h = hits[i];
+    const uint32_t prim = f2u(h.w);
+    EmiHit e; e.Ke = mk3(0.0f, 0.0f, 0.0f); e.q = 0.0f;
+    int32_t tex = -1;
+    if (prim != kMissPrim) {
+        const uint32_t mat = sc.shade[prim].mat;
+        if (mat < sc.nmat) {
+            const MatGPU& m = sc.mats[mat];
+            if (m.Ke_len > 0.0f) {
+                if (sc.map_ke) e = emi_hit(sc, m, mat, prim, h.y, h.z, &tex);
+                else { e.Ke = mk3(m.Ke[0], m.Ke[1], m.Ke[2]); e.q = (e.Ke.x + e.Ke.y + e.Ke.z) / 3.0f; }
+            }
+        }
+    }
+    float* o = out8 + 8 * (size_t)i;
+    o[0] = e.Ke.x; o[1] = e.Ke.y; o[2] = e.Ke.z; o[3] = e.q; o[4] = u2f((uint32_t)tex); o[5] = 0.0f; o[6] = 0.0f; o[7] = 0.0f;
+}
+// the first half of a triangle-light NEE sample, statement for statement as nee_sample (rtx_shade.hpp) runs it — the CDF search on the selection draw, the two area draws and
+// their fold, the sampled point — and the texel of the emission maps (emi_light_uv / emi_light_em) -> 12 words per seed: light index bits, the point, s, t, em * tl, pdf_l,
+// the seed after the three draws.  A light without the map gives s = t = 0 and the record's em.  The launcher checks that the scene has a light list
+__global__ __launch_bounds__(kBlock) void k_dbg_light_sample(DevScene sc, const uint32_t* __restrict__ seeds2, uint32_t n, float* __restrict__ out12) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    uint32_t s0 = seeds2[2 * (size_t)i], s1 = seeds2[2 * (size_t)i + 1];
+    const float rv = tea_next(s0, s1);
+    int left = 0, right = (int)sc.nlights - 1, sel = 0;
+    while (left <= right) {
+        const int mid = left + (right - left) / 2;
+        if (rv < sc.cdf[mid]) { sel = mid; right = mid - 1; } else left = mid + 1;
+    }
+    const LightGPU& lt = sc.lights[sel];
+    const f3 xv = mk3(lt.xv[0], lt.xv[1], lt.xv[2]), yv = mk3(lt.yv[0], lt.yv[1], lt.yv[2]), zv = mk3(lt.zv[0], lt.zv[1], lt.zv[2]);
+    float xi1 = tea_next(s0, s1), xi2 = tea_next(s0, s1);
+    if (xi1 + xi2 > 1.0f) { xi1 = 1.0f - xi1; xi2 = 1.0f - xi2; }
+    const float u = 1.0f - xi1 - xi2, v = xi1, w = xi2;
+    const f3 sp = lincomb3(xv, u, yv, v, zv, w);
+    float s = 0.0f, t = 0.0f;
+    f3 em = mk3(lt.em[0], lt.em[1], lt.em[2]);
+    if (sc.map_ke) { if (lt.emi_tex >= 0) emi_light_uv(sc, lt.prim, u, v, w, s, t); em = emi_light_em(sc, lt, u, v, w); }
+    float* o = out12 + 12 * (size_t)i;
+    o[0] = u2f((uint32_t)sel); o[1] = sp.x; o[2] = sp.y; o[3] = sp.z; o[4] = s; o[5] = t; o[6] = em.x; o[7] = em.y; o[8] = em.z; o[9] = lt.pdf_l; o[10] = u2f(s0); o[11] = u2f(s1);
+}
 // the environment's sampler and lookup (rtx_env.hpp), as k_shade<.., ENV> runs them (the marginal CDF from global memory: the same values as its LDS copy)
 __global__ __launch_bounds__(kBlock) void k_dbg_env_sample(DevScene sc, const uint32_t* __restrict__ seeds2, uint32_t n, F4* __restrict__ out) {
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;

@@ -30,7 +30,9 @@ namespace rtx {
 // SPC (implies TEX, never LAMBERT): some material has a specular, roughness or metalness map (rtx_specmap.hpp): Ks', Pr', Pm' of a lane that shades are formed once, next to
 // Kd' and n', and handed to the view terms, the NEE samples and the continuation as kdpi is — five floats live across the item, and where a roughness map meets an energy
 // table the view terms take their Ess from the table.  SPC = false is the code as it was.
-template <bool LAMBERT, bool TEX = false, bool ENV = false, bool NRM = false, bool SPC = false>
+// EMI (implies TEX): some emitter's material has an emission map (rtx_emimap.hpp): a lane that hits an emitter adds Ke' and weighs it by the triangle's q, and every
+// triangle-light NEE sample multiplies the light's emission by the texel at the sampled point.  Nothing of it lives across the item.  EMI = false is the code as it was.
+template <bool LAMBERT, bool TEX = false, bool ENV = false, bool NRM = false, bool SPC = false, bool EMI = false>
 __device__ __forceinline__ void shade_item(const DevScene& sc, const DevFrame& f, const DevPaths& p, uint32_t bounce, uint32_t nee, bool last, size_t qb,
                                            const uint32_t* __restrict__ myq, uint32_t* __restrict__ mynext, uint32_t* s_cnt, bool valid, uint32_t qi, Prof* pf, const float* lds_cdf = nullptr, const LightGPU* lds_lights = nullptr, const MatGPU* lds_mats = nullptr, const float* env_marg = nullptr) {
     PathState S = idle_path();
@@ -56,7 +58,10 @@ __device__ __forceinline__ void shade_item(const DevScene& sc, const DevFrame& f
             PF_MARK(1);
             if (sf.mat < sc.nmat) {
                 const MatGPU& m = mats[sf.mat];
-                if (m.Ke_len > 0.0f) add_emissive(sc, p, S, sf, m, bounce, nee);   // Hit.hlsl:126, Sampler_v6.hlsl:457
+                if (m.Ke_len > 0.0f) {                                             // Hit.hlsl:126, Sampler_v6.hlsl:457
+                    if (EMI) { const EmiHit eh = emi_hit(sc, m, sf.mat, prim, h.y, h.z); add_emissive(sc, p, S, sf, m, bounce, nee, false, &eh); }
+                    else add_emissive(sc, p, S, sf, m, bounce, nee);
+                }
                 else { shading = true; if (TEX) kdv = tex_kdpi(sc, m, sf.mat, prim, h.y, h.z); if (NRM) sf.normal = nrm_perturb(sc, sf, prim, h.y, h.z, -S.d);
                        if (SPC) { spv = spec_view(sc, m, sf.mat, prim, h.y, h.z); ess_tab = spec_ess_table(sc, sf.mat); } }
             }
@@ -77,7 +82,7 @@ __device__ __forceinline__ void shade_item(const DevScene& sc, const DevFrame& f
         bool push = false;
         F4 so = {0, 0, 0, 0}, sd = {0, 0, 0, 0}; f3 con = mk3(0, 0, 0);
         if (shading) { PF_COUNT(3); }
-        if (shading) push = nee_sample(sc, *mp, f.flags, nee, S, pos, normal, outgoing, so, sd, con, sc.nsmall != 0u && sf.near_hull, eta_p, mv, lds_cdf, lds_lights, kdpi, sp);
+        if (shading) push = nee_sample(sc, *mp, f.flags, nee, S, pos, normal, outgoing, so, sd, con, sc.nsmall != 0u && sf.near_hull, eta_p, mv, lds_cdf, lds_lights, kdpi, sp, EMI);
         PF_MARK(3);
         if (push) { PF_COUNT(4); }
         const size_t seg = (size_t)j * f.qcap * gridDim.x + qb;           // NEE slot j, this workgroup's sub-queue
@@ -152,13 +157,25 @@ __host__ __device__ inline uint32_t shade_env_lds(uint32_t lights_bytes, uint32_
 #ifndef RTX_SHADE_WAVES_SPC
 #define RTX_SHADE_WAVES_SPC 5      // ... of the SPC instantiations, with or without ENV / NRM (profiles/specmap_kernel_resources.md)
 #endif
-template <bool SORT, bool LAMBERT, bool TEX = false, bool ENV = false, bool NRM = false, bool SPC = false>     // LAMBERT: RTX_FLAG_LAMBERT_ONLY as a compile-time constant (no GGX / transmission code in that instantiation); TEX: texture maps, ENV: environment lighting, NRM: normal maps, SPC: specular maps (shade_item)
-__global__ __launch_bounds__(kBlock, (SPC ? RTX_SHADE_WAVES_SPC : NRM ? RTX_SHADE_WAVES_NRM : ENV ? RTX_SHADE_WAVES_ENV : RTX_SHADE_WAVES)) void k_shade(DevScene sc, DevFrame f_in, DevPaths p, uint32_t bounce,
+// ... of the EMI instantiations, with or without ENV / NRM (profiles/emimap_kernel_resources.md): the highest cap at which no form of the group spills a VGPR.  The light
+// sample's texel fetch is live beside the mixture's terms: the GGX forms spill 3 - 7 registers at 6 waves, the SPC forms 1 at 5; the Lambert forms fit 6
+#ifndef RTX_SHADE_WAVES_EMI
+#define RTX_SHADE_WAVES_EMI 5
+#endif
+#ifndef RTX_SHADE_WAVES_EMI_LAMBERT
+#define RTX_SHADE_WAVES_EMI_LAMBERT 6
+#endif
+#ifndef RTX_SHADE_WAVES_EMI_SPC
+#define RTX_SHADE_WAVES_EMI_SPC 4
+#endif
+template <bool SORT, bool LAMBERT, bool TEX = false, bool ENV = false, bool NRM = false, bool SPC = false, bool EMI = false>     // LAMBERT: RTX_FLAG_LAMBERT_ONLY as a compile-time constant (no GGX / transmission code in that instantiation); TEX: texture maps, ENV: environment lighting, NRM: normal maps, SPC: specular maps, EMI: emission maps (shade_item)
+__global__ __launch_bounds__(kBlock, (EMI ? (SPC ? RTX_SHADE_WAVES_EMI_SPC : LAMBERT ? RTX_SHADE_WAVES_EMI_LAMBERT : RTX_SHADE_WAVES_EMI) : SPC ? RTX_SHADE_WAVES_SPC : NRM ? RTX_SHADE_WAVES_NRM : ENV ? RTX_SHADE_WAVES_ENV : RTX_SHADE_WAVES)) void k_shade(DevScene sc, DevFrame f_in, DevPaths p, uint32_t bounce,
                                                   const uint32_t* __restrict__ queue, const uint32_t* __restrict__ qcount,
                                                   uint32_t* __restrict__ next_queue, uint32_t* __restrict__ next_count,
                                                   uint32_t* __restrict__ shcounts /* [nee][gridDim.x] */) {
     static_assert(!NRM || (TEX && !SORT), "the normal-mapped forms are TEX forms of the default kernel");
     static_assert(!SPC || (TEX && !SORT && !LAMBERT), "the specular-mapped forms are GGX TEX forms of the default kernel");
+    static_assert(!EMI || (TEX && !SORT), "the emission-mapped forms are TEX forms of the default kernel");
     const DevFrame f = frame_with_lambert<LAMBERT>(f_in);
     constexpr uint32_t kSlots = kMaxNee + (ENV ? 1u : 0u);  // (the environment's slot follows the nee_samples <= kMaxNee triangle-light slots)
     __shared__ uint32_t s_cnt[1 + kMaxNee + (ENV ? 4u : 0u)];     // [0] next-queue length, [1 + j] shadow queue j length (ENV: one slot more, in a 16-byte step: the static LDS precedes the dynamic region, whose float4 reads need their alignment)
@@ -228,7 +245,7 @@ __global__ __launch_bounds__(kBlock, (SPC ? RTX_SHADE_WAVES_SPC : NRM ? RTX_SHAD
         }
         for (uint32_t base = threadIdx.x & ~63u; base < cn; base += kBlock) {
             const uint32_t i = base + (threadIdx.x & 63u);
-            shade_item<LAMBERT, TEX, ENV, NRM, SPC>(sc, f, p, bounce, nee, last, qb, myq, mynext, s_cnt, i < cn, cb + (SORT ? s_sorted[i] : i), pf, lds_cdf, lds_lights, lds_mats, env_marg);
+            shade_item<LAMBERT, TEX, ENV, NRM, SPC, EMI>(sc, f, p, bounce, nee, last, qb, myq, mynext, s_cnt, i < cn, cb + (SORT ? s_sorted[i] : i), pf, lds_cdf, lds_lights, lds_mats, env_marg);
         }
         if (SORT) __syncthreads();                              // the next chunk overwrites the LDS buffers
     }

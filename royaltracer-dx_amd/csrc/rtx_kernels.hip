@@ -196,6 +196,16 @@ void launch_shade(hipStream_t st, const DevScene& sc, const DevFrame& f, const D
         // an environment is bound: the default kernel too, in its ENV form when the map has weight (a black map adds nothing and casts nothing: the kernels without it)
         // a specular map is active and the frame is not RTX_FLAG_LAMBERT_ONLY: the SPC form of the TEX kernel (tri_uv is set whenever map_pr is), with or without the
         // environment's sample and the normal maps.  A Lambert-only frame reads none of the three: it falls through to the kernels below
+        // an emission map is active: the EMI form of the TEX kernel (tri_uv is set whenever map_ke is), Lambert or GGX, with or without the environment's sample, the normal maps
+        // (tri_tan exists only while one is active) and, in a GGX frame, the specular maps
+        if (sc.map_ke) {
+            uint32_t lb, mb; shade_lds_plan(sc.nlights, sc.nmat, false, lb, mb);
+            dispatch_bool(sc.env_tex != nullptr, [&](auto env) { dispatch_bool(sc.tri_tan != nullptr, [&](auto nrm) { dispatch_bool(!LL && sc.map_pr != nullptr, [&](auto spc) {
+                constexpr bool EE = decltype(env)::value, SS = !LL && decltype(spc)::value;
+                hipLaunchKernelGGL((k_shade<false, LL, true, EE, decltype(nrm)::value, SS, true>), dim3(f.nblocks), dim3(kBlock), (size_t)lb + mb + (EE ? shade_env_lds(lb, mb, sc.env_n) : 0u), st, sc, f, p, bounce, queue, qcount, next_queue, next_count, shcounts);
+            }); }); });
+            return;
+        }
         if constexpr (!LL) if (sc.map_pr) {
             uint32_t lb, mb; shade_lds_plan(sc.nlights, sc.nmat, false, lb, mb);
             dispatch_bool(sc.env_tex != nullptr, [&](auto env) { dispatch_bool(sc.tri_tan != nullptr, [&](auto nrm) {
@@ -394,6 +404,12 @@ void launch_dbg_specular(hipStream_t st, const DevScene& sc, const F4* hits, uin
 }
 void launch_dbg_ess(hipStream_t st, const DevScene& sc, uint32_t material, const float* pr, const float* ndotv, uint32_t n, float* out) {
     hipLaunchKernelGGL(k_dbg_ess, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, sc, material, pr, ndotv, n, out);
+}
+void launch_dbg_emission(hipStream_t st, const DevScene& sc, const F4* hits, uint32_t n, float* out8) {
+    hipLaunchKernelGGL(k_dbg_emission, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, sc, hits, n, out8);
+}
+void launch_dbg_light_sample(hipStream_t st, const DevScene& sc, const uint32_t* seeds2, uint32_t n, float* out12) {
+    hipLaunchKernelGGL(k_dbg_light_sample, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, sc, seeds2, n, out12);
 }
 void launch_dbg_env_sample(hipStream_t st, const DevScene& sc, const uint32_t* seeds2, uint32_t n, F4* out) {
     hipLaunchKernelGGL(k_dbg_env_sample, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, st, sc, seeds2, n, out);

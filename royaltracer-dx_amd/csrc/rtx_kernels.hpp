@@ -64,6 +64,10 @@ struct DevScene {
     const int32_t* map_pm;              // ... of RTX_MAP_PM
     const float* ess_tab;               // rtx_set_ess_table: ess_rows x 16 floats, or nullptr (none set, or no specular map active)
     uint32_t ess_rows;
+    // emission maps (rtx_emimap.hpp; behind the last member again).  Both nullptr unless an emitting material that some triangle uses has RTX_MAP_KE: such scenes launch what
+    // they always launched; otherwise both are set, tri_uv and map_kd too, the light records carry prim / emi_tex, and k_shade<.., EMI> runs
+    const int32_t* map_ke;              // per material: texture id of RTX_MAP_KE, or -1
+    const float* emi_q;                 // per global triangle id: q of the emissive hit's MIS pdf (include/rtx.h, EMISSION MAPS)
 };
 
 // one sample batch of one frame
@@ -280,6 +284,8 @@ void launch_dbg_opacity(hipStream_t, const DevScene&, const F4* hits, uint32_t n
 void launch_dbg_shading_normal(hipStream_t, const DevScene&, const F4* rays, const F4* hits, uint32_t n, F4* out);   // surface() + nrm_perturb at n (ray, hit record) pairs -> (n', normal texture id bits or 0xFFFFFFFF)
 void launch_dbg_specular(hipStream_t, const DevScene&, const F4* hits, uint32_t n, float* out8);                    // spec_view at n hit records -> (Ks', Pr', Pm', ks / pr / pm texture id bits or 0xFFFFFFFF)
 void launch_dbg_ess(hipStream_t, const DevScene&, uint32_t material, const float* pr, const float* ndotv, uint32_t n, float* out);     // the Ess mix_view uses for `material` at n (Pr', NdotV) pairs
+void launch_dbg_emission(hipStream_t, const DevScene&, const F4* hits, uint32_t n, float* out8);                    // emi_hit at n hit records -> (Ke', q, emission texture id bits or 0xFFFFFFFF, 0, 0, 0)
+void launch_dbg_light_sample(hipStream_t, const DevScene&, const uint32_t* seeds2, uint32_t n, float* out12);       // emi_light_sample at n seeds -> (light index bits, point, s, t, em * tl, pdf_l, seed after)
 void launch_dbg_env_sample(hipStream_t, const DevScene&, const uint32_t* seeds2, uint32_t n, F4* out);
 void launch_dbg_env_eval(hipStream_t, const DevScene&, const float* dirs3, uint32_t n, F4* out);
 void launch_dbg_tea(hipStream_t, uint32_t s0, uint32_t s1, uint32_t n, float* out, uint32_t* seed_out);

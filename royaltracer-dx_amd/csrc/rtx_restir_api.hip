@@ -51,7 +51,7 @@ static int rs_plan(rtx_ctx* c, const DevFrame& f, uint32_t nitems, const uint32_
 static int rs_pass1(rtx_ctx* c, const DevFrame& f, uint32_t sample_id, F4* accum, const uint32_t* pixels, uint32_t npixels, uint32_t* const* bufs, uint32_t lane, hipStream_t st) {
     const uint32_t mb = f.max_bounces, rows = 4u + mb + 1u;
     RsPlan R; int r = rs_plan(c, f, pixels ? npixels : f.npl, pixels, rows, R, lane); if (r) return r;
-    DevScene sc = c->dsc; sc.tri_cut = nullptr; const RsQ& q = R.q;      // (the ReSTIR frame ignores alpha cut-outs, as it ignores map_Kd: its closest-hit launches are the plain instantiations)
+    DevScene sc = c->plain_scene(); sc.tri_cut = nullptr; const RsQ& q = R.q;      // (the ReSTIR frame ignores alpha cut-outs, as it ignores map_Kd: its closest-hit launches are the plain instantiations)
     const CameraGPU* cam = (const CameraGPU*)c->d_cam.p;
     auto row = [&](uint32_t k) { return R.cnt + (size_t)k * R.G; };
     uint32_t* res_di = (uint32_t*)c->rs.d_res_di.p; uint32_t* res_gi = (uint32_t*)c->rs.d_res_gi.p; uint32_t* sdata = (uint32_t*)c->rs.d_sdata.p;
@@ -78,11 +78,11 @@ static int rs_pass1(rtx_ctx* c, const DevFrame& f, uint32_t sample_id, F4* accum
 static int rs_pass3(rtx_ctx* c, const DevFrame& f, uint32_t* const bufs[6], F4* accum, const uint32_t* pixels, uint32_t npixels, uint32_t lane, hipStream_t st) {
     RsPlan R; int r = rs_plan(c, f, pixels ? npixels : f.npl, pixels, 2, R, lane); if (r) return r;
     const CameraGPU* cam = (const CameraGPU*)c->d_cam.p;
-    { Timed t(c, RTX_K_SHADE, st); launch_rs_p3_select(st, c->dsc, R.fq, R.q, cam, bufs, R.cnt, c->opt.restir_keys ? (F4*)c->rs.d_rs_key_a.p : nullptr, c->opt.restir_keys ? (F4*)c->rs.d_rs_key_b.p : nullptr); }
-    { Timed t(c, RTX_K_SHADOW, st); launch_trace_occ(st, c->dsc, R.q, R.cnt); }
-    { Timed t(c, RTX_K_SHADE, st); launch_rs_p3_merge(st, c->dsc, R.fq, R.q, bufs, R.cnt + R.G); }
-    { Timed t(c, RTX_K_SHADOW, st); launch_trace_occ(st, c->dsc, R.q, R.cnt + R.G); }
-    { Timed t(c, RTX_K_SHADE, st); launch_rs_p3_shade(st, c->dsc, R.fq, R.q, bufs, accum); }
+    { Timed t(c, RTX_K_SHADE, st); launch_rs_p3_select(st, c->plain_scene(), R.fq, R.q, cam, bufs, R.cnt, c->opt.restir_keys ? (F4*)c->rs.d_rs_key_a.p : nullptr, c->opt.restir_keys ? (F4*)c->rs.d_rs_key_b.p : nullptr); }
+    { Timed t(c, RTX_K_SHADOW, st); launch_trace_occ(st, c->plain_scene(), R.q, R.cnt); }
+    { Timed t(c, RTX_K_SHADE, st); launch_rs_p3_merge(st, c->plain_scene(), R.fq, R.q, bufs, R.cnt + R.G); }
+    { Timed t(c, RTX_K_SHADOW, st); launch_trace_occ(st, c->plain_scene(), R.q, R.cnt + R.G); }
+    { Timed t(c, RTX_K_SHADE, st); launch_rs_p3_shade(st, c->plain_scene(), R.fq, R.q, bufs, accum); }
     HIPCHK(c, hipGetLastError());
     return RTX_OK;
 }
@@ -135,7 +135,7 @@ int rtx_render_v6_pass1(rtx_ctx* c, const rtx_params* p) {
     for (uint32_t s = 0; s < p->spp; s++) {
         if (c->opt.restir_wave) { if ((r = rs_pass1(c, f, p->sample_base + s, c->accum_ptr(), nullptr, 0, nullptr, 0u, c->stream))) return r; }
         else { Timed t(c, RTX_K_BOUNCE);
-               launch_v6_pass1(c->stream, (uint32_t)c->num_cus * 8u, c->dsc, f, (const CameraGPU*)c->d_cam.p, p->sample_base + s, c->accum_ptr(),
+               launch_v6_pass1(c->stream, (uint32_t)c->num_cus * 8u, c->plain_scene(), f, (const CameraGPU*)c->d_cam.p, p->sample_base + s, c->accum_ptr(),
                                (uint32_t*)c->rs.d_res_di.p, (uint32_t*)c->rs.d_res_gi.p, (uint32_t*)c->rs.d_sdata.p, (unsigned long long*)c->rs.d_p1cnt.p); }
     }
     HIPCHK(c, hipEventRecord(c->ev.end, c->stream));
@@ -254,9 +254,9 @@ int rtx_render_restir(rtx_ctx* c, const rtx_params* p) {
             if ((r = rs_lanes(c, halo, nhalo, [&](const uint32_t* px, uint32_t n, uint32_t lane, hipStream_t st) { return rs_pass1(c, ff, 1u, (F4*)scratch.p, px, n, bufs, lane, st); }))) return r;   // passes 1 + 2
             if ((r = rs_lanes(c, own, nown, [&](const uint32_t* px, uint32_t n, uint32_t lane, hipStream_t st) { return rs_pass3(c, ff, bufs, c->accum_ptr(), px, n, lane, st); }))) return r;
         } else {                                                                                                                            // ... or literally, a thread per pixel
-            { Timed t(c, RTX_K_BOUNCE); launch_v6_pass1(c->stream, mbk, c->dsc, ff, cam, 1u, (F4*)scratch.p, bufs[0], bufs[1], bufs[2], (unsigned long long*)c->rs.d_p1cnt.p, sharded ? halo : nullptr, sharded ? nhalo : 0u); }   // Renderer.cpp:651-654
-            { Timed t(c, RTX_K_BOUNCE); launch_restir_pass2(c->stream, mbk, c->dsc, ff, cam, bufs, (unsigned long long*)c->rs.d_p1cnt.p, sharded ? halo : nullptr, sharded ? nhalo : 0u); }                                       // :662-664
-            { Timed t(c, RTX_K_BOUNCE); launch_restir_pass3(c->stream, mbk, c->dsc, ff, cam, bufs, c->accum_ptr(), (unsigned long long*)c->rs.d_p1cnt.p); }                                    // :671-673
+            { Timed t(c, RTX_K_BOUNCE); launch_v6_pass1(c->stream, mbk, c->plain_scene(), ff, cam, 1u, (F4*)scratch.p, bufs[0], bufs[1], bufs[2], (unsigned long long*)c->rs.d_p1cnt.p, sharded ? halo : nullptr, sharded ? nhalo : 0u); }   // Renderer.cpp:651-654
+            { Timed t(c, RTX_K_BOUNCE); launch_restir_pass2(c->stream, mbk, c->plain_scene(), ff, cam, bufs, (unsigned long long*)c->rs.d_p1cnt.p, sharded ? halo : nullptr, sharded ? nhalo : 0u); }                                       // :662-664
+            { Timed t(c, RTX_K_BOUNCE); launch_restir_pass3(c->stream, mbk, c->plain_scene(), ff, cam, bufs, c->accum_ptr(), (unsigned long long*)c->rs.d_p1cnt.p); }                                    // :671-673
         }
     }
     HIPCHK(c, hipEventRecord(c->ev.end, c->stream));

@@ -3,6 +3,7 @@
 #include "rtx_scene_host.hpp"
 #include "rtx_normalmap_host.hpp"
 #include "rtx_specmap_host.hpp"
+#include "rtx_emimap_host.hpp"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -73,7 +74,7 @@ bool SceneHost::set_materials(const void* mats, uint32_t count) {
     mats128.assign((const float*)mats, (const float*)mats + (size_t)count * 32);
     mats_dirty = true;
     if (any_map()) tex_dirty = true;
-    map_kd.clear(); map_opacity.clear(); map_normal.clear(); for (std::vector<int32_t>& v : map_spec) v.clear();        // the table is replaced: no material of the new one has a map (the energy table is no material's: it stays)
+    map_kd.clear(); map_opacity.clear(); map_normal.clear(); map_ke.clear(); for (std::vector<int32_t>& v : map_spec) v.clear();        // the table is replaced: no material of the new one has a map (the energy table is no material's: it stays)
     return true;
 }
 
@@ -164,9 +165,9 @@ bool SceneHost::set_texture(uint32_t tex, const void* rgba8, uint32_t width, uin
 }
 bool SceneHost::set_material_map(uint32_t material, uint32_t slot, int32_t tex) {
     if (material >= mats128.size() / 32) { err = "set_material_map: unknown material"; return false; }
-    if (slot != 0u && slot != 2u && slot != 4u && slot != 6u && slot != 8u && slot != 10u) { err = "set_material_map: unknown slot (RTX_MAP_KD = 0, RTX_MAP_OPACITY = 2, RTX_MAP_NORMAL = 4, RTX_MAP_KS = 6, RTX_MAP_PR = 8 or RTX_MAP_PM = 10)"; return false; }
+    if (slot > 12u || (slot & 1u)) { err = "set_material_map: unknown slot (RTX_MAP_KD = 0, RTX_MAP_OPACITY = 2, RTX_MAP_NORMAL = 4, RTX_MAP_KS = 6, RTX_MAP_PR = 8, RTX_MAP_PM = 10 or RTX_MAP_KE = 12)"; return false; }
     if (tex < -1 || (tex >= 0 && (size_t)tex >= textures.size())) { err = "set_material_map: unknown texture"; return false; }
-    std::vector<int32_t>& map = slot >= 6u ? map_spec[(slot - 6u) / 2u] : slot == 4u ? map_normal : slot == 2u ? map_opacity : map_kd;
+    std::vector<int32_t>& map = slot == 12u ? map_ke : slot >= 6u ? map_spec[(slot - 6u) / 2u] : slot == 4u ? map_normal : slot == 2u ? map_opacity : map_kd;
     if (map.size() < mats128.size() / 32) map.resize(mats128.size() / 32, -1);
     map[material] = tex;
     tex_dirty = true;
@@ -186,6 +187,11 @@ bool SceneHost::spec_active() const {
         if (mat >= mats128.size() / 32 || material_emits(mat)) continue;
         for (const std::vector<int32_t>& v : map_spec) if (mat < v.size() && v[mat] >= 0) return true;
     }
+    return false;
+}
+bool SceneHost::emi_active() const {
+    if (!any_emi_map()) return false;
+    for (size_t i = 0; i < matids.size(); i += 3) if (emi_texture(matids[i]) >= 0) return true;
     return false;
 }
 bool SceneHost::maps_active() const {
@@ -258,69 +264,107 @@ bool SceneHost::instance_emits(size_t inst) const { return mesh_emits(*this, mes
 void SceneHost::build_lights(BuiltScene& B) const {
     const uint32_t nmat = (uint32_t)(mats128.size() / 32);
     // ---- emissive triangle list + CDF: Renderer.cpp:2123-2233, 2237-2243 ----
-    struct Tmp { float w; uint32_t order; uint32_t inst; f3 p0, p1, p2; float em[3]; };
+    // EMISSION MAPS (include/rtx.h): while one is active the weight of a mapped emitter triangle follows the mean of its texels (rtx_emimap_host.hpp), every light carries
+    // its global triangle id and emission texture, and q per global triangle id is what the emissive hit's MIS pdf reads.  Inactive: the scan as it always was, nothing more
+    const bool emi = emi_active();
+    B.emi_q.clear(); B.light_emi.clear();
+    if (emi) { size_t nt = 0; for (const InstHost& in : insts) nt += meshes[in.mesh].idx.size() / 3; B.emi_q.assign(nt, 0.0f); }
+    const float zero_uv[6] = {0, 0, 0, 0, 0, 0};
+    struct Tmp { float w, w_plain; uint32_t order; uint32_t inst; f3 p0, p1, p2; float em[3]; uint32_t prim; int32_t tex; };
     std::vector<Tmp> tmp;
     for (size_t ii = 0; ii < insts.size(); ii++) {
         if (is_hidden(ii)) continue;                                 // InstanceMask 0: its emitters are no lights (the list of the scene without the instance, instance ids kept)
         const MeshHost& m = meshes[insts[ii].mesh];
         for (uint32_t t = 0; t < m.idx.size() / 3; t++) {
             uint32_t m0 = matids[m.matid_base + t * 3], m1 = matids[m.matid_base + t * 3 + 1], m2 = matids[m.matid_base + t * 3 + 2];
-            if (m0 != m1 || m0 != m2) continue;                      // :2153-2156
             if (m0 >= nmat) continue;
             const float* mat = &mats128[(size_t)m0 * 32];
+            float inten = (mat[8] + mat[9] + mat[10]) / 3.0f;
+            const float inten_plain = inten;
+            int32_t tex = -1;
+            if (emi && (mat[8] + mat[9] + mat[10] > 0.0f)) {          // (a hit reads the material of the first index entry: q is filled before the scan's own filters)
+                float E[3] = {mat[8], mat[9], mat[10]};
+                tex = emi_texture(m0);
+                if (tex >= 0) {
+                    const TexHost& T = textures[tex];
+                    float mean[3];
+                    emi_triangle_mean(T.rgba.data(), T.width, T.height, (T.flags & 1u) != 0u, m.uvs.empty() ? zero_uv : &m.uvs[(size_t)t * 6], mean);
+                    inten = emi_intensity(&mat[8], mean, E);
+                }
+                B.emi_q[(size_t)insts[ii].tri_base + t] = (half_round(E[0]) + half_round(E[1]) + half_round(E[2])) / 3.0f;
+            }
+            if (m0 != m1 || m0 != m2) continue;                      // :2153-2156
             if (!(mat[8] + mat[9] + mat[10] > 0.0f)) continue;       // :2162
             Tmp L;
             L.p0 = vpos(m, m.idx[t * 3]); L.p1 = vpos(m, m.idx[t * 3 + 1]); L.p2 = vpos(m, m.idx[t * 3 + 2]);
             float area = 0.5f * length(cross(L.p1 - L.p0, L.p2 - L.p0));   // ComputeTriangleWeight :2217-2233
-            float inten = (mat[8] + mat[9] + mat[10]) / 3.0f;
-            L.w = area * inten; L.order = (uint32_t)tmp.size(); L.inst = (uint32_t)ii;
+            L.w = area * inten; L.w_plain = area * inten_plain; L.order = (uint32_t)tmp.size(); L.inst = (uint32_t)ii;
+            L.prim = insts[ii].tri_base + t; L.tex = tex;
             L.em[0] = mat[8]; L.em[1] = mat[9]; L.em[2] = mat[10];
             tmp.push_back(L);
         }
     }
-    // :2187-2190 sorts descending by weight with std::sort (unstable); ties are broken here by collection order
-    std::sort(tmp.begin(), tmp.end(), [](const Tmp& a, const Tmp& b) { return a.w > b.w || (a.w == b.w && a.order < b.order); });
-    float total = 0.0f;
-    for (auto& L : tmp) total += L.w;
-    B.total_weight = total;
-    B.lights.resize(tmp.size()); B.lights80.assign(tmp.size() * 20, 0.0f);
-    float cum = 0.0f;
-    const uint32_t nl = (uint32_t)tmp.size();
-    for (size_t i = 0; i < tmp.size(); i++) {
-        Tmp& L = tmp[i];
-        float wn = L.w / total; cum += wn;
-        float cdf = (i + 1 == tmp.size()) ? 1.0f : cum;             // :2208-2210
-        float* r = &B.lights80[i * 20];
-        r[0] = L.p0.x; r[1] = L.p0.y; r[2] = L.p0.z; r[3] = cdf;
-        r[4] = L.p1.x; r[5] = L.p1.y; r[6] = L.p1.z; memcpy(&r[7], &L.inst, 4);
-        r[8] = L.p2.x; r[9] = L.p2.y; r[10] = L.p2.z; r[11] = wn;
-        r[12] = L.em[0]; r[13] = L.em[1]; r[14] = L.em[2]; memcpy(&r[15], &nl, 4);
-        r[16] = total;
+    // sorted descending by weight, the running CDF, the 80-byte records.  black: the list of an active emission map whose total weight is 0 gets wn = 0
+    auto fill = [&](std::vector<float>& rec80, float& total_out, bool black_ok) {
+        // :2187-2190 sorts descending by weight with std::sort (unstable); ties are broken here by collection order
+        std::sort(tmp.begin(), tmp.end(), [](const Tmp& a, const Tmp& b) { return a.w > b.w || (a.w == b.w && a.order < b.order); });
+        float total = 0.0f;
+        for (auto& L : tmp) total += L.w;
+        total_out = total;
+        rec80.assign(tmp.size() * 20, 0.0f);
+        float cum = 0.0f;
+        const uint32_t nl = (uint32_t)tmp.size();
+        for (size_t i = 0; i < tmp.size(); i++) {
+            Tmp& L = tmp[i];
+            float wn = (black_ok && !(total > 0.0f)) ? 0.0f : L.w / total; cum += wn;     // (emission maps, total == 0: every map black, no emitter has weight — the renderer then gets no light list)
+            float cdf = (i + 1 == tmp.size()) ? 1.0f : cum;             // :2208-2210
+            float* r = &rec80[i * 20];
+            r[0] = L.p0.x; r[1] = L.p0.y; r[2] = L.p0.z; r[3] = cdf;
+            r[4] = L.p1.x; r[5] = L.p1.y; r[6] = L.p1.z; memcpy(&r[7], &L.inst, 4);
+            r[8] = L.p2.x; r[9] = L.p2.y; r[10] = L.p2.z; r[11] = wn;
+            r[12] = L.em[0]; r[13] = L.em[1]; r[14] = L.em[2]; memcpy(&r[15], &nl, 4);
+            r[16] = total;
+        }
+    };
+    // rtx_render_v6_pass1 and rtx_render_restir ignore the emission maps: while one is active they keep the list of the unmapped scene (area x mean(Ke)), built first
+    B.lights80_plain.clear(); B.total_weight_plain = 0.0f;
+    if (emi) {
+        for (Tmp& L : tmp) std::swap(L.w, L.w_plain);
+        fill(B.lights80_plain, B.total_weight_plain, false);
+        for (Tmp& L : tmp) std::swap(L.w, L.w_plain);
     }
+    fill(B.lights80, B.total_weight, emi);
+    if (emi) for (const Tmp& L : tmp) { B.light_emi.push_back(L.prim); B.light_emi.push_back((uint32_t)L.tex); }
     refresh_lights(B);
+}
+// one device record from its 80-byte record: the corners through the instance's matrix, the light normal, the clamped area pdf
+static void light_record(const SceneHost& H, const float* r, LightGPU& G) {
+    uint32_t inst; memcpy(&inst, &r[7], 4);
+    const f3 p0 = mk3(r[0], r[1], r[2]), p1 = mk3(r[4], r[5], r[6]), p2 = mk3(r[8], r[9], r[10]);
+    const float cdf = r[3], wn = r[11];
+    const float* M = H.insts[inst].o2w;
+    f3 xv = xform_point(M, p0), yv = xform_point(M, p1), zv = xform_point(M, p2);
+    f3 cl = cross(yv - xv, zv - xv);
+    f3 nrm = normalize(cl);
+    float area_l = fabsf(length(cl) * 0.5f);
+    G.xv[0] = xv.x; G.xv[1] = xv.y; G.xv[2] = xv.z; G.cdf = cdf;
+    G.yv[0] = yv.x; G.yv[1] = yv.y; G.yv[2] = yv.z; G.pdf_l = maxf_(kEps, wn / maxf_(area_l, kEps));
+    G.zv[0] = zv.x; G.zv[1] = zv.y; G.zv[2] = zv.z; G.prim = 0u;
+    G.em[0] = r[12]; G.em[1] = r[13]; G.em[2] = r[14]; G.emi_tex = 0;
+    G.nl[0] = nrm.x; G.nl[1] = nrm.y; G.nl[2] = nrm.z; G.pad2 = 0.0f;
 }
 // the world-space half of the light records (the sample-independent part of SampleLightNEE_GI, Sampler_v6.hlsl:540-545, 566-575) from the 80-byte records, which hold the
 // object-space corners, the instance, the weight and the CDF: all a TRANSFORM-only commit has to redo (which triangles emit, their weights and their order do not depend on
 // the instance matrices — scanning the 11 M material ids of the street scene for them again was 3 ms of every refit commit)
 void SceneHost::refresh_lights(BuiltScene& B) const {
     B.lights.resize(B.lights80.size() / 20);
+    const bool emi = !B.lights.empty() && B.light_emi.size() == B.lights.size() * 2;      // (emission maps active: the triangle id and the texture; else both words 0, as they always were)
     for (size_t i = 0; i < B.lights.size(); i++) {
-        const float* r = &B.lights80[i * 20];
-        uint32_t inst; memcpy(&inst, &r[7], 4);
-        const f3 p0 = mk3(r[0], r[1], r[2]), p1 = mk3(r[4], r[5], r[6]), p2 = mk3(r[8], r[9], r[10]);
-        const float cdf = r[3], wn = r[11];
-        LightGPU& G = B.lights[i];
-        const float* M = insts[inst].o2w;
-        f3 xv = xform_point(M, p0), yv = xform_point(M, p1), zv = xform_point(M, p2);
-        f3 cl = cross(yv - xv, zv - xv);
-        f3 nrm = normalize(cl);
-        float area_l = fabsf(length(cl) * 0.5f);
-        G.xv[0] = xv.x; G.xv[1] = xv.y; G.xv[2] = xv.z; G.cdf = cdf;
-        G.yv[0] = yv.x; G.yv[1] = yv.y; G.yv[2] = yv.z; G.pdf_l = maxf_(kEps, wn / maxf_(area_l, kEps));
-        G.zv[0] = zv.x; G.zv[1] = zv.y; G.zv[2] = zv.z; G.pad0 = 0.0f;
-        G.em[0] = r[12]; G.em[1] = r[13]; G.em[2] = r[14]; G.pad1 = 0.0f;
-        G.nl[0] = nrm.x; G.nl[1] = nrm.y; G.nl[2] = nrm.z; G.pad2 = 0.0f;
+        light_record(*this, &B.lights80[i * 20], B.lights[i]);
+        if (emi) { B.lights[i].prim = B.light_emi[i * 2]; B.lights[i].emi_tex = (int32_t)B.light_emi[i * 2 + 1]; }
     }
+    B.lights_plain.resize(B.lights80_plain.size() / 20);             // (emission maps active: the unmapped scene's list beside it, for the renderers that ignore the maps)
+    for (size_t i = 0; i < B.lights_plain.size(); i++) light_record(*this, &B.lights80_plain[i * 20], B.lights_plain[i]);
 }
 
 // transform-only commit on the GPU-refit path: the kernels re-derive triangles and boxes; the host re-derives what is small
@@ -340,7 +384,8 @@ bool SceneHost::refresh_transforms(BuiltScene& B) {
     }
     commit_visibility(B);
     // new materials can change WHICH triangles emit, new vertices of an emitting mesh their areas, hence weights and order, a hidden or shown emitter the list itself: full scan
-    if (mats_changed || dirty_mesh_emits() || emitter_flipped) build_lights(B); else refresh_lights(B);
+    // ... and so do new UVs, texels or map ids while an emission map is active, or was at the last commit: the weights follow the texels
+    if (mats_changed || dirty_mesh_emits() || emitter_flipped || (tex_dirty && (B.emi_active || emi_active()))) build_lights(B); else refresh_lights(B);
     B.refit_count++;
     return true;
 }
@@ -496,8 +541,9 @@ bool SceneHost::build(BuiltScene& B) {
     // ... and one with a cut-out triangle (the pre-test path runs no alpha test)
     // ... and one with an active normal map (k_bounce_small perturbs no normal)
     // ... and one with an active specular, roughness or metalness map (k_bounce_small reads the material table alone)
-    B.maps_active = maps_active(); B.cutouts_active = cutouts_active(); B.normals_active = normals_active(); B.spec_active = spec_active(); B.env_active = env.n != 0;
-    if (B.any_hidden || B.maps_active || B.cutouts_active || B.normals_active || B.spec_active || B.env_active) { B.small_recs.clear(); B.small_tris.clear(); B.small_poly.clear(); B.small_slabs.clear(); B.small_excess.clear(); B.small_slab_mask = 0; B.small_nrec = 0; B.small_nocc = 0; }
+    // ... and one with an active emission map (k_bounce_small's emitters and light samples read no texel)
+    B.maps_active = maps_active(); B.cutouts_active = cutouts_active(); B.normals_active = normals_active(); B.spec_active = spec_active(); B.emi_active = emi_active(); B.env_active = env.n != 0;
+    if (B.any_hidden || B.maps_active || B.cutouts_active || B.normals_active || B.spec_active || B.emi_active || B.env_active) { B.small_recs.clear(); B.small_tris.clear(); B.small_poly.clear(); B.small_slabs.clear(); B.small_excess.clear(); B.small_slab_mask = 0; B.small_nrec = 0; B.small_nocc = 0; }
     else build_small_scene(B, wtri, scale);
     sw.lap("tris8 / small scene");
     B.any_order = probe_anyhit_order(B);

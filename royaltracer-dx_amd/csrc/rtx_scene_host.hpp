@@ -55,6 +55,11 @@ struct BuiltScene {
     bool normals_active = false;        // SceneHost::normals_active() AS COMMITTED: a tiny scene then runs on the general path, DevScene::tri_tan / map_nrm (and tri_uv / map_kd) are set
     bool spec_active = false;           // SceneHost::spec_active() AS COMMITTED: a tiny scene then runs on the general path, DevScene::map_ks / map_pr / map_pm (and tri_uv / map_kd) are set
     bool env_active = false;            // an environment is bound (SceneHost::env.n != 0) AS COMMITTED: a tiny scene then runs on the general path
+    // emission maps (include/rtx.h, EMISSION MAPS; rtx_emimap_host.hpp)
+    bool emi_active = false;            // SceneHost::emi_active() AS COMMITTED: a tiny scene then runs on the general path, DevScene::map_ke / emi_q (and tri_uv / map_kd) are set
+    std::vector<float> emi_q;           // build_lights while an emission map is active: q per GLOBAL triangle id (what the emissive hit's MIS pdf reads); else empty
+    std::vector<uint32_t> light_emi;    // ... and per light of `lights`, in its order: global triangle id, emission texture id bits (0xFFFFFFFF = none); else empty
+    std::vector<LightGPU> lights_plain; std::vector<float> lights80_plain; float total_weight_plain = 0.0f;      // ... and the list of the UNMAPPED scene, which rtx_render_v6_pass1 and rtx_render_restir keep sampling; else empty
     std::vector<uint32_t> inst_moved;   // refresh_transforms: 1 = the instance's objectToWorld differs from the last commit's, or its mesh's vertices do, or its visibility does (the GPU refit touches the triangles and nodes of these only)
 };
 
@@ -74,6 +79,7 @@ struct SceneHost {
     std::vector<int32_t> map_opacity;           // ... of RTX_MAP_OPACITY (alpha cut-outs), likewise
     std::vector<int32_t> map_normal;            // ... of RTX_MAP_NORMAL (tangent-space normal maps), likewise
     std::vector<int32_t> map_spec[3];           // ... of RTX_MAP_KS, RTX_MAP_PR, RTX_MAP_PM (specular, roughness and metalness maps), likewise
+    std::vector<int32_t> map_ke;                // ... of RTX_MAP_KE (emission maps), likewise
     std::vector<float> ess_table; uint32_t ess_rows = 0;        // rtx_set_ess_table: rows x 16 floats, or empty / 0 (a table edit like the maps: tex_dirty; rtx_set_materials keeps it)
     bool tex_dirty = false;                     // one of the four setters (UVs, texture, material map, energy table) since the last commit
     // environment lighting (include/rtx.h: rtx_set_environment; rtx_env_host.hpp)
@@ -102,7 +108,11 @@ struct SceneHost {
     bool any_opacity_map() const { for (int32_t t : map_opacity) if (t >= 0) return true; return false; }
     bool any_normal_map() const { for (int32_t t : map_normal) if (t >= 0) return true; return false; }
     bool any_spec_map() const { for (const std::vector<int32_t>& v : map_spec) for (int32_t t : v) if (t >= 0) return true; return false; }
-    bool any_map() const { for (int32_t t : map_kd) if (t >= 0) return true; return any_opacity_map() || any_normal_map() || any_spec_map(); }
+    bool any_emi_map() const { for (int32_t t : map_ke) if (t >= 0) return true; return false; }
+    bool any_map() const { for (int32_t t : map_kd) if (t >= 0) return true; return any_opacity_map() || any_normal_map() || any_spec_map() || any_emi_map(); }
+    // the emission texture of a triangle whose material (the id of its first index entry) is `mat`, or -1: the material has RTX_MAP_KE and emits
+    int32_t emi_texture(uint32_t mat) const { return mat < map_ke.size() && map_ke[mat] >= 0 && mat < mats128.size() / 32 && material_emits(mat) ? map_ke[mat] : -1; }
+    bool emi_active() const;                    // an emitting material that some triangle uses has an emission map
     bool set_ess_table(const float* table, uint32_t rows);
     bool spec_active() const;                   // a non-emitting material that some triangle uses has a specular, roughness or metalness map
     bool maps_active() const;                   // a material that some triangle uses has a diffuse map

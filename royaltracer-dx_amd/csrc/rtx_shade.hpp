@@ -2,6 +2,7 @@
 #pragma once
 #include "rtx_traverse.hpp"
 #include "rtx_texture.hpp"
+#include "rtx_emimap.hpp"
 #include "rtx_env.hpp"
 
 namespace rtx {
@@ -114,8 +115,9 @@ __device__ __forceinline__ PathState load_path(const DevPaths& p, uint32_t pid) 
 
 // hit on an emissive surface: Hit.hlsl:126-174 with the v6 pdf conventions (Sampler_v6.hlsl:459-465)
 // fresh: the path's radiance slot has not been written yet (bounce 0 of the fused path): start from zero instead of loading it
-__device__ __forceinline__ void add_emissive(const DevScene& sc, const DevPaths& p, const PathState& S, const Surf& sf, const MatGPU& m, uint32_t bounce, uint32_t nee, bool fresh = false) {
-    const f3 Ke = mk3(m.Ke[0], m.Ke[1], m.Ke[2]);
+// eh: Ke' and q of THIS hit under EMISSION MAPS (k_shade<.., EMI>: emi_hit, rtx_emimap.hpp); nullptr = the material's Ke and its mean (the choice is a constant after inlining)
+__device__ __forceinline__ void add_emissive(const DevScene& sc, const DevPaths& p, const PathState& S, const Surf& sf, const MatGPU& m, uint32_t bounce, uint32_t nee, bool fresh = false, const EmiHit* eh = nullptr) {
+    const f3 Ke = eh ? eh->Ke : mk3(m.Ke[0], m.Ke[1], m.Ke[2]);
     F4 radv = {0.0f, 0.0f, 0.0f, 0.0f};
     if (!fresh) radv = p.rad[S.pid];
     if (bounce == 0) { radv.x = radv.x + Ke.x; radv.y = radv.y + Ke.y; radv.z = radv.z + Ke.z; }   // Hit.hlsl:128-131
@@ -125,7 +127,8 @@ __device__ __forceinline__ void add_emissive(const DevScene& sc, const DevPaths&
             const f3 Lv = sf.pos - S.o;
             const float dist = length(Lv), dist2 = dist * dist;
             const float cos_t = fabsf(dot(sf.normal, -S.d));
-            const float pdf_light = (((Ke.x + Ke.y + Ke.z) / 3.0f) / sc.total_weight) * dist2 / maxf_(cos_t, kEps);
+            const float qe = eh ? eh->q : (Ke.x + Ke.y + Ke.z) / 3.0f;
+            const float pdf_light = (qe / sc.total_weight) * dist2 / maxf_(cos_t, kEps);
             mi = S.prev_pdf / ((float)nee * pdf_light + S.prev_pdf);
             if (S.prev_pdf < 0.0f) mi = 1.0f;                 // the ray came through a transmission lobe (sign of the stored pdf): NEE never samples through an interface
         }
@@ -148,8 +151,9 @@ __device__ __forceinline__ void add_visible(const DevPaths& p, const F4* __restr
 // mv: the view terms of the shading point (mix_view), shared with the continuation's mixture by k_shade; nullptr = computed here
 // kdpi (here and in bsdf_continue): Kd' / PI of the shading point under a texture map (bsdf_mixture); nullptr = the material's
 // sp (here, in env_nee_sample and in bsdf_continue): Ks', Pr', Pm' of the shading point under SPECULAR MAPS (rtx_bsdf.hpp: SpecView); nullptr = the material's
+// emi: EMISSION MAPS are active (k_shade<.., EMI>): the light's emission is multiplied by the texel at the sampled point (emi_light_em); false = the record's em, as ever
 __device__ __forceinline__ bool nee_sample(const DevScene& sc, const MatGPU& m, uint32_t flags, uint32_t nee, PathState& S, f3 pos, f3 normal, f3 outgoing,
-                                           F4& so, F4& sd, f3& con, bool near_hull = false, float eta_p = 0.0f, const MixView* mv = nullptr, const float* lds_cdf = nullptr, const LightGPU* lds_lights = nullptr, const f3* kdpi = nullptr, const SpecView* spec = nullptr) {
+                                           F4& so, F4& sd, f3& con, bool near_hull = false, float eta_p = 0.0f, const MixView* mv = nullptr, const float* lds_cdf = nullptr, const LightGPU* lds_lights = nullptr, const f3* kdpi = nullptr, const SpecView* spec = nullptr, bool emi = false) {
     const float rv = tea_next(S.s0, S.s1);
     int left = 0, right = (int)sc.nlights - 1, sel = 0;
 #ifndef RTX_NO_LDS_CDF
@@ -189,7 +193,8 @@ __device__ __forceinline__ bool nee_sample(const DevScene& sc, const MatGPU& m, 
     else bsdf_mixture(m, flags, normal, Ln, outgoing, F, P, pd, ps, eta_p, kdpi, spec);     // (Ln is on the reflection side: cos_x >= EPS; eta_p only rescales p_d)
     const float mi = pdf_light / ((float)nee * pdf_light + P);   // Path_Sampler_v6.hlsl:164
     const float g = cos_x / pdf_light * mi;
-    con = mk3(lt.em[0] * (S.thr.x * F.x) * g, lt.em[1] * (S.thr.y * F.y) * g, lt.em[2] * (S.thr.z * F.z) * g);
+    const f3 em = emi ? emi_light_em(sc, lt, u, v, w) : mk3(lt.em[0], lt.em[1], lt.em[2]);
+    con = mk3(em.x * (S.thr.x * F.x) * g, em.y * (S.thr.y * F.y) * g, em.z * (S.thr.z * F.z) * g);
     if (!finite3(con) || is_zero3(con)) return false;
     const f3 sorg = madd3(normalize(normal), kSBias, pos);    // :616-621
     so = {sorg.x, sorg.y, sorg.z, near_hull ? -0.5f * kSBias : 0.5f * kSBias};     // tmin; its sign carries the hull-guard flag of the tiny-scene path

@@ -67,11 +67,13 @@ struct alignas(16) InstGPU { float o2w[16]; float nrm[16]; float o2w_inv[16]; fl
 
 // LightTriangle (Renderer.h:113-124) with the sample-independent part of SampleLightNEE_GI
 // (Sampler_v6.hlsl:540-575) hoisted to the host: world-space vertices, light normal, clamped area pdf.
+// EMISSION MAPS (include/rtx.h): two of the three pad words carry the light's global triangle id and the emission texture of its material; both are 0 unless an emission
+// map is active (BuiltScene::emi_active), and only nee_sample's emi path reads them.
 struct alignas(16) LightGPU {
     float xv[3]; float cdf;
     float yv[3]; float pdf_l;      // max(EPS, weight / max(area, EPS))
-    float zv[3]; float pad0;
-    float em[3]; float pad1;
+    float zv[3]; uint32_t prim;    // emission maps: global triangle id (its corner UVs are DevScene::tri_uv[prim]); else 0
+    float em[3]; int32_t emi_tex;  // emission maps: the material's RTX_MAP_KE texture, or -1; 0 while no emission map is active
     float nl[3]; float pad2;       // normalize(cross(y - x, z - x)), before the per-sample flip
 };
 static_assert(sizeof(LightGPU) == 80, "LightGPU must be 80 bytes");

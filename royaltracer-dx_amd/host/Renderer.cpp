@@ -31,7 +31,7 @@ void Renderer::Check(int rc, const char* what) {
 void Renderer::OnInit() {
     if (!m_haveScene) {
         if (m_models.empty()) throw std::logic_error("Renderer::OnInit: no models (SetModels) and no scene (SetScene)");
-        m_scene = LoadObjScene(m_models, m_mtlDir, m_loadTextures, m_cutouts, m_normals, m_specMaps);                                 // CreateVB per model, Renderer.cpp:363-370
+        m_scene = LoadObjScene(m_models, m_mtlDir, m_loadTextures, m_cutouts, m_normals, m_specMaps, m_emissionMaps);                                 // CreateVB per model, Renderer.cpp:363-370
         m_haveScene = true;
     }
     CameraManip.setWindowSize((int)m_width, (int)m_height);                         // Renderer.cpp:45

@@ -17,6 +17,7 @@ public:
     void SetCutouts(SceneCutouts c) { m_cutouts = c; }          // which opacity maps SetModels' OBJ files load (rtx_render --no-cutouts / --kd-alpha); the default is their map_d images
     void SetNormalMaps(SceneNormalMode mode, float strength = 1.0f, bool flipY = false) { m_normals.mode = mode; m_normals.strength = strength; m_normals.flipY = flipY; }      // which normal maps SetModels' OBJ files load (rtx_render --no-normal-maps / --bump-as-normal / --bump-height / --normal-flip-y); the default is their norm images
     void SetSpecMaps(bool on) { m_specMaps = on; }              // false: SetModels' OBJ files bind no map_Ks / map_Pr / map_Pm image (rtx_render --no-spec-maps)
+    void SetEmissionMaps(bool on) { m_emissionMaps = on; }      // false: SetModels' OBJ files bind no map_Ke image (rtx_render --no-emission-maps)
     void SetLoadTextures(bool on) { m_loadTextures = on; }      // false: SetModels' OBJ files load without their map_Kd images (rtx_render --no-textures)
     void SetDevice(int ordinal) { m_device = ordinal; }
     rtx_params& Params() { return m_params; }
@@ -73,7 +74,7 @@ private:
     void Check(int rc, const char* what);
     UINT m_width, m_height; float m_aspectRatio; std::string m_title;
     std::vector<std::string> m_models; std::string m_mtlDir;
-    Scene m_scene; bool m_haveScene = false, m_loadTextures = true; SceneCutouts m_cutouts = kCutoutsMapD; SceneNormals m_normals; bool m_specMaps = true;
+    Scene m_scene; bool m_haveScene = false, m_loadTextures = true; SceneCutouts m_cutouts = kCutoutsMapD; SceneNormals m_normals; bool m_specMaps = true, m_emissionMaps = true;
     int m_device = 0;
     rtx_ctx* m_ctx = nullptr;
     rtx_params m_params{}, m_restir{};

@@ -3,6 +3,7 @@
 #include "ImageIO.h"
 #include "../csrc/rtx_normalmap_host.hpp"
 #include "../csrc/rtx_specmap_host.hpp"
+#include "../csrc/rtx_emimap_host.hpp"
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -544,7 +545,7 @@ Scene MakeBistroClass(uint32_t target, uint32_t seed, bool hard) {
 }
 
 // the reference's startup scene (Renderer.cpp:363-407, 444-449, 46-48)
-Scene LoadObjScene(const std::vector<std::string>& files, const std::string& mtl_dir, bool load_textures, SceneCutouts cutouts, SceneNormals normals, bool spec_maps) {
+Scene LoadObjScene(const std::vector<std::string>& files, const std::string& mtl_dir, bool load_textures, SceneCutouts cutouts, SceneNormals normals, bool spec_maps, bool emission_maps) {
     Scene s; s.name = "obj";
     UINT materialIDOffset = 0, materialVertexOffset = 0;       // Renderer members of the same name
     size_t total_ids = 0;
@@ -596,6 +597,15 @@ Scene LoadObjScene(const std::vector<std::string>& files, const std::string& mtl
             if (bound(x.map[MAP_PM], "map_Pm")) { s.pmMaps[m] = x.map[MAP_PM]; rtx::spec_unit_scalar(&mat.Pr_Pm_Ps_Pc.y); }
         }
     }
+    if (load_textures && emission_maps) {
+        s.keMaps.assign(s.materialExt.size(), -1);
+        for (size_t m = 0; m < s.materialExt.size() && m < s.materials.size(); m++) {
+            const int t = s.materialExt[m].map[MAP_KE];
+            load(t, "map_Ke");
+            // the unit-Ke rule: a bound map multiplies Ke, and (0, 0, 0) is what the parser leaves for a Ke the file does not give
+            if (t >= 0 && (size_t)t < s.images.size() && s.images[t].width != 0u) { s.keMaps[m] = t; rtx::emi_unit_ke(&s.materials[m].Ke.x); }
+        }
+    }
     if (load_textures && normals.mode != kNormalsOff) {
         s.normalMaps.assign(s.materialExt.size(), -1);
         const size_t nfile = s.textures.size();                // (copies are appended behind the files' entries, which keep their ids)
@@ -603,7 +613,7 @@ Scene LoadObjScene(const std::vector<std::string>& files, const std::string& mtl
         for (size_t m = 0; m < s.materialExt.size(); m++) {
             const int kd = s.materialExt[m].map[MAP_KD]; if (kd >= 0 && (size_t)kd < nfile) other[kd] = 1;
             const int op = m < s.opacityMaps.size() ? s.opacityMaps[m] : -1; if (op >= 0 && (size_t)op < nfile) other[op] = 1;
-            for (const std::vector<int>* sm : {&s.ksMaps, &s.prMaps, &s.pmMaps}) { const int t = m < sm->size() ? (*sm)[m] : -1; if (t >= 0 && (size_t)t < nfile) other[t] = 1; }
+            for (const std::vector<int>* sm : {&s.ksMaps, &s.prMaps, &s.pmMaps, &s.keMaps}) { const int t = m < sm->size() ? (*sm)[m] : -1; if (t >= 0 && (size_t)t < nfile) other[t] = 1; }
         }
         std::vector<int> as_normal(nfile, -1), as_height(nfile, -1);      // file image -> the entry that holds it as a normal map / converted from a height map
         for (size_t m = 0; m < s.materialExt.size(); m++) {
@@ -688,6 +698,10 @@ int BindSceneMaps(const Scene& s, rtx_ctx* ctx) {
     for (size_t m = 0; m < s.normalMaps.size() && m < s.materials.size(); m++) {
         const int t = s.normalMaps[m];
         if (t >= 0 && (size_t)t < id.size() && id[t] >= 0 && (r = rtx_set_material_map(ctx, (uint32_t)m, RTX_MAP_NORMAL, id[t]))) return r;
+    }
+    for (size_t m = 0; m < s.keMaps.size() && m < s.materials.size(); m++) {
+        const int t = s.keMaps[m];
+        if (t >= 0 && (size_t)t < id.size() && id[t] >= 0 && (r = rtx_set_material_map(ctx, (uint32_t)m, RTX_MAP_KE, id[t]))) return r;
     }
     bool pr_bound = false;
     const std::vector<int>* spec[3] = {&s.ksMaps, &s.prMaps, &s.pmMaps}; const uint32_t slot[3] = {RTX_MAP_KS, RTX_MAP_PR, RTX_MAP_PM};

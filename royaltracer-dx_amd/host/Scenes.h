@@ -32,6 +32,7 @@ struct Scene {
                                              // taken as a normal map or converted from a height map on load), or -1; empty = none
     std::vector<int> ksMaps, prMaps, pmMaps; // per material: the entry of `textures` bound as its specular / roughness / metalness map (RTX_MAP_KS / RTX_MAP_PR / RTX_MAP_PM: its
                                              // map_Ks / map_Pr / map_Pm image; one packed file may serve several slots), or -1; empty = none
+    std::vector<int> keMaps;                 // per material: the entry of `textures` bound as its emission map (RTX_MAP_KE: its map_Ke image), or -1; empty = none
     std::vector<SceneModel> models;
     std::vector<SceneInstance> instances;
     XMFLOAT3 eye{0, 0, 1}, center{0, 0, 0}, up{0, 1, 0};
@@ -63,7 +64,9 @@ struct SceneNormals { SceneNormalMode mode = kNormalsNorm; float strength = 1.0f
 // the parser records a scalar the file does not give as 0, which would switch the map off: so binding a decoded map_Pr sets Pr == 0 to 1 (and regenerates the material's LUT),
 // map_Pm likewise Pm, map_Ks a Ks of (0, 0, 0) to (1, 1, 1) (csrc/rtx_specmap_host.hpp) — a stated deviation from the reference's record, made only where a map is bound.
 // false = none bound, the records as parsed
-Scene LoadObjScene(const std::vector<std::string>& files, const std::string& mtl_dir, bool load_textures = true, SceneCutouts cutouts = kCutoutsMapD, SceneNormals normals = SceneNormals(), bool spec_maps = true);
+// emission_maps (ignored without load_textures): bind the image a map_Ke statement names (include/rtx.h, EMISSION MAPS); binding a decoded one sets a Ke of (0, 0, 0) to (1, 1, 1)
+// (csrc/rtx_emimap_host.hpp), the same stated deviation, made only where a map is bound.  false = none bound, the records as parsed
+Scene LoadObjScene(const std::vector<std::string>& files, const std::string& mtl_dir, bool load_textures = true, SceneCutouts cutouts = kCutoutsMapD, SceneNormals normals = SceneNormals(), bool spec_maps = true, bool emission_maps = true);
 // rtx_set_mesh_uvs / rtx_set_texture / rtx_set_material_map (every slot a kernel samples) for what the scene carries, and — where a roughness map was bound — rtx_set_ess_table with
 // 17 rows of GenerateEssLUT.  It only ADDS: slots and an energy table that an earlier scene left on the same context are not cleared (rtx_set_materials resets the slots; a
 // table without a roughness map is read by nothing; rtx_set_ess_table(ctx, NULL, 0) clears it); a scene without a decoded image binds nothing.  Before rtx_commit_scene

@@ -80,14 +80,14 @@ rtxh_scene* rtxh_scene_from_obj_ex(const char* const* files, uint32_t n, const c
     std::string dir = mtl_dir ? mtl_dir : "./";
     const SceneCutouts cut = (flags & RTXH_OBJ_NO_CUTOUTS) ? kCutoutsOff : (flags & RTXH_OBJ_KD_ALPHA) ? kCutoutsKdAlpha : kCutoutsMapD;
     SceneNormals nm; nm.mode = (flags & RTXH_OBJ_NO_NORMAL_MAPS) ? kNormalsOff : (flags & RTXH_OBJ_BUMP_AS_NORMAL) ? kNormalsBumpAsNormal : kNormalsNorm; nm.flipY = (flags & RTXH_OBJ_NORMAL_FLIP_Y) != 0;
-    return guarded([&] { return LoadObjScene(f, dir, !(flags & RTXH_OBJ_NO_TEXTURES), cut, nm, !(flags & RTXH_OBJ_NO_SPEC_MAPS)); });
+    return guarded([&] { return LoadObjScene(f, dir, !(flags & RTXH_OBJ_NO_TEXTURES), cut, nm, !(flags & RTXH_OBJ_NO_SPEC_MAPS), !(flags & RTXH_OBJ_NO_EMISSION_MAPS)); });
 }
 rtxh_scene* rtxh_scene_from_obj_ex2(const char* const* files, uint32_t n, const char* mtl_dir, uint32_t flags, float bump_height) {
     std::vector<std::string> f; for (uint32_t i = 0; i < n; i++) f.emplace_back(files[i]);
     std::string dir = mtl_dir ? mtl_dir : "./";
     const SceneCutouts cut = (flags & RTXH_OBJ_NO_CUTOUTS) ? kCutoutsOff : (flags & RTXH_OBJ_KD_ALPHA) ? kCutoutsKdAlpha : kCutoutsMapD;
     SceneNormals nm; nm.mode = (flags & RTXH_OBJ_NO_NORMAL_MAPS) ? kNormalsOff : kNormalsBumpHeight; nm.strength = bump_height; nm.flipY = (flags & RTXH_OBJ_NORMAL_FLIP_Y) != 0;
-    return guarded([&] { return LoadObjScene(f, dir, !(flags & RTXH_OBJ_NO_TEXTURES), cut, nm, !(flags & RTXH_OBJ_NO_SPEC_MAPS)); });
+    return guarded([&] { return LoadObjScene(f, dir, !(flags & RTXH_OBJ_NO_TEXTURES), cut, nm, !(flags & RTXH_OBJ_NO_SPEC_MAPS), !(flags & RTXH_OBJ_NO_EMISSION_MAPS)); });
 }
 void rtxh_scene_free(rtxh_scene* s) { delete s; }
 const char* rtxh_last_error(void) { return g_err.c_str(); }
@@ -115,6 +115,7 @@ int rtxh_scene_spec_map(const rtxh_scene* s, uint32_t material, uint32_t slot) {
     const std::vector<int>* v = slot == RTX_MAP_KS ? &s->s.ksMaps : slot == RTX_MAP_PR ? &s->s.prMaps : slot == RTX_MAP_PM ? &s->s.pmMaps : nullptr;
     return v && material < v->size() ? (*v)[material] : -1;
 }
+int rtxh_scene_emission_map(const rtxh_scene* s, uint32_t material) { return material < s->s.keMaps.size() ? s->s.keMaps[material] : -1; }
 int rtxh_scene_normal_map(const rtxh_scene* s, uint32_t material) { return material < s->s.normalMaps.size() ? s->s.normalMaps[material] : -1; }
 int rtxh_scene_opacity_map(const rtxh_scene* s, uint32_t material) { return material < s->s.opacityMaps.size() ? s->s.opacityMaps[material] : -1; }
 int rtxh_scene_mesh_uvs(const rtxh_scene* s, uint32_t i, const float** uv2, uint32_t* nidx) {

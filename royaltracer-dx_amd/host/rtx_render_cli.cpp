@@ -28,6 +28,7 @@
 //                   [--bump-as-normal] a material without a norm takes its map_Bump / bump image as a normal map   [--bump-height S] ... as a height map (channel 0), converted on load with strength S
 //                   [--normal-flip-y] DirectX-style normal maps (green = -bitangent): negate the green byte on load
 //                   [--no-spec-maps]  OBJ scenes: do not bind the images their map_Ks / map_Pr / map_Pm statements name: one Ks, Pr and Pm per material, the records as parsed
+//                   [--no-emission-maps] OBJ scenes: do not bind the image a map_Ke statement names: one Ke per material, the records as parsed
 //                   [--env FILE [--env-res N] [--env-yaw DEG] [--env-scale S] [--env-hidden]]   environment lighting (rtx_set_environment): FILE is a latitude-longitude Radiance .hdr or
 //                   colour .pfm, resampled to an N x N octahedral map (default 512), turned by DEG degrees about +Y, radiance times S; --env-hidden: camera rays that miss stay black
 //                   [--sky R,G,B]   a constant sky of that radiance instead of a file; both work with --gpus N (every rank binds the same map) and are ignored by --mode restir
@@ -62,6 +63,7 @@ static const char* kUsage =
     "                  [--no-normal-maps] OBJ scenes: ignore norm images (--no-textures implies it)   [--bump-as-normal | --bump-height S]   map_Bump / bump as a normal map / a height map of strength S\n"
     "                  [--normal-flip-y]  DirectX-style normal maps: negate green on load\n"
     "                  [--no-spec-maps]   OBJ scenes: ignore map_Ks / map_Pr / map_Pm images (--no-textures implies it)\n"
+    "                  [--no-emission-maps] OBJ scenes: ignore map_Ke images (--no-textures implies it)\n"
     "                  [--env FILE [--env-res N] [--env-yaw DEG] [--env-scale S] [--env-hidden]] [--sky R,G,B]   environment lighting\n"
     "                  [--aperture R [--focus D | --focus-pixel X,Y]]   thin-lens camera: depth of field (path tracer)\n"
     "                  [--gpus N [--devices 0,1,..] [--gather rccl|copy]]\n";
@@ -73,7 +75,7 @@ int main(int argc, char** argv) {
     std::vector<UINT> hide; int blink = -1;
     bool adaptive = false; rtx_adaptive ad{}; ad.min_spp = 8; ad.step_spp = 8;
     bool denoise = false; rtx_denoise_params dnp{};
-    bool textures = true; SceneCutouts cutouts = kCutoutsMapD; bool kd_alpha = false; SceneNormals normals; bool no_normals = false, spec_maps = true;
+    bool textures = true; SceneCutouts cutouts = kCutoutsMapD; bool kd_alpha = false; SceneNormals normals; bool no_normals = false, spec_maps = true, emission_maps = true;
     float aperture = 0.0f, focus = 0.0f; bool focus_set = false; std::string focus_pixel;
     std::string env_file, sky; UINT env_res = 512; float env_yaw = 0.0f, env_scale = 1.0f; bool env_hidden = false;
     for (int i = 1; i < argc; i++) {
@@ -87,6 +89,7 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--help") || !strcmp(argv[i], "-h")) { fputs(kUsage, stdout); return 0; }
         else if (!strcmp(argv[i], "--no-textures")) textures = false; else if (!strcmp(argv[i], "--no-cutouts")) cutouts = kCutoutsOff; else if (!strcmp(argv[i], "--kd-alpha")) kd_alpha = true;
         else if (!strcmp(argv[i], "--no-spec-maps")) spec_maps = false;
+        else if (!strcmp(argv[i], "--no-emission-maps")) emission_maps = false;
         else if (!strcmp(argv[i], "--no-normal-maps")) no_normals = true; else if (!strcmp(argv[i], "--normal-flip-y")) normals.flipY = true;
         else if (!strcmp(argv[i], "--bump-as-normal")) normals.mode = kNormalsBumpAsNormal; else if (arg("--bump-height")) { normals.strength = (float)atof(argv[++i]); normals.mode = kNormalsBumpHeight; }
         else if (arg("--env")) env_file = argv[++i]; else if (arg("--env-res")) env_res = (UINT)atoi(argv[++i]); else if (arg("--env-yaw")) env_yaw = (float)atof(argv[++i]);
@@ -148,7 +151,7 @@ int main(int argc, char** argv) {
             else { std::stringstream ss(devlist); std::string t; while (std::getline(ss, t, ',')) devs.push_back(atoi(t.c_str())); }
             if ((int)devs.size() != gpus) { fprintf(stderr, "--devices must list %d ordinals\n", gpus); return 2; }
             Scene sc = scene == "cornell" ? MakeCornellBox() : scene == "sponza" ? MakeSponzaClass() : scene == "bistro" ? MakeBistroClass() : Scene();
-            if (scene == "obj") { std::vector<std::string> f; std::stringstream ss(objs); std::string t; while (std::getline(ss, t, ',')) f.push_back(t); sc = LoadObjScene(f, mtl, textures, cutouts, normals, spec_maps); }
+            if (scene == "obj") { std::vector<std::string> f; std::stringstream ss(objs); std::string t; while (std::getline(ss, t, ',')) f.push_back(t); sc = LoadObjScene(f, mtl, textures, cutouts, normals, spec_maps, emission_maps); }
             if (scene == "cornell") lambert = true;
             if (env.n) sc.environment = env;
             MultiGpuFrame mg(devs, gather == "copy" ? MultiGpuFrame::Gather::COPY : MultiGpuFrame::Gather::RCCL, force_gather, only_rank);      // --force-gather: the collective also with one rank
@@ -195,7 +198,7 @@ int main(int argc, char** argv) {
         if (scene == "cornell") { r.SetScene(MakeCornellBox()); lambert = true; }
         else if (scene == "sponza") r.SetScene(MakeSponzaClass());
         else if (scene == "bistro") r.SetScene(MakeBistroClass());
-        else { std::vector<std::string> f; std::stringstream ss(objs); std::string t; while (std::getline(ss, t, ',')) f.push_back(t); r.SetLoadTextures(textures); r.SetCutouts(cutouts); r.SetNormalMaps(normals.mode, normals.strength, normals.flipY); r.SetSpecMaps(spec_maps); r.SetModels(f, mtl); }
+        else { std::vector<std::string> f; std::stringstream ss(objs); std::string t; while (std::getline(ss, t, ',')) f.push_back(t); r.SetLoadTextures(textures); r.SetCutouts(cutouts); r.SetNormalMaps(normals.mode, normals.strength, normals.flipY); r.SetSpecMaps(spec_maps); r.SetEmissionMaps(emission_maps); r.SetModels(f, mtl); }
         if (env.n) r.SetEnvironment(env);
         r.Params().spp = spp; r.Params().max_bounces = bounces; r.Params().nee_samples = nee; r.Params().flags = lambert ? RTX_FLAG_LAMBERT_ONLY : (scene == "bistro" ? RTX_FLAG_TRANSMISSION : 0);
         if (restir) {
