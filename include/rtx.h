@@ -656,6 +656,46 @@ int  rtx_read_denoised_srgb8(rtx_ctx*, uint8_t* rgba8, size_t bytes);   /* k_srg
 int  rtx_debug_denoise_guides(rtx_ctx*, uint32_t width, uint32_t height, float* out8 /* W*H*8 */);
 /* the MAP GUIDES as the filter reads them under a flag: per pixel A3, 0, nm3, 0 ((1, 1, 1, 0, 0, 0, 0, 0) where the pixel is not filterable by geometry); errors as above */
 int  rtx_debug_denoise_map_guides(rtx_ctx*, uint32_t width, uint32_t height, float* out8 /* W*H*8 */);
+/* DENOISING, VARIANCE-GUIDED (rtx_denoise_variance; rtx_denoise and its struct are unchanged).  The same filter, guides, taps, wn and wp, but the colour stop is scaled by the
+   centre pixel's OWN noise instead of one constant for the image (after Schied et al. 2017, SVGF): rtx_render_adaptive keeps `half`, the running sum of the odd sample ids, and
+   with u1 that gives an unbiased per-pixel estimate of the variance of the mean.  All arithmetic is float32 in exactly the written order, no contraction, IEEE / and sqrtf;
+   tests/denoise_var_ref.py replays it in numpy and tests/test_denoise_var.py holds the device to it bit for bit.
+   a = u1, hb = `half`.  Filterable, the taps, h[], wn, wp, A and nm are exactly as in DENOISING and MAP GUIDES above.
+   LEVEL-0 INPUT of a pixel with a.w > 0:
+       cnt = max(a.w, 1);   c.k = a.k / cnt;   e.k = (a.k - (hb.k + hb.k)) / cnt             (k = x, y, z; e = (even sum - odd sum) / N)
+       under RTX_DENOISE_ALBEDO, filterable pixels only:   c.k = c.k / A.k;   e.k = e.k / A.k
+       el = (0.2126f * e.x + 0.7152f * e.y) + 0.0722f * e.z;   v = el * el                    (unbiased for the variance of the mean's luminance when the halves balance)
+   EVERY LEVEL i, step s = 1 << i, for a filterable centre p, reading this level's input (c, v):
+       prefilter: q = p + (dx, dy), dy = -1 .. 1 outer, dx = -1 .. 1 inner, ALWAYS one pixel apart whatever s; g = (1/16, 1/8, 1/16, 1/8, 1/4, 1/8, 1/16, 1/8, 1/16);
+                  a position counts under the taps' rule (inside the image, filterable, mat_q == mat_p):   sg = sg + g * v_q;   sgw = sgw + g      (sequential from 0)
+       gv  = sg / sgw
+       inv = 1.0f / (sigma_var * sqrtf(gv) + 9.5367431640625e-07f)                            (2^-20: part of the definition; it bounds inv where a pixel's halves agree)
+       l_p = (0.2126f * c_p.x + 0.7152f * c_p.y) + 0.0722f * c_p.z;   l_q likewise
+       the 25 taps, same order and counting rule, wn and wp unchanged (nm under RTX_DENOISE_MAPPED_NORMALS):
+           dl = |l_q - l_p|;   wc = max(1 - dl * inv, 0);   w = ((h[dy+2] * h[dx+2]) * wn) * (wp * wc)
+           sum.xyz = sum.xyz + w * c_q.xyz;   sumw = sumw + w;   sumv = sumv + (w * w) * v_q
+       output c = sum.xyz / sumw,   v = sumv / (sumw * sumw)
+   Pass-through pixels behave as in rtx_denoise: their output is their input at every level, and they contribute to no tap and to no prefilter.  Under RTX_DENOISE_ALBEDO the
+   last level multiplies by A.  The last level stores w = 1.0; the filtered variance is not part of the result.  There is no sigma_color: the variance shrinks level by level,
+   which replaces Dammertz's halving.  The result is the denoised image of rtx_denoise (rtx_read_denoised, rtx_read_denoised_srgb8); stream semantics and the result fields are
+   rtx_denoise's.
+   STATE.  The call needs the adaptive state that belongs to u1: every sample since the last clear came from rtx_render_adaptive, the state is laid out for this width and
+   height, and every one of those calls was unsharded (shard_count <= 1; rtx_unpack_tiles counts as sharded: `half` is not gathered).  Anything else is RTX_ERR_STATE, on top
+   of rtx_denoise's own state errors.  A fixed sample count is rtx_render_adaptive with threshold 0, which is rtx_render's image to the bit.  RTX_ERR_INVALID as rtx_denoise:
+   size, levels, power, a sigma that is negative, not finite or whose reciprocal is not finite, unknown flag bits, a nonzero reserved word.  A failed call leaves u1, `half` and
+   the previous denoised image untouched. */
+typedef struct rtx_denoise_var_params {
+    uint32_t levels;              /* 1..8; 0 => 5 */
+    uint32_t normal_power_log2;   /* 1..7; 0 => 5 */
+    float    sigma_var;           /* > 0: standard deviations of the pixel's own noise at which the colour stop reaches zero; 0 => 4 (Schied et al. 2017, sigma_l) */
+    float    sigma_plane;         /* as rtx_denoise_params */
+    uint32_t flags;               /* RTX_DENOISE_ALBEDO | RTX_DENOISE_MAPPED_NORMALS, same meaning; any other bit is RTX_ERR_INVALID */
+    uint32_t reserved[3];         /* 0 */
+} rtx_denoise_var_params;         /* 32 bytes */
+int  rtx_denoise_variance(rtx_ctx*, uint32_t width, uint32_t height, const rtx_denoise_var_params* /* NULL = defaults */, rtx_denoise_result* /* may be NULL */);
+int  rtx_read_adaptive_half(rtx_ctx*, float* rgba32f, size_t bytes);     /* copy of `half` to the host, like rtx_read_accum; RTX_ERR_STATE without the state above */
+/* (v, gv) of level 0 as the filter reads them (flags: RTX_DENOISE_ALBEDO divides by A; the normals do not enter); (0, 0) for a pixel that is not filterable; state as above */
+int  rtx_debug_denoise_variance(rtx_ctx*, uint32_t width, uint32_t height, uint32_t flags, float* out2 /* W*H*2 */);
 /* The reference's OWN first pass, literally: RayGen of RayGen_v6_pass1.hlsl:48-190 (first DispatchRays,
    Renderer.cpp:651-654): primary hit, SampleRIS (Sampler_v6.hlsl:653-736), visibility, SamplePathSimple
    (Path_Sampler_v6.hlsl:3-286).  params: nee_samples = nee_samples_DI = nee_samples (Common_v6.hlsl:8-9, reference 4),

@@ -173,6 +173,10 @@ int  rtxh_renderer_set_mesh_vertices(rtxh_renderer*, uint32_t mesh, const void* 
 int  rtxh_renderer_on_render(rtxh_renderer*);
 int  rtxh_renderer_read_accum(rtxh_renderer*, float* rgba32f, size_t bytes);
 int  rtxh_renderer_read_output(rtxh_renderer*, uint8_t* rgba8, size_t bytes);
+/* Renderer::DenoiseVariance: rtx_denoise_variance on the renderer's context and size (params NULL = defaults; out may be NULL).  The image must have been sampled by
+   rtx_render_adaptive on rtxh_renderer_context() alone since its last clear.  RTX_ERR_STATE before on_init and in mode 1; RTX_ERR_INVALID when the context refuses the call
+   (its message: rtx_last_error(rtxh_renderer_context())) */
+int  rtxh_renderer_denoise_variance(rtxh_renderer*, const rtx_denoise_var_params* params, rtx_denoise_result* out);
 int  rtxh_renderer_on_key_up(rtxh_renderer*, uint8_t key);          /* 'C': next entry of m_displayLevels (Renderer.cpp:748-754); read_output returns that layer */
 uint32_t rtxh_renderer_display_layer(const rtxh_renderer*);
 void rtxh_renderer_destroy(rtxh_renderer*);

@@ -173,6 +173,14 @@ _sig("rtx_read_denoised_srgb8", C.c_int, _vp, _vp, C.c_size_t)
 _sig("rtx_debug_denoise_guides", C.c_int, _vp, _u32, _u32, _vp)
 _sig("rtx_debug_denoise_map_guides", C.c_int, _vp, _u32, _u32, _vp)
 DENOISE_ALBEDO, DENOISE_MAPPED_NORMALS = 1, 2      # rtx_denoise_params.flags, the first of DenoiseParams.reserved's four words
+class DenoiseVarParams(C.Structure):
+    """rtx_denoise_var_params (include/rtx.h); 0 = the default of a field"""
+    _fields_ = [("levels", C.c_uint32), ("normal_power_log2", C.c_uint32), ("sigma_var", C.c_float), ("sigma_plane", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+_sig("rtx_denoise_variance", C.c_int, _vp, _u32, _u32, C.POINTER(DenoiseVarParams), C.POINTER(DenoiseResult))
+_sig("rtx_read_adaptive_half", C.c_int, _vp, _vp, C.c_size_t)
+_sig("rtx_debug_denoise_variance", C.c_int, _vp, _u32, _u32, _u32, _vp)
 _sig("rtx_render_v6_pass1", C.c_int, _vp, C.POINTER(Params))
 _sig("rtx_render_restir", C.c_int, _vp, C.POINTER(Params))
 _sig("rtx_restir_reset", C.c_int, _vp)
@@ -291,6 +299,7 @@ _sig("rtxh_renderer_set_instance_visible", C.c_int, _vp, _u32, C.c_int)
 _sig("rtxh_renderer_on_render", C.c_int, _vp)
 _sig("rtxh_renderer_read_accum", C.c_int, _vp, _vp, C.c_size_t)
 _sig("rtxh_renderer_read_output", C.c_int, _vp, _vp, C.c_size_t)
+_sig("rtxh_renderer_denoise_variance", C.c_int, _vp, C.POINTER(DenoiseVarParams), C.POINTER(DenoiseResult))
 _sig("rtxh_renderer_on_key_up", C.c_int, _vp, C.c_uint8)
 _sig("rtxh_renderer_display_layer", _u32, _vp)
 _sig("rtxh_renderer_destroy", None, _vp)
@@ -919,11 +928,22 @@ class Context:
         self._ck(lib.rtx_read_accum(self._h, _ptr(out), out.nbytes), "rtx_read_accum")
         return out
 
-    def denoise(self, width, height, levels=0, sigma_color=0.0, sigma_plane=0.0, normal_power_log2=0, result=True, albedo=False, mapped_normals=False):
+    def denoise(self, width, height, levels=0, sigma_color=0.0, sigma_plane=0.0, normal_power_log2=0, result=True, albedo=False, mapped_normals=False, variance=False, sigma_var=0.0):
         """rtx_denoise: the edge-avoiding a-trous filter over the mean of u1, guided by first-hit position, normal and material (0 = a field's default) -> DenoiseResult.
         albedo: RTX_DENOISE_ALBEDO, filter the image divided by the first hit's Kd' so that texture detail survives; mapped_normals: RTX_DENOISE_MAPPED_NORMALS, the normal
-        stop compares normal-mapped shading normals.  result=False passes no result struct: on a caller-bound stream the call then only enqueues (no host join) and returns None"""
+        stop compares normal-mapped shading normals.  result=False passes no result struct: on a caller-bound stream the call then only enqueues (no host join) and returns None.
+        variance=True: rtx_denoise_variance — the colour stop is scaled by each pixel's own noise (sigma_var standard deviations, 0 = 4) instead of sigma_color, which must
+        then stay 0; the image must have been sampled by render_adaptive alone (threshold 0 for a fixed sample count)"""
         flags = (DENOISE_ALBEDO if albedo else 0) | (DENOISE_MAPPED_NORMALS if mapped_normals else 0)
+        if variance:
+            if sigma_color:
+                raise ValueError("denoise: sigma_color has no meaning with variance=True (sigma_var scales the colour stop)")
+            vp = DenoiseVarParams(int(levels), int(normal_power_log2), float(sigma_var), float(sigma_plane), flags)
+            res = DenoiseResult() if result else None
+            self._ck(lib.rtx_denoise_variance(self._h, int(width), int(height), C.byref(vp), C.byref(res) if result else None), "rtx_denoise_variance")
+            return res
+        if sigma_var:
+            raise ValueError("denoise: sigma_var needs variance=True")
         dp = DenoiseParams(int(levels), int(normal_power_log2), float(sigma_color), float(sigma_plane), (C.c_uint32 * 4)(flags, 0, 0, 0))
         res = DenoiseResult() if result else None
         self._ck(lib.rtx_denoise(self._h, int(width), int(height), C.byref(dp), C.byref(res) if result else None), "rtx_denoise")
@@ -938,6 +958,18 @@ class Context:
     def read_denoised_srgb8(self):
         out = np.zeros((self.height, self.width, 4), np.uint8)
         self._ck(lib.rtx_read_denoised_srgb8(self._h, _ptr(out), out.nbytes), "rtx_read_denoised_srgb8")
+        return out
+
+    def read_adaptive_half(self):
+        """`half` (H, W, 4) float32: render_adaptive's running sum of the odd sample ids, the second input of denoise(variance=True)"""
+        out = np.zeros((self.height, self.width, 4), np.float32)
+        self._ck(lib.rtx_read_adaptive_half(self._h, _ptr(out), out.nbytes), "rtx_read_adaptive_half")
+        return out
+
+    def denoise_variance_input(self, width, height, albedo=False):
+        """(H, W, 2) float32: level 0's (v, gv) as denoise(variance=True) reads them — the variance of the mean's luminance and its 3 x 3 prefilter; (0, 0) where not filterable"""
+        out = np.zeros((height, width, 2), np.float32)
+        self._ck(lib.rtx_debug_denoise_variance(self._h, int(width), int(height), DENOISE_ALBEDO if albedo else 0, _ptr(out)), "rtx_debug_denoise_variance")
         return out
 
     def denoise_guides(self, width, height):
@@ -1208,6 +1240,16 @@ class Renderer:
             return c.read_denoised()
         finally:
             c._h = None
+
+    def denoise_variance(self, levels=0, sigma_var=0.0, sigma_plane=0.0, normal_power_log2=0, albedo=False, mapped_normals=False):
+        """Renderer::DenoiseVariance: rtx_denoise_variance on the renderer's context, whose image must have been sampled by render_adaptive alone -> DenoiseResult"""
+        flags = (DENOISE_ALBEDO if albedo else 0) | (DENOISE_MAPPED_NORMALS if mapped_normals else 0)
+        vp, res = DenoiseVarParams(int(levels), int(normal_power_log2), float(sigma_var), float(sigma_plane), flags), DenoiseResult()
+        rc = lib.rtxh_renderer_denoise_variance(self._h, C.byref(vp), C.byref(res))
+        if rc != RTX_OK:
+            h = lib.rtxh_renderer_context(self._h)
+            raise RtxError(f"DenoiseVariance failed ({rc}): " + (lib.rtx_last_error(h).decode() if h else "renderer not initialised"))
+        return res
 
     def read_output(self):
         out = np.zeros((self.height, self.width, 4), np.uint8)

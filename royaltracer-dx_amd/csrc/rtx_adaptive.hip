@@ -29,8 +29,9 @@ int rtx_render_adaptive(rtx_ctx* c, const rtx_params* p, const rtx_adaptive* a, 
     const hipStream_t st = c->stream;
     if (c->ad.cleared) {
         HIPCHK(c, hipMemsetAsync(c->ad.d_half.p, 0, npix * 16, st)); HIPCHK(c, hipMemsetAsync(c->ad.d_count.p, 0, nwords * 4, st)); HIPCHK(c, hipMemsetAsync(c->ad.d_flag.p, 0, nwords * 4, st));
-        c->ad.cleared = false; memcpy(c->ad.key, key, sizeof(key));
+        c->ad.cleared = false; memcpy(c->ad.key, key, sizeof(key)); c->ad.whole = true;
     }
+    if (p->shard_count > 1) c->ad.whole = false;                             // (`half` of the other shards' pixels stays zero: rtx_denoise_variance refuses)
     const AdaptState S{(F4*)c->ad.d_half.p, (uint32_t*)c->ad.d_count.p, (uint32_t*)c->ad.d_flag.p};
     uint32_t* list = (uint32_t*)c->ad.d_list.p;
     const float dark_floor = a->dark_floor == 0.0f ? 0.01f : a->dark_floor;

@@ -378,6 +378,7 @@ int rtx_unpack_tiles(rtx_ctx* c, const rtx_params* p, const void* slabs) {
     DevFrame f; int r = make_frame(c, p, f); if (r) return r;
     if (!slabs) return RTX_ERR_INVALID;
     if ((r = ensure_accum(c, p->width, p->height, false))) return r;
+    c->ad.whole = false;                  // u1 gets samples `half` does not hold (gathering `half` is not offered)
     launch_unpack_tiles(c->stream, (uint32_t)c->num_cus * 8u, f, f.shard_count, (const F4*)slabs, c->accum_ptr());
     HIPCHK(c, hipGetLastError());
     if (c->own_stream) HIPCHK(c, hipStreamSynchronize(c->stream));

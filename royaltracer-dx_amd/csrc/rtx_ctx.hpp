@@ -4,7 +4,7 @@
 //   rtx_commit.hip       rtx_commit_scene (host or GPU build, GPU refit), the scene cache, finalise_scene
 //   rtx_render.hip       rtx_render (the wavefront path tracer), render_frame and finish_render
 //   rtx_adaptive.hip     rtx_render_adaptive: passes of render_frame over the chunks that have not converged
-//   rtx_denoise.hip      rtx_denoise and the reads of the denoised image
+//   rtx_denoise.hip      rtx_denoise, rtx_denoise_variance and the reads of the denoised image
 //   rtx_env.hip          environment lighting: rtx_set_environment and its three debug probes
 //   rtx_texture.hip      texture maps: rtx_set_mesh_uvs, rtx_set_texture, rtx_set_material_map and their two debug probes
 //   rtx_restir_api.hip   the ReSTIR frames, their work lists and lanes, the history / halo exchange between shards
@@ -177,6 +177,7 @@ struct rtx_ctx {
         bool pure = true;               // every sample in u1 since its last clear came from rtx_render_adaptive (rtx_render, rtx_render_v6_pass1 and rtx_render_restir clear this)
         bool cleared = true;            // u1 was cleared since the state above was last used: the next rtx_render_adaptive zeroes it
         uint32_t key[3] = {0, 0, 0};    // width, height, tile size the state is laid out for
+        bool whole = true;              // `half` holds the second sum of EVERY pixel of u1: no rtx_render_adaptive since the state was zeroed was sharded and no rtx_unpack_tiles wrote u1 (rtx_denoise_variance needs it)
     } ad;
 
     // ---- the denoiser (rtx_denoise.hip) ----

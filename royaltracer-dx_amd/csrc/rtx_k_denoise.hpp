@@ -182,6 +182,175 @@ __global__ __launch_bounds__(kBlock) void k_denoise_level_maps(DenoiseLevel a, c
     dn_level<S, FIRST, FL>(a, in, guides, mg, out, partial);
 }
 
+// ---- rtx_denoise_variance (rtx.h, DENOISING: VARIANCE-GUIDED; twin: tests/denoise_var_ref.py) ----
+// The same tile, guides, taps, wn and wp; the colour stop is a luminance distance scaled by the centre's own noise.  A colour record is (c.xyz, v): the VARIANCE of the mean's
+// luminance travels in w, between levels and in LDS, so the staged forms keep dn_level's bytes per pixel.  v is never negative (a square, or a sum of products of squares; it may
+// be +inf or NaN), so "the pixel holds no samples" is w = -1: a record counts for a tap while !(w < 0).
+constexpr float kDnvNoSamples = -1.0f;
+constexpr float kDnvEps = 9.5367431640625e-07f;      // 2^-20: part of the definition of inv
+__device__ __forceinline__ float dnv_luma(float x, float y, float z) { return (0.2126f * x + 0.7152f * y) + 0.0722f * z; }
+__device__ __forceinline__ bool dnv_sampled(F4 c) { return !(c.w < 0.0f); }
+
+// the record a level reads.  Level 0 (FIRST) forms it from u1 and `half`: c = a.xyz / cnt, e = (a.xyz - (hb.xyz + hb.xyz)) / cnt, v = luma(e)^2; under kDnAlbedo a pixel
+// that is filterable by geometry (geo) has both divided by A first.  Every later level reads the previous one's output as it is
+template <bool FIRST, bool ALB> __device__ __forceinline__ F4 dnv_colour(const F4* __restrict__ in, const F4* __restrict__ half, const F4* __restrict__ mg, size_t q, bool geo) {
+    const F4 a = in[q];
+    if constexpr (!FIRST) return a;
+    else {
+        const float cnt = maxf_(a.w, 1.0f);
+        if (!(a.w > 0.0f)) return {a.x / cnt, a.y / cnt, a.z / cnt, kDnvNoSamples};
+        const F4 hb = half[q];
+        F4 c = {a.x / cnt, a.y / cnt, a.z / cnt, 0.0f};
+        float ex = (a.x - (hb.x + hb.x)) / cnt, ey = (a.y - (hb.y + hb.y)) / cnt, ez = (a.z - (hb.z + hb.z)) / cnt;
+        if constexpr (ALB) { if (geo) { const F4 A = mg[2 * q]; dn_demodulate(c, A); ex = ex / A.x; ey = ey / A.y; ez = ez / A.z; } }
+        const float el = dnv_luma(ex, ey, ez);
+        c.w = el * el;
+        return c;
+    }
+}
+
+// 1 / (sigma_var * sqrt(gv) + 2^-20) from the prefilter's two sums
+__device__ __forceinline__ float dnv_inv(float sg, float sgw, float sigma_var) { const float gv = sg / sgw; return 1.0f / (sigma_var * sqrtf(gv) + kDnvEps); }
+__device__ __forceinline__ float dnv_g(int dy, int dx) { return (dy == 0 ? 0.5f : 0.25f) * (dx == 0 ? 0.5f : 0.25f); }      // (1/16, 1/8, 1/16, 1/8, 1/4, 1/8, 1/16, 1/8, 1/16)
+
+struct DnvSum { float x, y, z, w, v; };
+__device__ __forceinline__ void dnv_tap(DnvSum& S, const DenoiseLevel& a, F4 g0p, F4 g1p, F4 np, float lp, float inv, F4 g0q, F4 nq, F4 cq, float hh) {
+    const float dn = (np.x * nq.x + np.y * nq.y) + np.z * nq.z;
+    float wn = maxf_(dn, 0.0f);
+    for (uint32_t k = 0; k < a.normal_power_log2; k++) wn = wn * wn;
+    const float dx = g0q.x - g0p.x, dy = g0q.y - g0p.y, dz = g0q.z - g0p.z;
+    const float dp = fabsf((g1p.x * dx + g1p.y * dy) + g1p.z * dz);
+    const float wp = maxf_(1.0f - dp * a.inv_sigma_plane, 0.0f);
+    const float dl = fabsf(dnv_luma(cq.x, cq.y, cq.z) - lp);
+    const float wc = maxf_(1.0f - dl * inv, 0.0f);
+    const float w = (hh * wn) * (wp * wc);
+    S.x = S.x + w * cq.x; S.y = S.y + w * cq.y; S.z = S.z + w * cq.z; S.w = S.w + w; S.v = S.v + (w * w) * cq.w;
+}
+
+// One level, one thread per pixel, in dn_level's tile and with its two forms (S = 0 direct, S = 1, 2, 4 staged; a.inv_sigma_color_s is not read).  The prefilter's nine
+// positions lie ONE pixel apart whatever the step: the staged forms read them from the tile (the halo 2 S >= 2 covers them), the direct form from global memory.
+// dbg (FIRST only, rtx_debug_denoise_variance): the kernel stores (v, gv) of the centre, (0, 0) for a pixel that is not filterable, and nothing else.
+template <uint32_t S, bool FIRST, uint32_t FL, bool DBG = false>
+__device__ __forceinline__ void dnv_level(const DenoiseLevel& a, float sigma_var, const F4* __restrict__ in, const F4* __restrict__ half, const F4* __restrict__ guides, const F4* __restrict__ mg, F4* __restrict__ out, uint32_t* __restrict__ partial, float* __restrict__ dbg) {
+    constexpr bool ALB = (FL & kDnAlbedo) != 0, NM = (FL & kDnMappedNormals) != 0;
+    static_assert(!DBG || (FIRST && S == 0), "the debug form is the direct first level");
+    constexpr uint32_t RW = kDnTileW + 4u * S, RH = kDnTileH + 4u * S;
+    __shared__ F4 s_c[S ? RW * RH : 1], s_g0[S ? RW * RH : 1], s_g1[S ? RW * RH : 1], s_nm[S && NM ? RW * RH : 1];
+    __shared__ uint32_t s_cnt[kBlock / 64];
+    const uint32_t tx = blockIdx.x % a.tiles_x, ty = blockIdx.x / a.tiles_x;
+    const uint32_t lx = threadIdx.x & (kDnTileW - 1u), ly = threadIdx.x / kDnTileW;
+    const int x0 = (int)(tx * kDnTileW), y0 = (int)(ty * kDnTileH), W = (int)a.width, H = (int)a.height;
+    const int x = x0 + (int)lx, y = y0 + (int)ly, s = (int)a.step;
+    if constexpr (S != 0) {
+        for (uint32_t i = threadIdx.x; i < RW * RH; i += kBlock) {
+            const int qx = x0 - 2 * (int)S + (int)(i % RW), qy = y0 - 2 * (int)S + (int)(i / RW);
+            // a position outside the image reads its nearest pixel (always in bounds, no divergent load) and is marked kDnNoGeo: it counts for no tap
+            const bool ins = qx >= 0 && qx < W && qy >= 0 && qy < H;
+            const size_t q = (size_t)(qy < 0 ? 0 : (qy >= H ? H - 1 : qy)) * a.width + (size_t)(qx < 0 ? 0 : (qx >= W ? W - 1 : qx));
+            F4 g0 = guides[2 * q]; const F4 g1 = guides[2 * q + 1];
+            const F4 c = dnv_colour<FIRST, ALB>(in, half, mg, q, f2u(g0.w) != kDnNoGeo);
+            if (!ins) g0.w = u2f(kDnNoGeo);
+            s_c[i] = c; s_g0[i] = g0; s_g1[i] = g1;
+            if constexpr (NM) s_nm[i] = mg[2 * q + 1];
+        }
+        __syncthreads();
+    }
+    bool filt = false;
+    if (x < W && y < H) {
+        const size_t p = (size_t)y * a.width + (size_t)x;
+        const uint32_t lp = (ly + 2u * S) * RW + lx + 2u * S;
+        F4 cp, g0p, g1p = {0.0f, 0.0f, 0.0f, 0.0f}, np = {0.0f, 0.0f, 0.0f, 0.0f};
+        if constexpr (S != 0) { cp = s_c[lp]; g0p = s_g0[lp]; }
+        else { g0p = guides[2 * p]; cp = dnv_colour<FIRST, ALB>(in, half, mg, p, f2u(g0p.w) != kDnNoGeo); }
+        const uint32_t matp = f2u(g0p.w);
+        filt = matp != kDnNoGeo && dnv_sampled(cp);
+        F4 o = cp;
+        float sg = 0.0f, sgw = 0.0f;
+        if (filt) {
+            // the prefilter: gv = the binomial mean of v over the 3 x 3 positions that count
+#pragma unroll
+            for (int dy = -1; dy <= 1; dy++) {
+#pragma unroll
+                for (int dx = -1; dx <= 1; dx++) {
+                    const float gg = dnv_g(dy, dx);
+                    if constexpr (S != 0) {
+                        const uint32_t lq = (uint32_t)((int)lp + dy * (int)RW + dx);
+                        if (f2u(s_g0[lq].w) != matp) continue;
+                        const float vq = s_c[lq].w;
+                        if (vq < 0.0f) continue;
+                        sg = sg + gg * vq; sgw = sgw + gg;
+                    } else {
+                        const int qx = x + dx, qy = y + dy;
+                        if (qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
+                        const size_t q = (size_t)qy * a.width + (size_t)qx;
+                        if (f2u(guides[2 * q].w) != matp) continue;
+                        const F4 cq = dnv_colour<FIRST, ALB>(in, half, mg, q, true);
+                        if (!dnv_sampled(cq)) continue;
+                        sg = sg + gg * cq.w; sgw = sgw + gg;
+                    }
+                }
+            }
+        }
+        if constexpr (DBG) { dbg[2 * p] = filt ? cp.w : 0.0f; dbg[2 * p + 1] = filt ? sg / sgw : 0.0f; }
+        else {
+            if (filt) {
+                const float inv = dnv_inv(sg, sgw, sigma_var);
+                const float lum = dnv_luma(cp.x, cp.y, cp.z);
+                if constexpr (S != 0) g1p = s_g1[lp]; else g1p = guides[2 * p + 1];
+                if constexpr (!NM) np = g1p; else if constexpr (S != 0) np = s_nm[lp]; else np = mg[2 * p + 1];
+                DnvSum sum = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+                for (int dy = -2; dy <= 2; dy++) {
+#pragma unroll
+                    for (int dx = -2; dx <= 2; dx++) {
+                        const float hh = dn_h(dy) * dn_h(dx);
+                        if constexpr (S != 0) {
+                            const uint32_t lq = (uint32_t)((int)lp + (dy * (int)RW + dx) * (int)S);
+                            const F4 g0q = s_g0[lq];
+                            if (f2u(g0q.w) != matp) continue;
+                            const F4 cq = s_c[lq];
+                            if (!dnv_sampled(cq)) continue;
+                            if constexpr (NM) dnv_tap(sum, a, g0p, g1p, np, lum, inv, g0q, s_nm[lq], cq, hh);
+                            else dnv_tap(sum, a, g0p, g1p, np, lum, inv, g0q, s_g1[lq], cq, hh);
+                        } else {
+                            const int qx = x + s * dx, qy = y + s * dy;
+                            if (qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
+                            const size_t q = (size_t)qy * a.width + (size_t)qx;
+                            const F4 g0q = guides[2 * q];
+                            if (f2u(g0q.w) != matp) continue;
+                            const F4 cq = dnv_colour<FIRST, ALB>(in, half, mg, q, true);
+                            if (!dnv_sampled(cq)) continue;
+                            if constexpr (NM) dnv_tap(sum, a, g0p, g1p, np, lum, inv, g0q, mg[2 * q + 1], cq, hh);
+                            else dnv_tap(sum, a, g0p, g1p, np, lum, inv, g0q, guides[2 * q + 1], cq, hh);
+                        }
+                    }
+                }
+                o.x = sum.x / sum.w; o.y = sum.y / sum.w; o.z = sum.z / sum.w; o.w = sum.v / (sum.w * sum.w);
+                if constexpr (ALB) { if (a.last) { const F4 A = mg[2 * p]; o.x = o.x * A.x; o.y = o.y * A.y; o.z = o.z * A.z; } }
+            }
+            if (a.last) o.w = 1.0f;
+            out[p] = o;
+        }
+    }
+    if constexpr (FIRST && !DBG) {
+        const unsigned long long m = __ballot(filt);
+        if (lane_id() == 0) s_cnt[threadIdx.x >> 6] = (uint32_t)__popcll(m);
+        __syncthreads();
+        if (threadIdx.x == 0) partial[blockIdx.x] = (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);
+    }
+}
+// FL = 0 .. 3; mg is read only with a flag set, half only by the first level
+template <uint32_t S, bool FIRST, uint32_t FL>
+__global__ __launch_bounds__(kBlock) void k_denoise_level_var(DenoiseLevel a, float sigma_var, const F4* __restrict__ in, const F4* __restrict__ half, const F4* __restrict__ guides, const F4* __restrict__ mg, F4* __restrict__ out, uint32_t* __restrict__ partial) {
+    static_assert(FL <= 3u, "the flags word");
+    dnv_level<S, FIRST, FL>(a, sigma_var, in, half, guides, mg, out, partial, nullptr);
+}
+// rtx_debug_denoise_variance: (v, gv) of level 0 per pixel
+template <bool ALB>
+__global__ __launch_bounds__(kBlock) void k_denoise_var_input(DenoiseLevel a, const F4* __restrict__ in, const F4* __restrict__ half, const F4* __restrict__ guides, const F4* __restrict__ mg, float* __restrict__ out2) {
+    dnv_level<0u, true, ALB ? kDnAlbedo : 0u, true>(a, 0.0f, in, half, guides, mg, nullptr, nullptr, out2);
+}
+
 // the filterable pixels of the image: the sum of the level-0 workgroups' counts (one workgroup, a plain store)
 __global__ __launch_bounds__(kBlock) void k_denoise_count(const uint32_t* __restrict__ partial, uint32_t n, uint32_t* __restrict__ out) {
     __shared__ uint32_t s_sum[kBlock];

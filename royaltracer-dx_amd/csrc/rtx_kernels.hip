@@ -51,7 +51,7 @@ __device__ unsigned long long g_sec[36];          // [0,12) cycles, [12,24) acti
 #include "rtx_k_bounce_bvh.hpp"     // k_bounce_bvh, k_order_queues
 #include "rtx_k_film.hpp"           // k_accumulate, k_srgb8, k_debug_layer, k_pack_tiles, k_unpack_tiles
 #include "rtx_k_adaptive.hpp"       // k_adaptive_error, k_adaptive_compact
-#include "rtx_k_denoise.hpp"        // k_denoise_guides, k_denoise_level, k_denoise_count
+#include "rtx_k_denoise.hpp"        // k_denoise_guides, k_denoise_level, k_denoise_level_var, k_denoise_count
 #include "rtx_k_dbg.hpp"            // k_dbg_*
 
 namespace rtx {
@@ -357,6 +357,20 @@ void launch_denoise_level_maps(hipStream_t st, DenoiseLevel a, uint32_t flags, c
         denoise_level_form(a, staged, [&](auto ss, auto first) { hipLaunchKernelGGL((k_denoise_level_maps<decltype(ss)::value, decltype(first)::value, decltype(fl)::value>), grid, dim3(kBlock), 0, st, a, in, guides, mguides, out, partial); });
     };
     if (flags == 1u) pick(IntC<1>{}); else if (flags == 2u) pick(IntC<2>{}); else pick(IntC<3>{});
+}
+// rtx_denoise_variance: flags 0 .. 3; half is read by the first level, mguides with a flag set
+void launch_denoise_level_var(hipStream_t st, DenoiseLevel a, float sigma_var, uint32_t flags, const F4* in, const F4* half, const F4* guides, const F4* mguides, F4* out, uint32_t* partial, bool staged) {
+    a.tiles_x = (a.width + kDnTileW - 1u) / kDnTileW;
+    const dim3 grid(denoise_workgroups(a.width, a.height));
+    auto pick = [&](auto fl) {
+        denoise_level_form(a, staged, [&](auto ss, auto first) { hipLaunchKernelGGL((k_denoise_level_var<decltype(ss)::value, decltype(first)::value, decltype(fl)::value>), grid, dim3(kBlock), 0, st, a, sigma_var, in, half, guides, mguides, out, partial); });
+    };
+    if (flags == 0u) pick(IntC<0>{}); else if (flags == 1u) pick(IntC<1>{}); else if (flags == 2u) pick(IntC<2>{}); else pick(IntC<3>{});
+}
+void launch_denoise_var_input(hipStream_t st, uint32_t width, uint32_t height, bool albedo, const F4* in, const F4* half, const F4* guides, const F4* mguides, float* out2) {
+    DenoiseLevel a{};
+    a.width = width; a.height = height; a.step = 1u; a.first = 1u; a.tiles_x = (width + kDnTileW - 1u) / kDnTileW;
+    dispatch_bool(albedo, [&](auto alb) { hipLaunchKernelGGL(k_denoise_var_input<decltype(alb)::value>, dim3(denoise_workgroups(width, height)), dim3(kBlock), 0, st, a, in, half, guides, mguides, out2); });
 }
 void launch_denoise_count(hipStream_t st, const uint32_t* partial, uint32_t n, uint32_t* out) {
     hipLaunchKernelGGL(k_denoise_count, dim3(1), dim3(kBlock), 0, st, partial, n, out);

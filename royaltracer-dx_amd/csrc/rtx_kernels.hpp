@@ -259,6 +259,9 @@ uint32_t denoise_workgroups(uint32_t width, uint32_t height);                   
 // staged: the tile and its halo go through LDS (steps 1, 2 and 4 only); partial: per-workgroup counts of filterable pixels, written by the first level
 void launch_denoise_level(hipStream_t, DenoiseLevel, const F4* in, const F4* guides, F4* out, uint32_t* partial, bool staged);
 void launch_denoise_level_maps(hipStream_t, DenoiseLevel, uint32_t flags /* 1, 2 or 3 */, const F4* in, const F4* guides, const F4* mguides, F4* out, uint32_t* partial, bool staged);   // the forms with a flag of rtx_denoise_params set
+// rtx_denoise_variance: one level (DenoiseLevel::inv_sigma_color_s is not read; flags 0 .. 3; half: the adaptive sampler's second sum, read by the first level), and (v, gv) of level 0
+void launch_denoise_level_var(hipStream_t, DenoiseLevel, float sigma_var, uint32_t flags, const F4* in, const F4* half, const F4* guides, const F4* mguides, F4* out, uint32_t* partial, bool staged);
+void launch_denoise_var_input(hipStream_t, uint32_t width, uint32_t height, bool albedo, const F4* in, const F4* half, const F4* guides, const F4* mguides, float* out2);
 void launch_denoise_count(hipStream_t, const uint32_t* partial, uint32_t n, uint32_t* out);
 void launch_srgb8(hipStream_t, const F4* accum, uint32_t npix, uint32_t* out);
 void launch_debug_layer(hipStream_t, uint32_t max_blocks, const DevScene&, uint32_t width, uint32_t height, const CameraGPU* cam, uint32_t layer, uint32_t* out);

@@ -333,6 +333,11 @@ void MultiGpuFrame::Denoise(const rtx_denoise_params* params, int rank) {
     hipck(hipSetDevice(m_devices[rank]), "hipSetDevice");
     if (rtx_denoise(m->ctx[rank], m_w, m_h, params, nullptr) != RTX_OK) throw std::runtime_error(std::string("rtx_denoise: ") + rtx_last_error(m->ctx[rank]));
 }
+void MultiGpuFrame::DenoiseVariance(const rtx_denoise_var_params* params, int rank) {
+    if (m_devices.size() > 1) throw std::logic_error("MultiGpuFrame::DenoiseVariance: the adaptive sampler's second sum is not gathered across ranks; one rank only");
+    hipck(hipSetDevice(m_devices[rank]), "hipSetDevice");
+    if (rtx_denoise_variance(m->ctx[rank], m_w, m_h, params, nullptr) != RTX_OK) throw std::runtime_error(std::string("rtx_denoise_variance: ") + rtx_last_error(m->ctx[rank]));
+}
 std::vector<float> MultiGpuFrame::ReadDenoised(int rank) {
     std::vector<float> out((size_t)m_w * m_h * 4);
     hipck(hipSetDevice(m_devices[rank]), "hipSetDevice");

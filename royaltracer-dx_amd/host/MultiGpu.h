@@ -57,6 +57,9 @@ public:
     std::vector<uint8_t> ReadOutput(int rank = 0);
     // rtx_denoise on ONE rank's assembled image (after Render's gather every rank holds the whole accumulation buffer; the filter needs no shard fields), and its reads
     void Denoise(const rtx_denoise_params* params = nullptr, int rank = 0);
+    // rtx_denoise_variance: std::logic_error with more than one rank (`half` is per rank and is not gathered), and the context's RTX_ERR_STATE on one rank unless its image was
+    // sampled by rtx_render_adaptive alone
+    void DenoiseVariance(const rtx_denoise_var_params* params = nullptr, int rank = 0);
     std::vector<float> ReadDenoised(int rank = 0);
     std::vector<uint8_t> ReadDenoisedOutput(int rank = 0);
     rtx_stats Stats(int rank) const { return m_stats[rank]; }

@@ -62,6 +62,9 @@ public:
     // Path tracer frames only (std::logic_error in ReSTIR mode: that frame has its own reuse passes).  gPermanentData is left alone, so OnRender keeps accumulating; the
     // denoised image is read with ReadDenoised (RGBA32F, w = 1) / ReadDenoisedOutput (RGBA8 after the sRGB OETF).  Defined in RendererDenoise.cpp
     rtx_denoise_result Denoise(const rtx_denoise_params* params = nullptr);
+    // rtx_denoise_variance: the same filter with the colour stop scaled by each pixel's own noise.  The image must have been sampled by rtx_render_adaptive on Context()
+    // alone since its last clear (OnRender issues rtx_render: std::runtime_error after it, with the context's message); read like Denoise's.  Defined in RendererDenoise.cpp
+    rtx_denoise_result DenoiseVariance(const rtx_denoise_var_params* params = nullptr);
     std::vector<float> ReadDenoised();
     std::vector<uint8_t> ReadDenoisedOutput();
     std::vector<uint8_t> ReadOutput();              // the DISPLAYED layer of gOutput (RGBA8): what the reference copies to the back buffer (Renderer.cpp:690-698)
@@ -88,3 +91,6 @@ private:
     rtx_lens m_lens{};                                                        // SetLens: what it set (all zero = the pinhole)
     std::vector<uint8_t> m_hidden; std::vector<UINT> m_flippedInstances;      // visibility per instance as last asked for; the instances whose value changed since the last OnUpdate
 };
+
+// the handle of include/rtx_host.h's renderer functions (rtx_host_c.cpp; RendererDenoise.cpp for the one that needs the denoiser's entry points)
+struct rtxh_renderer { Renderer* r; };

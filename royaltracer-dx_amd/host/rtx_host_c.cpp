@@ -15,7 +15,6 @@
 #include "manipulator.h"
 
 struct rtxh_scene { Scene s; std::string cache_path; };     // cache_path: the scene came from rtxh_scene_load; rtxh_scene_upload hands the FILE to the context (no rebuild)
-struct rtxh_renderer { Renderer* r; };
 static thread_local std::string g_err;
 
 template <class F> static rtxh_scene* guarded(F&& f) {

@@ -21,6 +21,9 @@
 //                   [--denoise-albedo] with --denoise: RTX_DENOISE_ALBEDO, the filter works on the image divided by the first hit's Kd' (texture detail survives)
 //                   [--denoise-mapped-normals] with --denoise: RTX_DENOISE_MAPPED_NORMALS, the normal stop compares normal-mapped shading normals (shading relief survives);
 //                   either one without --denoise is a usage error
+//                   [--denoise-variance [--sigma-var K]] with --adaptive T: rtx_denoise_variance instead of rtx_denoise — the colour stop is scaled by each pixel's own noise, K
+//                   standard deviations (default 4), estimated from the adaptive sampler's two half sums; implies --denoise, combines with --denoise-albedo and
+//                   --denoise-mapped-normals, ignores --sigma-color; --adaptive 0 gives it a fixed --spp.  Without --adaptive, or with --gpus N > 1, a usage error
 //                   [--no-textures]   OBJ scenes: do not read the images their map_Kd statements name (binary PPM / PGM, 24- / 32-bit TGA): the image without diffuse maps
 //                   [--no-cutouts]    OBJ scenes: do not bind the images their map_d statements name as opacity maps (alpha cut-outs): the image with every card opaque
 //                   [--kd-alpha]      OBJ scenes: a material without a map_d whose map_Kd is a 32-bit TGA gets that texture's alpha as its opacity map too
@@ -58,6 +61,7 @@ static const char* kUsage =
     "                  [--adaptive THRESHOLD [--min-spp N] [--step-spp N]]\n"
     "                  [--denoise [--denoise-levels N] [--sigma-color X] [--sigma-plane X]]   write the denoised image to --out (path tracer only)\n"
     "                  [--denoise-albedo] [--denoise-mapped-normals]   with --denoise: keep texture detail (filter the image divided by Kd') / normal-map relief\n"
+    "                  [--denoise-variance [--sigma-var K]]   with --adaptive: scale the colour stop by each pixel's own noise (implies --denoise; one GPU)\n"
     "                  [--no-textures]   OBJ scenes: ignore map_Kd images (implies --no-cutouts)\n"
     "                  [--no-cutouts]    OBJ scenes: ignore map_d images (no alpha cut-outs)   [--kd-alpha]   a 32-bit map_Kd without a map_d is its material's opacity map too\n"
     "                  [--no-normal-maps] OBJ scenes: ignore norm images (--no-textures implies it)   [--bump-as-normal | --bump-height S]   map_Bump / bump as a normal map / a height map of strength S\n"
@@ -75,6 +79,7 @@ int main(int argc, char** argv) {
     std::vector<UINT> hide; int blink = -1;
     bool adaptive = false; rtx_adaptive ad{}; ad.min_spp = 8; ad.step_spp = 8;
     bool denoise = false; rtx_denoise_params dnp{};
+    bool denoise_var = false; float sigma_var = 0.0f; bool sigma_var_set = false;
     bool textures = true; SceneCutouts cutouts = kCutoutsMapD; bool kd_alpha = false; SceneNormals normals; bool no_normals = false, spec_maps = true, emission_maps = true;
     float aperture = 0.0f, focus = 0.0f; bool focus_set = false; std::string focus_pixel;
     std::string env_file, sky; UINT env_res = 512; float env_yaw = 0.0f, env_scale = 1.0f; bool env_hidden = false;
@@ -95,6 +100,7 @@ int main(int argc, char** argv) {
         else if (arg("--env")) env_file = argv[++i]; else if (arg("--env-res")) env_res = (UINT)atoi(argv[++i]); else if (arg("--env-yaw")) env_yaw = (float)atof(argv[++i]);
         else if (arg("--env-scale")) env_scale = (float)atof(argv[++i]); else if (!strcmp(argv[i], "--env-hidden")) env_hidden = true; else if (arg("--sky")) sky = argv[++i];
         else if (!strcmp(argv[i], "--denoise-albedo")) dnp.flags |= RTX_DENOISE_ALBEDO; else if (!strcmp(argv[i], "--denoise-mapped-normals")) dnp.flags |= RTX_DENOISE_MAPPED_NORMALS;
+        else if (!strcmp(argv[i], "--denoise-variance")) denoise_var = denoise = true; else if (arg("--sigma-var")) { sigma_var = (float)atof(argv[++i]); sigma_var_set = true; }
         else if (!strcmp(argv[i], "--denoise")) denoise = true; else if (arg("--denoise-levels")) dnp.levels = (uint32_t)atoi(argv[++i]); else if (arg("--sigma-color")) dnp.sigma_color = (float)atof(argv[++i]); else if (arg("--sigma-plane")) dnp.sigma_plane = (float)atof(argv[++i]);
         else if (arg("--aperture")) aperture = (float)atof(argv[++i]); else if (arg("--focus")) { focus = (float)atof(argv[++i]); focus_set = true; } else if (arg("--focus-pixel")) focus_pixel = argv[++i];
         else if (arg("--halo")) halo = (UINT)atoi(argv[++i]); else if (arg("--gpus")) gpus = atoi(argv[++i]); else if (arg("--devices")) devlist = argv[++i]; else if (arg("--gather")) gather = argv[++i];
@@ -108,6 +114,8 @@ int main(int argc, char** argv) {
     if (restir) { if (!nee_set) nee = 4; if (!bounces_set) bounces = 3; }
     if (adaptive && (restir || gpus > 1 || !devlist.empty())) { fprintf(stderr, "--adaptive is the path tracer on one GPU (no --mode restir, --gpus, --devices)\n"); return 2; }
     if (dnp.flags && !denoise) { fprintf(stderr, "--denoise-albedo and --denoise-mapped-normals are options of --denoise\n"); return 2; }
+    if (sigma_var_set && !denoise_var) { fprintf(stderr, "--sigma-var is an option of --denoise-variance\n"); return 2; }
+    if (denoise_var && (!adaptive || gpus > 1 || !devlist.empty())) { fprintf(stderr, "--denoise-variance needs --adaptive T (the sampler's half sums; T = 0 for a fixed --spp) on one GPU (no --gpus, --devices)\n"); return 2; }
     if (denoise && restir) { fprintf(stderr, "--denoise filters the path tracer's accumulation (no --mode restir: that frame has its own reuse passes)\n"); return 2; }
     if (!env_file.empty() && !sky.empty()) { fprintf(stderr, "--env and --sky exclude each other\n"); return 2; }
     UINT fpx = 0, fpy = 0;
@@ -238,8 +246,10 @@ int main(int argc, char** argv) {
                    (unsigned long long)s.rays_primary, (unsigned long long)s.rays_extension, (unsigned long long)s.rays_shadow);
         }
         if (denoise) {
-            const rtx_denoise_result dr = r.Denoise(&dnp);
-            printf("denoise: %u levels, %u pixels filtered, %u passed through\n", dr.levels, dr.pixels_filtered, dr.pixels_passed);
+            rtx_denoise_var_params dvp{};
+            dvp.levels = dnp.levels; dvp.sigma_var = sigma_var; dvp.sigma_plane = dnp.sigma_plane; dvp.flags = dnp.flags;
+            const rtx_denoise_result dr = denoise_var ? r.DenoiseVariance(&dvp) : r.Denoise(&dnp);
+            printf(denoise_var ? "denoise (variance-guided): %u levels, %u pixels filtered, %u passed through\n" : "denoise: %u levels, %u pixels filtered, %u passed through\n", dr.levels, dr.pixels_filtered, dr.pixels_passed);
         }
         if (!out.empty()) {
             const bool exr = out.size() > 4 && out.substr(out.size() - 4) == ".exr", png = out.size() > 4 && out.substr(out.size() - 4) == ".png";
