@@ -320,6 +320,24 @@ def _fptr(a):
 # ------------------------------------------------------------------------------------------------
 # host layer
 # ------------------------------------------------------------------------------------------------
+def _host_maps(fn, *slot):
+    """accessor of _SCENE_MAP_SLOTS over one of the host layer's rtxh_scene_*_map functions"""
+    return lambda scene, n: [int(fn(scene._h, i, *slot)) for i in range(n)]
+
+
+# the map slots of a scene: (Scene attribute, rtx_set_material_map slot, accessor(scene, material count) -> per material the index into `textures` or -1).  Scene.__init__ fills
+# the attributes from it and Context.bind_maps binds them by it (a duck-typed scene only needs the attributes it has)
+_SCENE_MAP_SLOTS = (
+    ("material_maps", MAP_KD, lambda scene, n: [scene.textures.index(e["maps"]["Kd"]) if "Kd" in e["maps"] else -1 for e in scene.material_ext]),
+    ("opacity_maps", MAP_OPACITY, _host_maps(lib.rtxh_scene_opacity_map)),
+    ("normal_maps", MAP_NORMAL, _host_maps(lib.rtxh_scene_normal_map)),
+    ("ks_maps", MAP_KS, _host_maps(lib.rtxh_scene_spec_map, MAP_KS)),
+    ("pr_maps", MAP_PR, _host_maps(lib.rtxh_scene_spec_map, MAP_PR)),
+    ("pm_maps", MAP_PM, _host_maps(lib.rtxh_scene_spec_map, MAP_PM)),
+    ("ke_maps", MAP_KE, _host_maps(lib.rtxh_scene_emission_map)),
+)
+
+
 class Scene:
     """A host-side scene in the reference's data model (global Material table, per-model
     Vertex / index / materialID arrays, instance list).  Arrays are numpy copies."""
@@ -345,16 +363,12 @@ class Scene:
             px, tw, th = _vp(), _u32(), _u32()
             lib.rtxh_scene_texture_pixels(handle, i, C.byref(px), C.byref(tw), C.byref(th))
             self.texture_pixels.append(np.array((C.c_uint8 * (tw.value * th.value * 4)).from_address(px.value), dtype=np.uint8).reshape(th.value, tw.value, 4) if px.value else None)
-        self.material_maps = [self.textures.index(e["maps"]["Kd"]) if "Kd" in e["maps"] else -1 for e in self.material_ext]
-        # ... and for the opacity maps (map_d; alpha byte = the file's alpha channel for a 32-bit TGA, else its first channel): per material the texture id or -1
-        self.opacity_maps = [int(lib.rtxh_scene_opacity_map(handle, i)) for i in range(n)]
-        # ... and for the normal maps (norm; on request map_Bump / bump, as it is or converted from a height map)
-        self.normal_maps = [int(lib.rtxh_scene_normal_map(handle, i)) for i in range(n)]
-        # ... and for the specular, roughness and metalness maps (map_Ks / map_Pr / map_Pm); ess_table: the 17-row energy table that goes with a roughness map, else None
-        self.ks_maps, self.pr_maps, self.pm_maps = ([int(lib.rtxh_scene_spec_map(handle, i, slot)) for i in range(n)] for slot in (MAP_KS, MAP_PR, MAP_PM))
+        # ... and per slot of _SCENE_MAP_SLOTS, per material, the texture id the host bound or -1: material_maps (map_Kd), opacity_maps (map_d; alpha byte = the file's alpha
+        # channel for a 32-bit TGA, else its first channel), normal_maps (norm; on request map_Bump / bump, as it is or converted from a height map), ks_maps / pr_maps /
+        # pm_maps (map_Ks / map_Pr / map_Pm), ke_maps (map_Ke); ess_table: the 17-row energy table that goes with a roughness map, else None
+        for attr, _, accessor in _SCENE_MAP_SLOTS:
+            setattr(self, attr, accessor(self, n))
         self.ess_table = ess_table_rows(17) if any(t >= 0 for t in self.pr_maps) else None
-        # ... and for the emission maps (map_Ke)
-        self.ke_maps = [int(lib.rtxh_scene_emission_map(handle, i)) for i in range(n)]
         self.meshes, self.uvs = [], []
         for i in range(lib.rtxh_scene_num_meshes(handle)):
             v, idx, mid = _vp(), _vp(), _vp()
@@ -804,16 +818,7 @@ class Context:
             if isinstance(px, np.ndarray) and px.ndim == 3:
                 ids[i] = len(ids)
                 self.set_texture(ids[i], px, srgb)
-        for mat, t in enumerate(getattr(scene, "material_maps", None) or []):
-            if t is not None and t >= 0 and t in ids:
-                self.set_material_map(mat, ids[t])
-        for mat, t in enumerate(getattr(scene, "opacity_maps", None) or []):
-            if t is not None and t >= 0 and t in ids:
-                self.set_material_map(mat, ids[t], MAP_OPACITY)
-        for mat, t in enumerate(getattr(scene, "normal_maps", None) or []):
-            if t is not None and t >= 0 and t in ids:
-                self.set_material_map(mat, ids[t], MAP_NORMAL)
-        for attr, slot in (("ks_maps", MAP_KS), ("pr_maps", MAP_PR), ("pm_maps", MAP_PM), ("ke_maps", MAP_KE)):
+        for attr, slot, _ in _SCENE_MAP_SLOTS:
             for mat, t in enumerate(getattr(scene, attr, None) or []):
                 if t is not None and t >= 0 and t in ids:
                     self.set_material_map(mat, ids[t], slot)

@@ -73,16 +73,12 @@ static void fill_tex_lut(std::vector<float>& lut) {
         lut[256 + b] = (float)(cs <= 0.04045 ? cs / 12.92 : pow((cs + 0.055) / 1.055, 2.4));
     }
 }
-// The device's texture tables follow the host's (SceneHost::textures / map_kd / MeshHost::uvs): tables only, no kernel runs.  renumbered: this commit numbered the global
+// The device's texture tables follow the host's (SceneHost::textures / maps / MeshHost::uvs): tables only, no kernel runs.  renumbered: this commit numbered the global
 // triangle ids anew (a build); deformed: a mesh got new vertices (the tangent records are derived from them).  What the kernels see of it is set by finalise_scene.
-static int sync_textures(rtx_ctx* c, bool renumbered, bool deformed) {
+static int sync_textures(rtx_ctx* c, MapUse use, bool renumbered, bool deformed) {
     SceneHost& H = c->host; rtx_ctx::Scene& S = c->scene;
-    S.built.maps_active = H.maps_active();
-    const bool cut = S.built.cutouts_active = H.cutouts_active();
-    const bool nrm = S.built.normals_active = H.normals_active();
-    const bool spc = S.built.spec_active = H.spec_active();
-    const bool emi = S.built.emi_active = H.emi_active();
-    const bool active = S.built.maps_active || cut || nrm || spc || emi;   // the UVs serve all five
+    S.built.map_use = use;
+    const bool active = use.any(), cut = use.cut(), nrm = use.nrm();       // (the UVs serve every group)
     int r;
     if (H.tex_dirty) {                                       // (a scene that never saw one of the three setters allocates nothing here)
         std::vector<TexDesc> desc(H.textures.size()); std::vector<uint32_t> pool;
@@ -91,28 +87,11 @@ static int sync_textures(rtx_ctx* c, bool renumbered, bool deformed) {
             desc[i] = TexDesc{(uint32_t)pool.size(), t.width, t.height, t.flags};
             pool.insert(pool.end(), t.rgba.begin(), t.rgba.end());
         }
-        std::vector<int32_t> maps(H.mats128.size() / 32, -1);
-        for (size_t m = 0; m < maps.size() && m < H.map_kd.size(); m++) maps[m] = H.map_kd[m];
-        if ((r = upload(c, S.d_tex_desc, desc)) || (r = upload(c, S.d_texels, pool)) || (r = upload(c, S.d_map_kd, maps))) return r;
-        if (!H.any_normal_map()) S.d_map_nrm.release();
-        else {
-            std::vector<int32_t> nmaps(H.mats128.size() / 32, -1);
-            for (size_t m = 0; m < nmaps.size() && m < H.map_normal.size(); m++) nmaps[m] = H.map_normal[m];
-            if ((r = upload(c, S.d_map_nrm, nmaps))) return r;
-        }
-        if (!H.any_spec_map()) S.d_map_spec.release();
-        else {
-            const size_t nm = H.mats128.size() / 32;
-            std::vector<int32_t> smaps(nm * 3, -1);
-            for (int k = 0; k < 3; k++) for (size_t m = 0; m < nm && m < H.map_spec[k].size(); m++) smaps[k * nm + m] = H.map_spec[k][m];
-            if ((r = upload(c, S.d_map_spec, smaps))) return r;
-        }
-        if (!H.any_emi_map()) S.d_map_ke.release();
-        else {
-            std::vector<int32_t> emaps(H.mats128.size() / 32, -1);
-            for (size_t m = 0; m < emaps.size() && m < H.map_ke.size(); m++) emaps[m] = H.map_ke[m];
-            if ((r = upload(c, S.d_map_ke, emaps))) return r;
-        }
+        const size_t nm = S.mat_maps_nmat = H.mats128.size() / 32;
+        std::vector<int32_t> ids(rtx_ctx::Scene::kMatMapRows * nm, -1);       // one row per slot the kernels read by material, -1 where the host's vector ends
+        for (uint32_t s = 0; s < kMapSlotCount; s++)
+            if (s != kMapOpacity) std::copy_n(H.maps[s].begin(), std::min(nm, H.maps[s].size()), ids.begin() + rtx_ctx::Scene::mat_map_row((MapSlot)s) * nm);
+        if ((r = upload(c, S.d_tex_desc, desc)) || (r = upload(c, S.d_texels, pool)) || (r = upload(c, S.d_mat_maps, ids))) return r;
         if (!H.ess_rows) S.d_ess_tab.release();
         else if ((r = upload(c, S.d_ess_tab, H.ess_table))) return r;
         if (!S.d_tex_lut.p) { std::vector<float> lut; fill_tex_lut(lut); if ((r = upload(c, S.d_tex_lut, lut))) return r; }
@@ -124,7 +103,7 @@ static int sync_textures(rtx_ctx* c, bool renumbered, bool deformed) {
         S.tri_uv_valid = true;
     }
     if (!active && S.tri_uv_valid) { S.d_tri_uv.release(); S.tri_uv_valid = false; }       // (allocated only while a map is active)
-    // alpha cut-outs: the opacity texture per GLOBAL triangle id — from map_opacity, the material ids and the emitter test, numbered like tri_uv; never part of the leaf records
+    // alpha cut-outs: the opacity texture per GLOBAL triangle id — from maps[kMapOpacity], the material ids and the emitter test, numbered like tri_uv; never part of the leaf records
     if (cut && (H.tex_dirty || renumbered || !S.tri_cut_valid)) {
         std::vector<int32_t> tc; H.fill_tri_cut(tc);
         if ((r = upload(c, S.d_tri_cut, tc))) return r;
@@ -443,8 +422,9 @@ int rtx_commit_scene(rtx_ctx* c) {
     int r;
     // On the GPU: a scene that is already resident and not a tiny one (whose pre-test records depend on world positions).
     // a tiny scene leaves its pre-test records for the general path while a texture map is active and returns to them afterwards: the commit that crosses that line rebuilds
+    const MapUse use = c->host.map_use();                  // the map groups active from this commit on (one pass over the triangles; nothing below changes what it reads)
     {   size_t ntri_all = 0; for (const InstHost& in : c->host.insts) ntri_all += c->host.meshes[in.mesh].idx.size() / 3;
-        if (c->host.tex_dirty && ntri_all <= kSmallSceneMaxTris && (c->host.maps_active() != c->scene.built.maps_active || c->host.cutouts_active() != c->scene.built.cutouts_active || c->host.normals_active() != c->scene.built.normals_active || c->host.spec_active() != c->scene.built.spec_active || c->host.emi_active() != c->scene.built.emi_active)) c->host.topo_dirty = true;
+        if (c->host.tex_dirty && ntri_all <= kSmallSceneMaxTris && use != c->scene.built.map_use) c->host.topo_dirty = true;
         // ... and so it does while an environment is bound
         if (c->host.env_dirty && ntri_all <= kSmallSceneMaxTris && (c->host.env.n != 0) != c->scene.built.env_active) c->host.topo_dirty = true; }
     bool build = !(c->opt.gpu_refit && gpu_refittable(c) && !c->host.topo_dirty);
@@ -457,7 +437,7 @@ int rtx_commit_scene(rtx_ctx* c) {
     // ... and likewise when only the environment changed
     const bool tex_only = !build && (c->host.tex_dirty || c->host.env_dirty) && c->host.only_maps_changed(B0);
     // ... except that, while an emission map is active on an emitter or was at the previous commit, the light list follows the texels: rebuilt on the host, uploaded
-    if (tex_only && c->host.tex_dirty && (B0.emi_active || c->host.emi_active())) {
+    if (tex_only && c->host.tex_dirty && (B0.map_use.emi() || use.emi())) {
         c->host.build_lights(c->scene.built);
         if ((r = upload_lights(c))) return r;
     }
@@ -476,7 +456,7 @@ int rtx_commit_scene(rtx_ctx* c) {
         if ((r = build_and_upload(c))) return r;
     }
     c->host.dirty_meshes.clear();
-    if ((r = sync_textures(c, build, deform))) return r;
+    if ((r = sync_textures(c, use, build, deform))) return r;
     if ((r = sync_environment(c))) return r;
     r = finalise_scene(c);
     if (r == RTX_OK && c->scene.dev_built && c->scene.n_nodes8 && probe) {          // the visiting order of any-hit rays, probed on the device (the host probe replays its mirror of the tree)
@@ -496,11 +476,8 @@ int rtx_save_scene_cache(rtx_ctx* c, const char* path) {
     if (c->scene.host_mirror_stale) { c->err = "save_scene_cache: the per-triangle records were re-derived on the GPU after rtx_update_mesh_vertices and the host holds no current copy; commit with RTX_OPT_DEFORM_REBUILD 1 (host builder) to save a cache"; return RTX_ERR_STATE; }
     if (c->scene.built.any_hidden) { c->err = "save_scene_cache: an instance is hidden (rtx_set_instance_visible): the device's boxes and triangle records leave it out and the file format holds no visibility; show every instance and commit to save a cache"; return RTX_ERR_STATE; }
     if (c->host.env.n) { c->err = "save_scene_cache: an environment is bound (rtx_set_environment) and the file format holds no environment; clear it and commit to save a cache"; return RTX_ERR_STATE; }
-    if (c->host.any_emi_map()) { c->err = "save_scene_cache: a material has an emission map (rtx_set_material_map, RTX_MAP_KE) and the file format holds no texels; unmap every material and commit to save a cache"; return RTX_ERR_STATE; }
-    if (c->host.any_spec_map()) { c->err = "save_scene_cache: a material has a specular, roughness or metalness map (rtx_set_material_map, RTX_MAP_KS / RTX_MAP_PR / RTX_MAP_PM) and the file format holds no texels; unmap every material and commit to save a cache"; return RTX_ERR_STATE; }
-    if (c->host.any_normal_map()) { c->err = "save_scene_cache: a material has a normal map (rtx_set_material_map, RTX_MAP_NORMAL) and the file format holds no texels; unmap every material and commit to save a cache"; return RTX_ERR_STATE; }
-    if (c->host.any_opacity_map()) { c->err = "save_scene_cache: a material has an opacity map (rtx_set_material_map, RTX_MAP_OPACITY) and the file format holds no texels; unmap every material and commit to save a cache"; return RTX_ERR_STATE; }
-    if (c->host.any_map()) { c->err = "save_scene_cache: a material has a texture map (rtx_set_material_map) and the file format holds no texels; unmap every material and commit to save a cache"; return RTX_ERR_STATE; }
+    for (uint32_t s = 0; s < kMapSlotCount; s++)
+        if (c->host.any_bound((MapSlot)s)) { c->err = std::string("save_scene_cache: a material has a texture map (rtx_set_material_map, ") + kMapSlots[s].name + ") and the file format holds no texels; unmap every material and commit to save a cache"; return RTX_ERR_STATE; }
     if (c->scene.dev_built) { c->err = "save_scene_cache: the tree was built on the GPU (RTX_OPT_GPU_BUILD) and has no host mirror; commit with the host builder to save a cache"; return RTX_ERR_STATE; }
     if (!save_scene_cache(c->host, c->scene.built, path, c->err)) return RTX_ERR_INVALID;
     return RTX_OK;
@@ -514,7 +491,7 @@ int rtx_load_scene_cache(rtx_ctx* c, const char* path) {
     int r = upload_built(c);
     if (r) return r;
     c->host.tex_dirty = true;                  // (another scene: no textures, no maps)
-    if ((r = sync_textures(c, true, false))) return r;
+    if ((r = sync_textures(c, c->host.map_use(), true, false))) return r;
     c->host.env = EnvHost{}; c->host.env_dirty = true;      // (another scene: no environment)
     if ((r = sync_environment(c))) return r;
     return finalise_scene(c);
@@ -547,7 +524,8 @@ static int finalise_scene(rtx_ctx* c) {
     s.insts = (const InstGPU*)c->scene.d_insts.p; s.ninst = (uint32_t)B.insts.size();
     s.lights = (const LightGPU*)c->scene.d_lights.p; s.nlights = (uint32_t)B.lights.size(); s.cdf = (const float*)c->scene.d_cdf.p;
     s.total_weight = B.total_weight;
-    if (B.emi_active && !(B.total_weight > 0.0f)) s.nlights = 0;      // emission maps: every map black, no emitter has weight — the renderer has no light list (rtx_stats.lights and rtx_get_lights keep the count)
+    const MapUse use = B.map_use;
+    if (use.emi() && !(B.total_weight > 0.0f)) s.nlights = 0;     // emission maps: every map black, no emitter has weight — the renderer has no light list (rtx_stats.lights and rtx_get_lights keep the count)
     // texture maps: the sampler's tables whenever there are textures; UVs and map ids only while a map is active (then k_shade<.., TEX> runs, rtx_render.hip)
     s.tex_desc = (const TexDesc*)c->scene.d_tex_desc.p; s.ntex = c->scene.ntex; s.texels = (const uint32_t*)c->scene.d_texels.p; s.tex_lut = (const float*)c->scene.d_tex_lut.p;
     // environment lighting: env_n says one is bound (the separate default kernels run), env_tex that it has weight (k_shade<.., ENV> runs)
@@ -555,14 +533,14 @@ static int finalise_scene(rtx_ctx* c) {
     const bool env_lit = s.env_n && c->scene.env_total > 0.0;
     s.env_tex = env_lit ? (const F4*)c->scene.d_env_tex.p : nullptr; s.env_marg = env_lit ? (const float*)c->scene.d_env_marg.p : nullptr; s.env_cond = env_lit ? (const float*)c->scene.d_env_cond.p : nullptr;
     // (a scene with cut-outs and no diffuse map: k_shade<.., TEX> runs all the same, selected by tri_uv, and reads a map_kd table of -1s — every material keeps its own Kd)
-    const bool uv_active = B.maps_active || B.cutouts_active || B.normals_active || B.spec_active || B.emi_active;
-    s.tri_uv = uv_active ? (const float*)c->scene.d_tri_uv.p : nullptr; s.map_kd = uv_active ? (const int32_t*)c->scene.d_map_kd.p : nullptr;
-    s.tri_cut = B.cutouts_active ? (const int32_t*)c->scene.d_tri_cut.p : nullptr;
-    {   const int32_t* ms = B.spec_active ? (const int32_t*)c->scene.d_map_spec.p : nullptr; const size_t nm = c->host.mats128.size() / 32;
-        s.map_ks = ms; s.map_pr = ms ? ms + nm : nullptr; s.map_pm = ms ? ms + 2 * nm : nullptr;
-        s.ess_tab = (B.spec_active && c->host.ess_rows) ? (const float*)c->scene.d_ess_tab.p : nullptr; s.ess_rows = s.ess_tab ? c->host.ess_rows : 0u; }
-    s.map_ke = B.emi_active ? (const int32_t*)c->scene.d_map_ke.p : nullptr; s.emi_q = B.emi_active ? (const float*)c->scene.d_emi_q.p : nullptr;
-    s.tri_tan = B.normals_active ? (const float*)c->scene.d_tri_tan.p : nullptr; s.map_nrm = B.normals_active ? (const int32_t*)c->scene.d_map_nrm.p : nullptr;
+    // the per-material id rows: null unless the slot's group is active, except that map_kd is set whenever any group is
+    const rtx_ctx::Scene& S = c->scene;
+    s.tri_uv = use.any() ? (const float*)S.d_tri_uv.p : nullptr; s.map_kd = use.any() ? S.mat_maps(kMapKd) : nullptr;
+    s.tri_cut = use.cut() ? (const int32_t*)S.d_tri_cut.p : nullptr;
+    s.map_ks = use.spc() ? S.mat_maps(kMapKs) : nullptr; s.map_pr = use.spc() ? S.mat_maps(kMapPr) : nullptr; s.map_pm = use.spc() ? S.mat_maps(kMapPm) : nullptr;
+    s.ess_tab = (use.spc() && c->host.ess_rows) ? (const float*)S.d_ess_tab.p : nullptr; s.ess_rows = s.ess_tab ? c->host.ess_rows : 0u;
+    s.map_ke = use.emi() ? S.mat_maps(kMapKe) : nullptr; s.emi_q = use.emi() ? (const float*)S.d_emi_q.p : nullptr;
+    s.tri_tan = use.nrm() ? (const float*)S.d_tri_tan.p : nullptr; s.map_nrm = use.nrm() ? S.mat_maps(kMapNormal) : nullptr;
     // LDS budget per workgroup: stack + top of tree + first triangles, kept <= 64 KiB
     // exact bound of the 8-wide tree, no slack: a level adds ONE entry (the rest of its hit siblings) and only where a node has >= 2 internal
     // children (collapse_bvh8: need[]); a pop precedes every descent from an exhausted group.  Each entry costs 1.5 KB of LDS per workgroup (6 B per lane: kStackEntryBytes), and

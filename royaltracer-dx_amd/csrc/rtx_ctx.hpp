@@ -6,9 +6,9 @@
 //   rtx_adaptive.hip     rtx_render_adaptive: passes of render_frame over the chunks that have not converged
 //   rtx_denoise.hip      rtx_denoise, rtx_denoise_variance and the reads of the denoised image
 //   rtx_env.hip          environment lighting: rtx_set_environment and its three debug probes
-//   rtx_texture.hip      texture maps: rtx_set_mesh_uvs, rtx_set_texture, rtx_set_material_map and their two debug probes
+//   rtx_texture.hip      texture maps: rtx_set_mesh_uvs, rtx_set_texture, rtx_set_material_map, rtx_set_ess_table and the sampler's debug probe
 //   rtx_restir_api.hip   the ReSTIR frames, their work lists and lanes, the history / halo exchange between shards
-//   rtx_debug.hip        the rtx_debug_* entry points
+//   rtx_debug.hip        the rtx_debug_* entry points, the per-hit probes of the map slots among them (hit_probe)
 // Ownership: every resource of a context is a member of an owning type (rtx_devmem.hpp, rtx_staging.hpp), so `delete c` releases it all.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -122,19 +122,18 @@ struct rtx_ctx {
         DevBuf d_nodes_wide; bool wide_nodes = false;    // the copy with one node per 128-B line (RTX_OPT_NODE_STRIDE)
         uint32_t lds_nodes_closest = 0;                  // staged nodes of the closest-hit launches (pick_lds_closest)
         DevBuf d_stack_ovf;                              // the traversal stack's overflow columns of deeper trees (RTX_OPT_STACK_CAP)
-        // diffuse texture maps (sync_textures, rtx_commit.hip): descriptors, the texel pool and the per-material map ids follow the host's tables at every commit that
-        // changed them; the two byte -> float tables once; tri_uv only while a map is active (BuiltScene::maps_active), rebuilt when UVs or the triangle numbering changed
-        // (or a cut-out is: BuiltScene::cutouts_active), rebuilt when UVs or the triangle numbering changed; tri_cut only while a cut-out is active, rebuilt with it
-        DevBuf d_tri_uv, d_map_kd, d_tex_desc, d_texels, d_tex_lut; bool tri_uv_valid = false; uint32_t ntex = 0;
-        DevBuf d_tri_cut; bool tri_cut_valid = false;
-        // tangent-space normal maps: the per-material map ids with the other tables; tri_tan only while a normal map is active (BuiltScene::normals_active), rebuilt when UVs, the
-        // triangle numbering or a mesh's vertices changed (object space: a transform-only commit leaves it alone)
-        DevBuf d_tri_tan, d_map_nrm; bool tri_tan_valid = false;
-        // specular, roughness and metalness maps: the three per-material map tables back to back (ks | pr | pm, nmat entries each) and the energy table of rtx_set_ess_table,
-        // both with the other tables and only while the host holds a map resp. a table
-        DevBuf d_map_spec, d_ess_tab;
-        // emission maps: the per-material map ids with the other tables, only while the host holds one; q per global triangle id with the light list, only while one is active
-        DevBuf d_map_ke, d_emi_q;
+        // texture maps (sync_textures, rtx_commit.hip): descriptors, the texel pool and the per-material map ids follow the host's tables at every commit that changed them;
+        // the byte -> float tables once.  d_mat_maps: ONE int32 table, a row of mat_maps_nmat entries per slot the kernels read by material (every MapSlot but the opacity
+        // slot, whose ids are per triangle: d_tri_cut), -1 = no map; finalise_scene points DevScene::map_* at its rows.  The energy table of rtx_set_ess_table only while the
+        // host holds one
+        DevBuf d_tex_desc, d_texels, d_tex_lut, d_mat_maps, d_ess_tab; uint32_t ntex = 0; size_t mat_maps_nmat = 0;
+        static constexpr uint32_t kMatMapRows = kMapSlotCount - 1;
+        static uint32_t mat_map_row(MapSlot s) { return s < kMapOpacity ? s : s - 1u; }
+        const int32_t* mat_maps(MapSlot s) const { return d_mat_maps.p ? (const int32_t*)d_mat_maps.p + mat_map_row(s) * mat_maps_nmat : nullptr; }
+        // the per-triangle tables, by GLOBAL triangle id: tri_uv while any map group is active (BuiltScene::map_use), rebuilt when UVs or the triangle numbering changed;
+        // tri_cut while a cut-out is active, rebuilt with it; tri_tan while a normal map is active, rebuilt when UVs, the triangle numbering or a mesh's vertices changed
+        // (object space: a transform-only commit leaves it alone); q of the emission maps with the light list, while one is active
+        DevBuf d_tri_uv, d_tri_cut, d_tri_tan, d_emi_q; bool tri_uv_valid = false, tri_cut_valid = false, tri_tan_valid = false;
         DevBuf d_lights_plain, d_cdf_plain; std::vector<float> h_cdf_plain;      // ... and the unmapped scene's light list, for the renderers that ignore the maps (plain_scene())
         // environment lighting (sync_environment, rtx_commit.hip): the tables of the bound map, rebuilt by the commit after rtx_set_environment; env_total = their weight sum
         DevBuf d_env_tex, d_env_marg, d_env_cond; double env_total = 0.0;
@@ -143,7 +142,7 @@ struct rtx_ctx {
     // light list of the unmapped scene and no emission tables; otherwise dsc as it is
     DevScene plain_scene() const {
         DevScene s = dsc;
-        if (scene.built.emi_active) {
+        if (scene.built.map_use.emi()) {
             s.lights = (const LightGPU*)scene.d_lights_plain.p; s.cdf = (const float*)scene.d_cdf_plain.p; s.nlights = (uint32_t)scene.built.lights_plain.size();
             s.total_weight = scene.built.total_weight_plain; s.map_ke = nullptr; s.emi_q = nullptr;
         }

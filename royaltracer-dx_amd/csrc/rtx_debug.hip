@@ -2,6 +2,30 @@
 // build times, work counters.  Tooling and tests; no frame goes through here (rtx_ctx.hpp).
 #include "rtx_ctx.hpp"
 
+// The body the per-hit probes of the map slots share: n hit records as rtx_debug_trace_closest writes them (and, for a probe that takes them, the n rays behind them) go to the
+// device, launch(rays, hits, out) runs the probe's kernel, out_item bytes per record come back.  Checked in this order: committed, n == 0, null arrays ("<name>: null array"),
+// triangle ids ("<name>: triangle id out of range": an id the scene does not have would index past the per-triangle tables)
+template <class Launch>
+static int hit_probe(rtx_ctx* c, const char* name, bool takes_rays, const float* rays8, const float* hits4, uint32_t n, void* out, size_t out_item, Launch launch) {
+    BIND(c);
+    if (!c->committed) { c->err = "scene not committed"; return RTX_ERR_STATE; }
+    if (!n) return RTX_OK;
+    if ((takes_rays && !rays8) || !hits4 || !out) { c->err = std::string(name) + ": null array"; return RTX_ERR_INVALID; }
+    for (uint32_t i = 0; i < n; i++) {
+        uint32_t prim; memcpy(&prim, &hits4[(size_t)i * 4 + 3], 4);
+        if (prim != kMissPrim && prim >= c->stats.triangles) { c->err = std::string(name) + ": triangle id out of range"; return RTX_ERR_INVALID; }
+    }
+    DevBuf d_rays, d_hits, d_out;
+    if (takes_rays) { HIPCHK(c, d_rays.ensure((size_t)n * 32)); TO_DEVICE(c, d_rays.p, rays8, (size_t)n * 32); }
+    HIPCHK(c, d_hits.ensure((size_t)n * 16)); HIPCHK(c, d_out.ensure((size_t)n * out_item));
+    TO_DEVICE(c, d_hits.p, hits4, (size_t)n * 16);
+    launch((const F4*)d_rays.p, (const F4*)d_hits.p, d_out.p);
+    HIPCHK(c, hipGetLastError());
+    TO_HOST(c, out, d_out.p, (size_t)n * out_item);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RTX_OK;
+}
+
 extern "C" {
 
 int rtx_debug_primary_rays(rtx_ctx* c, const rtx_params* p, uint32_t sample_id, float* rays8) {
@@ -174,23 +198,17 @@ int rtx_debug_surface(rtx_ctx* c, const float* rays8, const float* hits4, uint32
 }
 // the shading normal under the normal maps (rtx_normalmap.hpp), by the device functions k_shade<.., NRM> runs for a lane that shades
 int rtx_debug_shading_normal(rtx_ctx* c, const float* rays8, const float* hits4, uint32_t n, float* out4) {
-    BIND(c);
-    if (!c->committed) { c->err = "scene not committed"; return RTX_ERR_STATE; }
-    if (!n) return RTX_OK;
-    if (!rays8 || !hits4 || !out4) { c->err = "shading_normal: null array"; return RTX_ERR_INVALID; }
-    for (uint32_t i = 0; i < n; i++) {                       // a triangle id the scene does not have would index past the per-triangle tables
-        uint32_t prim; memcpy(&prim, &hits4[(size_t)i * 4 + 3], 4);
-        if (prim != kMissPrim && prim >= c->stats.triangles) { c->err = "shading_normal: triangle id out of range"; return RTX_ERR_INVALID; }
-    }
-    DevBuf d_rays, d_hits, d_out;
-    HIPCHK(c, d_rays.ensure((size_t)n * 32)); HIPCHK(c, d_hits.ensure((size_t)n * 16)); HIPCHK(c, d_out.ensure((size_t)n * 16));
-    TO_DEVICE(c, d_rays.p, rays8, (size_t)n * 32);
-    TO_DEVICE(c, d_hits.p, hits4, (size_t)n * 16);
-    launch_dbg_shading_normal(c->stream, c->dsc, (const F4*)d_rays.p, (const F4*)d_hits.p, n, (F4*)d_out.p);
-    HIPCHK(c, hipGetLastError());
-    TO_HOST(c, out4, d_out.p, (size_t)n * 16);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return RTX_OK;
+    return hit_probe(c, "shading_normal", true, rays8, hits4, n, out4, 16, [&](const F4* rays, const F4* hits, void* out) { launch_dbg_shading_normal(c->stream, c->dsc, rays, hits, n, (F4*)out); });
+}
+// the per-hit diffuse colour under the diffuse maps (rtx_texture.hpp).  rays8 is taken for symmetry with rtx_debug_surface; the albedo depends on the hit record alone
+// (triangle id and barycentrics)
+int rtx_debug_albedo(rtx_ctx* c, const float* rays8, const float* hits4, uint32_t n, float* out4) {
+    (void)rays8;
+    return hit_probe(c, "albedo", false, nullptr, hits4, n, out4, 16, [&](const F4*, const F4* hits, void* out) { launch_dbg_albedo(c->stream, c->dsc, hits, n, (F4*)out); });
+}
+// (alpha as the traversal computes it, opacity texture id as uint bits): cut_alpha of rtx_cutout.hpp, the function cut_accept compares
+int rtx_debug_opacity(rtx_ctx* c, const float* hits4, uint32_t n, float* out2) {
+    return hit_probe(c, "opacity", false, nullptr, hits4, n, out2, 8, [&](const F4*, const F4* hits, void* out) { launch_dbg_opacity(c->stream, c->dsc, hits, n, (float*)out); });
 }
 int rtx_debug_tri_tangents(rtx_ctx* c, uint32_t first, uint32_t count, float* out6) {
     BIND(c);
@@ -205,22 +223,7 @@ int rtx_debug_tri_tangents(rtx_ctx* c, uint32_t first, uint32_t count, float* ou
 }
 // Ks', Pr', Pm' under the specular maps (rtx_specmap.hpp), by the device function k_shade<.., SPC> runs for a lane that shades
 int rtx_debug_specular(rtx_ctx* c, const float* hits4, uint32_t n, float* out8) {
-    BIND(c);
-    if (!c->committed) { c->err = "scene not committed"; return RTX_ERR_STATE; }
-    if (!n) return RTX_OK;
-    if (!hits4 || !out8) { c->err = "specular: null array"; return RTX_ERR_INVALID; }
-    for (uint32_t i = 0; i < n; i++) {                       // a triangle id the scene does not have would index past the per-triangle tables
-        uint32_t prim; memcpy(&prim, &hits4[(size_t)i * 4 + 3], 4);
-        if (prim != kMissPrim && prim >= c->stats.triangles) { c->err = "specular: triangle id out of range"; return RTX_ERR_INVALID; }
-    }
-    DevBuf d_hits, d_out;
-    HIPCHK(c, d_hits.ensure((size_t)n * 16)); HIPCHK(c, d_out.ensure((size_t)n * 32));
-    TO_DEVICE(c, d_hits.p, hits4, (size_t)n * 16);
-    launch_dbg_specular(c->stream, c->dsc, (const F4*)d_hits.p, n, (float*)d_out.p);
-    HIPCHK(c, hipGetLastError());
-    TO_HOST(c, out8, d_out.p, (size_t)n * 32);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return RTX_OK;
+    return hit_probe(c, "specular", false, nullptr, hits4, n, out8, 32, [&](const F4*, const F4* hits, void* out) { launch_dbg_specular(c->stream, c->dsc, hits, n, (float*)out); });
 }
 // the Ess the view terms take for `material` at n (Pr', NdotV) pairs: the energy table where the material has a roughness map and a table is set, else its own LUT
 int rtx_debug_ess(rtx_ctx* c, uint32_t material, const float* pr, const float* ndotv, uint32_t n, float* out) {
@@ -241,22 +244,7 @@ int rtx_debug_ess(rtx_ctx* c, uint32_t material, const float* pr, const float* n
 }
 // Ke' and q under the emission maps (rtx_emimap.hpp), by the device function k_shade<.., EMI> runs for a lane that hits an emitter
 int rtx_debug_emission(rtx_ctx* c, const float* hits4, uint32_t n, float* out8) {
-    BIND(c);
-    if (!c->committed) { c->err = "scene not committed"; return RTX_ERR_STATE; }
-    if (!n) return RTX_OK;
-    if (!hits4 || !out8) { c->err = "emission: null array"; return RTX_ERR_INVALID; }
-    for (uint32_t i = 0; i < n; i++) {                       // a triangle id the scene does not have would index past the per-triangle tables
-        uint32_t prim; memcpy(&prim, &hits4[(size_t)i * 4 + 3], 4);
-        if (prim != kMissPrim && prim >= c->stats.triangles) { c->err = "emission: triangle id out of range"; return RTX_ERR_INVALID; }
-    }
-    DevBuf d_hits, d_out;
-    HIPCHK(c, d_hits.ensure((size_t)n * 16)); HIPCHK(c, d_out.ensure((size_t)n * 32));
-    TO_DEVICE(c, d_hits.p, hits4, (size_t)n * 16);
-    launch_dbg_emission(c->stream, c->dsc, (const F4*)d_hits.p, n, (float*)d_out.p);
-    HIPCHK(c, hipGetLastError());
-    TO_HOST(c, out8, d_out.p, (size_t)n * 32);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return RTX_OK;
+    return hit_probe(c, "emission", false, nullptr, hits4, n, out8, 32, [&](const F4*, const F4* hits, void* out) { launch_dbg_emission(c->stream, c->dsc, hits, n, (float*)out); });
 }
 // the first half of a triangle-light NEE sample with the texel of the emission maps, by the device functions nee_sample runs
 int rtx_debug_light_sample(rtx_ctx* c, const uint32_t* seeds2, uint32_t n, float* out12) {

@@ -73,8 +73,10 @@ bool SceneHost::set_materials(const void* mats, uint32_t count) {
     if (!mats && count) { err = "materials pointer is null"; return false; }
     mats128.assign((const float*)mats, (const float*)mats + (size_t)count * 32);
     mats_dirty = true;
-    if (any_map()) tex_dirty = true;
-    map_kd.clear(); map_opacity.clear(); map_normal.clear(); map_ke.clear(); for (std::vector<int32_t>& v : map_spec) v.clear();        // the table is replaced: no material of the new one has a map (the energy table is no material's: it stays)
+    for (uint32_t s = 0; s < kMapSlotCount; s++) {           // the table is replaced: no material of the new one has a map (the energy table is no material's: it stays)
+        if (any_bound((MapSlot)s)) tex_dirty = true;
+        maps[s].clear();
+    }
     return true;
 }
 
@@ -165,9 +167,10 @@ bool SceneHost::set_texture(uint32_t tex, const void* rgba8, uint32_t width, uin
 }
 bool SceneHost::set_material_map(uint32_t material, uint32_t slot, int32_t tex) {
     if (material >= mats128.size() / 32) { err = "set_material_map: unknown material"; return false; }
-    if (slot > 12u || (slot & 1u)) { err = "set_material_map: unknown slot (RTX_MAP_KD = 0, RTX_MAP_OPACITY = 2, RTX_MAP_NORMAL = 4, RTX_MAP_KS = 6, RTX_MAP_PR = 8, RTX_MAP_PM = 10 or RTX_MAP_KE = 12)"; return false; }
+    const uint32_t s = map_slot_of(slot);
+    if (s == kMapSlotCount) { err = "set_material_map: unknown slot (RTX_MAP_KD = 0, RTX_MAP_OPACITY = 2, RTX_MAP_NORMAL = 4, RTX_MAP_KS = 6, RTX_MAP_PR = 8, RTX_MAP_PM = 10 or RTX_MAP_KE = 12)"; return false; }
     if (tex < -1 || (tex >= 0 && (size_t)tex >= textures.size())) { err = "set_material_map: unknown texture"; return false; }
-    std::vector<int32_t>& map = slot == 12u ? map_ke : slot >= 6u ? map_spec[(slot - 6u) / 2u] : slot == 4u ? map_normal : slot == 2u ? map_opacity : map_kd;
+    std::vector<int32_t>& map = maps[s];
     if (map.size() < mats128.size() / 32) map.resize(mats128.size() / 32, -1);
     map[material] = tex;
     tex_dirty = true;
@@ -180,42 +183,24 @@ bool SceneHost::set_ess_table(const float* table, uint32_t rows) {
     tex_dirty = true;
     return true;
 }
-bool SceneHost::spec_active() const {
-    if (!any_spec_map()) return false;
-    for (size_t i = 0; i < matids.size(); i += 3) {
-        const uint32_t mat = matids[i];
-        if (mat >= mats128.size() / 32 || material_emits(mat)) continue;
-        for (const std::vector<int32_t>& v : map_spec) if (mat < v.size() && v[mat] >= 0) return true;
-    }
-    return false;
-}
-bool SceneHost::emi_active() const {
-    if (!any_emi_map()) return false;
-    for (size_t i = 0; i < matids.size(); i += 3) if (emi_texture(matids[i]) >= 0) return true;
-    return false;
-}
-bool SceneHost::maps_active() const {
-    if (!any_map()) return false;
-    for (size_t i = 0; i < matids.size(); i += 3) if (matids[i] < map_kd.size() && map_kd[matids[i]] >= 0) return true;      // (a triangle's material is the id of its first index entry: flatten_range)
-    return false;
-}
-bool SceneHost::cutouts_active() const {
-    if (!any_opacity_map()) return false;
-    for (size_t i = 0; i < matids.size(); i += 3) if (cut_texture(matids[i]) >= 0) return true;
-    return false;
+MapUse SceneHost::map_use() const {
+    // per material the groups a triangle of it activates, and their union: what a triangle can still add (most scenes bind nothing, and no triangle is looked at)
+    std::vector<uint8_t> of_mat(mats128.size() / 32, 0);
+    MapUse reachable, use;
+    for (uint32_t s = 0; s < kMapSlotCount; s++)
+        for (size_t mat = 0; mat < maps[s].size() && mat < of_mat.size(); mat++)
+            if (bound_texture((MapSlot)s, (uint32_t)mat) >= 0) { of_mat[mat] |= (uint8_t)(1u << kMapSlots[s].group); reachable.groups |= of_mat[mat]; }
+    for (size_t i = 0; i < matids.size() && use != reachable; i += 3)      // (a triangle's material is the id of its first index entry: flatten_range)
+        if (matids[i] < of_mat.size()) use.groups |= of_mat[matids[i]];
+    return use;
 }
 void SceneHost::fill_tri_cut(std::vector<int32_t>& out) const {
     size_t nt = 0; for (const InstHost& in : insts) nt += meshes[in.mesh].idx.size() / 3;
     out.assign(nt, -1);
     for (const InstHost& in : insts) {
         const MeshHost& m = meshes[in.mesh];
-        for (size_t t = 0; t < m.idx.size() / 3; t++) out[(size_t)in.tri_base + t] = cut_texture(matids[m.matid_base + 3 * t]);
+        for (size_t t = 0; t < m.idx.size() / 3; t++) out[(size_t)in.tri_base + t] = bound_texture(kMapOpacity, matids[m.matid_base + 3 * t]);
     }
-}
-bool SceneHost::normals_active() const {
-    if (!any_normal_map()) return false;
-    for (size_t i = 0; i < matids.size(); i += 3) { const uint32_t mat = matids[i]; if (mat < map_normal.size() && map_normal[mat] >= 0 && mat < mats128.size() / 32 && !material_emits(mat)) return true; }
-    return false;
 }
 void SceneHost::fill_tri_tan(std::vector<float>& out) const {
     size_t nt = 0; for (const InstHost& in : insts) nt += meshes[in.mesh].idx.size() / 3;
@@ -266,7 +251,7 @@ void SceneHost::build_lights(BuiltScene& B) const {
     // ---- emissive triangle list + CDF: Renderer.cpp:2123-2233, 2237-2243 ----
     // EMISSION MAPS (include/rtx.h): while one is active the weight of a mapped emitter triangle follows the mean of its texels (rtx_emimap_host.hpp), every light carries
     // its global triangle id and emission texture, and q per global triangle id is what the emissive hit's MIS pdf reads.  Inactive: the scan as it always was, nothing more
-    const bool emi = emi_active();
+    const bool emi = map_use().emi();
     B.emi_q.clear(); B.light_emi.clear();
     if (emi) { size_t nt = 0; for (const InstHost& in : insts) nt += meshes[in.mesh].idx.size() / 3; B.emi_q.assign(nt, 0.0f); }
     const float zero_uv[6] = {0, 0, 0, 0, 0, 0};
@@ -284,7 +269,7 @@ void SceneHost::build_lights(BuiltScene& B) const {
             int32_t tex = -1;
             if (emi && (mat[8] + mat[9] + mat[10] > 0.0f)) {          // (a hit reads the material of the first index entry: q is filled before the scan's own filters)
                 float E[3] = {mat[8], mat[9], mat[10]};
-                tex = emi_texture(m0);
+                tex = bound_texture(kMapKe, m0);
                 if (tex >= 0) {
                     const TexHost& T = textures[tex];
                     float mean[3];
@@ -385,7 +370,7 @@ bool SceneHost::refresh_transforms(BuiltScene& B) {
     commit_visibility(B);
     // new materials can change WHICH triangles emit, new vertices of an emitting mesh their areas, hence weights and order, a hidden or shown emitter the list itself: full scan
     // ... and so do new UVs, texels or map ids while an emission map is active, or was at the last commit: the weights follow the texels
-    if (mats_changed || dirty_mesh_emits() || emitter_flipped || (tex_dirty && (B.emi_active || emi_active()))) build_lights(B); else refresh_lights(B);
+    if (mats_changed || dirty_mesh_emits() || emitter_flipped || (tex_dirty && (B.map_use.emi() || map_use().emi()))) build_lights(B); else refresh_lights(B);
     B.refit_count++;
     return true;
 }
@@ -542,8 +527,8 @@ bool SceneHost::build(BuiltScene& B) {
     // ... and one with an active normal map (k_bounce_small perturbs no normal)
     // ... and one with an active specular, roughness or metalness map (k_bounce_small reads the material table alone)
     // ... and one with an active emission map (k_bounce_small's emitters and light samples read no texel)
-    B.maps_active = maps_active(); B.cutouts_active = cutouts_active(); B.normals_active = normals_active(); B.spec_active = spec_active(); B.emi_active = emi_active(); B.env_active = env.n != 0;
-    if (B.any_hidden || B.maps_active || B.cutouts_active || B.normals_active || B.spec_active || B.emi_active || B.env_active) { B.small_recs.clear(); B.small_tris.clear(); B.small_poly.clear(); B.small_slabs.clear(); B.small_excess.clear(); B.small_slab_mask = 0; B.small_nrec = 0; B.small_nocc = 0; }
+    B.map_use = map_use(); B.env_active = env.n != 0;
+    if (B.any_hidden || B.map_use.any() || B.env_active) { B.small_recs.clear(); B.small_tris.clear(); B.small_poly.clear(); B.small_slabs.clear(); B.small_excess.clear(); B.small_slab_mask = 0; B.small_nrec = 0; B.small_nocc = 0; }
     else build_small_scene(B, wtri, scale);
     sw.lap("tris8 / small scene");
     B.any_order = probe_anyhit_order(B);

@@ -8,6 +8,7 @@
 #include "rtx_types.hpp"
 #include "rtx_bvh_host.hpp"
 #include "rtx_env_host.hpp"
+#include "rtx_map_slots.hpp"
 
 namespace rtx {
 
@@ -50,13 +51,9 @@ struct BuiltScene {
     uint32_t refit_count = 0;           // commits since the last full build that only refitted the boxes
     std::vector<uint32_t> inst_hidden;  // one word per instance, non-zero = hidden, AS COMMITTED: what the resident tree's boxes, the never-hit triangle records and the light list reflect (the refit kernels read it)
     bool any_hidden = false;            // ... and whether any word of it is set
-    bool maps_active = false;           // SceneHost::maps_active() AS COMMITTED: a tiny scene then runs on the general path, DevScene::tri_uv / map_kd are set
-    bool cutouts_active = false;        // SceneHost::cutouts_active() AS COMMITTED: a tiny scene then runs on the general path, DevScene::tri_cut (and tri_uv / map_kd) are set
-    bool normals_active = false;        // SceneHost::normals_active() AS COMMITTED: a tiny scene then runs on the general path, DevScene::tri_tan / map_nrm (and tri_uv / map_kd) are set
-    bool spec_active = false;           // SceneHost::spec_active() AS COMMITTED: a tiny scene then runs on the general path, DevScene::map_ks / map_pr / map_pm (and tri_uv / map_kd) are set
+    MapUse map_use;                     // SceneHost::map_use() AS COMMITTED: while any() a tiny scene runs on the general path and DevScene::tri_uv / map_kd are set; per group, the DevScene members rtx_map_slots.hpp names
     bool env_active = false;            // an environment is bound (SceneHost::env.n != 0) AS COMMITTED: a tiny scene then runs on the general path
     // emission maps (include/rtx.h, EMISSION MAPS; rtx_emimap_host.hpp)
-    bool emi_active = false;            // SceneHost::emi_active() AS COMMITTED: a tiny scene then runs on the general path, DevScene::map_ke / emi_q (and tri_uv / map_kd) are set
     std::vector<float> emi_q;           // build_lights while an emission map is active: q per GLOBAL triangle id (what the emissive hit's MIS pdf reads); else empty
     std::vector<uint32_t> light_emi;    // ... and per light of `lights`, in its order: global triangle id, emission texture id bits (0xFFFFFFFF = none); else empty
     std::vector<LightGPU> lights_plain; std::vector<float> lights80_plain; float total_weight_plain = 0.0f;      // ... and the list of the UNMAPPED scene, which rtx_render_v6_pass1 and rtx_render_restir keep sampling; else empty
@@ -75,11 +72,7 @@ struct SceneHost {
     std::vector<uint8_t> inst_hidden;           // rtx_set_instance_visible: 1 = hidden, as the caller wants it from the next commit on; shorter than insts = the rest is visible (every instance starts visible)
     // diffuse texture maps (include/rtx.h: rtx_set_mesh_uvs, rtx_set_texture, rtx_set_material_map)
     std::vector<TexHost> textures;
-    std::vector<int32_t> map_kd;                // per material: texture id of RTX_MAP_KD or -1; shorter than the table = the rest has none (rtx_set_materials empties it)
-    std::vector<int32_t> map_opacity;           // ... of RTX_MAP_OPACITY (alpha cut-outs), likewise
-    std::vector<int32_t> map_normal;            // ... of RTX_MAP_NORMAL (tangent-space normal maps), likewise
-    std::vector<int32_t> map_spec[3];           // ... of RTX_MAP_KS, RTX_MAP_PR, RTX_MAP_PM (specular, roughness and metalness maps), likewise
-    std::vector<int32_t> map_ke;                // ... of RTX_MAP_KE (emission maps), likewise
+    std::vector<int32_t> maps[kMapSlotCount];   // per slot (rtx_map_slots.hpp), per material: the texture id bound or -1; shorter than the table = the rest has none (rtx_set_materials empties them all)
     std::vector<float> ess_table; uint32_t ess_rows = 0;        // rtx_set_ess_table: rows x 16 floats, or empty / 0 (a table edit like the maps: tex_dirty; rtx_set_materials keeps it)
     bool tex_dirty = false;                     // one of the four setters (UVs, texture, material map, energy table) since the last commit
     // environment lighting (include/rtx.h: rtx_set_environment; rtx_env_host.hpp)
@@ -105,23 +98,18 @@ struct SceneHost {
     bool set_mesh_uvs(uint32_t mesh, const float* uv2, uint32_t nidx);
     bool set_texture(uint32_t tex, const void* rgba8, uint32_t width, uint32_t height, uint32_t flags);
     bool set_material_map(uint32_t material, uint32_t slot, int32_t tex);
-    bool any_opacity_map() const { for (int32_t t : map_opacity) if (t >= 0) return true; return false; }
-    bool any_normal_map() const { for (int32_t t : map_normal) if (t >= 0) return true; return false; }
-    bool any_spec_map() const { for (const std::vector<int32_t>& v : map_spec) for (int32_t t : v) if (t >= 0) return true; return false; }
-    bool any_emi_map() const { for (int32_t t : map_ke) if (t >= 0) return true; return false; }
-    bool any_map() const { for (int32_t t : map_kd) if (t >= 0) return true; return any_opacity_map() || any_normal_map() || any_spec_map() || any_emi_map(); }
-    // the emission texture of a triangle whose material (the id of its first index entry) is `mat`, or -1: the material has RTX_MAP_KE and emits
-    int32_t emi_texture(uint32_t mat) const { return mat < map_ke.size() && map_ke[mat] >= 0 && mat < mats128.size() / 32 && material_emits(mat) ? map_ke[mat] : -1; }
-    bool emi_active() const;                    // an emitting material that some triangle uses has an emission map
+    bool any_bound(MapSlot slot) const { for (int32_t t : maps[slot]) if (t >= 0) return true; return false; }
+    // the texture that slot `slot` gives a triangle whose material (the id of its first index entry) is `mat`, or -1: the material has the map AND the slot's rule (kMapSlots) lets it
+    // act there — an emitter's opacity, normal and specular maps have no effect (opacity: what is left are the CUT-OUT TRIANGLES), an emission map acts on an emitter only
+    int32_t bound_texture(MapSlot slot, uint32_t mat) const {
+        if (mat >= maps[slot].size() || maps[slot][mat] < 0 || mat >= mats128.size() / 32) return -1;
+        const MapRule rule = kMapSlots[slot].rule;
+        return rule == kMapAnyMaterial || material_emits(mat) == (rule == kMapOnlyOnEmitter) ? maps[slot][mat] : -1;
+    }
+    MapUse map_use() const;                     // which groups are active: a material that some triangle uses has a map of the group whose rule lets it act (one pass over the triangles)
     bool set_ess_table(const float* table, uint32_t rows);
-    bool spec_active() const;                   // a non-emitting material that some triangle uses has a specular, roughness or metalness map
-    bool maps_active() const;                   // a material that some triangle uses has a diffuse map
     bool material_emits(uint32_t mat) const { const float* m = &mats128[(size_t)mat * 32]; return m[8] > 0.0f || m[9] > 0.0f || m[10] > 0.0f; }      // a component of Ke is > 0
-    // the opacity texture of a triangle whose material (the id of its first index entry) is `mat`, or -1: the material has RTX_MAP_OPACITY and does not emit (a CUT-OUT TRIANGLE)
-    int32_t cut_texture(uint32_t mat) const { return mat < map_opacity.size() && map_opacity[mat] >= 0 && mat < mats128.size() / 32 && !material_emits(mat) ? map_opacity[mat] : -1; }
-    bool cutouts_active() const;                // some triangle is a cut-out triangle
-    void fill_tri_cut(std::vector<int32_t>& out) const;     // cut_texture per global triangle id (numbered like fill_tri_uv)
-    bool normals_active() const;                // a non-emitting material that some triangle uses has a normal map
+    void fill_tri_cut(std::vector<int32_t>& out) const;     // bound_texture(kMapOpacity, ..) per global triangle id (numbered like fill_tri_uv)
     void fill_tri_tan(std::vector<float>& out) const;       // the tangent record (rtx_normalmap_host.hpp) per global triangle id (numbered like fill_tri_uv), from the meshes' current object-space vertices
     bool only_maps_changed(const BuiltScene& b) const;      // against the committed scene b: no instance moved, was hidden or shown, no mesh got new vertices, same topology and material table
     void fill_tri_uv(std::vector<float>& out) const;        // 6 floats per global triangle id (InstHost::tri_base as the last geometry-changing commit numbered them)

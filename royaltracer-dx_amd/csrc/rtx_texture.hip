@@ -1,5 +1,5 @@
-// rtx_texture.hip — diffuse texture maps at the C-ABI of include/rtx.h: per-corner UVs, the texture table, the per-material map slot, and the two probes that run the device's
-// sampler and per-hit albedo for the tests.  Host code only: the setters change SceneHost and un-commit the scene; rtx_commit_scene uploads the tables (sync_textures,
+// rtx_texture.hip — diffuse texture maps at the C-ABI of include/rtx.h: per-corner UVs, the texture table, the per-material map slots, and the probe that runs the device's
+// sampler for the tests (the per-hit probes of the slots are in rtx_debug.hip).  Host code only: the setters change SceneHost and un-commit the scene; rtx_commit_scene uploads the tables (sync_textures,
 // rtx_commit.hip); the device functions are rtx_texture.hpp (rtx_ctx.hpp).
 #include "rtx_ctx.hpp"
 
@@ -39,46 +39,6 @@ int rtx_debug_texture_sample(rtx_ctx* c, uint32_t tex, const float* uv2, uint32_
     launch_dbg_tex_sample(c->stream, c->dsc, tex, (const float*)d_uv.p, n, (F4*)d_out.p);
     HIPCHK(c, hipGetLastError());
     TO_HOST(c, out4, d_out.p, (size_t)n * 16);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return RTX_OK;
-}
-// rays8 is taken for symmetry with rtx_debug_surface; the albedo depends on the hit record alone (triangle id and barycentrics)
-int rtx_debug_albedo(rtx_ctx* c, const float* rays8, const float* hits4, uint32_t n, float* out4) {
-    BIND(c);
-    (void)rays8;
-    if (!c->committed) { c->err = "scene not committed"; return RTX_ERR_STATE; }
-    if (!n) return RTX_OK;
-    if (!hits4 || !out4) { c->err = "albedo: null array"; return RTX_ERR_INVALID; }
-    for (uint32_t i = 0; i < n; i++) {                       // a triangle id the scene does not have would index past the per-triangle tables
-        uint32_t prim; memcpy(&prim, &hits4[(size_t)i * 4 + 3], 4);
-        if (prim != kMissPrim && prim >= c->stats.triangles) { c->err = "albedo: triangle id out of range"; return RTX_ERR_INVALID; }
-    }
-    DevBuf d_hits, d_out;
-    HIPCHK(c, d_hits.ensure((size_t)n * 16)); HIPCHK(c, d_out.ensure((size_t)n * 16));
-    TO_DEVICE(c, d_hits.p, hits4, (size_t)n * 16);
-    launch_dbg_albedo(c->stream, c->dsc, (const F4*)d_hits.p, n, (F4*)d_out.p);
-    HIPCHK(c, hipGetLastError());
-    TO_HOST(c, out4, d_out.p, (size_t)n * 16);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return RTX_OK;
-}
-
-// hits4 as rtx_debug_trace_closest writes them -> (alpha as the traversal computes it, opacity texture id as uint bits): cut_alpha of rtx_cutout.hpp, the function cut_accept compares
-int rtx_debug_opacity(rtx_ctx* c, const float* hits4, uint32_t n, float* out2) {
-    BIND(c);
-    if (!c->committed) { c->err = "scene not committed"; return RTX_ERR_STATE; }
-    if (!n) return RTX_OK;
-    if (!hits4 || !out2) { c->err = "opacity: null array"; return RTX_ERR_INVALID; }
-    for (uint32_t i = 0; i < n; i++) {                       // a triangle id the scene does not have would index past the per-triangle tables
-        uint32_t prim; memcpy(&prim, &hits4[(size_t)i * 4 + 3], 4);
-        if (prim != kMissPrim && prim >= c->stats.triangles) { c->err = "opacity: triangle id out of range"; return RTX_ERR_INVALID; }
-    }
-    DevBuf d_hits, d_out;
-    HIPCHK(c, d_hits.ensure((size_t)n * 16)); HIPCHK(c, d_out.ensure((size_t)n * 8));
-    TO_DEVICE(c, d_hits.p, hits4, (size_t)n * 16);
-    launch_dbg_opacity(c->stream, c->dsc, (const F4*)d_hits.p, n, (float*)d_out.p);
-    HIPCHK(c, hipGetLastError());
-    TO_HOST(c, out2, d_out.p, (size_t)n * 8);
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return RTX_OK;
 }

@@ -68,7 +68,7 @@ struct alignas(16) InstGPU { float o2w[16]; float nrm[16]; float o2w_inv[16]; fl
 // LightTriangle (Renderer.h:113-124) with the sample-independent part of SampleLightNEE_GI
 // (Sampler_v6.hlsl:540-575) hoisted to the host: world-space vertices, light normal, clamped area pdf.
 // EMISSION MAPS (include/rtx.h): two of the three pad words carry the light's global triangle id and the emission texture of its material; both are 0 unless an emission
-// map is active (BuiltScene::emi_active), and only nee_sample's emi path reads them.
+// map is active (BuiltScene::map_use.emi()), and only nee_sample's emi path reads them.
 struct alignas(16) LightGPU {
     float xv[3]; float cdf;
     float yv[3]; float pdf_l;      // max(EPS, weight / max(area, EPS))

@@ -571,9 +571,9 @@ Scene LoadObjScene(const std::vector<std::string>& files, const std::string& mtl
         if (ReadImage((!name.empty() && name[0] == '/') ? name : dir + name, img.rgba, img.width, img.height, img.channels, err)) s.images[t] = std::move(img);
         else fprintf(stderr, "%s skipped: %s\n", what, err.c_str());
     };
-    for (const MaterialExt& x : s.materialExt) load(x.map[MAP_KD], "map_Kd");
+    for (const MaterialExt& x : s.materialExt) { load(x.map[MAP_KD], "map_Kd"); s.boundMaps[rtx::kMapKd].push_back(x.map[MAP_KD]); }
     if (load_textures && cutouts != kCutoutsOff) {
-        s.opacityMaps.assign(s.materialExt.size(), -1);
+        s.boundMaps[rtx::kMapOpacity].assign(s.materialExt.size(), -1);
         std::vector<char> opacity(s.textures.size(), 0);       // images some material reads its alpha from
         for (size_t m = 0; m < s.materialExt.size(); m++) {
             const MaterialExt& x = s.materialExt[m];
@@ -581,40 +581,37 @@ Scene LoadObjScene(const std::vector<std::string>& files, const std::string& mtl
             if (t >= 0) load(t, "map_d");
             else if (cutouts == kCutoutsKdAlpha) { t = x.map[MAP_KD]; if (t < 0 || (size_t)t >= s.images.size() || s.images[t].channels != 4u) t = -1; }
             if (t < 0 || (size_t)t >= s.images.size() || !s.images[t].width) continue;
-            s.opacityMaps[m] = t; opacity[t] = 1;
+            s.boundMaps[rtx::kMapOpacity][m] = t; opacity[t] = 1;
         }
         for (size_t t = 0; t < s.images.size(); t++) if (opacity[t]) OpacityAlphaFromChannels(s.images[t].rgba, s.images[t].channels);
     }
     if (load_textures && spec_maps) {
-        s.ksMaps.assign(s.materialExt.size(), -1); s.prMaps.assign(s.materialExt.size(), -1); s.pmMaps.assign(s.materialExt.size(), -1);
+        for (rtx::MapSlot k : {rtx::kMapKs, rtx::kMapPr, rtx::kMapPm}) s.boundMaps[k].assign(s.materialExt.size(), -1);
         for (size_t m = 0; m < s.materialExt.size() && m < s.materials.size(); m++) {
             const MaterialExt& x = s.materialExt[m];
             Material& mat = s.materials[m];
             auto bound = [&](int t, const char* what) { load(t, what); return t >= 0 && (size_t)t < s.images.size() && s.images[t].width != 0u; };
             // the zero-scalar rule: a bound map multiplies its scalar, and 0 is what the parser leaves for a scalar the file does not give
-            if (bound(x.map[MAP_KS], "map_Ks")) { s.ksMaps[m] = x.map[MAP_KS]; rtx::spec_unit_colour(&mat.Ks.x); }
-            if (bound(x.map[MAP_PR], "map_Pr")) { s.prMaps[m] = x.map[MAP_PR]; if (rtx::spec_unit_scalar(&mat.Pr_Pm_Ps_Pc.x)) GenerateEssLUT(mat); }
-            if (bound(x.map[MAP_PM], "map_Pm")) { s.pmMaps[m] = x.map[MAP_PM]; rtx::spec_unit_scalar(&mat.Pr_Pm_Ps_Pc.y); }
+            if (bound(x.map[MAP_KS], "map_Ks")) { s.boundMaps[rtx::kMapKs][m] = x.map[MAP_KS]; rtx::spec_unit_colour(&mat.Ks.x); }
+            if (bound(x.map[MAP_PR], "map_Pr")) { s.boundMaps[rtx::kMapPr][m] = x.map[MAP_PR]; if (rtx::spec_unit_scalar(&mat.Pr_Pm_Ps_Pc.x)) GenerateEssLUT(mat); }
+            if (bound(x.map[MAP_PM], "map_Pm")) { s.boundMaps[rtx::kMapPm][m] = x.map[MAP_PM]; rtx::spec_unit_scalar(&mat.Pr_Pm_Ps_Pc.y); }
         }
     }
     if (load_textures && emission_maps) {
-        s.keMaps.assign(s.materialExt.size(), -1);
+        s.boundMaps[rtx::kMapKe].assign(s.materialExt.size(), -1);
         for (size_t m = 0; m < s.materialExt.size() && m < s.materials.size(); m++) {
             const int t = s.materialExt[m].map[MAP_KE];
             load(t, "map_Ke");
             // the unit-Ke rule: a bound map multiplies Ke, and (0, 0, 0) is what the parser leaves for a Ke the file does not give
-            if (t >= 0 && (size_t)t < s.images.size() && s.images[t].width != 0u) { s.keMaps[m] = t; rtx::emi_unit_ke(&s.materials[m].Ke.x); }
+            if (t >= 0 && (size_t)t < s.images.size() && s.images[t].width != 0u) { s.boundMaps[rtx::kMapKe][m] = t; rtx::emi_unit_ke(&s.materials[m].Ke.x); }
         }
     }
     if (load_textures && normals.mode != kNormalsOff) {
-        s.normalMaps.assign(s.materialExt.size(), -1);
+        s.boundMaps[rtx::kMapNormal].assign(s.materialExt.size(), -1);
         const size_t nfile = s.textures.size();                // (copies are appended behind the files' entries, which keep their ids)
         std::vector<char> other(nfile, 0);                     // images another slot reads
-        for (size_t m = 0; m < s.materialExt.size(); m++) {
-            const int kd = s.materialExt[m].map[MAP_KD]; if (kd >= 0 && (size_t)kd < nfile) other[kd] = 1;
-            const int op = m < s.opacityMaps.size() ? s.opacityMaps[m] : -1; if (op >= 0 && (size_t)op < nfile) other[op] = 1;
-            for (const std::vector<int>* sm : {&s.ksMaps, &s.prMaps, &s.pmMaps, &s.keMaps}) { const int t = m < sm->size() ? (*sm)[m] : -1; if (t >= 0 && (size_t)t < nfile) other[t] = 1; }
-        }
+        for (uint32_t k = 0; k < rtx::kMapSlotCount; k++)
+            if (k != rtx::kMapNormal) for (int t : s.boundMaps[k]) if (t >= 0 && (size_t)t < nfile) other[t] = 1;
         std::vector<int> as_normal(nfile, -1), as_height(nfile, -1);      // file image -> the entry that holds it as a normal map / converted from a height map
         for (size_t m = 0; m < s.materialExt.size(); m++) {
             const MaterialExt& x = s.materialExt[m];
@@ -632,7 +629,7 @@ Scene LoadObjScene(const std::vector<std::string>& files, const std::string& mtl
                 if (height) { std::vector<uint8_t> nm; rtx::HeightToNormalMap(im.rgba.data(), im.width, im.height, (double)normals.strength, nm); im.rgba = std::move(nm); }
                 if (normals.flipY) rtx::FlipGreen(im.rgba.data(), (size_t)im.width * im.height);
             }
-            s.normalMaps[m] = slot;
+            s.boundMaps[rtx::kMapNormal][m] = slot;
         }
     }
     return s;
@@ -687,29 +684,12 @@ int BindSceneMaps(const Scene& s, rtx_ctx* ctx) {
     if (!n) return RTX_OK;
     for (size_t m = 0; m < s.models.size(); m++)
         if (!s.models[m].uvs.empty() && (r = rtx_set_mesh_uvs(ctx, (uint32_t)m, s.models[m].uvs.data(), (uint32_t)s.models[m].indices.size()))) return r;
-    for (size_t m = 0; m < s.materialExt.size() && m < s.materials.size(); m++) {
-        const int t = s.materialExt[m].map[MAP_KD];
-        if (t >= 0 && (size_t)t < id.size() && id[t] >= 0 && (r = rtx_set_material_map(ctx, (uint32_t)m, RTX_MAP_KD, id[t]))) return r;
-    }
-    for (size_t m = 0; m < s.opacityMaps.size() && m < s.materials.size(); m++) {
-        const int t = s.opacityMaps[m];
-        if (t >= 0 && (size_t)t < id.size() && id[t] >= 0 && (r = rtx_set_material_map(ctx, (uint32_t)m, RTX_MAP_OPACITY, id[t]))) return r;
-    }
-    for (size_t m = 0; m < s.normalMaps.size() && m < s.materials.size(); m++) {
-        const int t = s.normalMaps[m];
-        if (t >= 0 && (size_t)t < id.size() && id[t] >= 0 && (r = rtx_set_material_map(ctx, (uint32_t)m, RTX_MAP_NORMAL, id[t]))) return r;
-    }
-    for (size_t m = 0; m < s.keMaps.size() && m < s.materials.size(); m++) {
-        const int t = s.keMaps[m];
-        if (t >= 0 && (size_t)t < id.size() && id[t] >= 0 && (r = rtx_set_material_map(ctx, (uint32_t)m, RTX_MAP_KE, id[t]))) return r;
-    }
     bool pr_bound = false;
-    const std::vector<int>* spec[3] = {&s.ksMaps, &s.prMaps, &s.pmMaps}; const uint32_t slot[3] = {RTX_MAP_KS, RTX_MAP_PR, RTX_MAP_PM};
-    for (int k = 0; k < 3; k++) for (size_t m = 0; m < spec[k]->size() && m < s.materials.size(); m++) {
-        const int t = (*spec[k])[m];
+    for (uint32_t k = 0; k < rtx::kMapSlotCount; k++) for (size_t m = 0; m < s.boundMaps[k].size() && m < s.materials.size(); m++) {
+        const int t = s.boundMaps[k][m];
         if (t < 0 || (size_t)t >= id.size() || id[t] < 0) continue;
-        if ((r = rtx_set_material_map(ctx, (uint32_t)m, slot[k], id[t]))) return r;
-        if (k == 1) pr_bound = true;
+        if ((r = rtx_set_material_map(ctx, (uint32_t)m, rtx::kMapSlots[k].api, id[t]))) return r;
+        if (k == rtx::kMapPr) pr_bound = true;
     }
     // the energy compensation follows a mapped roughness through a table of LUTs (include/rtx.h, ENERGY TABLE): set only where some roughness map was bound
     if (pr_bound && rtx_set_ess_table && (r = rtx_set_ess_table(ctx, EssTable17().data(), 17))) return r;

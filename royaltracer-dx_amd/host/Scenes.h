@@ -8,6 +8,7 @@
 #include "Vertex.h"
 #include "ObjLoader.h"
 #include "../../include/rtx.h"
+#include "../csrc/rtx_map_slots.hpp"
 
 struct SceneModel { std::vector<Vertex> vertices; std::vector<UINT> indices; std::vector<UINT> materialIDs;
                     std::vector<float> uvs; };      // one (u, v) per entry of `indices` (the OBJ's vt, per corner), or empty
@@ -26,13 +27,12 @@ struct Scene {
     std::vector<std::string> textures;       // texture map ids the 128-byte record has no room for (Vertex.h:21 "ADD MAP IDs LATER"), and the distinct map file names
     std::vector<SceneImage> images;          // index-aligned with `textures`: the decoded map_Kd files (host/ImageIO readers); an entry that no map_Kd names, or whose file
                                              // is missing or in another format, stays empty.  BindSceneMaps hands the loaded ones to a context, sRGB-encoded
-    std::vector<int> opacityMaps;            // per material: the entry of `textures` bound as its opacity map (RTX_MAP_OPACITY: its map_d, or with kCutoutsKdAlpha its 32-bit map_Kd), or
-                                             // -1; empty = none.  The alpha byte of such an image is the file's own alpha channel (32-bit TGA) or its first channel (PGM / PPM / 24-bit TGA)
-    std::vector<int> normalMaps;             // per material: the entry of `textures` bound as its normal map (RTX_MAP_NORMAL: its norm image, or on request its map_Bump / bump image,
-                                             // taken as a normal map or converted from a height map on load), or -1; empty = none
-    std::vector<int> ksMaps, prMaps, pmMaps; // per material: the entry of `textures` bound as its specular / roughness / metalness map (RTX_MAP_KS / RTX_MAP_PR / RTX_MAP_PM: its
-                                             // map_Ks / map_Pr / map_Pm image; one packed file may serve several slots), or -1; empty = none
-    std::vector<int> keMaps;                 // per material: the entry of `textures` bound as its emission map (RTX_MAP_KE: its map_Ke image), or -1; empty = none
+    std::vector<int> boundMaps[rtx::kMapSlotCount];   // per slot (csrc/rtx_map_slots.hpp), per material: the entry of `textures` BindSceneMaps binds there, or -1; empty = none.
+                                             // LoadObjScene fills them: kMapKd the map_Kd; kMapOpacity the map_d, or with kCutoutsKdAlpha the 32-bit map_Kd (the alpha byte of such an image is the
+                                             // file's own alpha channel (32-bit TGA) or its first channel (PGM / PPM / 24-bit TGA)); kMapNormal the norm image, or on request the map_Bump / bump
+                                             // image, taken as a normal map or converted from a height map on load; kMapKs / kMapPr / kMapPm the map_Ks / map_Pr / map_Pm image (one packed file
+                                             // may serve several slots); kMapKe the map_Ke image
+    int boundMap(rtx::MapSlot slot, size_t material) const { return material < boundMaps[slot].size() ? boundMaps[slot][material] : -1; }
     std::vector<SceneModel> models;
     std::vector<SceneInstance> instances;
     XMFLOAT3 eye{0, 0, 1}, center{0, 0, 0}, up{0, 1, 0};

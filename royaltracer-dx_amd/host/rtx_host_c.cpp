@@ -110,13 +110,10 @@ int rtxh_scene_texture_pixels(const rtxh_scene* s, uint32_t i, const void** rgba
     *rgba8 = have ? s->s.images[i].rgba.data() : nullptr; *width = have ? s->s.images[i].width : 0; *height = have ? s->s.images[i].height : 0;
     return RTX_OK;
 }
-int rtxh_scene_spec_map(const rtxh_scene* s, uint32_t material, uint32_t slot) {
-    const std::vector<int>* v = slot == RTX_MAP_KS ? &s->s.ksMaps : slot == RTX_MAP_PR ? &s->s.prMaps : slot == RTX_MAP_PM ? &s->s.pmMaps : nullptr;
-    return v && material < v->size() ? (*v)[material] : -1;
-}
-int rtxh_scene_emission_map(const rtxh_scene* s, uint32_t material) { return material < s->s.keMaps.size() ? s->s.keMaps[material] : -1; }
-int rtxh_scene_normal_map(const rtxh_scene* s, uint32_t material) { return material < s->s.normalMaps.size() ? s->s.normalMaps[material] : -1; }
-int rtxh_scene_opacity_map(const rtxh_scene* s, uint32_t material) { return material < s->s.opacityMaps.size() ? s->s.opacityMaps[material] : -1; }
+int rtxh_scene_spec_map(const rtxh_scene* s, uint32_t material, uint32_t slot) { return slot == RTX_MAP_KS || slot == RTX_MAP_PR || slot == RTX_MAP_PM ? s->s.boundMap((rtx::MapSlot)rtx::map_slot_of(slot), material) : -1; }
+int rtxh_scene_emission_map(const rtxh_scene* s, uint32_t material) { return s->s.boundMap(rtx::kMapKe, material); }
+int rtxh_scene_normal_map(const rtxh_scene* s, uint32_t material) { return s->s.boundMap(rtx::kMapNormal, material); }
+int rtxh_scene_opacity_map(const rtxh_scene* s, uint32_t material) { return s->s.boundMap(rtx::kMapOpacity, material); }
 int rtxh_scene_mesh_uvs(const rtxh_scene* s, uint32_t i, const float** uv2, uint32_t* nidx) {
     if (!uv2 || !nidx || i >= s->s.models.size()) return RTX_ERR_INVALID;
     const SceneModel& m = s->s.models[i];

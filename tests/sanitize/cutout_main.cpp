@@ -49,27 +49,28 @@ int main(int argc, char** argv) {
     H.insts[1].tri_base = 3;                                                       // (what a commit's numbering gives two instances of a 3-triangle mesh)
     const uint32_t texel = 0x80FFFFFFu;
     if (!H.set_texture(0, &texel, 1, 1, 0) || !H.set_texture(1, &texel, 1, 1, 1)) return fail("set_texture");
-    if (H.cutouts_active() || H.any_opacity_map()) return fail("active without a map");
+    if (H.map_use().cut() || H.any_bound(rtx::kMapOpacity)) return fail("active without a map");
     // refusals change nothing
     H.tex_dirty = false;
     if (H.set_material_map(3, OPA, 0) || H.set_material_map(0, 1, 0) || H.set_material_map(0, 3, 0) || H.set_material_map(0, OPA, 2) || H.set_material_map(0, OPA, -2) || H.set_material_map(0xFFFFFFFFu, OPA, 0)) return fail("an invalid call was accepted");
-    if (H.tex_dirty || !H.map_opacity.empty() || !H.map_kd.empty()) return fail("a refused call changed the scene");
+    if (H.tex_dirty || !H.maps[rtx::kMapOpacity].empty() || !H.maps[rtx::kMapKd].empty()) return fail("a refused call changed the scene");
     // an emitter's map has no effect
     if (!H.set_material_map(2, OPA, 0)) return fail("a valid call was refused");
-    if (!H.any_opacity_map() || H.cutouts_active() || !H.tex_dirty) return fail("an emitter's map");
+    if (!H.any_bound(rtx::kMapOpacity) || H.map_use().cut() || !H.tex_dirty) return fail("an emitter's map");
     if (!H.set_material_map(1, OPA, 1) || !H.set_material_map(1, 0, 1)) return fail("both slots, one texture");
-    if (!H.cutouts_active() || !H.maps_active() || H.map_kd[1] != 1 || H.map_opacity[1] != 1) return fail("slots");
+    if (!H.map_use().cut() || !H.map_use().kd() || H.maps[rtx::kMapKd][1] != 1 || H.maps[rtx::kMapOpacity][1] != 1) return fail("slots");
     std::vector<int32_t> tc; H.fill_tri_cut(tc);
     if (tc != std::vector<int32_t>({-1, 1, -1, -1, 1, -1})) return fail("per-triangle table");
-    if (H.cut_texture(7) != -1 || H.cut_texture(0xFFFFFFFFu) != -1) return fail("out-of-range material id");
+    if (H.bound_texture(rtx::kMapOpacity, 7) != -1 || H.bound_texture(rtx::kMapOpacity, 0xFFFFFFFFu) != -1) return fail("out-of-range material id");
     std::vector<float> uv; H.fill_tri_uv(uv);
     if (uv.size() != 36) return fail("uv table");
     // unbinding, and rtx_set_materials: every map back to -1
-    if (!H.set_material_map(1, OPA, -1) || H.cutouts_active() || !H.maps_active()) return fail("unbind");
-    if (!H.set_material_map(0, OPA, 0) || !H.cutouts_active()) return fail("rebind");
+    if (!H.set_material_map(1, OPA, -1) || H.map_use().cut() || !H.map_use().kd()) return fail("unbind");
+    if (!H.set_material_map(0, OPA, 0) || !H.map_use().cut()) return fail("rebind");
     H.tex_dirty = false;
     if (!H.set_materials(mats.data(), 2)) return fail("set_materials again");
-    if (!H.tex_dirty || H.any_map() || H.cutouts_active() || H.maps_active()) return fail("set_materials keeps a map");
+    bool any_map = false; for (uint32_t s = 0; s < rtx::kMapSlotCount; s++) any_map = any_map || H.any_bound((rtx::MapSlot)s);
+    if (!H.tex_dirty || any_map || H.map_use().cut() || H.map_use().kd()) return fail("set_materials keeps a map");
     H.fill_tri_cut(tc);                                                            // material ids 2 are now out of range: no cut-out, no read past the table
     for (int32_t t : tc) if (t != -1) return fail("table after set_materials");
     if (H.set_material_map(2, OPA, 0)) return fail("a material beyond the new table");

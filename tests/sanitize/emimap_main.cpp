@@ -61,12 +61,13 @@ int main(int argc, char** argv) {
     H.tex_dirty = false;
     if (H.set_material_map(0, 11, -1) || H.set_material_map(0, 13, -1) || H.set_material_map(0, 14, -1) || H.set_material_map(nmat, KE, -1) || H.set_material_map(0, KE, (int32_t)ntex) || H.set_material_map(0, KE, -2))
         return fail("an invalid call was accepted");
-    if (H.tex_dirty || !H.map_ke.empty() || H.any_emi_map() || H.emi_active()) return fail("a refused call changed the scene");
+    if (H.tex_dirty || !H.maps[rtx::kMapKe].empty() || H.any_bound(rtx::kMapKe) || H.map_use().emi()) return fail("a refused call changed the scene");
     for (uint32_t m = 0; m < nmat; m++) if (ke[m] >= 0 && !H.set_material_map(m, KE, ke[m])) return fail("a valid call was refused");
     rtx::BuiltScene B;
     H.build_lights(B);
-    printf("A %d\nT %08x\n", (int)H.emi_active(), word(B.total_weight));
-    if (H.emi_active() != !B.emi_q.empty() || (H.emi_active() && (B.emi_q.size() != nt || B.light_emi.size() != B.lights.size() * 2))) return fail("table sizes");
+    const bool emi_active = H.map_use().emi();
+    printf("A %d\nT %08x\n", (int)emi_active, word(B.total_weight));
+    if (emi_active != !B.emi_q.empty() || (emi_active && (B.emi_q.size() != nt || B.light_emi.size() != B.lights.size() * 2))) return fail("table sizes");
     for (size_t i = 0; i < B.lights.size(); i++) {
         printf("L");
         for (int k = 0; k < 20; k++) printf(" %08x", word(B.lights80[i * 20 + k]));
@@ -78,7 +79,7 @@ int main(int argc, char** argv) {
     // rtx_set_materials resets the slot: the list of the unmapped scene again
     H.tex_dirty = false;
     if (!H.set_materials(mats.data(), nmat)) return fail("set_materials again");
-    if (H.any_emi_map() || H.emi_active() || !H.map_ke.empty()) return fail("set_materials keeps a map");
+    if (H.any_bound(rtx::kMapKe) || H.map_use().emi() || !H.maps[rtx::kMapKe].empty()) return fail("set_materials keeps a map");
     H.build_lights(B);
     if (!B.emi_q.empty() || !B.light_emi.empty()) return fail("tables without a map");
     for (const rtx::LightGPU& L : B.lights) if (L.prim != 0u || L.emi_tex != 0) return fail("pad words without a map");

@@ -580,6 +580,26 @@ def test_host_layer_under_asan_ubsan(tmp_path, golden_dir):
     assert "done" in r.stdout and "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-3000:]
 
 
+def test_map_slot_table_under_asan_ubsan(tmp_path):
+    """the host scene's map-slot table as a stand-alone program (tests/sanitize/mapslots_main.cpp, its own main) compiled with g++ -fsanitize=address,undefined and run
+    as a child process: every slot on a plain, an emitting and an unused material against the rules of include/rtx.h, written out by hand in the driver"""
+    import subprocess, shutil
+    if not shutil.which("g++"):
+        pytest.skip("g++ not available")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    pk = os.path.join(root, "royaltracer-dx_amd")
+    srcs = [os.path.join(root, "tests", "sanitize", f) for f in ("mapslots_main.cpp", "device_stubs.cpp")] + _host_layer_sources(pk)
+    exe = str(tmp_path / "san_mapslots")
+    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-ffp-contract=off",
+           "-I" + os.path.join(root, "include"), "-I" + os.path.join(pk, "csrc"), "-I" + os.path.join(pk, "host"), "-pthread", "-o", exe] + srcs
+    b = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert b.returncode == 0, b.stderr[-2000:]
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=600,
+                       env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1"))
+    assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
+    assert "done" in r.stdout and "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-3000:]
+
+
 def test_parallel_builder_under_tsan(tmp_path):
     """"same tree for any thread count" is a correctness premise of the parallel top-down build, so the threaded host code runs under ThreadSanitizer
     (g++ -fsanitize=thread, CPU only, device API stubbed): build + re-insertion + wide collapse with 1 / 3 / 16 builder threads on 66 000 triangles — the three trees replay
