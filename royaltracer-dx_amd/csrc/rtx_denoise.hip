@@ -1,7 +1,8 @@
-// rtx_denoise.hip — rtx_denoise: the edge-avoiding a-trous filter over the mean of u1, and the reads of the denoised image.  Validate, guides (k_denoise_guides, one primary
-// ray per pixel, every call; with a flag of rtx_denoise_params set its map-guide form, k_denoise_map_guides, and the levels' *_maps forms), then one k_denoise_level per level between u1, two ping-pong images and the denoised image.  Part of the C-ABI of include/rtx.h (rtx_ctx.hpp);
-// the kernels and the tap arithmetic: rtx_k_denoise.hpp.  rtx_denoise_variance is the same sequence with k_denoise_level_var in the place of the level kernels: it reads `half`,
-// the adaptive sampler's second sum, beside u1 (half_state: when that sum belongs to u1); rtx_read_adaptive_half and rtx_debug_denoise_variance show its two inputs.
+// rtx_denoise.hip — rtx_denoise and rtx_denoise_variance: the edge-avoiding a-trous filters over the mean of u1, and the reads of the denoised image.  Validate, guides
+// (k_denoise_guides, one primary ray per pixel, every call; with a flag of the parameters set the form that writes the map-guide record too), then one k_denoise_level per level
+// between u1, two ping-pong images and the denoised image.  Part of the C-ABI of include/rtx.h (rtx_ctx.hpp); the kernels and the tap arithmetic: rtx_k_denoise.hpp.
+// rtx_denoise_variance is the same sequence with the level kernel's VAR forms: they read `half`, the adaptive sampler's second sum, beside u1 (half_state: when that sum belongs
+// to u1); rtx_read_adaptive_half and rtx_debug_denoise_variance show its two inputs.
 #include <cmath>
 #include "rtx_ctx.hpp"
 
@@ -43,8 +44,8 @@ template <class P> static int filter_checks(rtx_ctx* c, const char* who, uint32_
     return RTX_OK;
 }
 
-// what rtx_denoise and rtx_denoise_variance share once their arguments are validated: memory, guides, the levels, the result.  variance: the levels are k_denoise_level_var,
-// which read `half` beside u1 at level 0 and take sigma = sigma_var; else rtx_denoise's own kernels with sigma = 1 / sigma_color
+// what rtx_denoise and rtx_denoise_variance share once their arguments are validated: memory, guides, the levels, the result.  variance: the levels are the VAR forms of
+// k_denoise_level, which read `half` beside u1 at level 0 and take sigma = sigma_var; else the plain forms with sigma = 1 / sigma_color
 static int filter_levels(rtx_ctx* c, uint32_t width, uint32_t height, uint32_t levels, uint32_t normal_power_log2, float inv_plane, uint32_t flags, bool variance, float sigma, rtx_denoise_result* out) {
     const size_t npix = (size_t)width * height;
     // ---- 2. memory: allocated on first use, resized with the image ----
@@ -65,8 +66,8 @@ static int filter_levels(rtx_ctx* c, uint32_t width, uint32_t height, uint32_t l
     if (timing) for (hipEvent_t& e : ev) e = D.ev.take();
     const bool timed = timing && ev[0] && ev[1] && ev[2] && ev[3];
     if (timed) (void)hipEventRecord(ev[0], st);
-    if (flags) launch_denoise_map_guides(st, (uint32_t)c->num_cus * 8u, c->dsc, width, height, (const CameraGPU*)c->d_cam.p, (F4*)D.d_guides.p, (F4*)D.d_mguides.p);
-    else launch_denoise_guides(st, (uint32_t)c->num_cus * 8u, c->dsc, width, height, (const CameraGPU*)c->d_cam.p, (F4*)D.d_guides.p);
+    F4* mg = flags ? (F4*)D.d_mguides.p : nullptr;                      // (the buffer may outlive a call with a flag set: this call's flags decide, not its pointer)
+    launch_denoise_guides(st, (uint32_t)c->num_cus * 8u, c->dsc, width, height, (const CameraGPU*)c->d_cam.p, (F4*)D.d_guides.p, mg);
     if (timed) { (void)hipEventRecord(ev[1], st); (void)hipEventRecord(ev[2], st); }
     const F4* in = c->accum_ptr();
     for (uint32_t i = 0; i < levels; i++) {
@@ -74,9 +75,7 @@ static int filter_levels(rtx_ctx* c, uint32_t width, uint32_t height, uint32_t l
         a.width = width; a.height = height; a.step = 1u << i; a.normal_power_log2 = normal_power_log2; a.first = i == 0; a.last = i + 1 == levels;
         a.inv_sigma_plane = inv_plane; a.inv_sigma_color_s = variance ? 0.0f : sigma * (float)a.step;
         F4* dst = (F4*)(a.last ? D.d_out.p : D.d_pp[i & 1u].p);
-        if (variance) launch_denoise_level_var(st, a, sigma, flags, in, (const F4*)c->ad.d_half.p, (const F4*)D.d_guides.p, (const F4*)D.d_mguides.p, dst, (uint32_t*)D.d_partial.p, a.step <= D.lds_step);
-        else if (flags) launch_denoise_level_maps(st, a, flags, in, (const F4*)D.d_guides.p, (const F4*)D.d_mguides.p, dst, (uint32_t*)D.d_partial.p, a.step <= D.lds_step);
-        else launch_denoise_level(st, a, in, (const F4*)D.d_guides.p, dst, (uint32_t*)D.d_partial.p, a.step <= D.lds_step);
+        launch_denoise_level(st, a, variance, variance ? sigma : 0.0f, flags, in, variance ? (const F4*)c->ad.d_half.p : nullptr, (const F4*)D.d_guides.p, mg, dst, (uint32_t*)D.d_partial.p, a.step <= D.lds_step);
         in = dst;
     }
     if (timed) (void)hipEventRecord(ev[3], st);
@@ -96,6 +95,34 @@ static int filter_levels(rtx_ctx* c, uint32_t width, uint32_t height, uint32_t l
     }
     if (c->own_stream) HIPCHK(c, hipStreamSynchronize(c->stream));            // on a caller-bound stream what follows is stream-ordered: no host bubble
     return RTX_OK;
+}
+
+// what the rtx_debug_denoise_* entry points share: the state check, check(npix) — the entry point's own checks, RTX_OK to go on —, PRIVATE records (a debug call must not
+// disturb the filter's own, nor a denoised image of another size), the guides launch (maps: the form that writes the map-guide record too) and the copy back.  out_item = 0:
+// `out` receives the record itself (the map-guide record when maps), 32 bytes per pixel; else second(guides, mguides, d_out) launches the kernel that writes out_item bytes per pixel
+template <class Check, class Second>
+static int guides_probe(rtx_ctx* c, const char* name, uint32_t width, uint32_t height, bool maps, void* out, size_t out_item, Check check, Second second) {
+    BIND(c);
+    if (!c->committed || !c->camera_set) { c->err = std::string(name) + ": scene not committed or camera not set"; return RTX_ERR_STATE; }
+    const size_t npix = (size_t)width * height;
+    if (const int r = check(npix)) return r;
+    DevBuf d_g, d_m, d_o;
+    HIPCHK(c, d_g.ensure(npix * 32));
+    if (maps) HIPCHK(c, d_m.ensure(npix * 32));
+    if (out_item) HIPCHK(c, d_o.ensure(npix * out_item));
+    launch_denoise_guides(c->stream, (uint32_t)c->num_cus * 8u, c->dsc, width, height, (const CameraGPU*)c->d_cam.p, (F4*)d_g.p, (F4*)d_m.p);
+    if (out_item) second((const F4*)d_g.p, (const F4*)d_m.p, d_o.p);
+    HIPCHK(c, hipGetLastError());
+    TO_HOST(c, out, out_item ? d_o.p : (maps ? d_m.p : d_g.p), npix * (out_item ? out_item : 32));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RTX_OK;
+}
+// the two entry points that return a record
+static int record_probe(rtx_ctx* c, const char* name, uint32_t width, uint32_t height, bool maps, float* out8) {
+    return guides_probe(c, name, width, height, maps, out8, 0, [&](size_t npix) {
+        if (!out8 || !npix || npix > 0x7FFFFFFFull) { c->err = std::string(name) + ": bad size"; return RTX_ERR_INVALID; }
+        return RTX_OK;
+    }, [](const F4*, const F4*, void*) {});
 }
 
 extern "C" {
@@ -150,25 +177,14 @@ int rtx_read_adaptive_half(rtx_ctx* c, float* out, size_t bytes) {
 }
 
 int rtx_debug_denoise_variance(rtx_ctx* c, uint32_t width, uint32_t height, uint32_t flags, float* out2) {
-    BIND(c);
-    if (!c->committed || !c->camera_set) { c->err = "denoise_variance_input: scene not committed or camera not set"; return RTX_ERR_STATE; }
-    if (!c->accum_ptr() || !c->acc_w || !c->acc_h) { c->err = "denoise_variance_input: no accumulation buffer yet"; return RTX_ERR_STATE; }
-    const size_t npix = (size_t)width * height;
-    if (!out2 || width != c->acc_w || height != c->acc_h || npix > 0x7FFFFFFFull || (flags & ~(RTX_DENOISE_ALBEDO | RTX_DENOISE_MAPPED_NORMALS))) { c->err = "denoise_variance_input: bad size or flags"; return RTX_ERR_INVALID; }
-    if (c->ext_accum && c->ext_accum_bytes < npix * 16) { c->err = "bound accumulation buffer is smaller than width*height*16 bytes"; return RTX_ERR_INVALID; }
-    if (const char* why = half_state(c, width, height)) { c->err = std::string("denoise_variance_input: ") + why; return RTX_ERR_STATE; }
     const bool alb = (flags & RTX_DENOISE_ALBEDO) != 0;                        // (the normals of the normal stop do not enter v or gv)
-    DevBuf d_g, d_m, d_o;                                                    // (private, as rtx_debug_denoise_guides': a debug call must not disturb the filter's record)
-    HIPCHK(c, d_g.ensure(npix * 32)); HIPCHK(c, d_o.ensure(npix * 8));
-    if (alb) {
-        HIPCHK(c, d_m.ensure(npix * 32));
-        launch_denoise_map_guides(c->stream, (uint32_t)c->num_cus * 8u, c->dsc, width, height, (const CameraGPU*)c->d_cam.p, (F4*)d_g.p, (F4*)d_m.p);
-    } else launch_denoise_guides(c->stream, (uint32_t)c->num_cus * 8u, c->dsc, width, height, (const CameraGPU*)c->d_cam.p, (F4*)d_g.p);
-    launch_denoise_var_input(c->stream, width, height, alb, c->accum_ptr(), (const F4*)c->ad.d_half.p, (const F4*)d_g.p, (const F4*)d_m.p, (float*)d_o.p);
-    HIPCHK(c, hipGetLastError());
-    TO_HOST(c, out2, d_o.p, npix * 8);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return RTX_OK;
+    return guides_probe(c, "denoise_variance_input", width, height, alb, out2, 8, [&](size_t npix) {
+        if (!c->accum_ptr() || !c->acc_w || !c->acc_h) { c->err = "denoise_variance_input: no accumulation buffer yet"; return RTX_ERR_STATE; }
+        if (!out2 || width != c->acc_w || height != c->acc_h || npix > 0x7FFFFFFFull || (flags & ~(RTX_DENOISE_ALBEDO | RTX_DENOISE_MAPPED_NORMALS))) { c->err = "denoise_variance_input: bad size or flags"; return RTX_ERR_INVALID; }
+        if (c->ext_accum && c->ext_accum_bytes < npix * 16) { c->err = "bound accumulation buffer is smaller than width*height*16 bytes"; return RTX_ERR_INVALID; }
+        if (const char* why = half_state(c, width, height)) { c->err = std::string("denoise_variance_input: ") + why; return RTX_ERR_STATE; }
+        return RTX_OK;
+    }, [&](const F4* guides, const F4* mguides, void* out) { launch_denoise_var_input(c->stream, width, height, alb, c->accum_ptr(), (const F4*)c->ad.d_half.p, guides, mguides, (float*)out); });
 }
 
 int rtx_read_denoised(rtx_ctx* c, float* out, size_t bytes) {
@@ -193,32 +209,7 @@ int rtx_read_denoised_srgb8(rtx_ctx* c, uint8_t* out, size_t bytes) {
     return RTX_OK;
 }
 
-int rtx_debug_denoise_guides(rtx_ctx* c, uint32_t width, uint32_t height, float* out8) {
-    BIND(c);
-    if (!c->committed || !c->camera_set) { c->err = "denoise_guides: scene not committed or camera not set"; return RTX_ERR_STATE; }
-    const size_t npix = (size_t)width * height;
-    if (!out8 || !npix || npix > 0x7FFFFFFFull) { c->err = "denoise_guides: bad size"; return RTX_ERR_INVALID; }
-    DevBuf d_g;                                                              // (not the filter's own record: a debug call must not disturb a denoised image of another size)
-    HIPCHK(c, d_g.ensure(npix * 32));
-    launch_denoise_guides(c->stream, (uint32_t)c->num_cus * 8u, c->dsc, width, height, (const CameraGPU*)c->d_cam.p, (F4*)d_g.p);
-    HIPCHK(c, hipGetLastError());
-    TO_HOST(c, out8, d_g.p, npix * 32);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return RTX_OK;
-}
-
-int rtx_debug_denoise_map_guides(rtx_ctx* c, uint32_t width, uint32_t height, float* out8) {
-    BIND(c);
-    if (!c->committed || !c->camera_set) { c->err = "denoise_map_guides: scene not committed or camera not set"; return RTX_ERR_STATE; }
-    const size_t npix = (size_t)width * height;
-    if (!out8 || !npix || npix > 0x7FFFFFFFull) { c->err = "denoise_map_guides: bad size"; return RTX_ERR_INVALID; }
-    DevBuf d_g, d_m;                                                         // (private, as rtx_debug_denoise_guides': the kernel writes both records)
-    HIPCHK(c, d_g.ensure(npix * 32)); HIPCHK(c, d_m.ensure(npix * 32));
-    launch_denoise_map_guides(c->stream, (uint32_t)c->num_cus * 8u, c->dsc, width, height, (const CameraGPU*)c->d_cam.p, (F4*)d_g.p, (F4*)d_m.p);
-    HIPCHK(c, hipGetLastError());
-    TO_HOST(c, out8, d_m.p, npix * 32);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return RTX_OK;
-}
+int rtx_debug_denoise_guides(rtx_ctx* c, uint32_t width, uint32_t height, float* out8) { return record_probe(c, "denoise_guides", width, height, false, out8); }
+int rtx_debug_denoise_map_guides(rtx_ctx* c, uint32_t width, uint32_t height, float* out8) { return record_probe(c, "denoise_map_guides", width, height, true, out8); }
 
 }  // extern "C"

@@ -51,7 +51,7 @@ __device__ unsigned long long g_sec[36];          // [0,12) cycles, [12,24) acti
 #include "rtx_k_bounce_bvh.hpp"     // k_bounce_bvh, k_order_queues
 #include "rtx_k_film.hpp"           // k_accumulate, k_srgb8, k_debug_layer, k_pack_tiles, k_unpack_tiles
 #include "rtx_k_adaptive.hpp"       // k_adaptive_error, k_adaptive_compact
-#include "rtx_k_denoise.hpp"        // k_denoise_guides, k_denoise_level, k_denoise_level_var, k_denoise_count
+#include "rtx_k_denoise.hpp"        // k_denoise_guides, k_denoise_level (both filters), k_denoise_var_input, k_denoise_count
 #include "rtx_k_dbg.hpp"            // k_dbg_*
 
 namespace rtx {
@@ -330,11 +330,10 @@ void launch_adaptive_error(hipStream_t st, const DevFrame& f, const F4* accum, c
 void launch_adaptive_compact(hipStream_t st, const DevFrame& f, const AdaptState& ad, uint32_t max_spp, uint32_t* list, uint32_t* out5) {
     hipLaunchKernelGGL(k_adaptive_compact, dim3(1), dim3(kCompactBlock), 0, st, f, ad, max_spp, list, out5);
 }
-void launch_denoise_guides(hipStream_t st, uint32_t max_blocks, const DevScene& sc, uint32_t width, uint32_t height, const CameraGPU* cam, F4* guides) {
-    dispatch_bool(sc.tri_cut != nullptr, [&](auto cut) { hipLaunchKernelGGL(k_denoise_guides<decltype(cut)::value>, dim3(grid_for(width * height, max_blocks)), dim3(kBlock), trace_lds_bytes(sc), st, sc, sc.small, width, height, cam, guides); });
-}
-void launch_denoise_map_guides(hipStream_t st, uint32_t max_blocks, const DevScene& sc, uint32_t width, uint32_t height, const CameraGPU* cam, F4* guides, F4* mguides) {
-    dispatch_bool(sc.tri_cut != nullptr, [&](auto cut) { hipLaunchKernelGGL(k_denoise_map_guides<decltype(cut)::value>, dim3(grid_for(width * height, max_blocks)), dim3(kBlock), trace_lds_bytes(sc), st, sc, sc.small, width, height, cam, guides, mguides); });
+// mguides != nullptr: the form that writes the map-guide record too
+void launch_denoise_guides(hipStream_t st, uint32_t max_blocks, const DevScene& sc, uint32_t width, uint32_t height, const CameraGPU* cam, F4* guides, F4* mguides) {
+    dispatch_bool(sc.tri_cut != nullptr, [&](auto cut) { dispatch_bool(mguides != nullptr, [&](auto maps) {
+        hipLaunchKernelGGL((k_denoise_guides<decltype(cut)::value, decltype(maps)::value>), dim3(grid_for(width * height, max_blocks)), dim3(kBlock), trace_lds_bytes(sc), st, sc, sc.small, width, height, cam, guides, mguides); }); });
 }
 uint32_t denoise_workgroups(uint32_t width, uint32_t height) { return ((width + kDnTileW - 1u) / kDnTileW) * ((height + kDnTileH - 1u) / kDnTileH); }
 // which form a level runs: go(S, FIRST) with S = the level's step where it is staged (1, 2 or 4 and `staged`), else 0
@@ -344,28 +343,14 @@ template <class Go> static void denoise_level_form(const DenoiseLevel& a, bool s
     else if (staged && a.step == 4u) go(IntC<4>{}, BoolC<false>{});
     else go(IntC<0>{}, BoolC<false>{});
 }
-void launch_denoise_level(hipStream_t st, DenoiseLevel a, const F4* in, const F4* guides, F4* out, uint32_t* partial, bool staged) {
+// every form of both filters: FL from the two bits of flags (RTX_DENOISE_ALBEDO | RTX_DENOISE_MAPPED_NORMALS), VAR from variance
+void launch_denoise_level(hipStream_t st, DenoiseLevel a, bool variance, float sigma_var, uint32_t flags, const F4* in, const F4* half, const F4* guides, const F4* mguides, F4* out, uint32_t* partial, bool staged) {
     a.tiles_x = (a.width + kDnTileW - 1u) / kDnTileW;
     const dim3 grid(denoise_workgroups(a.width, a.height));
-    denoise_level_form(a, staged, [&](auto ss, auto first) { hipLaunchKernelGGL((k_denoise_level<decltype(ss)::value, decltype(first)::value>), grid, dim3(kBlock), 0, st, a, in, guides, out, partial); });
-}
-// flags: 1, 2 or 3 (RTX_DENOISE_ALBEDO | RTX_DENOISE_MAPPED_NORMALS)
-void launch_denoise_level_maps(hipStream_t st, DenoiseLevel a, uint32_t flags, const F4* in, const F4* guides, const F4* mguides, F4* out, uint32_t* partial, bool staged) {
-    a.tiles_x = (a.width + kDnTileW - 1u) / kDnTileW;
-    const dim3 grid(denoise_workgroups(a.width, a.height));
-    auto pick = [&](auto fl) {
-        denoise_level_form(a, staged, [&](auto ss, auto first) { hipLaunchKernelGGL((k_denoise_level_maps<decltype(ss)::value, decltype(first)::value, decltype(fl)::value>), grid, dim3(kBlock), 0, st, a, in, guides, mguides, out, partial); });
-    };
-    if (flags == 1u) pick(IntC<1>{}); else if (flags == 2u) pick(IntC<2>{}); else pick(IntC<3>{});
-}
-// rtx_denoise_variance: flags 0 .. 3; half is read by the first level, mguides with a flag set
-void launch_denoise_level_var(hipStream_t st, DenoiseLevel a, float sigma_var, uint32_t flags, const F4* in, const F4* half, const F4* guides, const F4* mguides, F4* out, uint32_t* partial, bool staged) {
-    a.tiles_x = (a.width + kDnTileW - 1u) / kDnTileW;
-    const dim3 grid(denoise_workgroups(a.width, a.height));
-    auto pick = [&](auto fl) {
-        denoise_level_form(a, staged, [&](auto ss, auto first) { hipLaunchKernelGGL((k_denoise_level_var<decltype(ss)::value, decltype(first)::value, decltype(fl)::value>), grid, dim3(kBlock), 0, st, a, sigma_var, in, half, guides, mguides, out, partial); });
-    };
-    if (flags == 0u) pick(IntC<0>{}); else if (flags == 1u) pick(IntC<1>{}); else if (flags == 2u) pick(IntC<2>{}); else pick(IntC<3>{});
+    dispatch_bool((flags & kDnAlbedo) != 0u, [&](auto alb) { dispatch_bool((flags & kDnMappedNormals) != 0u, [&](auto nm) { dispatch_bool(variance, [&](auto var) {
+        constexpr uint32_t FL = (decltype(alb)::value ? kDnAlbedo : 0u) | (decltype(nm)::value ? kDnMappedNormals : 0u);
+        denoise_level_form(a, staged, [&](auto ss, auto first) { hipLaunchKernelGGL((k_denoise_level<decltype(ss)::value, decltype(first)::value, FL, decltype(var)::value>), grid, dim3(kBlock), 0, st, a, sigma_var, in, half, guides, mguides, out, partial); });
+    }); }); });
 }
 void launch_denoise_var_input(hipStream_t st, uint32_t width, uint32_t height, bool albedo, const F4* in, const F4* half, const F4* guides, const F4* mguides, float* out2) {
     DenoiseLevel a{};

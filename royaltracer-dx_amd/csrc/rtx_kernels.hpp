@@ -253,14 +253,13 @@ void launch_adaptive_compact(hipStream_t, const DevFrame&, const AdaptState&, ui
 // one level of the a-trous filter: step = 1 << level; first: `in` is u1 (the mean is formed on the fly), else the previous level's output; last: w of the output is 1.0;
 // inv_sigma_color_s = (1 / sigma_color) * step
 struct DenoiseLevel { uint32_t width, height, tiles_x, step, normal_power_log2, first, last; float inv_sigma_plane, inv_sigma_color_s; };
-void launch_denoise_guides(hipStream_t, uint32_t max_blocks, const DevScene&, uint32_t width, uint32_t height, const CameraGPU* cam, F4* guides);   // two F4 per pixel
-void launch_denoise_map_guides(hipStream_t, uint32_t max_blocks, const DevScene&, uint32_t width, uint32_t height, const CameraGPU* cam, F4* guides, F4* mguides);   // ... and the map-guide record (A, 0) (nm, 0), two F4 per pixel
+void launch_denoise_guides(hipStream_t, uint32_t max_blocks, const DevScene&, uint32_t width, uint32_t height, const CameraGPU* cam, F4* guides, F4* mguides);   // two F4 per pixel; mguides != nullptr: and the map-guide record (A, 0) (nm, 0), two F4 per pixel
 uint32_t denoise_workgroups(uint32_t width, uint32_t height);                                         // tiles of a level launch = entries of `partial`
-// staged: the tile and its halo go through LDS (steps 1, 2 and 4 only); partial: per-workgroup counts of filterable pixels, written by the first level
-void launch_denoise_level(hipStream_t, DenoiseLevel, const F4* in, const F4* guides, F4* out, uint32_t* partial, bool staged);
-void launch_denoise_level_maps(hipStream_t, DenoiseLevel, uint32_t flags /* 1, 2 or 3 */, const F4* in, const F4* guides, const F4* mguides, F4* out, uint32_t* partial, bool staged);   // the forms with a flag of rtx_denoise_params set
-// rtx_denoise_variance: one level (DenoiseLevel::inv_sigma_color_s is not read; flags 0 .. 3; half: the adaptive sampler's second sum, read by the first level), and (v, gv) of level 0
-void launch_denoise_level_var(hipStream_t, DenoiseLevel, float sigma_var, uint32_t flags, const F4* in, const F4* half, const F4* guides, const F4* mguides, F4* out, uint32_t* partial, bool staged);
+// staged: the tile and its halo go through LDS (steps 1, 2 and 4 only); partial: per-workgroup counts of filterable pixels, written by the first level.  flags 0 .. 3: the
+// flags word of rtx_denoise_params (mguides is read with a flag set).  variance: a level of rtx_denoise_variance — sigma_var, and half (the adaptive sampler's second sum, read
+// by the first level) are read and DenoiseLevel::inv_sigma_color_s is not; else both may be 0 / null
+void launch_denoise_level(hipStream_t, DenoiseLevel, bool variance, float sigma_var, uint32_t flags, const F4* in, const F4* half, const F4* guides, const F4* mguides, F4* out, uint32_t* partial, bool staged);
+// rtx_debug_denoise_variance: (v, gv) of level 0
 void launch_denoise_var_input(hipStream_t, uint32_t width, uint32_t height, bool albedo, const F4* in, const F4* half, const F4* guides, const F4* mguides, float* out2);
 void launch_denoise_count(hipStream_t, const uint32_t* partial, uint32_t n, uint32_t* out);
 void launch_srgb8(hipStream_t, const F4* accum, uint32_t npix, uint32_t* out);

@@ -197,6 +197,30 @@ def test_threshold_zero_is_the_fixed_spp_route(rt, box):
     assert res.pixels_filtered == nf
 
 
+@pytest.mark.parametrize("lds", [4, 0])
+def test_the_two_filters_alternate_on_one_context(rt, box, lds):
+    """Both filters go through one level launcher and share the context's guide, ping-pong and count buffers: rtx_denoise, rtx_denoise_variance, rtx_denoise again, flags 3,
+    3 levels at 37 x 19 (partial tiles, clamped halos) — each image and count is its twin's, and the variance call leaves nothing behind that the third call picks up"""
+    w, h = SIZES[1]
+    a, hb = sample_box(rt, box, w, h)
+    g, mg = box.denoise_guides(w, h), box.denoise_map_guides(w, h)
+    want = {False: mr.emulate_maps(a, g, mg, 3, 3, sigma_color=ref.SIGMA_COLOR, **KW), True: vr.emulate_var(a, hb, g, mg, 3, 3, **KW)}
+    got = []
+    try:
+        box.set_option(rt.OPT_DENOISE_LDS_STEP, lds)
+        for variance in (False, True, False):
+            kw = dict(variance=True) if variance else dict(sigma_color=ref.SIGMA_COLOR)
+            res = box.denoise(w, h, 3, albedo=True, mapped_normals=True, **kw, **KW)
+            got.append(box.read_denoised())
+            e, nf = want[variance]
+            same_image(got[-1], e, f"call {len(got)} (variance {variance}), LDS up to step {lds}")
+            assert (res.levels, res.pixels_filtered, res.pixels_passed) == (3, nf, w * h - nf), f"call {len(got)}"
+    finally:
+        box.set_option(rt.OPT_DENOISE_LDS_STEP, 4)
+    same_image(got[2], got[0], "rtx_denoise after rtx_denoise_variance against rtx_denoise before it")
+    assert not np.array_equal(bits(got[1]), bits(got[0])), "the two filters differ on this frame"
+
+
 # ---- 5: errors ----
 def test_errors(rt, box):
     w, h = ar.W, ar.H

@@ -4,8 +4,8 @@
 The scene and method of tools/denoise_maps_time.py: the Cornell box at 1920 x 1080 with a 256 x 256 texture bound as map_Kd and as normal map on its four non-emitting
 materials, sampled with 16 spp by rtx_render_adaptive at threshold 0 (rtx_render's image, plus the second sum the variance-guided filter reads).  Per flags word 0 .. 3 and
 per entry point: levels = 1 .. 5; rtx_denoise_result gives the guides and the filter as two hipEvent intervals, and the time of level i is filter_ms(levels = i + 1) -
-filter_ms(levels = i).  Each measurement is a process of its own (--child); with --parent DIR (a built checkout of the parent commit) the parent's rtx_denoise is measured
-too, the two trees ALTERNATING round by round.
+filter_ms(levels = i).  Each measurement is a process of its own (--child); with --parent DIR (a built checkout of the parent commit) the parent's two entry points are
+measured too, the two trees ALTERNATING round by round.
     python tools/denoise_var_time.py [--parent DIR] [--rounds 5] [--out profiles/denoise_var_time.md]"""
 import argparse, json, os, statistics, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -91,12 +91,15 @@ def main():
            f"process of its own, the trees alternating round by round; inside a process the median of {REPS} calls; below: the median over the rounds (min .. max over the rounds =",
            "the run-to-run spread), in ms.  Level i has step 1 << i.", ""]
     if old:
-        out += ["## rtx_denoise against the parent commit (expected difference: none — the same kernels are launched)", "",
-                "| | " + " | ".join(f"flags {f}: parent | flags {f}: this tree" for f in range(4)) + " |", "|---|" + "---|" * 8]
-        cols = [rows_of(runs, f"d{f}") for f in range(4) for runs in (old, new)]
-        for i, label in enumerate(LABELS):
-            out.append(f"| {label} | " + " | ".join(spread(c[i]) for c in cols) + " |")
-        out.append("")
+        for e, entry in (("d", "rtx_denoise"), ("v", "rtx_denoise_variance")):
+            if not all(f"{e}0" in r for r in old):
+                continue                                                # (a parent from before the variance-guided filter)
+            out += [f"## {entry} against the parent commit", "",
+                    "| | " + " | ".join(f"flags {f}: parent | flags {f}: this tree" for f in range(4)) + " |", "|---|" + "---|" * 8]
+            cols = [rows_of(runs, f"{e}{f}") for f in range(4) for runs in (old, new)]
+            for i, label in enumerate(LABELS):
+                out.append(f"| {label} | " + " | ".join(spread(c[i]) for c in cols) + " |")
+            out.append("")
     out += ["## rtx_denoise (d) and rtx_denoise_variance (v) on this tree", "", "| | " + " | ".join(f"d, flags {f} | v, flags {f}" for f in range(4)) + " |", "|---|" + "---|" * 8]
     cols = [rows_of(new, f"{e}{f}") for f in range(4) for e in "dv"]
     for i, label in enumerate(LABELS):
